@@ -7,13 +7,17 @@ One "step" = one pass of the hot path over one batch of B synthetic stereo frame
 ORBextractor x2, ComputeStereoMatches, ComputeBoW, SearchByBoW against the previous frame.  N > 1: one process per GPU
 (torch.distributed, RCCL), frames dealt round-robin; the previous frame lives on the previous rank, so every step ships the
 left-image features one rank up the ring (point-to-point over xGMI, morb_slam_amd/parallel.py) -> weak scaling.  The timed
-region is bracketed by barrier + synchronize and the MAX over ranks is reported.  Rank 0 prints ONE JSON line: the contract's keys, `roofline` (HBM, the
-longest extraction stage alone on the chip) with `roofline_issue` (what really bounds that kernel: vector-instruction issue), `cpu_baseline` (the oracle on the
-host's cores, bounded sample), `latency` (round 6: ONE frame / keyframe per call, host to host — the reference's call pattern — each with the oracle on one thread
-beside it), `h2d_inclusive`, `sustained`, `extra_metrics` (optimisers with the PoseOptimization path that ran, tracking chain, the other BASELINE configs).
+region is bracketed by barrier + synchronize and the MAX over ranks is reported.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the
+K steps and prints the contract's keys (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) with `config` (and `multi_gpu` for N > 1).
+With --full the line also carries `roofline` (HBM, the longest extraction stage alone on the chip) with `roofline_issue` (what really bounds that kernel:
+vector-instruction issue), the per-stage times, `verified` (the oracle self-check of the last timed step), `cpu_baseline` (the oracle on the host's cores,
+bounded sample), `latency` (ONE frame / keyframe per call, host to host — the reference's call pattern — each with the oracle on one thread beside it),
+`h2d_inclusive`, `sustained`, `two_extraction_streams`, `extra_metrics` (optimisers with the PoseOptimization path that ran, tracking chain, the other
+BASELINE configs); the --no-* options trim that.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed
+sample of frames; inputs are seeded, so two builds can be compared array by array).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4] [--batch B] [--matchers beside-pyramid|under-quadtree|under-fast]
-                    [--exchange ring|allgather] [--no-cpu-baseline] [--no-extras]
+                    [--exchange ring|allgather] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extras] [--no-verify] [--sustained-s S]]
     (--workload vga: 640x480 / 600 features, for tests that drive the launcher with many ranks on one GPU; not a BASELINE configuration)
 """
 import argparse
@@ -74,6 +78,48 @@ def make_batch(global_ids, total, seed=0):
         imgs[k, 0] = shift_image(l, dx, dy)
         imgs[k, 1] = shift_image(r, dx, dy)
     return imgs
+
+
+DUMP_BUDGET = 64 << 20    # bytes of .npy payload --dump-outputs may write in all
+
+
+def dump_outputs(fe, S, out_dir, max_frames=32, seed=0):
+    """--dump-outputs: what buffer set S (the last timed step; all streams synchronised) hands its caller, as float32 / float64 .npy files.
+    Per-image / per-pair counts cover the whole batch; the per-feature tables cover a fixed, seeded sample of frames (at most `max_frames`,
+    fewer if the tables would pass DUMP_BUDGET).  Table entries beyond a row's count are not outputs of the step and are written as 0."""
+    import torch
+    from morb_slam_amd.capi import KP_DTYPE
+    B, cap = fe.B, fe.cap
+    kps, desc, cnt, mono = S.out
+    per_frame = cap * (2 * 7 * 8 + 2 * 32 * 4 + 2 * 4 + 3 * 8)     # keypoints f64 + descriptors f32 (both images), uR / depth f32, word / node / match f64
+    n = max(1, min(B, max_frames, (DUMP_BUDGET - 16 * B * 8) // per_frame))
+    frames = np.sort(np.random.default_rng(seed).choice(B, size=n, replace=False))
+    fidx = torch.from_numpy(frames).to(kps.device)
+    iidx = torch.stack([2 * fidx, 2 * fidx + 1], 1).reshape(-1)                 # left, right image of each sampled frame
+    cnt_all = cnt.cpu().numpy()
+    ci = cnt_all[np.stack([2 * frames, 2 * frames + 1], 1)]                     # [n, 2]
+    valid = np.arange(cap)[None, None, :] < ci[:, :, None]                      # [n, 2, cap]
+    raw = kps.index_select(0, iidx).cpu().numpy().reshape(n, 2, cap, 28)
+    raw[~valid] = 0                                                             # (unwritten slots: whatever bytes the buffer held)
+    rec = raw.reshape(n, 2, cap * 28).view(KP_DTYPE)
+    kp = np.stack([rec[f].astype(np.float64) for f in KP_DTYPE.names], -1)      # [n, 2, cap, 7]: x y size angle response octave class_id
+    ds = desc.index_select(0, iidx).cpu().numpy().reshape(n, 2, cap, 32).astype(np.float32)
+    lv = valid[:, 0]                                                            # the left image's features: stereo, BoW, SearchByBoW rows
+    uR, dep = (t.index_select(0, fidx).cpu().numpy() for t in S.st_out)
+    word, node = (t.index_select(0, 2 * fidx).cpu().numpy().astype(np.float64) for t in S.bow_out)
+    mt, nm = S.match_out      # SearchByBoW: pair p = local frame p (its left image against the predecessor's); row entries = its left features
+    out = {"frames": frames.astype(np.float64),
+           "keypoint_count": cnt_all.astype(np.float64), "mono_count": mono.cpu().numpy().astype(np.float64),
+           "keypoints": kp, "descriptors": np.where(valid[..., None], ds, np.float32(0)),
+           "stereo_uright": np.where(lv, uR, np.float32(0)), "stereo_depth": np.where(lv, dep, np.float32(0)),
+           "bow_word": np.where(lv, word, 0.0), "bow_node": np.where(lv, node, 0.0),
+           "search_by_bow_match": np.where(lv, mt.index_select(0, fidx).cpu().numpy().astype(np.float64), 0.0),
+           "search_by_bow_count": nm.cpu().numpy().astype(np.float64)}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BUDGET
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(out)
 
 
 def cpu_baseline(target_s=12.0):
@@ -619,15 +665,22 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="join all streams at the end of every step instead of running step i's matchers underneath step "
                          "i + 1's extraction (one buffer set instead of two)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-region oracle self-check of the last timed step")
-    ap.add_argument("--verify-frames", type=int, default=8, help="stereo frames of the last timed step compared with the oracle")
-    ap.add_argument("--sustained-s", type=float, default=2.0, help="seconds of the sustained run (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="headline workload only (used for the committed profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-stage / roofline figures, the oracle self-check of the last timed step, the "
+                         "sustained run, the other schedules, H2D-inclusive and one-frame latency, the extra metrics and the CPU baseline (the options "
+                         "below trim it); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, a fixed sample of frames)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="(--full) skip the post-region oracle self-check of the last timed step")
+    ap.add_argument("--verify-frames", type=int, default=8, help="(--full) stereo frames of the last timed step compared with the oracle")
+    ap.add_argument("--sustained-s", type=float, default=2.0, help="(--full) seconds of the sustained run (0 = skip)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) headline workload only (used for the committed profiles)")
     ap.add_argument("--launch-probe", action="store_true",
                     help="ranks only rendezvous (gloo, CPU), count each other and exit: checks the --gpus N launcher without a GPU")
     args = ap.parse_args()
     W, H, NFEAT, defB = WORKLOADS[args.workload]
+    full = args.full          # False: the headline figure only (set up, warm up, time the steps, print the line)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: THIS process becomes the launcher.  It has not touched the GPU
@@ -701,8 +754,9 @@ def main():
         fe.exch.prime(dev)      # communicator + one dummy exchange BEFORE any step: RCCL builds it lazily, and --warmup 0 is a legal request
     for _ in range(args.warmup):
         step()
-    for e in exts:
-        e.set_profiling(True)   # stage-boundary HIP events on the launch stream; no host sync inside the timed region
+    if full:
+        for e in exts:
+            e.set_profiling(True)   # stage-boundary HIP events on the launch stream; no host sync inside the timed region
     sync_all()
     if fe.exch is not None:
         fe.drain_exchange_ms(); fe.exchange_ms = []       # from here on: HIP events around every step's pack -> transfer -> unpack
@@ -728,13 +782,16 @@ def main():
                                           "what": "HIP events on the exchange stream around slab pack -> transfer -> unpack (runs beside the next step's extraction)"},
                  "exchange": args.exchange, "backend": dist.get_backend()}
         dist.barrier()
-    # per-stage ms per extract call (= per step), averaged over the handles of the buffer sets
-    per_set = [e.stage_ms() for e in exts]
-    stages = {k: sum(ps[k] for ps in per_set) / len(per_set) for k in per_set[0]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fe, fe.last, args.dump_outputs)      # before anything below reuses the buffer sets
+    if full:
+        # per-stage ms per extract call (= per step), averaged over the handles of the buffer sets
+        per_set = [e.stage_ms() for e in exts]
+        stages = {k: sum(ps[k] for ps in per_set) / len(per_set) for k in per_set[0]}
     # ---- post-region self-check (outside the timed region, like cpu_baseline): sampled frames of the LAST timed step against the CPU
     # oracle, every field of the chain (tests/chain_check.py) — the configuration in the headline is one the oracle has seen
     verified = None
-    if world == 1 and rank == 0 and not args.no_verify:
+    if full and world == 1 and rank == 0 and not args.no_verify:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import chain_check
         sample = sorted(set(int(x) for x in np.linspace(0, B - 1, min(B, args.verify_frames))))
@@ -745,7 +802,7 @@ def main():
     # ---- sustained figure (never `value`): the same step for >= 2 s and >= 1000 steps in windows of <= 100 steps; the headline's K steps fit inside one
     # boost-clock burst, this does not
     sustained = None
-    if world == 1 and rank == 0 and args.sustained_s > 0:
+    if full and world == 1 and rank == 0 and args.sustained_s > 0:
         # windows of ~0.2 s (at least 10 steps, at most 100), at least 10 of them, at least --sustained-s seconds and at least 1000 steps in all
         win = int(min(100, max(10, round(0.2 / max(dt / args.steps, 1e-6)))))
         wfps, wst, tot = [], [], 0.0
@@ -768,19 +825,20 @@ def main():
                                                        "max": max(w[k] for w in wst)} for k in wst[0]}}
     # reference point outside the timed region: the same extraction with nothing else on the chip (the pipelined steps
     # above share the CUs between two extractions and the matchers, which stretches every kernel's launch duration)
-    iso_n = 5
-    for _ in range(iso_n):
-        exts[0].extract_batch(images, out=sets[0].out, stream=estreams[0].cuda_stream)
-        estreams[0].synchronize()
-    iso = exts[0].stage_ms()
-    for e in exts:
-        e.set_profiling(False)
+    if full:
+        iso_n = 5
+        for _ in range(iso_n):
+            exts[0].extract_batch(images, out=sets[0].out, stream=estreams[0].cuda_stream)
+            estreams[0].synchronize()
+        iso = exts[0].stage_ms()
+        for e in exts:
+            e.set_profiling(False)
     cnt = sets[0].out[2].cpu().numpy()
     n_stereo = float((sets[0].st_out[0] >= 0).sum().item()) / B
     n_bow = float(sets[0].match_out[1].float().mean().item())
 
     h2d = lat = alt = None
-    if world == 1 and not args.no_extras and NSET >= 2 and len(set(id(x) for x in estreams)) == 1:
+    if full and world == 1 and not args.no_extras and NSET >= 2 and len(set(id(x) for x in estreams)) == 1:
         # ---- the other schedule, for the record (never `value`): one extraction stream per buffer set, so two extractions overlap each
         # other too.  A few per cent more frames/s, but every extraction kernel then shares the chip with another one and its launch
         # time in the region says little about the kernel.
@@ -810,7 +868,7 @@ def main():
             alt["staggered"] = {"value": B / dts, "ms_per_step": dts * 1e3, "steps": ksa}
             fe.stagger = False
         estreams[:] = saved
-    if world == 1 and not args.no_extras:
+    if full and world == 1 and not args.no_extras:
         # ---- the same steps with the images arriving over PCIe: pinned host frames, uploaded on a copy stream into one of two
         # device buffers while the previous step computes (never `value`: the contract's number is HBM-resident)
         pinned = host_frames.view(2 * B, H, W).pin_memory()
@@ -916,53 +974,6 @@ def main():
 
     if rank == 0:
         fps = B * world * args.steps / dt
-        ab = algorithmic_bytes(W, H)
-        nimg = 2 * B
-        kern = {"pyramid": "k_level0+k_resize", "blur": "k_blur", "fast": "k_fastw"}
-        # HBM bytes per launch from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate runs of the extraction
-        # at 128 images per launch; profiles/<round>/pmc_traffic_b64.json) — not measurable live.  Corrected as the calibration kernel
-        # prescribes (profiles/r03/fetch_calib.txt: FETCH_SIZE reads 0.500 x the bytes of coalesced 4 / 8 / 16-byte reads, WRITE_SIZE 1.0 x):
-        # traffic = 2 x FETCH_SIZE + WRITE_SIZE
-        pm = pmi = None
-        pm_src = None
-        for rnd, fn in (("r06", "pmc_traffic_b512.json"), ("r05", "pmc_traffic_b512.json"), ("r04", "pmc_traffic_b64.json"), ("r03", "pmc_traffic_b64.json")):   # newest first; since r05: taken AT the bench batch
-            try:
-                pm = json.load(open(os.path.join(ROOT, "profiles", rnd, fn)))
-                pm_src = f"profiles/{rnd}/{fn}"
-                break
-            except Exception:
-                pm = None
-        pmi_src = None
-        for rnd in ("r06", "r05"):
-            try:
-                pmi = json.load(open(os.path.join(ROOT, "profiles", rnd, "pmc_issue_b512.json")))
-                pmi_src = f"profiles/{rnd}/pmc_issue_b512.json"
-                break
-            except Exception:
-                pmi = None
-
-        def traffic_of(stage):
-            if pm is None or args.workload != "c2":
-                return None
-            try:
-                # launches per extraction: level 0, seven resizes; two k_fastw launch groups (the per-launch mean is over both)
-                names = {"pyramid": [("k_level0", 1), ("k_resize", 7)], "blur": [("k_blur", 1)], "fast": [("k_fastw", 2)]}[stage]
-                return sum(pm[k]["traffic_KB_per_launch"] * 1024 * m for k, m in names) * nimg / pm.get("images_per_launch", 128)
-            except Exception:
-                return None
-
-        def roof(stage):
-            ach = ab[stage] * nimg / (stages[stage] * 1e-3) / 1e9    # algorithmic bytes of the stage's launches / their in-region time
-            return {"bound": "hbm", "kernel": kern[stage], "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                    "traffic": traffic_of(stage), "algorithmic_bytes_per_launch": ab[stage] * nimg, "avg_launch_ms": stages[stage],
-                    # not part of the timed region: the stage alone on the chip (steps not overlapped)
-                    "isolated_avg_launch_ms": iso[stage], "isolated_frac": ab[stage] * nimg / (iso[stage] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        # the dominant streaming stage of the extractor = the longest of the three when each runs ALONE on the chip (the same launches,
-        # not overlapped with another step: `iso`).  Inside the timed region the pyramid runs beside the previous step's matchers and is
-        # stretched by them (1.17 ms against 0.76 alone at B = 512), so since round 4's k_fastw (1.08 ms) the in-region maximum would name
-        # a stage for what the matchers cost it.  `achieved` is still the stage's in-region time (HIP events on the launch stream; "pyramid"
-        # is the dependent launches of k_level0 / k_resize, "fast" the two k_fastw launch groups); all three stages are in `stage_roofline`.
-        dom = max(("pyramid", "blur", "fast"), key=lambda k: iso[k])
         wl = {"c2": f"BASELINE configs[1]: EuRoC-shaped stereo {W}x{H}, {NFEAT} feat", "c4": f"BASELINE configs[3]: synthetic stereo {W}x{H}, {NFEAT} feat",
               "vga": f"FUNCTIONAL TEST SHAPE (not a BASELINE configuration): synthetic stereo {W}x{H}, {NFEAT} feat"}[args.workload]
         cfg_tag = {"c2": "= BASELINE configs[1]", "c4": "= BASELINE configs[3]", "vga": "functional test shape, NOT a BASELINE configuration"}[args.workload]
@@ -979,33 +990,81 @@ def main():
                        "stages_in_step": ["extract_left+right", "stereo_match", "bow_transform"] + (["feature_exchange"] if world > 1 else []) + ["search_by_bow"],
                        "mean_keypoints_per_image": float(cnt.mean()), "mean_stereo_matches_per_frame": n_stereo,
                        "mean_bow_matches_per_frame": n_bow},
-            "roofline": roof(dom),
-            "stage_roofline": {k: {kk: vv for kk, vv in roof(k).items() if kk in ("kernel", "achieved", "frac", "avg_launch_ms", "isolated_avg_launch_ms", "isolated_frac", "traffic")}
-                               for k in ("pyramid", "blur", "fast")},
-            "extract_stage_ms_per_step": stages,
         }
-        if pm_src is not None:
-            line["roofline"]["traffic_source"] = pm_src + (" (counters at this batch)" if pm.get("images_per_launch") == nimg else
-                                                           f" (counters at {pm.get('images_per_launch')} images per launch, scaled)")
-        line["roofline"]["peak_measured_copy"] = 6290.0      # GB/s, the guide's measured HBM copy rate beside the 8 TB/s specification
-        line["roofline"]["frac_of_measured_copy"] = line["roofline"]["achieved"] / 6290.0
-        if pmi is not None and args.workload == "c2" and "k_fastw" in pmi and pmi.get("images_per_launch") == nimg:
-            # k_fastw is bound by vector-instruction ISSUE, not by HBM (traffic = 1.07 x algorithmic, every instruction removed is
-            # time): its real roof.  Instruction counts from the committed counter pass at this batch (not measurable live), duration measured live.
-            kf = pmi["k_fastw"]
-            per_step = kf["valu_insts_per_launch"] * 2             # two launch groups per extraction
-            simd_cycles = pmi["simds"] * stages["fast"] * 1e-3 * pmi["clock_GHz"] * 1e9
-            # measured quantities only (round 5 reported min(1, instructions x a separately measured 4.1 cycles / cycles), a model that overshot its own
-            # ceiling): SIMD cycles available per VALU wave-instruction of the stage, live, and the utilisation that follows from the FASTEST issue
-            # rate this chip has for a wave64 VALU instruction (4 cycles on a 16-lane SIMD) — a lower bound on how busy the issue port is, since the
-            # packed / three-operand / DPP forms the kernel is made of take longer.  `roofline.frac` stays the HBM figure.
-            line["roofline_issue"] = {"bound": "valu_issue", "kernel": "k_fastw", "valu_wave_instructions_per_step": per_step,
-                                      "simd_cycles_per_valu_instruction": simd_cycles / per_step,
-                                      "issue_utilisation": 4.0 / (simd_cycles / per_step), "issue_utilisation_basis": "4.0 SIMD cycles per wave64 VALU instruction (the minimum) at an ASSUMED 2.4 GHz; uncapped — a value a few per cent above 1 "
-                                                                 "is the error of that clock assumption / of the counter pass taken at another time, not a faster chip",
-                                      "valu_lane_slots_per_pixel": per_step * 64 / (ab["fast"] * nimg),
-                                      "valu_per_cell_wave": kf["valu_per_wave"], "salu_per_cell_wave": kf["salu_per_wave"], "lds_per_cell_wave": kf["lds_per_wave"],
-                                      "source": f"{pmi_src} (SQ_INSTS_VALU per launch) / live k_fastw time x 1024 SIMDs x 2.4 GHz"}
+        if full:
+            ab = algorithmic_bytes(W, H)
+            nimg = 2 * B
+            kern = {"pyramid": "k_level0+k_resize", "blur": "k_blur", "fast": "k_fastw"}
+            # HBM bytes per launch from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate runs of the extraction
+            # at 128 images per launch; profiles/<round>/pmc_traffic_b64.json) — not measurable live.  Corrected as the calibration kernel
+            # prescribes (profiles/r03/fetch_calib.txt: FETCH_SIZE reads 0.500 x the bytes of coalesced 4 / 8 / 16-byte reads, WRITE_SIZE 1.0 x):
+            # traffic = 2 x FETCH_SIZE + WRITE_SIZE
+            pm = pmi = None
+            pm_src = None
+            for rnd, fn in (("r06", "pmc_traffic_b512.json"), ("r05", "pmc_traffic_b512.json"), ("r04", "pmc_traffic_b64.json"), ("r03", "pmc_traffic_b64.json")):   # newest first; since r05: taken AT the bench batch
+                try:
+                    pm = json.load(open(os.path.join(ROOT, "profiles", rnd, fn)))
+                    pm_src = f"profiles/{rnd}/{fn}"
+                    break
+                except Exception:
+                    pm = None
+            pmi_src = None
+            for rnd in ("r06", "r05"):
+                try:
+                    pmi = json.load(open(os.path.join(ROOT, "profiles", rnd, "pmc_issue_b512.json")))
+                    pmi_src = f"profiles/{rnd}/pmc_issue_b512.json"
+                    break
+                except Exception:
+                    pmi = None
+
+            def traffic_of(stage):
+                if pm is None or args.workload != "c2":
+                    return None
+                try:
+                    # launches per extraction: level 0, seven resizes; two k_fastw launch groups (the per-launch mean is over both)
+                    names = {"pyramid": [("k_level0", 1), ("k_resize", 7)], "blur": [("k_blur", 1)], "fast": [("k_fastw", 2)]}[stage]
+                    return sum(pm[k]["traffic_KB_per_launch"] * 1024 * m for k, m in names) * nimg / pm.get("images_per_launch", 128)
+                except Exception:
+                    return None
+
+            def roof(stage):
+                ach = ab[stage] * nimg / (stages[stage] * 1e-3) / 1e9    # algorithmic bytes of the stage's launches / their in-region time
+                return {"bound": "hbm", "kernel": kern[stage], "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                        "traffic": traffic_of(stage), "algorithmic_bytes_per_launch": ab[stage] * nimg, "avg_launch_ms": stages[stage],
+                        # not part of the timed region: the stage alone on the chip (steps not overlapped)
+                        "isolated_avg_launch_ms": iso[stage], "isolated_frac": ab[stage] * nimg / (iso[stage] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            # the dominant streaming stage of the extractor = the longest of the three when each runs ALONE on the chip (the same launches,
+            # not overlapped with another step: `iso`).  Inside the timed region the pyramid runs beside the previous step's matchers and is
+            # stretched by them (1.17 ms against 0.76 alone at B = 512), so since round 4's k_fastw (1.08 ms) the in-region maximum would name
+            # a stage for what the matchers cost it.  `achieved` is still the stage's in-region time (HIP events on the launch stream; "pyramid"
+            # is the dependent launches of k_level0 / k_resize, "fast" the two k_fastw launch groups); all three stages are in `stage_roofline`.
+            dom = max(("pyramid", "blur", "fast"), key=lambda k: iso[k])
+            line["roofline"] = roof(dom)
+            line["stage_roofline"] = {k: {kk: vv for kk, vv in roof(k).items() if kk in ("kernel", "achieved", "frac", "avg_launch_ms", "isolated_avg_launch_ms", "isolated_frac", "traffic")}
+                                      for k in ("pyramid", "blur", "fast")}
+            line["extract_stage_ms_per_step"] = stages
+            if pm_src is not None:
+                line["roofline"]["traffic_source"] = pm_src + (" (counters at this batch)" if pm.get("images_per_launch") == nimg else
+                                                               f" (counters at {pm.get('images_per_launch')} images per launch, scaled)")
+            line["roofline"]["peak_measured_copy"] = 6290.0      # GB/s, the guide's measured HBM copy rate beside the 8 TB/s specification
+            line["roofline"]["frac_of_measured_copy"] = line["roofline"]["achieved"] / 6290.0
+            if pmi is not None and args.workload == "c2" and "k_fastw" in pmi and pmi.get("images_per_launch") == nimg:
+                # k_fastw is bound by vector-instruction ISSUE, not by HBM (traffic = 1.07 x algorithmic, every instruction removed is
+                # time): its real roof.  Instruction counts from the committed counter pass at this batch (not measurable live), duration measured live.
+                kf = pmi["k_fastw"]
+                per_step = kf["valu_insts_per_launch"] * 2             # two launch groups per extraction
+                simd_cycles = pmi["simds"] * stages["fast"] * 1e-3 * pmi["clock_GHz"] * 1e9
+                # measured quantities only (round 5 reported min(1, instructions x a separately measured 4.1 cycles / cycles), a model that overshot its own
+                # ceiling): SIMD cycles available per VALU wave-instruction of the stage, live, and the utilisation that follows from the FASTEST issue
+                # rate this chip has for a wave64 VALU instruction (4 cycles on a 16-lane SIMD) — a lower bound on how busy the issue port is, since the
+                # packed / three-operand / DPP forms the kernel is made of take longer.  `roofline.frac` stays the HBM figure.
+                line["roofline_issue"] = {"bound": "valu_issue", "kernel": "k_fastw", "valu_wave_instructions_per_step": per_step,
+                                          "simd_cycles_per_valu_instruction": simd_cycles / per_step,
+                                          "issue_utilisation": 4.0 / (simd_cycles / per_step), "issue_utilisation_basis": "4.0 SIMD cycles per wave64 VALU instruction (the minimum) at an ASSUMED 2.4 GHz; uncapped — a value a few per cent above 1 "
+                                                                     "is the error of that clock assumption / of the counter pass taken at another time, not a faster chip",
+                                          "valu_lane_slots_per_pixel": per_step * 64 / (ab["fast"] * nimg),
+                                          "valu_per_cell_wave": kf["valu_per_wave"], "salu_per_cell_wave": kf["salu_per_wave"], "lds_per_cell_wave": kf["lds_per_wave"],
+                                          "source": f"{pmi_src} (SQ_INSTS_VALU per launch) / live k_fastw time x 1024 SIMDs x 2.4 GHz"}
         if multi is not None:
             line["multi_gpu"] = multi
         if verified is not None:
@@ -1018,12 +1077,12 @@ def main():
             line["h2d_inclusive"] = h2d
         if lat is not None:
             line["latency_b1"] = lat
-        if world == 1 and not args.no_extras:
+        if full and world == 1 and not args.no_extras:
             line["extra_metrics"] = optimizer_extras(local_rank)
             line["extra_metrics"].update(tracking_extras(local_rank))
             if args.workload == "c2":
                 line["extra_metrics"].update(config_extras(local_rank))
-        if world == 1 and not args.no_cpu_baseline:      # reported on rank 0 at N = 1 only
+        if full and world == 1 and not args.no_cpu_baseline:      # reported on rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline()
         if world == 1 and lat is not None:
             # What a drop-in sees: the reference calls this path ONE frame at a time (src/Frame.cc:190-226 extraction + ComputeStereoMatches per frame,

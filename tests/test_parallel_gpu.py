@@ -81,7 +81,7 @@ def _bench_line(tmp_path, args, gloo=True, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     if gloo:
         env["MORB_DIST_BACKEND"] = "gloo"
-    r = spawn([sys.executable, os.path.join(root, "bench.py")] + args + ["--no-extras", "--no-cpu-baseline"], env, tmp_path / ("bench_" + "_".join(a.strip("-") for a in args[:6])),
+    r = spawn([sys.executable, os.path.join(root, "bench.py")] + args + ["--full", "--no-extras", "--no-cpu-baseline"], env, tmp_path / ("bench_" + "_".join(a.strip("-") for a in args[:6])),
               timeout=timeout)
     assert r.returncode == 0, describe([r])
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 for rep in 1 2; do
 for c in 0 64 128 256 512; do
   export MORB_PYR_CHUNK=$c
-  python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras --no-verify --sustained-s 0 2>/dev/null | python3 -c "
+  python3 bench.py --steps 40 --warmup 5 --full --no-cpu-baseline --no-extras --no-verify --sustained-s 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ for b in 8 16 32 64 128; do
   if [ $wl = c4 ] && [ $b -gt 32 ]; then continue; fi
   for n in product team64 team256; do
     if [ "$n" = product ]; then unset MORB_HIP_LIB; else export MORB_HIP_LIB=$PWD/morb_slam_amd/libmorb_hip_$n.so; fi
-    python3 bench.py --workload $wl --batch $b --steps 40 --warmup 5 --no-cpu-baseline --no-extras --no-verify --sustained-s 0 2>/dev/null | python3 -c "
+    python3 bench.py --workload $wl --batch $b --steps 40 --warmup 5 --full --no-cpu-baseline --no-extras --no-verify --sustained-s 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

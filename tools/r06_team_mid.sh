@@ -1,7 +1,7 @@
 cd "$GRAFT_REPO_ROOT"
 for b in 64 128 256 512; do
   for mid in 0 2048; do
-    MORB_TEAM_MID=$mid python3 bench.py --batch $b --steps 40 --warmup 5 --no-cpu-baseline --no-extras --no-verify --sustained-s 0 2>/dev/null | python3 -c "
+    MORB_TEAM_MID=$mid python3 bench.py --batch $b --steps 40 --warmup 5 --full --no-cpu-baseline --no-extras --no-verify --sustained-s 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

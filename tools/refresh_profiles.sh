@@ -12,11 +12,11 @@ T="timeout 420"
 mkdir -p "$O"
 if [ -z "${MORB_REFRESH_TAIL:-}" ]; then
 rm -rf "$O" && mkdir -p "$O"
-$T rocprofv3 --kernel-trace --stats -d "$O/stats" -o s --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-verify --sustained-s 0 > "$O/bench_under_rocprof.json" 2>/dev/null
+$T rocprofv3 --kernel-trace --stats -d "$O/stats" -o s --output-format csv -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras --no-verify --sustained-s 0 > "$O/bench_under_rocprof.json" 2>/dev/null
 for p in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM SQ_LDS_IDX_ACTIVE"; do
   n=$(echo "$p" | cut -c1-12 | tr " " _)
   # counter passes at B = 64 (128 images per launch), un-pipelined: kernels are serialised under --pmc anyway
-  timeout 300 rocprofv3 --pmc $p --kernel-trace -d "$O/pmc/$n" -o q --output-format csv -- python3 bench.py --batch 64 --no-pipeline --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-verify --sustained-s 0 > /dev/null 2>&1
+  timeout 300 rocprofv3 --pmc $p --kernel-trace -d "$O/pmc/$n" -o q --output-format csv -- python3 bench.py --batch 64 --no-pipeline --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --no-verify --sustained-s 0 > /dev/null 2>&1
 done
 $T python3 tools/pmc_table.py "$O/pmc" > "$O/pmc_issue_table.txt"
 $T python3 tools/pmc_traffic.py "$O/pmc" 128 > "$O/pmc_traffic_b64.json"
@@ -24,7 +24,7 @@ $T python3 tools/pmc_traffic.py "$O/pmc" 128 > "$O/pmc_traffic_b64.json"
 # (`roofline.traffic`, `roofline_issue`): traffic and instruction counts per launch, no scaling from a smaller batch
 for p in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY"; do
   n=$(echo "$p" | cut -c1-12 | tr " " _)
-  timeout 600 rocprofv3 --pmc $p --kernel-trace -d "$O/pmc512/$n" -o q --output-format csv -- python3 bench.py --batch 512 --no-pipeline --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-verify --sustained-s 0 > /dev/null 2>&1
+  timeout 600 rocprofv3 --pmc $p --kernel-trace -d "$O/pmc512/$n" -o q --output-format csv -- python3 bench.py --batch 512 --no-pipeline --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras --no-verify --sustained-s 0 > /dev/null 2>&1
 done
 $T python3 tools/pmc_traffic.py "$O/pmc512" 1024 > "$O/pmc_traffic_b512.json"
 $T python3 tools/pmc_issue.py "$O/pmc512" 1024 > "$O/pmc_issue_b512.json"
@@ -64,10 +64,10 @@ fi   # (MORB_REFRESH_TAIL)
   unset MORB_EXTRA_DEFS MORB_TIMING_TAG; } > "$O/k_distribute_phases.txt" 2>/dev/null
 { $T python3 tools/latency_b1.py; MORB_W=1920 MORB_H=1080 MORB_NF=4000 $T python3 tools/latency_b1.py; } 2>/dev/null | grep -v amdgpu.ids > "$O/latency_b1.txt"
 # the other headline shapes: BASELINE configs[3] on one GPU, and the --gpus 2 launcher path (two ranks sharing this GPU, gloo)
-$T python3 bench.py --workload c4 --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_c4.json" 2>/dev/null
-$T python3 bench.py --workload c4 --batch 1 --no-cpu-baseline > "$O/bench_c4_batch1.json" 2>/dev/null     # one 1920 x 1080 stereo frame per step: what each rank of the 8-GPU run executes
+$T python3 bench.py --workload c4 --full --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_c4.json" 2>/dev/null
+$T python3 bench.py --workload c4 --batch 1 --full --no-cpu-baseline > "$O/bench_c4_batch1.json" 2>/dev/null     # one 1920 x 1080 stereo frame per step: what each rank of the 8-GPU run executes
 # the three placements of a step's matchers, each twice
-for rep in 1 2; do for m in beside-pyramid under-quadtree under-fast; do python3 bench.py --matchers $m --no-extras --no-cpu-baseline --steps 40 --warmup 5 --sustained-s 0 2>/dev/null | python3 -c "
+for rep in 1 2; do for m in beside-pyramid under-quadtree under-fast; do python3 bench.py --matchers $m --full --no-extras --no-cpu-baseline --steps 40 --warmup 5 --sustained-s 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
@@ -77,9 +77,9 @@ for l in sys.stdin:
 $T bash tools/r06_pyr_chunk.sh > "$O/pyramid_chunk_sweep.txt" 2>/dev/null
 # does v_mfma_f64_4x4x4 add its four products in order, each rounded?  (the probe the edge-order PoseOptimization rests on; the handle repeats a short form of it at creation)
 { hipcc --offload-arch=gfx950 -O3 -o /tmp/mfma_chain tools/micro/mfma_chain.hip 2>&1 && /tmp/mfma_chain; } > "$O/mfma_chain_probe.txt" 2>&1
-MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --batch 64 --steps 10 --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_gpus2_gloo_one_gpu.json" 2>/dev/null
-MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --batch 64 --steps 10 --exchange allgather --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_gpus2_allgather_gloo_one_gpu.json" 2>/dev/null
-MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --workload c4 --steps 10 --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_c4_gpus2_gloo_one_gpu.json" 2>/dev/null
+MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --batch 64 --steps 10 --full --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_gpus2_gloo_one_gpu.json" 2>/dev/null
+MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --batch 64 --steps 10 --exchange allgather --full --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_gpus2_allgather_gloo_one_gpu.json" 2>/dev/null
+MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --workload c4 --steps 10 --full --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_c4_gpus2_gloo_one_gpu.json" 2>/dev/null
 # the tracking-side matchers (north_star's SearchByProjection / SearchForTriangulation kernels): kernel stats of the chain + keyframe searches,
 # kernel timelines of one step (one frame, 256 frames).  (No eight-rank one-GPU runs any more: not evidence of anything)
 $T bash tools/prof_tracking.sh trk_$R 256 > "$O/tracking_profile_log.txt" 2>&1
@@ -93,7 +93,7 @@ for shape in "1920 1080 4000" "752 480 1200"; do set -- $shape
 done
 $T python3 tools/ablate_matchers.py > "$O/matcher_ablation.txt" 2>/dev/null
 $T python3 tools/h2d_bw.py > "$O/h2d_copy_bandwidth_by_streams.txt" 2>/dev/null
-$T python3 bench.py > "$O/bench_default.json" 2>/dev/null
+$T python3 bench.py --full > "$O/bench_default.json" 2>/dev/null
 $T python3 tools/time_stats.py "$O" 50 10 > /dev/null 2>&1
 rm -rf "$O/stats" "$O"/pmc/*/q_kernel_trace.csv "$O"/pmc/*/q_agent_info.csv "$O/pmc"
 ls -la "$O"

@@ -7,7 +7,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 ev = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")) for r in rows]
 ev.sort()
 fast = [e for e in ev if e[2].startswith("k_fast")]
-# steady state of the timed region: skip the warm-up launches and the five serial "isolated" extractions bench.py appends
+# steady state of the timed region: skip the warm-up launches and the five serial "isolated" extractions bench.py --full appends
 t0, t1 = fast[4][0], fast[-7][1]
 win = [e for e in ev if e[0] >= t0 and e[1] <= t1]
 pts = []
