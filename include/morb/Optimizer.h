@@ -92,6 +92,24 @@ struct LocalBAView {
   int outerIterations = 0, lmTrials = 0;
 };
 
+// What Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) reads and writes
+// (Optimizer.cc:2065-2322), per KF1 feature i < N as morb_optimize_sim3_batch (include/morb_hip.h) takes it: entry bits (matched, pMP1
+// present, pMP1 bad, pMP2 bad), world positions of pMP1 / pMP2, i2, the two keypoints and their mvInvLevelSigma2; the keyframe poses
+// (R row-major + t), the cameras (kind 0 pinhole / 1 KB8 + 8 parameters), th2, the flags and g2oS12 (qx qy qz qw tx ty tz s).
+struct OptimizeSim3View {
+  int N = 0;
+  const uint8_t* entry = nullptr;
+  const float *Xw1 = nullptr, *Xw2 = nullptr;
+  const int* i2 = nullptr;
+  const float *obs1 = nullptr, *invSigma2_1 = nullptr, *obs2 = nullptr, *invSigma2_2 = nullptr;
+  float T1w[12] = {0}, T2w[12] = {0}, cam1[9] = {0}, cam2[9] = {0};
+  float th2 = 10.f;
+  bool bFixScale = false, bAllPoints = false;
+  double S12[8] = {0, 0, 0, 1, 0, 0, 0, 1};   // in / out (written only when the function reaches its end)
+  std::vector<uint8_t> keep;                 // out: vpMatches1[i] != NULL on return
+  int stats[8] = {0};                        // out: as morb_optimize_sim3_batch's d_stats (stats[4] = reached the end)
+};
+
 class Optimizer {
  public:
   // static int PoseOptimization(Frame* pFrame)  Optimizer.h:86 -> number of inliers
@@ -173,6 +191,38 @@ class Optimizer {
     g.outerIterations = stats[0]; g.lmTrials = stats[1]; g.ok = stats[2] != 0;
   }
 
+  // static int OptimizeSim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, g2o::Sim3&, float th2, bool bFixScale, Matrix<double,7,7>&, bool bAllPoints)
+  // Optimizer.h:97-101 -> nIn (0 on the early return).  One problem through morb_optimize_sim3_batch on the loop-closing handle.
+  static int OptimizeSim3(OptimizeSim3View& v, int device = 0) {
+    using morb_adapter::DeviceBuffer;
+    const int N = v.N;
+    v.keep.assign(N > 0 ? N : 0, 0);
+    for (int i = 0; i < N; ++i) v.keep[i] = v.entry[i] & 1;
+    for (int& s : v.stats) s = 0;
+    if (N <= 0) return 0;
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    morb_adapter::StreamScope scope_(morb_optimizer_stream(o.h));
+    struct Staging { DeviceBuffer<uint8_t> entry, fix, keep; DeviceBuffer<float> Xw1, Xw2, obs1, inv1, obs2, inv2, T1, T2, c1, c2, th2;
+                     DeviceBuffer<int> i2, cnt, nin, stats; DeviceBuffer<double> S; };
+    static thread_local Staging per_device[kMaxDevices];
+    Staging& s = per_device[device];
+    const uint8_t fix = v.bFixScale ? 1 : 0;
+    s.entry.assign(v.entry, N); s.Xw1.assign(v.Xw1, (size_t)N * 3); s.Xw2.assign(v.Xw2, (size_t)N * 3); s.i2.assign(v.i2, N);
+    s.obs1.assign(v.obs1, (size_t)N * 2); s.inv1.assign(v.invSigma2_1, N); s.obs2.assign(v.obs2, (size_t)N * 2); s.inv2.assign(v.invSigma2_2, N);
+    s.T1.assign(v.T1w, 12); s.T2.assign(v.T2w, 12); s.c1.assign(v.cam1, 9); s.c2.assign(v.cam2, 9); s.th2.assign(&v.th2, 1); s.fix.assign(&fix, 1);
+    s.S.assign(v.S12, 8); s.cnt.assign(&N, 1); s.keep.resize(N); s.nin.resize(1); s.stats.resize(8);
+    check(morb_optimize_sim3_batch(o.h, 1, N, s.cnt.get(), s.entry.get(), s.Xw1.get(), s.Xw2.get(), s.i2.get(), s.obs1.get(), s.inv1.get(), s.obs2.get(),
+                                   s.inv2.get(), s.T1.get(), s.T2.get(), s.c1.get(), s.c2.get(), s.th2.get(), s.fix.get(), v.bAllPoints ? 1 : 0,
+                                   s.S.get(), s.keep.get(), s.nin.get(), s.stats.get(), nullptr));
+    morb_adapter::sync_current_stream();
+    s.S.download(v.S12, 8);
+    v.keep = s.keep.to_host();
+    s.stats.download(v.stats, 8);
+    return s.nin.to_host()[0];
+  }
+
   // ---- the reference's own signatures (include/Optimizer.h:67-101) as static member templates: the call sites of src/Tracking.cc and
   // src/LocalMapping.cc compile unchanged (definitions: Optimizer_reference.h, included below) ----
   template <class FrameT> static int PoseOptimization(FrameT* pFrame);
@@ -183,12 +233,15 @@ class Optimizer {
   template <class KF, class MapT>
   static void LocalInertialBA(KF* pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges, bool bLarge = false,
                               bool bRecInit = false);
+  template <class KF, class MP, class Sim3T, class Mat77>
+  static int OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale, Mat77& mAcumHessian,
+                          const bool bAllPoints = false);
 
   // The reference's Optimizer is a stateless static class entered concurrently from Tracking (PoseOptimization, every frame) and from
   // LocalMapping (LocalBundleAdjustment, hundreds of milliseconds of LM trials): each role has its own handle — own stream, own
   // workspace — per device, created once (std::call_once), so a tracked frame never queues behind local-mapping trials; a mutex per
   // handle serialises callers of the same role.
-  enum Role { kTracking = 0, kMapping = 1 };
+  enum Role { kTracking = 0, kMapping = 1, kLoopClosing = 2 };
   static morb_optimizer* optimizer(int device = 0, Role role = kTracking) { return slot(device, role).h; }
 
  private:
@@ -254,7 +307,7 @@ class Optimizer {
   struct Slot { std::once_flag once; std::mutex mu; morb_optimizer* h = nullptr; };
   static Slot& slot(int device, Role role) {
     if (device < 0 || device >= kMaxDevices) throw std::runtime_error("bad device");
-    static Slot slots[kMaxDevices][2];
+    static Slot slots[kMaxDevices][3];
     Slot& o = slots[device][role];
     std::call_once(o.once, [&] {
       if (morb_optimizer_create(&o.h, device) != MORB_OK) { o.h = nullptr; throw std::runtime_error(std::string("morb_optimizer_create: ") + morb_last_error()); }

@@ -482,6 +482,90 @@ void Optimizer::LocalInertialBA(KF* pKF, bool* pbStopFlag, MapT* pMap, int& num_
   pMap->IncreaseChangeIndex();
 }
 // Sophus::SE3f(Matrix3f Rcw, Vector3f tcw) (:2840-2842)
+// int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+//                             const bool bFixScale, Eigen::Matrix<double, 7, 7>& mAcumHessian, const bool bAllPoints)  Optimizer.cc:2065-2322
+// Gathers what the edge loop (:2118-2231) reads, runs morb_optimize_sim3_batch, nulls the vpMatches1 entries the two inlier tests null,
+// and writes g2oS12 back / zeroes mAcumHessian only when the reference reaches its end (the early return at :2272 leaves both).
+// Uses only g2o::Sim3's rotation() / translation() / scale() and (Quaterniond, Vector3d, double) constructor, and Matrix::setZero().
+// Camera kind: a KannalaBrandt8 camera has 8 parameters, a Pinhole 4.  On a KB8 rig keyframe the reference's mvKeysUn[i] is out of bounds
+// for i >= NLeft: feature i's own row is read (mvKeysRight[i - NLeft]), as DESIGN.md section 6 decides for SearchByProjection(Frame, KeyFrame).
+template <class KF, class MP, class Sim3T, class Mat77>
+int Optimizer::OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale,
+                            Mat77& mAcumHessian, const bool bAllPoints) {
+  const int N = (int)vpMatches1.size();
+  const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  std::vector<uint8_t> entry(N, 0);
+  std::vector<float> Xw1((size_t)N * 3, 0.f), Xw2((size_t)N * 3, 0.f), obs1((size_t)N * 2, 0.f), obs2((size_t)N * 2, 0.f), inv1(N, 0.f), inv2(N, 0.f);
+  std::vector<int> i2v(N, -1);
+  auto key_of = [](KF* pKF, int i) -> decltype(pKF->mvKeysUn[0]) {
+    return (pKF->NLeft != -1 && i >= pKF->NLeft) ? pKF->mvKeysRight[i - pKF->NLeft] : pKF->mvKeysUn[i];
+  };
+  for (int i = 0; i < N; ++i) {
+    MP* pMP2 = vpMatches1[i];
+    if (!pMP2) continue;
+    MP* pMP1 = vpMapPoints1[i];
+    uint8_t e = 1;
+    const int i2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKF2));
+    i2v[i] = i2;
+    if (pMP1) {
+      e |= 2;
+      if (pMP1->isBad()) e |= 4;
+      const auto X = pMP1->GetWorldPos();
+      for (int k = 0; k < 3; ++k) Xw1[(size_t)i * 3 + k] = X(k);
+    }
+    if (pMP2->isBad()) e |= 8;
+    const auto X2 = pMP2->GetWorldPos();
+    for (int k = 0; k < 3; ++k) Xw2[(size_t)i * 3 + k] = X2(k);
+    entry[i] = e;
+    if (!(e & 2) || (e & 12)) continue;   // no edge: nothing else is read
+    const auto& kp1 = key_of(pKF1, i);
+    obs1[(size_t)i * 2] = kp1.pt.x; obs1[(size_t)i * 2 + 1] = kp1.pt.y;
+    inv1[i] = pKF1->mvInvLevelSigma2[kp1.octave];
+    if (i2 >= 0) {
+      const auto& kp2 = key_of(pKF2, i2);
+      obs2[(size_t)i * 2] = kp2.pt.x; obs2[(size_t)i * 2 + 1] = kp2.pt.y;
+      inv2[i] = pKF2->mvInvLevelSigma2[kp2.octave];
+    } else {
+      // kpUn2 = cv::KeyPoint(cv::Point2f(x, y), pMP2->mnTrackScaleLevel): that argument is the keypoint's SIZE, its octave stays 0
+      inv2[i] = pKF2->mvInvLevelSigma2[0];
+    }
+  }
+  OptimizeSim3View v;
+  v.N = N; v.entry = entry.data(); v.Xw1 = Xw1.data(); v.Xw2 = Xw2.data(); v.i2 = i2v.data();
+  v.obs1 = obs1.data(); v.invSigma2_1 = inv1.data(); v.obs2 = obs2.data(); v.invSigma2_2 = inv2.data();
+  auto pose12 = [](KF* pKF, float* T) {
+    const auto Tcw = pKF->GetPose();
+    const auto R = Tcw.rotationMatrix();
+    const auto t = Tcw.translation();
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) T[r * 3 + c] = R(r, c);
+    for (int k = 0; k < 3; ++k) T[9 + k] = t(k);
+  };
+  pose12(pKF1, v.T1w); pose12(pKF2, v.T2w);
+  auto cam9 = [](KF* pKF, float* c) {
+    morb_glue::cam8(pKF->mpCamera, c + 1);
+    c[0] = pKF->mpCamera->size() >= 8 ? 1.f : 0.f;
+  };
+  cam9(pKF1, v.cam1); cam9(pKF2, v.cam2);
+  v.th2 = th2; v.bFixScale = bFixScale; v.bAllPoints = bAllPoints;
+  const auto& q = g2oS12.rotation();
+  v.S12[0] = q.x(); v.S12[1] = q.y(); v.S12[2] = q.z(); v.S12[3] = q.w();
+  for (int k = 0; k < 3; ++k) v.S12[4 + k] = g2oS12.translation()(k);
+  v.S12[7] = g2oS12.scale();
+  const int nIn = OptimizeSim3(v);
+  for (int i = 0; i < N; ++i)
+    if (vpMatches1[i] && !v.keep[i]) vpMatches1[i] = static_cast<MP*>(NULL);
+  if (v.stats[4]) {
+    using Quat = typename std::decay<decltype(g2oS12.rotation())>::type;
+    using Vec3 = typename std::decay<decltype(g2oS12.translation())>::type;
+    Vec3 t;
+    for (int k = 0; k < 3; ++k) t(k) = v.S12[4 + k];
+    g2oS12 = Sim3T(Quat(v.S12[3], v.S12[0], v.S12[1], v.S12[2]), t, v.S12[7]);
+    mAcumHessian.setZero();
+  }
+  return nIn;
+}
+
 template <class SE3>
 SE3 Optimizer::se3_from_matrix(const double R[9], const double t[3]) {
   typename std::decay<decltype(std::declval<SE3>().rotationMatrix())>::type Rm;

@@ -570,6 +570,37 @@ int morb_pose_optimization_fisheye_batch(morb_optimizer*, int nframes, int cap, 
                                          const float* d_Xw, const float* camL8, const float* camR8, const float* Trl7,
                                          float* d_pose, uint8_t* d_outlier, int* d_nInliers, int* d_stats, void* stream);
 
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)  src/Optimizer.cc:2065-2322
+ * (include/Optimizer.h:97-101), nprob problems, one workgroup each, asynchronous on `stream` (NULL = the handle's own).
+ * Per KF1 feature i < d_count[p] (NULL = cap), arrays [nprob][cap]:
+ *   d_entry  bit 0 vpMatches1[i] != NULL, bit 1 pMP1 = pKF1->GetMapPointMatches()[i] != NULL, bit 2 pMP1->isBad(), bit 3 pMP2->isBad();
+ *   d_Xw1 / d_Xw2 [..][3] GetWorldPos() of pMP1 / pMP2; d_i2 = get<0>(pMP2->GetIndexInKeyFrame(pKF2));
+ *   d_obs1 [..][2] = pKF1->mvKeysUn[i].pt, d_invSigma2_1 = pKF1->mvInvLevelSigma2[its octave];
+ *   d_obs2 [..][2] = pKF2->mvKeysUn[i2].pt (unused when i2 < 0), d_invSigma2_2 = pKF2->mvInvLevelSigma2[octave of that keypoint]; when
+ *   i2 < 0 the reference reads mvInvLevelSigma2[0]: its stand-in keypoint cv::KeyPoint(pt, pMP2->mnTrackScaleLevel) takes the level as
+ *   the SIZE argument and keeps octave 0.
+ * Per problem: d_T1w / d_T2w [12] = R row-major + t (float); d_cam1 / d_cam2 [9] = kind (0 Pinhole, 1 KannalaBrandt8) + the 8 parameters
+ * of pKF1->mpCamera / pKF2->mpCamera; d_th2; d_fixScale; d_S12 [8] in / out = qx qy qz qw tx ty tz s (g2o::Sim3, doubles).
+ * Outputs: d_keep[p][i] = vpMatches1[i] != NULL on return; d_nIn[p] = the return value; d_stats[p][8] = LM iterations and trials of
+ * optimize(5), of the second optimize, 1 if the function reached its end (it then zeroes mAcumHessian and writes g2oS12; an early return
+ * at nCorrespondences - nBad < 10 leaves both, but its nulled matches stay nulled), nCorrespondences, nBad, nIn.
+ * Reproduced as the reference runs them:
+ *   * an edge pair (EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ) per match with both points good, skipped when i2 < 0 && !bAllPoints
+ *     or P3D2c.z < 0 (float); camera-frame points R * Xw + t in float; Huber delta = sqrtf(th2); edges in feature order;
+ *   * i2 < 0: the e21 "observation" is the NORMALISED (x, y) of P3D2c compared against pixels (such edges end as outliers);
+ *   * g2o's Levenberg-Marquardt (optimization_algorithm_levenberg.cpp:61-169) with numeric Jacobians (delta 1e-9, central
+ *     differences), sums in edge order, the 7 x 7 system by Eigen::LDLT; the phase-1 inlier test reads the errors of the last
+ *     EVALUATED trial (a failed last trial is popped without recomputing them);
+ *   * KannalaBrandt8::project(Vector3d) calls atan2f / sqrtf in float (its numeric Jacobian is quantised the same way) and cos / sin of
+ *     a double: glibc's, bit for bit (csrc/libm_f32.h, csrc/libm_f64.h).
+ * Rig keyframes: the reference reads pKF1->mvKeysUn[i] for every i, out of bounds for i >= NLeft on a KB8 rig; pass feature i's own
+ * row (mvKeysRight[i - NLeft]) as DESIGN.md section 6 decides for SearchByProjection(Frame, KeyFrame). */
+int morb_optimize_sim3_batch(morb_optimizer*, int nprob, int cap, const int* d_count, const uint8_t* d_entry, const float* d_Xw1,
+                             const float* d_Xw2, const int* d_i2, const float* d_obs1, const float* d_invSigma2_1, const float* d_obs2,
+                             const float* d_invSigma2_2, const float* d_T1w, const float* d_T2w, const float* d_cam1, const float* d_cam2,
+                             const float* d_th2, const uint8_t* d_fixScale, int bAllPoints, double* d_S12, uint8_t* d_keep, int* d_nIn,
+                             int* d_stats, void* stream);
+
 /* ---- visual-inertial tracking and mapping ----
  * IMU::Preintegrated as plain data (include/ImuTypes.h:154-263): 3 x 3 blocks row-major, C = the 15 x 15 covariance
  * row-major, b = the bias the measurements were integrated with in IMU::Bias order (bax bay baz bwx bwy bwz),

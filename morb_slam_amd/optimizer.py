@@ -72,6 +72,28 @@ class Optimizer:
                                                            ptr(out[2]), st))
         return out
 
+    def OptimizeSim3(self, entry, Xw1, Xw2, i2, obs1, invSigma2_1, obs2, invSigma2_2, T1w, T2w, cam1, cam2, th2, fixScale, S12,
+                     bAllPoints=False, count=None, out=None, stream=None):
+        """Batched Optimizer::OptimizeSim3 (morb_optimize_sim3_batch).  Device tensors, P problems of up to cap KF1 features:
+        entry u8 [P, cap] (bit 0 vpMatches1[i] != NULL, bit 1 pMP1 present, bit 2 pMP1 bad, bit 3 pMP2 bad), Xw1 / Xw2 f32 [P, cap, 3],
+        i2 i32 [P, cap], obs1 / obs2 f32 [P, cap, 2], invSigma2_1 / invSigma2_2 f32 [P, cap], T1w / T2w f32 [P, 12] (R row-major + t),
+        cam1 / cam2 f32 [P, 9] (kind 0 pinhole / 1 KB8 + 8 parameters), th2 f32 [P], fixScale u8 [P], S12 f64 [P, 8]
+        (qx qy qz qw tx ty tz s; in / out, written only where the function reaches its end), count i32 [P] or None.  bAllPoints defaults
+        to False as in the reference's declaration; invSigma2_2 of an i2 < 0 entry is mvInvLevelSigma2[0] (see include/morb_hip.h).
+        Returns (nIn i32 [P], keep u8 [P, cap], stats i32 [P, 8]); keep[p, i] = vpMatches1[i] != NULL on return; stats = LM iterations
+        and trials of phase 1, of phase 2, reached-the-end flag, correspondences, phase-1 outliers, nIn."""
+        import torch
+        P, cap = entry.shape
+        if out is None:
+            out = (torch.empty((P,), dtype=torch.int32, device=entry.device),
+                   torch.empty((P, cap), dtype=torch.uint8, device=entry.device),
+                   torch.empty((P, 8), dtype=torch.int32, device=entry.device))
+        st = stream_arg(stream)
+        check(self._L.morb_optimize_sim3_batch(self._h, P, cap, ptr(count), ptr(entry), ptr(Xw1), ptr(Xw2), ptr(i2), ptr(obs1), ptr(invSigma2_1),
+                                               ptr(obs2), ptr(invSigma2_2), ptr(T1w), ptr(T2w), ptr(cam1), ptr(cam2), ptr(th2), ptr(fixScale),
+                                               int(bool(bAllPoints)), ptr(S12), ptr(out[1]), ptr(out[0]), ptr(out[2]), st))
+        return out
+
     # ---- visual-inertial tracking and mapping (SURVEY 8(f) N1) ---------------------------------------------------
     def PreintegrateIMU(self, start, acc, gyro, dt, bias, nga, walk, out=None, stream=None):
         """IMU::Preintegrated::Initialize + IntegrateNewMeasurement for many measurement sequences at once.

@@ -519,3 +519,98 @@ def make_inertial_ba_problem(n_opt=10, n_fixed_vis=6, n_points=1500, n_imu=40, s
                 dt=np.array(dts, np.float32), bias=np.concatenate([ba, bg]).astype(np.float32),
                 Tbc12=np.concatenate([Tbc[:3, :3].ravel(), Tbc[:3, 3]]).astype(np.float32), cam=cam, true=true, truePts=X,
                 eRight=np.array(eRight, np.uint8), rig28=tumvi_rig28() if rig else None)
+
+
+# ---- Optimizer::OptimizeSim3 (two keyframes of one scene under a known Sim3) -----------------------------------
+SIM3_PINHOLE9 = np.array([0, EUROC_CAM["fx"], EUROC_CAM["fy"], EUROC_CAM["cx"], EUROC_CAM["cy"], 0, 0, 0, 0], np.float32)
+
+
+def sim3_camera9(kind):
+    """morb_optimize_sim3_batch camera record: kind (0 pinhole, 1 KannalaBrandt8) + 8 parameters."""
+    if kind == "pinhole":
+        return SIM3_PINHOLE9.copy()
+    return np.concatenate([[1.0], TUMVI_CAM_L]).astype(np.float32)
+
+
+def _sim3_project(kind, X):
+    c = sim3_camera9(kind)[1:].astype(np.float64)
+    if kind == "pinhole":
+        return np.stack([c[0] * X[:, 0] / X[:, 2] + c[2], c[1] * X[:, 1] / X[:, 2] + c[3]], 1)
+    return kb8_project(c, X)
+
+
+def make_sim3_problem(n=400, seed=0, cam1="pinhole", cam2="pinhole", fix_scale=False, outlier_frac=0.0, neg_i2_frac=0.0, bad_frac=0.0,
+                      no_mp1_frac=0.0, unmatched_frac=0.1, perturb=True, noise_px=0.0, th2=10.0):
+    """One OptimizeSim3 input: n KF1 features, most matched to a KF2 map point; x1 = S12 * x2 with a known S12 (scale != 1 unless
+    fix_scale, the stereo case).  Options: KB8 or pinhole on either side, gross outliers (obs1 moved 20 - 60 px), matches whose map point
+    is not seen in KF2 (i2 = -1), bad map points, matches without pMP1, a perturbed initial S12 (perturb) and pixel noise.
+    Returns a dict of the morb_optimize_sim3_batch per-problem arrays plus the true S12 and the planted outliers."""
+    rng = np.random.default_rng(0x53B3 + seed)
+    lev = (1.2 ** np.arange(8)) ** 2
+    inv_level = (1.0 / lev).astype(np.float32)
+    # scene in KF1's camera frame, inside both fields of view
+    z1 = rng.uniform(2.0, 8.0, n)
+    half = 0.55 if cam1 == "pinhole" else 1.2
+    X1c = np.stack([rng.uniform(-half, half, n) * z1, rng.uniform(-0.4, 0.4, n) * z1, z1], 1)
+    s = 1.0 if fix_scale else float(rng.uniform(0.6, 1.6))
+    q = _quat_from_rotvec(rng.normal(0, 0.08, 3))
+    t = rng.normal(0, 0.15, 3)
+    S12 = np.concatenate([q, t, [s]])                      # x1 = s R x2 + t
+    qc = q * np.array([-1, -1, -1, 1.0])
+    X2c = np.array([_quat_rot(qc, (x - t) / s) for x in X1c])
+    # keyframe poses (world -> camera) and world positions of the two map points of each match
+    def pose():
+        return _rot_from_rotvec(rng.normal(0, 0.3, 3)), rng.normal(0, 1.0, 3)
+    R1, t1 = pose()
+    R2, t2 = pose()
+    Xw1 = ((X1c - t1) @ R1).astype(np.float32)
+    Xw2 = ((X2c - t2) @ R2).astype(np.float32)
+    T1w = np.concatenate([R1.reshape(-1), t1]).astype(np.float32)
+    T2w = np.concatenate([R2.reshape(-1), t2]).astype(np.float32)
+    obs1 = _sim3_project(cam1, X1c) + rng.normal(0, noise_px, (n, 2))
+    obs2 = _sim3_project(cam2, X2c) + rng.normal(0, noise_px, (n, 2))
+    oct1 = rng.integers(0, 8, n)
+    oct2 = rng.integers(0, 8, n)
+    outlier = rng.random(n) < outlier_frac
+    shift = rng.uniform(20, 60, (n, 2)) * rng.choice([-1, 1], (n, 2))
+    obs1[outlier] += shift[outlier]
+    matched = rng.random(n) >= unmatched_frac
+    has_mp1 = rng.random(n) >= no_mp1_frac
+    bad1 = rng.random(n) < bad_frac / 2
+    bad2 = rng.random(n) < bad_frac / 2
+    entry = (matched.astype(np.uint8) | (has_mp1.astype(np.uint8) << 1) | (bad1.astype(np.uint8) << 2) |
+             (bad2.astype(np.uint8) << 3)).astype(np.uint8)
+    i2 = rng.permutation(4 * n)[:n].astype(np.int32)
+    i2[rng.random(n) < neg_i2_frac] = -1
+    inv2 = inv_level[oct2]
+    inv2[i2 < 0] = inv_level[0]        # the reference's stand-in keypoint of an i2 < 0 match keeps octave 0
+    S0 = S12.copy()
+    if perturb:
+        S0[:4] = _quat_mul(_quat_from_rotvec(rng.normal(0, 0.01, 3)), q)
+        S0[4:7] = t + rng.normal(0, 0.02, 3)
+        S0[7] = s * (1.0 if fix_scale else float(np.exp(rng.normal(0, 0.03))))
+    return dict(n=n, entry=entry, Xw1=Xw1, Xw2=Xw2, i2=i2, obs1=obs1.astype(np.float32), inv1=inv_level[oct1],
+                obs2=obs2.astype(np.float32), inv2=inv2, T1w=T1w, T2w=T2w, cam1=sim3_camera9(cam1), cam2=sim3_camera9(cam2),
+                th2=np.float32(th2), fix_scale=bool(fix_scale), S12=S0.astype(np.float64), S12_true=S12, outlier=outlier & matched)
+
+
+def pack_sim3_problems(probs, device):
+    """make_sim3_problem dicts -> the padded [P, cap] torch tensors of Optimizer.OptimizeSim3 on `device` (cap = the largest n)."""
+    import torch
+    P, cap = len(probs), max(max(p["n"] for p in probs), 1)
+
+    def stack(key, shape, dtype):
+        a = np.zeros((P, cap) + shape, dtype)
+        for k, p in enumerate(probs):
+            a[k, :p["n"]] = p[key]
+        return torch.from_numpy(a).to(device)
+    t = {"entry": stack("entry", (), np.uint8), "Xw1": stack("Xw1", (3,), np.float32), "Xw2": stack("Xw2", (3,), np.float32),
+         "i2": stack("i2", (), np.int32), "obs1": stack("obs1", (2,), np.float32), "obs2": stack("obs2", (2,), np.float32),
+         "inv1": stack("inv1", (), np.float32), "inv2": stack("inv2", (), np.float32)}
+    for k in ("T1w", "T2w", "cam1", "cam2"):
+        t[k] = torch.from_numpy(np.stack([p[k] for p in probs]).astype(np.float32)).to(device)
+    t["th2"] = torch.tensor([float(p["th2"]) for p in probs], dtype=torch.float32, device=device)
+    t["fix"] = torch.tensor([int(p["fix_scale"]) for p in probs], dtype=torch.uint8, device=device)
+    t["S12"] = torch.from_numpy(np.stack([p["S12"] for p in probs]).astype(np.float64)).to(device)
+    t["count"] = torch.tensor([p["n"] for p in probs], dtype=torch.int32, device=device)
+    return t
