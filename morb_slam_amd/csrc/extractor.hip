@@ -20,6 +20,7 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "common.h"
@@ -997,26 +998,14 @@ namespace {
 
 static int cvRoundF(float v) { return (int)lrintf(v); }
 
-void free_buffers(morb_extractor* e) {
-  auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  F(e->d_geom); F(e->d_geomTeam); F(e->d_tabs); F(e->d_pcol); F(e->d_prow); F(e->d_pedge); F(e->d_segTab); F(e->d_pyr); F(e->d_blur); F(e->d_cand); F(e->d_qt); F(e->d_sel);
-  F(e->d_candCnt); F(e->d_selCnt); F(e->d_kref); F(e->d_lap);
-  e->W = e->H = e->nimgCap = 0;
-  e->lapLast.clear();
-}
-void free_staging(morb_extractor* e) {
-  auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  F(e->d_img); F(e->d_out1); e->d_kps1 = nullptr; e->d_desc1 = nullptr; e->d_cnt1 = nullptr; e->d_mono1 = nullptr;
-  e->imgBytes = 0;
-  if (e->h_io1) { (void)hipHostFree(e->h_io1); e->h_io1 = nullptr; e->ioBytes1 = 0; }
-}
-
-// Build geometry + tables for (W, H) and allocate for nimg images.
+// Build geometry + tables for (W, H) and allocate for nimg images.  The device tables and buffers of the old size are replaced one
+// by one (each owner's alloc() frees its old block first); until that has succeeded the handle is configured for no size.
 int configure(morb_extractor* e, int W, int H, int nimg) {
   if (e->W == W && e->H == H && e->nimgCap >= nimg) return MORB_OK;
   MORB_HIP_CHECK(hipSetDevice(e->device));
   MORB_HIP_CHECK(hipStreamSynchronize(e->stream));
-  free_buffers(e);
+  e->W = e->H = e->nimgCap = 0;
+  e->lapLast.clear();
   const int L = e->nlevels;
   std::vector<ResizeTab> tabs;
   std::vector<PyrCol> pcols; std::vector<PyrRow> prows; std::vector<PyrEdge> pedges;
@@ -1284,9 +1273,9 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
     for (int b = 0; b < tb; ++b) e->distSmemTeam = std::max(e->distSmemTeam, tFill[b]);
   }
 
-  MORB_HIP_CHECK(hipMalloc(&e->d_geom, sizeof(LevelGeom) * kMaxLevels));
+  MORB_HIP_CHECK(e->d_geom.alloc(sizeof(LevelGeom) * kMaxLevels));
   MORB_HIP_CHECK(hipMemcpy(e->d_geom, e->geom, sizeof(LevelGeom) * kMaxLevels, hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(hipMalloc(&e->d_geomTeam, sizeof(LevelGeom) * kMaxLevels));
+  MORB_HIP_CHECK(e->d_geomTeam.alloc(sizeof(LevelGeom) * kMaxLevels));
   MORB_HIP_CHECK(hipMemcpy(e->d_geomTeam, teamGeom, sizeof(LevelGeom) * kMaxLevels, hipMemcpyHostToDevice));
   for (int l = 0; l < kMaxLevels; ++l) {
     const LevelGeom& g = e->geom[l < L ? l : L - 1];
@@ -1298,26 +1287,26 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
     e->descGeom.blurImg[l] = g.blurImg; e->descGeom.pstride[l] = g.pstride; e->descGeom.bstride[l] = g.bstride;
     e->descGeom.scale[l] = g.scale; e->descGeom.kpSize[l] = g.kpSize;
   }
-  MORB_HIP_CHECK(hipMalloc(&e->d_segTab, sizeof(FastSeg) * segs.size()));
+  MORB_HIP_CHECK(e->d_segTab.alloc(sizeof(FastSeg) * segs.size()));
   MORB_HIP_CHECK(hipMemcpy(e->d_segTab, segs.data(), sizeof(FastSeg) * segs.size(), hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(hipMalloc(&e->d_tabs, sizeof(ResizeTab) * std::max<size_t>(tabs.size(), 1)));
+  MORB_HIP_CHECK(e->d_tabs.alloc(sizeof(ResizeTab) * std::max<size_t>(tabs.size(), 1)));
   if (!tabs.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_tabs, tabs.data(), sizeof(ResizeTab) * tabs.size(), hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(hipMalloc(&e->d_pcol, sizeof(PyrCol) * std::max<size_t>(pcols.size(), 1)));
+  MORB_HIP_CHECK(e->d_pcol.alloc(sizeof(PyrCol) * std::max<size_t>(pcols.size(), 1)));
   if (!pcols.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_pcol, pcols.data(), sizeof(PyrCol) * pcols.size(), hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(hipMalloc(&e->d_prow, sizeof(PyrRow) * std::max<size_t>(prows.size(), 1)));
+  MORB_HIP_CHECK(e->d_prow.alloc(sizeof(PyrRow) * std::max<size_t>(prows.size(), 1)));
   if (!prows.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_prow, prows.data(), sizeof(PyrRow) * prows.size(), hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(hipMalloc(&e->d_pedge, sizeof(PyrEdge) * std::max<size_t>(pedges.size(), 1)));
+  MORB_HIP_CHECK(e->d_pedge.alloc(sizeof(PyrEdge) * std::max<size_t>(pedges.size(), 1)));
   if (!pedges.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_pedge, pedges.data(), sizeof(PyrEdge) * pedges.size(), hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(hipMalloc(&e->d_pyr, e->pyrBytes + 256));
+  MORB_HIP_CHECK(e->d_pyr.alloc(e->pyrBytes + 256));
   MORB_HIP_CHECK(hipMemset(e->d_pyr, 0, e->pyrBytes + 256));   // (the alignment slack behind each row is never written; other kernels' wide loads may touch it)
-  MORB_HIP_CHECK(hipMalloc(&e->d_blur, e->blurBytes + 256));
-  MORB_HIP_CHECK(hipMalloc(&e->d_cand, sizeof(uint32_t) * (size_t)nimg * e->totalCells * e->cellCap));
-  MORB_HIP_CHECK(hipMalloc(&e->d_candCnt, sizeof(int) * (size_t)nimg * e->totalCells));
-  MORB_HIP_CHECK(hipMalloc(&e->d_qt, sizeof(uint32_t) * std::max<size_t>(e->qtElems, 1)));
-  MORB_HIP_CHECK(hipMalloc(&e->d_sel, sizeof(uint32_t) * (size_t)nimg * e->selPerImg));
-  MORB_HIP_CHECK(hipMalloc(&e->d_selCnt, sizeof(int) * (size_t)nimg * L));
-  MORB_HIP_CHECK(hipMalloc(&e->d_kref, sizeof(int2) * (size_t)nimg * e->selPerImg));
-  MORB_HIP_CHECK(hipMalloc(&e->d_lap, sizeof(int) * (size_t)nimg * 2));
+  MORB_HIP_CHECK(e->d_blur.alloc(e->blurBytes + 256));
+  MORB_HIP_CHECK(e->d_cand.alloc(sizeof(uint32_t) * (size_t)nimg * e->totalCells * e->cellCap));
+  MORB_HIP_CHECK(e->d_candCnt.alloc(sizeof(int) * (size_t)nimg * e->totalCells));
+  MORB_HIP_CHECK(e->d_qt.alloc(sizeof(uint32_t) * std::max<size_t>(e->qtElems, 1)));
+  MORB_HIP_CHECK(e->d_sel.alloc(sizeof(uint32_t) * (size_t)nimg * e->selPerImg));
+  MORB_HIP_CHECK(e->d_selCnt.alloc(sizeof(int) * (size_t)nimg * L));
+  MORB_HIP_CHECK(e->d_kref.alloc(sizeof(int2) * (size_t)nimg * e->selPerImg));
+  MORB_HIP_CHECK(e->d_lap.alloc(sizeof(int) * (size_t)nimg * 2));
   MORB_HIP_CHECK(hipMemset(e->d_selCnt, 0, sizeof(int) * (size_t)nimg * L));
   MORB_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_umax), e->umax, sizeof(int) * 16));
   MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_distribute),
@@ -1365,7 +1354,7 @@ int morb_extractor_create(morb_extractor** out, int nfeatures, float scaleFactor
   int ndev = 0;
   MORB_HIP_CHECK(hipGetDeviceCount(&ndev));
   MORB_REQUIRE(device >= 0 && device < ndev, MORB_ERR_INVALID, "no such HIP device");
-  morb_extractor* e = new morb_extractor();
+  std::unique_ptr<morb_extractor> e(new morb_extractor());
   e->nfeatures = nfeatures; e->scaleFactor = scaleFactor; e->nlevels = nlevels; e->iniTh = iniThFAST;
   e->minTh = minThFAST; e->device = device;
   // ORBextractor.cc:413-443
@@ -1394,32 +1383,27 @@ int morb_extractor_create(morb_extractor** out, int nfeatures, float scaleFactor
   {
     static const int kStd[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
     for (int i = 0; i < 16; ++i)
-      if (e->umax[i] != kStd[i]) { set_error("umax table mismatch"); delete e; return MORB_ERR_UNSUPPORTED; }
+      if (e->umax[i] != kStd[i]) { set_error("umax table mismatch"); return MORB_ERR_UNSUPPORTED; }
   }
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamDefault) != hipSuccess ||
-      hipStreamCreateWithFlags(&e->sideStream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->evFork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->evPyr, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->evJoin, hipEventDisableTiming) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || e->stream.create(hipStreamDefault) != hipSuccess ||
+      e->sideStream.create(hipStreamNonBlocking) != hipSuccess || e->evFork.create(hipEventDisableTiming) != hipSuccess ||
+      e->evPyr.create(hipEventDisableTiming) != hipSuccess || e->evJoin.create(hipEventDisableTiming) != hipSuccess) {
     set_error("cannot create a stream on device %d", device);
-    delete e;
     return MORB_ERR_HIP;
   }
   // status word the kernels can flag (pinned, device-mapped: the host reads it after a synchronisation without a copy)
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_status), sizeof(int), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&e->d_status), e->h_status, 0) != hipSuccess) {
+  if (e->status.alloc(sizeof(int), hipHostMallocMapped) != hipSuccess) {
     set_error("cannot allocate the status word");
-    morb_extractor_destroy(e);
     return MORB_ERR_HIP;
   }
-  *e->h_status = 0;
-  *out = e;
+  *e->status.get() = 0;
+  *out = e.release();
   return MORB_OK;
 }
 
 int morb_extractor_status(morb_extractor* e, int* flags) {
   MORB_REQUIRE(e, MORB_ERR_INVALID, "extractor is NULL");
-  const int f = __atomic_exchange_n(e->h_status, 0, __ATOMIC_ACQ_REL);
+  const int f = __atomic_exchange_n(e->status.get(), 0, __ATOMIC_ACQ_REL);
   if (flags) *flags = f;
   // (bit 0 was "a level held more than 65535 FAST candidates" until round 5; the quadtree no longer has that limit and no kernel raises a flag today)
   if (f) { set_error("an extraction was flagged on the device (flags 0x%x): the keypoints of that call are not valid", f); return MORB_ERR_UNSUPPORTED; }
@@ -1429,17 +1413,8 @@ int morb_extractor_status(morb_extractor* e, int* flags) {
 void morb_extractor_destroy(morb_extractor* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  free_buffers(e);
-  free_staging(e);
-  for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
-  e->ev.clear();
-  if (e->evFork) (void)hipEventDestroy(e->evFork);
-  if (e->evPyr) (void)hipEventDestroy(e->evPyr);
-  if (e->evJoin) (void)hipEventDestroy(e->evJoin);
-  if (e->sideStream) (void)hipStreamDestroy(e->sideStream);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  if (e->h_status) (void)hipHostFree(e->h_status);
+  (void)hipStreamSynchronize(e->sideStream);
+  (void)hipStreamSynchronize(e->stream);
   delete e;
 }
 
@@ -1468,8 +1443,8 @@ int morb_extractor_set_profiling(morb_extractor* e, int enable) {
   e->profiling = enable != 0;
   e->profCalls = 0;
   if (e->profiling && e->ev.empty()) {
-    e->ev.resize((size_t)morb_extractor::kProfRing * 8, nullptr);
-    for (auto& ev : e->ev) MORB_HIP_CHECK(hipEventCreate(&ev));
+    e->ev.resize((size_t)morb_extractor::kProfRing * 8);
+    for (auto& ev : e->ev) MORB_HIP_CHECK(ev.create(hipEventDefault));
   }
   return MORB_OK;
 }
@@ -1496,7 +1471,7 @@ int morb_extractor_stage_ms(morb_extractor* e, float* ms7) {
   for (int c = 0; c < n; ++c) {
     // events: 0 start, 1 pyramid done, 2 FAST done, 3 quadtree done, 4 layout done, 5 describe done (launch stream);
     // 6 / 7 around the blur on the side stream.  Stages: pyramid, blur, fast, distribute, layout, describe, total.
-    hipEvent_t* ev = &e->ev[(size_t)c * 8];
+    const morb::Event* ev = &e->ev[(size_t)c * 8];
     MORB_HIP_CHECK(hipEventSynchronize(ev[5]));
     MORB_HIP_CHECK(hipEventSynchronize(ev[7]));
     const int from[7] = {0, 6, 1, 2, 3, 4, 0}, to[7] = {1, 7, 2, 3, 4, 5, 5};
@@ -1537,7 +1512,7 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
     }
   }
 
-  hipEvent_t* evs = e->profiling ? &e->ev[(size_t)(e->profCalls % morb_extractor::kProfRing) * 8] : nullptr;
+  const morb::Event* evs = e->profiling ? &e->ev[(size_t)(e->profCalls % morb_extractor::kProfRing) * 8] : nullptr;
   auto mark = [&](int i) { if (evs) (void)hipEventRecord(evs[i], st); };
   mark(0);
   {
@@ -1616,16 +1591,16 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
   static const int teamMid = [] { const char* v = getenv("MORB_TEAM_MID"); return v ? atoi(v) : 0; }();
   if (nimg <= kTeamMaxImages && e->distGroupsTeam > 0)   // few images: latency matters, the big levels are worked by teams of waves
     hipLaunchKernelGGL(k_distribute, dim3(nimg, e->distGroupsTeam), dim3(64 * QT_TEAM_WAVES), e->distSmemTeam, st, e->d_geomTeam, e->d_cand, e->d_candCnt,
-                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->d_status);
+                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->status.dev());
   else if (nimg <= teamMid && e->distGroupsTeam > 0)
     hipLaunchKernelGGL(k_distribute, dim3(nimg, e->distGroupsTeam), dim3(64 * QT_MAX_WAVES), e->distSmemTeam, st, e->d_geomTeam, e->d_cand, e->d_candCnt,
-                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->d_status);
+                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->status.dev());
   else
     // (one launch per bin of levels, each with its own LDS size — all bins of one launch get the largest bin's — measured: the launches
     // follow each other on the stream, 128 -> 204 us per 128 images, 420 -> 435 per 512; round 4: a launch per LEVEL, single-wave workgroups with
     // exactly the level's LDS, the eight launches side by side on streams of their own: 399 -> 513 us per 512 images alone, bench 124.5 -> 112.8 k frames/s)
     hipLaunchKernelGGL(k_distribute, dim3(nimg, e->distGroups), dim3(64 * e->distWaves), e->distSmem, st, e->d_geom, e->d_cand, e->d_candCnt,
-                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->d_status);
+                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->status.dev());
   hipStream_t sideStream = e->sideStream;
   MORB_HIP_CHECK(hipStreamWaitEvent(sideStream, e->evFork, 0));
   if (evs) (void)hipEventRecord(evs[6], sideStream);
@@ -1658,59 +1633,42 @@ int morb_extract(morb_extractor* e, const uint8_t* image, int width, int height,
   MORB_HIP_CHECK(hipSetDevice(e->device));
   const size_t bytes = (size_t)stride * height;
   const int maxk = morb_extractor_max_keypoints(e);
-  if (e->imgBytes < bytes || !e->d_kps1) {
-    MORB_HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (e->d_img) (void)hipFree(e->d_img);
-    e->d_img = nullptr;
-    MORB_HIP_CHECK(hipMalloc(&e->d_img, bytes));
-    e->imgBytes = bytes;
-    if (!e->d_kps1) {
-      // ONE device block laid out like the pinned buffer of the way back: count | monoIndex | pad to 16 | keypoints | descriptors — one copy brings a call's results
-      // home (four copies before round 6: ~6 us of launch latency each on a 0.2 ms call)
-      const size_t out1 = 16 + (sizeof(morb_keypoint) + 32) * (size_t)maxk;
-      MORB_HIP_CHECK(hipMalloc(&e->d_out1, out1));
-      uint8_t* b = static_cast<uint8_t*>(e->d_out1);
-      e->d_cnt1 = reinterpret_cast<int*>(b); e->d_mono1 = reinterpret_cast<int*>(b) + 1;
-      e->d_kps1 = reinterpret_cast<morb_keypoint*>(b + 16); e->d_desc1 = b + 16 + sizeof(morb_keypoint) * (size_t)maxk;
-    }
-  }
-  int rc = configure(e, width, height, 1);
+  // ONE device block laid out like the pinned buffer of the way back: count | monoIndex | pad to 16 | keypoints | descriptors — one copy brings a call's
+  // results home (four copies before round 6: ~6 us of launch latency each on a 0.2 ms call).  Host <-> device through ONE pinned buffer: the image is
+  // copied into it and uploaded asynchronously, the results come back in one asynchronous copy and one synchronisation; pageable copies straight from /
+  // to the caller's buffers are staged and synchronised by the runtime one by one.  (The staging only grows and keeps what it outgrows: no wait here.)
+  const size_t outBytes = 16 + (sizeof(morb_keypoint) + 32) * (size_t)maxk, descAt = 16 + sizeof(morb_keypoint) * (size_t)maxk;
+  void *img1 = nullptr, *out1 = nullptr, *io1 = nullptr;
+  int rc = e->img1.ensure(bytes, &img1);
+  if (rc == MORB_OK) rc = e->out1.ensure(outBytes, &out1);
+  if (rc == MORB_OK) rc = e->io1.ensure(std::max(bytes, outBytes), &io1);
+  if (rc == MORB_OK) rc = configure(e, width, height, 1);
   if (rc != MORB_OK) return rc;
-  // Host <-> device through ONE pinned buffer: the image is copied into it and uploaded asynchronously, the results (count, monoIndex,
-  // all keypoint / descriptor slots) come back in one asynchronous copy and one synchronisation; pageable copies straight from / to the
-  // caller's buffers are staged and synchronised by the runtime one by one.
-  const size_t outBytes = 16 + (sizeof(morb_keypoint) + 32) * (size_t)maxk, need = std::max(bytes, outBytes);
-  if (e->ioBytes1 < need) {
-    MORB_HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (e->h_io1) (void)hipHostFree(e->h_io1);
-    e->h_io1 = nullptr; e->ioBytes1 = 0;
-    MORB_HIP_CHECK(hipHostMalloc(&e->h_io1, need));
-    e->ioBytes1 = need;
-  }
-  const int stale = __atomic_load_n(e->h_status, __ATOMIC_ACQUIRE);   // flags of earlier, unqueried calls on this handle
+  uint8_t *d_img = static_cast<uint8_t*>(img1), *d_out1 = static_cast<uint8_t*>(out1), *h_io1 = static_cast<uint8_t*>(io1);
+  const int stale = __atomic_load_n(e->status.get(), __ATOMIC_ACQUIRE);   // flags of earlier, unqueried calls on this handle
   {
     // the image goes up in pieces: while the copy engine moves piece k the host copies piece k + 1 into the pinned buffer (a 1920 x 1080 image is 2 MB:
     // ~0.1 ms of memcpy in front of a 0.06 ms upload when done in one go)
     const size_t piece = bytes > ((size_t)512 << 10) ? (bytes / 4 + 4095) & ~(size_t)4095 : bytes;
     for (size_t o = 0; o < bytes; o += piece) {
       const size_t nb = std::min(piece, bytes - o);
-      memcpy(e->h_io1 + o, image + o, nb);
-      MORB_HIP_CHECK(hipMemcpyAsync(e->d_img + o, e->h_io1 + o, nb, hipMemcpyHostToDevice, e->stream));
+      memcpy(h_io1 + o, image + o, nb);
+      MORB_HIP_CHECK(hipMemcpyAsync(d_img + o, h_io1 + o, nb, hipMemcpyHostToDevice, e->stream));
     }
   }
   int lap[2] = {lap0, lap1};
-  rc = morb_extract_batch(e, e->d_img, 1, width, height, stride, bytes, lap, e->d_kps1, e->d_desc1, maxk, e->d_cnt1,
-                          e->d_mono1, e->stream);
+  rc = morb_extract_batch(e, d_img, 1, width, height, stride, bytes, lap, reinterpret_cast<morb_keypoint*>(d_out1 + 16), d_out1 + descAt, maxk,
+                          reinterpret_cast<int*>(d_out1), reinterpret_cast<int*>(d_out1) + 1, e->stream);
   if (rc != MORB_OK) return rc;
-  int* hcnt = reinterpret_cast<int*>(e->h_io1);
-  morb_keypoint* hkps = reinterpret_cast<morb_keypoint*>(e->h_io1 + 16);
-  uint8_t* hdesc = e->h_io1 + 16 + sizeof(morb_keypoint) * (size_t)maxk;
+  int* hcnt = reinterpret_cast<int*>(h_io1);
+  morb_keypoint* hkps = reinterpret_cast<morb_keypoint*>(h_io1 + 16);
+  uint8_t* hdesc = h_io1 + descAt;
   // (the upload is ordered before these copies on the same stream, so the buffer can be reused for the way back)
-  MORB_HIP_CHECK(hipMemcpyAsync(e->h_io1, e->d_out1, outBytes, hipMemcpyDeviceToHost, e->stream));   // count | monoIndex | keypoints | descriptors: one copy
+  MORB_HIP_CHECK(hipMemcpyAsync(h_io1, d_out1, outBytes, hipMemcpyDeviceToHost, e->stream));   // count | monoIndex | keypoints | descriptors: one copy
   MORB_HIP_CHECK(hipStreamSynchronize(e->stream));
   {   // only THIS call's flags decide its result: what an earlier batched call left unqueried stays for morb_extractor_status
-    const int own = __atomic_exchange_n(e->h_status, 0, __ATOMIC_ACQ_REL) & ~stale;
-    if (stale) __atomic_fetch_or(e->h_status, stale, __ATOMIC_ACQ_REL);
+    const int own = __atomic_exchange_n(e->status.get(), 0, __ATOMIC_ACQ_REL) & ~stale;
+    if (stale) __atomic_fetch_or(e->status.get(), stale, __ATOMIC_ACQ_REL);
     if (own) { set_error("the extraction was flagged on the device (flags 0x%x)", own); *n = 0; return MORB_ERR_UNSUPPORTED; }
   }
   const int cnt = hcnt[0], mono = hcnt[1];

@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "hip_owned.h"
 #include "morb_hip.h"
 
 namespace morb {
@@ -84,7 +85,7 @@ struct PyrLevel0 { int nInt, j0, nEdge, nG, nIntItems, nItems; uint32_t magicInt
 struct morb_extractor {
   morb::FastGeom fastGeom = {};
   morb::DescGeom descGeom = {};
-  int2* d_kref = nullptr;   // per selected keypoint: output slot | level << 24 (or -1), packed key (k_layout -> k_describe)
+  morb::DeviceArray<int2> d_kref;   // per selected keypoint: output slot | level << 24 (or -1), packed key (k_layout -> k_describe)
   int nfeatures = 0, nlevels = 0, iniTh = 0, minTh = 0, device = 0;
   float scaleFactor = 1.2f;
   std::vector<float> scale, invScale, sigma2, invSigma2;
@@ -102,34 +103,34 @@ struct morb_extractor {
   int distGroups = 0, distWaves = 1;         // k_distribute grid: workgroups per image, waves per workgroup
   // the same for calls with few images (latency): the big levels are worked by a team of QT_MAX_WAVES waves each
   int distGroupsTeam = 0; size_t distSmemTeam = 0;
-  morb::LevelGeom* d_geomTeam = nullptr;
+  morb::DeviceArray<morb::LevelGeom> d_geomTeam;
 
-  hipStream_t stream = nullptr;
-  hipStream_t sideStream = nullptr;          // the blur runs here, underneath the quadtree (fork after FAST, join before describe)
-  hipEvent_t evFork = nullptr, evJoin = nullptr;
-  hipEvent_t evPyr = nullptr;      // recorded on the launch stream behind the last pyramid launch (morb_extractor_event_after_pyramid)
+  morb::Stream stream;
+  morb::Stream sideStream;                   // the blur runs here, underneath the quadtree (fork after FAST, join before describe)
+  morb::Event evFork, evJoin;
+  morb::Event evPyr;               // recorded on the launch stream behind the last pyramid launch (morb_extractor_event_after_pyramid)
   bool wantPyrEvent = false;       // ... once a caller has asked for it
-  morb::LevelGeom* d_geom = nullptr;
-  morb::ResizeTab* d_tabs = nullptr;
-  morb::PyrCol* d_pcol = nullptr; morb::PyrRow* d_prow = nullptr; morb::PyrEdge* d_pedge = nullptr;
+  // device tables and buffers of the configured size (configure() replaces them)
+  morb::DeviceArray<morb::LevelGeom> d_geom;
+  morb::DeviceArray<morb::ResizeTab> d_tabs;
+  morb::DeviceArray<morb::PyrCol> d_pcol; morb::DeviceArray<morb::PyrRow> d_prow; morb::DeviceArray<morb::PyrEdge> d_pedge;
   morb::PyrLevel pyrLv[morb::kMaxLevels] = {}; morb::PyrLevel0 pyrL0 = {};
   bool pyrPacked = true;   // every level's four-pixel chunks fit k_resize's 8-byte source windows (scale factors up to ~1.75)
-  morb::FastSeg* d_segTab = nullptr;
-  uint8_t *d_pyr = nullptr, *d_blur = nullptr;
-  uint32_t *d_cand = nullptr, *d_qt = nullptr, *d_sel = nullptr;
-  int *d_candCnt = nullptr, *d_selCnt = nullptr,  *d_lap = nullptr;
-  int *h_status = nullptr, *d_status = nullptr;   // pinned, device-mapped flags the kernels can raise (bit 0: a level with > 65535 FAST candidates)
-  // staging for the single-image host API
-  uint8_t* d_img = nullptr; size_t imgBytes = 0;
-  void* d_out1 = nullptr;   // morb_extract's result block: the four pointers below point into it
-  morb_keypoint* d_kps1 = nullptr; uint8_t* d_desc1 = nullptr; int *d_cnt1 = nullptr, *d_mono1 = nullptr;
-  uint8_t* h_io1 = nullptr; size_t ioBytes1 = 0;   // pinned host staging of morb_extract: the image on the way in, [cnt, mono | keypoints | descriptors] on the way out
+  morb::DeviceArray<morb::FastSeg> d_segTab;
+  morb::DeviceArray<uint8_t> d_pyr, d_blur;
+  morb::DeviceArray<uint32_t> d_cand, d_qt, d_sel;
+  morb::DeviceArray<int> d_candCnt, d_selCnt, d_lap;
+  morb::PinnedArray<int> status;   // pinned, device-mapped flags the kernels can raise (bit 0: a level with > 65535 FAST candidates)
+  // staging for the single-image host API (grow-only)
+  morb::DeviceGrow img1;    // morb_extract's image
+  morb::DeviceGrow out1;    // morb_extract's result block: count | monoIndex | pad to 16 | keypoints | descriptors
+  morb::PinnedGrow io1;     // pinned host staging of morb_extract: the image on the way in, the result block on the way out
   std::vector<int> lapLast;  // host mirror of d_lap
   // profiling: a ring of event sets, one per morb_extract_batch call, read back (and averaged) on demand so the
   // timed region never synchronises with the host
   bool profiling = false;
   static constexpr int kProfRing = 64;
-  std::vector<hipEvent_t> ev;  // [kProfRing][8]
+  std::vector<morb::Event> ev;  // [kProfRing][8]
   int profCalls = 0;
   float stageMs[7] = {0};
 };

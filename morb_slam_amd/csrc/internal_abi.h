@@ -1,6 +1,7 @@
 // Helpers the translation units of libmorb_hip.so share with each other (handle fields, grow-only workspaces).  C linkage so that the
 // handle structs stay private to their units, HIDDEN visibility so that the library exports exactly what include/morb_hip.h declares
-// (tests/test_oracle_cpu.py compares `nm -D` with the header).
+// (tests/test_oracle_cpu.py compares `nm -D` with the header).  The workspaces follow the one growth policy of hip_owned.h (GrowOnly):
+// a returned block stays valid until the handle is destroyed, even after a larger request has replaced it.
 #pragma once
 #include <cstddef>
 

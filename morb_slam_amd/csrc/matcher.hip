@@ -1136,37 +1136,31 @@ __global__ void k_fill_i32(int* p, size_t n, int v) {
 // =====================================================================================================
 struct morb_matcher {
   int device = 0;
-  hipStream_t stream = nullptr;
-  // workspace (grown on demand)
-  unsigned long long *d_sortA = nullptr, *d_sortB = nullptr;
-  int* d_bin = nullptr;
-  int* d_sad = nullptr;
-  uint8_t* d_stereoRec = nullptr;   // k_stereo_prep's per-frame records
-  float *d_scale = nullptr, *d_invScale = nullptr;
-  int* d_idx = nullptr;
-  size_t sortElems = 0, binElems = 0, sadElems = 0, idxElems = 0, stereoRecBytes = 0;
-  void* ws[8] = {nullptr};   // generic workspaces for projection.hip
-  size_t wsBytes[8] = {0};
-  std::vector<void*> retired;   // outgrown workspaces: kernels queued on a caller's stream may still read them, so they are freed with the handle
+  morb::Stream stream;
+  // grow-only workspaces (hip_owned.h: kernels queued on a caller's stream may still read an outgrown block, so it lives as long as the handle)
+  morb::DeviceGrow sortA;        // k_bow_sort's sorted (node, feature) keys
+  morb::DeviceGrow bin;          // k_bow_match / k_rot_filter: rotation histogram bins
+  morb::DeviceGrow sad;          // k_stereo_match / k_stereo_median
+  morb::DeviceGrow stereoRec;    // k_stereo_prep's per-frame records
+  morb::DeviceGrow ws[8];        // generic workspaces for projection.hip
   // small constant tables (PredictScale thresholds, camera parameters): device copy + the host bytes it was made from, so that a
   // call with the same table neither uploads nor waits (projection.hip: morb_matcher_const)
   // Four most-recently-used copies per slot (a KB8 rig alternates the left and the right camera's table on one slot); a live copy is never
-  // rewritten — a kernel of an earlier call, queued on another caller's stream, may still be reading it.
-  struct ConstCopy { void* d = nullptr; std::vector<uint8_t> host; unsigned long long used = 0; };
+  // rewritten — a kernel of an earlier call, queued on another caller's stream, may still be reading it: a replaced copy is retired, and
+  // freed with the handle.
+  struct ConstCopy { morb::DeviceArray<> d; std::vector<uint8_t> host; unsigned long long used = 0; };
   struct ConstSlot { ConstCopy way[4]; unsigned long long clock = 0; };
   ConstSlot consts[4];
+  std::vector<morb::DeviceArray<>> retired;
 };
 
 namespace {
 template <typename T>
-int grow(T*& p, size_t& have, size_t need) {
-  if (have >= need) return MORB_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  have = 0;
-  MORB_HIP_CHECK(hipMalloc(&p, sizeof(T) * need));
-  have = need;
-  return MORB_OK;
+int grow(morb::DeviceGrow& b, size_t n, T** out) {
+  void* p = nullptr;
+  const int rc = b.ensure(sizeof(T) * n, &p);
+  *out = static_cast<T*>(p);
+  return rc;
 }
 }  // namespace
 
@@ -1179,21 +1173,15 @@ int morb_matcher_create(morb_matcher** out, int device) {
   MORB_HIP_CHECK(hipGetDeviceCount(&ndev));
   MORB_REQUIRE(device >= 0 && device < ndev, MORB_ERR_INVALID, "no such HIP device");
   MORB_HIP_CHECK(hipSetDevice(device));
-  morb_matcher* m = new morb_matcher();
+  std::unique_ptr<morb_matcher> m(new morb_matcher());
   m->device = device;
   // the handle's own stream (used when the caller passes stream = NULL) is a BLOCKING stream: it is implicitly ordered with the
   // legacy default stream, so callers that prepare inputs / consume outputs there (torch's default stream) need no events
-  if (hipStreamCreateWithFlags(&m->stream, hipStreamDefault) != hipSuccess) {
-    delete m;
+  if (m->stream.create(hipStreamDefault) != hipSuccess) {
     set_error("cannot create stream");
     return MORB_ERR_HIP;
   }
-  if (hipMalloc(&m->d_scale, sizeof(float) * 32) != hipSuccess || hipMalloc(&m->d_invScale, sizeof(float) * 32) != hipSuccess) {
-    set_error("hipMalloc failed");
-    delete m;
-    return MORB_ERR_HIP;
-  }
-  *out = m;
+  *out = m.release();
   return MORB_OK;
 }
 
@@ -1208,12 +1196,6 @@ void morb_matcher_destroy(morb_matcher* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   (void)hipStreamSynchronize(m->stream);
-  auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  F(m->d_sortA); F(m->d_sortB); F(m->d_bin); F(m->d_sad); F(m->d_stereoRec); F(m->d_scale); F(m->d_invScale); F(m->d_idx);
-  for (auto& w : m->ws) F(w);
-  for (auto& w : m->retired) F(w);
-  for (auto& c : m->consts) for (auto& k : c.way) F(k.d);
-  (void)hipStreamDestroy(m->stream);
   delete m;
 }
 
@@ -1221,24 +1203,7 @@ int morb_matcher_device(const morb_matcher* m) { return m->device; }
 void* morb_matcher_stream(const morb_matcher* m) { return (void*)m->stream; }
 int morb_matcher_workspace(morb_matcher* m, int which, size_t bytes, void** out) {
   MORB_REQUIRE(m && out && which >= 0 && which < 8, MORB_ERR_INVALID, "bad workspace request");
-  if (m->wsBytes[which] < bytes) {
-    // no device-wide wait and no hipFree here (hipFree waits for the whole device: the Tracking thread would stall behind a
-    // LocalBundleAdjustment running on another stream): the outgrown buffer is retired and the new one is half as large again
-    // as asked, so the retired bytes stay below twice the final size
-    void* fresh = nullptr;
-    const size_t want = bytes + bytes / 2;
-    if (hipMalloc(&fresh, want) != hipSuccess) {
-      (void)hipGetLastError();
-      MORB_HIP_CHECK(hipMalloc(&fresh, bytes));
-      m->wsBytes[which] = bytes;
-    } else {
-      m->wsBytes[which] = want;
-    }
-    if (m->ws[which]) m->retired.push_back(m->ws[which]);
-    m->ws[which] = fresh;
-  }
-  *out = m->ws[which];
-  return MORB_OK;
+  return m->ws[which].ensure(bytes, out);
 }
 // Device copy of a small host table that rarely changes (level thresholds, camera parameters).  Same bytes as the last call on
 // this slot: no upload, no wait.  Otherwise the table is uploaded in stream order and the call waits for the copy.
@@ -1252,10 +1217,10 @@ int morb_matcher_const(morb_matcher* m, int slot, const void* host, size_t bytes
     if (c.way[w].used < c.way[victim].used) victim = w;   // (an empty way has used == 0)
   }
   morb_matcher::ConstCopy& k = c.way[victim];
-  void* fresh = nullptr;
-  MORB_HIP_CHECK(hipMalloc(&fresh, bytes));
-  if (k.d) m->retired.push_back(k.d);   // freed with the handle: never overwritten while a kernel may read it
-  k.d = fresh;
+  morb::DeviceArray<> fresh;
+  MORB_HIP_CHECK(fresh.alloc(bytes));
+  if (k.d) m->retired.push_back(std::move(k.d));   // freed with the handle: never overwritten while a kernel may read it
+  k.d = std::move(fresh);
   k.host.assign((const uint8_t*)host, (const uint8_t*)host + bytes);
   k.used = ++c.clock;
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
@@ -1270,11 +1235,12 @@ int morb_bow_sort_images(morb_matcher* m, int nimg, const int* d_node, const int
   while (P < cap) P <<= 1;
   MORB_REQUIRE((size_t)P * 8 <= 160 * 1024, MORB_ERR_UNSUPPORTED, "too many features per frame for the LDS sort");
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-  int rc = grow(m->d_sortA, m->sortElems, (size_t)nimg * cap);
+  unsigned long long* sortA = nullptr;
+  int rc = grow(m->sortA, (size_t)nimg * cap, &sortA);
   if (rc != MORB_OK) return rc;
   MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_sort), hipFuncAttributeMaxDynamicSharedMemorySize, P * 8));
-  hipLaunchKernelGGL(k_bow_sort, dim3(nimg), dim3(P / 2 < 64 ? 64 : P / 2 > 1024 ? 1024 : P / 2), (size_t)P * 8, st, d_node, d_count, cap, P, m->d_sortA);
-  *d_sorted = m->d_sortA;
+  hipLaunchKernelGGL(k_bow_sort, dim3(nimg), dim3(P / 2 < 64 ? 64 : P / 2 > 1024 ? 1024 : P / 2), (size_t)P * 8, st, d_node, d_count, cap, P, sortA);
+  *d_sorted = sortA;
   return MORB_OK;
 }
 
@@ -1355,7 +1321,9 @@ int morb_stereo_match_batch(morb_matcher* m, const morb_extractor* e, int nframe
   MORB_REQUIRE(e->device == m->device, MORB_ERR_INVALID, "extractor and matcher live on different devices");
   MORB_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-  int rc = grow(m->d_sad, m->sadElems, (size_t)nframes * cap);
+  int* sad = nullptr;
+  uint8_t* stereoRec = nullptr;
+  int rc = grow(m->sad, (size_t)nframes * cap, &sad);
   if (rc != MORB_OK) return rc;
   StereoGeom sg = {};
   for (int l = 0; l < 16; ++l) {
@@ -1365,7 +1333,7 @@ int morb_stereo_match_batch(morb_matcher* m, const morb_extractor* e, int nframe
   }
   sg.nRows = e->geom[0].h;
   const StereoRec ro = stereo_rec(cap);
-  rc = grow(m->d_stereoRec, m->stereoRecBytes, (size_t)nframes * ro.bytes);
+  rc = grow(m->stereoRec, (size_t)nframes * ro.bytes, &stereoRec);
   if (rc != MORB_OK) return rc;
   const size_t prepSmem = (size_t)ro.bytes + SM_MAXB * sizeof(int);
   const size_t stereoSmem = (size_t)ro.bytes + 4 * SM_KQ * (32 + 8) + 4 * SM_PCAP * sizeof(uint32_t);
@@ -1373,11 +1341,11 @@ int morb_stereo_match_batch(morb_matcher* m, const morb_extractor* e, int nframe
   MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_prep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)prepSmem));
   MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_match), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stereoSmem));
   const int lk = sm_lk_for(nframes);
-  hipLaunchKernelGGL(k_stereo_prep, dim3(nframes), dim3(nframes <= 16 ? 1024 : 256), prepSmem, st, sg, d_kps, d_count, cap, m->d_stereoRec);
+  hipLaunchKernelGGL(k_stereo_prep, dim3(nframes), dim3(nframes <= 16 ? 1024 : 256), prepSmem, st, sg, d_kps, d_count, cap, stereoRec);
   hipLaunchKernelGGL(k_stereo_match, dim3(div_up(cap, lk), nframes), dim3(256), stereoSmem, st, sg, e->d_pyr, d_kps, d_desc,
-                     d_count, cap, mbf, mb, d_uRight, d_depth, m->d_sad, lk, m->d_stereoRec);
-  if (nframes <= 16) hipLaunchKernelGGL(k_stereo_median<16>, dim3(nframes), dim3(64 * 16), 0, st, d_count, cap, d_uRight, d_depth, m->d_sad);
-  else hipLaunchKernelGGL(k_stereo_median<4>, dim3(nframes), dim3(64 * 4), 0, st, d_count, cap, d_uRight, d_depth, m->d_sad);
+                     d_count, cap, mbf, mb, d_uRight, d_depth, sad, lk, stereoRec);
+  if (nframes <= 16) hipLaunchKernelGGL(k_stereo_median<16>, dim3(nframes), dim3(64 * 16), 0, st, d_count, cap, d_uRight, d_depth, sad);
+  else hipLaunchKernelGGL(k_stereo_median<4>, dim3(nframes), dim3(64 * 4), 0, st, d_count, cap, d_uRight, d_depth, sad);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }
@@ -1533,12 +1501,14 @@ static int search_by_bow_impl(morb_matcher* m, int npairs, const int* d_kfImg, c
   MORB_REQUIRE((size_t)P * 8 <= 160 * 1024, MORB_ERR_UNSUPPORTED, "too many features per frame for the LDS sort");
   MORB_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-  int rc = grow(m->d_sortA, m->sortElems, (size_t)nimg * cap);
+  unsigned long long* sortA = nullptr;
+  int* bin = nullptr;
+  int rc = grow(m->sortA, (size_t)nimg * cap, &sortA);
   if (rc != MORB_OK) return rc;
-  rc = grow(m->d_bin, m->binElems, (size_t)npairs * cap);
+  rc = grow(m->bin, (size_t)npairs * cap, &bin);
   if (rc != MORB_OK) return rc;
   MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_sort), hipFuncAttributeMaxDynamicSharedMemorySize, P * 8));
-  hipLaunchKernelGGL(k_bow_sort, dim3(nimg), dim3(P / 2 < 64 ? 64 : P / 2 > 1024 ? 1024 : P / 2), (size_t)P * 8, st, d_node, d_count, cap, P, m->d_sortA);
+  hipLaunchKernelGGL(k_bow_sort, dim3(nimg), dim3(P / 2 < 64 ? 64 : P / 2 > 1024 ? 1024 : P / 2), (size_t)P * 8, st, d_node, d_count, cap, P, sortA);
   const size_t nm = (size_t)npairs * cap;
   hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, st, d_matchF, nm, -1);
   int* matched2 = nullptr;
@@ -1551,12 +1521,12 @@ static int search_by_bow_impl(morb_matcher* m, int npairs, const int* d_kfImg, c
   }
   MORB_REQUIRE(cap < 65536 && (size_t)cap * 18 <= 160 * 1024, MORB_ERR_UNSUPPORTED, "too many features per frame for the LDS-resident node tables");
   MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_match), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)cap * 18)));
-  hipLaunchKernelGGL(k_bow_match, dim3(BM_NB, npairs), dim3(256), (size_t)cap * 18, st, m->d_sortA, m->d_sortA, d_count, d_count,
-                     cap, d_desc, d_hasMP, d_kps, d_desc, d_kps, d_kfImg, d_fImg, nnratio, d_matchF, m->d_bin, d_nLeft, d_hasMP2,
+  hipLaunchKernelGGL(k_bow_match, dim3(BM_NB, npairs), dim3(256), (size_t)cap * 18, st, sortA, sortA, d_count, d_count,
+                     cap, d_desc, d_hasMP, d_kps, d_desc, d_kps, d_kfImg, d_fImg, nnratio, d_matchF, bin, d_nLeft, d_hasMP2,
                      d_nValid, matched2);
   // the table is indexed by frame feature (M3) or by keyframe-1 feature (SearchByBoW(KF, KF))
   hipLaunchKernelGGL(k_rot_filter, dim3(npairs), dim3(256), 0, st, d_count, d_hasMP2 ? d_kfImg : d_fImg, cap, checkOri, d_matchF,
-                     m->d_bin, d_nmatches);
+                     bin, d_nmatches);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }

@@ -26,9 +26,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "common.h"
+#include "hip_owned.h"
 #include "internal_abi.h"
 #include "kb8.h"
 #include "dense_ldlt.h"
@@ -2247,52 +2249,45 @@ __global__ void k_ba_reset(BaDev pb, const float* __restrict__ pose0, const floa
 // =====================================================================================================
 struct morb_optimizer {
   int device = 0;
-  hipStream_t stream = nullptr;
+  morb::Stream stream;
   // grid-mode LocalBA runs pairs of independent small phases side by side (per-point / per-keyframe builds, Schur
   // complement / reduced right-hand side): fork-join on a side stream
-  hipStream_t side = nullptr;
-  hipEvent_t evFork = nullptr, evJoin = nullptr;
-  void* work = nullptr;        // grow-only device workspace of the one-shot entry points (morb_local_inertial_ba)
-  size_t workBytes = 0;
-  int* lmWords = nullptr;      // 16 pinned, device-mapped ints: LM state mirror of morb_local_inertial_ba (device-side LM control)
-  int* lmWordsDev = nullptr;
-  void* stage = nullptr;       // grow-only pinned host buffer: the one-shot entry points gather their inputs here for a single upload
-  size_t stageBytes = 0;
+  morb::Stream side;
+  morb::Event evFork, evJoin;
+  // grow-only buffers (hip_owned.h: growth neither waits nor frees — Optimizer.h:46-139 is all-static and entered from three threads, and a
+  // tracking-thread call must not wait for the LocalBundleAdjustment another thread has running on this device)
+  morb::DeviceGrow work;       // device workspace of the one-shot entry points (morb_local_inertial_ba, the one-shot LocalBundleAdjustment)
+  morb::DeviceGrow spill;      // device buffer of the BATCH entry points: edge lists that do not fit the LDS
+  morb::PinnedGrow stage;      // pinned host buffer: the one-shot entry points gather their inputs here for a single upload
+  morb::PinnedArray<int> lmWords;   // 16 pinned, device-mapped ints: LM state mirror of the one-shot entry points (device-side LM control)
   bool arenaCreate = false;    // morb_ba_problem_create carves the problem from `work` / `stage` (the one-shot entry points set this around the call)
-  double* scalPinned = nullptr;   // pinned scalars of an arena-mode problem
   int exactOrder = 1;             // PoseOptimization: 1 (default) = edge-order sums, the LM path of g2o decision for decision; 0 = tree sums
   int mfmaChain = 0;              // ... carried by the FP64 matrix core (this device passed k_mfma_order_selftest) instead of dependent v_add_f64
   int mfmaSelftest = -1;          // what k_mfma_order_selftest said on this device: 1 passed, 0 rejected, -1 not run (MORB_PO2_CHAIN forced the choice) or failed to run
-  // outgrown workspaces / staging buffers: a kernel or copy queued earlier (on this handle's stream or a caller's) may still use them, so growth neither
-  // waits for a stream nor frees (hipFree waits for the DEVICE): they are released with the handle.  Each growth asks for half as much again, so the
-  // retired bytes stay below twice the final size.
-  std::vector<void*> retiredDev, retiredHost;
-  void* spill = nullptr;       // grow-only device buffer of the BATCH entry points (the one-shot ones own `work`): edge lists that do not fit the LDS
-  size_t spillBytes = 0;
 };
 
 struct morb_ba_problem {
   morb_optimizer* opt = nullptr;
   BaDev h;                 // host copy of the device descriptor
   BaDev* d_desc = nullptr;
-  std::vector<void*> allocs;
   float *d_pose0 = nullptr, *d_pt0 = nullptr;
+  // a persistent problem (three-step API) owns its device block and pinned words; a one-shot problem borrows them from the optimizer handle
+  morb::DeviceArray<> mem;
+  morb::PinnedArray<int> words;
   int* h_stop = nullptr;   // [16] pinned, device-mapped host words: [0] abort flag (morb_ba_set_stop writes it without any HIP call, kernels poll it), [1] forwarded *pbStopFlag, [4..7] LM state mirror
   const volatile unsigned char* userStop = nullptr;   // the caller's *pbStopFlag (one-shot entry points), polled by the host LM loop
   int useLds = 1;
   size_t ldsBytes = 0;
   size_t denseLds = 0;     // LDS bytes of the triangle-resident solver (0: the system is too large for it)
   int mode = 0;            // 0 = grid (one launch per LM phase, host-side accept/reject), 1 = one persistent workgroup
-  hipEvent_t solved = nullptr;   // recorded behind the last morb_ba_solve on whatever stream it ran on: morb_ba_results waits for the EVENT — not for
+  morb::Event solved;            // recorded behind the last morb_ba_solve on whatever stream it ran on: morb_ba_results waits for the EVENT — not for
                                  // the device, and not through the caller's stream handle, which the caller may have destroyed since
   int redBlocks = 0;
   morbschur::Plan schur;
   size_t nPairEntries = 0;   // (e1, e2) observation pairs of the sparse block-pair Schur form (flop accounting only)
-  double* h_scal = nullptr;  // pinned host mirror of scal[0..3]
   double* d_ldws = nullptr;  // panel copies of the global-memory LDL^T when they do not fit LDS (dense_ldlt.h: global_panel_doubles)
   size_t globalLds = 0;      // dynamic LDS of k_g_ldlt_global
   int panelInLds = 1;
-  bool arena = false;        // device memory and pinned words belong to the optimizer handle (one-shot entry points): nothing to free
 };
 
 extern "C" {
@@ -2304,13 +2299,10 @@ int morb_optimizer_create(morb_optimizer** out, int device) {
   MORB_HIP_CHECK(hipGetDeviceCount(&ndev));
   MORB_REQUIRE(device >= 0 && device < ndev, MORB_ERR_INVALID, "no such HIP device");
   MORB_HIP_CHECK(hipSetDevice(device));
-  morb_optimizer* o = new morb_optimizer();
+  std::unique_ptr<morb_optimizer> o(new morb_optimizer());
   o->device = device;
-  if (hipStreamCreateWithFlags(&o->stream, hipStreamDefault) != hipSuccess ||
-      hipStreamCreateWithFlags(&o->side, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&o->evFork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&o->evJoin, hipEventDisableTiming) != hipSuccess) {
-    delete o;
+  if (o->stream.create(hipStreamDefault) != hipSuccess || o->side.create(hipStreamNonBlocking) != hipSuccess ||
+      o->evFork.create(hipEventDisableTiming) != hipSuccess || o->evJoin.create(hipEventDisableTiming) != hipSuccess) {
     set_error("cannot create stream");
     return MORB_ERR_HIP;
   }
@@ -2318,18 +2310,17 @@ int morb_optimizer_create(morb_optimizer** out, int device) {
     const char* force = getenv("MORB_PO2_CHAIN");
     if (force && (!strcmp(force, "valu") || !strcmp(force, "mfma"))) o->mfmaChain = force[0] == 'm';
     else {
-      int* d_bad = nullptr;
+      morb::DeviceArray<int> d_bad;
       int bad = -1;
-      if (hipMalloc((void**)&d_bad, sizeof(int)) == hipSuccess && hipMemsetAsync(d_bad, 0, sizeof(int), o->stream) == hipSuccess) {
-        hipLaunchKernelGGL(k_mfma_order_selftest, dim3(1), dim3(64), 0, o->stream, 1024, d_bad);
+      if (d_bad.alloc(sizeof(int)) == hipSuccess && hipMemsetAsync(d_bad, 0, sizeof(int), o->stream) == hipSuccess) {
+        hipLaunchKernelGGL(k_mfma_order_selftest, dim3(1), dim3(64), 0, o->stream, 1024, d_bad.get());
         if (hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, o->stream) != hipSuccess || hipStreamSynchronize(o->stream) != hipSuccess) bad = -1;
       }
-      if (d_bad) (void)hipFree(d_bad);
       o->mfmaChain = bad == 0;
       o->mfmaSelftest = bad < 0 ? -1 : (bad == 0 ? 1 : 0);
     }
   }
-  *out = o;
+  *out = o.release();
   return MORB_OK;
 }
 
@@ -2337,57 +2328,27 @@ int morb_optimizer_device(const morb_optimizer* o) { return o ? o->device : 0; }
 void* morb_optimizer_stream(const morb_optimizer* o) { return o ? (void*)o->stream : nullptr; }
 int morb_optimizer_workspace(morb_optimizer* o, size_t bytes, void** out) {
   MORB_REQUIRE(o && out, MORB_ERR_INVALID, "NULL argument");
-  if (bytes > o->workBytes) {
-    // no hipStreamSynchronize, no hipFree on the caller's path (Optimizer.h:46-139 is all-static and entered from three threads: a tracking-thread
-    // call must not wait for the LocalBundleAdjustment another thread has running on this device)
-    void* fresh = nullptr;
-    const size_t want = bytes + bytes / 2;
-    MORB_HIP_CHECK(hipMalloc(&fresh, want));
-    if (o->work) o->retiredDev.push_back(o->work);
-    o->work = fresh;
-    o->workBytes = want;
-  }
-  *out = o->work;
-  return MORB_OK;
+  return o->work.ensure(bytes, out);
 }
 
 int morb_optimizer_spill(morb_optimizer* o, size_t bytes, void** out) {
   MORB_REQUIRE(o && out, MORB_ERR_INVALID, "NULL argument");
-  if (bytes > o->spillBytes) {
-    void* fresh = nullptr;
-    const size_t want = bytes + bytes / 2;
-    MORB_HIP_CHECK(hipMalloc(&fresh, want));
-    if (o->spill) o->retiredDev.push_back(o->spill);
-    o->spill = fresh;
-    o->spillBytes = want;
-  }
-  *out = o->spill;
-  return MORB_OK;
+  return o->spill.ensure(bytes, out);
 }
 
 int morb_optimizer_lm_words(morb_optimizer* o, int** host, int** dev) {
   MORB_REQUIRE(o && host && dev, MORB_ERR_INVALID, "NULL argument");
   if (!o->lmWords) {
-    MORB_HIP_CHECK(hipHostMalloc(&o->lmWords, sizeof(int) * 16, hipHostMallocMapped));
+    MORB_HIP_CHECK(o->lmWords.alloc(sizeof(int) * 16, hipHostMallocMapped));
     memset(o->lmWords, 0, sizeof(int) * 16);
-    MORB_HIP_CHECK(hipHostGetDevicePointer((void**)&o->lmWordsDev, o->lmWords, 0));
   }
-  *host = o->lmWords; *dev = o->lmWordsDev;
+  *host = o->lmWords; *dev = o->lmWords.dev();
   return MORB_OK;
 }
 
 int morb_optimizer_staging(morb_optimizer* o, size_t bytes, void** host) {
   MORB_REQUIRE(o && host, MORB_ERR_INVALID, "NULL argument");
-  if (bytes > o->stageBytes) {
-    void* fresh = nullptr;
-    const size_t want = bytes + bytes / 2;
-    MORB_HIP_CHECK(hipHostMalloc(&fresh, want));
-    if (o->stage) o->retiredHost.push_back(o->stage);     // an upload queued from it may still be in flight
-    o->stage = fresh;
-    o->stageBytes = want;
-  }
-  *host = o->stage;
-  return MORB_OK;
+  return o->stage.ensure(bytes, host);
 }
 
 int morb_optimizer_info(const morb_optimizer* o, int* mfma_chain, int* exact_order, int* mfma_selftest) {
@@ -2415,17 +2376,7 @@ void morb_optimizer_destroy(morb_optimizer* o) {
   if (!o) return;
   (void)hipSetDevice(o->device);
   (void)hipStreamSynchronize(o->stream);
-  if (o->side) { (void)hipStreamSynchronize(o->side); (void)hipStreamDestroy(o->side); }
-  if (o->evFork) (void)hipEventDestroy(o->evFork);
-  if (o->evJoin) (void)hipEventDestroy(o->evJoin);
-  if (o->work) (void)hipFree(o->work);
-  if (o->spill) (void)hipFree(o->spill);
-  for (void* w : o->retiredDev) (void)hipFree(w);
-  if (o->lmWords) (void)hipHostFree(o->lmWords);
-  if (o->stage) (void)hipHostFree(o->stage);
-  for (void* w : o->retiredHost) (void)hipHostFree(w);
-  if (o->scalPinned) (void)hipHostFree(o->scalPinned);
-  (void)hipStreamDestroy(o->stream);
+  (void)hipStreamSynchronize(o->side);
   delete o;
 }
 
@@ -2492,17 +2443,18 @@ int morb_pose_optimization_fisheye_batch(morb_optimizer* o, int nframes, int cap
   return MORB_OK;
 }
 
-int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
-                           int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
-                           const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
-                           int lambdaInit100) {
+// morb_ba_problem_create, with the fisheye rig of morb_ba_problem_create_fisheye (nullptr: pinhole)
+static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                             int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
+                             const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
+                             int lambdaInit100, const Rig* rig) {
   MORB_REQUIRE(o && out && kfPose && kfFixed && mpPos && eKF && eMP && eObs && eInvSigma2, MORB_ERR_INVALID, "NULL argument");
   *out = nullptr;
   MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
   for (int e = 0; e < nE; ++e)
     MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
   MORB_HIP_CHECK(hipSetDevice(o->device));
-  morb_ba_problem* p = new morb_ba_problem();
+  std::unique_ptr<morb_ba_problem> p(new morb_ba_problem());
   p->opt = o;
   BaDev& h = p->h;
   memset(&h, 0, sizeof h);
@@ -2578,30 +2530,23 @@ int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, co
   kfChunkStart[nKF] = (int)chunkKF.size();
   h.nChunks = (int)chunkKF.size();
   bool fail = false;
-  // Memory: a persistent problem (three-step API) owns one hipMalloc per array.  The one-shot entry points (arena mode) carve
-  // everything from the optimizer's grow-only workspace — uploads first, mirrored in a pinned host buffer and sent in ONE copy,
-  // device-only arrays behind them — because ~45 hipMalloc / hipFree pairs and ~25 synchronous copies were 3.5 ms of a 4.7 ms call.
+  // Memory: every array is carved from ONE device block — uploads first, gathered in a host staging buffer and sent in ONE copy, device-only
+  // arrays behind them — because ~45 hipMalloc / hipFree pairs and ~25 synchronous copies were 3.5 ms of a 4.7 ms call.  A dry run of the carve
+  // sizes the block.  The one-shot entry points (arena mode) take the block, the pinned staging buffer and the pinned words from the optimizer
+  // handle; a persistent problem (three-step API) owns its block and words.
   const bool arena = o->arenaCreate;
-  p->arena = arena;
-  bool dry = false;
+  bool dry = true;
   size_t upOff = 0, devOff = 0, upCap = 0, devCap = 0;
   char *aBase = nullptr, *stage = nullptr;
   auto up = [&](const void* src, size_t bytes) -> void* {
-    if (arena) {
-      const size_t sz = (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255;
-      size_t& off = src ? upOff : devOff;
-      const size_t at = off;
-      off += sz;
-      if (dry) return nullptr;
-      if (off > (src ? upCap : devCap)) { fail = true; return nullptr; }
-      if (src) { memcpy(stage + at, src, bytes); return aBase + at; }
-      return aBase + upCap + at;
-    }
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) { fail = true; return nullptr; }
-    p->allocs.push_back(d);
-    if (src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) fail = true;
-    return d;
+    const size_t sz = (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255;
+    size_t& off = src ? upOff : devOff;
+    const size_t at = off;
+    off += sz;
+    if (dry) return nullptr;
+    if (off > (src ? upCap : devCap)) { fail = true; return nullptr; }
+    if (src) { memcpy(stage + at, src, bytes); return aBase + at; }
+    return aBase + upCap + at;
   };
   hipStream_t cst = o->stream;
   auto carve = [&]() {
@@ -2634,8 +2579,8 @@ int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, co
     for (int bi = 0; bi < sp.nb; ++bi) for (int bj = bi; bj < sp.nb; ++bj) { blkIndex[(size_t)bi * sp.nb + bj] = (int)blocks.size(); blocks.push_back(make_int2(bi, bj)); }
     h.sW = (double*)up(nullptr, sizeof(double) * sp.wElems());
     h.sWD = (double*)up(nullptr, sizeof(double) * sp.wElems());
-    if (!dry && !fail && (arena ? (hipMemsetAsync(h.sW, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess || hipMemsetAsync(h.sWD, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess)
-                              : (hipMemset(h.sW, 0, sizeof(double) * sp.wElems()) != hipSuccess || hipMemset(h.sWD, 0, sizeof(double) * sp.wElems()) != hipSuccess))) fail = true;
+    if (!dry && !fail && (hipMemsetAsync(h.sW, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
+                          hipMemsetAsync(h.sWD, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess)) fail = true;
     h.sPart = (double*)up(nullptr, sizeof(double) * sp.partElems());
     h.sBlocks = (const int2*)up(blocks.data(), sizeof(int2) * blocks.size());
     h.sBlkIndex = (const int*)up(blkIndex.data(), sizeof(int) * blkIndex.size());
@@ -2661,46 +2606,40 @@ int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, co
   h.stats = (int*)up(nullptr, sizeof(int) * 2);
   h.lmd = (double*)up(nullptr, sizeof(double) * 4);
   h.kfTicket = (int*)up(nullptr, sizeof(int) * std::max(nKF, 1));
-  if (!dry && !fail && (arena ? hipMemsetAsync(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1), cst) : hipMemset(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1))) != hipSuccess) fail = true;
+  if (!dry && !fail && hipMemsetAsync(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1), cst) != hipSuccess) fail = true;
   h.lmi = (int*)up(nullptr, sizeof(int) * 16);
   // mapped host words: [0] morb_ba_set_stop, [1] the caller's *pbStopFlag as the host loop forwards it, [4..7] the LM state mirror
   if (!dry) {
-    if (arena) {
-      int* dv = nullptr;
-      if (morb_optimizer_lm_words(o, &p->h_stop, &dv) != MORB_OK) { p->h_stop = nullptr; fail = true; }
-      else { memset(p->h_stop, 0, sizeof(int) * 16); h.stop = dv; h.lmHost = dv + 4; }
-    } else if (hipHostMalloc(&p->h_stop, sizeof(int) * 16, hipHostMallocMapped) != hipSuccess) { p->h_stop = nullptr; fail = true; }
-    else {
-      memset(p->h_stop, 0, sizeof(int) * 16);
-      int* dv = nullptr;
-      if (hipHostGetDevicePointer((void**)&dv, p->h_stop, 0) != hipSuccess) fail = true;
-      h.stop = dv; h.lmHost = dv + 4;
-    }
+    int *hw = nullptr, *dv = nullptr;
+    if (arena) { if (morb_optimizer_lm_words(o, &hw, &dv) != MORB_OK) fail = true; }
+    else if (p->words.alloc(sizeof(int) * 16, hipHostMallocMapped) != hipSuccess) fail = true;
+    else { hw = p->words; dv = p->words.dev(); }
+    if (hw) { memset(hw, 0, sizeof(int) * 16); p->h_stop = hw; h.stop = dv; h.lmHost = dv + 4; }
   }
   h.cam = Cam{fx, fy, cx, cy, bf};
-  h.rig = nullptr;
+  h.rig = rig ? (const Rig*)up(rig, sizeof(Rig)) : nullptr;
   h.userLambda = lambdaInit100 ? 100.0 : 0.0;
   p->d_pose0 = (float*)up(kfPose, sizeof(float) * 7 * nKF);
   p->d_pt0 = (float*)up(mpPos, sizeof(float) * 3 * nMP);
   p->d_desc = (BaDev*)up(&h, sizeof(BaDev));
   };   // carve
+  carve();   // (dry: sizes)
+  upCap = upOff; devCap = devOff; upOff = devOff = 0; dry = false;
+  std::vector<char> hostStage;   // a persistent problem's staging: pageable, the upload is waited for below
   if (arena) {
-    dry = true; carve(); dry = false;   // sizes
-    upCap = upOff; devCap = devOff; upOff = devOff = 0;
     void *w = nullptr, *sg = nullptr;
     if (morb_optimizer_workspace(o, upCap + devCap, &w) != MORB_OK || morb_optimizer_staging(o, upCap, &sg) != MORB_OK) fail = true;
     aBase = (char*)w; stage = (char*)sg;
-    if (!fail) {
-      carve();
-      if (!fail && hipMemcpyAsync(aBase, stage, upCap, hipMemcpyHostToDevice, cst) != hipSuccess) fail = true;   // the one upload
-    }
-    if (!fail) {
-      if (!o->scalPinned && hipHostMalloc(&o->scalPinned, sizeof(double) * 8) != hipSuccess) fail = true;
-      p->h_scal = o->scalPinned;
-    }
   } else {
+    if (p->mem.alloc(upCap + devCap) != hipSuccess) fail = true;
+    hostStage.resize(upCap);
+    aBase = (char*)p->mem.get(); stage = hostStage.data();
+  }
+  if (!fail) {
     carve();
-    if (!fail && hipHostMalloc(&p->h_scal, sizeof(double) * 8) != hipSuccess) fail = true;
+    if (!fail && hipMemcpyAsync(aBase, stage, upCap, hipMemcpyHostToDevice, cst) != hipSuccess) fail = true;   // the one upload
+    // a persistent problem is complete when create returns (like the synchronous copies it was once made with): it may be solved on any stream
+    if (!fail && !arena && hipStreamSynchronize(cst) != hipSuccess) fail = true;
   }
   p->ldsBytes = sizeof(double) * (size_t)h.P * (h.P + 1);
   p->useLds = (p->ldsBytes <= 136 * 1024 && h.P <= 192) ? 1 : 0;
@@ -2716,26 +2655,25 @@ int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, co
   if (!fail && p->useLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_ba), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024) != hipSuccess)
     fail = true;
   if (fail) {
-    for (void* d : p->allocs) (void)hipFree(d);
-    if (p->h_stop && !p->arena) (void)hipHostFree(p->h_stop);
-    delete p;
     set_error("device allocation/copy failed while creating the BA problem");
     return MORB_ERR_HIP;
   }
-  *out = p;
+  *out = p.release();
   return MORB_OK;
+}
+
+int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                           int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
+                           const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
+                           int lambdaInit100) {
+  return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf, lambdaInit100, nullptr);
 }
 
 void morb_ba_problem_destroy(morb_ba_problem* p) {
   if (!p) return;
   (void)hipSetDevice(p->opt->device);
   (void)hipStreamSynchronize(p->opt->stream);
-  if (p->solved) { (void)hipEventSynchronize(p->solved); (void)hipEventDestroy(p->solved); }
-  for (void* d : p->allocs) (void)hipFree(d);
-  if (!p->arena) {
-    if (p->h_scal) (void)hipHostFree(p->h_scal);
-    if (p->h_stop) (void)hipHostFree(p->h_stop);
-  }
+  if (p->solved) (void)hipEventSynchronize(p->solved);
   delete p;
 }
 
@@ -2749,10 +2687,6 @@ int morb_ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int
   // -3 = EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl)
   std::vector<float> obs3((size_t)nE * 3);
   for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = eRight[e] ? -3.0f : -2.0f; }
-  int rc = morb_ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, 0.f, 0.f, 0.f, 0.f,
-                                  0.f, lambdaInit100);
-  if (rc != MORB_OK) return rc;
-  morb_ba_problem* p = *out;
   Rig rig;
   memcpy(rig.kbL, camL8, 32);
   memcpy(rig.kbR, camR8, 32);
@@ -2763,23 +2697,8 @@ int morb_ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int
     for (int i = 0; i < 4; ++i) rig.Trl.q[i] = q[i] / n;
     for (int i = 0; i < 3; ++i) rig.Trl.t[i] = Trl7[4 + i];
   }
-  void* d_rig = nullptr;
-  if (hipMalloc(&d_rig, sizeof(Rig)) != hipSuccess || hipMemcpy(d_rig, &rig, sizeof(Rig), hipMemcpyHostToDevice) != hipSuccess) {
-    if (d_rig) (void)hipFree(d_rig);
-    morb_ba_problem_destroy(p);
-    *out = nullptr;
-    set_error("cannot upload the fisheye rig");
-    return MORB_ERR_HIP;
-  }
-  p->allocs.push_back(d_rig);
-  p->h.rig = (const Rig*)d_rig;
-  if (hipMemcpy(p->d_desc, &p->h, sizeof(BaDev), hipMemcpyHostToDevice) != hipSuccess) {
-    morb_ba_problem_destroy(p);
-    *out = nullptr;
-    set_error("cannot upload the problem descriptor");
-    return MORB_ERR_HIP;
-  }
-  return MORB_OK;
+  return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, 0.f, 0.f, 0.f, 0.f, 0.f,
+                           lambdaInit100, &rig);
 }
 
 
@@ -2801,7 +2720,7 @@ int morb_ba_solve(morb_ba_problem* p, void* stream) {
   MORB_REQUIRE(p, MORB_ERR_INVALID, "NULL problem");
   MORB_HIP_CHECK(hipSetDevice(p->opt->device));
   hipStream_t st = stream ? (hipStream_t)stream : p->opt->stream;
-  if (!p->solved) MORB_HIP_CHECK(hipEventCreateWithFlags(&p->solved, hipEventDisableTiming));
+  MORB_HIP_CHECK(p->solved.create(hipEventDisableTiming));
   struct RecordOnExit { hipEvent_t ev; hipStream_t st; ~RecordOnExit() { (void)hipEventRecord(ev, st); } } recordOnExit{p->solved, st};
   const int n = std::max(p->h.nKF, p->h.nMP * 3);
   hipLaunchKernelGGL(k_ba_reset, dim3(div_up(n, 256)), dim3(256), 0, st, p->h, p->d_pose0, p->d_pt0);
@@ -2874,8 +2793,8 @@ int morb_ba_schur_profile(morb_ba_problem* p, int iters, float* msPerLaunch, dou
   MORB_REQUIRE(p && iters > 0 && msPerLaunch && flops && usefulFlops, MORB_ERR_INVALID, "bad argument");
   MORB_HIP_CHECK(hipSetDevice(p->opt->device));
   hipStream_t st = p->opt->stream;
-  hipEvent_t e0, e1;
-  MORB_HIP_CHECK(hipEventCreate(&e0)); MORB_HIP_CHECK(hipEventCreate(&e1));
+  morb::Event e0, e1;
+  MORB_HIP_CHECK(e0.create(hipEventDefault)); MORB_HIP_CHECK(e1.create(hipEventDefault));
   const morbschur::Plan& sp = p->schur;
   auto launch = [&]() { hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(sp.nblk, sp.nsplit), dim3(64), 0, st, (const double*)p->h.sWD, (const double*)p->h.sW, sp.Mp, sp.ksteps, sp.stepsPerSplit, p->h.sBlocks, p->h.sPart, (const int*)nullptr); };
   launch();
@@ -2888,7 +2807,6 @@ int morb_ba_schur_profile(morb_ba_problem* p, int iters, float* msPerLaunch, dou
   *msPerLaunch = ms / iters;
   *flops = 2.0 * sp.nblk * morbschur::SB * morbschur::SB * (double)sp.nsplit * sp.stepsPerSplit * 4;
   *usefulFlops = 2.0 * 6 * 3 * (3 + 6) * (double)p->nPairEntries;   // per (e1, e2) entry: B1 D^-1 (6x3x3) and (B1 D^-1) B2^T (6x3x6)
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return MORB_OK;
 }
 

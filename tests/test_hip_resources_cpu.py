@@ -1,0 +1,48 @@
+"""Every HIP resource of libmorb_hip.so has one owner: device and pinned memory, streams and events are allocated and released only
+inside csrc/hip_owned.h (move-only owners and the one grow-only buffer).  A call anywhere else in csrc/ would bring back a hand-written
+release list or a second growth policy."""
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "morb_slam_amd", "csrc")
+OWNER = "hip_owned.h"
+
+_CALL = re.compile(r"\b(hipMalloc\w*|hipExtMalloc\w*|hipHostMalloc\w*|hipFree\w*|hipHostFree\w*|hipStreamCreate\w*|hipStreamDestroy\w*"
+                   r"|hipEventCreate\w*|hipEventDestroy\w*)\s*\(")
+# comments and string / character literals, in one pass so that a quote inside a comment (or // inside a string) is read right
+_NOISE = re.compile(r"//[^\n]*|/\*.*?\*/|\"(?:\\.|[^\"\\\n])*\"|'(?:\\.|[^'\\\n])*'", re.S)
+
+
+def _code(path):
+    text = open(path, encoding="utf-8").read()
+    return _NOISE.sub(lambda m: "\n" * m.group(0).count("\n") if m.group(0).startswith("/") else '""', text)
+
+
+def _calls(path):
+    code = _code(path)
+    return [(code.count("\n", 0, m.start()) + 1, m.group(1)) for m in _CALL.finditer(code)]
+
+
+def _sources():
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")))
+
+
+def test_hip_resources_are_allocated_only_by_the_owner_module():
+    bad = [f"{os.path.basename(p)}:{line}: {name}" for p in _sources() if os.path.basename(p) != OWNER for line, name in _calls(p)]
+    assert not bad, "allocate / release HIP resources through csrc/hip_owned.h:\n" + "\n".join(bad)
+
+
+def test_owner_module_is_where_the_calls_are():
+    names = {name for _, name in _calls(os.path.join(CSRC, OWNER))}
+    for want in ("hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree", "hipStreamCreateWithFlags", "hipStreamDestroy",
+                 "hipEventCreateWithFlags", "hipEventDestroy"):
+        assert want in names, want
+
+
+def test_scanner_sees_calls_and_skips_comments_and_strings(tmp_path):
+    src = tmp_path / "x.hip"
+    src.write_text('// hipMalloc(&p, 1)\n/* hipFree(p);\n */ set_error("hipHostFree(p)");\n'
+                   "MORB_HIP_CHECK(hipMalloc (&p, n)); char c = '\"'; hipEventDestroy(e);\n")
+    assert _calls(str(src)) == [(4, "hipMalloc"), (4, "hipEventDestroy")]

@@ -242,8 +242,8 @@ def test_local_ba_oneshot_polls_the_callers_flag():
 
 
 def test_local_ba_oneshot_equals_the_three_step_form():
-    # the one-shot entry carves its problem from the handle's workspace and uploads it in one copy; the persistent form owns one
-    # allocation per array: same kernels, same numbers — bit for bit — and the workspace is reused by the next call
+    # the one-shot entry carves its problem from the handle's workspace and uploads it in one copy; the persistent form carves the same
+    # layout from a block it owns: same kernels, same numbers — bit for bit — and the workspace is reused by the next call
     from morb_slam_amd import Optimizer
     from morb_slam_amd.optimizer import local_bundle_adjustment_oneshot
     opt = Optimizer()
