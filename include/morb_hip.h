@@ -601,6 +601,61 @@ int morb_optimize_sim3_batch(morb_optimizer*, int nprob, int cap, const int* d_c
                              const float* d_th2, const uint8_t* d_fixScale, int bAllPoints, double* d_S12, uint8_t* d_keep, int* d_nIn,
                              int* d_stats, void* stream);
 
+/* Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h): the constructor, SetRansacParameters, both iterate overloads and find, for
+ * nprob problems at once, one workgroup each, asynchronous on `stream` (NULL = the handle's own).  Stateless apart from the
+ * per-problem state record: every call recomputes the constructor and SetRansacParameters (cheap) and runs iterate(nIterations, ...)
+ * from state.iterations on, so one entry serves find() (nIterations = maxIterations), LoopClosing's chunked
+ * `while (!bConverge && !bNoMore) iterate(20, ...)` (LoopClosing.cc:705-722) and one call with the whole budget.
+ * Per problem (DEVICE array of records): */
+typedef struct morb_sim3_solver_params {
+  float T1w[12], T2w[12];   /* pKF1 / pKF2 GetRotation() row-major + GetTranslation() (:65-68); X3Dc2 always uses pKF2's pose */
+  float cam1[9], cam2[9];   /* kind (0 Pinhole, 1 KannalaBrandt8) + the 8 parameters of pKF1->mpCamera / pKF2->mpCamera */
+  double probability;       /* SetRansacParameters(probability, minInliers, maxIterations) (:122-146) */
+  int minInliers;           /* >= 3 in every use of the reference; with fewer, N < 3 returns as N < minInliers does (sampling 3 of
+                               fewer than 3 is undefined in the reference) */
+  int maxIterations;
+  int fixScale;             /* bFixScale: ms12i = 1 */
+  int n;                    /* mN1 = vpMatched12.size() (<= cap) */
+} morb_sim3_solver_params;
+
+/* In / out, one per problem.  Zero it before the first call (the constructor's mnIterations = mnBestInliers = 0); the kernel
+ * reads iterations, bestInliers and the best* fields and writes every field. */
+typedef struct morb_sim3_solver_state {
+  int N;             /* correspondences kept by the constructor (:76-112) */
+  int budget;        /* mRansacMaxIts after SetRansacParameters (:133-143) */
+  int iterations;    /* mnIterations: iterations done over all calls so far */
+  int bestInliers;   /* mnBestInliers */
+  int converged;     /* this call's bConverge (:246-253): an iteration had more than minInliers inliers */
+  int noMore;        /* this call's bNoMore: N < minInliers (:223-226), or the budget is spent without convergence (:259) */
+  int nInliers;      /* this call's nInliers: the inliers of the converged hypothesis, else 0 */
+  int convergedAt;   /* global index of the converged iteration, -1 */
+  float bestT12[16]; /* mBestT12 row-major (GetEstimatedTransformation) */
+  float bestR[9];    /* mBestRotation row-major (GetEstimatedRotation) */
+  float bestt[3];    /* mBestTranslation */
+  float bestScale;   /* mBestScale */
+  float sim3[16];    /* this call's return value of iterate(.., bConverge): mBestT12 on convergence, else bestSim3 = mBestT12 when an
+                        iteration of THIS call reached the best count, else identity (the reference leaves bestSim3 uninitialised
+                        there).  The other iterate overload and find() return identity unless converged. */
+} morb_sim3_solver_state;
+
+/* Per KF1 feature i < params.n, arrays [nprob][cap]:
+ *   d_entry  bit 0 vpMatched12[i] != NULL, bit 1 pMP1 = pKF1->GetMapPointMatches()[i] != NULL, bit 2 pMP1->isBad(), bit 3 pMP2->isBad(),
+ *            bit 4 get<0>(pMP1->GetIndexInKeyFrame(pKF1)) < 0, bit 5 get<0>(pMP2->GetIndexInKeyFrame(pKFm)) < 0 (:76-93);
+ *   d_Xw1 / d_Xw2 [..][3] GetWorldPos() of pMP1 / pMP2;
+ *   d_sigma2_1 = pKF1->mvLevelSigma2[octave of mvKeysUn[indexKF1]], d_sigma2_2 = pKFm->mvLevelSigma2[octave of pKFm->mvKeysUn[indexKF2]],
+ *            pKFm = vpKeyFrameMatchedMP[i] (pKF2 when the vector is empty); thresholds (size_t)(9.210 * sigma2) (:98-99).
+ * d_rand [nprob][randCap]: the rand() values of DUtils::Random::RandomInt, three per iteration, iteration g (global, from 0) reading
+ * d_rand[p][3g .. 3g+2]; a call stops at iteration randCap / 3.  Outputs: d_state; d_inliers [nprob][cap] = vbInliers (all zero
+ * unless converged; indexed by KF1 feature); d_hypInliers (optional) [nprob][hypCap] = the inlier count of global iteration g for
+ * every g this call evaluates (entries of iterations not evaluated are left as they are: pre-fill them with -1).
+ * Every iteration restates the reference in float: sampling, ComputeSim3 (Horn's closed form; the eigenvector of N by an FP64
+ * cyclic Jacobi instead of Eigen::EigenSolver: DESIGN.md section 6), CheckInliers with both cameras; iterate's running best uses >=
+ * and it returns at the first iteration with more than minInliers inliers. */
+int morb_sim3_solver_batch(morb_optimizer*, int nprob, int cap, const morb_sim3_solver_params* d_params, const uint8_t* d_entry,
+                           const float* d_Xw1, const float* d_Xw2, const float* d_sigma2_1, const float* d_sigma2_2, int nIterations,
+                           const int* d_rand, int randCap, morb_sim3_solver_state* d_state, uint8_t* d_inliers, int* d_hypInliers,
+                           int hypCap, void* stream);
+
 /* ---- visual-inertial tracking and mapping ----
  * IMU::Preintegrated as plain data (include/ImuTypes.h:154-263): 3 x 3 blocks row-major, C = the 15 x 15 covariance
  * row-major, b = the bias the measurements were integrated with in IMU::Bias order (bax bay baz bwx bwy bwz),

@@ -14,6 +14,14 @@ PREINT_FIELDS = {"dT": (0, 1), "dR": (1, 9), "dV": (10, 3), "dP": (13, 3), "JRg"
                  "avgA": (304, 3), "avgW": (307, 3)}
 PREINT_FLOATS = 310
 
+# morb_sim3_solver_params / morb_sim3_solver_state (include/morb_hip.h) as numpy records
+SIM3_SOLVER_PARAMS = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("cam1", "<f4", 9), ("cam2", "<f4", 9), ("probability", "<f8"),
+                               ("minInliers", "<i4"), ("maxIterations", "<i4"), ("fixScale", "<i4"), ("n", "<i4")], align=True)
+SIM3_SOLVER_STATE = np.dtype([("N", "<i4"), ("budget", "<i4"), ("iterations", "<i4"), ("bestInliers", "<i4"), ("converged", "<i4"),
+                              ("noMore", "<i4"), ("nInliers", "<i4"), ("convergedAt", "<i4"), ("bestT12", "<f4", 16), ("bestR", "<f4", 9),
+                              ("bestt", "<f4", 3), ("bestScale", "<f4"), ("sim3", "<f4", 16)], align=True)
+assert SIM3_SOLVER_PARAMS.itemsize == 192 and SIM3_SOLVER_STATE.itemsize == 212
+
 
 class Optimizer:
     def __init__(self, device=0):
@@ -93,6 +101,31 @@ class Optimizer:
                                                ptr(obs2), ptr(invSigma2_2), ptr(T1w), ptr(T2w), ptr(cam1), ptr(cam2), ptr(th2), ptr(fixScale),
                                                int(bool(bAllPoints)), ptr(S12), ptr(out[1]), ptr(out[0]), ptr(out[2]), st))
         return out
+
+    def Sim3Solver(self, params, entry, Xw1, Xw2, sigma2_1, sigma2_2, rand, state, nIterations, inliers=None, hypInliers=None,
+                   stream=None):
+        """Batched Sim3Solver (morb_sim3_solver_batch): the constructor, SetRansacParameters and iterate(nIterations, ...) from
+        state.iterations on.  Device tensors, P problems of up to cap KF1 features: params u8 [P, 192] (SIM3_SOLVER_PARAMS records),
+        entry u8 [P, cap] (bits 0-5: matched, pMP1 present, pMP1 bad, pMP2 bad, indexKF1 < 0, indexKF2 < 0), Xw1 / Xw2 f32 [P, cap, 3],
+        sigma2_1 / sigma2_2 f32 [P, cap] (mvLevelSigma2 of the two keypoints' octaves), rand i32 [P, randCap] (rand() values, three
+        per iteration by global iteration number), state u8 [P, 212] (SIM3_SOLVER_STATE records, in / out; zero before the first
+        call).  hypInliers i32 [P, hypCap] or None receives the inlier count of every iteration evaluated.  Returns
+        (state, inliers u8 [P, cap], hypInliers); inliers = vbInliers, set only on convergence."""
+        import torch
+        P, cap = entry.shape
+        if inliers is None:
+            inliers = torch.empty((P, cap), dtype=torch.uint8, device=entry.device)
+        hypCap = 0 if hypInliers is None else hypInliers.shape[1]
+        st = stream_arg(stream)
+        check(self._L.morb_sim3_solver_batch(self._h, P, cap, ptr(params), ptr(entry), ptr(Xw1), ptr(Xw2), ptr(sigma2_1), ptr(sigma2_2),
+                                             int(nIterations), ptr(rand), rand.shape[1], ptr(state), ptr(inliers), ptr(hypInliers), hypCap,
+                                             st))
+        return state, inliers, hypInliers
+
+    @staticmethod
+    def sim3_solver_state(state):
+        """The state tensor u8 [P, 212] -> numpy SIM3_SOLVER_STATE records [P]."""
+        return np.frombuffer(state.cpu().numpy().tobytes(), SIM3_SOLVER_STATE).copy()
 
     # ---- visual-inertial tracking and mapping (SURVEY 8(f) N1) ---------------------------------------------------
     def PreintegrateIMU(self, start, acc, gyro, dt, bias, nga, walk, out=None, stream=None):

@@ -614,3 +614,88 @@ def pack_sim3_problems(probs, device):
     t["S12"] = torch.from_numpy(np.stack([p["S12"] for p in probs]).astype(np.float64)).to(device)
     t["count"] = torch.tensor([p["n"] for p in probs], dtype=torch.int32, device=device)
     return t
+
+
+def make_sim3_solver_problem(n=400, seed=0, cam1="pinhole", cam2="pinhole", fix_scale=False, outlier_frac=0.3, bad_frac=0.04,
+                             no_mp1_frac=0.03, unmatched_frac=0.1, neg_idx_frac=0.03, dup_frac=0.02, collinear=False, identical=False,
+                             noise_px=0.3,
+                             min_inliers=20, probability=0.99, max_iterations=300):
+    """One Sim3Solver input on make_sim3_problem's geometry: n KF1 features; entry bits 0-3 as there, bit 4 / 5 = a negative keyframe
+    index of pMP1 / pMP2; outliers move pMP2's world position by ~0.5 m (the solver projects map points, not keypoints); octaves
+    give sigma2 = 1.44^octave on each side (pKFm's octave for side 2); dup_frac of the features repeat another feature's points;
+    collinear puts every pMP1 / pMP2 pair on one line, identical every pair on one point (every triple is degenerate).  Returns a dict of the morb_sim3_solver_batch
+    per-problem arrays and parameters."""
+    if n == 0:
+        p = make_sim3_solver_problem(1, seed, cam1, cam2, fix_scale, min_inliers=min_inliers, probability=probability,
+                                     max_iterations=max_iterations)
+        for k in ("entry", "Xw1", "Xw2", "sigma2_1", "sigma2_2", "outlier"):
+            p[k] = p[k][:0]
+        p["n"] = 0
+        return p
+    base = make_sim3_problem(n=n, seed=seed, cam1=cam1, cam2=cam2, fix_scale=fix_scale, outlier_frac=0.0, bad_frac=bad_frac,
+                             no_mp1_frac=no_mp1_frac, unmatched_frac=unmatched_frac, perturb=False, noise_px=0.0)
+    rng = np.random.default_rng(0x5A3C + seed)
+    Xw1, Xw2 = base["Xw1"].astype(np.float64), base["Xw2"].astype(np.float64)
+    Xw2 = Xw2 + rng.normal(0, noise_px * 2e-3, Xw2.shape)       # ~noise_px pixels at a few metres
+    outlier = rng.random(n) < outlier_frac
+    Xw2[outlier] += rng.normal(0, 0.5, (int(outlier.sum()), 3))
+    if n > 1:
+        dup = np.nonzero(rng.random(n) < dup_frac)[0]
+        src = rng.integers(0, n, len(dup))
+        Xw1[dup], Xw2[dup] = Xw1[src], Xw2[src]
+    if collinear:
+        u = rng.uniform(-1, 1, n)[:, None]
+        Xw1 = Xw1[0] + u * np.array([0.3, 0.1, 0.05])
+        Xw2 = Xw2[0] + u * np.array([0.2, -0.1, 0.04])
+    if identical:
+        Xw1, Xw2 = np.repeat(Xw1[:1], n, 0), np.repeat(Xw2[:1], n, 0)
+    entry = base["entry"].copy()
+    entry |= ((rng.random(n) < neg_idx_frac / 2).astype(np.uint8) << 4)
+    entry |= ((rng.random(n) < neg_idx_frac / 2).astype(np.uint8) << 5)
+    lev = (1.2 ** np.arange(8)) ** 2
+    oct1, oct2 = rng.integers(0, 8, n), rng.integers(0, 8, n)
+    return dict(n=n, entry=entry.astype(np.uint8), Xw1=Xw1.astype(np.float32), Xw2=Xw2.astype(np.float32),
+                sigma2_1=lev[oct1].astype(np.float32), sigma2_2=lev[oct2].astype(np.float32), T1w=base["T1w"], T2w=base["T2w"],
+                cam1=base["cam1"], cam2=base["cam2"], fix_scale=bool(fix_scale), min_inliers=int(min_inliers),
+                probability=float(probability), max_iterations=int(max_iterations), outlier=outlier, S12_true=base["S12_true"])
+
+
+def libc_rand(seed, count):
+    """count values of the C library's rand() after srand(seed): the draws DUtils::Random::RandomInt makes in the reference."""
+    import ctypes
+    import ctypes.util
+    libc = ctypes.CDLL(ctypes.util.find_library("c"))
+    libc.srand(ctypes.c_uint(seed))
+    return np.array([libc.rand() for _ in range(count)], np.int32)
+
+
+def pack_sim3_solver_problems(probs, device, rand=None, cap=None):
+    """make_sim3_solver_problem dicts -> the torch tensors of Optimizer.Sim3Solver on `device` (cap = the largest n unless given):
+    params u8 [P, 192], entry, Xw1, Xw2, sigma2_1, sigma2_2, rand i32 [P, randCap] (the given list of arrays, zero padded) and a zeroed
+    state u8 [P, 212]."""
+    import torch
+    from .optimizer import SIM3_SOLVER_PARAMS, SIM3_SOLVER_STATE
+    P = len(probs)
+    cap = cap or max(max(p["n"] for p in probs), 1)
+
+    def stack(key, shape, dtype):
+        a = np.zeros((P, cap) + shape, dtype)
+        for k, p in enumerate(probs):
+            a[k, :p["n"]] = p[key]
+        return torch.from_numpy(a).to(device)
+    prm = np.zeros(P, SIM3_SOLVER_PARAMS)
+    for k, p in enumerate(probs):
+        prm[k]["T1w"], prm[k]["T2w"], prm[k]["cam1"], prm[k]["cam2"] = p["T1w"], p["T2w"], p["cam1"], p["cam2"]
+        prm[k]["probability"], prm[k]["minInliers"], prm[k]["maxIterations"] = p["probability"], p["min_inliers"], p["max_iterations"]
+        prm[k]["fixScale"], prm[k]["n"] = int(p["fix_scale"]), p["n"]
+    t = {"entry": stack("entry", (), np.uint8), "Xw1": stack("Xw1", (3,), np.float32), "Xw2": stack("Xw2", (3,), np.float32),
+         "sigma2_1": stack("sigma2_1", (), np.float32), "sigma2_2": stack("sigma2_2", (), np.float32)}
+    t["params"] = torch.from_numpy(np.frombuffer(prm.tobytes(), np.uint8).reshape(P, -1).copy()).to(device)
+    t["state"] = torch.zeros((P, SIM3_SOLVER_STATE.itemsize), dtype=torch.uint8, device=device)
+    if rand is not None:
+        rc = max(max(len(r) for r in rand), 1)
+        a = np.zeros((P, rc), np.int32)
+        for k, r in enumerate(rand):
+            a[k, :len(r)] = r
+        t["rand"] = torch.from_numpy(a).to(device)
+    return t
