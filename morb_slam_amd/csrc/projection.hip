@@ -22,6 +22,7 @@
 #include "common.h"
 #include "internal_abi.h"
 #include "libm_f32.h"
+#include "search_tier.h"
 #include "wave.h"
 #include "kb8.h"
 
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(256) void k_prep_last_fisheye(morb_frame_params P, 
 //   projMode 0: pCamera->project(p3Dc) = fx * X / Z + cx            (Fuse, SearchByProjection v1; KB8 when cam8 != NULL)
 //            1: invz = 1 / Z (float), u = fx * (X * invz) + cx       (SearchByProjection with vpPointsKFs, :531-536)
 //            2: invz = (float)(1.0 / Z), same form                    (SearchBySim3, :1373-1378)
-//   sim (8 floats per problem, RxSO3 quaternion + translation, or NULL): applied after T; then dist3D = |p| in the
+//   sim (7 floats per problem, RxSO3 quaternion + translation, as morb_hip.h documents S12 / S21; or NULL): applied after T; then dist3D = |p| in the
 //   target camera and there is no viewing-angle test (SearchBySim3); otherwise dist3D = |Pw - Ow| and PO . Pn >= dist / 2.
 __device__ __forceinline__ void sim3_map_f(const float* S, const float* p, float* out) {   // Sophus rxso3.hpp:265-273
   const float qx = S[0], qy = S[1], qz = S[2], qw = S[3];
@@ -383,7 +384,7 @@ __global__ __launch_bounds__(256) void k_prep_kfproj(morb_frame_params P, int mp
     float p[3];
     q_rotate_f(T + 7 * f, X, p);
     p[0] += T[7 * f + 4]; p[1] += T[7 * f + 5]; p[2] += T[7 * f + 6];
-    if (sim) { float p2[3]; sim3_map_f(sim + 8 * f, p, p2); p[0] = p2[0]; p[1] = p2[1]; p[2] = p2[2]; }
+    if (sim) { float p2[3]; sim3_map_f(sim + 7 * f, p, p2); p[0] = p2[0]; p[1] = p2[1]; p[2] = p2[2]; }
     if (p[2] < 0.0f) break;
     float u, v;
     if (kb8) kb8_project_dev(kb8, p, u, v);
@@ -771,11 +772,8 @@ struct SearchLds {   // carved from dynamic LDS
   uint8_t* blk0;     // [capR]           blocked on entry; later: "an entry of this feature fell to the rotation filter"
   uint32_t* blk2;    // [capR]           the fixed point's second copy of blk (the passes alternate)
 };
-__host__ __device__ inline size_t search_lds_bytes(int cap, int qCap, bool withDesc) {
-  const size_t capR = (size_t)(cap + 3) & ~(size_t)3, qCapR = (size_t)(qCap + 3) & ~(size_t)3;
-  return 4 * ((size_t)GRID_CELLS + 4) + 4 * (size_t)GRID_CELLS + 4 * capR + 4 * qCapR + 16 * capR + (withDesc ? 32 * capR : 0) + 2 * capR * 3 +
-         4 * qCapR + 4 * (qCapR + 4) + 4 * qCapR + capR + 4 * capR;
-}
+// (its size, search_lds_bytes(), and the choice between this kernel and the serial replay live in search_tier.h)
+static_assert(morbst::SEARCH_GRID_CELLS == GRID_CELLS, "search_tier.h sizes the grid of k_search");
 
 #ifdef MORB_SEARCH_CYCLES   // developer build (tools/ab_build.py): thread 0 of frame 0 adds up where its cycles go
 __device__ unsigned long long g_searchCyc[8];
@@ -1421,10 +1419,11 @@ static int window_search(morb_matcher* m, const morb_frame_params* P, int mode, 
                          float* d_prevMatched, hipStream_t st, const int* d_l2r = nullptr, const int* d_r2l = nullptr,
                          const int* d_nLeft = nullptr, bool ranged = false) {   // ranged: queries carry a feature-index range (jLo / jHi)
   void *cand = nullptr, *cnt = nullptr, *ej = nullptr, *eb = nullptr;
-  if ((mode == 0 || mode == 1) && !ranged && cap <= 65535 && qCap <= 65535 && search_lds_bytes(cap, qCap, false) <= 150 * 1024 && !getenv("MORB_SERIAL_RESOLVE")) {
+  const int tier = morbst::search_tier(cap, qCap, !((mode == 0 || mode == 1) && !ranged) || getenv("MORB_SERIAL_RESOLVE") != nullptr);
+  if (tier != 3) {
     // one launch, one workgroup per frame: grid in LDS, candidate lists, blocked-feature fixed point (k_search)
-    const int withDesc = search_lds_bytes(cap, qCap, true) <= 150 * 1024 ? 1 : 0;
-    const size_t lds = search_lds_bytes(cap, qCap, withDesc != 0);
+    const int withDesc = tier == 1 ? 1 : 0;
+    const size_t lds = morbst::search_lds_bytes(cap, qCap, withDesc != 0);
     int rc = morb_matcher_workspace(m, 0, sizeof(uint32_t) * (size_t)nframes * qCap * SEARCH_CAP, &cand);
     if (rc != MORB_OK) return rc;
 #define MORB_SEARCH(MODE, WD)                                                                                                              \
@@ -1625,6 +1624,8 @@ int morb_search_for_initialization_batch(morb_matcher* m, const morb_frame_param
   MORB_REQUIRE(m && P && d_img1 && d_img2 && d_count && d_kps && d_desc && d_prevMatched && d_matches12 && d_nmatches,
                MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(npairs > 0 && cap > 0 && cap <= 65535, MORB_ERR_INVALID, "bad sizes");
+  // (before any launch: a refused call leaves d_matches12, d_nmatches and d_prevMatched as they were)
+  MORB_REQUIRE((size_t)cap * 8 <= 64 * 1024, MORB_ERR_UNSUPPORTED, "too many features for SearchForInitialization's LDS state");
   MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
   void *qs = nullptr, *nq = nullptr, *qd = nullptr;
@@ -1746,9 +1747,10 @@ static int kfproj_candidates(morb_matcher* m, const morb_frame_params* P, int np
 static int best_per_query(morb_matcher* m, const morb_frame_params* P, int nprob, int qCap, const int* d_nQ, const Query* qs, const uint8_t* d_qDesc,
                           const int* d_kfImg, int cap, const int* d_count, const morb_keypoint* d_kps, const uint8_t* d_desc, const float* d_uRight,
                           int thAccept, int* d_bestIdx, int* d_bestDist, hipStream_t st) {
-  if (cap <= 65535 && qCap <= 65535 && search_lds_bytes(cap, qCap, false) <= 150 * 1024 && !getenv("MORB_SERIAL_RESOLVE")) {
-    const bool withDesc = search_lds_bytes(cap, qCap, true) <= 150 * 1024;
-    const size_t lds = search_lds_bytes(cap, qCap, withDesc);
+  const int tier = morbst::search_tier(cap, qCap, getenv("MORB_SERIAL_RESOLVE") != nullptr);
+  if (tier != 3) {
+    const bool withDesc = tier == 1;
+    const size_t lds = morbst::search_lds_bytes(cap, qCap, withDesc);
     if (withDesc) {
       MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search<5, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL((k_search<5, true>), dim3(nprob), dim3(SEARCH_THREADS), lds, st, *P, qCap, d_nQ, qs, d_qDesc, (const uint8_t*)nullptr, d_kfImg, cap,

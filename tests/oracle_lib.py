@@ -314,10 +314,11 @@ def search_by_projection_mps_fisheye(F, Nleft, l2r, r2l, blocked, trkL, trkR, is
     return r, m
 
 
-def search_by_projection_last(Cur, blocked, Tcw7, lastKps, lastValid, lastXw, lastMPdesc, lastHasObs, th, fwd, bwd, checkOri):
+def search_by_projection_last(Cur, blocked, Tcw7, lastKps, lastValid, lastXw, lastMPdesc, lastHasObs, th, fwd, bwd, checkOri, match_init=None):
+    """match_init: CurrentFrame.mvpMapPoints on entry (the table is in/out); None = all -1."""
     L = lib()
     L.orc_search_by_projection_last.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    m = np.full(Cur.N, -1, np.int32)
+    m = np.full(Cur.N, -1, np.int32) if match_init is None else match_init.astype(np.int32).copy()
     a = [np.ascontiguousarray(x) for x in (blocked.astype(np.uint8), np.asarray(Tcw7, np.float32), lastKps, lastValid.astype(np.uint8),
                                            np.asarray(lastXw, np.float32), lastMPdesc, lastHasObs.astype(np.uint8))]
     r = L.orc_search_by_projection_last(C.byref(Cur), _p(a[0]), _p(a[1]), len(lastKps), _p(a[2]), _p(a[3]), _p(a[4]), _p(a[5]), _p(a[6]),
@@ -452,10 +453,11 @@ def search_for_triangulation(k1, d1, node1, has1, ur1, k2, d2, node2, has2, ur2,
     return r, m
 
 
-def search_by_projection_kf(Cur, curHasMP, Tcw7, Ow, kfKps, kfValid, Xw, maxD, minD, mpDesc, th, ORBdist, checkOri):
+def search_by_projection_kf(Cur, curHasMP, Tcw7, Ow, kfKps, kfValid, Xw, maxD, minD, mpDesc, th, ORBdist, checkOri, match_init=None):
+    """match_init: CurrentFrame.mvpMapPoints on entry (the table is in/out); None = all -1."""
     L = lib()
     L.orc_search_by_projection_kf.argtypes = [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_void_p]
-    m = np.full(Cur.N, -1, np.int32)
+    m = np.full(Cur.N, -1, np.int32) if match_init is None else match_init.astype(np.int32).copy()
     a = [np.ascontiguousarray(x) for x in (curHasMP.astype(np.uint8), np.asarray(Tcw7, np.float32), np.asarray(Ow, np.float32), kfKps,
                                            kfValid.astype(np.uint8), np.asarray(Xw, np.float32), np.asarray(maxD, np.float32),
                                            np.asarray(minD, np.float32), mpDesc)]

@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from morb_slam_amd.synth import make_stereo_pair, make_vocabulary, shift_image
+from matcher_scenes import lc_scene as _lc_scene, make_batch, quat_from_R as _quat_from_R, scene as _scene
+from morb_slam_amd.synth import make_stereo_pair, make_vocabulary
 
 pytestmark = pytest.mark.gpu
 
@@ -14,30 +15,6 @@ MBF, MB = np.float32(458.654 * 0.11), np.float32(0.11)   # EuRoC: bf = fx * base
 @pytest.fixture(scope="module")
 def batch():
     return make_batch()
-
-
-def make_batch():
-    """4 stereo frames extracted on the GPU (bit-exact with the oracle per test_extractor_gpu) + oracle twins."""
-    import torch
-    from morb_slam_amd import KP_DTYPE, ORBextractor
-    import os
-    off = 10 * int(os.environ.get("MORB_TEST_SEED", "0"))   # (tools/stress_matchers.sh: the whole file again on other images)
-    pairs = [make_stereo_pair(752, 480, seed=60 + off + i) for i in range(2)]
-    pairs += [tuple(shift_image(im, 4, 2) for im in pairs[0]), tuple(shift_image(im, 7, -3) for im in pairs[1])]
-    imgs = np.stack([im for p in pairs for im in p])
-    ext = ORBextractor(1200, 1.2, 8, 20, 7)
-    d = torch.from_numpy(imgs).cuda()
-    kps, desc, cnt, mono = ext.extract_batch(d)
-    torch.cuda.synchronize()
-    ora = []
-    for im in imgs:
-        o = O.OracleExtractor(1200)
-        _, k, dd = o(im)
-        ora.append((o, k, dd))
-    c = cnt.cpu().numpy()
-    for i in range(len(imgs)):
-        assert kps[i, :c[i]].cpu().numpy().reshape(-1).view(KP_DTYPE).tobytes() == ora[i][1].tobytes()
-    return dict(ext=ext, kps=kps, desc=desc, cnt=cnt, ora=ora, imgs=imgs, KP=KP_DTYPE)
 
 
 def test_descriptor_distance(batch):
@@ -235,20 +212,6 @@ def test_search_by_bow_keyframes(batch, k, Lv, lup):
 
 
 # ---- projection-guided searches --------------------------------------------------------------------------
-def _scene(batch):
-    """Map points = stereo-triangulated features of frame 0 (identity pose), observed again in frame 2 (a shifted copy)."""
-    import torch
-    from morb_slam_amd import ORBmatcher
-    from morb_slam_amd.capi import make_frame_params
-    ext = batch["ext"]
-    P = make_frame_params(752, 480, 458.654, 457.296, 367.215, 248.375, float(MBF), float(MB), ext.GetScaleFactors(),
-                          ext.GetScaleSigmaSquares())
-    m = ORBmatcher(0.8, True)
-    u, d = m.ComputeStereoMatches(ext, batch["kps"], batch["desc"], batch["cnt"], MBF, MB)
-    torch.cuda.synchronize()
-    return P, u, d
-
-
 def test_is_in_frustum_and_search_by_projection_mappoints(batch):
     import torch
     from morb_slam_amd import ORBmatcher
@@ -472,36 +435,6 @@ def test_search_by_projection_keyframe(batch):
 
 
 # ---- M7: loop-closing / local-mapping searches -----------------------------------------------------------------
-def _quat_from_R(R):
-    from morb_slam_amd.synth import _quat_from_R as q
-    return q(R)
-
-
-def _lc_scene(batch):
-    """Keyframe A = image 0 (world = its camera frame), keyframe B = image 4 (a 4 x 2 px shifted copy) with a nearby pose;
-    map points = stereo back-projections of each keyframe's own features."""
-    from morb_slam_amd.synth import _quat_from_rotvec, _quat_rot
-    P, uR, dep = _scene(batch)
-    rng = np.random.default_rng(21)
-    out = {}
-    q2 = _quat_from_rotvec(np.array([0.002, -0.004, 0.001])); t2 = np.array([-0.03, -0.015, 0.01])
-    T = {0: np.array([0, 0, 0, 1, 0, 0, 0], np.float64), 4: np.concatenate([q2, t2])}
-    for img, fr in ((0, 0), (4, 2)):
-        k, d = batch["ora"][img][1], batch["ora"][img][2]
-        z = dep[fr, :len(k)].cpu().numpy()
-        Xc = np.stack([(k["x"] - P.cx) * np.abs(z) / P.fx, (k["y"] - P.cy) * np.abs(z) / P.fy, np.abs(z)], 1)
-        qinv = T[img][:4] * np.array([-1, -1, -1, 1])
-        Xw = np.array([_quat_rot(qinv, x - T[img][4:]) for x in Xc])
-        dist = np.linalg.norm(Xc, axis=1)
-        maxD = dist * 1.2 ** k["octave"] * rng.uniform(0.9, 1.3, len(k)); minD = maxD / 1.2 ** 7
-        Ow = -_quat_rot(qinv, T[img][4:])
-        nrm = (Xw - Ow) / np.linalg.norm(Xw - Ow, axis=1, keepdims=True) + rng.normal(0, 0.2, Xw.shape)
-        out[img] = dict(k=k, d=d, valid=z > 0, Xw=Xw.astype(np.float32), maxD=maxD.astype(np.float32), minD=minD.astype(np.float32),
-                        normal=nrm.astype(np.float32), T=T[img].astype(np.float32), Ow=Ow.astype(np.float32),
-                        uR=uR[fr, :len(k)].cpu().numpy())
-    return P, out
-
-
 def test_fuse_and_search_by_projection_sim3(batch):
     """Fuse x2 and SearchByProjection(KF, Sim3) x2: map points of keyframe A searched in keyframe B."""
     import torch
