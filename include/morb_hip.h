@@ -56,7 +56,10 @@ int morb_extractor_max_keypoints(const morb_extractor*);
  * ORBextractor.h:55-57, ORBextractor.cc:1006-1086.  Host image in (CV_8UC1, `stride` bytes per row), host
  * keypoints (28 B each) and descriptors (32 B each) out, *n = number of keypoints.
  * Returns monoIndex (>= 0) exactly as the reference does, MORB_ERR_EMPTY for an empty image (reference: -1),
- * or another negative status. */
+ * or another negative status.
+ * `image` may be a cv::Mat with a step or a ROI of a larger frame: stride >= width, and only the `width` bytes of each row are read —
+ * nothing between two rows, nothing beyond (height - 1) * stride + width.  Limits (MORB_ERR_UNSUPPORTED): stride < 2^24 and
+ * stride * height < 2^32. */
 int morb_extract(morb_extractor*, const uint8_t* image, int width, int height, int stride, int lap0, int lap1,
                  morb_keypoint* kps, uint8_t* desc, int cap, int* n);
 
@@ -64,7 +67,10 @@ int morb_extract(morb_extractor*, const uint8_t* image, int width, int height, i
  * d_images + i*image_pitch.  lap = host array [nimg][2] of lapping areas, or NULL for {0,0} (the rectified
  * stereo call, Frame.cc:194-197).  Outputs are device arrays: d_kps [nimg][cap], d_desc [nimg][cap][32],
  * d_count [nimg], d_mono [nimg] (monoIndex); cap >= morb_extractor_max_keypoints() (else MORB_ERR_CAPACITY: the lapping-area
- * keypoints fill every image's range from the back).  Asynchronous on `stream`. */
+ * keypoints fill every image's range from the back).  Asynchronous on `stream`.
+ * Rows lie `stride` bytes apart (stride >= width, any alignment of d_images), image_pitch >= stride * height; only the `width` bytes
+ * of each row are read, and the images are never written.  Limits (MORB_ERR_UNSUPPORTED): stride < 2^24 and stride * height < 2^32,
+ * what the 32-bit row offsets of the level-0 kernel carry. */
 int morb_extract_batch(morb_extractor*, const uint8_t* d_images, int nimg, int width, int height, int stride,
                        size_t image_pitch, const int* lap, morb_keypoint* d_kps, uint8_t* d_desc, int cap,
                        int* d_count, int* d_mono, void* stream);

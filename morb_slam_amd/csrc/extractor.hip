@@ -1493,6 +1493,9 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
   MORB_REQUIRE(nimg > 0, MORB_ERR_INVALID, "nimg must be positive");
   if (width <= 0 || height <= 0) { set_error("empty image"); return MORB_ERR_EMPTY; }
   MORB_REQUIRE(stride >= width && image_pitch >= (size_t)stride * height, MORB_ERR_INVALID, "bad stride/pitch");
+  // k_level0 addresses a pixel as __umul24(row, stride) + column in 32 bits: a wider stride would silently read other rows
+  MORB_REQUIRE(stride < (1 << 24) && (unsigned long long)stride * (unsigned)height < (1ull << 32), MORB_ERR_UNSUPPORTED,
+               "stride too large for the 32-bit row offsets (need stride < 2^24 and stride * height < 2^32)");
   // k_layout places the lapping-area keypoints from the back of [0, count): a smaller cap would cut the wrong end
   MORB_REQUIRE(cap >= morb_extractor_max_keypoints(e), MORB_ERR_CAPACITY, "cap must be at least morb_extractor_max_keypoints()");
   MORB_HIP_CHECK(hipSetDevice(e->device));
@@ -1630,8 +1633,13 @@ int morb_extract(morb_extractor* e, const uint8_t* image, int width, int height,
   if (!image || width <= 0 || height <= 0) { set_error("empty image"); return MORB_ERR_EMPTY; }
   MORB_REQUIRE(kps && desc, MORB_ERR_INVALID, "NULL output");
   MORB_REQUIRE(stride >= width, MORB_ERR_INVALID, "bad stride");
+  MORB_REQUIRE(stride < (1 << 24) && (unsigned long long)stride * (unsigned)height < (1ull << 32), MORB_ERR_UNSUPPORTED,
+               "stride too large (need stride < 2^24 and stride * height < 2^32, as for morb_extract_batch)");
   MORB_HIP_CHECK(hipSetDevice(e->device));
-  const size_t bytes = (size_t)stride * height;
+  // The device copy is dense (row pitch = width): a row of the caller's image owns `width` bytes, not `stride` — the last row of a ROI that touches
+  // the bottom of its parent, or of a cv::Mat whose allocation ends with its last row, has nothing behind it.  No byte beyond
+  // (height - 1) * stride + width is read, and the bytes between two rows are not read either.
+  const size_t bytes = (size_t)width * height;
   const int maxk = morb_extractor_max_keypoints(e);
   // ONE device block laid out like the pinned buffer of the way back: count | monoIndex | pad to 16 | keypoints | descriptors — one copy brings a call's
   // results home (four copies before round 6: ~6 us of launch latency each on a 0.2 ms call).  Host <-> device through ONE pinned buffer: the image is
@@ -1652,12 +1660,18 @@ int morb_extract(morb_extractor* e, const uint8_t* image, int width, int height,
     const size_t piece = bytes > ((size_t)512 << 10) ? (bytes / 4 + 4095) & ~(size_t)4095 : bytes;
     for (size_t o = 0; o < bytes; o += piece) {
       const size_t nb = std::min(piece, bytes - o);
-      memcpy(h_io1 + o, image + o, nb);
+      if (stride == width) memcpy(h_io1 + o, image + o, nb);
+      else
+        for (size_t p = o; p < o + nb;) {   // the piece's part of each row, from where the row lies in the caller's image
+          const size_t row = p / (size_t)width, col = p - row * (size_t)width, len = std::min((size_t)width - col, o + nb - p);
+          memcpy(h_io1 + p, image + row * (size_t)stride + col, len);
+          p += len;
+        }
       MORB_HIP_CHECK(hipMemcpyAsync(d_img + o, h_io1 + o, nb, hipMemcpyHostToDevice, e->stream));
     }
   }
   int lap[2] = {lap0, lap1};
-  rc = morb_extract_batch(e, d_img, 1, width, height, stride, bytes, lap, reinterpret_cast<morb_keypoint*>(d_out1 + 16), d_out1 + descAt, maxk,
+  rc = morb_extract_batch(e, d_img, 1, width, height, width, bytes, lap, reinterpret_cast<morb_keypoint*>(d_out1 + 16), d_out1 + descAt, maxk,
                           reinterpret_cast<int*>(d_out1), reinterpret_cast<int*>(d_out1) + 1, e->stream);
   if (rc != MORB_OK) return rc;
   int* hcnt = reinterpret_cast<int*>(h_io1);

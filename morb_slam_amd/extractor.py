@@ -43,9 +43,9 @@ class ORBextractor:
         if image is None or image.size == 0:
             return -1, np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)
         assert image.dtype == np.uint8 and image.ndim == 2, "CV_8UC1 expected (ORBextractor.cc:1014)"
-        if image.strides[1] != 1:
-            image = np.ascontiguousarray(image)
         h, w = image.shape
+        if image.strides[1] != 1 or image.strides[0] < w:   # the ABI takes unit pixel steps and a row pitch >= width: no flipped or broadcast rows
+            image = np.ascontiguousarray(image)
         stride = image.strides[0]
         cap = self.max_keypoints
         kps = np.zeros(cap, KP_DTYPE)

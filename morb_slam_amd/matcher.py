@@ -163,14 +163,16 @@ class ORBmatcher:
         return out
 
     def ComputeStereoFromRGBD(self, kps, kpsUn, count, depth, bf, out=None, stream=None):
-        """Frame::ComputeStereoFromRGBD: depth f32 [F, H, W] (contiguous).  Returns (mvuRight, mvDepth) f32 [F, cap]."""
+        """Frame::ComputeStereoFromRGBD: depth f32 [F, H, W], unit pixel step; rows and images may be views of a larger tensor
+        (their pitches are taken from the tensor's strides).  Returns (mvuRight, mvDepth) f32 [F, cap]."""
         import torch
         F, cap = kps.shape[0], kps.shape[1]
         H, W = depth.shape[1], depth.shape[2]
+        assert depth.dtype == torch.float32 and depth.stride(2) == 1
         if out is None:
             out = (torch.empty((F, cap), dtype=torch.float32, device=kps.device), torch.empty((F, cap), dtype=torch.float32, device=kps.device))
         st = stream_arg(stream)
-        check(self._L.morb_stereo_from_rgbd_batch(self._h, F, cap, ptr(count), ptr(kps), ptr(kpsUn), ptr(depth), W, H, W, H * W, float(bf),
+        check(self._L.morb_stereo_from_rgbd_batch(self._h, F, cap, ptr(count), ptr(kps), ptr(kpsUn), ptr(depth), W, H, depth.stride(1), depth.stride(0), float(bf),
                                                   ptr(out[0]), ptr(out[1]), st))
         return out
 

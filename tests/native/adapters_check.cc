@@ -48,6 +48,15 @@ int main(int argc, char** argv) {
     const int mono2 = ext(img, k, d, {dims[4], dims[5]});   // a second extraction invalidates the host copies
     const int again[2] = {mono2 == mono ? 1 : 0, ext.mvImagePyramid.downloaded() ? 1 : 0};
     dump("ext_pyr_again", again, 2);
+    // the same image as a stepped Mat (img.step > img.cols, what a ROI or an aligned allocation gives) with poison in the row padding and NOTHING
+    // behind the last row's pixels: same expected bytes as the dense case
+    podcv::Mat8u st; st.cols = img.cols; st.rows = img.rows; st.step = img.cols + 37;
+    st.data.assign((size_t)(st.rows - 1) * st.step + st.cols, 0xA5);
+    for (int y = 0; y < st.rows; ++y) std::memcpy(&st.data[(size_t)y * st.step], &img.data[(size_t)y * img.cols], (size_t)img.cols);
+    std::vector<podcv::KeyPoint> ks; std::vector<uint8_t> ds;
+    const int monoS = ext(st, ks, ds, {dims[4], dims[5]});
+    const int headS[2] = {monoS, (int)ks.size()};
+    dump("ext_step_head", headS, 2); dump("ext_step_kps", ks.data(), ks.size()); dump("ext_step_desc", ds.data(), ds.size());
   }
   // ---- ORBmatcher::SearchByProjection(Frame, MapPoints)
   {

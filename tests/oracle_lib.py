@@ -86,14 +86,19 @@ class OracleExtractor:
         self.L.orc_extractor_tables(self.h, _p(sc), _p(isc), _p(s2), _p(is2), _p(fpl), _p(umax))
         return dict(scale=sc, inv_scale=isc, sigma2=s2, inv_sigma2=is2, feat_per_level=fpl, umax=umax)
 
-    def __call__(self, img, lap=(0, 0)):
-        img = np.ascontiguousarray(img, np.uint8)
+    def __call__(self, img, lap=(0, 0), stride=None):
+        """stride=None: a dense copy of img is extracted.  stride=n: img is a uint8 view whose rows lie n bytes apart; it is read where it lies."""
+        if stride is None:
+            img = np.ascontiguousarray(img, np.uint8)
+            stride = img.shape[1]
+        else:
+            assert img.dtype == np.uint8 and img.strides == (stride, 1) and stride >= img.shape[1]
         h, w = img.shape
         cap = self.nfeatures + 16 * self.nlevels
         kps = np.zeros(cap, KP_DTYPE)
         desc = np.zeros((cap, 32), np.uint8)
         n = C.c_int(0)
-        mono = self.L.orc_extract(self.h, _p(img), w, h, w, lap[0], lap[1], _p(kps), _p(desc), cap, C.byref(n))
+        mono = self.L.orc_extract(self.h, _p(img), w, h, stride, lap[0], lap[1], _p(kps), _p(desc), cap, C.byref(n))
         assert mono != -2
         return mono, kps[:n.value].copy(), desc[:n.value].copy()
 

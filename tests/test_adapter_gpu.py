@@ -97,6 +97,10 @@ def test_cpp_adapters_match_oracle(tmp_path):
     assert head.tolist() == [mono_o, len(ko)]
     assert get("ext_kps", np.uint8).tobytes() == ko.tobytes()
     assert get("ext_desc", np.uint8).tobytes() == do.tobytes()
+    # the same image as a stepped Mat (step = cols + 37, poison in the padding, the buffer ends with the last row's pixels): same bytes
+    assert get("ext_step_head", np.int32).tolist() == [mono_o, len(ko)]
+    assert get("ext_step_kps", np.uint8).tobytes() == ko.tobytes()
+    assert get("ext_step_desc", np.uint8).tobytes() == do.tobytes()
     # lazy mvImagePyramid: not downloaded by operator(), fetched on first access, invalidated by the next extraction
     oe2 = O.OracleExtractor(nfeat, 1.2, nlev, 20, 7); oe2(img, lap)
     l2 = oe2.level_image(2)[19:-19, 19:-19]      # (the POD build exposes the interior of each level; with OpenCV: ROIs into the padded copies)

@@ -88,6 +88,44 @@ def test_stereo_from_rgbd_and_image_bounds(matcher):
     assert ORBmatcher.ComputeImageBounds(W, H, TUM_CAM, (0.0, 0, 0, 0)) == (0.0, float(W), 0.0, float(H))
 
 
+def test_stereo_from_rgbd_on_a_view_of_a_larger_depth_tensor(matcher):
+    """depth as a ROI (x0, y0 > 0) of a parent with gap rows between the images and NaN / negative values everywhere around the images: the row and
+    image pitches come from the tensor's strides.  A kernel that indexed with W or H * W would read the surroundings: NaN and negative depths give
+    -1 where the oracle on the dense copy has a depth.  Keypoints on the last row and the last column included (u = W - 1, v = H - 1, and
+    x = W - 0.01, which truncates to W - 1)."""
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(8)
+    H, W, cap, x0, y0, PW, PH = 120, 160, 400, 7, 3, 160 + 21, 120 + 9      # PH - H - y0 = 6 gap rows below each image
+    counts = np.array([400, 257, 1], np.int32)
+    depth = rng.uniform(0.3, 8.0, (3, H, W)).astype(np.float32)
+    depth[rng.random((3, H, W)) < 0.2] = 0.0                    # holes
+    depth[:, H - 1, :] = rng.uniform(0.3, 8.0, (3, W)); depth[:, :, W - 1] = rng.uniform(0.3, 8.0, (3, H))     # the last row / column have a depth
+    parent = np.where(rng.random((3, PH, PW)) < 0.5, np.float32(np.nan), rng.uniform(-9.0, -0.1, (3, PH, PW)).astype(np.float32)).astype(np.float32)
+    parent[:, y0:y0 + H, x0:x0 + W] = depth
+    xy = [np.stack([rng.uniform(0, W - 0.01, n), rng.uniform(0, H - 0.01, n)], 1).astype(np.float32) for n in counts]
+    xy[0][:6] = [[W - 1, 5], [7, H - 1], [W - 1, H - 1], [W - 0.01, 11], [13, H - 0.01], [W - 0.01, H - 0.01]]
+    xy[1][:3] = [[0, 0], [W - 1, 0], [0, H - 1]]
+    xy[2][0] = [W - 0.01, H - 0.01]
+    assert int(np.float32(W - 0.01)) == W - 1 and int(np.float32(H - 0.01)) == H - 1
+    rec = _records(xy, cap)
+    kps = torch.from_numpy(rec).to(dev); cnt = torch.from_numpy(counts).to(dev)
+    un = matcher.UndistortKeyPoints(kps, cnt, TUM_CAM, TUM_DIST)
+    d_parent = torch.from_numpy(parent).to(dev)
+    view = d_parent[:, y0:y0 + H, x0:x0 + W]
+    assert view.stride() == (PH * PW, PW, 1) and not view.is_contiguous()
+    ur, dd = matcher.ComputeStereoFromRGBD(kps, un, cnt, view, TUM_CAM["bf"])
+    torch.cuda.synchronize()
+    assert d_parent.cpu().numpy().tobytes() == parent.tobytes()
+    unh = un.cpu().numpy().view(np.float32).reshape(3, cap, 7)
+    for f, n in enumerate(counts):
+        ur_o, d_o = orc.stereo_from_rgbd(xy[f], unh[f, :n, :2], depth[f], TUM_CAM["bf"])
+        assert ur[f, :n].cpu().numpy().tobytes() == ur_o.tobytes() and dd[f, :n].cpu().numpy().tobytes() == d_o.tobytes()
+        assert (ur[f, n:] == -1).all() and (dd[f, n:] == -1).all()
+    d0 = dd[0, :6].cpu().numpy()
+    assert (d0 > 0).all() and d0[0] == depth[0, 5, W - 1] and d0[2] == depth[0, H - 1, W - 1] and d0[3] == depth[0, 11, W - 1] and d0[5] == depth[0, H - 1, W - 1]
+    assert float(dd[2, 0]) == depth[2, H - 1, W - 1]
+
+
 @pytest.mark.parametrize("weighting,scoring", [(0, 0), (1, 1), (0, 5), (1, 5), (2, 0), (3, 5), (0, 3)])
 def test_bow_vector(matcher, weighting, scoring):
     """BowVector of TemplatedVocabulary::transform: bit-exact doubles, map order, stopped words, every weighting / norm branch."""

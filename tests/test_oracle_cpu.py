@@ -666,3 +666,28 @@ def test_oracle_matches_opencv_vectors():
     import make_opencv_golden as g
     ref = dict(np.load(path, allow_pickle=False))
     assert g.compare(ref, g.from_oracle(g.cases())) == 0
+
+
+def test_oracle_on_a_strided_view_equals_the_dense_copy():
+    """orc_extract takes a row stride: the GPU tests of strided / ROI inputs lean on the oracle run on np.ascontiguousarray(view), so the oracle itself is
+    pinned here for that input shape.  Sixteen consecutive widths (every residue of (width + 19) mod 16 and of width mod 4, which decide the interior / edge
+    split of the level-0 kernel), the image as a view 13 bytes and 5 rows into a poisoned parent with rows of width + 37 bytes: keypoints, descriptors and
+    every pyramid level equal the dense run's whatever the poison, and level 0 equals np.pad(mode="reflect") (= copyMakeBorder BORDER_REFLECT_101),
+    a reference that does not depend on the oracle."""
+    from strided_views import POISONS, host_view, layout, poisoned_parent
+    h = 120
+    for w in range(320, 336):
+        img = make_image(w, h, seed=700 + w)
+        dense = OracleExtractor(300, 1.2, 3, 20, 7)
+        mono, k, d = dense(img)
+        assert len(k) >= 100, (w, len(k))
+        np.testing.assert_array_equal(dense.level_image(0), np.pad(img, 19, mode="reflect"), err_msg=f"width {w}")
+        lay = layout(w, h, x0=13, y0=5, row_pad=37)
+        for kind in POISONS:
+            view = host_view(poisoned_parent(img[None], lay, kind, seed=w), lay)[0]
+            assert view.strides == (w + 37, 1) and not view.flags.c_contiguous and np.array_equal(view, img)
+            o = OracleExtractor(300, 1.2, 3, 20, 7)
+            mono_v, kv, dv = o(view, stride=lay.stride)
+            assert mono_v == mono and kv.tobytes() == k.tobytes() and np.array_equal(dv, d), (w, kind)
+            for l in range(3):
+                np.testing.assert_array_equal(o.level_image(l), dense.level_image(l), err_msg=f"width {w}, {kind} poison, level {l}")
