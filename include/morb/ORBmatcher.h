@@ -7,9 +7,10 @@
 // repository has no OpenCV / Eigen / Sophus) the header compiles as is.  Results come back as index tables with the meaning of the
 // containers the reference methods fill (vpMapPointMatches[i] = map point of keyframe feature table[i], ...); the bookkeeping on live
 // map state (AddObservation, Replace, ...) stays with the caller, as DESIGN.md states for the whole matcher family.
-// Every method: hipSetDevice(device), uploads into per-thread, per-device staging buffers that only grow, one C-ABI call per
-// reference call, synchronised on the handle's own stream (never the device: Tracking's matcher calls do not wait for the LocalBundleAdjustment
-// trials the mapping thread has in flight on its optimizer handle).
+// Every method: one morb_adapter::CallStaging (device_buffer.h: hipSetDevice(device), uploads and device arrays from per-thread, per-device
+// staging that only grows), one C-ABI call per reference call, synchronised on the handle's own stream (never the device: Tracking's matcher
+// calls do not wait for the LocalBundleAdjustment trials the mapping thread has in flight on its optimizer handle; only a call that outgrows
+// the staging pays for an allocation, which does).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -82,7 +83,7 @@ class ORBmatcher {
   static const int HISTO_LENGTH = 30;
 
   ORBmatcher(float nnratio = 0.6f, bool checkOri = true, int device = 0) : mfNNratio(nnratio), mbCheckOrientation(checkOri), device_(device) {
-    if (device < 0 || device >= kMaxDevices) throw std::runtime_error("ORBmatcher: bad device");
+    if (device < 0 || device >= morb_adapter::kMaxDevices) throw std::runtime_error("ORBmatcher: bad device");
     if (morb_matcher_create(&h_, device) != MORB_OK) throw std::runtime_error(std::string("morb_matcher_create: ") + morb_last_error());
   }
   ~ORBmatcher() { morb_matcher_destroy(h_); }
@@ -111,32 +112,31 @@ class ORBmatcher {
                          float thFarPoints = 50.f, float viewingCosLimit = 0.5f) {
     const int N = F.N, M = mps.n;
     if (N <= 0 || M <= 0) { matchF.assign(N > 0 ? N : 0, -1); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    s.kp[0].assign(F.mvKeysUn, N);
-    s.u8[0].assign(F.mDescriptors, (size_t)N * 32);
-    if (F.mvuRight) s.f32[0].assign(F.mvuRight, N);
-    s.u8[1].resize(N);
-    if (F.hasTrackedMapPoint) s.u8[1].upload(F.hasTrackedMapPoint, N); else s.u8[1].fill_bytes(0);
-    const int one = 0, cnt = N, nmp = M;
-    s.i32[0].assign(&one, 1); s.i32[1].assign(&cnt, 1); s.i32[2].assign(&nmp, 1); s.i32[3].resize(1); s.i32[3].fill_bytes(0);
-    s.f32[1].assign(F.mRcw, 9); s.f32[2].assign(F.mtcw, 3); s.f32[3].assign(F.mOw, 3); s.f32[4].assign(mps.worldPos, (size_t)M * 3);
-    s.f32[5].assign(mps.normal, (size_t)M * 3); s.f32[6].assign(mps.maxDistance, M); s.f32[7].assign(mps.minDistance, M);
-    for (int k = 8; k <= 12; ++k) s.f32[k].resize(M);   // projX, projY, projXR, depth, viewCos
-    s.u8[2].resize(M); s.u8[3].assign(mps.isBad, M); s.u8[4].assign(mps.hasObservations, M); s.u8[5].assign(mps.descriptor, (size_t)M * 32);
-    s.i32[4].resize(M); s.i32[5].resize(N);
-    if ((int)matchF.size() == N) s.i32[5].upload(matchF.data(), N); else s.i32[5].fill_bytes(0xFF);   // -1
-    check(morb_is_in_frustum_batch(h_, &F.params, 1, s.f32[1].get(), s.f32[2].get(), s.f32[3].get(), M, s.i32[2].get(), s.f32[4].get(), s.f32[5].get(),
-                                   s.f32[6].get(), s.f32[7].get(), viewingCosLimit, s.u8[2].get(), s.f32[8].get(), s.f32[9].get(), s.f32[10].get(),
-                                   s.f32[11].get(), s.i32[4].get(), s.f32[12].get(), nullptr));
-    check(morb_search_by_projection_mps_batch(h_, &F.params, 1, s.i32[0].get(), N, s.i32[1].get(), s.kp[0].get(), s.u8[0].get(),
-                                              F.mvuRight ? s.f32[0].get() : nullptr, s.u8[1].get(), M, s.i32[2].get(), s.u8[2].get(), s.u8[3].get(),
-                                              s.f32[11].get(), s.f32[8].get(), s.f32[9].get(), s.f32[10].get(), s.i32[4].get(), s.f32[12].get(),
-                                              s.u8[5].get(), s.u8[4].get(), th, bFarPoints ? 1 : 0, thFarPoints, mfNNratio, s.i32[5].get(),
-                                              s.i32[3].get(), nullptr));
-    sync();
-    matchF = s.i32[5].to_host();
-    return s.i32[3].to_host()[0];
+    Call c(device_, morb_matcher_stream(h_));
+    const int img = 0;
+    const int *d_fImg = c.in(&img, 1), *d_count = c.in(&N, 1);
+    const morb_keypoint* d_kps = c.in(F.mvKeysUn, N);
+    const uint8_t* d_desc = c.in(F.mDescriptors, (size_t)N * 32);
+    const float* d_uRight = F.mvuRight ? c.in(F.mvuRight, N) : nullptr;
+    const uint8_t* d_blocked = F.hasTrackedMapPoint ? c.in(F.hasTrackedMapPoint, N) : c.out_filled<uint8_t>(N, 0);
+    const float *d_Rcw = c.in(F.mRcw, 9), *d_tcw = c.in(F.mtcw, 3), *d_Ow = c.in(F.mOw, 3);
+    const int* d_nMP = c.in(&M, 1);
+    const float *d_Pw = c.in(mps.worldPos, (size_t)M * 3), *d_normal = c.in(mps.normal, (size_t)M * 3), *d_maxDist = c.in(mps.maxDistance, M);
+    const float* d_minDist = c.in(mps.minDistance, M);
+    const uint8_t *d_isBad = c.in(mps.isBad, M), *d_mpDesc = c.in(mps.descriptor, (size_t)M * 32), *d_mpHasObs = c.in(mps.hasObservations, M);
+    uint8_t* d_inView = c.out<uint8_t>(M);   // what isInFrustum leaves in the map points
+    float *d_projX = c.out<float>(M), *d_projY = c.out<float>(M), *d_projXR = c.out<float>(M), *d_depth = c.out<float>(M), *d_viewCos = c.out<float>(M);
+    int* d_level = c.out<int>(M);
+    int* d_matchF = (int)matchF.size() == N ? c.in(matchF.data(), N) : c.out_filled<int>(N, 0xFF);   // -1
+    int* d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_is_in_frustum_batch(h_, &F.params, 1, d_Rcw, d_tcw, d_Ow, M, d_nMP, d_Pw, d_normal, d_maxDist, d_minDist, viewingCosLimit, d_inView,
+                                   d_projX, d_projY, d_projXR, d_depth, d_level, d_viewCos, nullptr));
+    check(morb_search_by_projection_mps_batch(h_, &F.params, 1, d_fImg, N, d_count, d_kps, d_desc, d_uRight, d_blocked, M, d_nMP, d_inView, d_isBad,
+                                              d_depth, d_projX, d_projY, d_projXR, d_level, d_viewCos, d_mpDesc, d_mpHasObs, th, bFarPoints ? 1 : 0,
+                                              thFarPoints, mfNNratio, d_matchF, d_nmatches, nullptr));
+    c.wait();
+    matchF = c.fetch(d_matchF, N);
+    return c.fetch(d_nmatches, 1)[0];
   }
 
   // int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono)  (ORBmatcher.h:51-52,
@@ -146,30 +146,28 @@ class ORBmatcher {
   int SearchByProjection(const FrameView& Cur, const FrameView& Last, std::vector<int>& matchCur, float th, bool bMono) {
     const int N = Cur.N, NL = Last.N;
     if (N <= 0 || NL <= 0) { matchCur.assign(N > 0 ? N : 0, -1); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&Cur, &Last});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&Cur, &Last});
+    const int cap = pool.cap;
     // :1536-1539: tlc = Tlw * twc; forward / backward motion widens the octave range
     float tlc2 = Last.mtcw[2];
     for (int k = 0; k < 3; ++k) tlc2 += Last.mRcw[6 + k] * Cur.mOw[k];
     const uint8_t fwd = (tlc2 > Cur.params.mb && !bMono) ? 1 : 0, bwd = (-tlc2 > Cur.params.mb && !bMono) ? 1 : 0;
     const int cur = 0, last = 1;
-    s.i32[2].assign(&cur, 1); s.i32[3].assign(&last, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0);
-    s.u8[2].assign(&fwd, 1); s.u8[3].assign(&bwd, 1);
-    s.f32[1].assign(Cur.Tcw, 7);
-    up_row(s.u8[4], Cur.hasTrackedMapPoint, N, cap, 1);                  // curBlocked
-    up_row(s.u8[5], Last.hasMapPoint, NL, cap, 1);                       // lastValid
-    up_row(s.f32[2], Last.mpWorldPos, NL, cap, 3);
-    up_row(s.u8[6], Last.mpDescriptor, NL, cap, 32);
-    up_row(s.u8[7], Last.mpHasObservations, NL, cap, 1);
-    init_match(s.i32[5], matchCur, N, cap);
-    check(morb_search_by_projection_last_batch(h_, &Cur.params, 1, s.i32[2].get(), s.i32[3].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(),
-                                               Cur.mvuRight ? s.f32[0].get() : nullptr, s.u8[4].get(), s.f32[1].get(), s.u8[5].get(), s.f32[2].get(),
-                                               s.u8[6].get(), s.u8[7].get(), th, s.u8[2].get(), s.u8[3].get(), mbCheckOrientation ? 1 : 0,
-                                               s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    matchCur = s.i32[5].to_host(); matchCur.resize(N);
-    return s.i32[4].to_host()[0];
+    const int *d_curImg = c.in(&cur, 1), *d_lastImg = c.in(&last, 1);
+    const uint8_t* d_curBlocked = c.in_rows(Cur.hasTrackedMapPoint, N, cap, 1);
+    const float* d_Tcw = c.in(Cur.Tcw, 7);
+    const uint8_t* d_lastValid = c.in_rows(Last.hasMapPoint, NL, cap, 1);
+    const float* d_lastXw = c.in_rows(Last.mpWorldPos, NL, cap, 3);
+    const uint8_t *d_lastMPdesc = c.in_rows(Last.mpDescriptor, NL, cap, 32), *d_lastMPhasObs = c.in_rows(Last.mpHasObservations, NL, cap, 1);
+    const uint8_t *d_bForward = c.in(&fwd, 1), *d_bBackward = c.in(&bwd, 1);
+    int *d_matchCur = in_match(c, matchCur, N, cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_by_projection_last_batch(h_, &Cur.params, 1, d_curImg, d_lastImg, cap, pool.count, pool.kps, pool.desc,
+                                               Cur.mvuRight ? pool.uRight : nullptr, d_curBlocked, d_Tcw, d_lastValid, d_lastXw, d_lastMPdesc,
+                                               d_lastMPhasObs, th, d_bForward, d_bBackward, mbCheckOrientation ? 1 : 0, d_matchCur, d_nmatches, nullptr));
+    c.wait();
+    matchCur = c.fetch(d_matchCur, cap); matchCur.resize(N);
+    return c.fetch(d_nmatches, 1)[0];
   }
 
   // int SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th, const int ORBdist)
@@ -182,32 +180,32 @@ class ORBmatcher {
                          float th, int ORBdist, const float* curCam8 = nullptr, int curNLeft = -1) {
     const int N = Cur.N, NK = KF.N;
     if (N <= 0 || NK <= 0) { matchCur.assign(N > 0 ? N : 0, -1); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&Cur, &KF});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&Cur, &KF});
+    const int cap = pool.cap;
     std::vector<uint8_t> kfValid(NK);
     for (int i = 0; i < NK; ++i) kfValid[i] = (KF.hasMapPoint && KF.hasMapPoint[i] && !(i < (int)alreadyFound.size() && alreadyFound[i])) ? 1 : 0;
     const int cur = 0, kf = 1;
-    s.i32[2].assign(&cur, 1); s.i32[3].assign(&kf, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0);
-    s.f32[1].assign(Cur.Tcw, 7); s.f32[2].assign(Cur.mOw, 3);
-    up_row(s.u8[2], Cur.hasMapPoint, N, cap, 1);
-    up_row(s.u8[3], kfValid.data(), NK, cap, 1);
-    up_row(s.f32[3], KF.mpWorldPos, NK, cap, 3); up_row(s.f32[4], KF.mpMaxDistance, NK, cap, 1); up_row(s.f32[5], KF.mpMinDistance, NK, cap, 1);
-    up_row(s.u8[4], KF.mpDescriptor, NK, cap, 32);
-    init_match(s.i32[5], matchCur, N, cap);
+    const int *d_curImg = c.in(&cur, 1), *d_kfImg = c.in(&kf, 1);
+    const uint8_t* d_curHasMP = c.in_rows(Cur.hasMapPoint, N, cap, 1);
+    const float *d_Tcw = c.in(Cur.Tcw, 7), *d_Ow = c.in(Cur.mOw, 3);
+    const uint8_t* d_kfValid = c.in_rows(kfValid.data(), NK, cap, 1);
+    const float *d_Xw = c.in_rows(KF.mpWorldPos, NK, cap, 3), *d_maxDist = c.in_rows(KF.mpMaxDistance, NK, cap, 1);
+    const float* d_minDist = c.in_rows(KF.mpMinDistance, NK, cap, 1);
+    const uint8_t* d_mpDesc = c.in_rows(KF.mpDescriptor, NK, cap, 32);
+    int *d_matchCur = in_match(c, matchCur, N, cap), *d_nmatches = c.out_filled<int>(1, 0);
     if (curCam8 && curNLeft >= 0) {
-      s.i32[6].assign(&curNLeft, 1);
-      check(morb_search_by_projection_kf_rig_batch(h_, &Cur.params, curCam8, 1, s.i32[2].get(), s.i32[3].get(), s.i32[6].get(), cap, s.i32[0].get(),
-                                                   s.kp[0].get(), s.u8[0].get(), s.u8[2].get(), s.f32[1].get(), s.f32[2].get(), s.u8[3].get(),
-                                                   s.f32[3].get(), s.f32[4].get(), s.f32[5].get(), s.u8[4].get(), th, ORBdist,
-                                                   mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
+      const int* d_nLeftCur = c.in(&curNLeft, 1);
+      check(morb_search_by_projection_kf_rig_batch(h_, &Cur.params, curCam8, 1, d_curImg, d_kfImg, d_nLeftCur, cap, pool.count, pool.kps, pool.desc,
+                                                   d_curHasMP, d_Tcw, d_Ow, d_kfValid, d_Xw, d_maxDist, d_minDist, d_mpDesc, th, ORBdist,
+                                                   mbCheckOrientation ? 1 : 0, d_matchCur, d_nmatches, nullptr));
     } else
-    check(morb_search_by_projection_kf_batch(h_, &Cur.params, 1, s.i32[2].get(), s.i32[3].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(),
-                                             s.u8[2].get(), s.f32[1].get(), s.f32[2].get(), s.u8[3].get(), s.f32[3].get(), s.f32[4].get(), s.f32[5].get(),
-                                             s.u8[4].get(), th, ORBdist, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    matchCur = s.i32[5].to_host(); matchCur.resize(N);
-    return s.i32[4].to_host()[0];
+    check(morb_search_by_projection_kf_batch(h_, &Cur.params, 1, d_curImg, d_kfImg, cap, pool.count, pool.kps, pool.desc, d_curHasMP, d_Tcw, d_Ow,
+                                             d_kfValid, d_Xw, d_maxDist, d_minDist, d_mpDesc, th, ORBdist, mbCheckOrientation ? 1 : 0, d_matchCur,
+                                             d_nmatches, nullptr));
+    c.wait();
+    matchCur = c.fetch(d_matchCur, cap); matchCur.resize(N);
+    return c.fetch(d_nmatches, 1)[0];
   }
 
   // int SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th,
@@ -231,32 +229,32 @@ class ORBmatcher {
   // reference keyframe, relocalisation).  vpMapPointMatches[j] = keyframe feature whose map point is matched to frame feature j, or -1.
   int SearchByBoW(const KeyFrameView& KF, const FrameView& F, std::vector<int>& vpMapPointMatches) {
     if (KF.N <= 0 || F.N <= 0) { vpMapPointMatches.assign(F.N > 0 ? F.N : 0, -1); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&KF, &F});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&KF, &F});
     const int kf = 0, fr = 1;
-    s.i32[2].assign(&kf, 1); s.i32[3].assign(&fr, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap);
-    check(morb_search_by_bow_batch(h_, 1, s.i32[2].get(), s.i32[3].get(), 2, s.kp[0].get(), s.u8[0].get(), s.i32[1].get(), s.i32[0].get(), s.u8[1].get(),
-                                   cap, mfNNratio, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    vpMapPointMatches = s.i32[5].to_host(); vpMapPointMatches.resize(F.N);
-    return s.i32[4].to_host()[0];
+    const int *d_kfImg = c.in(&kf, 1), *d_fImg = c.in(&fr, 1);
+    int *d_matchF = c.out<int>(pool.cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_by_bow_batch(h_, 1, d_kfImg, d_fImg, 2, pool.kps, pool.desc, pool.node, pool.count, pool.hasMP, pool.cap, mfNNratio,
+                                   mbCheckOrientation ? 1 : 0, d_matchF, d_nmatches, nullptr));
+    c.wait();
+    vpMapPointMatches = c.fetch(d_matchF, pool.cap); vpMapPointMatches.resize(F.N);
+    return c.fetch(d_nmatches, 1)[0];
   }
   // int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)  (ORBmatcher.h:80-81, ORBmatcher.cc:702-819; loop closing).
   // vpMatches12[i1] = feature of pKF2 whose map point is matched to feature i1 of pKF1, or -1.
   int SearchByBoW(const KeyFrameView& KF1, const KeyFrameView& KF2, std::vector<int>& vpMatches12) {
     if (KF1.N <= 0 || KF2.N <= 0) { vpMatches12.assign(KF1.N > 0 ? KF1.N : 0, -1); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&KF1, &KF2});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&KF1, &KF2});
     const int a = 0, b = 1;
     const int nv[2] = {KF1.nValid >= 0 ? KF1.nValid : KF1.N, KF2.nValid >= 0 ? KF2.nValid : KF2.N};
-    s.i32[2].assign(&a, 1); s.i32[3].assign(&b, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap); s.i32[6].assign(nv, 2);
-    check(morb_search_by_bow_kfkf_batch(h_, 1, s.i32[2].get(), s.i32[3].get(), s.i32[6].get(), 2, s.kp[0].get(), s.u8[0].get(), s.i32[1].get(),
-                                        s.i32[0].get(), s.u8[1].get(), cap, mfNNratio, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    vpMatches12 = s.i32[5].to_host(); vpMatches12.resize(KF1.N);
-    return s.i32[4].to_host()[0];
+    const int *d_kf1Img = c.in(&a, 1), *d_kf2Img = c.in(&b, 1), *d_nValid = c.in(nv, 2);
+    int *d_match12 = c.out<int>(pool.cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_by_bow_kfkf_batch(h_, 1, d_kf1Img, d_kf2Img, d_nValid, 2, pool.kps, pool.desc, pool.node, pool.count, pool.hasMP, pool.cap,
+                                        mfNNratio, mbCheckOrientation ? 1 : 0, d_match12, d_nmatches, nullptr));
+    c.wait();
+    vpMatches12 = c.fetch(d_match12, pool.cap); vpMatches12.resize(KF1.N);
+    return c.fetch(d_nmatches, 1)[0];
   }
 
   // int SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12, int windowSize)
@@ -264,20 +262,22 @@ class ORBmatcher {
   int SearchForInitialization(const FrameView& F1, const FrameView& F2, std::vector<float>& vbPrevMatched, std::vector<int>& vnMatches12,
                               int windowSize = 10) {
     if (F1.N <= 0 || F2.N <= 0) { vnMatches12.assign(F1.N > 0 ? F1.N : 0, -1); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&F1, &F2});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&F1, &F2});
+    const int cap = pool.cap;
     const int a = 0, b = 1;
-    s.i32[2].assign(&a, 1); s.i32[3].assign(&b, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap);
+    const int *d_img1 = c.in(&a, 1), *d_img2 = c.in(&b, 1);
     std::vector<float> prev((size_t)cap * 2, 0.f);
     std::copy(vbPrevMatched.begin(), vbPrevMatched.begin() + std::min(vbPrevMatched.size(), (size_t)F1.N * 2), prev.begin());
-    s.f32[1].assign(prev.data(), prev.size());
-    check(morb_search_for_initialization_batch(h_, &F2.params, 1, s.i32[2].get(), s.i32[3].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(),
-                                               s.f32[1].get(), windowSize, mfNNratio, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    vnMatches12 = s.i32[5].to_host(); vnMatches12.resize(F1.N);
-    prev = s.f32[1].to_host(); vbPrevMatched.assign(prev.begin(), prev.begin() + (size_t)F1.N * 2);
-    return s.i32[4].to_host()[0];
+    float* d_prevMatched = c.in(prev.data(), prev.size());
+    int *d_matches12 = c.out<int>(cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_for_initialization_batch(h_, &F2.params, 1, d_img1, d_img2, cap, pool.count, pool.kps, pool.desc, d_prevMatched, windowSize,
+                                               mfNNratio, mbCheckOrientation ? 1 : 0, d_matches12, d_nmatches, nullptr));
+    c.wait();
+    vnMatches12 = c.fetch(d_matches12, cap); vnMatches12.resize(F1.N);
+    c.fetch(d_prevMatched, prev.data(), prev.size());
+    vbPrevMatched.assign(prev.begin(), prev.begin() + (size_t)F1.N * 2);
+    return c.fetch(d_nmatches, 1)[0];
   }
 
   // int SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, vector<pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo, bool bCoarse)
@@ -288,19 +288,19 @@ class ORBmatcher {
                              std::vector<std::pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo, bool bCoarse = false) {
     vMatchedPairs.clear();
     if (KF1.N <= 0 || KF2.N <= 0) return 0;
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&KF1, &KF2});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&KF1, &KF2});
     const int a = 0, b = 1;
-    s.i32[2].assign(&a, 1); s.i32[3].assign(&b, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap);
-    check(morb_search_for_triangulation_batch(h_, &KF1.params, 1, s.i32[2].get(), s.i32[3].get(), 2, cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(),
-                                              s.i32[1].get(), s.u8[1].get(), (KF1.mvuRight || KF2.mvuRight) ? s.f32[0].get() : nullptr, R12, t12, ep,
-                                              bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    const std::vector<int> m12 = s.i32[5].to_host();
+    const int *d_img1 = c.in(&a, 1), *d_img2 = c.in(&b, 1);
+    int *d_match12 = c.out<int>(pool.cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_for_triangulation_batch(h_, &KF1.params, 1, d_img1, d_img2, 2, pool.cap, pool.count, pool.kps, pool.desc, pool.node, pool.hasMP,
+                                              (KF1.mvuRight || KF2.mvuRight) ? pool.uRight : nullptr, R12, t12, ep, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0,
+                                              mbCheckOrientation ? 1 : 0, d_match12, d_nmatches, nullptr));
+    c.wait();
+    const std::vector<int> m12 = c.fetch(d_match12, pool.cap);
     for (int i = 0; i < KF1.N; ++i)
       if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);   // :1030-1036: ascending feature of pKF1
-    return s.i32[4].to_host()[0];
+    return c.fetch(d_nmatches, 1)[0];
   }
 
   // int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const Sophus::Sim3f& S12, const float th)
@@ -310,9 +310,9 @@ class ORBmatcher {
   int SearchBySim3(const KeyFrameView& KF1, const KeyFrameView& KF2, std::vector<int>& vpMatches12, const float S12[7], const float S21[7], float th) {
     const int N1 = KF1.N, N2 = KF2.N;
     if (N1 <= 0 || N2 <= 0) return 0;
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&KF1, &KF2});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&KF1, &KF2});
+    const int cap = pool.cap;
     if ((int)vpMatches12.size() != N1) vpMatches12.assign(N1, -1);
     std::vector<uint8_t> v1(N1), v2(N2);
     std::vector<uint8_t> already2(N2, 0);
@@ -320,28 +320,30 @@ class ORBmatcher {
     for (int i = 0; i < N1; ++i) v1[i] = (KF1.hasMapPoint && KF1.hasMapPoint[i] && vpMatches12[i] < 0) ? 1 : 0;
     for (int i = 0; i < N2; ++i) v2[i] = (KF2.hasMapPoint && KF2.hasMapPoint[i] && !already2[i]) ? 1 : 0;
     const int a = 0, b = 1;
-    s.i32[2].assign(&a, 1); s.i32[3].assign(&b, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap); s.i32[6].resize(cap); s.i32[7].resize(cap);
-    s.f32[1].assign(KF1.Tcw, 7); s.f32[2].assign(KF2.Tcw, 7); s.f32[3].assign(S12, 7); s.f32[4].assign(S21, 7);
-    up_row(s.u8[2], v1.data(), N1, cap, 1); up_row(s.f32[5], KF1.mpWorldPos, N1, cap, 3); up_row(s.f32[6], KF1.mpMaxDistance, N1, cap, 1);
-    up_row(s.f32[7], KF1.mpMinDistance, N1, cap, 1); up_row(s.u8[3], KF1.mpDescriptor, N1, cap, 32);
-    up_row(s.u8[4], v2.data(), N2, cap, 1); up_row(s.f32[8], KF2.mpWorldPos, N2, cap, 3); up_row(s.f32[9], KF2.mpMaxDistance, N2, cap, 1);
-    up_row(s.f32[10], KF2.mpMinDistance, N2, cap, 1); up_row(s.u8[5], KF2.mpDescriptor, N2, cap, 32);
+    const int *d_kf1Img = c.in(&a, 1), *d_kf2Img = c.in(&b, 1);
+    const float *d_T1w = c.in(KF1.Tcw, 7), *d_T2w = c.in(KF2.Tcw, 7), *d_S12 = c.in(S12, 7), *d_S21 = c.in(S21, 7);
+    const uint8_t* d_valid1 = c.in_rows(v1.data(), N1, cap, 1);
+    const float *d_Pw1 = c.in_rows(KF1.mpWorldPos, N1, cap, 3), *d_maxDist1 = c.in_rows(KF1.mpMaxDistance, N1, cap, 1);
+    const float* d_minDist1 = c.in_rows(KF1.mpMinDistance, N1, cap, 1);
+    const uint8_t *d_mpDesc1 = c.in_rows(KF1.mpDescriptor, N1, cap, 32), *d_valid2 = c.in_rows(v2.data(), N2, cap, 1);
+    const float *d_Pw2 = c.in_rows(KF2.mpWorldPos, N2, cap, 3), *d_maxDist2 = c.in_rows(KF2.mpMaxDistance, N2, cap, 1);
+    const float* d_minDist2 = c.in_rows(KF2.mpMinDistance, N2, cap, 1);
+    const uint8_t* d_mpDesc2 = c.in_rows(KF2.mpDescriptor, N2, cap, 32);
+    int *d_vnMatch1 = c.out<int>(cap), *d_vnMatch2 = c.out<int>(cap), *d_match12 = c.out<int>(cap), *d_nFound = c.out_filled<int>(1, 0);
     if (KF1.NLeft >= 0 || KF2.NLeft >= 0) {   // rig keyframes: the candidates are the left features (a keyframe without a right camera: all of them)
       const int nl1 = KF1.NLeft >= 0 ? KF1.NLeft : N1, nl2 = KF2.NLeft >= 0 ? KF2.NLeft : N2;
-      rigI32(0).assign(&nl1, 1); rigI32(1).assign(&nl2, 1);
-      check(morb_search_by_sim3_rig_batch(h_, &KF1.params, 1, s.i32[2].get(), s.i32[3].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(), s.f32[1].get(),
-                                          s.f32[2].get(), s.f32[3].get(), s.f32[4].get(), s.u8[2].get(), s.f32[5].get(), s.f32[6].get(), s.f32[7].get(),
-                                          s.u8[3].get(), s.u8[4].get(), s.f32[8].get(), s.f32[9].get(), s.f32[10].get(), s.u8[5].get(), th, rigI32(0).get(),
-                                          rigI32(1).get(), s.i32[5].get(), s.i32[6].get(), s.i32[7].get(), s.i32[4].get(), nullptr));
+      const int *d_nLeft1 = c.in(&nl1, 1), *d_nLeft2 = c.in(&nl2, 1);
+      check(morb_search_by_sim3_rig_batch(h_, &KF1.params, 1, d_kf1Img, d_kf2Img, cap, pool.count, pool.kps, pool.desc, d_T1w, d_T2w, d_S12, d_S21,
+                                          d_valid1, d_Pw1, d_maxDist1, d_minDist1, d_mpDesc1, d_valid2, d_Pw2, d_maxDist2, d_minDist2, d_mpDesc2, th,
+                                          d_nLeft1, d_nLeft2, d_vnMatch1, d_vnMatch2, d_match12, d_nFound, nullptr));
     } else
-    check(morb_search_by_sim3_batch(h_, &KF1.params, 1, s.i32[2].get(), s.i32[3].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(), s.f32[1].get(),
-                                    s.f32[2].get(), s.f32[3].get(), s.f32[4].get(), s.u8[2].get(), s.f32[5].get(), s.f32[6].get(), s.f32[7].get(),
-                                    s.u8[3].get(), s.u8[4].get(), s.f32[8].get(), s.f32[9].get(), s.f32[10].get(), s.u8[5].get(), th, s.i32[5].get(),
-                                    s.i32[6].get(), s.i32[7].get(), s.i32[4].get(), nullptr));
-    sync();
-    const std::vector<int> m12 = s.i32[7].to_host();
+    check(morb_search_by_sim3_batch(h_, &KF1.params, 1, d_kf1Img, d_kf2Img, cap, pool.count, pool.kps, pool.desc, d_T1w, d_T2w, d_S12, d_S21, d_valid1,
+                                    d_Pw1, d_maxDist1, d_minDist1, d_mpDesc1, d_valid2, d_Pw2, d_maxDist2, d_minDist2, d_mpDesc2, th, d_vnMatch1,
+                                    d_vnMatch2, d_match12, d_nFound, nullptr));
+    c.wait();
+    const std::vector<int> m12 = c.fetch(d_match12, cap);
     for (int i = 0; i < N1; ++i) if (m12[i] >= 0) vpMatches12[i] = m12[i];   // :1506-1515
-    return s.i32[4].to_host()[0];
+    return c.fetch(d_nFound, 1)[0];
   }
 
   // int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th, const bool bRight)  (ORBmatcher.h:107-108,
@@ -405,40 +407,18 @@ class ORBmatcher {
   int Fuse(KF* pKF, Sim3& Scw, const std::vector<MP*>& vpPoints, float th, std::vector<MP*>& vpReplacePoint);
 
  protected:
-  static constexpr int kMaxDevices = 16;
-  // grow-only device staging, one set per host thread and device (the reference constructs a matcher per call; the buffers outlive it)
-  struct Staging {
-    morb_adapter::DeviceBuffer<morb_keypoint> kp[1];
-    morb_adapter::DeviceBuffer<uint8_t> u8[8];
-    morb_adapter::DeviceBuffer<float> f32[13];
-    morb_adapter::DeviceBuffer<int> i32[8];
-    morb_adapter::DeviceBuffer<int> rig[2];   // fisheye forms: mvRightToLeftMatch, mnTrackScaleLevelR
-  };
-  morb_adapter::DeviceBuffer<int>& rigI32(int k) { return staging().rig[k]; }
+  using Call = morb_adapter::CallStaging;   // one per method call: device, the handle's stream, this thread's staging (device_buffer.h)
   template <class KF, class Sim3, class MP>
   int sim3_projection_ref(KF* pKF, Sim3& Scw, const std::vector<MP*>& vpPoints, const std::vector<KF*>* vpPointsKFs, std::vector<MP*>& vpMatched,
                           std::vector<KF*>* vpMatchedKF, int th, float ratioHamming);
-  Staging& staging() {
-    morb_adapter::hip_check(hipSetDevice(device_), "hipSetDevice");   // the buffers below and the handle's kernels live on device_
-    static thread_local Staging per_device[kMaxDevices];
-    return per_device[device_];
-  }
-  static void sync() { morb_adapter::sync_current_stream(); }   // the handle's stream only (a device-wide wait would also wait for LocalMapping's optimizer)
   static void check(int rc) { if (rc < 0) throw std::runtime_error(morb_last_error()); }
-  // row r (of capacity cap elements x width) of a pooled device array <- n elements of a host array (NULL = zeros)
-  template <typename T>
-  static void up_row(morb_adapter::DeviceBuffer<T>& d, const T* host, int n, int cap, int width) {
-    std::vector<T> tmp((size_t)cap * width, T());
-    if (host) std::copy(host, host + (size_t)n * width, tmp.begin());
-    d.assign(tmp.data(), tmp.size());
-  }
-  static void init_match(morb_adapter::DeviceBuffer<int>& d, const std::vector<int>& m, int N, int cap) {
-    std::vector<int> tmp(cap, -1);
-    if ((int)m.size() == N) std::copy(m.begin(), m.end(), tmp.begin());
-    d.assign(tmp.data(), tmp.size());
-  }
-  // the pool the batched entry points index: image k = views[k]; kps, descriptors, counts, BoW nodes, hasMapPoint, uRight, [nimg][cap]
-  static int load_pool(Staging& s, std::initializer_list<const FrameView*> views) {
+  // a match table of cap entries: the caller's N assignments where it holds N, -1 everywhere else
+  static int* in_match(Call& c, const std::vector<int>& m, int N, int cap) { return c.in_rows((int)m.size() == N ? m.data() : nullptr, N, cap, 1, -1); }
+  // the pool the batched entry points index: image k = views[k], every array [nimg][cap]
+  struct Pool {   // count [nimg]; node = BoW node of a feature, -1 if none; uRight -1 where a view has none
+    int cap; const morb_keypoint* kps; const uint8_t *desc, *hasMP; const int *count, *node; const float* uRight;
+  };
+  static Pool load_pool(Call& c, std::initializer_list<const FrameView*> views) {
     int cap = 1;
     for (const FrameView* v : views) cap = std::max(cap, v->N);
     const int nimg = (int)views.size();
@@ -457,64 +437,67 @@ class ORBmatcher {
       if (v->mvuRight) std::copy(v->mvuRight, v->mvuRight + v->N, ur.begin() + (size_t)k * cap);
       ++k;
     }
-    s.kp[0].assign(kps.data(), kps.size()); s.u8[0].assign(desc.data(), desc.size()); s.u8[1].assign(has.data(), has.size());
-    s.i32[0].assign(count.data(), count.size()); s.i32[1].assign(node.data(), node.size()); s.f32[0].assign(ur.data(), ur.size());
-    return cap;
+    Pool p; p.cap = cap;
+    p.kps = c.in(kps.data(), kps.size()); p.desc = c.in(desc.data(), desc.size()); p.hasMP = c.in(has.data(), has.size());
+    p.count = c.in(count.data(), count.size()); p.node = c.in(node.data(), node.size()); p.uRight = c.in(ur.data(), ur.size());
+    return p;
   }
-  void load_points(Staging& s, const MapPointView& P) {   // u8[2] valid, f32[3] Pw, [4] normal, [5] maxDist, [6] minDist, u8[3] descriptors
-    const int M = P.n;
-    s.u8[2].assign(P.valid, M); s.f32[3].assign(P.worldPos, (size_t)M * 3); s.f32[4].assign(P.normal, (size_t)M * 3);
-    s.f32[5].assign(P.maxDistance, M); s.f32[6].assign(P.minDistance, M); s.u8[3].assign(P.descriptor, (size_t)M * 32);
+  struct Points { const uint8_t *valid, *desc; const float *Pw, *normal, *maxDist, *minDist; };
+  static Points load_points(Call& c, const MapPointView& P) {
+    const size_t M = P.n;
+    Points p; p.valid = c.in(P.valid, M); p.Pw = c.in(P.worldPos, M * 3); p.normal = c.in(P.normal, M * 3);
+    p.maxDist = c.in(P.maxDistance, M); p.minDist = c.in(P.minDistance, M); p.desc = c.in(P.descriptor, M * 32);
+    return p;
   }
   int sim3_projection(const KeyFrameView& KF, const Sim3View& Scw, const MapPointView& P, std::vector<int>& vpMatched, int th, float ratioHamming,
                       int manual) {
     const int N = KF.N, M = P.n;
     if ((int)vpMatched.size() != N) vpMatched.assign(N > 0 ? N : 0, -1);
     if (N <= 0 || M <= 0) return 0;
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&KF});
-    load_points(s, P);
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&KF});
+    const Points pts = load_points(c, P);
+    const int cap = pool.cap;
     std::vector<uint8_t> matched(cap, 0);
     for (int i = 0; i < N; ++i) matched[i] = vpMatched[i] >= 0 ? 1 : 0;
-    const int kf = 0, nmp = M;
-    s.i32[2].assign(&kf, 1); s.i32[3].assign(&nmp, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap);
-    s.f32[1].assign(Scw.Tcw, 7); s.f32[2].assign(Scw.Ow, 3); s.u8[4].assign(matched.data(), cap);
+    const int kf = 0;
+    const int* d_kfImg = c.in(&kf, 1);
+    const float *d_Tcw = c.in(Scw.Tcw, 7), *d_Ow = c.in(Scw.Ow, 3);
+    const int* d_nMP = c.in(&M, 1);
+    const uint8_t* d_matched = c.in(matched.data(), cap);
+    int *d_matchF = c.out<int>(cap), *d_nmatches = c.out_filled<int>(1, 0);
     if (KF.NLeft >= 0) {   // rig keyframe: left features, the left KB8 camera where the reference calls mpCamera->project
-      rigI32(0).assign(&KF.NLeft, 1);
-      check(morb_search_by_projection_sim3_rig_batch(h_, &KF.params, 1, s.i32[2].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(), s.f32[1].get(),
-                                                     s.f32[2].get(), M, s.i32[3].get(), s.u8[2].get(), s.f32[3].get(), s.f32[4].get(), s.f32[5].get(),
-                                                     s.f32[6].get(), s.u8[3].get(), s.u8[4].get(), th, ratioHamming, manual, KF.rigCam8, rigI32(0).get(),
-                                                     s.i32[5].get(), s.i32[4].get(), nullptr));
+      const int* d_nLeft = c.in(&KF.NLeft, 1);
+      check(morb_search_by_projection_sim3_rig_batch(h_, &KF.params, 1, d_kfImg, cap, pool.count, pool.kps, pool.desc, d_Tcw, d_Ow, M, d_nMP, pts.valid,
+                                                     pts.Pw, pts.normal, pts.maxDist, pts.minDist, pts.desc, d_matched, th, ratioHamming, manual,
+                                                     KF.rigCam8, d_nLeft, d_matchF, d_nmatches, nullptr));
     } else
-    check(morb_search_by_projection_sim3_batch(h_, &KF.params, 1, s.i32[2].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(), s.f32[1].get(),
-                                               s.f32[2].get(), M, s.i32[3].get(), s.u8[2].get(), s.f32[3].get(), s.f32[4].get(), s.f32[5].get(),
-                                               s.f32[6].get(), s.u8[3].get(), s.u8[4].get(), th, ratioHamming, manual, s.i32[5].get(), s.i32[4].get(),
+    check(morb_search_by_projection_sim3_batch(h_, &KF.params, 1, d_kfImg, cap, pool.count, pool.kps, pool.desc, d_Tcw, d_Ow, M, d_nMP, pts.valid, pts.Pw,
+                                               pts.normal, pts.maxDist, pts.minDist, pts.desc, d_matched, th, ratioHamming, manual, d_matchF, d_nmatches,
                                                nullptr));
-    sync();
-    const std::vector<int> mf = s.i32[5].to_host();
+    c.wait();
+    const std::vector<int> mf = c.fetch(d_matchF, cap);
     for (int i = 0; i < N; ++i) if (mf[i] >= 0) vpMatched[i] = mf[i];
-    return s.i32[4].to_host()[0];
+    return c.fetch(d_nmatches, 1)[0];
   }
   int fuse(const KeyFrameView& KF, const Sim3View& T, const MapPointView& P, std::vector<int>& bestIdx, std::vector<int>& bestDist, float th, int sim3Form,
            const RigSide* side = nullptr) {
     const int N = KF.N, M = P.n;
     bestIdx.assign(M > 0 ? M : 0, -1); bestDist.assign(M > 0 ? M : 0, 256);
     if (N <= 0 || M <= 0) return 0;
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));   // uploads, kernels, downloads: the handle's stream, never the null stream
-    Staging& s = staging();
-    const int cap = load_pool(s, {&KF});
-    load_points(s, P);
-    const int kf = 0, nmp = M;
-    s.i32[2].assign(&kf, 1); s.i32[3].assign(&nmp, 1); s.i32[5].resize(M); s.i32[6].resize(M);
-    s.f32[1].assign(T.Tcw, 7); s.f32[2].assign(T.Ow, 3);
-    if (side) { s.i32[4].assign(&side->jLo, 1); s.i32[7].assign(&side->jHi, 1); }
-    check(morb_fuse_batch(h_, &KF.params, 1, s.i32[2].get(), cap, s.i32[0].get(), s.kp[0].get(), s.u8[0].get(), (KF.mvuRight && !side) ? s.f32[0].get() : nullptr,
-                          s.f32[1].get(), s.f32[2].get(), side ? side->cam8 : nullptr, side ? s.i32[4].get() : nullptr, side ? s.i32[7].get() : nullptr, M,
-                          s.i32[3].get(), s.u8[2].get(), s.f32[3].get(), s.f32[4].get(),
-                          s.f32[5].get(), s.f32[6].get(), s.u8[3].get(), th, sim3Form, s.i32[5].get(), s.i32[6].get(), nullptr));
-    sync();
-    bestIdx = s.i32[5].to_host(); bestDist = s.i32[6].to_host();
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&KF});
+    const Points pts = load_points(c, P);
+    const int kf = 0;
+    const int* d_kfImg = c.in(&kf, 1);
+    const float *d_Tcw = c.in(T.Tcw, 7), *d_Ow = c.in(T.Ow, 3);
+    const int *d_jLo = side ? c.in(&side->jLo, 1) : nullptr, *d_jHi = side ? c.in(&side->jHi, 1) : nullptr, *d_nMP = c.in(&M, 1);
+    int *d_bestIdx = c.out<int>(M), *d_bestDist = c.out<int>(M);
+    check(morb_fuse_batch(h_, &KF.params, 1, d_kfImg, pool.cap, pool.count, pool.kps, pool.desc, (KF.mvuRight && !side) ? pool.uRight : nullptr, d_Tcw, d_Ow,
+                          side ? side->cam8 : nullptr, d_jLo, d_jHi, M, d_nMP, pts.valid, pts.Pw, pts.normal, pts.maxDist, pts.minDist, pts.desc, th,
+                          sim3Form, d_bestIdx, d_bestDist, nullptr));
+    c.wait();
+    bestIdx = c.fetch(d_bestIdx, M); bestDist = c.fetch(d_bestDist, M);
     int hits = 0;
     for (int i = 0; i < M; ++i) hits += bestIdx[i] >= 0 ? 1 : 0;
     return hits;

@@ -55,43 +55,45 @@ int ORBmatcher::SearchByProjection(FrameT& F, const std::vector<MP*>& vpMapPoint
     const auto d = p->GetDescriptor();
     std::memcpy(&desc[(size_t)j * 32], d.template ptr<uint8_t>(0), 32);
   }
-  morb_adapter::StreamScope scope_(morb_matcher_stream(h_));
-  Staging& s = staging();
-  const int zero = 0;
-  s.kp[0].assign(fs.kps.data(), N); s.u8[0].assign(fs.desc.data(), (size_t)N * 32); s.u8[1].assign(blocked.data(), N);
-  s.i32[0].assign(&zero, 1); s.i32[1].assign(&N, 1); s.i32[2].assign(&M, 1); s.i32[3].resize(1); s.i32[3].fill_bytes(0);
-  s.u8[2].assign(inL.data(), M); s.u8[3].assign(bad.data(), M); s.u8[4].assign(hasObs.data(), M); s.u8[5].assign(desc.data(), desc.size());
-  s.f32[11].assign(depth.data(), M); s.f32[8].assign(pxL.data(), M); s.f32[9].assign(pyL.data(), M); s.f32[12].assign(cosL.data(), M);
-  s.i32[4].assign(lvL.data(), M); s.i32[5].resize(N); s.i32[5].fill_bytes(0xFF);
+  Call c(device_, morb_matcher_stream(h_));
+  const int img = 0;
+  const int *d_fImg = c.in(&img, 1), *d_count = c.in(&N, 1);
+  const morb_keypoint* d_kps = c.in(fs.kps.data(), N);
+  const uint8_t *d_desc = c.in(fs.desc.data(), (size_t)N * 32), *d_blocked = c.in(blocked.data(), N);
+  const int* d_nMP = c.in(&M, 1);
+  const uint8_t *d_inViewL = c.in(inL.data(), M), *d_isBad = c.in(bad.data(), M);
+  const float *d_depth = c.in(depth.data(), M), *d_projXL = c.in(pxL.data(), M), *d_projYL = c.in(pyL.data(), M);
+  const int* d_levelL = c.in(lvL.data(), M);
+  const float* d_viewCosL = c.in(cosL.data(), M);
+  const uint8_t *d_mpDesc = c.in(desc.data(), desc.size()), *d_mpHasObs = c.in(hasObs.data(), M);
+  int* d_matchF = c.out_filled<int>(N, 0xFF);   // -1
+  int* d_nmatches = c.out_filled<int>(1, 0);
   if (!rig) {
-    if (fs.v.mvuRight) s.f32[0].assign(fs.v.mvuRight, N);
-    s.f32[10].assign(pxrL.data(), M);
-    check(morb_search_by_projection_mps_batch(h_, &fs.v.params, 1, s.i32[0].get(), N, s.i32[1].get(), s.kp[0].get(), s.u8[0].get(),
-                                              fs.v.mvuRight ? s.f32[0].get() : nullptr, s.u8[1].get(), M, s.i32[2].get(), s.u8[2].get(), s.u8[3].get(),
-                                              s.f32[11].get(), s.f32[8].get(), s.f32[9].get(), s.f32[10].get(), s.i32[4].get(), s.f32[12].get(),
-                                              s.u8[5].get(), s.u8[4].get(), th, bFarPoints ? 1 : 0, thFarPoints, mfNNratio, s.i32[5].get(),
-                                              s.i32[3].get(), nullptr));
+    const float *d_uRight = fs.v.mvuRight ? c.in(fs.v.mvuRight, N) : nullptr, *d_projXR = c.in(pxrL.data(), M);
+    check(morb_search_by_projection_mps_batch(h_, &fs.v.params, 1, d_fImg, N, d_count, d_kps, d_desc, d_uRight, d_blocked, M, d_nMP, d_inViewL, d_isBad,
+                                              d_depth, d_projXL, d_projYL, d_projXR, d_levelL, d_viewCosL, d_mpDesc, d_mpHasObs, th, bFarPoints ? 1 : 0,
+                                              thFarPoints, mfNNratio, d_matchF, d_nmatches, nullptr));
   } else {
     // :97-133, :142-206: left pass + right pass, stereo partners through mvLeftToRightMatch / mvRightToLeftMatch
     std::vector<int> l2r(N, -1), r2l(N, -1);
     for (int i = 0; i < (int)F.mvLeftToRightMatch.size() && i < N; ++i) l2r[i] = F.mvLeftToRightMatch[i];
     for (int i = 0; i < (int)F.mvRightToLeftMatch.size() && i < N; ++i) r2l[i] = F.mvRightToLeftMatch[i];
     const int nl = F.Nleft;
-    s.i32[6].assign(&nl, 1); s.i32[7].assign(l2r.data(), N);
-    morb_adapter::DeviceBuffer<int>& dR2L = rigI32(0); dR2L.assign(r2l.data(), N);
-    morb_adapter::DeviceBuffer<int>& dLvR = rigI32(1); dLvR.assign(lvR.data(), M);
-    s.u8[6].assign(inR.data(), M); s.f32[10].assign(pxR.data(), M); s.f32[7].assign(pyR.data(), M); s.f32[6].assign(cosR.data(), M);
-    check(morb_search_by_projection_mps_fisheye_batch(h_, &fs.v.params, 1, s.i32[0].get(), N, s.i32[1].get(), s.i32[6].get(), s.kp[0].get(), s.u8[0].get(),
-                                                      s.i32[7].get(), dR2L.get(), s.u8[1].get(), M, s.i32[2].get(), s.u8[2].get(), s.u8[6].get(), s.u8[3].get(),
-                                                      s.f32[11].get(), s.f32[8].get(), s.f32[9].get(), s.i32[4].get(), s.f32[12].get(), s.f32[10].get(),
-                                                      s.f32[7].get(), dLvR.get(), s.f32[6].get(), s.u8[5].get(), s.u8[4].get(), th, bFarPoints ? 1 : 0,
-                                                      thFarPoints, mfNNratio, s.i32[5].get(), s.i32[3].get(), nullptr));
+    const int *d_nLeft = c.in(&nl, 1), *d_l2r = c.in(l2r.data(), N), *d_r2l = c.in(r2l.data(), N);
+    const uint8_t* d_inViewR = c.in(inR.data(), M);
+    const float *d_projXR = c.in(pxR.data(), M), *d_projYR = c.in(pyR.data(), M);
+    const int* d_levelR = c.in(lvR.data(), M);
+    const float* d_viewCosR = c.in(cosR.data(), M);
+    check(morb_search_by_projection_mps_fisheye_batch(h_, &fs.v.params, 1, d_fImg, N, d_count, d_nLeft, d_kps, d_desc, d_l2r, d_r2l, d_blocked, M, d_nMP,
+                                                      d_inViewL, d_inViewR, d_isBad, d_depth, d_projXL, d_projYL, d_levelL, d_viewCosL, d_projXR, d_projYR,
+                                                      d_levelR, d_viewCosR, d_mpDesc, d_mpHasObs, th, bFarPoints ? 1 : 0, thFarPoints, mfNNratio, d_matchF,
+                                                      d_nmatches, nullptr));
   }
-  sync();
-  const std::vector<int> matchF = s.i32[5].to_host();
+  c.wait();
+  const std::vector<int> matchF = c.fetch(d_matchF, N);
   for (int i = 0; i < N; ++i)
     if (matchF[i] >= 0) F.mvpMapPoints[i] = vpMapPoints[matchF[i]];   // :132, :197
-  return s.i32[3].to_host()[0];
+  return c.fetch(d_nmatches, 1)[0];
 }
 
 // int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)  ORBmatcher.cc:1521-1733 (Tracking::TrackWithMotionModel)
@@ -112,25 +114,27 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame
     float c8[8], trl[7];
     morb_glue::cam8(CurrentFrame.mpCamera, c8);
     morb_glue::pose7(CurrentFrame.GetRelativePoseTrl(), trl);
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));
-    Staging& s = staging();
-    const int cap = load_pool(s, {&cur.v, &last.v});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&cur.v, &last.v});
+    const int cap = pool.cap;
     float tlc2 = last.v.mtcw[2];
     for (int k = 0; k < 3; ++k) tlc2 += last.v.mRcw[6 + k] * cur.v.mOw[k];   // :1536-1539
     const uint8_t fwd = (tlc2 > cur.v.params.mb && !bMono) ? 1 : 0, bwd = (-tlc2 > cur.v.params.mb && !bMono) ? 1 : 0;
     const int ci = 0, li = 1, nl = CurrentFrame.Nleft;
-    s.i32[2].assign(&ci, 1); s.i32[3].assign(&li, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[6].assign(&nl, 1);
-    s.u8[2].assign(&fwd, 1); s.u8[3].assign(&bwd, 1); s.f32[1].assign(cur.v.Tcw, 7);
-    up_row(s.u8[4], cur.v.hasTrackedMapPoint, N, cap, 1); up_row(s.u8[5], last.v.hasMapPoint, NL, cap, 1);
-    up_row(s.f32[2], last.v.mpWorldPos, NL, cap, 3); up_row(s.u8[6], last.v.mpDescriptor, NL, cap, 32); up_row(s.u8[7], last.v.mpHasObservations, NL, cap, 1);
-    init_match(s.i32[5], matchCur, N, cap);
-    check(morb_search_by_projection_last_fisheye_batch(h_, &cur.v.params, c8, trl, 1, s.i32[2].get(), s.i32[3].get(), s.i32[6].get(), cap, s.i32[0].get(),
-                                                       s.kp[0].get(), s.u8[0].get(), s.u8[4].get(), s.f32[1].get(), s.u8[5].get(), s.f32[2].get(), s.u8[6].get(),
-                                                       s.u8[7].get(), th, s.u8[2].get(), s.u8[3].get(), mbCheckOrientation ? 1 : 0, s.i32[5].get(),
-                                                       s.i32[4].get(), nullptr));
-    sync();
-    matchCur = s.i32[5].to_host(); matchCur.resize(N);
-    n = s.i32[4].to_host()[0];
+    const int *d_curImg = c.in(&ci, 1), *d_lastImg = c.in(&li, 1), *d_nLeftCur = c.in(&nl, 1);
+    const uint8_t* d_curBlocked = c.in_rows(cur.v.hasTrackedMapPoint, N, cap, 1);
+    const float* d_Tcw = c.in(cur.v.Tcw, 7);
+    const uint8_t* d_lastValid = c.in_rows(last.v.hasMapPoint, NL, cap, 1);
+    const float* d_lastXw = c.in_rows(last.v.mpWorldPos, NL, cap, 3);
+    const uint8_t *d_lastMPdesc = c.in_rows(last.v.mpDescriptor, NL, cap, 32), *d_lastMPhasObs = c.in_rows(last.v.mpHasObservations, NL, cap, 1);
+    const uint8_t *d_bForward = c.in(&fwd, 1), *d_bBackward = c.in(&bwd, 1);
+    int *d_matchCur = in_match(c, matchCur, N, cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_by_projection_last_fisheye_batch(h_, &cur.v.params, c8, trl, 1, d_curImg, d_lastImg, d_nLeftCur, cap, pool.count, pool.kps, pool.desc,
+                                                       d_curBlocked, d_Tcw, d_lastValid, d_lastXw, d_lastMPdesc, d_lastMPhasObs, th, d_bForward, d_bBackward,
+                                                       mbCheckOrientation ? 1 : 0, d_matchCur, d_nmatches, nullptr));
+    c.wait();
+    matchCur = c.fetch(d_matchCur, cap); matchCur.resize(N);
+    n = c.fetch(d_nmatches, 1)[0];
   }
   for (int i = 0; i < CurrentFrame.N; ++i)
     if (matchCur[i] >= 0) CurrentFrame.mvpMapPoints[i] = Last.mvpMapPoints[matchCur[i]];   // :1627, :1692
@@ -218,16 +222,16 @@ int ORBmatcher::SearchByBoW(KF* pKF, FrameT& F, std::vector<MP*>& vpMapPointMatc
   } else {
     // :262-299, :333-365: left and right candidates of a node ranked separately
     if (kf.v.N <= 0 || fr.v.N <= 0) { vpMapPointMatches.assign(F.N > 0 ? F.N : 0, static_cast<MP*>(NULL)); return 0; }
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));
-    Staging& s = staging();
-    const int cap = load_pool(s, {&kf.v, &fr.v});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&kf.v, &fr.v});
     const int ki = 0, fi = 1, nl = F.Nleft;
-    s.i32[2].assign(&ki, 1); s.i32[3].assign(&fi, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap); s.i32[6].assign(&nl, 1);
-    check(morb_search_by_bow_fisheye_batch(h_, 1, s.i32[2].get(), s.i32[3].get(), s.i32[6].get(), 2, s.kp[0].get(), s.u8[0].get(), s.i32[1].get(), s.i32[0].get(),
-                                           s.u8[1].get(), cap, mfNNratio, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    idx = s.i32[5].to_host(); idx.resize(F.N);
-    n = s.i32[4].to_host()[0];
+    const int *d_kfImg = c.in(&ki, 1), *d_fImg = c.in(&fi, 1), *d_nLeft = c.in(&nl, 1);
+    int *d_matchF = c.out<int>(pool.cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_by_bow_fisheye_batch(h_, 1, d_kfImg, d_fImg, d_nLeft, 2, pool.kps, pool.desc, pool.node, pool.count, pool.hasMP, pool.cap, mfNNratio,
+                                           mbCheckOrientation ? 1 : 0, d_matchF, d_nmatches, nullptr));
+    c.wait();
+    idx = c.fetch(d_matchF, pool.cap); idx.resize(F.N);
+    n = c.fetch(d_nmatches, 1)[0];
   }
   vpMapPointMatches.assign(F.N, static_cast<MP*>(NULL));   // :222
   for (int j = 0; j < F.N; ++j)
@@ -282,19 +286,19 @@ int ORBmatcher::SearchForTriangulation(KF* pKF1, KF* pKF2, std::vector<std::pair
     float T4[4][12], camL[8], camR[8];
     morb_glue::rt12(T1w * Tw2, T4[0]); morb_glue::rt12(T1w * Twr2, T4[1]); morb_glue::rt12(Tr1w * Tw2, T4[2]); morb_glue::rt12(Tr1w * Twr2, T4[3]);
     morb_glue::cam8(pKF1->mpCamera, camL); morb_glue::cam8(pKF1->mpCamera2, camR);
-    morb_adapter::StreamScope scope_(morb_matcher_stream(h_));
-    Staging& s = staging();
-    const int cap = load_pool(s, {&a.v, &b.v});
+    Call c(device_, morb_matcher_stream(h_));
+    const Pool pool = load_pool(c, {&a.v, &b.v});
     const int i1 = 0, i2 = 1, nl1 = pKF1->NLeft, nl2 = pKF2->NLeft;
-    s.i32[2].assign(&i1, 1); s.i32[3].assign(&i2, 1); s.i32[4].resize(1); s.i32[4].fill_bytes(0); s.i32[5].resize(cap); s.i32[6].assign(&nl1, 1); s.i32[7].assign(&nl2, 1);
-    check(morb_search_for_triangulation_fisheye_batch(h_, &a.v.params, 1, s.i32[2].get(), s.i32[3].get(), s.i32[6].get(), s.i32[7].get(), 2, cap, s.i32[0].get(),
-                                                      s.kp[0].get(), s.u8[0].get(), s.i32[1].get(), s.u8[1].get(), camL, camR, &T4[0][0], bOnlyStereo ? 1 : 0,
-                                                      bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, s.i32[5].get(), s.i32[4].get(), nullptr));
-    sync();
-    const std::vector<int> m12 = s.i32[5].to_host();
+    const int *d_img1 = c.in(&i1, 1), *d_img2 = c.in(&i2, 1), *d_nLeft1 = c.in(&nl1, 1), *d_nLeft2 = c.in(&nl2, 1);
+    int *d_match12 = c.out<int>(pool.cap), *d_nmatches = c.out_filled<int>(1, 0);
+    check(morb_search_for_triangulation_fisheye_batch(h_, &a.v.params, 1, d_img1, d_img2, d_nLeft1, d_nLeft2, 2, pool.cap, pool.count, pool.kps, pool.desc,
+                                                      pool.node, pool.hasMP, camL, camR, &T4[0][0], bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0,
+                                                      mbCheckOrientation ? 1 : 0, d_match12, d_nmatches, nullptr));
+    c.wait();
+    const std::vector<int> m12 = c.fetch(d_match12, pool.cap);
     for (int i = 0; i < a.v.N; ++i)
       if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);   // :1030-1036
-    return s.i32[4].to_host()[0];
+    return c.fetch(d_nmatches, 1)[0];
   }
   // :829-838
   const auto T1w = pKF1->GetPose();

@@ -116,36 +116,31 @@ class Optimizer {
  public:
   // static int PoseOptimization(Frame* pFrame)  Optimizer.h:86 -> number of inliers
   static int PoseOptimization(PoseOptimizationView& f, int device = 0) {
-    using morb_adapter::DeviceBuffer;
     if (f.N <= 0) return 0;
     const int N = f.N;
     Slot& o = slot(device, kTracking);
     std::lock_guard<std::mutex> lock(o.mu);   // one caller per handle at a time (Tracking's handle is not LocalMapping's: see slot())
-    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
-    morb_adapter::StreamScope scope_(morb_optimizer_stream(o.h));   // uploads, the kernel, downloads: this handle's stream, never the null stream
-    // per-thread, per-device staging buffers that only grow: Tracking calls this once per frame, and eight hipMalloc / hipFree pairs
-    // per call cost more than the optimisation itself
-    struct Staging { DeviceBuffer<uint8_t> has, outl; DeviceBuffer<float> obs, inv, Xw, pose; DeviceBuffer<int> nin, cnt, nl; };
-    static thread_local Staging per_device[kMaxDevices];
-    Staging& s = per_device[device];
-    s.has.assign(f.hasMapPoint, N); s.outl.resize(N);
+    Call c(device, morb_optimizer_stream(o.h));   // uploads, the kernel, downloads: this handle's stream, never the null stream
+    const int* d_count = c.in(&N, 1);
+    const uint8_t* d_hasMP = c.in(f.hasMapPoint, N);
+    const float *d_obs = c.in(f.obs, (size_t)N * 3), *d_invSigma2 = c.in(f.invSigma2, N), *d_Xw = c.in(f.worldPos, (size_t)N * 3);
+    float* d_pose = c.in(f.pose, 7);
     // mvbOutlier is only written for features that hold a map point (Optimizer.cc:817, :860): the others keep what they had
-    if ((int)f.mvbOutlier.size() == N) s.outl.upload(f.mvbOutlier.data(), N); else s.outl.fill_bytes(0);
-    s.obs.assign(f.obs, (size_t)N * 3); s.inv.assign(f.invSigma2, N); s.Xw.assign(f.worldPos, (size_t)N * 3); s.pose.assign(f.pose, 7);
-    s.nin.resize(1); s.cnt.assign(&N, 1);
+    uint8_t* d_outlier = (int)f.mvbOutlier.size() == N ? c.in(f.mvbOutlier.data(), N) : c.out_filled<uint8_t>(N, 0);
+    int* d_nInliers = c.out<int>(1);
     if (f.rig28) {
       float trl7[7];
       rot_to_pose7(f.rig28 + 16, trl7);
-      s.nl.assign(&f.nLeft, 1);
-      check(morb_pose_optimization_fisheye_batch(o.h, 1, N, s.cnt.get(), s.nl.get(), s.has.get(), s.obs.get(), s.inv.get(), s.Xw.get(), f.rig28, f.rig28 + 8,
-                                                 trl7, s.pose.get(), s.outl.get(), s.nin.get(), nullptr, nullptr));
+      const int* d_nLeft = c.in(&f.nLeft, 1);
+      check(morb_pose_optimization_fisheye_batch(o.h, 1, N, d_count, d_nLeft, d_hasMP, d_obs, d_invSigma2, d_Xw, f.rig28, f.rig28 + 8, trl7, d_pose,
+                                                 d_outlier, d_nInliers, nullptr, nullptr));
     } else
-    check(morb_pose_optimization_batch(o.h, 1, N, s.cnt.get(), s.has.get(), s.obs.get(), s.inv.get(), s.Xw.get(), f.fx, f.fy, f.cx, f.cy, f.mbf,
-                                       s.pose.get(), s.outl.get(), s.nin.get(), nullptr, nullptr));
-    morb_adapter::sync_current_stream();   // (the tracking handle's stream: a LocalBundleAdjustment on the mapping handle keeps running)
-    s.pose.download(f.pose, 7);
-    f.mvbOutlier = s.outl.to_host();
-    return s.nin.to_host()[0];
+    check(morb_pose_optimization_batch(o.h, 1, N, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, f.fx, f.fy, f.cx, f.cy, f.mbf, d_pose, d_outlier,
+                                       d_nInliers, nullptr, nullptr));
+    c.wait();   // (the tracking handle's stream: a LocalBundleAdjustment on the mapping handle keeps running)
+    c.fetch(d_pose, f.pose, 7);
+    f.mvbOutlier = c.fetch(d_outlier, N);
+    return c.fetch(d_nInliers, 1)[0];
   }
 
   // static void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int&, int&, int&, int&)  Optimizer.h:67-69.  pbStopFlag is
@@ -196,7 +191,6 @@ class Optimizer {
   // static int OptimizeSim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, g2o::Sim3&, float th2, bool bFixScale, Matrix<double,7,7>&, bool bAllPoints)
   // Optimizer.h:97-101 -> nIn (0 on the early return).  One problem through morb_optimize_sim3_batch on the loop-closing handle.
   static int OptimizeSim3(OptimizeSim3View& v, int device = 0) {
-    using morb_adapter::DeviceBuffer;
     const int N = v.N;
     v.keep.assign(N > 0 ? N : 0, 0);
     for (int i = 0; i < N; ++i) v.keep[i] = v.entry[i] & 1;
@@ -204,25 +198,26 @@ class Optimizer {
     if (N <= 0) return 0;
     Slot& o = slot(device, kLoopClosing);
     std::lock_guard<std::mutex> lock(o.mu);
-    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
-    morb_adapter::StreamScope scope_(morb_optimizer_stream(o.h));
-    struct Staging { DeviceBuffer<uint8_t> entry, fix, keep; DeviceBuffer<float> Xw1, Xw2, obs1, inv1, obs2, inv2, T1, T2, c1, c2, th2;
-                     DeviceBuffer<int> i2, cnt, nin, stats; DeviceBuffer<double> S; };
-    static thread_local Staging per_device[kMaxDevices];
-    Staging& s = per_device[device];
+    Call c(device, morb_optimizer_stream(o.h));
     const uint8_t fix = v.bFixScale ? 1 : 0;
-    s.entry.assign(v.entry, N); s.Xw1.assign(v.Xw1, (size_t)N * 3); s.Xw2.assign(v.Xw2, (size_t)N * 3); s.i2.assign(v.i2, N);
-    s.obs1.assign(v.obs1, (size_t)N * 2); s.inv1.assign(v.invSigma2_1, N); s.obs2.assign(v.obs2, (size_t)N * 2); s.inv2.assign(v.invSigma2_2, N);
-    s.T1.assign(v.T1w, 12); s.T2.assign(v.T2w, 12); s.c1.assign(v.cam1, 9); s.c2.assign(v.cam2, 9); s.th2.assign(&v.th2, 1); s.fix.assign(&fix, 1);
-    s.S.assign(v.S12, 8); s.cnt.assign(&N, 1); s.keep.resize(N); s.nin.resize(1); s.stats.resize(8);
-    check(morb_optimize_sim3_batch(o.h, 1, N, s.cnt.get(), s.entry.get(), s.Xw1.get(), s.Xw2.get(), s.i2.get(), s.obs1.get(), s.inv1.get(), s.obs2.get(),
-                                   s.inv2.get(), s.T1.get(), s.T2.get(), s.c1.get(), s.c2.get(), s.th2.get(), s.fix.get(), v.bAllPoints ? 1 : 0,
-                                   s.S.get(), s.keep.get(), s.nin.get(), s.stats.get(), nullptr));
-    morb_adapter::sync_current_stream();
-    s.S.download(v.S12, 8);
-    v.keep = s.keep.to_host();
-    s.stats.download(v.stats, 8);
-    return s.nin.to_host()[0];
+    const int* d_count = c.in(&N, 1);
+    const uint8_t* d_entry = c.in(v.entry, N);
+    const float *d_Xw1 = c.in(v.Xw1, (size_t)N * 3), *d_Xw2 = c.in(v.Xw2, (size_t)N * 3);
+    const int* d_i2 = c.in(v.i2, N);
+    const float *d_obs1 = c.in(v.obs1, (size_t)N * 2), *d_invSigma2_1 = c.in(v.invSigma2_1, N);
+    const float *d_obs2 = c.in(v.obs2, (size_t)N * 2), *d_invSigma2_2 = c.in(v.invSigma2_2, N);
+    const float *d_T1w = c.in(v.T1w, 12), *d_T2w = c.in(v.T2w, 12), *d_cam1 = c.in(v.cam1, 9), *d_cam2 = c.in(v.cam2, 9), *d_th2 = c.in(&v.th2, 1);
+    const uint8_t* d_fixScale = c.in(&fix, 1);
+    double* d_S12 = c.in(v.S12, 8);
+    uint8_t* d_keep = c.out<uint8_t>(N);
+    int *d_nIn = c.out<int>(1), *d_stats = c.out<int>(8);
+    check(morb_optimize_sim3_batch(o.h, 1, N, d_count, d_entry, d_Xw1, d_Xw2, d_i2, d_obs1, d_invSigma2_1, d_obs2, d_invSigma2_2, d_T1w, d_T2w, d_cam1,
+                                   d_cam2, d_th2, d_fixScale, v.bAllPoints ? 1 : 0, d_S12, d_keep, d_nIn, d_stats, nullptr));
+    c.wait();
+    c.fetch(d_S12, v.S12, 8);
+    v.keep = c.fetch(d_keep, N);
+    c.fetch(d_stats, v.stats, 8);
+    return c.fetch(d_nIn, 1)[0];
   }
 
   // ---- the reference's own signatures (include/Optimizer.h:67-101) as static member templates: the call sites of src/Tracking.cc and
@@ -263,53 +258,53 @@ class Optimizer {
   }
   // one frame through morb_pose_inertial_optimization_last_{keyframe,frame}[_fisheye]_batch
   static int pose_inertial(PoseInertialView& v, bool bRecInit, bool lastFrame, int device) {
-    using morb_adapter::DeviceBuffer;
     if (v.N <= 0) return 0;
     const int N = v.N;
     Slot& o = slot(device, kTracking);
     std::lock_guard<std::mutex> lock(o.mu);
-    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
-    morb_adapter::StreamScope scope_(morb_optimizer_stream(o.h));
-    struct Staging { DeviceBuffer<uint8_t> has, close, outl; DeviceBuffer<float> obs, inv, Xw, st, other; DeviceBuffer<int> nin, cnt, nl;
-                     DeviceBuffer<morb_imu_preintegrated> pre, preKF; DeviceBuffer<double> prior, prevPrior; };
-    static thread_local Staging per_device[kMaxDevices];
-    Staging& s = per_device[device];
-    s.has.assign(v.hasMapPoint, N); s.close.assign(v.close, N); s.outl.resize(N);
-    if ((int)v.mvbOutlier.size() == N) s.outl.upload(v.mvbOutlier.data(), N); else s.outl.fill_bytes(0);
-    s.obs.assign(v.obs, (size_t)N * 3); s.inv.assign(v.invSigma2, N); s.Xw.assign(v.worldPos, (size_t)N * 3);
-    s.st.assign(v.state, 21); s.other.assign(v.otherState, 21); s.pre.assign(&v.pre, 1); s.nin.resize(1); s.cnt.assign(&N, 1); s.prior.resize(246);
-    if (v.rig28) s.nl.assign(&v.nLeft, 1);
+    Call c(device, morb_optimizer_stream(o.h));
+    const int* d_count = c.in(&N, 1);
+    const int* d_nLeft = v.rig28 ? c.in(&v.nLeft, 1) : nullptr;
+    const uint8_t* d_hasMP = c.in(v.hasMapPoint, N);
+    const float *d_obs = c.in(v.obs, (size_t)N * 3), *d_invSigma2 = c.in(v.invSigma2, N), *d_Xw = c.in(v.worldPos, (size_t)N * 3);
+    const uint8_t* d_close = c.in(v.close, N);
+    const float* d_other = c.in(v.otherState, 21);   // the fixed keyframe's state / the free previous frame's
+    const morb_imu_preintegrated* d_pre = c.in(&v.pre, 1);
+    float* d_state = c.in(v.state, 21);
+    uint8_t* d_outlier = (int)v.mvbOutlier.size() == N ? c.in(v.mvbOutlier.data(), N) : c.out_filled<uint8_t>(N, 0);
+    int* d_nInliers = c.out<int>(1);
+    double* d_prior = c.out<double>(246);
     if (!lastFrame) {
       if (v.rig28)
-        check(morb_pose_inertial_optimization_last_keyframe_fisheye_batch(o.h, 1, N, s.cnt.get(), s.nl.get(), s.has.get(), s.obs.get(), s.inv.get(), s.Xw.get(),
-                                                                          s.close.get(), v.rig28, v.Tbc12, s.other.get(), s.pre.get(), bRecInit ? 1 : 0,
-                                                                          s.st.get(), s.outl.get(), s.nin.get(), s.prior.get(), nullptr));
+        check(morb_pose_inertial_optimization_last_keyframe_fisheye_batch(o.h, 1, N, d_count, d_nLeft, d_hasMP, d_obs, d_invSigma2, d_Xw, d_close, v.rig28,
+                                                                          v.Tbc12, d_other, d_pre, bRecInit ? 1 : 0, d_state, d_outlier, d_nInliers,
+                                                                          d_prior, nullptr));
       else
-        check(morb_pose_inertial_optimization_last_keyframe_batch(o.h, 1, N, s.cnt.get(), s.has.get(), s.obs.get(), s.inv.get(), s.Xw.get(), s.close.get(), v.fx,
-                                                                  v.fy, v.cx, v.cy, v.mbf, v.Tbc12, s.other.get(), s.pre.get(), bRecInit ? 1 : 0, s.st.get(),
-                                                                  s.outl.get(), s.nin.get(), s.prior.get(), nullptr));
+        check(morb_pose_inertial_optimization_last_keyframe_batch(o.h, 1, N, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, d_close, v.fx, v.fy, v.cx, v.cy,
+                                                                  v.mbf, v.Tbc12, d_other, d_pre, bRecInit ? 1 : 0, d_state, d_outlier, d_nInliers,
+                                                                  d_prior, nullptr));
     } else {
-      s.preKF.assign(&v.preKF, 1); s.prevPrior.assign(v.prevPrior, 246);
+      const morb_imu_preintegrated* d_preKF = c.in(&v.preKF, 1);
+      const double* d_prevPrior = c.in(v.prevPrior, 246);
       if (v.rig28)
-        check(morb_pose_inertial_optimization_last_frame_fisheye_batch(o.h, 1, N, s.cnt.get(), s.nl.get(), s.has.get(), s.obs.get(), s.inv.get(), s.Xw.get(),
-                                                                       s.close.get(), v.rig28, v.Tbc12, s.other.get(), s.pre.get(), s.preKF.get(),
-                                                                       s.prevPrior.get(), bRecInit ? 1 : 0, s.st.get(), s.outl.get(), s.nin.get(),
-                                                                       s.prior.get(), nullptr));
+        check(morb_pose_inertial_optimization_last_frame_fisheye_batch(o.h, 1, N, d_count, d_nLeft, d_hasMP, d_obs, d_invSigma2, d_Xw, d_close, v.rig28,
+                                                                       v.Tbc12, d_other, d_pre, d_preKF, d_prevPrior, bRecInit ? 1 : 0, d_state,
+                                                                       d_outlier, d_nInliers, d_prior, nullptr));
       else
-        check(morb_pose_inertial_optimization_last_frame_batch(o.h, 1, N, s.cnt.get(), s.has.get(), s.obs.get(), s.inv.get(), s.Xw.get(), s.close.get(), v.fx, v.fy,
-                                                               v.cx, v.cy, v.mbf, v.Tbc12, s.other.get(), s.pre.get(), s.preKF.get(), s.prevPrior.get(),
-                                                               bRecInit ? 1 : 0, s.st.get(), s.outl.get(), s.nin.get(), s.prior.get(), nullptr));
+        check(morb_pose_inertial_optimization_last_frame_batch(o.h, 1, N, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, d_close, v.fx, v.fy, v.cx, v.cy,
+                                                               v.mbf, v.Tbc12, d_other, d_pre, d_preKF, d_prevPrior, bRecInit ? 1 : 0, d_state, d_outlier,
+                                                               d_nInliers, d_prior, nullptr));
     }
-    morb_adapter::sync_current_stream();
-    s.st.download(v.state, 21); s.prior.download(v.prior, 246);
-    v.mvbOutlier = s.outl.to_host();
-    return s.nin.to_host()[0];
+    c.wait();
+    c.fetch(d_state, v.state, 21); c.fetch(d_prior, v.prior, 246);
+    v.mvbOutlier = c.fetch(d_outlier, N);
+    return c.fetch(d_nInliers, 1)[0];
   }
-  static constexpr int kMaxDevices = 16;
+  using Call = morb_adapter::CallStaging;   // one per staged call: device, the handle's stream, this thread's staging (device_buffer.h)
   struct Slot { std::once_flag once; std::mutex mu; morb_optimizer* h = nullptr; };
   static Slot& slot(int device, Role role) {
-    if (device < 0 || device >= kMaxDevices) throw std::runtime_error("bad device");
-    static Slot slots[kMaxDevices][3];
+    if (device < 0 || device >= morb_adapter::kMaxDevices) throw std::runtime_error("bad device");
+    static Slot slots[morb_adapter::kMaxDevices][3];
     Slot& o = slots[device][role];
     std::call_once(o.once, [&] {
       if (morb_optimizer_create(&o.h, device) != MORB_OK) { o.h = nullptr; throw std::runtime_error(std::string("morb_optimizer_create: ") + morb_last_error()); }

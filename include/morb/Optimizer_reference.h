@@ -110,8 +110,8 @@ int Optimizer::PoseOptimization(FrameT* pFrame) {
   f.mvbOutlier = fe.outlier;
   f.fx = pFrame->fx; f.fy = pFrame->fy; f.cx = pFrame->cx; f.cy = pFrame->cy; f.mbf = pFrame->mbf;
   morb_glue::pose7(pFrame->GetPose(), f.pose);                     // :781-783
-  float rig[28];
-  if (pFrame->mpCamera2) { morb_glue::rig28(pFrame, rig); f.nLeft = pFrame->Nleft; f.rig28 = rig; }   // :880-946
+  float rigp[28];
+  if (pFrame->mpCamera2) { morb_glue::rig28(pFrame, rigp); f.nLeft = pFrame->Nleft; f.rig28 = rigp; }   // :880-946
   int nInitialCorrespondences = 0;
   for (int i = 0; i < fe.N; ++i) nInitialCorrespondences += fe.has[i] ? 1 : 0;
   if (fe.N <= 0 || nInitialCorrespondences < 3) {                   // :951: the reference returns without touching the pose; the graph fill
@@ -135,8 +135,8 @@ int Optimizer::PoseInertialOptimizationLastKeyFrame(FrameT* pFrame, bool bRecIni
   v.N = fe.N; v.nLeft = fe.nLeft; v.hasMapPoint = fe.has.data(); v.obs = fe.obs.data(); v.invSigma2 = fe.inv.data(); v.worldPos = fe.Xw.data();
   v.close = fe.close.data(); v.mvbOutlier = fe.outlier;
   v.fx = pFrame->fx; v.fy = pFrame->fy; v.cx = pFrame->cx; v.cy = pFrame->cy; v.mbf = pFrame->mbf;
-  float rig[28];
-  if (pFrame->mpCamera2) { morb_glue::rig28(pFrame, rig); v.rig28 = rig; }
+  float rigp[28];
+  if (pFrame->mpCamera2) { morb_glue::rig28(pFrame, rigp); v.rig28 = rigp; }
   morb_glue::tbc12(pFrame->mImuCalib.mTbc, v.Tbc12);
   morb_glue::imu_state21(pFrame, v.state); morb_glue::bias6(pFrame->mImuBias, v.state + 15);          // VertexPose(pFrame), ... :4411-4426
   auto* pKF = pFrame->mpLastKeyFrame;                                                                  // :4548-4566: fixed vertices
@@ -162,8 +162,8 @@ int Optimizer::PoseInertialOptimizationLastFrame(FrameT* pFrame, bool bRecInit) 
   v.N = fe.N; v.nLeft = fe.nLeft; v.hasMapPoint = fe.has.data(); v.obs = fe.obs.data(); v.invSigma2 = fe.inv.data(); v.worldPos = fe.Xw.data();
   v.close = fe.close.data(); v.mvbOutlier = fe.outlier;
   v.fx = pFrame->fx; v.fy = pFrame->fy; v.cx = pFrame->cx; v.cy = pFrame->cy; v.mbf = pFrame->mbf;
-  float rig[28];
-  if (pFrame->mpCamera2) { morb_glue::rig28(pFrame, rig); v.rig28 = rig; }
+  float rigp[28];
+  if (pFrame->mpCamera2) { morb_glue::rig28(pFrame, rigp); v.rig28 = rigp; }
   morb_glue::tbc12(pFrame->mImuCalib.mTbc, v.Tbc12);
   morb_glue::imu_state21(pFrame, v.state); morb_glue::bias6(pFrame->mImuBias, v.state + 15);
   morb_glue::imu_state21(pFp, v.otherState); morb_glue::bias6(pFp->mImuBias, v.otherState + 15);      // :4922-4937: free vertices of the previous frame

@@ -196,26 +196,22 @@ class Sim3Solver {
     for (int k = 0; k < 3 * its; ++k) rand_[(size_t)3 * state_.iterations + k] = std::rand();
     std::vector<uint8_t> mask(n > 0 ? n : 1, 0);
     if (n > 0) {
-      using morb_adapter::DeviceBuffer;
       Optimizer::Slot& o = Optimizer::slot(device_, Optimizer::kLoopClosing);
       std::lock_guard<std::mutex> lock(o.mu);
-      morb_adapter::hip_check(hipSetDevice(device_), "hipSetDevice");
-      morb_adapter::StreamScope scope_(morb_optimizer_stream(o.h));
-      struct Staging { DeviceBuffer<uint8_t> entry, inl; DeviceBuffer<float> Xw1, Xw2, s1, s2; DeviceBuffer<int> rnd;
-                       DeviceBuffer<morb_sim3_solver_params> prm; DeviceBuffer<morb_sim3_solver_state> st; };
-      static thread_local Staging per_device[Optimizer::kMaxDevices];
-      Staging& s = per_device[device_];
-      s.entry.assign(view_.entry.data(), n); s.Xw1.assign(view_.Xw1.data(), (size_t)n * 3); s.Xw2.assign(view_.Xw2.data(), (size_t)n * 3);
-      s.s1.assign(view_.sigma2_1.data(), n); s.s2.assign(view_.sigma2_2.data(), n); s.prm.assign(&P, 1); s.st.assign(&state_, 1);
+      Optimizer::Call c(device_, morb_optimizer_stream(o.h));
       const int randCap = (int)rand_.size();
-      if (randCap > 0) s.rnd.assign(rand_.data(), rand_.size());
-      s.inl.resize(n);
-      Optimizer::check(morb_sim3_solver_batch(o.h, 1, n, s.prm.get(), s.entry.get(), s.Xw1.get(), s.Xw2.get(), s.s1.get(), s.s2.get(),
-                                              nIterations, randCap > 0 ? s.rnd.get() : nullptr, randCap, s.st.get(), s.inl.get(), nullptr, 0,
-                                              nullptr));
-      morb_adapter::sync_current_stream();
-      s.st.download(&state_, 1);
-      s.inl.download(mask.data(), n);
+      const morb_sim3_solver_params* d_params = c.in(&P, 1);
+      const uint8_t* d_entry = c.in(view_.entry.data(), n);
+      const float *d_Xw1 = c.in(view_.Xw1.data(), (size_t)n * 3), *d_Xw2 = c.in(view_.Xw2.data(), (size_t)n * 3);
+      const float *d_sigma2_1 = c.in(view_.sigma2_1.data(), n), *d_sigma2_2 = c.in(view_.sigma2_2.data(), n);
+      const int* d_rand = randCap > 0 ? c.in(rand_.data(), rand_.size()) : nullptr;
+      morb_sim3_solver_state* d_state = c.in(&state_, 1);
+      uint8_t* d_inliers = c.out<uint8_t>(n);
+      Optimizer::check(morb_sim3_solver_batch(o.h, 1, n, d_params, d_entry, d_Xw1, d_Xw2, d_sigma2_1, d_sigma2_2, nIterations, d_rand, randCap, d_state,
+                                              d_inliers, nullptr, 0, nullptr));
+      c.wait();
+      c.fetch(d_state, &state_, 1);
+      c.fetch(d_inliers, mask.data(), n);
     } else {   // mN1 = 0: N = 0 < minInliers
       state_.converged = 0; state_.noMore = 1; state_.nInliers = 0;
       for (int i = 0; i < 16; ++i) state_.sim3[i] = (i % 5 == 0) ? 1.f : 0.f;

@@ -147,3 +147,39 @@ def test_cpp_adapters_match_oracle(tmp_path):
     assert np.abs(get("ba_kf", np.float32).reshape(-1, 7) - kfe).max() <= 1e-4
     assert np.abs(get("ba_mp", np.float32).reshape(-1, 3) - mpe).max() <= 1e-4 * max(1.0, np.abs(mpe).max())
     np.testing.assert_array_equal(get("ba_erase", np.uint8), ee)
+
+
+def test_cpp_adapter_call_leaves_nothing_behind_on_a_destroyed_stream(tmp_path):
+    """One thread, the reference's tracking pattern (tests/native/adapter_stream_lifetime_check.cc): a matcher call that throws after it has
+    queued its uploads (the C entry point refuses 70000 features), the ORBmatcher — and its stream — destroyed, then PoseOptimization on the
+    optimizer handle made earlier, then another matcher call.  Both must give what they gave before the disturbance, i.e. the oracle's."""
+    d = tmp_path / "io"
+    d.mkdir()
+    put = lambda name, a: np.ascontiguousarray(a).tofile(str(d / (name + ".bin")))
+    get = lambda name, dt: np.fromfile(str(d / ("out_" + name + ".bin")), dtype=dt)
+    pp = make_pose_problem(600, seed=3)   # the po_* inputs of test_cpp_adapters_match_oracle
+    cam = pp["cam"]
+    put("po_has", pp["hasMP"]); put("po_obs", pp["obs"]); put("po_inv", pp["invSigma2"]); put("po_xw", pp["Xw"]); put("po_pose", pp["pose0"])
+    put("po_cam", np.array([cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["bf"]], np.float32))
+    # SearchByBoW(pKF, F): the frame's descriptors are the keyframe's with a few bits flipped, ten vocabulary nodes
+    rng = np.random.default_rng(11)
+    n = 500
+    kps = np.zeros(n, O.KP_DTYPE)
+    kps["angle"] = rng.uniform(0, 360, n).astype(np.float32)
+    dKF = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    dF = dKF ^ (np.uint8(1) << rng.integers(0, 8, (n, 32)).astype(np.uint8)) * (rng.random((n, 32)) < 0.15).astype(np.uint8)
+    node = rng.integers(0, 10, n).astype(np.int32)
+    hasKF = (rng.random(n) < 0.8).astype(np.uint8)
+    put("bow_kps", kps); put("bow_kf_desc", dKF); put("bow_f_desc", dF); put("bow_kf_node", node); put("bow_f_node", node); put("bow_kf_hasmp", hasKF)
+    out = subprocess.run([_build(tmp_path, "adapter_stream_lifetime_check.cc"), str(d)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "refused as expected" in out.stdout and "stream lifetime ok" in out.stdout, out.stdout + out.stderr
+    ro, pe, oe_, _ = O.pose_optimization(pp)
+    ne, me = O.search_by_bow(dKF, kps["angle"], hasKF, node, dF, kps["angle"], node, 0.7, True)
+    assert ne > 200
+    for when in ("before", "after"):
+        assert int(get(when + "_nin", np.int32)[0]) == ro, when
+        assert np.abs(get(when + "_pose", np.float32) - pe).max() <= 1e-4, when
+        np.testing.assert_array_equal(get(when + "_outlier", np.uint8), oe_, err_msg=when)
+        assert int(get("bow_" + when + "_n", np.int32)[0]) == ne, when
+        np.testing.assert_array_equal(get("bow_" + when + "_match", np.int32), me, err_msg=when)
+    assert get("after_pose", np.float32).tobytes() == get("before_pose", np.float32).tobytes()

@@ -1,6 +1,7 @@
 """Every HIP resource of libmorb_hip.so has one owner: device and pinned memory, streams and events are allocated and released only
 inside csrc/hip_owned.h (move-only owners and the one grow-only buffer).  A call anywhere else in csrc/ would bring back a hand-written
-release list or a second growth policy."""
+release list or a second growth policy.  The C++ adapters above the library keep the same rule for memory: include/morb/ allocates
+and frees device and pinned memory only inside device_buffer.h (the per-thread staging every adapter call goes through)."""
 import glob
 import os
 import re
@@ -8,6 +9,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "morb_slam_amd", "csrc")
 OWNER = "hip_owned.h"
+ADAPTERS = os.path.join(ROOT, "include", "morb")
+ADAPTER_OWNER = "device_buffer.h"
 
 _CALL = re.compile(r"\b(hipMalloc\w*|hipExtMalloc\w*|hipHostMalloc\w*|hipFree\w*|hipHostFree\w*|hipStreamCreate\w*|hipStreamDestroy\w*"
                    r"|hipEventCreate\w*|hipEventDestroy\w*)\s*\(")
@@ -38,6 +41,18 @@ def test_owner_module_is_where_the_calls_are():
     names = {name for _, name in _calls(os.path.join(CSRC, OWNER))}
     for want in ("hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree", "hipStreamCreateWithFlags", "hipStreamDestroy",
                  "hipEventCreateWithFlags", "hipEventDestroy"):
+        assert want in names, want
+
+
+def test_adapters_allocate_memory_only_in_the_staging_header():
+    mem = re.compile(r"hip(Ext|Host)?(Malloc|Free)\w*")
+    headers = sorted(glob.glob(os.path.join(ADAPTERS, "*.h")))
+    assert os.path.join(ADAPTERS, ADAPTER_OWNER) in headers
+    bad = [f"{os.path.basename(p)}:{line}: {name}" for p in headers if os.path.basename(p) != ADAPTER_OWNER for line, name in _calls(p)
+           if mem.fullmatch(name)]
+    assert not bad, "stage adapter calls through include/morb/device_buffer.h:\n" + "\n".join(bad)
+    names = {name for _, name in _calls(os.path.join(ADAPTERS, ADAPTER_OWNER))}
+    for want in ("hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree"):
         assert want in names, want
 
 
