@@ -10,18 +10,10 @@
 #include <cstring>
 
 #include "common.h"
-#include "internal_abi.h"
+#include "handles.h"
 #include "kb8.h"
 
 using namespace morb;
-
-struct morb_matcher;
-extern "C" {
-void* morb_matcher_stream(const morb_matcher*);
-int morb_hamming_knn2_batch(morb_matcher*, int nprob, const uint8_t* d_query, const int* d_nq, int qPitch, const int* d_qOff,
-                            const uint8_t* d_train, const int* d_nt, int tPitch, const int* d_tOff, int* d_idx, int* d_dist,
-                            void* stream);
-}
 
 namespace {
 
@@ -83,27 +75,27 @@ extern "C" int morb_stereo_fisheye_match_batch(morb_matcher* m, int nframes, con
   MORB_REQUIRE(m && d_kps && d_desc && d_count && d_mono && camL8 && camR8 && Rlr9 && tlr3 && levelSigma2 && d_leftToRight &&
                    d_rightToLeft && d_depth && d_p3D && d_nMatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && nlevels >= 1 && nlevels <= 16, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   RigF g;
   memset(&g, 0, sizeof g);
   memcpy(g.cl.p, camL8, 32); memcpy(g.cr.p, camR8, 32);
   memcpy(g.Rlr, Rlr9, 36); memcpy(g.tlr, tlr3, 12);
   memcpy(g.sigma2, levelSigma2, sizeof(float) * nlevels);
-  void *aux = nullptr, *idx = nullptr, *dist = nullptr;
-  int rc = morb_matcher_workspace(m, 5, sizeof(int) * 4 * (size_t)nframes, &aux);
+  // (queries / candKeys / candCount hold these across morb_hamming_knn2_batch below, which takes no workspace)
+  int *nq = nullptr, *idx = nullptr, *dist = nullptr;
+  int rc = grow(m->queries, 4 * (size_t)nframes, &nq);
   // knn outputs indexed by (problem, query row) with the query pitch = 2*cap rows (left image of frame f = row block 2f)
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 0, sizeof(int) * 2 * (size_t)nframes * 2 * cap, &idx);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 1, sizeof(int) * 2 * (size_t)nframes * 2 * cap, &dist);
+  if (rc == MORB_OK) rc = grow(m->candKeys, 2 * (size_t)nframes * 2 * cap, &idx);
+  if (rc == MORB_OK) rc = grow(m->candCount, 2 * (size_t)nframes * 2 * cap, &dist);
   if (rc != MORB_OK) return rc;
-  int* nq = (int*)aux; int* nt = nq + nframes; int* qOff = nt + nframes; int* tOff = qOff + nframes;
+  int* nt = nq + nframes; int* qOff = nt + nframes; int* tOff = qOff + nframes;
   hipLaunchKernelGGL(k_fe_prepare, dim3(div_up(nframes, 256)), dim3(256), 0, st, d_count, d_mono, nframes, nq, nt, qOff, tOff);
   hipLaunchKernelGGL(k_fe_init, dim3(div_up(nframes * cap, 256)), dim3(256), 0, st, nframes * cap, d_leftToRight, d_rightToLeft, d_depth, d_p3D);
   MORB_HIP_CHECK(hipMemsetAsync(d_nMatches, 0, sizeof(int) * nframes, st));
-  rc = morb_hamming_knn2_batch(m, nframes, d_desc, nq, 2 * cap, qOff, d_desc + (size_t)cap * 32, nt, 2 * cap, tOff, (int*)idx, (int*)dist, st);
+  rc = morb_hamming_knn2_batch(m, nframes, d_desc, nq, 2 * cap, qOff, d_desc + (size_t)cap * 32, nt, 2 * cap, tOff, idx, dist, st);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_fe_triangulate, dim3(div_up(cap, 256), nframes), dim3(256), 0, st, g, cap, d_count, d_mono, d_kps,
-                     (const int*)idx, (const int*)dist, d_leftToRight, d_rightToLeft, d_depth, d_p3D, d_nMatches);
+                     idx, dist, d_leftToRight, d_rightToLeft, d_depth, d_p3D, d_nMatches);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }

@@ -10,14 +10,9 @@
 #include <cstring>
 
 #include "common.h"
-#include "internal_abi.h"
+#include "handles.h"
 
 using namespace morb;
-
-struct morb_matcher;
-extern "C" {
-void* morb_matcher_stream(const morb_matcher*);
-}
 
 namespace {
 
@@ -170,8 +165,7 @@ int morb_undistort_keypoints_batch(morb_matcher* m, int nimg, int cap, const int
                                    float fy, float cx, float cy, const float* dist5, morb_keypoint* d_kpsUn, void* stream) {
   MORB_REQUIRE(m && d_kps && d_kpsUn && dist5, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nimg > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   Distortion D;
   make_distortion(fx, fy, cx, cy, dist5, D);
   hipLaunchKernelGGL(k_undistort, dim3(div_up(cap, 256), nimg), dim3(256), 0, st, D, dist5[0] == 0.0f ? 1 : 0, cap, d_count, d_kps, d_kpsUn);
@@ -185,8 +179,7 @@ int morb_stereo_from_rgbd_batch(morb_matcher* m, int nimg, int cap, const int* d
   MORB_REQUIRE(m && d_kps && d_kpsUn && d_depth && d_uRight && d_depthOut, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nimg > 0 && cap > 0 && width > 0 && height > 0 && rowPitchFloats >= (size_t)width &&
                    imagePitchFloats >= rowPitchFloats * (size_t)height, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_rgbd, dim3(div_up(cap, 256), nimg), dim3(256), 0, st, cap, d_count, d_kps, d_kpsUn, d_depth, width, height,
                      rowPitchFloats, imagePitchFloats, bf, d_uRight, d_depthOut);
   MORB_HIP_CHECK(hipGetLastError());
@@ -202,8 +195,7 @@ int morb_bow_vector_batch(morb_matcher* m, int nimg, const int* d_leaf, const in
   while (P < cap) P <<= 1;
   const size_t lds = (size_t)P * (8 + 8 + 4);
   MORB_REQUIRE(lds <= 150 * 1024, MORB_ERR_CAPACITY, "cap too large for the BowVector kernel");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   if (lds > 48 * 1024) MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_vector), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_bow_vector, dim3(nimg), dim3(256), lds, st, d_leaf, d_count, cap, P, d_nodeWordId, d_nodeWeight, weighting, scoring,
                      d_bowWord, d_bowValue, d_bowCount);

@@ -29,11 +29,6 @@
 
 using namespace morb;
 
-struct morb_optimizer;
-extern "C" {
-void* morb_optimizer_stream(const morb_optimizer*);
-}
-
 #define WAVE_SYNC_F()                                      \
   do {                                                     \
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); \
@@ -1785,8 +1780,7 @@ int morb_imu_preintegrate_batch(morb_optimizer* o, int nseq, const int* d_start,
                                 morb_imu_preintegrated* d_out, void* stream) {
   MORB_REQUIRE(o && d_start && d_acc && d_gyro && d_dt && d_bias && ngaDiag6 && walkDiag6 && d_out, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nseq > 0, MORB_ERR_INVALID, "nseq must be positive");
-  MORB_HIP_CHECK(hipSetDevice(morb_optimizer_device(o)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_optimizer_stream(o);
+  MORB_ENTER(st, o, stream);
   morb_imu_preintegrated calib;
   memset(&calib, 0, sizeof calib);
   memcpy(calib.nga, ngaDiag6, sizeof(float) * 6);
@@ -1830,21 +1824,20 @@ static int launch_pose_inertial(bool lastFrame, morb_optimizer* o, int nframes, 
   MORB_REQUIRE(!lastFrame || (d_preKF && d_prevPrior), MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(!rig28 || d_nLeft, MORB_ERR_INVALID, "a fisheye rig needs d_nLeft");
   MORB_REQUIRE(nframes > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_optimizer_device(o)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_optimizer_stream(o);
+  MORB_ENTER(st, o, stream);
   CamGeom g;
   make_geom(Tbc12, fx, fy, cx, cy, bf, rig28, g);
   const size_t edgeLds = (size_t)cap * 32;   // the active visual edges of a frame, eight floats each
   // (round 5 refused frames whose list does not fit the LDS; now they take the same kernel with the list in a global spill buffer of the handle)
   const bool spill = edgeLds + sizeof(InertialWork) + 1024 > 160 * 1024;
-  void* gEdge = nullptr;
-  if (spill) { const int rc = morb_optimizer_spill(o, (size_t)nframes * edgeLds, &gEdge); if (rc != MORB_OK) return rc; }
+  float* gEdge = nullptr;
+  if (spill) { const int rc = grow(o->spill, (size_t)nframes * cap * 8, &gEdge); if (rc != MORB_OK) return rc; }
 #define MORB_LAUNCH_PI2(LF, RG, GE)                                                                                                  \
   do {                                                                                                                               \
     const size_t lds_ = GE ? 0 : edgeLds;                                                                                            \
     MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_inertial<LF, RG, GE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
     hipLaunchKernelGGL((k_pose_inertial<LF, RG, GE>), dim3(nframes), dim3(256), lds_, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, d_close, \
-                       g, d_state1, d_pre, d_preKF, d_prevPrior, d_nLeft, bRecInit, d_state, d_outlier, d_nInliers, d_prior, (float*)gEdge);  \
+                       g, d_state1, d_pre, d_preKF, d_prevPrior, d_nLeft, bRecInit, d_state, d_outlier, d_nInliers, d_prior, gEdge);          \
   } while (0)
 #define MORB_LAUNCH_PI(LF, RG) do { if (spill) MORB_LAUNCH_PI2(LF, RG, true); else MORB_LAUNCH_PI2(LF, RG, false); } while (0)
   if (lastFrame) { if (rig28) MORB_LAUNCH_PI(true, true); else MORB_LAUNCH_PI(true, false); }
@@ -1910,8 +1903,7 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   MORB_REQUIRE(o && kfState21 && kfKind && mpPos && mpClose && eKF && eMP && eObs && eInvSigma2 && iKF1 && iKF2 && iPre && iRobust &&
                    iInfoScale && Tbc12 && eraseFlag, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0 && nI >= 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_optimizer_device(o)));
-  hipStream_t st = (hipStream_t)morb_optimizer_stream(o);
+  MORB_ENTER(st, o, nullptr);
   // ---- host-side graph layout
   std::vector<int> col(nKF, -1);
   int nOpt = 0;
@@ -1957,18 +1949,18 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
                    sizeof(int) * (size_t)nI, sizeof(double) * 27 * (size_t)nChunks, sizeof(int) * (size_t)nKF,
                    sizeof(double) * (size_t)div_up(nE + nI, 256), sizeof(double) * (size_t)div_up(nMP + nKF, 256)})
     reserve(b);
-  void* arena = nullptr;
-  { const int rc = morb_optimizer_workspace(o, arenaBytes, &arena); if (rc != MORB_OK) return rc; }
+  char* arena = nullptr;
+  { const int rc = grow(o->work, arenaBytes, &arena); if (rc != MORB_OK) return rc; }
   size_t arenaOff = 0;
   auto dalloc = [&](size_t bytes) -> void* {
-    void* p = (char*)arena + arenaOff;
+    void* p = arena + arenaOff;
     arenaOff += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
     return arenaOff <= arenaBytes ? p : nullptr;
   };
   auto cleanup = [&]() {};
   // host -> device: every array goes into a pinned mirror of the arena's upload prefix first and crosses PCIe in ONE copy (twenty
   // pageable hipMemcpyAsync calls, each staged and synchronised by the runtime, were ~0.25 ms of a 1.8 ms call)
-  void* stage = nullptr;
+  char* stage = nullptr;
   size_t stageCap = 0;
   {
     size_t upBytes = 0;
@@ -1979,7 +1971,7 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
                      sizeof(float) * 21 * (size_t)nKF, sizeof(float) * 3 * (size_t)nMP, (size_t)nE, sizeof(int2) * (size_t)splan.nblk,
                      sizeof(int) * (size_t)splan.nb * splan.nb, sizeof(int) * (size_t)nI})
       upBytes += (std::max<size_t>(b, 16) + 255) & ~(size_t)255;
-    const int rc = morb_optimizer_staging(o, upBytes, &stage);
+    const int rc = grow(o->stage, upBytes, &stage);
     if (rc != MORB_OK) return rc;
     stageCap = upBytes;
   }
@@ -1989,7 +1981,7 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
     void* d = dalloc(bytes);
     if (d && bytes) {
       if (off + bytes > stageCap) return nullptr;   // (cannot happen: the uploads are the arena's first allocations, sized above)
-      memcpy((char*)stage + off, h, bytes); upHi = off + bytes;
+      memcpy(stage + off, h, bytes); upHi = off + bytes;
     }
     return d;
   };

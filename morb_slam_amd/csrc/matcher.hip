@@ -1134,36 +1134,6 @@ __global__ void k_fill_i32(int* p, size_t n, int v) {
 }  // namespace
 
 // =====================================================================================================
-struct morb_matcher {
-  int device = 0;
-  morb::Stream stream;
-  // grow-only workspaces (hip_owned.h: kernels queued on a caller's stream may still read an outgrown block, so it lives as long as the handle)
-  morb::DeviceGrow sortA;        // k_bow_sort's sorted (node, feature) keys
-  morb::DeviceGrow bin;          // k_bow_match / k_rot_filter: rotation histogram bins
-  morb::DeviceGrow sad;          // k_stereo_match / k_stereo_median
-  morb::DeviceGrow stereoRec;    // k_stereo_prep's per-frame records
-  morb::DeviceGrow ws[8];        // generic workspaces for projection.hip
-  // small constant tables (PredictScale thresholds, camera parameters): device copy + the host bytes it was made from, so that a
-  // call with the same table neither uploads nor waits (projection.hip: morb_matcher_const)
-  // Four most-recently-used copies per slot (a KB8 rig alternates the left and the right camera's table on one slot); a live copy is never
-  // rewritten — a kernel of an earlier call, queued on another caller's stream, may still be reading it: a replaced copy is retired, and
-  // freed with the handle.
-  struct ConstCopy { morb::DeviceArray<> d; std::vector<uint8_t> host; unsigned long long used = 0; };
-  struct ConstSlot { ConstCopy way[4]; unsigned long long clock = 0; };
-  ConstSlot consts[4];
-  std::vector<morb::DeviceArray<>> retired;
-};
-
-namespace {
-template <typename T>
-int grow(morb::DeviceGrow& b, size_t n, T** out) {
-  void* p = nullptr;
-  const int rc = b.ensure(sizeof(T) * n, &p);
-  *out = static_cast<T*>(p);
-  return rc;
-}
-}  // namespace
-
 extern "C" {
 
 int morb_matcher_create(morb_matcher** out, int device) {
@@ -1199,17 +1169,12 @@ void morb_matcher_destroy(morb_matcher* m) {
   delete m;
 }
 
-int morb_matcher_device(const morb_matcher* m) { return m->device; }
 void* morb_matcher_stream(const morb_matcher* m) { return (void*)m->stream; }
-int morb_matcher_workspace(morb_matcher* m, int which, size_t bytes, void** out) {
-  MORB_REQUIRE(m && out && which >= 0 && which < 8, MORB_ERR_INVALID, "bad workspace request");
-  return m->ws[which].ensure(bytes, out);
-}
 // Device copy of a small host table that rarely changes (level thresholds, camera parameters).  Same bytes as the last call on
 // this slot: no upload, no wait.  Otherwise the table is uploaded in stream order and the call waits for the copy.
-int morb_matcher_const(morb_matcher* m, int slot, const void* host, size_t bytes, void** d_out, void* stream) {
-  MORB_REQUIRE(m && host && d_out && slot >= 0 && slot < 4 && bytes > 0, MORB_ERR_INVALID, "bad constant-table request");
-  morb_matcher::ConstSlot& c = m->consts[slot];
+int morb_matcher_const(morb_matcher* m, morb_matcher::ConstTable table, const void* host, size_t bytes, void** d_out, void* stream) {
+  MORB_REQUIRE(m && host && d_out && bytes > 0, MORB_ERR_INVALID, "bad constant-table request");
+  morb_matcher::ConstSlot& c = m->consts[table];
   int victim = 0;
   for (int w = 0; w < 4; ++w) {
     morb_matcher::ConstCopy& k = c.way[w];
@@ -1223,7 +1188,7 @@ int morb_matcher_const(morb_matcher* m, int slot, const void* host, size_t bytes
   k.d = std::move(fresh);
   k.host.assign((const uint8_t*)host, (const uint8_t*)host + bytes);
   k.used = ++c.clock;
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  hipStream_t st = stream_or_own(m, stream);
   MORB_HIP_CHECK(hipMemcpyAsync(k.d, k.host.data(), bytes, hipMemcpyHostToDevice, st));
   MORB_HIP_CHECK(hipStreamSynchronize(st));   // (k.host may be reassigned by the next miss on this way)
   *d_out = k.d;
@@ -1234,7 +1199,7 @@ int morb_bow_sort_images(morb_matcher* m, int nimg, const int* d_node, const int
   int P = 1;
   while (P < cap) P <<= 1;
   MORB_REQUIRE((size_t)P * 8 <= 160 * 1024, MORB_ERR_UNSUPPORTED, "too many features per frame for the LDS sort");
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  hipStream_t st = stream_or_own(m, stream);
   unsigned long long* sortA = nullptr;
   int rc = grow(m->sortA, (size_t)nimg * cap, &sortA);
   if (rc != MORB_OK) return rc;
@@ -1271,8 +1236,7 @@ __global__ __launch_bounds__(256) void k_slab_copy(int S, int cap, const int* __
 int morb_feature_slab_pack(morb_matcher* m, int S, int cap, const int* d_rows, const morb_keypoint* d_kps, const uint8_t* d_desc, const int* d_node,
                            const int* d_count, void* d_slab, void* stream) {
   MORB_REQUIRE(m && S > 0 && cap > 0 && d_kps && d_desc && d_count && d_slab, MORB_ERR_INVALID, "bad argument");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_slab_copy, dim3(S, 3), dim3(256), 0, st, S, cap, d_rows, (uint32_t*)d_kps, (uint32_t*)d_desc, (uint32_t*)d_node, (int*)d_count,
                      (uint32_t*)d_slab, 0);
   MORB_HIP_CHECK(hipGetLastError());
@@ -1281,8 +1245,7 @@ int morb_feature_slab_pack(morb_matcher* m, int S, int cap, const int* d_rows, c
 int morb_feature_slab_unpack(morb_matcher* m, int S, int cap, const void* d_slab, const int* d_rows, morb_keypoint* d_kps, uint8_t* d_desc, int* d_node,
                              int* d_count, void* stream) {
   MORB_REQUIRE(m && S > 0 && cap > 0 && d_kps && d_desc && d_count && d_slab, MORB_ERR_INVALID, "bad argument");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_slab_copy, dim3(S, 3), dim3(256), 0, st, S, cap, d_rows, (uint32_t*)d_kps, (uint32_t*)d_desc, (uint32_t*)d_node, d_count,
                      (uint32_t*)const_cast<void*>(d_slab), 1);
   MORB_HIP_CHECK(hipGetLastError());
@@ -1291,8 +1254,7 @@ int morb_feature_slab_unpack(morb_matcher* m, int S, int cap, const void* d_slab
 
 int morb_hamming_pairs(morb_matcher* m, const uint8_t* d_a, const uint8_t* d_b, int n, int* d_out, void* stream) {
   MORB_REQUIRE(m && d_a && d_b && d_out && n >= 0, MORB_ERR_INVALID, "bad argument");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   if (n) hipLaunchKernelGGL(k_hamming_pairs, dim3(div_up(n, 256)), dim3(256), 0, st, d_a, d_b, n, d_out);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
@@ -1303,8 +1265,7 @@ int morb_hamming_knn2_batch(morb_matcher* m, int nprob, const uint8_t* d_query, 
                             int* d_idx, int* d_dist, void* stream) {
   MORB_REQUIRE(m && d_query && d_train && d_nq && d_nt && d_idx && d_dist, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nprob > 0 && qPitch > 0 && tPitch > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_knn2, dim3(div_up(qPitch, 256), nprob), dim3(256), 0, st, d_query, d_nq, qPitch, d_train, d_nt,
                      tPitch, d_qOff, d_tOff, d_idx, d_dist);
   MORB_HIP_CHECK(hipGetLastError());
@@ -1319,8 +1280,7 @@ int morb_stereo_match_batch(morb_matcher* m, const morb_extractor* e, int nframe
   MORB_REQUIRE(e->W > 0 && e->nimgLast >= 2 * nframes, MORB_ERR_INVALID,
                "the extractor must have processed the 2*nframes images (left = 2f, right = 2f+1) of this batch");
   MORB_REQUIRE(e->device == m->device, MORB_ERR_INVALID, "extractor and matcher live on different devices");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   int* sad = nullptr;
   uint8_t* stereoRec = nullptr;
   int rc = grow(m->sad, (size_t)nframes * cap, &sad);
@@ -1386,8 +1346,7 @@ int morb_bow_transform_batch(morb_matcher* m, int nimg, const uint8_t* d_desc, c
                              int* d_wordId, int* d_nodeId, void* stream) {
   MORB_REQUIRE(m && d_desc && d_count && d_nodeDesc && d_firstChild && d_wordId && d_nodeId, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nimg > 0 && cap > 0 && k > 0 && L > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   return launch_bow_transform(st, nimg, d_desc, d_count, cap, d_nodeDesc, d_firstChild, k, k, L, levelsup, d_wordId, d_nodeId, nullptr);
 }
 
@@ -1397,8 +1356,7 @@ int morb_bow_transform_tree_batch(morb_matcher* m, int nimg, const uint8_t* d_de
   MORB_REQUIRE(m && d_desc && d_count && d_nodeDesc && d_firstChild && d_childCount && d_wordId && d_nodeId, MORB_ERR_INVALID,
                "NULL argument");
   MORB_REQUIRE(nimg > 0 && cap > 0 && L > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   return launch_bow_transform(st, nimg, d_desc, d_count, cap, d_nodeDesc, d_firstChild, 0, BT_K, L, levelsup, d_wordId, d_nodeId, d_childCount);   // (nodes with more than ten children are handled inside)
 }
 
@@ -1499,8 +1457,7 @@ static int search_by_bow_impl(morb_matcher* m, int npairs, const int* d_kfImg, c
   int P = 1;
   while (P < cap) P <<= 1;
   MORB_REQUIRE((size_t)P * 8 <= 160 * 1024, MORB_ERR_UNSUPPORTED, "too many features per frame for the LDS sort");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   unsigned long long* sortA = nullptr;
   int* bin = nullptr;
   int rc = grow(m->sortA, (size_t)nimg * cap, &sortA);
@@ -1513,10 +1470,8 @@ static int search_by_bow_impl(morb_matcher* m, int npairs, const int* d_kfImg, c
   hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, st, d_matchF, nm, -1);
   int* matched2 = nullptr;
   if (d_hasMP2) {   // vbMatched2 of the general path (nodes with very many features)
-    void* w = nullptr;
-    rc = morb_matcher_workspace(m, 7, sizeof(int) * nm, &w);
+    rc = grow(m->scratch, nm, &matched2);
     if (rc != MORB_OK) return rc;
-    matched2 = (int*)w;
     hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, st, matched2, nm, 0);
   }
   MORB_REQUIRE(cap < 65536 && (size_t)cap * 18 <= 160 * 1024, MORB_ERR_UNSUPPORTED, "too many features per frame for the LDS-resident node tables");
@@ -1542,8 +1497,7 @@ int morb_search_by_bow_batch(morb_matcher* m, int npairs, const int* d_kfImg, co
 int morb_distinctive_descriptors_batch(morb_matcher* m, int nMP, const int* d_start, const uint8_t* d_desc, int* d_bestIdx,
                                        void* stream) {
   MORB_REQUIRE(m && d_start && d_desc && d_bestIdx && nMP >= 0, MORB_ERR_INVALID, "bad argument");
-  MORB_HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  MORB_ENTER(st, m, stream);
   if (nMP) hipLaunchKernelGGL(k_distinctive, dim3(nMP), dim3(64), 0, st, d_start, d_desc, d_bestIdx);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;

@@ -30,7 +30,6 @@
 #include <vector>
 
 #include "common.h"
-#include "hip_owned.h"
 #include "internal_abi.h"
 #include "kb8.h"
 #include "dense_ldlt.h"
@@ -2247,25 +2246,6 @@ __global__ void k_ba_reset(BaDev pb, const float* __restrict__ pose0, const floa
 }  // namespace
 
 // =====================================================================================================
-struct morb_optimizer {
-  int device = 0;
-  morb::Stream stream;
-  // grid-mode LocalBA runs pairs of independent small phases side by side (per-point / per-keyframe builds, Schur
-  // complement / reduced right-hand side): fork-join on a side stream
-  morb::Stream side;
-  morb::Event evFork, evJoin;
-  // grow-only buffers (hip_owned.h: growth neither waits nor frees — Optimizer.h:46-139 is all-static and entered from three threads, and a
-  // tracking-thread call must not wait for the LocalBundleAdjustment another thread has running on this device)
-  morb::DeviceGrow work;       // device workspace of the one-shot entry points (morb_local_inertial_ba, the one-shot LocalBundleAdjustment)
-  morb::DeviceGrow spill;      // device buffer of the BATCH entry points: edge lists that do not fit the LDS
-  morb::PinnedGrow stage;      // pinned host buffer: the one-shot entry points gather their inputs here for a single upload
-  morb::PinnedArray<int> lmWords;   // 16 pinned, device-mapped ints: LM state mirror of the one-shot entry points (device-side LM control)
-  bool arenaCreate = false;    // morb_ba_problem_create carves the problem from `work` / `stage` (the one-shot entry points set this around the call)
-  int exactOrder = 1;             // PoseOptimization: 1 (default) = edge-order sums, the LM path of g2o decision for decision; 0 = tree sums
-  int mfmaChain = 0;              // ... carried by the FP64 matrix core (this device passed k_mfma_order_selftest) instead of dependent v_add_f64
-  int mfmaSelftest = -1;          // what k_mfma_order_selftest said on this device: 1 passed, 0 rejected, -1 not run (MORB_PO2_CHAIN forced the choice) or failed to run
-};
-
 struct morb_ba_problem {
   morb_optimizer* opt = nullptr;
   BaDev h;                 // host copy of the device descriptor
@@ -2289,6 +2269,41 @@ struct morb_ba_problem {
   size_t globalLds = 0;      // dynamic LDS of k_g_ldlt_global
   int panelInLds = 1;
 };
+
+// the fisheye rig of a call: KB8 cameras and Trl7 = (qx, qy, qz, qw, tx, ty, tz)
+static Rig make_rig(const float* camL8, const float* camR8, const float* Trl7) {
+  Rig rig;
+  memcpy(rig.kbL, camL8, 32);
+  memcpy(rig.kbR, camR8, 32);
+  {  // g2o::SE3Quat(Trl.unit_quaternion().cast<double>(), Trl.translation().cast<double>()) incl. normalisation
+    double q[4] = {Trl7[0], Trl7[1], Trl7[2], Trl7[3]};
+    if (q[3] < 0) for (double& c : q) c = -c;
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) rig.Trl.q[i] = q[i] / n;
+    for (int i = 0; i < 3; ++i) rig.Trl.t[i] = Trl7[4 + i];
+  }
+  return rig;
+}
+
+// PoseOptimization's dispatch: k_pose_opt2 where it has a form of this mode and size and the caller allows it, else the old k_pose_opt
+template <bool FISH>
+static int pose_optimization(const morb_optimizer* o, bool allowOpt2, int nframes, hipStream_t st, int cap, const int* d_count, const uint8_t* d_hasMP,
+                             const float* d_obs, const float* d_invSigma2, const float* d_Xw, const Cam& cam, const Rig& rig, const int* d_nLeft,
+                             float* d_pose, uint8_t* d_outlier, int* d_nInliers, int* d_stats) {
+  if (pose_opt2_covers(o->exactOrder != 0, o->mfmaChain != 0, cap) && allowOpt2 && !getenv("MORB_PO_OLD")) {
+    const int rc = launch_pose_opt2<FISH>(o->exactOrder != 0, o->mfmaChain != 0, nframes, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig, d_nLeft, d_pose,
+                                          d_outlier, d_nInliers, d_stats);
+    if (rc != MORB_OK) return rc;
+  } else if (o->exactOrder) {
+    hipLaunchKernelGGL((k_pose_opt<FISH, true, 256>), dim3(nframes), dim3(256), 0, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig,
+                       d_nLeft, d_pose, d_outlier, d_nInliers, d_stats);
+  } else {
+    hipLaunchKernelGGL((k_pose_opt<FISH, false, MORB_PO_NT>), dim3(nframes), dim3(MORB_PO_NT), 0, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig,
+                       d_nLeft, d_pose, d_outlier, d_nInliers, d_stats);
+  }
+  MORB_HIP_CHECK(hipGetLastError());
+  return MORB_OK;
+}
 
 extern "C" {
 
@@ -2324,18 +2339,7 @@ int morb_optimizer_create(morb_optimizer** out, int device) {
   return MORB_OK;
 }
 
-int morb_optimizer_device(const morb_optimizer* o) { return o ? o->device : 0; }
 void* morb_optimizer_stream(const morb_optimizer* o) { return o ? (void*)o->stream : nullptr; }
-int morb_optimizer_workspace(morb_optimizer* o, size_t bytes, void** out) {
-  MORB_REQUIRE(o && out, MORB_ERR_INVALID, "NULL argument");
-  return o->work.ensure(bytes, out);
-}
-
-int morb_optimizer_spill(morb_optimizer* o, size_t bytes, void** out) {
-  MORB_REQUIRE(o && out, MORB_ERR_INVALID, "NULL argument");
-  return o->spill.ensure(bytes, out);
-}
-
 int morb_optimizer_lm_words(morb_optimizer* o, int** host, int** dev) {
   MORB_REQUIRE(o && host && dev, MORB_ERR_INVALID, "NULL argument");
   if (!o->lmWords) {
@@ -2344,11 +2348,6 @@ int morb_optimizer_lm_words(morb_optimizer* o, int** host, int** dev) {
   }
   *host = o->lmWords; *dev = o->lmWords.dev();
   return MORB_OK;
-}
-
-int morb_optimizer_staging(morb_optimizer* o, size_t bytes, void** host) {
-  MORB_REQUIRE(o && host, MORB_ERR_INVALID, "NULL argument");
-  return o->stage.ensure(bytes, host);
 }
 
 int morb_optimizer_info(const morb_optimizer* o, int* mfma_chain, int* exact_order, int* mfma_selftest) {
@@ -2386,8 +2385,7 @@ int morb_pose_optimization_batch(morb_optimizer* o, int nframes, int cap, const 
                                  int* d_stats, void* stream) {
   MORB_REQUIRE(o && d_hasMP && d_obs && d_invSigma2 && d_Xw && d_pose && d_outlier && d_nInliers, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(o->device));
-  hipStream_t st = stream ? (hipStream_t)stream : o->stream;
+  MORB_ENTER(st, o, stream);
   Cam cam{fx, fy, cx, cy, bf};
   Rig rig;
   memset(&rig, 0, sizeof rig);
@@ -2395,18 +2393,8 @@ int morb_pose_optimization_batch(morb_optimizer* o, int nframes, int cap, const 
   // empty stage per pass — 0.447 against 0.400 ms per launch at 600 features; k_pose_opt's 256 threads with 2 - 3 edges each stay the faster
   // form there.  Frames of ~1200 features of which half hold a map point — tracking — are where the compaction of k_pose_opt2 pays.)
   const bool smallTree = !o->exactOrder && cap <= 640;
-  if (pose_opt2_covers(o->exactOrder != 0, o->mfmaChain != 0, cap) && !smallTree && !getenv("MORB_PO_OLD")) {
-    const int rc = launch_pose_opt2<false>(o->exactOrder != 0, o->mfmaChain != 0, nframes, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig, nullptr, d_pose,
-                                           d_outlier, d_nInliers, d_stats);
-    if (rc != MORB_OK) return rc;
-  } else
-  if (o->exactOrder) hipLaunchKernelGGL((k_pose_opt<false, true, 256>), dim3(nframes), dim3(256), 0, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig,
-                     (const int*)nullptr, d_pose, d_outlier, d_nInliers, d_stats);
-  else hipLaunchKernelGGL((k_pose_opt<false, false, MORB_PO_NT>), dim3(nframes), dim3(MORB_PO_NT), 0, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig,
-                     (const int*)nullptr, d_pose, d_outlier, d_nInliers, d_stats);
-
-  MORB_HIP_CHECK(hipGetLastError());
-  return MORB_OK;
+  return pose_optimization<false>(o, !smallTree, nframes, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig, nullptr, d_pose, d_outlier,
+                                  d_nInliers, d_stats);
 }
 
 int morb_pose_optimization_fisheye_batch(morb_optimizer* o, int nframes, int cap, const int* d_count, const int* d_nLeft,
@@ -2416,38 +2404,19 @@ int morb_pose_optimization_fisheye_batch(morb_optimizer* o, int nframes, int cap
   MORB_REQUIRE(o && d_count && d_nLeft && d_hasMP && d_obs && d_invSigma2 && d_Xw && camL8 && camR8 && Trl7 && d_pose && d_outlier &&
                    d_nInliers, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(o->device));
-  hipStream_t st = stream ? (hipStream_t)stream : o->stream;
+  MORB_ENTER(st, o, stream);
   Cam cam{0, 0, 0, 0, 0};
-  Rig rig;
-  memcpy(rig.kbL, camL8, 32);
-  memcpy(rig.kbR, camR8, 32);
-  {  // g2o::SE3Quat(Trl.unit_quaternion().cast<double>(), Trl.translation().cast<double>()) incl. normalisation
-    double q[4] = {Trl7[0], Trl7[1], Trl7[2], Trl7[3]};
-    if (q[3] < 0) for (double& c : q) c = -c;
-    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) rig.Trl.q[i] = q[i] / n;
-    for (int i = 0; i < 3; ++i) rig.Trl.t[i] = Trl7[4 + i];
-  }
-  if (pose_opt2_covers(o->exactOrder != 0, o->mfmaChain != 0, cap) && !getenv("MORB_PO_OLD")) {
-    const int rc = launch_pose_opt2<true>(o->exactOrder != 0, o->mfmaChain != 0, nframes, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig, d_nLeft, d_pose,
-                                          d_outlier, d_nInliers, d_stats);
-    if (rc != MORB_OK) return rc;
-  } else
-  if (o->exactOrder) hipLaunchKernelGGL((k_pose_opt<true, true, 256>), dim3(nframes), dim3(256), 0, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig,
-                     d_nLeft, d_pose, d_outlier, d_nInliers, d_stats);
-  else hipLaunchKernelGGL((k_pose_opt<true, false, MORB_PO_NT>), dim3(nframes), dim3(MORB_PO_NT), 0, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig,
-                     d_nLeft, d_pose, d_outlier, d_nInliers, d_stats);
-
-  MORB_HIP_CHECK(hipGetLastError());
-  return MORB_OK;
+  const Rig rig = make_rig(camL8, camR8, Trl7);
+  return pose_optimization<true>(o, true, nframes, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig, d_nLeft, d_pose, d_outlier,
+                                 d_nInliers, d_stats);
 }
 
-// morb_ba_problem_create, with the fisheye rig of morb_ba_problem_create_fisheye (nullptr: pinhole)
+// morb_ba_problem_create, with the fisheye rig of morb_ba_problem_create_fisheye (nullptr: pinhole).  arena: the problem of a one-shot
+// entry point, carved from the handle's `work` / `stage` / `lmWords` for the duration of that call (it owns no memory of its own)
 static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
                              int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
                              const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
-                             int lambdaInit100, const Rig* rig) {
+                             int lambdaInit100, const Rig* rig, bool arena) {
   MORB_REQUIRE(o && out && kfPose && kfFixed && mpPos && eKF && eMP && eObs && eInvSigma2, MORB_ERR_INVALID, "NULL argument");
   *out = nullptr;
   MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
@@ -2485,7 +2454,7 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
   // mode on the matrix cores, which only needs the number of entries (flop accounting): they skip the lists (0.3 ms of host work, 0.6 MB).
   std::vector<int> pairBlock, pairStart;
   std::vector<int2> pairEntries;
-  const bool wantPairs = !o->arenaCreate;
+  const bool wantPairs = !arena;
   size_t nPairEntriesCount = 0;
   if (!wantPairs) {
     for (int m = 0; m < nMP; ++m) {
@@ -2534,7 +2503,6 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
   // arrays behind them — because ~45 hipMalloc / hipFree pairs and ~25 synchronous copies were 3.5 ms of a 4.7 ms call.  A dry run of the carve
   // sizes the block.  The one-shot entry points (arena mode) take the block, the pinned staging buffer and the pinned words from the optimizer
   // handle; a persistent problem (three-step API) owns its block and words.
-  const bool arena = o->arenaCreate;
   bool dry = true;
   size_t upOff = 0, devOff = 0, upCap = 0, devCap = 0;
   char *aBase = nullptr, *stage = nullptr;
@@ -2627,9 +2595,7 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
   upCap = upOff; devCap = devOff; upOff = devOff = 0; dry = false;
   std::vector<char> hostStage;   // a persistent problem's staging: pageable, the upload is waited for below
   if (arena) {
-    void *w = nullptr, *sg = nullptr;
-    if (morb_optimizer_workspace(o, upCap + devCap, &w) != MORB_OK || morb_optimizer_staging(o, upCap, &sg) != MORB_OK) fail = true;
-    aBase = (char*)w; stage = (char*)sg;
+    if (grow(o->work, upCap + devCap, &aBase) != MORB_OK || grow(o->stage, upCap, &stage) != MORB_OK) fail = true;
   } else {
     if (p->mem.alloc(upCap + devCap) != hipSuccess) fail = true;
     hostStage.resize(upCap);
@@ -2666,7 +2632,7 @@ int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, co
                            int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
                            const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
                            int lambdaInit100) {
-  return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf, lambdaInit100, nullptr);
+  return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf, lambdaInit100, nullptr, false);
 }
 
 void morb_ba_problem_destroy(morb_ba_problem* p) {
@@ -2677,30 +2643,28 @@ void morb_ba_problem_destroy(morb_ba_problem* p) {
   delete p;
 }
 
-int morb_ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
-                                   int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs2,
-                                   const uint8_t* eRight, const float* eInvSigma2, const float* camL8, const float* camR8,
-                                   const float* Trl7, int lambdaInit100) {
+static int ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                                     int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs2,
+                                     const uint8_t* eRight, const float* eInvSigma2, const float* camL8, const float* camR8,
+                                     const float* Trl7, int lambdaInit100, bool arena) {
   MORB_REQUIRE(out && eObs2 && eRight && camL8 && camR8 && Trl7, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nE > 0, MORB_ERR_INVALID, "empty problem");
   // the edge kind travels in the third observation slot: -2 = EdgeSE3ProjectXYZ with the left KB8 camera,
   // -3 = EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl)
   std::vector<float> obs3((size_t)nE * 3);
   for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = eRight[e] ? -3.0f : -2.0f; }
-  Rig rig;
-  memcpy(rig.kbL, camL8, 32);
-  memcpy(rig.kbR, camR8, 32);
-  {  // g2o::SE3Quat(Trl.unit_quaternion().cast<double>(), Trl.translation().cast<double>()) incl. normalisation
-    double q[4] = {Trl7[0], Trl7[1], Trl7[2], Trl7[3]};
-    if (q[3] < 0) for (double& c : q) c = -c;
-    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) rig.Trl.q[i] = q[i] / n;
-    for (int i = 0; i < 3; ++i) rig.Trl.t[i] = Trl7[4 + i];
-  }
+  const Rig rig = make_rig(camL8, camR8, Trl7);
   return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, 0.f, 0.f, 0.f, 0.f, 0.f,
-                           lambdaInit100, &rig);
+                           lambdaInit100, &rig, arena);
 }
 
+int morb_ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                                   int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs2,
+                                   const uint8_t* eRight, const float* eInvSigma2, const float* camL8, const float* camR8,
+                                   const float* Trl7, int lambdaInit100) {
+  return ba_problem_create_fisheye(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs2, eRight, eInvSigma2, camL8, camR8, Trl7,
+                                   lambdaInit100, false);
+}
 
 int morb_ba_set_mode(morb_ba_problem* p, int mode) {
   MORB_REQUIRE(p && (mode == 0 || mode == 1), MORB_ERR_INVALID, "mode must be 0 (grid) or 1 (persistent workgroup)");
@@ -2718,8 +2682,7 @@ int morb_ba_set_stop(morb_ba_problem* p, int stop) {
 
 int morb_ba_solve(morb_ba_problem* p, void* stream) {
   MORB_REQUIRE(p, MORB_ERR_INVALID, "NULL problem");
-  MORB_HIP_CHECK(hipSetDevice(p->opt->device));
-  hipStream_t st = stream ? (hipStream_t)stream : p->opt->stream;
+  MORB_ENTER(st, p->opt, stream);
   MORB_HIP_CHECK(p->solved.create(hipEventDisableTiming));
   struct RecordOnExit { hipEvent_t ev; hipStream_t st; ~RecordOnExit() { (void)hipEventRecord(ev, st); } } recordOnExit{p->solved, st};
   const int n = std::max(p->h.nKF, p->h.nMP * 3);
@@ -2826,23 +2789,24 @@ int morb_ba_results(morb_ba_problem* p, float* kfPose, float* mpPos, uint8_t* er
   return MORB_OK;
 }
 
+// the one-shot LocalBundleAdjustment behind its create call (p lives in the handle's workspace for the duration of the call)
+static int local_ba_solve_once(morb_ba_problem* p, const unsigned char* stopFlag, float* kfPose, float* mpPos, uint8_t* eraseFlag, int* stats2) {
+  p->userStop = stopFlag;   // optimizer.setForceStopFlag(pbStopFlag) (:1142): the LM loop polls the caller's flag at every iteration and trial
+  int rc = morb_ba_solve(p, nullptr);
+  if (rc == MORB_OK) rc = morb_ba_results(p, kfPose, mpPos, eraseFlag, stats2);
+  morb_ba_problem_destroy(p);
+  return rc;
+}
+
 int morb_local_bundle_adjustment(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
                                  int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
                                  float fx, float fy, float cx, float cy, float bf, int lambdaInit100,
                                  const unsigned char* stopFlag, uint8_t* eraseFlag, int* stats2) {
   if (stopFlag && *(const volatile unsigned char*)stopFlag) { if (stats2) stats2[0] = stats2[1] = 0; return MORB_OK; }  // :1355-1356
   morb_ba_problem* p = nullptr;
-  MORB_REQUIRE(o, MORB_ERR_INVALID, "NULL optimizer");
-  o->arenaCreate = true;   // the problem lives in the handle's workspace for the duration of this call
-  int rc = morb_ba_problem_create(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf,
-                                  lambdaInit100);
-  o->arenaCreate = false;
-  if (rc != MORB_OK) return rc;
-  p->userStop = stopFlag;   // optimizer.setForceStopFlag(pbStopFlag) (:1142): the LM loop polls the caller's flag at every iteration and trial
-  rc = morb_ba_solve(p, nullptr);
-  if (rc == MORB_OK) rc = morb_ba_results(p, kfPose, mpPos, eraseFlag, stats2);
-  morb_ba_problem_destroy(p);
-  return rc;
+  const int rc = ba_problem_create(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf, lambdaInit100,
+                                   nullptr, true);
+  return rc != MORB_OK ? rc : local_ba_solve_once(p, stopFlag, kfPose, mpPos, eraseFlag, stats2);
 }
 
 int morb_local_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
@@ -2851,17 +2815,9 @@ int morb_local_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPo
                                          int lambdaInit100, const unsigned char* stopFlag, uint8_t* eraseFlag, int* stats2) {
   if (stopFlag && *(const volatile unsigned char*)stopFlag) { if (stats2) stats2[0] = stats2[1] = 0; return MORB_OK; }  // :1355-1356
   morb_ba_problem* p = nullptr;
-  MORB_REQUIRE(o, MORB_ERR_INVALID, "NULL optimizer");
-  o->arenaCreate = true;
-  int rc = morb_ba_problem_create_fisheye(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs2, eRight, eInvSigma2, camL8,
-                                          camR8, Trl7, lambdaInit100);
-  o->arenaCreate = false;
-  if (rc != MORB_OK) return rc;
-  p->userStop = stopFlag;   // optimizer.setForceStopFlag(pbStopFlag) (:1142): the LM loop polls the caller's flag at every iteration and trial
-  rc = morb_ba_solve(p, nullptr);
-  if (rc == MORB_OK) rc = morb_ba_results(p, kfPose, mpPos, eraseFlag, stats2);
-  morb_ba_problem_destroy(p);
-  return rc;
+  const int rc = ba_problem_create_fisheye(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs2, eRight, eInvSigma2, camL8, camR8, Trl7,
+                                           lambdaInit100, true);
+  return rc != MORB_OK ? rc : local_ba_solve_once(p, stopFlag, kfPose, mpPos, eraseFlag, stats2);
 }
 
 }  // extern "C"

@@ -28,11 +28,6 @@
 
 using namespace morb;
 
-struct morb_matcher;  // defined in matcher.hip
-extern "C" {
-void* morb_matcher_stream(const morb_matcher*);
-}
-
 namespace {
 
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;
@@ -1366,6 +1361,20 @@ static void level_thresholds(const morb_frame_params* P, float* thr16) {
   memcpy(thr16, ct, sizeof ct);
 }
 
+// device copy of the level thresholds and, behind them, the KB8 camera (isInFrustum and the keyframe projections share the table)
+static int upload_ratio_thresholds(morb_matcher* m, const morb_frame_params* P, const float* cam8, hipStream_t st, const float** d_thr,
+                                   const float** d_kb8) {
+  float thr[24];   // 16 level thresholds + the 8 camera parameters of the KB8 variant
+  level_thresholds(P, thr);
+  for (int n = 0; n < 8; ++n) thr[16 + n] = cam8 ? cam8[n] : 0.f;
+  void* d = nullptr;
+  int rc = morb_matcher_const(m, cam8 ? morb_matcher::kThresholdsKB8 : morb_matcher::kThresholdsPinhole, thr, sizeof thr, &d, st);
+  if (rc != MORB_OK) return rc;
+  *d_thr = (const float*)d;
+  *d_kb8 = cam8 ? (const float*)d + 16 : nullptr;
+  return MORB_OK;
+}
+
 static int frustum_impl(morb_matcher* m, const morb_frame_params* P, const float* cam8, int nframes, const float* d_Rcw,
                         const float* d_tcw, const float* d_Ow, int mpCap, const int* d_nMP, const float* d_Pw,
                         const float* d_normal, const float* d_maxDist, const float* d_minDist, float viewingCosLimit,
@@ -1374,17 +1383,12 @@ static int frustum_impl(morb_matcher* m, const morb_frame_params* P, const float
   MORB_REQUIRE(m && P && d_Rcw && d_tcw && d_Ow && d_nMP && d_Pw && d_normal && d_maxDist && d_minDist && d_inView && d_projX &&
                    d_projY && d_projXR && d_depth && d_level && d_viewCos, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && mpCap > 0 && P->nlevels >= 1 && P->nlevels <= 16, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  float thr[24];   // 16 level thresholds + the 8 camera parameters of the KB8 variant
-  level_thresholds(P, thr);
-  for (int n = 0; n < 8; ++n) thr[16 + n] = cam8 ? cam8[n] : 0.f;
-  void* d_thr = nullptr;
-  int rc = morb_matcher_const(m, cam8 ? 1 : 0, thr, sizeof thr, &d_thr, st);   // uploaded once per camera, not per call
+  MORB_ENTER(st, m, stream);
+  const float *d_thr = nullptr, *d_kb8 = nullptr;
+  int rc = upload_ratio_thresholds(m, P, cam8, st, &d_thr, &d_kb8);   // uploaded once per camera, not per call
   if (rc != MORB_OK) return rc;
-  const float* d_kb8 = cam8 ? (const float*)d_thr + 16 : nullptr;
   hipLaunchKernelGGL(k_frustum, dim3(div_up(mpCap, 256), nframes), dim3(256), 0, st, *P, d_Rcw, d_tcw, d_Ow, mpCap, d_nMP, d_Pw,
-                     d_normal, d_maxDist, d_minDist, viewingCosLimit, (const float*)d_thr, (const float*)d_kb8, d_inView, d_projX,
+                     d_normal, d_maxDist, d_minDist, viewingCosLimit, d_thr, d_kb8, d_inView, d_projX,
                      d_projY, d_projXR, d_depth, d_level, d_viewCos);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
@@ -1404,12 +1408,12 @@ int morb_is_in_frustum_kb8_batch(morb_matcher* m, const morb_frame_params* P, co
                                  const float* d_normal, const float* d_maxDist, const float* d_minDist, float viewingCosLimit,
                                  uint8_t* d_inView, float* d_projX, float* d_projY, float* d_depth, int* d_level,
                                  float* d_viewCos, void* stream) {
-  MORB_REQUIRE(cam8, MORB_ERR_INVALID, "NULL camera");
-  void* xr = nullptr;   // the pinhole-only mTrackProjXR slot of the shared kernel
-  int rc = morb_matcher_workspace(m, 7, sizeof(float) * (size_t)nframes * mpCap, &xr);
+  MORB_REQUIRE(m && cam8, MORB_ERR_INVALID, "NULL matcher or camera");
+  float* xr = nullptr;   // the pinhole-only mTrackProjXR slot of the shared kernel
+  int rc = grow(m->scratch, (size_t)nframes * mpCap, &xr);
   if (rc != MORB_OK) return rc;
   return frustum_impl(m, P, cam8, nframes, d_R, d_t, d_twc, mpCap, d_nMP, d_Pw, d_normal, d_maxDist, d_minDist, viewingCosLimit,
-                      d_inView, d_projX, d_projY, (float*)xr, d_depth, d_level, d_viewCos, stream);
+                      d_inView, d_projX, d_projY, xr, d_depth, d_level, d_viewCos, stream);
 }
 
 static int window_search(morb_matcher* m, const morb_frame_params* P, int mode, int nframes, int qCap, const int* d_nQ,
@@ -1418,19 +1422,19 @@ static int window_search(morb_matcher* m, const morb_frame_params* P, int mode, 
                          const uint8_t* d_blocked, float nnratio, int thAccept, int checkOri, int* d_match, int* d_nmatches,
                          float* d_prevMatched, hipStream_t st, const int* d_l2r = nullptr, const int* d_r2l = nullptr,
                          const int* d_nLeft = nullptr, bool ranged = false) {   // ranged: queries carry a feature-index range (jLo / jHi)
-  void *cand = nullptr, *cnt = nullptr, *ej = nullptr, *eb = nullptr;
   const int tier = morbst::search_tier(cap, qCap, !((mode == 0 || mode == 1) && !ranged) || getenv("MORB_SERIAL_RESOLVE") != nullptr);
   if (tier != 3) {
     // one launch, one workgroup per frame: grid in LDS, candidate lists, blocked-feature fixed point (k_search)
     const int withDesc = tier == 1 ? 1 : 0;
     const size_t lds = morbst::search_lds_bytes(cap, qCap, withDesc != 0);
-    int rc = morb_matcher_workspace(m, 0, sizeof(uint32_t) * (size_t)nframes * qCap * SEARCH_CAP, &cand);
+    uint32_t* cand = nullptr;
+    int rc = grow(m->candKeys, (size_t)nframes * qCap * SEARCH_CAP, &cand);
     if (rc != MORB_OK) return rc;
 #define MORB_SEARCH(MODE, WD)                                                                                                              \
   do {                                                                                                                                     \
     MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search<MODE, WD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
     hipLaunchKernelGGL((k_search<MODE, WD>), dim3(nframes), dim3(SEARCH_THREADS), lds, st, *P, qCap, d_nQ, d_qs, d_qDesc, d_qHasObs, d_fImg, cap, \
-                       d_count, d_kps, d_desc, d_uRight, d_blocked, (uint32_t*)cand, nnratio, thAccept, checkOri, d_match, d_nmatches);         \
+                       d_count, d_kps, d_desc, d_uRight, d_blocked, cand, nnratio, thAccept, checkOri, d_match, d_nmatches);                    \
   } while (0)
     if (mode == 0) { if (withDesc) MORB_SEARCH(0, true); else MORB_SEARCH(0, false); }
     else { if (withDesc) MORB_SEARCH(1, true); else MORB_SEARCH(1, false); }
@@ -1438,17 +1442,19 @@ static int window_search(morb_matcher* m, const morb_frame_params* P, int mode, 
     MORB_HIP_CHECK(hipGetLastError());
     return MORB_OK;
   }
-  int rc = morb_matcher_workspace(m, 0, sizeof(unsigned long long) * (size_t)nframes * qCap * CAND_CAP, &cand);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 1, sizeof(int) * (size_t)nframes * qCap, &cnt);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 2, sizeof(int) * (size_t)nframes * qCap, &ej);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 3, sizeof(int) * (size_t)nframes * qCap, &eb);
+  unsigned long long* cand = nullptr;
+  int *cnt = nullptr, *ej = nullptr, *eb = nullptr;
+  int rc = grow(m->candKeys, (size_t)nframes * qCap * CAND_CAP, &cand);
+  if (rc == MORB_OK) rc = grow(m->candCount, (size_t)nframes * qCap, &cnt);
+  if (rc == MORB_OK) rc = grow(m->evictJ, (size_t)nframes * qCap, &ej);
+  if (rc == MORB_OK) rc = grow(m->evictB, (size_t)nframes * qCap, &eb);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_candidates, dim3(div_up(qCap, 4), nframes), dim3(256), 0, st, *P, qCap, d_qs, d_qDesc, d_fImg, cap, d_count,
-                     d_kps, d_desc, d_uRight, (unsigned long long*)cand, (int*)cnt, (mode == 3 || mode == 4) ? 1 : 0);
+                     d_kps, d_desc, d_uRight, cand, cnt, (mode == 3 || mode == 4) ? 1 : 0);
 #define MORB_RESOLVE(MODE, SMEM)                                                                                             \
   hipLaunchKernelGGL(k_resolve<MODE>, dim3(nframes), dim3(64), (SMEM), st, *P, qCap, d_nQ, d_qs, d_qDesc, d_qHasObs, d_fImg, cap, \
-                     d_count, d_kps, d_desc, d_uRight, d_blocked, (const unsigned long long*)cand, (const int*)cnt, nnratio,   \
-                     thAccept, checkOri, d_match, d_nmatches, (int*)ej, (int*)eb, d_prevMatched, d_l2r, d_r2l, d_nLeft)
+                     d_count, d_kps, d_desc, d_uRight, d_blocked, cand, cnt, nnratio, thAccept, checkOri, d_match, d_nmatches, ej, eb, \
+                     d_prevMatched, d_l2r, d_r2l, d_nLeft)
   if (mode == 1) MORB_RESOLVE(1, (size_t)cap);
   else if (mode == 3) MORB_RESOLVE(3, (size_t)cap);
   else if (mode == 4) MORB_RESOLVE(4, (size_t)cap);
@@ -1472,14 +1478,13 @@ int morb_search_by_projection_mps_batch(morb_matcher* m, const morb_frame_params
   MORB_REQUIRE(m && P && d_fImg && d_count && d_kps && d_desc && d_nMP && d_inView && d_isBad && d_depth && d_projX && d_projY &&
                    d_projXR && d_level && d_viewCos && d_mpDesc && d_mpHasObs && d_matchF && d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && cap <= 65535 && mpCap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  void* qs = nullptr;
-  int rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)nframes * mpCap, &qs);
+  MORB_ENTER(st, m, stream);
+  Query* qs = nullptr;
+  int rc = grow(m->queries, (size_t)nframes * mpCap, &qs);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_mps, dim3(div_up(mpCap, 256), nframes), dim3(256), 0, st, *P, mpCap, d_nMP, d_inView, d_isBad, d_depth,
-                     d_projX, d_projY, d_projXR, d_level, d_viewCos, th, bFarPoints, thFarPoints, (Query*)qs);
-  return window_search(m, P, 1, nframes, mpCap, d_nMP, (const Query*)qs, d_mpDesc, d_mpHasObs, d_fImg, cap, d_count, d_kps,
+                     d_projX, d_projY, d_projXR, d_level, d_viewCos, th, bFarPoints, thFarPoints, qs);
+  return window_search(m, P, 1, nframes, mpCap, d_nMP, qs, d_mpDesc, d_mpHasObs, d_fImg, cap, d_count, d_kps,
                        d_desc, d_uRight, d_blocked, nnratio, TH_HIGH, 0, d_matchF, d_nmatches, nullptr, st);
 }
 
@@ -1497,16 +1502,15 @@ int morb_search_by_projection_mps_fisheye_batch(morb_matcher* m, const morb_fram
                    d_isBad && d_depthL && d_projXL && d_projYL && d_levelL && d_viewCosL && d_projXR && d_projYR && d_levelR &&
                    d_viewCosR && d_mpDesc && d_mpHasObs && d_matchF && d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && cap <= 65535 && mpCap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  void* qs = nullptr;
-  int rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)nframes * mpCap * 2, &qs);
+  MORB_ENTER(st, m, stream);
+  Query* qs = nullptr;
+  int rc = grow(m->queries, (size_t)nframes * mpCap * 2, &qs);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_mps_fisheye, dim3(div_up(mpCap, 256), nframes), dim3(256), 0, st, *P, mpCap, d_nMP, d_fImg, d_count,
                      d_nLeft, d_inViewL, d_inViewR, d_isBad, d_depthL, d_projXL, d_projYL, d_levelL, d_viewCosL, d_projXR, d_projYR,
-                     d_levelR, d_viewCosR, th, bFarPoints, thFarPoints, (Query*)qs);
+                     d_levelR, d_viewCosR, th, bFarPoints, thFarPoints, qs);
   // 2 queries per map point; the resolve pass (mode 3) walks them as (left, right) pairs in map-point order
-  return window_search(m, P, 3, nframes, 2 * mpCap, d_nMP, (const Query*)qs, d_mpDesc, d_mpHasObs, d_fImg, cap, d_count, d_kps,
+  return window_search(m, P, 3, nframes, 2 * mpCap, d_nMP, qs, d_mpDesc, d_mpHasObs, d_fImg, cap, d_count, d_kps,
                        d_desc, nullptr, d_blocked, nnratio, TH_HIGH, 0, d_matchF, d_nmatches, nullptr, st, d_l2r, d_r2l, d_nLeft);
 }
 
@@ -1520,18 +1524,17 @@ int morb_search_by_projection_last_batch(morb_matcher* m, const morb_frame_param
   MORB_REQUIRE(m && P && d_curImg && d_lastImg && d_count && d_kps && d_desc && d_Tcw && d_lastValid && d_lastXw && d_lastMPdesc &&
                    d_lastMPhasObs && d_bForward && d_bBackward && d_matchCur && d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && cap <= 65535, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  void* qs = nullptr;
-  int rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)nframes * cap, &qs);
+  MORB_ENTER(st, m, stream);
+  Query* qs = nullptr;
+  int rc = grow(m->queries, (size_t)nframes * cap, &qs);
   if (rc != MORB_OK) return rc;
   // the number of queries of frame f is the feature count of its LAST image (written by the same launch)
-  void* nq = nullptr;
-  rc = morb_matcher_workspace(m, 6, sizeof(int) * (size_t)nframes, &nq);
+  int* nq = nullptr;
+  rc = grow(m->queryCount, (size_t)nframes, &nq);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_last, dim3(div_up(cap, 256), nframes), dim3(256), 0, st, *P, cap, d_count, d_lastImg, d_kps, d_lastValid,
-                     d_lastXw, d_Tcw, th, d_bForward, d_bBackward, (Query*)qs, (int*)nq);
-  return window_search(m, P, 0, nframes, cap, (const int*)nq, (const Query*)qs, d_lastMPdesc, d_lastMPhasObs, d_curImg, cap,
+                     d_lastXw, d_Tcw, th, d_bForward, d_bBackward, qs, nq);
+  return window_search(m, P, 0, nframes, cap, nq, qs, d_lastMPdesc, d_lastMPhasObs, d_curImg, cap,
                        d_count, d_kps, d_desc, d_curURight, d_curBlocked, 0.f, TH_HIGH, checkOri, d_matchCur, d_nmatches, nullptr, st);
 }
 
@@ -1547,24 +1550,23 @@ int morb_search_by_projection_last_fisheye_batch(morb_matcher* m, const morb_fra
                    d_lastXw && d_lastMPdesc && d_lastMPhasObs && d_bForward && d_bBackward && d_matchCur && d_nmatches,
                MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && cap <= 65535, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   float ct[15];
   for (int i = 0; i < 8; ++i) ct[i] = cam8[i];
   for (int i = 0; i < 7; ++i) ct[8 + i] = Trl7[i];
   void* d_ct = nullptr;
-  int rc = morb_matcher_const(m, 2, ct, sizeof ct, &d_ct, st);
+  int rc = morb_matcher_const(m, morb_matcher::kRigLastFrame, ct, sizeof ct, &d_ct, st);
   if (rc != MORB_OK) return rc;
-  void* qs = nullptr;
-  rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)nframes * cap * 2, &qs);
+  Query* qs = nullptr;
+  rc = grow(m->queries, (size_t)nframes * cap * 2, &qs);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_last_fisheye, dim3(div_up(cap, 256), nframes), dim3(256), 0, st, *P, cap, d_count, d_lastImg, d_curImg,
-                     d_nLeftCur, d_kps, d_lastValid, d_lastXw, d_Tcw, (const float*)d_ct, th, d_bForward, d_bBackward, (Query*)qs);
-  void* nq = nullptr;
-  rc = morb_matcher_workspace(m, 6, sizeof(int) * (size_t)nframes, &nq);
+                     d_nLeftCur, d_kps, d_lastValid, d_lastXw, d_Tcw, (const float*)d_ct, th, d_bForward, d_bBackward, qs);
+  int* nq = nullptr;
+  rc = grow(m->queryCount, (size_t)nframes, &nq);
   if (rc != MORB_OK) return rc;
-  hipLaunchKernelGGL(k_gather_counts, dim3(div_up(nframes, 256)), dim3(256), 0, st, d_count, d_lastImg, nframes, (int*)nq);
-  return window_search(m, P, 4, nframes, 2 * cap, (const int*)nq, (const Query*)qs, d_lastMPdesc, d_lastMPhasObs, d_curImg, cap,
+  hipLaunchKernelGGL(k_gather_counts, dim3(div_up(nframes, 256)), dim3(256), 0, st, d_count, d_lastImg, nframes, nq);
+  return window_search(m, P, 4, nframes, 2 * cap, nq, qs, d_lastMPdesc, d_lastMPhasObs, d_curImg, cap,
                        d_count, d_kps, d_desc, nullptr, d_curBlocked, 0.f, TH_HIGH, checkOri, d_matchCur, d_nmatches, nullptr, st);
 }
 
@@ -1577,21 +1579,18 @@ static int search_by_projection_kf_impl(morb_matcher* m, const morb_frame_params
   MORB_REQUIRE(m && P && d_curImg && d_kfImg && d_count && d_kps && d_desc && d_Tcw && d_Ow && d_kfValid && d_Xw && d_maxDist &&
                    d_minDist && d_mpDesc && d_matchCur && d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && cap <= 65535, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  float thr[24] = {0};   // (same table as isInFrustum's, so the two share constant slots 0 / 1)
-  level_thresholds(P, thr);
-  for (int n = 0; n < 8; ++n) thr[16 + n] = cam8 ? cam8[n] : 0.f;
-  void *d_thr = nullptr, *qs = nullptr, *nq = nullptr;
-  int rc = morb_matcher_const(m, cam8 ? 1 : 0, thr, sizeof thr, &d_thr, st);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)nframes * cap, &qs);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 6, sizeof(int) * (size_t)nframes, &nq);
+  MORB_ENTER(st, m, stream);
+  const float *d_thr = nullptr, *d_kb8 = nullptr;
+  Query* qs = nullptr;
+  int* nq = nullptr;
+  int rc = upload_ratio_thresholds(m, P, cam8, st, &d_thr, &d_kb8);
+  if (rc == MORB_OK) rc = grow(m->queries, (size_t)nframes * cap, &qs);
+  if (rc == MORB_OK) rc = grow(m->queryCount, (size_t)nframes, &nq);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_kf, dim3(div_up(cap, 256), nframes), dim3(256), 0, st, *P, cap, d_count, d_kfImg, d_kps, d_kfValid, d_Xw,
-                     d_maxDist, d_minDist, d_Tcw, d_Ow, th, (const float*)d_thr, (Query*)qs, cam8 ? (const float*)d_thr + 16 : (const float*)nullptr,
-                     d_nLeftCur);
-  hipLaunchKernelGGL(k_gather_counts, dim3(div_up(nframes, 256)), dim3(256), 0, st, d_count, d_kfImg, nframes, (int*)nq);
-  return window_search(m, P, 0, nframes, cap, (const int*)nq, (const Query*)qs, d_mpDesc, nullptr, d_curImg, cap, d_count, d_kps,
+                     d_maxDist, d_minDist, d_Tcw, d_Ow, th, d_thr, qs, d_kb8, d_nLeftCur);
+  hipLaunchKernelGGL(k_gather_counts, dim3(div_up(nframes, 256)), dim3(256), 0, st, d_count, d_kfImg, nframes, nq);
+  return window_search(m, P, 0, nframes, cap, nq, qs, d_mpDesc, nullptr, d_curImg, cap, d_count, d_kps,
                        d_desc, nullptr, d_curHasMP, 0.f, ORBdist, checkOri, d_matchCur, d_nmatches, nullptr, st, nullptr, nullptr, nullptr,
                        d_nLeftCur != nullptr);
 }
@@ -1626,20 +1625,21 @@ int morb_search_for_initialization_batch(morb_matcher* m, const morb_frame_param
   MORB_REQUIRE(npairs > 0 && cap > 0 && cap <= 65535, MORB_ERR_INVALID, "bad sizes");
   // (before any launch: a refused call leaves d_matches12, d_nmatches and d_prevMatched as they were)
   MORB_REQUIRE((size_t)cap * 8 <= 64 * 1024, MORB_ERR_UNSUPPORTED, "too many features for SearchForInitialization's LDS state");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  void *qs = nullptr, *nq = nullptr, *qd = nullptr;
-  int rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)npairs * cap, &qs);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 6, sizeof(int) * (size_t)npairs, &nq);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 7, (size_t)npairs * cap * 32, &qd);
+  MORB_ENTER(st, m, stream);
+  Query* qs = nullptr;
+  int* nq = nullptr;
+  uint8_t* qd = nullptr;
+  int rc = grow(m->queries, (size_t)npairs * cap, &qs);
+  if (rc == MORB_OK) rc = grow(m->queryCount, (size_t)npairs, &nq);
+  if (rc == MORB_OK) rc = grow(m->scratch, (size_t)npairs * cap * 32, &qd);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_init, dim3(div_up(cap, 256), npairs), dim3(256), 0, st, cap, d_count, d_img1, d_kps, d_prevMatched,
-                     windowSize, (Query*)qs);
-  hipLaunchKernelGGL(k_gather_counts, dim3(div_up(npairs, 256)), dim3(256), 0, st, d_count, d_img1, npairs, (int*)nq);
+                     windowSize, qs);
+  hipLaunchKernelGGL(k_gather_counts, dim3(div_up(npairs, 256)), dim3(256), 0, st, d_count, d_img1, npairs, nq);
   // query descriptors = F1's descriptor rows, gathered per pair
-  hipLaunchKernelGGL(k_gather_desc, dim3(div_up(cap * 2, 256), npairs), dim3(256), 0, st, d_desc, d_img1, cap, (uint8_t*)qd);
+  hipLaunchKernelGGL(k_gather_desc, dim3(div_up(cap * 2, 256), npairs), dim3(256), 0, st, d_desc, d_img1, cap, qd);
   hipLaunchKernelGGL(k_fill_m1, dim3(div_up(npairs * cap, 256)), dim3(256), 0, st, d_matches12, npairs * cap);
-  return window_search(m, P, 2, npairs, cap, (const int*)nq, (const Query*)qs, (const uint8_t*)qd, nullptr, d_img2, cap, d_count,
+  return window_search(m, P, 2, npairs, cap, nq, qs, qd, nullptr, d_img2, cap, d_count,
                        d_kps, d_desc, nullptr, nullptr, nnratio, TH_LOW, checkOri, d_matches12, d_nmatches, d_prevMatched, st);
 }
 
@@ -1705,20 +1705,7 @@ __global__ __launch_bounds__(256) void k_rot_filter12(const int* __restrict__ co
 }  // namespace
 
 // ---- M7 host side ---------------------------------------------------------------------------------------------------
-static int upload_ratio_thresholds(morb_matcher* m, const morb_frame_params* P, const float* cam8, hipStream_t st, const float** d_thr,
-                                   const float** d_kb8) {
-  float thr[24];
-  level_thresholds(P, thr);
-  for (int n = 0; n < 8; ++n) thr[16 + n] = cam8 ? cam8[n] : 0.f;
-  void* d = nullptr;
-  int rc = morb_matcher_const(m, cam8 ? 1 : 0, thr, sizeof thr, &d, st);
-  if (rc != MORB_OK) return rc;
-  *d_thr = (const float*)d;
-  *d_kb8 = cam8 ? (const float*)d + 16 : nullptr;
-  return MORB_OK;
-}
-
-// queries -> candidate keys (workspaces 0 / 1 / 5)
+// queries -> candidate keys
 static int kfproj_candidates(morb_matcher* m, const morb_frame_params* P, int nprob, const int* d_kfImg, int cap, const int* d_count,
                              const morb_keypoint* d_kps, const uint8_t* d_desc, const float* d_uRight, int mpCap, const int* d_nMP,
                              const uint8_t* d_valid, const float* d_Pw, const float* d_normal, const float* d_maxDist,
@@ -1728,18 +1715,20 @@ static int kfproj_candidates(morb_matcher* m, const morb_frame_params* P, int np
   const float *d_thr = nullptr, *d_kb8 = nullptr;
   int rc = upload_ratio_thresholds(m, P, cam8, st, &d_thr, &d_kb8);
   if (rc != MORB_OK) return rc;
-  void *qs = nullptr, *cand = nullptr, *cnt = nullptr;
-  rc = morb_matcher_workspace(m, 5, sizeof(Query) * (size_t)nprob * mpCap, &qs);
-  if (rc == MORB_OK && candOut) rc = morb_matcher_workspace(m, 0, sizeof(unsigned long long) * (size_t)nprob * mpCap * CAND_CAP, &cand);
-  if (rc == MORB_OK && candOut) rc = morb_matcher_workspace(m, 1, sizeof(int) * (size_t)nprob * mpCap, &cnt);
+  Query* qs = nullptr;
+  unsigned long long* cand = nullptr;
+  int* cnt = nullptr;
+  rc = grow(m->queries, (size_t)nprob * mpCap, &qs);
+  if (rc == MORB_OK && candOut) rc = grow(m->candKeys, (size_t)nprob * mpCap * CAND_CAP, &cand);
+  if (rc == MORB_OK && candOut) rc = grow(m->candCount, (size_t)nprob * mpCap, &cnt);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_prep_kfproj, dim3(div_up(mpCap, 256), nprob), dim3(256), 0, st, *P, mpCap, d_nMP, d_valid, d_Pw, d_normal,
-                     d_maxDist, d_minDist, d_T, d_sim, d_Ow, d_thr, d_kb8, d_jLo, d_jHi, th, projMode, gate, (Query*)qs);
-  *qsOut = (const Query*)qs;
+                     d_maxDist, d_minDist, d_T, d_sim, d_Ow, d_thr, d_kb8, d_jLo, d_jHi, th, projMode, gate, qs);
+  *qsOut = qs;
   if (!candOut) return MORB_OK;
-  hipLaunchKernelGGL(k_candidates, dim3(div_up(mpCap, 4), nprob), dim3(256), 0, st, *P, mpCap, (const Query*)qs, d_mpDesc, d_kfImg, cap,
-                     d_count, d_kps, d_desc, d_uRight, (unsigned long long*)cand, (int*)cnt, 0);
-  *candOut = (const unsigned long long*)cand; *cntOut = (const int*)cnt;
+  hipLaunchKernelGGL(k_candidates, dim3(div_up(mpCap, 4), nprob), dim3(256), 0, st, *P, mpCap, qs, d_mpDesc, d_kfImg, cap,
+                     d_count, d_kps, d_desc, d_uRight, cand, cnt, 0);
+  *candOut = cand; *cntOut = cnt;
   return MORB_OK;
 }
 
@@ -1763,14 +1752,15 @@ static int best_per_query(morb_matcher* m, const morb_frame_params* P, int nprob
     MORB_HIP_CHECK(hipGetLastError());
     return MORB_OK;
   }
-  void *cand = nullptr, *cnt = nullptr;
-  int rc = morb_matcher_workspace(m, 0, sizeof(unsigned long long) * (size_t)nprob * qCap * CAND_CAP, &cand);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 1, sizeof(int) * (size_t)nprob * qCap, &cnt);
+  unsigned long long* cand = nullptr;
+  int* cnt = nullptr;
+  int rc = grow(m->candKeys, (size_t)nprob * qCap * CAND_CAP, &cand);
+  if (rc == MORB_OK) rc = grow(m->candCount, (size_t)nprob * qCap, &cnt);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_candidates, dim3(div_up(qCap, 4), nprob), dim3(256), 0, st, *P, qCap, qs, d_qDesc, d_kfImg, cap, d_count, d_kps, d_desc, d_uRight,
-                     (unsigned long long*)cand, (int*)cnt, 0);
+                     cand, cnt, 0);
   hipLaunchKernelGGL(k_best_per_query, dim3(div_up(qCap, 4), nprob), dim3(256), 0, st, *P, qCap, qs, d_qDesc, d_kfImg, cap, d_count, d_kps, d_desc, d_uRight,
-                     (const unsigned long long*)cand, (const int*)cnt, thAccept, d_bestIdx, d_bestDist);
+                     cand, cnt, thAccept, d_bestIdx, d_bestDist);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }
@@ -1785,8 +1775,7 @@ extern "C" int morb_fuse_batch(morb_matcher* m, const morb_frame_params* P, int 
                    d_minDist && d_mpDesc && d_bestIdx, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nprob > 0 && cap > 0 && cap <= 65535 && mpCap > 0 && P->nlevels >= 1 && P->nlevels <= 16, MORB_ERR_INVALID, "bad sizes");
   MORB_REQUIRE((d_jLo == nullptr) == (d_jHi == nullptr), MORB_ERR_INVALID, "feature range needs both ends");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   const Query* qs; const unsigned long long* cand; const int* cnt;
   int rc = kfproj_candidates(m, P, nprob, d_kfImg, cap, d_count, d_kps, d_desc, d_uRight, mpCap, d_nMP, d_valid, d_Pw, d_normal,
                              d_maxDist, d_minDist, d_mpDesc, d_Tcw, nullptr, d_Ow, cam8, d_jLo, d_jHi, th, 0, sim3Form ? 0 : 1, st, &qs,
@@ -1807,16 +1796,15 @@ static int search_by_projection_sim3_impl(morb_matcher* m, const morb_frame_para
   MORB_REQUIRE(m && P && d_kfImg && d_count && d_kps && d_desc && d_Tcw && d_Ow && d_nMP && d_valid && d_Pw && d_normal && d_maxDist &&
                    d_minDist && d_mpDesc && d_matched && d_matchF && d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nprob > 0 && cap > 0 && cap <= 65535 && mpCap > 0 && P->nlevels >= 1 && P->nlevels <= 16, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   const Query* qs; const unsigned long long* cand; const int* cnt;
   int rc = kfproj_candidates(m, P, nprob, d_kfImg, cap, d_count, d_kps, d_desc, nullptr, mpCap, d_nMP, d_valid, d_Pw, d_normal, d_maxDist,
                              d_minDist, d_mpDesc, d_Tcw, nullptr, d_Ow, cam8, nullptr, d_nLeft, (float)th, manualProjection ? 1 : 0, 0,
                              st, &qs, &cand, &cnt);
   if (rc != MORB_OK) return rc;
-  void *ej = nullptr, *eb = nullptr;
-  rc = morb_matcher_workspace(m, 2, sizeof(int) * (size_t)nprob * mpCap, &ej);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 3, sizeof(int) * (size_t)nprob * mpCap, &eb);
+  int *ej = nullptr, *eb = nullptr;
+  rc = grow(m->evictJ, (size_t)nprob * mpCap, &ej);
+  if (rc == MORB_OK) rc = grow(m->evictB, (size_t)nprob * mpCap, &eb);
   if (rc != MORB_OK) return rc;
   // bestDist <= TH_LOW * ratioHamming (int vs float product, :486 / :593) == bestDist <= floor(TH_LOW * ratioHamming)
   const int thAccept = (int)floorf((float)TH_LOW * ratioHamming);
@@ -1824,7 +1812,7 @@ static int search_by_projection_sim3_impl(morb_matcher* m, const morb_frame_para
   // the sequential pass: features already holding a match are skipped and a new match blocks its feature (:466, :487)
   hipLaunchKernelGGL(k_resolve<0>, dim3(nprob), dim3(64), (size_t)cap, st, *P, mpCap, d_nMP, qs, d_mpDesc, (const uint8_t*)nullptr,
                      d_kfImg, cap, d_count, d_kps, d_desc, (const float*)nullptr, d_matched, cand, cnt, 0.f, thAccept, 0, d_matchF,
-                     d_nmatches, (int*)ej, (int*)eb, (float*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
+                     d_nmatches, ej, eb, (float*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }
@@ -1864,12 +1852,11 @@ static int search_by_sim3_impl(morb_matcher* m, const morb_frame_params* P, int 
                    d_maxDist1 && d_minDist1 && d_mpDesc1 && d_valid2 && d_Pw2 && d_maxDist2 && d_minDist2 && d_mpDesc2 && d_vnMatch1 &&
                    d_vnMatch2 && d_match12 && d_nFound, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(npairs > 0 && cap > 0 && cap <= 65535 && P->nlevels >= 1 && P->nlevels <= 16, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
-  void* nq = nullptr;
-  int rc = morb_matcher_workspace(m, 6, sizeof(int) * (size_t)npairs * 2, &nq);
+  MORB_ENTER(st, m, stream);
+  int* n1 = nullptr;
+  int rc = grow(m->queryCount, (size_t)npairs * 2, &n1);
   if (rc != MORB_OK) return rc;
-  int* n1 = (int*)nq; int* n2 = n1 + npairs;
+  int* n2 = n1 + npairs;
   hipLaunchKernelGGL(k_gather_counts, dim3(div_up(npairs, 256)), dim3(256), 0, st, d_count, d_kf1Img, npairs, n1);
   hipLaunchKernelGGL(k_gather_counts, dim3(div_up(npairs, 256)), dim3(256), 0, st, d_count, d_kf2Img, npairs, n2);
   const Query* qs; const unsigned long long* cand; const int* cnt;
@@ -1914,6 +1901,30 @@ extern "C" int morb_search_by_sim3_rig_batch(morb_matcher* m, const morb_frame_p
                              d_mpDesc1, d_valid2, d_Pw2, d_maxDist2, d_minDist2, d_mpDesc2, th, d_nLeft1, d_nLeft2, d_vnMatch1, d_vnMatch2, d_match12, d_nFound, stream);
 }
 
+// SearchForTriangulation behind the sort and the table set-up: hf = the host tables of the form (F12 and epipoles per pair | the rig's
+// cameras and transforms, d_nLeft1 / d_nLeft2 != NULL)
+static int search_for_triangulation_impl(morb_matcher* m, const morb_frame_params* P, int npairs, const int* d_img1, const int* d_img2,
+                                         const int* d_nLeft1, const int* d_nLeft2, const unsigned long long* sorted, int cap,
+                                         const int* d_count, const morb_keypoint* d_kps, const uint8_t* d_desc, const int* d_node,
+                                         const uint8_t* d_hasMP, const float* d_uRight, const std::vector<float>& hf, int bOnlyStereo,
+                                         int bCoarse, int checkOri, int* d_match12, int* d_nmatches, hipStream_t st) {
+  float* dF = nullptr;
+  int* dBin = nullptr;
+  int rc = grow(m->pairTables, hf.size(), &dF);
+  if (rc == MORB_OK) rc = grow(m->evictJ, (size_t)npairs * cap, &dBin);
+  if (rc != MORB_OK) return rc;
+  MORB_HIP_CHECK(hipMemcpyAsync(dF, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice, st));
+  MORB_HIP_CHECK(hipStreamSynchronize(st));  // hf is the caller's local
+  const bool rig = d_nLeft1 != nullptr;
+  const float* d_ep = rig ? dF : dF + (size_t)npairs * 9;   // (the rig form reads no epipoles)
+  const float* d_rig = rig ? dF : nullptr;
+  hipLaunchKernelGGL(k_triangulation, dim3(div_up(cap, 4), npairs), dim3(256), 0, st, sorted, cap, d_count, d_img1, d_img2, d_kps,
+                     d_desc, d_node, d_hasMP, d_uRight, *P, dF, d_ep, bOnlyStereo, bCoarse, d_match12, dBin, d_rig, d_nLeft1, d_nLeft2);
+  hipLaunchKernelGGL(k_rot_filter12, dim3(npairs), dim3(256), 0, st, d_count, d_img1, cap, checkOri, d_match12, dBin, d_nmatches);
+  MORB_HIP_CHECK(hipGetLastError());
+  return MORB_OK;
+}
+
 extern "C" int morb_search_for_triangulation_batch(morb_matcher* m, const morb_frame_params* P, int npairs, const int* d_img1,
                                                    const int* d_img2, int nimg, int cap, const int* d_count,
                                                    const morb_keypoint* d_kps, const uint8_t* d_desc, const int* d_node,
@@ -1923,8 +1934,7 @@ extern "C" int morb_search_for_triangulation_batch(morb_matcher* m, const morb_f
   MORB_REQUIRE(m && P && d_img1 && d_img2 && d_count && d_kps && d_desc && d_node && d_hasMP && R12 && t12 && ep && d_match12 &&
                    d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(npairs > 0 && nimg > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   unsigned long long* sorted = nullptr;
   int rc = morb_bow_sort_images(m, nimg, d_node, d_count, cap, &sorted, st);
   if (rc != MORB_OK) return rc;
@@ -1935,18 +1945,8 @@ extern "C" int morb_search_for_triangulation_batch(morb_matcher* m, const morb_f
     hf[(size_t)npairs * 9 + 2 * p] = ep[2 * p];
     hf[(size_t)npairs * 9 + 2 * p + 1] = ep[2 * p + 1];
   }
-  void *dF = nullptr, *dBin = nullptr;
-  rc = morb_matcher_workspace(m, 4, sizeof(float) * hf.size(), &dF);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 2, sizeof(int) * (size_t)npairs * cap, &dBin);
-  if (rc != MORB_OK) return rc;
-  MORB_HIP_CHECK(hipMemcpyAsync(dF, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice, st));
-  MORB_HIP_CHECK(hipStreamSynchronize(st));  // hf is a local
-  hipLaunchKernelGGL(k_triangulation, dim3(div_up(cap, 4), npairs), dim3(256), 0, st, sorted, cap, d_count, d_img1, d_img2, d_kps,
-                     d_desc, d_node, d_hasMP, d_uRight, *P, (const float*)dF, (const float*)dF + (size_t)npairs * 9, bOnlyStereo,
-                     bCoarse, d_match12, (int*)dBin, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(k_rot_filter12, dim3(npairs), dim3(256), 0, st, d_count, d_img1, cap, checkOri, d_match12, (const int*)dBin, d_nmatches);
-  MORB_HIP_CHECK(hipGetLastError());
-  return MORB_OK;
+  return search_for_triangulation_impl(m, P, npairs, d_img1, d_img2, nullptr, nullptr, sorted, cap, d_count, d_kps, d_desc, d_node, d_hasMP,
+                                       d_uRight, hf, bOnlyStereo, bCoarse, checkOri, d_match12, d_nmatches, st);
 }
 
 extern "C" int morb_search_for_triangulation_fisheye_batch(morb_matcher* m, const morb_frame_params* P, int npairs, const int* d_img1,
@@ -1958,24 +1958,13 @@ extern "C" int morb_search_for_triangulation_fisheye_batch(morb_matcher* m, cons
   MORB_REQUIRE(m && P && d_img1 && d_img2 && d_nLeft1 && d_nLeft2 && d_count && d_kps && d_desc && d_node && d_hasMP && camL8 && camR8 &&
                    T4 && d_match12 && d_nmatches, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(npairs > 0 && nimg > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   unsigned long long* sorted = nullptr;
   int rc = morb_bow_sort_images(m, nimg, d_node, d_count, cap, &sorted, st);
   if (rc != MORB_OK) return rc;
   std::vector<float> hf(16 + (size_t)npairs * 48);
   for (int i = 0; i < 8; ++i) { hf[i] = camL8[i]; hf[8 + i] = camR8[i]; }
   for (size_t i = 0; i < (size_t)npairs * 48; ++i) hf[16 + i] = T4[i];
-  void *dF = nullptr, *dBin = nullptr;
-  rc = morb_matcher_workspace(m, 4, sizeof(float) * hf.size(), &dF);
-  if (rc == MORB_OK) rc = morb_matcher_workspace(m, 2, sizeof(int) * (size_t)npairs * cap, &dBin);
-  if (rc != MORB_OK) return rc;
-  MORB_HIP_CHECK(hipMemcpyAsync(dF, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice, st));
-  MORB_HIP_CHECK(hipStreamSynchronize(st));  // hf is a local
-  hipLaunchKernelGGL(k_triangulation, dim3(div_up(cap, 4), npairs), dim3(256), 0, st, sorted, cap, d_count, d_img1, d_img2, d_kps,
-                     d_desc, d_node, d_hasMP, (const float*)nullptr, *P, (const float*)dF, (const float*)dF, bOnlyStereo, bCoarse,
-                     d_match12, (int*)dBin, (const float*)dF, d_nLeft1, d_nLeft2);
-  hipLaunchKernelGGL(k_rot_filter12, dim3(npairs), dim3(256), 0, st, d_count, d_img1, cap, checkOri, d_match12, (const int*)dBin, d_nmatches);
-  MORB_HIP_CHECK(hipGetLastError());
-  return MORB_OK;
+  return search_for_triangulation_impl(m, P, npairs, d_img1, d_img2, d_nLeft1, d_nLeft2, sorted, cap, d_count, d_kps, d_desc, d_node, d_hasMP,
+                                       nullptr, hf, bOnlyStereo, bCoarse, checkOri, d_match12, d_nmatches, st);
 }

@@ -20,7 +20,7 @@
 #include <cstdint>
 
 #include "common.h"
-#include "internal_abi.h"
+#include "handles.h"
 #include "libm_f32.h"
 #include "libm_f64.h"
 
@@ -558,15 +558,14 @@ extern "C" int morb_optimize_sim3_batch(morb_optimizer* o, int nprob, int cap, c
                    d_cam2 && d_th2 && d_fixScale && d_S12 && d_keep && d_nIn && d_stats,
                MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nprob > 0 && cap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_optimizer_device(o)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_optimizer_stream(o);
+  MORB_ENTER(st, o, stream);
   const size_t pitch = s3_bytes_per_problem(cap);
-  void* ws = nullptr;
-  const int rc = morb_optimizer_spill(o, pitch * (size_t)nprob, &ws);
+  char* ws = nullptr;
+  const int rc = morb::grow(o->spill, pitch * (size_t)nprob, &ws);
   if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_optimize_sim3, dim3(nprob), dim3(S3_NT), 0, st, cap, d_count, d_entry, d_Xw1, d_Xw2, d_i2, d_obs1, d_invSigma2_1,
                      d_obs2, d_invSigma2_2, d_T1w, d_T2w, d_cam1, d_cam2, d_th2, d_fixScale, bAllPoints, d_S12, d_keep, d_nIn, d_stats,
-                     (char*)ws, pitch);
+                     ws, pitch);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }

@@ -17,7 +17,7 @@
 #include <cstdint>
 
 #include "common.h"
-#include "internal_abi.h"
+#include "handles.h"
 #include "kb8.h"
 #include "libm_f32.h"
 #include "morb_hip.h"
@@ -422,17 +422,16 @@ extern "C" int morb_sim3_solver_batch(morb_optimizer* o, int nprob, int cap, con
                "NULL argument");
   MORB_REQUIRE(nprob > 0 && cap > 0 && randCap >= 0 && (d_rand || randCap == 0) && (d_hypInliers == nullptr || hypCap >= 0),
                MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_optimizer_device(o)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_optimizer_stream(o);
+  MORB_ENTER(st, o, stream);
   size_t pitch = 0;
-  void* ws = nullptr;
+  char* ws = nullptr;
   if (cap > SS_LDS_N) {   // only problems with more than SS_LDS_N correspondences use it
     pitch = ss_bytes_per_problem(cap);
-    const int rc = morb_optimizer_spill(o, pitch * (size_t)nprob, &ws);
+    const int rc = morb::grow(o->spill, pitch * (size_t)nprob, &ws);
     if (rc != MORB_OK) return rc;
   }
   hipLaunchKernelGGL(k_sim3_solver, dim3(nprob), dim3(SS_NT), 0, st, cap, d_params, d_entry, d_Xw1, d_Xw2, d_sigma2_1, d_sigma2_2,
-                     nIterations, d_rand, randCap, d_state, d_inliers, d_hypInliers, hypCap, (char*)ws, pitch);
+                     nIterations, d_rand, randCap, d_state, d_inliers, d_hypInliers, hypCap, ws, pitch);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
 }

@@ -13,14 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "internal_abi.h"
+#include "handles.h"
 
 using namespace morb;
-
-struct morb_matcher;
-extern "C" {
-void* morb_matcher_stream(const morb_matcher*);
-}
 
 namespace {
 
@@ -132,8 +127,7 @@ int morb_frame_set_pose_batch(morb_matcher* m, int nframes, const float* d_pose7
                               void* stream) {
   MORB_REQUIRE(m && d_pose7 && d_Rcw && d_tcw && d_Ow, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_set_pose, dim3(div_up(nframes, 64)), dim3(64), 0, st, nframes, d_pose7, d_Rcw, d_tcw, d_Ow);
   MORB_HIP_CHECK(hipGetLastError());
   return MORB_OK;
@@ -146,8 +140,7 @@ int morb_pose_edges_batch(morb_matcher* m, const morb_frame_params* P, int nfram
   MORB_REQUIRE(m && P && d_fImg && d_count && d_kps && d_mpXw && d_frameMP && d_hasMP && d_obs && d_invSigma2 && d_Xw,
                MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && mpCap > 0 && (!d_remap || (d_match && remapCap > 0)), MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_pose_edges, dim3(div_up(cap, 256), nframes), dim3(256), 0, st, *P, cap, d_fImg, d_count, d_kps, d_uRight,
                      d_match, d_remap, remapCap, mpCap, d_mpXw, d_frameMP, d_hasMP, d_obs, d_invSigma2, d_Xw);
   MORB_HIP_CHECK(hipGetLastError());
@@ -159,8 +152,7 @@ int morb_track_discard_outliers_batch(morb_matcher* m, int nframes, const int* d
                                       uint8_t* d_mpSeen, int* d_nmatches, int* d_nmatchesMap, void* stream) {
   MORB_REQUIRE(m && d_fImg && d_count && d_frameMP && d_outlier, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nframes > 0 && cap > 0 && mpCap > 0, MORB_ERR_INVALID, "bad sizes");
-  MORB_HIP_CHECK(hipSetDevice(morb_matcher_device(m)));
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)morb_matcher_stream(m);
+  MORB_ENTER(st, m, stream);
   hipLaunchKernelGGL(k_discard, dim3(nframes), dim3(1024), 0, st,   // (one frame's 2048 map points and ~1200 features in two trips each)
                      cap, d_fImg, d_count, d_frameMP, d_outlier, mpCap, d_mpHasObs,
                      d_blocked, d_mpSeen, d_nmatches, d_nmatchesMap);

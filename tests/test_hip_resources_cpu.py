@@ -61,3 +61,59 @@ def test_scanner_sees_calls_and_skips_comments_and_strings(tmp_path):
     src.write_text('// hipMalloc(&p, 1)\n/* hipFree(p);\n */ set_error("hipHostFree(p)");\n'
                    "MORB_HIP_CHECK(hipMalloc (&p, n)); char c = '\"'; hipEventDestroy(e);\n")
     assert _calls(str(src)) == [(4, "hipMalloc"), (4, "hipEventDestroy")]
+
+
+def _second_argument(code, start):
+    """The second argument of the call whose '(' is at code[start]."""
+    depth, args, cur = 0, [], []
+    for ch in code[start:]:
+        if ch in "([{":
+            depth += 1
+            if depth == 1:
+                continue
+        elif ch in ")]}":
+            depth -= 1
+            if depth == 0:
+                break
+        if ch == "," and depth == 1:
+            args.append("".join(cur)); cur = []
+        else:
+            cur.append(ch)
+    args.append("".join(cur))
+    return args[1] if len(args) > 1 else ""
+
+
+def _numbered_selectors(path):
+    """Workspaces and constant tables of a handle picked by a bare integer: an accessor call whose selector holds a literal, or a
+    literal index into a handle's array of them."""
+    code = _code(path)
+    bad = []
+    for m in re.finditer(r"\bmorb_(?:matcher|optimizer)_(?:workspace|const|spill|staging)\s*\(", code):
+        if re.search(r"(?<![\w.])\d+\b", _second_argument(code, m.end() - 1)):
+            bad.append((code.count("\n", 0, m.start()) + 1, m.group(0).rstrip("( ")))
+    for m in re.finditer(r"(?:->|\.)\s*(?:ws|consts)\s*\[\s*[^\]]*?(?<![\w.])\d+\b[^\]]*\]", code):
+        bad.append((code.count("\n", 0, m.start()) + 1, m.group(0)))
+    return bad
+
+
+def test_handle_workspaces_are_named_and_the_handles_have_one_definition():
+    """A handle's device scratch is a named, typed member of the struct in csrc/handles.h, reached through grow(): no call picks a
+    workspace or a constant table by number, and no unit declares the handle structs for itself (which is what made numbered C
+    accessors necessary)."""
+    bad = [f"{os.path.basename(p)}:{line}: {what}" for p in _sources() for line, what in _numbered_selectors(p)]
+    assert not bad, "name the workspace / constant table (csrc/handles.h):\n" + "\n".join(bad)
+    decl = re.compile(r"\bstruct\s+morb_(matcher|optimizer)\b")
+    stray = [f"{os.path.basename(p)}:{_code(p).count(chr(10), 0, m.start()) + 1}" for p in _sources() if os.path.basename(p) != "handles.h"
+             for m in decl.finditer(_code(p))]
+    assert not stray, "the handle structs are declared in csrc/handles.h only:\n" + "\n".join(stray)
+    assert {m.group(1) for m in decl.finditer(_code(os.path.join(CSRC, "handles.h")))} == {"matcher", "optimizer"}
+
+
+def test_selector_scanner_sees_numbered_calls(tmp_path):
+    src = tmp_path / "y.hip"
+    src.write_text("rc = morb_matcher_workspace(m, 5, sizeof(Query) * n, &qs);\n"
+                   "rc = morb_matcher_const(m, cam8 ? 1 : 0, thr, sizeof thr, &d, st);\n"
+                   "rc = morb_matcher_const(m, cam8 ? morb_matcher::kThresholdsKB8 : morb_matcher::kThresholdsPinhole, thr, 96, &d, st);\n"
+                   "rc = grow(m->queries, 2 * (size_t)n, &qs);  // morb_matcher_workspace(m, 5, ...)\n"
+                   "return m->ws[which].ensure(bytes, out) + o->consts[2].clock + m->consts[table].clock;\n")
+    assert [line for line, _ in _numbered_selectors(str(src))] == [1, 2, 5]
