@@ -662,6 +662,65 @@ int morb_sim3_solver_batch(morb_optimizer*, int nprob, int cap, const morb_sim3_
                            const int* d_rand, int randCap, morb_sim3_solver_state* d_state, uint8_t* d_inliers, int* d_hypInliers,
                            int hypCap, void* stream);
 
+/* MLPnPsolver (src/MLPnPsolver.cpp, include/MLPnPsolver.h): the constructor, SetRansacParameters and iterate, for nprob problems at
+ * once, one workgroup each, asynchronous on `stream` (NULL = the handle's own).  Stateless apart from the per-problem state record
+ * and the best mask: every call recomputes the constructor and SetRansacParameters (cheap) and runs iterate(nIterations, ...) from
+ * state.iterations on, so one entry serves Tracking::Relocalization's round-robin `iterate(5, ...)` (Tracking.cc:3405-3432) and one
+ * call with the whole budget.  Per problem (DEVICE array of records): */
+typedef struct morb_mlpnp_solver_params {
+  float cam[9];        /* kind (0 Pinhole, 1 KannalaBrandt8) + the 8 parameters of F.mpCamera (:56): unproject in the constructor
+                          (:78), project in CheckInliers (:276) */
+  double probability;  /* SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon, th2) (:225-260); Tracking
+                          passes (0.99, 10, 300, 6, 0.5, 5.991) */
+  int minInliers;      /* raised to int(N * epsilon) and to minSet (:237-242) */
+  int maxIterations;   /* the budget is ceil(log(1 - p) / log(1 - eps^3)) clipped to [1, maxIterations] (:248-255) */
+  int minSet;          /* correspondences per hypothesis, 6 .. 16; a value outside runs no iteration and reports budget = 0,
+                          noMore = 1 (a device-side field cannot fail the call: the Python and C++ fronts, which hold the host
+                          copy, return MORB_ERR_INVALID's error before the launch) */
+  float epsilon;       /* raised to (float)minInliers / N (:244-245) */
+  float th2;           /* mvMaxError[i] = sigma2[i] * th2 in float (:257-259) */
+  int n;               /* vpMapPointMatches.size() (<= cap) */
+} morb_mlpnp_solver_params;
+
+/* In / out, one per problem.  Zero it before the first call (the constructor's mnIterations = mnBestInliers = 0); the kernel reads
+ * iterations, bestInliers and bestTcw and writes every field. */
+typedef struct morb_mlpnp_solver_state {
+  int N;            /* correspondences kept by the constructor (:66-94) */
+  int minInliers;   /* mRansacMinInliers after SetRansacParameters (:237-242) */
+  int budget;       /* mRansacMaxIts after SetRansacParameters (:255) */
+  int iterations;   /* mnIterations: iterations done over all calls so far */
+  int bestInliers;  /* mnBestInliers */
+  int ok;           /* this call's return value of iterate (:199, :218) */
+  int noMore;       /* this call's bNoMore: N < minInliers (:106-110), or the budget is spent (:205-207), also beside ok = 1 of the
+                       post-loop branch; not set by a call that returns from Refine() */
+  int nInliers;     /* this call's nInliers: mnRefinedInliers (:191), mnBestInliers of the post-loop branch (:210), else 0 */
+  int refined;      /* 1: Tcw is mRefinedTcw (:198); 0: mBestTcw (:217) or none */
+  int returnedAt;   /* global index of the iteration whose Refine() succeeded, else -1 */
+  float bestTcw[16];/* mBestTcw row-major (:181-183): the double pose of the best iteration rounded to float */
+  float Tcw[16];    /* this call's Tout: identity unless ok */
+} morb_mlpnp_solver_state;
+
+/* Per feature i < params.n, arrays [nprob][cap]:
+ *   d_entry  bit 0 vpMapPointMatches[i] != NULL, bit 1 pMP->isBad(), bit 2 i >= F.mvKeysUn.size() (:67-71); a feature is kept iff
+ *            bit 0 is set and bits 1, 2 are clear;
+ *   d_uv [..][2] F.mvKeysUn[i].pt (mvP2D, float; the bearing vector is unproject(pt) / z in float, NOT normalised, :74-81);
+ *   d_sigma2 = F.mvLevelSigma2[kp.octave] (:75);  d_Xw [..][3] pMP->GetWorldPos() (:84-86).
+ * d_rand [nprob][randCap]: the rand() values of DUtils::Random::RandomInt (:130), minSet per iteration (six with the reference's
+ * default), iteration g (global, from 0) reading d_rand[p][minSet * g .. minSet * g + minSet - 1]; a call stops at iteration
+ * randCap / minSet.  nIterations is iterate's first argument: the loop condition (:115) is an OR, so a call runs to the end of the
+ * budget or nIterations iterations, whichever comes later.
+ * d_bestInliers [nprob][cap], in / out: mvbBestInliers by feature; the kernel clears it while state.bestInliers == 0, so a zeroed
+ * state needs nothing else.  Outputs: d_state; d_inliers [nprob][cap] = vbInliers by feature (all zero unless ok); d_hypInliers
+ * (optional) [nprob][hypCap] = mnInliersi of global iteration g for every g this call evaluates (entries of iterations not
+ * evaluated are left as they are: pre-fill them with -1).
+ * computePose (:356-658) runs in FP64 with the project's own routines where the reference calls Eigen (cyclic Jacobi for the
+ * 12 x 12 / 9 x 9 / 3 x 3 symmetric eigenproblems, the 3 x 3 SVD built on it, a 6 x 6 LDL^T, a hand-derived Gauss-Newton Jacobian:
+ * DESIGN.md section 6, "MLPnPsolver"); CheckInliers (:262-293) rounds R X + t to float and projects in float, error2 < maxError. */
+int morb_mlpnp_solver_batch(morb_optimizer*, int nprob, int cap, const morb_mlpnp_solver_params* d_params, const uint8_t* d_entry,
+                            const float* d_uv, const float* d_sigma2, const float* d_Xw, int nIterations, const int* d_rand, int randCap,
+                            morb_mlpnp_solver_state* d_state, uint8_t* d_bestInliers, uint8_t* d_inliers, int* d_hypInliers, int hypCap,
+                            void* stream);
+
 /* ---- visual-inertial tracking and mapping ----
  * IMU::Preintegrated as plain data (include/ImuTypes.h:154-263): 3 x 3 blocks row-major, C = the 15 x 15 covariance
  * row-major, b = the bias the measurements were integrated with in IMU::Bias order (bax bay baz bwx bwy bwz),

@@ -172,6 +172,7 @@ def lib():
         L.morb_local_inertial_ba_fisheye.argtypes = [vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, i, vp, vp]
         L.morb_optimize_sim3_batch.argtypes = [vp, i, i] + [vp] * 15 + [i, vp, vp, vp, vp, vp]
         L.morb_sim3_solver_batch.argtypes = [vp, i, i] + [vp] * 6 + [i, vp, i, vp, vp, vp, i, vp]
+        L.morb_mlpnp_solver_batch.argtypes = [vp, i, i] + [vp] * 5 + [i, vp, i, vp, vp, vp, vp, i, vp]
         L.morb_pose_optimization_fisheye_batch.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.morb_ba_problem_create_fisheye.argtypes = [vp, C.POINTER(vp), i, vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i]
         L.morb_local_bundle_adjustment.argtypes = [vp, i, vp, vp, i, vp, i, vp, vp, vp, vp, f, f, f, f, f, i, vp, vp, vp]

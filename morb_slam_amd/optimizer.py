@@ -21,6 +21,13 @@ SIM3_SOLVER_STATE = np.dtype([("N", "<i4"), ("budget", "<i4"), ("iterations", "<
                               ("noMore", "<i4"), ("nInliers", "<i4"), ("convergedAt", "<i4"), ("bestT12", "<f4", 16), ("bestR", "<f4", 9),
                               ("bestt", "<f4", 3), ("bestScale", "<f4"), ("sim3", "<f4", 16)], align=True)
 assert SIM3_SOLVER_PARAMS.itemsize == 192 and SIM3_SOLVER_STATE.itemsize == 212
+# morb_mlpnp_solver_params / morb_mlpnp_solver_state
+MLPNP_SOLVER_PARAMS = np.dtype([("cam", "<f4", 9), ("probability", "<f8"), ("minInliers", "<i4"), ("maxIterations", "<i4"), ("minSet", "<i4"),
+                                ("epsilon", "<f4"), ("th2", "<f4"), ("n", "<i4")], align=True)
+MLPNP_SOLVER_STATE = np.dtype([("N", "<i4"), ("minInliers", "<i4"), ("budget", "<i4"), ("iterations", "<i4"), ("bestInliers", "<i4"),
+                               ("ok", "<i4"), ("noMore", "<i4"), ("nInliers", "<i4"), ("refined", "<i4"), ("returnedAt", "<i4"),
+                               ("bestTcw", "<f4", 16), ("Tcw", "<f4", 16)], align=True)
+assert MLPNP_SOLVER_PARAMS.itemsize == 72 and MLPNP_SOLVER_STATE.itemsize == 168
 
 
 class Optimizer:
@@ -126,6 +133,30 @@ class Optimizer:
     def sim3_solver_state(state):
         """The state tensor u8 [P, 212] -> numpy SIM3_SOLVER_STATE records [P]."""
         return np.frombuffer(state.cpu().numpy().tobytes(), SIM3_SOLVER_STATE).copy()
+
+    def MLPnPsolver(self, params, entry, uv, sigma2, Xw, rand, state, bestInliers, nIterations, inliers=None, hypInliers=None, stream=None):
+        """Batched MLPnPsolver (morb_mlpnp_solver_batch): the constructor, SetRansacParameters and iterate(nIterations, ...) from
+        state.iterations on.  Device tensors, P problems of up to cap features: params u8 [P, 72] (MLPNP_SOLVER_PARAMS records), entry
+        u8 [P, cap] (bit 0 matched, bit 1 bad map point, bit 2 feature index beyond mvKeysUn), uv f32 [P, cap, 2] (mvKeysUn[i].pt),
+        sigma2 f32 [P, cap], Xw f32 [P, cap, 3], rand i32 [P, randCap] (rand() values, minSet per iteration by global iteration
+        number), state u8 [P, 168] (MLPNP_SOLVER_STATE records, in / out; zero before the first call), bestInliers u8 [P, cap]
+        (mvbBestInliers, in / out).  hypInliers i32 [P, hypCap] or None receives the inlier count of every iteration evaluated.
+        Returns (state, inliers u8 [P, cap], hypInliers); inliers = vbInliers, set only when state.ok."""
+        import torch
+        P, cap = entry.shape
+        if inliers is None:
+            inliers = torch.empty((P, cap), dtype=torch.uint8, device=entry.device)
+        hypCap = 0 if hypInliers is None else hypInliers.shape[1]
+        st = stream_arg(stream)
+        check(self._L.morb_mlpnp_solver_batch(self._h, P, cap, ptr(params), ptr(entry), ptr(uv), ptr(sigma2), ptr(Xw), int(nIterations),
+                                              ptr(rand), rand.shape[1], ptr(state), ptr(bestInliers), ptr(inliers), ptr(hypInliers), hypCap,
+                                              st))
+        return state, inliers, hypInliers
+
+    @staticmethod
+    def mlpnp_solver_state(state):
+        """The state tensor u8 [P, 168] -> numpy MLPNP_SOLVER_STATE records [P]."""
+        return np.frombuffer(state.cpu().numpy().tobytes(), MLPNP_SOLVER_STATE).copy()
 
     # ---- visual-inertial tracking and mapping (SURVEY 8(f) N1) ---------------------------------------------------
     def PreintegrateIMU(self, start, acc, gyro, dt, bias, nga, walk, out=None, stream=None):

@@ -699,3 +699,90 @@ def pack_sim3_solver_problems(probs, device, rand=None, cap=None):
             a[k, :len(r)] = r
         t["rand"] = torch.from_numpy(a).to(device)
     return t
+
+
+# ---- MLPnPsolver (one frame against the map points of a relocalisation candidate) ------------------------------
+def make_mlpnp_problem(n=100, seed=0, cam="pinhole", outlier_frac=0.3, noise_px=0.5, bad_frac=0.03, unmatched_frac=0.1, planar=False,
+                       dup_frac=0.0, identical=False, beyond_frac=0.0, probability=0.99, min_inliers=10, max_iterations=300, min_set=6,
+                       epsilon=0.5, th2=5.991):
+    """One MLPnPsolver input: n features of a frame with a true pose Tcw; map points in front of the camera (on the world plane z = 0,
+    exactly, when planar), octaves U{0..7} with sigma2 = 1.44^octave, pixel noise noise_px * 1.2^octave, gross outliers moved by
+    +-20..80 px per axis.  entry bit 0 = matched, bit 1 = bad map point, bit 2 = a feature index beyond mvKeysUn (beyond_frac);
+    dup_frac of the features repeat another feature's point and keypoint, identical makes all of them one.  The parameters default to
+    Tracking::Relocalization's SetRansacParameters(0.99, 10, 300, 6, 0.5, 5.991).  Returns a dict of the morb_mlpnp_solver_batch
+    per-problem arrays and parameters plus the true pose (Tcw_true, 4 x 4) and the planted outliers."""
+    if n == 0:
+        p = make_mlpnp_problem(1, seed, cam, probability=probability, min_inliers=min_inliers, max_iterations=max_iterations,
+                               min_set=min_set, epsilon=epsilon, th2=th2)
+        for k in ("entry", "uv", "sigma2", "Xw", "outlier"):
+            p[k] = p[k][:0]
+        p["n"] = 0
+        return p
+    rng = np.random.default_rng(0x3E77 + seed)
+    R = _rot_from_rotvec(rng.normal(0, 0.35, 3))
+    if planar:
+        t = np.array([rng.normal(0, 0.3), rng.normal(0, 0.3), rng.uniform(3.5, 5.0)])
+        Xw = np.stack([rng.uniform(-1.6, 1.6, n), rng.uniform(-1.2, 1.2, n), np.zeros(n)], 1)
+    else:
+        t = rng.normal(0, 0.8, 3)
+        z = rng.uniform(2.0, 8.0, n)
+        half = 0.55 if cam == "pinhole" else 1.2
+        Xc = np.stack([rng.uniform(-half, half, n) * z, rng.uniform(-0.4, 0.4, n) * z, z], 1)
+        Xw = (Xc - t) @ R
+    Xw = Xw.astype(np.float32)
+    octave = rng.integers(0, 8, n)
+    noise = rng.normal(0, 1.0, (n, 2)) * (noise_px * 1.2 ** octave)[:, None]
+    outlier = rng.random(n) < outlier_frac
+    shift = rng.uniform(20, 80, (n, 2)) * rng.choice([-1, 1], (n, 2))
+    dup = np.nonzero(rng.random(n) < dup_frac)[0] if n > 1 else np.zeros(0, np.int64)
+    src = rng.integers(0, n, len(dup))
+    matched = rng.random(n) >= unmatched_frac
+    bad = rng.random(n) < bad_frac
+    beyond = rng.random(n) < beyond_frac
+    uv = _sim3_project(cam, Xw.astype(np.float64) @ R.T + t) + noise
+    uv[outlier] += shift[outlier]
+    uv = uv.astype(np.float32)
+    Xw[dup], uv[dup], octave[dup] = Xw[src], uv[src], octave[src]
+    if identical:
+        Xw, uv, octave = np.repeat(Xw[:1], n, 0), np.repeat(uv[:1], n, 0), np.repeat(octave[:1], n, 0)
+    entry = (matched.astype(np.uint8) | (bad.astype(np.uint8) << 1) | (beyond.astype(np.uint8) << 2)).astype(np.uint8)
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    return dict(n=n, entry=entry, uv=uv, sigma2=(1.44 ** octave).astype(np.float32), Xw=Xw, cam=sim3_camera9(cam),
+                probability=float(probability), min_inliers=int(min_inliers), max_iterations=int(max_iterations), min_set=int(min_set),
+                epsilon=float(epsilon), th2=float(th2), Tcw_true=T, outlier=outlier)
+
+
+def pack_mlpnp_problems(probs, device, rand=None, cap=None):
+    """make_mlpnp_problem dicts -> the torch tensors of Optimizer.MLPnPsolver on `device` (cap = the largest n unless given): params u8
+    [P, 72], entry, uv, sigma2, Xw, rand i32 [P, randCap] (the given list of arrays, zero padded), a zeroed state u8 [P, 168] and a
+    zeroed bestInliers u8 [P, cap]."""
+    import torch
+    from .optimizer import MLPNP_SOLVER_PARAMS, MLPNP_SOLVER_STATE
+    P = len(probs)
+    cap = cap or max(max(p["n"] for p in probs), 1)
+
+    def stack(key, shape, dtype):
+        a = np.zeros((P, cap) + shape, dtype)
+        for k, p in enumerate(probs):
+            a[k, :p["n"]] = p[key]
+        return torch.from_numpy(a).to(device)
+    prm = np.zeros(P, MLPNP_SOLVER_PARAMS)
+    for k, p in enumerate(probs):
+        if not 6 <= p["min_set"] <= 16:
+            raise ValueError("min_set outside [6, 16]")   # the entry point's argument error: the kernel cannot return one
+        prm[k]["cam"], prm[k]["probability"], prm[k]["minInliers"] = p["cam"], p["probability"], p["min_inliers"]
+        prm[k]["maxIterations"], prm[k]["minSet"], prm[k]["epsilon"], prm[k]["th2"], prm[k]["n"] = \
+            p["max_iterations"], p["min_set"], p["epsilon"], p["th2"], p["n"]
+    t = {"entry": stack("entry", (), np.uint8), "uv": stack("uv", (2,), np.float32), "sigma2": stack("sigma2", (), np.float32),
+         "Xw": stack("Xw", (3,), np.float32)}
+    t["params"] = torch.from_numpy(np.frombuffer(prm.tobytes(), np.uint8).reshape(P, -1).copy()).to(device)
+    t["state"] = torch.zeros((P, MLPNP_SOLVER_STATE.itemsize), dtype=torch.uint8, device=device)
+    t["bestInliers"] = torch.zeros((P, cap), dtype=torch.uint8, device=device)
+    if rand is not None:
+        rc = max(max(len(r) for r in rand), 1)
+        a = np.zeros((P, rc), np.int32)
+        for k, r in enumerate(rand):
+            a[k, :len(r)] = r
+        t["rand"] = torch.from_numpy(a).to(device)
+    return t

@@ -1,0 +1,173 @@
+"""MLPnPsolver without a GPU: the CPU oracle (tests/native/mlpnp_solver_oracle.cc) on problems with a known answer, SetRansacParameters
+of the oracle against the scalar header the kernel shares with the adapter (include/morb/mlpnp_solver_math.h), the reference's
+quirks (the OR in iterate's loop condition, Refine() on the best mask), the hand-derived Gauss-Newton Jacobian against finite
+differences, the corpus of the GPU test through the oracle built two ways, the new kernel's scratch use, and the C++ adapter against
+mock reference types."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import mlpnp_solver_corpus
+import mlpnp_solver_oracle
+from morb_slam_amd.synth import libc_rand, make_mlpnp_problem
+from test_sim3_solver_cpu import _kernel_scratch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NATIVE = os.path.join(ROOT, "tests", "native")
+LLVM = "/opt/rocm/lib/llvm/bin"
+CLEAN = dict(outlier_frac=0.0, noise_px=0.0, bad_frac=0.0, unmatched_frac=0.0)
+FAST = ("-O3", "-ffp-contract=fast", "-march=native")
+
+
+@pytest.fixture(scope="module")
+def mpm(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("mpm") / "libmpm.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", out,
+                           os.path.join(NATIVE, "mlpnp_solver_math_check.cc")])
+    L = C.CDLL(out)
+    L.mpm_ransac.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_void_p]
+    L.mpm_max_error.argtypes = [C.c_float, C.c_float]
+    L.mpm_max_error.restype = C.c_float
+    return L
+
+
+def _header_ransac(mpm, N, min_inliers=10, max_iterations=300, min_set=6, epsilon=0.5, probability=0.99):
+    out = np.zeros(2, np.int32)
+    mpm.mpm_ransac(N, min_inliers, max_iterations, min_set, epsilon, probability, out.ctypes.data_as(C.c_void_p))
+    return int(out[0]), int(out[1])
+
+
+@pytest.mark.parametrize("cam", ["pinhole", "kb8"])
+@pytest.mark.parametrize("planar", [False, True])
+def test_oracle_recovers_known_pose(cam, planar):
+    p = make_mlpnp_problem(120, seed=3, cam=cam, planar=planar, **CLEAN)
+    if planar:
+        assert (p["Xw"][:, 2] == 0).all()
+    calls, summ = mlpnp_solver_oracle.run(p, libc_rand(7, 6 * 300), calls=[5] * 8, stop=False)
+    assert len(calls) == 8
+    for k, c in enumerate(calls):   # every call returns from Refine() at its first iteration: eight hypotheses, each with N inliers
+        assert (c["ok"], c["refined"], c["nInliers"], c["N"], c["iterations"], c["returnedAt"]) == (1, 1, 120, 120, k + 1, k)
+        assert c["mask"].all()
+        assert np.abs(c["Tcw"].reshape(4, 4) - p["Tcw_true"]).max() <= 1e-4      # the project's pose gate
+        assert np.abs(c["bestTcw"].reshape(4, 4) - p["Tcw_true"]).max() <= 1e-4  # the six-point hypothesis itself
+    assert (summ["hyp"][:8] == 120).all() and (summ["hyp"][8:] == -1).all()
+
+
+def test_budget_and_thresholds_match_the_shared_header(mpm):
+    assert mlpnp_solver_oracle.ransac(100) == (50, 35) == _header_ransac(mpm, 100)   # Tracking's parameters
+    assert mlpnp_solver_oracle.ransac(15) == (10, 14) == _header_ransac(mpm, 15)
+    assert mlpnp_solver_oracle.ransac(10) == (10, 1) == _header_ransac(mpm, 10)      # N == minInliers
+    for m in (6, 8, 10, 25):
+        for eps in (0.25, 0.4, 0.5, 0.75):
+            for N in list(range(0, 700)) + [1000, 4096, 8191]:
+                for ms in (6, 8):
+                    assert mlpnp_solver_oracle.ransac(N, m, 300, ms, eps) == _header_ransac(mpm, N, m, 300, ms, eps), (N, m, eps, ms)
+    assert mlpnp_solver_oracle.ransac(400, 10, 7, 6, 0.25) == (100, 7)               # clipped to maxIterations
+    lev = (1.44 ** np.arange(8)).astype(np.float32)
+    for s in lev:
+        assert mpm.mpm_max_error(float(s), 5.991) == float(np.float32(s) * np.float32(5.991))
+    rng = np.random.default_rng(0)
+    for r, d in list(zip(rng.integers(0, 2 ** 31, 5000), rng.integers(1, 4097, 5000))) + [(2 ** 31 - 1, 4096), (0, 1)]:
+        assert mpm.mpm_random_int(int(r), int(d)) == int((float(r) / (2147483647 + 1.0)) * int(d))
+    assert [mpm.mpm_call_end(0, 35, 5), mpm.mpm_call_end(35, 35, 5), mpm.mpm_call_end(3, 2, 5), mpm.mpm_call_end(7, 35, 0)] == [35, 40, 8, 35]
+
+
+def test_too_few_correspondences_report_no_more_without_an_iteration():
+    for p in (make_mlpnp_problem(0), make_mlpnp_problem(8, seed=1, **CLEAN), make_mlpnp_problem(40, seed=2, unmatched_frac=1.0)):
+        calls, summ = mlpnp_solver_oracle.run(p, libc_rand(1, 600), calls=[5, 5], stop=False)
+        for c in calls:
+            assert (c["ok"], c["noMore"], c["iterations"], c["nInliers"]) == (0, 1, 0, 0) and c["N"] < c["minInliers"]
+            assert np.array_equal(c["Tcw"], np.eye(4, dtype=np.float32).reshape(-1)) and not c["mask"].any()
+        assert (summ["hyp"] == -1).all()
+
+
+def test_iterate_loop_condition_is_an_or():
+    # 85 % outliers: no hypothesis reaches minInliers.  The first iterate(5) runs the whole budget of 35, a second call exactly 5 more
+    p = make_mlpnp_problem(150, seed=11, outlier_frac=0.85)
+    calls, summ = mlpnp_solver_oracle.run(p, libc_rand(3, 6 * 340), calls=[5, 5], stop=False)
+    assert summ["budget"] == 35
+    assert (calls[0]["ok"], calls[0]["noMore"], calls[0]["iterations"]) == (0, 1, 35)
+    assert (calls[1]["ok"], calls[1]["noMore"], calls[1]["iterations"]) == (0, 1, 40)
+    assert (summ["hyp"][:40] >= 0).all() and (summ["hyp"][40:] == -1).all() and summ["hyp"][:40].max() < summ["minInliers"]
+
+
+def test_refine_uses_the_best_mask_not_the_current_one():
+    # The first call returns from Refine() at iteration 2, whose 113 inliers are the best set.  The second call continues: iteration 3
+    # stays below minInliers, iteration 4 reaches it with 97 inliers, fewer than the best.  Refine() then runs on the BEST set again, so
+    # the call returns what the first call returned; a solver refining the current set would return another pose.
+    p = make_mlpnp_problem(160, seed=301, outlier_frac=0.15, noise_px=0.8)
+    r = libc_rand(301, 6 * 340)
+    calls, summ = mlpnp_solver_oracle.run(p, r, calls=[5, 5], stop=False)
+    a, b = calls
+    assert (a["ok"], a["refined"], a["returnedAt"], b["ok"], b["refined"], b["returnedAt"]) == (1, 1, 2, 1, 1, 4)
+    assert summ["hyp"][2] == a["bestInliers"] == b["bestInliers"] == 113 and summ["minInliers"] <= summ["hyp"][4] == 97 < 113
+    assert summ["hyp"][3] < summ["minInliers"]
+    assert np.array_equal(a["Tcw"], b["Tcw"]) and np.array_equal(a["mask"], b["mask"]) and a["nInliers"] == b["nInliers"] == 121
+    assert np.array_equal(a["bestMask"], b["bestMask"])
+    other, _ = mlpnp_solver_oracle.run(p, r, calls=[5, 5], stop=False, refine_current=True)   # the test knob: NOT the reference
+    assert other[1]["returnedAt"] == 4 and not np.array_equal(other[1]["Tcw"], b["Tcw"])
+
+
+def test_hand_derived_jacobian_matches_finite_differences():
+    rng = np.random.default_rng(5)
+    for w in [rng.normal(0, 0.5, 3) for _ in range(20)] + [np.zeros(3), rng.normal(0, 1e-9, 3), rng.normal(0, 1e-7, 3), rng.normal(0, 3e-8, 3),
+                                                           np.array([3.0, 0.5, -0.2])]:
+        x = np.concatenate([w, rng.normal(0, 1, 3)])
+        X = rng.normal(0, 1, 3) + [0, 0, 4]
+        f = np.array([rng.uniform(-0.8, 0.8), rng.uniform(-0.6, 0.6), 1.0])
+        _, J = mlpnp_solver_oracle.residual_jac(x, X, f)
+        Jn = np.zeros((2, 6))
+        for a in range(6):
+            d = np.zeros(6)
+            d[a] = 1e-6
+            Jn[:, a] = (mlpnp_solver_oracle.residual_jac(x + d, X, f)[0] - mlpnp_solver_oracle.residual_jac(x - d, X, f)[0]) / 2e-6
+        assert np.abs(J - Jn).max() <= 2e-8, (w, np.abs(J - Jn).max())   # central differences of step 1e-6: O(h^2) + eps / h ~ 1e-10
+
+
+def test_rounding_does_not_move_the_corpus():
+    """Every per-iteration count, mask, iteration number and return flag of the GPU corpus is the same whether the oracle is built
+    with -O2 -ffp-contract=off or with -O3 -ffp-contract=fast -march=native: the exact comparison on the GPU judges the kernel,
+    not rounding.  A seed that fails here is replaced in tests/mlpnp_solver_corpus.py (SEEDS), never tolerated."""
+    probs, rands = mlpnp_solver_corpus.problems()
+    assert len(probs) >= 25
+    for k, (p, r) in enumerate(zip(probs, rands)):
+        a, sa = mlpnp_solver_oracle.run(p, r, calls=[5] * 6, stop=False)
+        b, sb = mlpnp_solver_oracle.run(p, r, calls=[5] * 6, stop=False, flags=FAST)
+        assert np.array_equal(sa["hyp"], sb["hyp"]), (k, np.nonzero(sa["hyp"] != sb["hyp"])[0])
+        assert len(a) == len(b) == 6
+        for x, y in zip(a, b):
+            for f in ("ok", "noMore", "nInliers", "iterations", "bestInliers", "refined", "returnedAt", "N", "minInliers", "budget"):
+                assert x[f] == y[f], (k, f)
+            assert np.array_equal(x["mask"], y["mask"]) and np.array_equal(x["bestMask"], y["bestMask"]), k
+            assert np.abs(x["Tcw"] - y["Tcw"]).max() <= 1e-4 and np.abs(x["bestTcw"] - y["bestTcw"]).max() <= 1e-4, k
+
+
+def test_mlpnp_solver_kernel_uses_no_scratch(tmp_path):
+    lib = os.path.join(ROOT, "morb_slam_amd", "libmorb_hip.so")
+    assert os.path.exists(lib), "build() first"
+    assert all(shutil.which(os.path.join(LLVM, t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"))
+    meta = _kernel_scratch(lib, str(tmp_path))
+    ks = {k: v for k, v in meta.items() if "k_mlpnp_solver" in k and not k.endswith(".kd")}
+    assert ks, "k_mlpnp_solver is missing from the library"
+    assert all(v == 0 for v in ks.values()), ks
+
+
+def test_adapter_call_form_compiles_against_mocks(tmp_path):
+    """tests/native/mlpnp_solver_call_check.cc: a relocalisation caller written for this test against mock frames / map points /
+    Matrix4f; compiled to an object, the adapter's constructor template, the six-argument SetRansacParameters and iterate into a
+    Matrix4f must be instantiated."""
+    obj = str(tmp_path / "mp_call.o")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-c", "-o", obj, "-I" + os.path.join(NATIVE, "mock_ref"),
+                        "-I" + os.path.join(NATIVE, "mock_mlpnp_solver"), "-I" + os.path.join(ROOT, "include", "morb"),
+                        "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", os.path.join(NATIVE, "mlpnp_solver_call_check.cc")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    syms = subprocess.run(["nm", "-C", obj], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"MLPnPsolver::MLPnPsolver<ORB_SLAM3::Frame, ORB_SLAM3::MapPoint>", syms)
+    assert "MLPnPsolver::SetRansacParameters(double, int, int, int, float, float)" in syms
+    assert re.search(r"MLPnPsolver::iterate<Eigen::MatF<4, 4> >", syms)
