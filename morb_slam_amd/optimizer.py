@@ -5,29 +5,17 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import check, lib, ptr, stream_arg
+from .capi import HEADER, check, lib, ptr, stream_arg
 
 
-# morb_imu_preintegrated as a float32 record: field -> (offset, length)
-PREINT_FIELDS = {"dT": (0, 1), "dR": (1, 9), "dV": (10, 3), "dP": (13, 3), "JRg": (16, 9), "JVg": (25, 9), "JVa": (34, 9),
-                 "JPg": (43, 9), "JPa": (52, 9), "C": (61, 225), "b": (286, 6), "nga": (292, 6), "ngaWalk": (298, 6),
-                 "avgA": (304, 3), "avgW": (307, 3)}
-PREINT_FLOATS = 310
-
-# morb_sim3_solver_params / morb_sim3_solver_state (include/morb_hip.h) as numpy records
-SIM3_SOLVER_PARAMS = np.dtype([("T1w", "<f4", 12), ("T2w", "<f4", 12), ("cam1", "<f4", 9), ("cam2", "<f4", 9), ("probability", "<f8"),
-                               ("minInliers", "<i4"), ("maxIterations", "<i4"), ("fixScale", "<i4"), ("n", "<i4")], align=True)
-SIM3_SOLVER_STATE = np.dtype([("N", "<i4"), ("budget", "<i4"), ("iterations", "<i4"), ("bestInliers", "<i4"), ("converged", "<i4"),
-                              ("noMore", "<i4"), ("nInliers", "<i4"), ("convergedAt", "<i4"), ("bestT12", "<f4", 16), ("bestR", "<f4", 9),
-                              ("bestt", "<f4", 3), ("bestScale", "<f4"), ("sim3", "<f4", 16)], align=True)
-assert SIM3_SOLVER_PARAMS.itemsize == 192 and SIM3_SOLVER_STATE.itemsize == 212
-# morb_mlpnp_solver_params / morb_mlpnp_solver_state
-MLPNP_SOLVER_PARAMS = np.dtype([("cam", "<f4", 9), ("probability", "<f8"), ("minInliers", "<i4"), ("maxIterations", "<i4"), ("minSet", "<i4"),
-                                ("epsilon", "<f4"), ("th2", "<f4"), ("n", "<i4")], align=True)
-MLPNP_SOLVER_STATE = np.dtype([("N", "<i4"), ("minInliers", "<i4"), ("budget", "<i4"), ("iterations", "<i4"), ("bestInliers", "<i4"),
-                               ("ok", "<i4"), ("noMore", "<i4"), ("nInliers", "<i4"), ("refined", "<i4"), ("returnedAt", "<i4"),
-                               ("bestTcw", "<f4", 16), ("Tcw", "<f4", 16)], align=True)
-assert MLPNP_SOLVER_PARAMS.itemsize == 72 and MLPNP_SOLVER_STATE.itemsize == 168
+# morb_imu_preintegrated (include/morb_hip.h) as a float32 record: field -> (offset, length), both in floats
+_PREINT = HEADER.records["morb_imu_preintegrated"]
+assert all(_PREINT[n].base == np.float32 for n in _PREINT.names)
+PREINT_FIELDS = {n: (_PREINT.fields[n][1] // 4, int(np.prod(_PREINT[n].shape, dtype=int))) for n in _PREINT.names}
+PREINT_FLOATS = _PREINT.itemsize // 4
+# morb_sim3_solver_params / _state and morb_mlpnp_solver_params / _state as numpy records
+SIM3_SOLVER_PARAMS, SIM3_SOLVER_STATE, MLPNP_SOLVER_PARAMS, MLPNP_SOLVER_STATE = (
+    HEADER.records[f"morb_{s}_solver_{r}"] for s in ("sim3", "mlpnp") for r in ("params", "state"))
 
 
 class Optimizer:
@@ -277,10 +265,6 @@ def local_bundle_adjustment_oneshot(opt, kfPose, kfFixed, mpPos, eKF, eMP, eObs,
          np.ascontiguousarray(mpPos, np.float32).copy(), np.ascontiguousarray(eKF, np.int32), np.ascontiguousarray(eMP, np.int32),
          np.ascontiguousarray(eObs, np.float32), np.ascontiguousarray(eInvSigma2, np.float32)]
     erase = np.zeros(len(a[3]), np.uint8); stats = np.zeros(2, np.int32)
-    L.morb_local_bundle_adjustment.restype = C.c_int
-    L.morb_local_bundle_adjustment.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                               C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     check(L.morb_local_bundle_adjustment(opt._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), len(a[3]), ptr(a[3]), ptr(a[4]),
                                          ptr(a[5]), ptr(a[6]), cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["bf"],
                                          1 if inertial else 0, ptr(stop_flag) if stop_flag is not None else None, ptr(erase), ptr(stats)))
@@ -296,9 +280,6 @@ def local_bundle_adjustment_fisheye_oneshot(opt, kfPose, kfFixed, mpPos, eKF, eM
          np.ascontiguousarray(eObs2, np.float32), np.ascontiguousarray(eRight, np.uint8), np.ascontiguousarray(eInvSigma2, np.float32),
          np.ascontiguousarray(camL, np.float32), np.ascontiguousarray(camR, np.float32), np.ascontiguousarray(Trl, np.float32)]
     erase = np.zeros(len(a[3]), np.uint8); stats = np.zeros(2, np.int32)
-    L.morb_local_bundle_adjustment_fisheye.restype = C.c_int
-    L.morb_local_bundle_adjustment_fisheye.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + \
-        [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     check(L.morb_local_bundle_adjustment_fisheye(opt._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), len(a[3]), ptr(a[3]), ptr(a[4]),
                                                  ptr(a[5]), ptr(a[6]), ptr(a[7]), ptr(a[8]), ptr(a[9]), ptr(a[10]), 1 if inertial else 0,
                                                  ptr(stop_flag) if stop_flag is not None else None, ptr(erase), ptr(stats)))
@@ -345,7 +326,6 @@ class BAProblem:
     def schur_profile(self, iters=50):
         """(ms per launch, MFMA flops issued per launch, flops of the sparse block-pair form) of the Schur product."""
         ms = C.c_float(); fl = C.c_double(); uf = C.c_double()
-        self._L.morb_ba_schur_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self._L.morb_ba_schur_profile(self._h, int(iters), C.byref(ms), C.byref(fl), C.byref(uf)))
         return ms.value, fl.value, uf.value
 
