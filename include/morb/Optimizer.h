@@ -113,6 +113,7 @@ struct OptimizeSim3View {
 class Optimizer {
   friend class Sim3Solver;    // Sim3Solver.h: the solver runs on the kLoopClosing handle, under its mutex
   friend class MLPnPsolver;   // MLPnPsolver.h: the relocalisation solver runs on the kTracking handle, under its mutex
+  friend class TwoViewReconstruction;   // TwoViewReconstruction.h: the monocular initialisation, on the kTracking handle as well
 
  public:
   // static int PoseOptimization(Frame* pFrame)  Optimizer.h:86 -> number of inliers

@@ -721,6 +721,30 @@ int morb_mlpnp_solver_batch(morb_optimizer*, int nprob, int cap, const morb_mlpn
                             morb_mlpnp_solver_state* d_state, uint8_t* d_bestInliers, uint8_t* d_inliers, int* d_hypInliers, int hypCap,
                             void* stream);
 
+/* bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, T21, vP3D, vbTriangulated), src/TwoViewReconstruction.cc:41-130 with
+ * everything it calls and GeometricTools::Triangulate (src/GeometricTools.cc:48-72): what Pinhole::ReconstructWithTwoViews
+ * (src/CameraModels/Pinhole.cpp:85-98) runs for Tracking::MonocularInitialization (src/Tracking.cc:2326).  nprob problems, one workgroup
+ * each, asynchronous on the stream.  Problem p = (image d_img1[p], image d_img2[p]) of a keypoint pool [nimg][cap] with its counts, as
+ * the matcher entries take them: d_kpsUn holds mvKeysUn (undistorted; a KannalaBrandt8 caller undistorts first), and
+ * d_matches12 [nprob][cap] is vnMatches12 as the SearchForInitialization entry above writes it (an entry outside [0, count of image 2)
+ * is no match).  d_K4 [nprob][4] = fx fy cx cy of toK_(), d_sigma [nprob] = mSigma (1.0 in the reference).  maxIterations = the
+ * constructor's iterations (200).  d_rand [nprob][randCap]: the rand() values of DUtils::Random::RandomInt (:87), eight per iteration,
+ * iteration-major.  Outputs: d_ok [nprob] the return value; d_T21 [nprob][12] R21 row-major then t21 (zero unless ok);
+ * d_P3D [nprob][cap][3] and d_triangulated [nprob][cap] by frame-1 keypoint: the winning hypothesis' vP3D / vbTriangulated on BOTH
+ * paths (ReconstructH of this fork never assigns vP3D, :712-718), zero everywhere else, beyond the count and whenever ok is 0;
+ * d_stats [nprob][16] and d_fstats [nprob][29]: rows indexed by the enums TwoViewStat / TwoViewFStat of include/morb/two_view_math.h
+ * (N, model, best iterations, inlier count, nGood and parallax of every motion hypothesis, the chosen one, why it failed; SH SF RH, the
+ * best H21 and F21).  Optional (NULL to skip): d_inliersH / d_inliersF [nprob][cap] the best masks BY MATCH (entry k = the k-th match in
+ * frame-1 order), d_hypScores [nprob][2][maxIterations] the score of every iteration, H then F.
+ * Fewer than eight matches (undefined in the reference): no iteration, ok 0, model 0.  MORB_ERR_INVALID before any launch for
+ * maxIterations below 1, randCap below 8 * maxIterations or cap below 1.  The SVDs are the project's own FP64 Jacobi routines, the score
+ * sums the reference's sequential float sums ("TwoViewReconstruction"). */
+int morb_two_view_reconstruction_batch(morb_optimizer*, int nprob, int cap, const int* d_img1, const int* d_img2, const int* d_count,
+                                       const morb_keypoint* d_kpsUn, const int* d_matches12, const float* d_K4, const float* d_sigma,
+                                       int maxIterations, const int* d_rand, int randCap, int* d_ok, float* d_T21, float* d_P3D,
+                                       uint8_t* d_triangulated, int* d_stats, float* d_fstats, uint8_t* d_inliersH, uint8_t* d_inliersF,
+                                       float* d_hypScores, void* stream);
+
 /* ---- visual-inertial tracking and mapping ----
  * IMU::Preintegrated as plain data (include/ImuTypes.h:154-263): 3 x 3 blocks row-major, C = the 15 x 15 covariance
  * row-major, b = the bias the measurements were integrated with in IMU::Bias order (bax bay baz bwx bwy bwz),

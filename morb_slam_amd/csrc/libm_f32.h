@@ -5,10 +5,13 @@
 //   atan2f  sysdeps/ieee754/flt-32/e_atan2f.c   (fdlibm: quadrant logic around atanf(|y / x|))
 //   tanf    sysdeps/ieee754/flt-32/s_tanf.c, k_tanf.c  (fdlibm kernel behind the double-precision reduce_fast of sincosf.h; |x| < 120)
 //   sinf / cosf  sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c, sincosf.h (double-precision polynomials; restated for |x| < 120)
+//   acosf   sysdeps/ieee754/flt-32/e_acosf.c    (fdlibm: rational approximation on |x| < 0.5, sqrt((1 -+ x) / 2) beyond); every float in
+//           [-1, 1], NaN and |x| > 1 (NaN) are compared with this libm by tests/test_two_view_cpu.py
 // tools/check_libm_f32.cc compares every one of them against this container's libm: atanf over ALL floats, tanf, sinf and cosf over
 // all floats in [-8, 8], atan2f over 2^32 structured + random pairs — bit-equal.
 // Everything is plain IEEE arithmetic; the library is built with -ffp-contract=off, which these sequences rely on.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 
@@ -55,6 +58,41 @@ MORB_LIBM_FN float atanf_glibc(float x) {
   if (id < 0) return x - x * (s1 + s2);
   const float r = atanhi[id] - ((x * (s1 + s2) - atanlo[id]) - x);
   return hx < 0 ? -r : r;
+}
+
+MORB_LIBM_FN float acosf_glibc(float x) {
+  const float pi = 3.1415925026e+00f, pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f;
+  const float pS0 = 1.6666667163e-01f, pS1 = -3.2556581497e-01f, pS2 = 2.0121252537e-01f, pS3 = -4.0055535734e-02f, pS4 = 7.9153501429e-04f,
+              pS5 = 3.4793309169e-05f, qS1 = -2.4033949375e+00f, qS2 = 2.0209457874e+00f, qS3 = -6.8828397989e-01f, qS4 = 7.7038154006e-02f;
+  const int32_t hx = (int32_t)f2u(x), ix = hx & 0x7fffffff;
+  if (ix == 0x3f800000) return hx > 0 ? 0.0f : pi + 2.0f * pio2_lo;   // |x| == 1
+  if (ix > 0x3f800000) return (x - x) / (x - x);                       // |x| > 1 or NaN
+  if (ix < 0x3f000000) {                                               // |x| < 0.5
+    if (ix <= 0x32800000) return pio2_hi + pio2_lo;                    // |x| <= 2^-26
+    const float z = x * x;
+    const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const float q = 1.0f + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const float r = p / q;
+    return pio2_hi - (x - (pio2_lo - r * x));
+  }
+  if (hx < 0) {                                                        // x < -0.5
+    const float z = (1.0f + x) * 0.5f;
+    const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const float q = 1.0f + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const float s = sqrtf(z);
+    const float r = p / q;
+    const float w = r * s - pio2_lo;
+    return pi - 2.0f * (s + w);
+  }
+  const float z = (1.0f - x) * 0.5f;                                   // x > 0.5
+  const float s = sqrtf(z);
+  const float df = u2f(f2u(s) & 0xfffff000u);
+  const float c = (z - df * df) / (s + df);
+  const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+  const float q = 1.0f + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+  const float r = p / q;
+  const float w = r * s + c;
+  return 2.0f * (df + w);
 }
 
 MORB_LIBM_FN float atan2f_glibc(float y, float x) {

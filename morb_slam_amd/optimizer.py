@@ -16,6 +16,12 @@ PREINT_FLOATS = _PREINT.itemsize // 4
 # morb_sim3_solver_params / _state and morb_mlpnp_solver_params / _state as numpy records
 SIM3_SOLVER_PARAMS, SIM3_SOLVER_STATE, MLPNP_SOLVER_PARAMS, MLPNP_SOLVER_STATE = (
     HEADER.records[f"morb_{s}_solver_{r}"] for s in ("sim3", "mlpnp") for r in ("params", "state"))
+# the rows morb_two_view_reconstruction_batch writes to d_stats / d_fstats, index by index: the enums TwoViewStat / TwoViewFStat of
+# include/morb/two_view_math.h (tests/test_two_view_cpu.py compares these tuples with what the compiler makes of the enums)
+TWO_VIEW_STATS = ("N", "MODEL", "BEST_IT_H", "BEST_IT_F", "NINLIERS", "NHYP", "CHOSEN", "FAIL") + tuple(f"NGOOD{k}" for k in range(8))
+TWO_VIEW_FSTATS = ("SH", "SF", "RH") + tuple(f"H21_{k}" for k in range(9)) + tuple(f"F21_{k}" for k in range(9)) + \
+    tuple(f"PARALLAX{k}" for k in range(8))
+TWO_VIEW_FAIL = ("NONE", "FEW_MATCHES", "ZERO_SCORE", "DEGENERATE_H", "AMBIGUOUS", "PARALLAX")
 
 
 class Optimizer:
@@ -145,6 +151,37 @@ class Optimizer:
     def mlpnp_solver_state(state):
         """The state tensor u8 [P, 168] -> numpy MLPNP_SOLVER_STATE records [P]."""
         return np.frombuffer(state.cpu().numpy().tobytes(), MLPNP_SOLVER_STATE).copy()
+
+    def TwoViewReconstruction(self, img1, img2, count, kps, matches12, K4, sigma, rand, maxIterations=200, out=None, masks=False,
+                              hypScores=False, stream=None):
+        """Batched TwoViewReconstruction::Reconstruct (morb_two_view_reconstruction_batch), what Pinhole::ReconstructWithTwoViews runs
+        for the monocular initialisation.  Device tensors, P problems over a keypoint pool: img1 / img2 i32 [P] (pool images), count
+        i32 [nimg], kps [nimg, cap] KP_DTYPE records (mvKeysUn; a u8 view [nimg, cap, 28] will do), matches12 i32 [P, cap] (vnMatches12
+        as SearchForInitialization writes it), K4 f32 [P, 4] (fx fy cx cy), sigma f32 [P], rand i32 [P, randCap >= 8 maxIterations]
+        (rand() values, eight per iteration).  out = (ok i32 [P], T21 f32 [P, 12], P3D f32 [P, cap, 3], triangulated u8 [P, cap],
+        stats i32 [P, len(TWO_VIEW_STATS)], fstats f32 [P, len(TWO_VIEW_FSTATS)]) or None.  masks / hypScores: True allocates, a tuple
+        (inliersH, inliersF) u8 [P, cap] / a tensor f32 [P, 2, maxIterations] is used as given.  Returns a dict of all of them."""
+        import torch
+        P, cap = matches12.shape
+        dev = matches12.device
+        if out is None:
+            out = (torch.empty((P,), dtype=torch.int32, device=dev), torch.empty((P, 12), dtype=torch.float32, device=dev),
+                   torch.empty((P, cap, 3), dtype=torch.float32, device=dev), torch.empty((P, cap), dtype=torch.uint8, device=dev),
+                   torch.empty((P, len(TWO_VIEW_STATS)), dtype=torch.int32, device=dev),
+                   torch.empty((P, len(TWO_VIEW_FSTATS)), dtype=torch.float32, device=dev))
+        if masks is True:
+            masks = (torch.empty((P, cap), dtype=torch.uint8, device=dev), torch.empty((P, cap), dtype=torch.uint8, device=dev))
+        if hypScores is True:
+            hypScores = torch.empty((P, 2, max(int(maxIterations), 1)), dtype=torch.float32, device=dev)
+        inlH, inlF = masks if masks else (None, None)
+        hyp = hypScores if hypScores is not False else None
+        st = stream_arg(stream)
+        check(self._L.morb_two_view_reconstruction_batch(self._h, P, cap, ptr(img1), ptr(img2), ptr(count), ptr(kps), ptr(matches12), ptr(K4),
+                                                         ptr(sigma), int(maxIterations), ptr(rand), rand.shape[1], ptr(out[0]), ptr(out[1]),
+                                                         ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(out[5]), ptr(inlH), ptr(inlF), ptr(hyp),
+                                                         st))
+        return dict(ok=out[0], T21=out[1], P3D=out[2], triangulated=out[3], stats=out[4], fstats=out[5], inliersH=inlH, inliersF=inlF,
+                    hypScores=hyp)
 
     # ---- visual-inertial tracking and mapping (SURVEY 8(f) N1) ---------------------------------------------------
     def PreintegrateIMU(self, start, acc, gyro, dt, bias, nga, walk, out=None, stream=None):

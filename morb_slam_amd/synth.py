@@ -786,3 +786,100 @@ def pack_mlpnp_problems(probs, device, rand=None, cap=None):
             a[k, :len(r)] = r
         t["rand"] = torch.from_numpy(a).to(device)
     return t
+
+
+# ---- TwoViewReconstruction (two frames of a monocular initialisation and vnMatches12) ---------------------------
+TWO_VIEW_KINDS = ("general", "planar", "rotation", "outliers", "tiny", "small_baseline", "epipolar", "corners")
+
+
+def make_two_view_problem(seed=0, kind="general", n1=300, n2=280, n_matches=200, noise_px=0.4, outlier_frac=None, sigma=1.0,
+                          max_iterations=200, K4=(520.0, 522.0, 318.5, 241.0), width=640, height=480, corner_px=1.5):
+    """One TwoViewReconstruction input: n1 / n2 undistorted keypoints of frames 1 and 2 (matched and unmatched ones in a seeded random
+    order), vnMatches12 [n1] (frame-2 index or -1) with n_matches matches, a pinhole K4 = fx fy cx cy, and the ground truth T21 (4 x 4;
+    the translation's length is not observable).  kind: "general" (points at depths 2.5 .. 9), "planar" (points on one tilted plane),
+    "rotation" (a baseline of 1e-4: near-pure rotation), "outliers" (45 % of the matches wrong unless outlier_frac says otherwise),
+    "tiny" (as general; meant for n_matches around 8), "small_baseline" (a clear winner whose parallax stays below one degree),
+    "epipolar" (a fifth of the matches moved along their epipolar line to a negative depth: they pass CheckFundamental and fail
+    CheckRT), "corners" (five corners of one tilted plane under a wide baseline, each matched n_matches / 5 times within corner_px
+    pixels of the corner in frame 1: with corner_px = 0 the frame-1 positions of a corner's matches coincide, as one corner detected
+    on several pyramid levels does; the one kind whose samples let SH exceed SF, see tests/two_view_corpus.py).  Matched keypoints carry
+    Gaussian pixel noise noise_px in frame 2."""
+    assert kind in TWO_VIEW_KINDS and n_matches <= min(n1, n2)
+    rng = np.random.default_rng(0x7E01 + seed)
+    fx, fy, cx, cy = K4
+    if outlier_frac is None:
+        outlier_frac = 0.45 if kind == "outliers" else 0.08
+    R = _rot_from_rotvec(rng.normal(0, 0.06, 3))
+    tdir = np.array([rng.choice([-1.0, 1.0]) * rng.uniform(0.7, 1.0), rng.normal(0, 0.25), rng.normal(0, 0.25)])
+    tdir /= np.linalg.norm(tdir)
+    base = {"rotation": 1e-4, "small_baseline": 0.08, "corners": rng.uniform(0.9, 1.3)}.get(kind, rng.uniform(0.35, 0.6))
+    t = tdir * base
+    m = n_matches
+    u = np.stack([rng.uniform(30, width - 30, m), rng.uniform(30, height - 30, m)], 1)
+    if kind == "corners":   # five corners of one plane, each detected many times within a pixel or two
+        centre = np.stack([rng.uniform(60, width - 60, 5), rng.uniform(60, height - 60, 5)], 1)
+        u = centre[np.arange(m) % 5] + rng.uniform(-corner_px, corner_px, (m, 2))
+    ray = np.stack([(u[:, 0] - cx) / fx, (u[:, 1] - cy) / fy, np.ones(m)], 1)
+    if kind in ("planar", "corners"):
+        tilt = 0.6 if kind == "corners" else 0.25
+        nrm = np.array([rng.normal(0, tilt), rng.normal(0, tilt), -1.0])
+        nrm /= np.linalg.norm(nrm)
+        z = 4.5 * nrm[2] / (ray @ nrm)   # the plane nrm . X = 4.5 nrm_z: depth 4.5 on the optical axis
+    elif kind == "small_baseline":
+        z = rng.uniform(5.5, 7.0, m)
+    else:
+        z = rng.uniform(2.5, 9.0, m)
+    X1 = ray * z[:, None]
+    X2 = X1 @ R.T + t
+    v = np.stack([fx * X2[:, 0] / X2[:, 2] + cx, fy * X2[:, 1] / X2[:, 2] + cy], 1)
+    if kind == "epipolar":   # reflect the projection through the vanishing point of the ray: a negative depth on the same epipolar line
+        Xinf = ray @ R.T
+        vinf = np.stack([fx * Xinf[:, 0] / Xinf[:, 2] + cx, fy * Xinf[:, 1] / Xinf[:, 2] + cy], 1)
+        moved = rng.random(m) < 0.2
+        v[moved] = 2 * vinf[moved] - v[moved]
+    v = v + rng.normal(0, noise_px, (m, 2))
+    out = rng.random(m) < outlier_frac
+    v[out] = np.stack([rng.uniform(0, width, int(out.sum())), rng.uniform(0, height, int(out.sum()))], 1)
+    kp1 = np.stack([rng.uniform(0, width, n1), rng.uniform(0, height, n1)], 1)
+    kp2 = np.stack([rng.uniform(0, width, n2), rng.uniform(0, height, n2)], 1)
+    i1 = np.sort(rng.permutation(n1)[:m])
+    i2 = rng.permutation(n2)[:m]
+    kp1[i1], kp2[i2] = u, v
+    matches = np.full(n1, -1, np.int32)
+    matches[i1] = i2
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    return dict(kind=kind, n1=n1, n2=n2, kp1=kp1.astype(np.float32), kp2=kp2.astype(np.float32), matches12=matches,
+                K4=np.array(K4, np.float32), sigma=float(sigma), max_iterations=int(max_iterations), T21_true=T, outlier=out,
+                noise_px=float(noise_px))
+
+
+def pack_two_view_problems(probs, device, rand=None, cap=None):
+    """make_two_view_problem dicts -> the torch tensors of Optimizer.TwoViewReconstruction on `device`: a keypoint pool kps u8 view of
+    KP_DTYPE records [2 P, cap] (problem p owns images 2 p and 2 p + 1), img1 / img2 i32 [P], count i32 [2 P], matches12 i32 [P, cap]
+    (-1 padded), K4 f32 [P, 4], sigma f32 [P], rand i32 [P, randCap] (the given list of arrays, zero padded).  cap = the largest frame
+    unless given."""
+    import torch
+    from .capi import KP_DTYPE
+    P = len(probs)
+    cap = cap or max(max(max(p["n1"], p["n2"]) for p in probs), 1)
+    kps = np.zeros((2 * P, cap), KP_DTYPE)
+    count = np.zeros(2 * P, np.int32)
+    m12 = np.full((P, cap), -1, np.int32)
+    for k, p in enumerate(probs):
+        for j, (key, n) in enumerate((("kp1", p["n1"]), ("kp2", p["n2"]))):
+            kps[2 * k + j, :n]["x"], kps[2 * k + j, :n]["y"] = p[key][:, 0], p[key][:, 1]
+            count[2 * k + j] = n
+        m12[k, :p["n1"]] = p["matches12"]
+    t = {"kps": torch.from_numpy(kps.view(np.uint8).reshape(2 * P, cap, KP_DTYPE.itemsize).copy()).to(device),
+         "img1": torch.arange(0, 2 * P, 2, dtype=torch.int32).to(device), "img2": torch.arange(1, 2 * P, 2, dtype=torch.int32).to(device),
+         "count": torch.from_numpy(count).to(device), "matches12": torch.from_numpy(m12).to(device),
+         "K4": torch.from_numpy(np.stack([p["K4"] for p in probs]).astype(np.float32)).to(device),
+         "sigma": torch.from_numpy(np.array([p["sigma"] for p in probs], np.float32)).to(device)}
+    if rand is not None:
+        rc = max(max(len(r) for r in rand), 1)
+        a = np.zeros((P, rc), np.int32)
+        for k, r in enumerate(rand):
+            a[k, :len(r)] = r
+        t["rand"] = torch.from_numpy(a).to(device)
+    return t
