@@ -15,6 +15,7 @@
 
 #include "Optimizer.h"
 #include "mlpnp_solver_math.h"
+#include "ransac_math.h"
 
 namespace ORB_SLAM3 {
 
@@ -61,7 +62,7 @@ class MLPnPsolver {
     params_.epsilon = epsilon;
     params_.th2 = th2;
     minInliers_ = morbpnp::mlpnp_min_inliers(N_, minInliers, minSet, epsilon);
-    budget_ = morbpnp::mlpnp_budget(N_, minInliers_, morbpnp::mlpnp_epsilon(N_, minInliers_, epsilon), probability, maxIterations);
+    budget_ = morbransac::ransac_budget(N_, minInliers_, morbpnp::mlpnp_epsilon(N_, minInliers_, epsilon), probability, maxIterations);
   }
 
   // bool iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers, Eigen::Matrix4f& Tout)  (:100-223)

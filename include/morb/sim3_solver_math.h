@@ -1,8 +1,7 @@
 // Scalar pieces of Sim3Solver (reference src/Sim3Solver.cc) shared by the kernel (sim3_solver.hip), the C++ adapter
 // (include/morb/Sim3Solver.h) and the CPU tests: plain C++ that compiles for the host and for the device.
-//   * sim3s_budget: SetRansacParameters (:122-146), mRansacMaxIts from N;
+//   * sim3s_budget: SetRansacParameters (:122-146), mRansacMaxIts from N (the formula itself is ransac_math.h's);
 //   * sim3s_max_error: 9.210 * sigma2 stored in a std::vector<size_t> (Sim3Solver.h:84-85, :98-99), i.e. truncated;
-//   * sim3s_random_int: DUtils::Random::RandomInt(0, d - 1) on a rand() value;
 //   * sim3s_atan2: the double atan2 of ComputeSim3 (:335), fdlibm's e_atan2.c / s_atan.c.  The reference rounds 2 * atan2(..)
 //     to float at once, so this restatement is held to that precision: tests/test_sim3_solver_cpu.py compares
 //     (float)(2 * sim3s_atan2(y, x)) with the host libm's over float-valued arguments.
@@ -11,8 +10,9 @@
 #include <cstdint>
 #include <cstring>
 
+#include "ransac_math.h"
+
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
 #define MORB_SIM3S_FN __host__ __device__ __forceinline__
 #else
 #define MORB_SIM3S_FN inline
@@ -20,33 +20,16 @@
 
 namespace morbs3 {
 
-// SetRansacParameters: epsilon = (float)minInliers / N; nIterations = minInliers == N ? 1 : ceil(log(1 - p) / log(1 - pow(eps, 3)));
-// max(1, min(nIterations, maxIterations)).  pow(float, int) is the double pow; the double -> int conversion of a NaN or of a
-// value beyond int is x86-64's cvttsd2si result INT_MIN (N < minInliers gives a NaN, minInliers / N below ~1.29e-3 a value
-// beyond 2^31), which the max(1, ..) clamp turns into a budget of 1.
-MORB_SIM3S_FN int cvt_i32_x86(double v) {
-  if (!(v >= -2147483648.0 && v < 2147483648.0)) return (int)0x80000000u;
-  return (int)v;
-}
+// SetRansacParameters: epsilon = (float)minInliers / N, then the shared budget (N < minInliers gives a NaN ratio, minInliers / N
+// below ~1.29e-3 one beyond 2^31: both a budget of 1)
 MORB_SIM3S_FN int sim3s_budget(int N, int minInliers, double probability, int maxIterations) {
   const float epsilon = (float)minInliers / N;
-  int nIterations;
-  if (minInliers == N) nIterations = 1;
-  else {
-    const double e = (double)epsilon;
-    nIterations = cvt_i32_x86(ceil(log(1 - probability) / log(1 - pow(e, 3.0))));
-  }
-  const int m = nIterations < maxIterations ? nIterations : maxIterations;
-  return m > 1 ? m : 1;
+  return morbransac::ransac_budget(N, minInliers, (double)epsilon, probability, maxIterations);
 }
 
 MORB_SIM3S_FN float sim3s_max_error(float sigma2) {   // (float)(size_t)(9.210 * sigma2)
   return (float)(uint64_t)(9.210 * (double)sigma2);
 }
-
-// int(((double)r / ((double)RAND_MAX + 1.0)) * d): RAND_MAX = 2^31 - 1 (glibc), so the quotient is r * 2^-31 exactly and the
-// product r * d < 2^53 is exact too: the index is (r * d) >> 31.
-MORB_SIM3S_FN int sim3s_random_int(int r, int d) { return (int)(((uint64_t)(uint32_t)r * (uint64_t)(uint32_t)d) >> 31); }
 
 MORB_SIM3S_FN uint64_t d2u(double x) { uint64_t u; memcpy(&u, &x, 8); return u; }
 

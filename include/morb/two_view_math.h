@@ -3,13 +3,12 @@
 // the device.
 //   * TwoViewStat / TwoViewFStat: the rows morb_two_view_reconstruction_batch writes to d_stats / d_fstats, index by index;
 //   * TwoViewFail: why a problem returned false (d_stats[TV_S_FAIL]);
-//   * tv_random_int: DUtils::Random::RandomInt(0, d - 1) on a rand() value (the formula of morbpnp::mlpnp_random_int);
-//   * tv_sample8: one iteration's minimal set (:82-95), swap-with-back sampling without the vector;
+//   * tv_sample8: one iteration's minimal set (:82-95), swap-with-back sampling without the vector (RandomInt is ransac_math.h's);
 //   * tv_min_good: nMinGood of ReconstructF (:510);  tv_parallax_deg: acos(c) * 180 / CV_PI as the reference's types evaluate it (:875).
 #pragma once
 #include <cstdint>
 
-#include "mlpnp_solver_math.h"
+#include "ransac_math.h"
 
 #if defined(__HIPCC__)
 #define MORB_TV_FN __host__ __device__ __forceinline__
@@ -60,8 +59,6 @@ constexpr int TV_MIN_TRIANGULATED = 50;   // Reconstruct's last argument to Reco
 constexpr float TV_MIN_PARALLAX = 1.0f;   // (:115)
 constexpr int TV_PARALLAX_RANK = 50;      // vCosParallax[min(50, size - 1)] of the sorted list (:874)
 
-MORB_TV_FN int tv_random_int(int r, int d) { return morbpnp::mlpnp_random_int(r, d); }
-
 // vAvailableIndices = 0 .. N-1; eight times: randi = RandomInt(0, size - 1), take [randi], move the back there, pop (:83-94).
 // Without the vector: the value at a position is the latest one moved there, or the position itself.  N >= 8.
 MORB_TV_FN void tv_sample8(const int* r, int N, int* idx) {
@@ -69,7 +66,7 @@ MORB_TV_FN void tv_sample8(const int* r, int N, int* idx) {
   MORB_TV_UNROLL
   for (int i = 0; i < TV_SET; ++i) {
     const int size = N - i;
-    const int randi = tv_random_int(r[i], size);
+    const int randi = morbransac::random_int(r[i], size);
     int v = randi, bv = size - 1;
     MORB_TV_UNROLL
     for (int k = 0; k < TV_SET; ++k) {

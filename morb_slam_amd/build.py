@@ -27,8 +27,7 @@ def build_hip(force=False, verbose=False, extra_flags=(), out=OUT):
     from concurrent.futures import ThreadPoolExecutor
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + \
-        glob.glob(os.path.join(ROOT, "include", "*.h")) + [os.path.join(ROOT, "include", "morb", "sim3_solver_math.h"), os.path.join(ROOT, "include", "morb", "mlpnp_solver_math.h"),
-                                                       os.path.join(ROOT, "include", "morb", "two_view_math.h")]
+        glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(ROOT, "include", "morb", "*.h"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(CSRC, "_obj" + ("_" + "".join(c for c in "".join(extra_flags) if c.isalnum()) if extra_flags else ""))
     os.makedirs(objdir, exist_ok=True)

@@ -77,6 +77,16 @@ int grow(GrowOnly<Block>& b, size_t n, T** out) {
   return rc;
 }
 
+// The per-problem workspace of a batched RANSAC solver, whose entries (`words` 4-byte words each) live in LDS up to ldsN per problem:
+// only a batch whose cap exceeds ldsN gets one, *pitch bytes (a multiple of 256) per problem at *ws; else *ws = null, *pitch = 0.
+inline int grow_beyond_lds(DeviceGrow& b, int nprob, int cap, int ldsN, int words, char** ws, size_t* pitch) {
+  *ws = nullptr;
+  *pitch = 0;
+  if (cap <= ldsN) return MORB_OK;
+  *pitch = ((size_t)cap * words * 4 + 255) / 256 * 256;
+  return grow(b, *pitch * (size_t)nprob, ws);
+}
+
 // the stream a call runs on: the caller's, or the handle's own when the caller passes none
 template <class Handle>
 inline hipStream_t stream_or_own(const Handle* h, void* stream) { return stream ? (hipStream_t)stream : (hipStream_t)h->stream; }

@@ -39,6 +39,29 @@ __device__ __forceinline__ void kb8_unproject(const KB8& c, float px, float py, 
   }
   ray[0] = pwx * scale; ray[1] = pwy * scale; ray[2] = 1.f;
 }
+
+// A camera of either model, as the RANSAC solvers hold it (sim3_solver.hip, mlpnp_solver.hip): k.p = fx fy cx cy k0 k1 k2 k3.
+struct Cam { int kb8; KB8 k; };
+
+// Pinhole::project (Pinhole.cpp:46-52), KannalaBrandt8::project (KannalaBrandt8.cpp:68-86), both in float
+__device__ __forceinline__ void cam_project(const Cam& c, const float* v, float* uv) {
+  if (!c.kb8) {
+    uv[0] = c.k.p[0] * v[0] / v[2] + c.k.p[2];
+    uv[1] = c.k.p[1] * v[1] / v[2] + c.k.p[3];
+    return;
+  }
+  kb8_project_f(c.k, v, uv);
+}
+__device__ __forceinline__ void cam_unproject(const Cam& c, float px, float py, float* ray) {   // unproject(cv::Point2f)
+  if (!c.kb8) {
+    ray[0] = (px - c.k.p[2]) / c.k.p[0];
+    ray[1] = (py - c.k.p[3]) / c.k.p[1];
+    ray[2] = 1.f;
+    return;
+  }
+  kb8_unproject(c.k, px, py, ray);
+}
+
 // (the (p, q) loops and every k loop are unrolled: with run-time indices M and V live in scratch memory and each of the 180 rotations is
 // ~50 dependent memory accesses; with constant indices they are 32 FP64 registers)
 __device__ inline void null_vector4(const float* A, double* out) {

@@ -1,14 +1,14 @@
 // MLPnPsolver (reference src/MLPnPsolver.cpp) for MI355X (gfx950), batched: one 256-thread workgroup per problem (a frame and the map
 // points one relocalisation candidate matched to it).  Each call restates
-//   * the constructor (:55-97): the kept matches compacted in feature order (wave ballots), bearing vectors unproject(kp.pt) / z
-//     in float (Pinhole, or KannalaBrandt8's Newton unprojection of kb8.h), world points, sigma2;
-//   * SetRansacParameters (:225-260) from the device-side N (include/morb/mlpnp_solver_math.h);
+//   * the constructor (:55-97): the kept matches compacted in feature order (ransac_block.h), bearing vectors unproject(kp.pt) / z
+//     in float (cam_unproject of kb8.h: Pinhole, or KannalaBrandt8's Newton unprojection), world points, sigma2;
+//   * SetRansacParameters (:225-260) from the device-side N (include/morb/mlpnp_solver_math.h, ransac_math.h);
 //   * iterate (:100-223) from state.iterations on: DUtils::Random::RandomInt + swap-with-back sampling on the caller's rand() values
 //     (minSet per iteration, indexed by the global iteration number), computePose (:356-658) in FP64, CheckInliers (:262-293) in
 //     float, the running best, Refine() on the BEST mask after every iteration that reaches minInliers, the post-loop best branch.
 // Mapping: the correspondences (10 words each) live in LDS up to MP_LDS_N, in the handle's mlpnpCorr workspace beyond.  Hypotheses
 // are built MP_G at a time, speculatively (sampling depends only on the rand() stream and N): a row of 16 lanes per hypothesis,
-// its 12 x 12 normal matrix and eigenvector matrix resident in LDS, lane k owning row / column k of a Jacobi rotation; the six
+// its 12 x 12 normal matrix and eigenvector matrix resident in LDS, lane k owning row / column k of a Jacobi rotation (row_jacobi.h); the six
 // residual rows of the Gauss-Newton are one lane each.  Their inliers are counted one wave per hypothesis (ballots), then the
 // reference's rule is applied in iteration order, so nothing after the first success is reported.  Refine() runs the same
 // 16-lane routine over the best inliers, 16 correspondences at a time.  The numerical choices Eigen made for the reference
@@ -23,6 +23,9 @@
 #include "libm_f32.h"
 #include "morb_hip.h"
 #include "morb/mlpnp_solver_math.h"
+#include "morb/ransac_math.h"
+#include "ransac_block.h"
+#include "row_jacobi.h"
 
 #ifndef MORB_MLPNP_THREADS
 #define MORB_MLPNP_THREADS 256
@@ -32,7 +35,7 @@ namespace {
 
 constexpr int MP_NT = MORB_MLPNP_THREADS;
 constexpr int MP_NW = MP_NT / 64;
-constexpr int MP_GL = 16;              // lanes per hypothesis
+constexpr int MP_GL = morbrow::ROW_LANES;   // lanes per hypothesis
 constexpr int MP_G = MP_NT / MP_GL;    // hypotheses built per batch
 constexpr int MP_LDS_N = 384;          // correspondences held in LDS; beyond, the global workspace
 constexpr int MP_W = 10;               // words per correspondence
@@ -40,34 +43,17 @@ constexpr int MP_MAXSET = 16;          // largest minSet
 constexpr double MP_EPS = 2.220446049250313e-16;
 static_assert(MP_NT % 64 == 0 && MP_NT >= 64, "whole waves");
 
-#define MP_GSYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-struct Cam { int kb8; morbkb8::KB8 k; };
-
-__device__ __forceinline__ void cam_project(const Cam& c, const float* v, float* uv) {   // project(cv::Point3f)
-  if (!c.kb8) {
-    uv[0] = c.k.p[0] * v[0] / v[2] + c.k.p[2];
-    uv[1] = c.k.p[1] * v[1] / v[2] + c.k.p[3];
-    return;
-  }
-  morbkb8::kb8_project_f(c.k, v, uv);
-}
-__device__ __forceinline__ void cam_unproject(const Cam& c, float px, float py, float* ray) {   // unproject(cv::Point2f)
-  if (!c.kb8) {
-    ray[0] = (px - c.k.p[2]) / c.k.p[0];
-    ray[1] = (py - c.k.p[3]) / c.k.p[1];
-    ray[2] = 1.f;
-    return;
-  }
-  morbkb8::kb8_unproject(c.k, px, py, ray);
-}
+using morbkb8::Cam;
+using morbkb8::cam_project;
+using morbkb8::cam_unproject;
+using namespace morbransac;
+using morbrow::g_jacobi;
 
 struct Corr {   // structure of arrays, `stride` entries each
   float *X, *uv, *err, *br;
   int *id, *list;
   int stride;
 };
-__host__ __device__ inline size_t mp_bytes_per_problem(int cap) { return ((size_t)cap * MP_W * 4 + 255) / 256 * 256; }
 __device__ inline Corr mp_carve(float* base, int stride) {
   Corr c;
   c.X = base; c.uv = base + 3 * stride; c.err = base + 5 * stride; c.br = base + 6 * stride;
@@ -227,75 +213,14 @@ __device__ __forceinline__ bool ldlt6_solve(const double* A, const double* g, do
   return ok;
 }
 
-// sum over columns j of the squares of column j's entries (all rows, or the rows above the diagonal), columns added in order
-__device__ __forceinline__ double g_colsum(Grp& g, const double* A, int m, int l, bool upper) {
-  double c = 0;
-  if (l < m) {
-    const int rows = upper ? l : m;
-    for (int i = 0; i < rows; ++i) c += A[i * m + l] * A[i * m + l];
-  }
-  g.red[l] = c;
-  MP_GSYNC();
-  double s = 0;
-  for (int j = 0; j < m; ++j) s += g.red[j];
-  MP_GSYNC();
-  return s;
-}
-
-// cyclic Jacobi of the symmetric m x m matrix A (LDS, row-major) by the 16 lanes of a row; V receives the eigenvectors as columns
-__device__ __forceinline__ void g_jacobi(Grp& g, int m, int l) {
-  double* A = g.W;
-  double* V = g.W + 144;
-  for (int e = l; e < m * m; e += MP_GL) V[e] = (e / m == e % m) ? 1.0 : 0.0;
-  MP_GSYNC();
-  const double fro = g_colsum(g, A, m, l, false);
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    const double off = g_colsum(g, A, m, l, true);
-    if (!(off > 1e-30 * fro)) break;
-    for (int p = 0; p < m - 1; ++p)
-      for (int q = p + 1; q < m; ++q) {
-        const double apq = A[p * m + q];
-        if (apq == 0.0) continue;
-        const double app = A[p * m + p], aqq = A[q * m + q];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        if (l < m) {
-          const int k = l;
-          double np_ = 0, nq = 0;
-          const bool mid = k != p && k != q;
-          if (mid) {
-            const double akp = A[k * m + p], akq = A[k * m + q];
-            np_ = c * akp - s * akq;
-            nq = s * akp + c * akq;
-          }
-          const double vkp = V[k * m + p], vkq = V[k * m + q];
-          if (mid) {
-            A[k * m + p] = np_; A[p * m + k] = np_;
-            A[k * m + q] = nq; A[q * m + k] = nq;
-          }
-          V[k * m + p] = c * vkp - s * vkq;
-          V[k * m + q] = s * vkp + c * vkq;
-          if (k == p) {
-            A[p * m + p] = app - t * apq;
-            A[q * m + q] = aqq + t * apq;
-            A[p * m + q] = 0.0;
-            A[q * m + p] = 0.0;
-          }
-        }
-        MP_GSYNC();
-      }
-  }
-}
-
 // U V^T of the SVD of M = M (M^T M)^-1/2, negated when its determinant is negative; every lane of the row returns it
 __device__ __forceinline__ void g_nearest_rotation(Grp& g, const double* M, int l, double* R) {
   if (l < 9) {
     const int i = l / 3, j = l % 3;
     g.W[l] = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j];
   }
-  MP_GSYNC();
-  g_jacobi(g, 3, l);
+  MORB_ROW_SYNC();
+  g_jacobi(g.W, g.W + 144, g.red, 3, l);
   const double* V = g.W + 144;
   const double w[3] = {1.0 / sqrt(g.W[0]), 1.0 / sqrt(g.W[4]), 1.0 / sqrt(g.W[8])};
   double S[9];
@@ -311,7 +236,7 @@ __device__ __forceinline__ void g_nearest_rotation(Grp& g, const double* M, int 
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = -R[i];
   }
-  MP_GSYNC();
+  MORB_ROW_SYNC();
 }
 
 // sum over the first six correspondences of 1 - normalize(R X + t) . f (the un-normalised bearing vector)
@@ -340,8 +265,8 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
     }
     g.W[l] = s;
   }
-  MP_GSYNC();
-  g_jacobi(g, 3, l);
+  MORB_ROW_SYNC();
+  g_jacobi(g.W, g.W + 144, g.red, 3, l);
   bool planar;
   {
     const double e0 = g.W[0], e1 = g.W[4], e2 = g.W[8];
@@ -365,7 +290,7 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
       }
     }
   }
-  MP_GSYNC();
+  MORB_ROW_SYNC();
   const int m = planar ? 9 : 12;
   // ---- A^T A: lane j sums column j over the correspondences in list order, row r then row s of each ----
   {
@@ -415,8 +340,8 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
         if (i < m) g.W[i * m + l] = acc[i];
     }
   }
-  MP_GSYNC();
-  g_jacobi(g, m, l);
+  MORB_ROW_SYNC();
+  g_jacobi(g.W, g.W + 144, g.red, m, l);
   {
     int kmin = 0;
     double best = fabs(g.W[0]);
@@ -426,7 +351,7 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
     }
     if (l < m) g.x[l] = g.W[144 + l * m + kmin];
   }
-  MP_GSYNC();
+  MORB_ROW_SYNC();
   double x[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) x[k] = g.x[k];
@@ -512,7 +437,7 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
         for (int a = 0; a < 12; ++a) w[a] = J[a];
         w[12] = r[0]; w[13] = r[1];
       }
-      MP_GSYNC();
+      MORB_ROW_SYNC();
       const int cnt = min(MP_GL, n - base);
       for (int kk = 0; kk < cnt; ++kk) {
         const double* w = g.W + kk * 14;
@@ -524,18 +449,18 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
             acc[u] += w[row * 6 + ia[u]] * b;
           }
       }
-      MP_GSYNC();
+      MORB_ROW_SYNC();
     }
 #pragma unroll
     for (int u = 0; u < 3; ++u)
       if (l + 16 * u < 42) g.W[l + 16 * u] = acc[u];
-    MP_GSYNC();
+    MORB_ROW_SYNC();
     double A[36], gv[6], dx[6];
 #pragma unroll
     for (int e = 0; e < 36; ++e) A[e] = g.W[e];
 #pragma unroll
     for (int e = 0; e < 6; ++e) gv[e] = g.W[36 + e];
-    MP_GSYNC();
+    MORB_ROW_SYNC();
     if (!ldlt6_solve(A, gv, dx)) break;
     double mx = 0, mn = 1e300;
 #pragma unroll
@@ -564,10 +489,10 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
       }
     }
     g.red[l] = dl;
-    MP_GSYNC();
+    MORB_ROW_SYNC();
     dl = 0;
     for (int j = 0; j < MP_GL; ++j) dl = dl < g.red[j] ? g.red[j] : dl;
-    MP_GSYNC();
+    MORB_ROW_SYNC();
 #pragma unroll
     for (int a = 0; a < 6; ++a) xs[a] -= dx[a];
     if (dl < 1e-5) break;
@@ -576,7 +501,7 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
   rodrigues2rot(xs, R);
   if (l < 9) g.R[l] = R[l];
   if (l < 3) g.t[l] = xs[3 + l];
-  MP_GSYNC();
+  MORB_ROW_SYNC();
 }
 
 struct Pose { double R[9], t[3]; };
@@ -605,9 +530,6 @@ __device__ __forceinline__ Pose load_pose(const Grp& g) {
 
 __device__ inline bool kept(uint8_t en) { return (en & 1) && !(en & 2) && !(en & 4); }
 
-__device__ __forceinline__ void identity16(float* T) {
-  for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
-}
 __device__ __forceinline__ void pose_to_tcw(const Pose& P, float* T) {   // Rcw / tcw converted to CV_32F inside an identity
   identity16(T);
   for (int r = 0; r < 3; ++r) {
@@ -628,14 +550,8 @@ __device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n,
   for (int base = 0; base < n; base += MP_NT) {
     const int i = base + t;
     const bool valid = i < n && kept(d_entry[pc + i]);
-    const unsigned long long bal = __ballot(valid);
-    const int below = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) sh.wcount[wv] = __popcll(bal);
-    __syncthreads();
-    int off = sh.nc;
-    for (int k = 0; k < wv; ++k) off += sh.wcount[k];
+    const int c = ordered_slot(valid, lane, wv, sh.wcount, &sh.nc);
     if (valid) {
-      const int c = off + below;
       const float u = d_uv[(pc + i) * 2], v = d_uv[(pc + i) * 2 + 1];
       float ray[3];
       cam_unproject(cam, u, v, ray);
@@ -646,13 +562,11 @@ __device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n,
       C.err[c] = morbpnp::mlpnp_max_error(d_sigma2[pc + i], prm.th2);
       C.id[c] = i;
     }
-    __syncthreads();
-    if (t == 0) { int tot = 0; for (int k = 0; k < MP_NW; ++k) tot += sh.wcount[k]; sh.nc += tot; }
-    __syncthreads();
+    ordered_commit<MP_NW>(sh.wcount, &sh.nc);
   }
   const int N = sh.N;
   const int minInl = morbpnp::mlpnp_min_inliers(N, prm.minInliers, prm.minSet, prm.epsilon);
-  const int budget = morbpnp::mlpnp_budget(N, minInl, morbpnp::mlpnp_epsilon(N, minInl, prm.epsilon), prm.probability, prm.maxIterations);
+  const int budget = ransac_budget(N, minInl, morbpnp::mlpnp_epsilon(N, minInl, prm.epsilon), prm.probability, prm.maxIterations);
   const int it0 = d_state[p].iterations;
   const int minSet = prm.minSet;
   if (t == 0) {
@@ -680,7 +594,7 @@ __device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n,
         const int* r = d_rand + (size_t)p * randCap + (size_t)minSet * (size_t)(b0 + gi);
         for (int i = 0; i < minSet; ++i) {
           const int size = N - i;
-          const int randi = morbpnp::mlpnp_random_int(r[i], size);
+          const int randi = random_int(r[i], size);
           int v = randi, bv = size - 1;
           for (int k = 0; k < i; ++k) {   // the latest substitution of a position wins
             if (g.pos[k] == randi) v = g.val[k];
@@ -690,7 +604,7 @@ __device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n,
           g.pos[i] = randi; g.val[i] = bv;
         }
       }
-      MP_GSYNC();
+      MORB_ROW_SYNC();
       g_compute_pose(g, C, g.idx, minSet, gl);
     }
     __syncthreads();
@@ -740,16 +654,9 @@ __device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n,
       for (int base = 0; base < N; base += MP_NT) {
         const int i = base + t;
         const bool valid = i < N && d_best[pc + C.id[i]] != 0;
-        const unsigned long long bal = __ballot(valid);
-        const int below = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) sh.wcount[wv] = __popcll(bal);
-        __syncthreads();
-        int off = sh.nList;
-        for (int k = 0; k < wv; ++k) off += sh.wcount[k];
-        if (valid) C.list[off + below] = i;
-        __syncthreads();
-        if (t == 0) { int tot = 0; for (int k = 0; k < MP_NW; ++k) tot += sh.wcount[k]; sh.nList += tot; }
-        __syncthreads();
+        const int c = ordered_slot(valid, lane, wv, sh.wcount, &sh.nList);
+        if (valid) C.list[c] = i;
+        ordered_commit<MP_NW>(sh.wcount, &sh.nList);
       }
       if (gi == 0) g_compute_pose(sh.grp[0], C, C.list, sh.nList, gl);
       if (t == 0) sh.nRef = 0;
@@ -811,7 +718,7 @@ __global__ __launch_bounds__(MP_NT) void k_mlpnp_solver(int cap, const morb_mlpn
                                                         uint8_t* __restrict__ d_inliers, int* __restrict__ d_hyp, int hypCap,
                                                         char* __restrict__ ws, size_t wsPitch) {
   __shared__ MpShared sh;
-  const int p = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int p = blockIdx.x, t = threadIdx.x;
   const morb_mlpnp_solver_params prm = d_params[p];
   const int n = min(max(prm.n, 0), cap);
   const size_t pc = (size_t)p * cap;
@@ -835,13 +742,7 @@ __global__ __launch_bounds__(MP_NT) void k_mlpnp_solver(int cap, const morb_mlpn
   }
   if (t == 0) { sh.N = 0; sh.nc = 0; }
   __syncthreads();
-  int cnt = 0;
-  for (int base = 0; base < n; base += MP_NT) {
-    const int i = base + t;
-    cnt += __popcll(__ballot(i < n && kept(d_entry[pc + i])));
-  }
-  if (lane == 0) atomicAdd(&sh.N, cnt);
-  __syncthreads();
+  block_count<MP_NT>(n, &sh.N, [=](int i) { return kept(d_entry[pc + i]); });
   // two inlined call sites: in the first the correspondence arrays are known to be LDS, so it addresses them with ds_* instructions
   if (sh.N <= MP_LDS_N)
     solve(sh, mp_carve(sh.corr, MP_LDS_N), p, n, cap, prm, cam, d_entry, d_uv, d_sigma2, d_Xw, nIterations, d_rand, randCap, d_state, d_best,
@@ -861,13 +762,10 @@ extern "C" int morb_mlpnp_solver_batch(morb_optimizer* o, int nprob, int cap, co
   MORB_REQUIRE(nprob > 0 && cap > 0 && randCap >= 0 && (d_rand || randCap == 0) && (d_hypInliers == nullptr || hypCap >= 0),
                MORB_ERR_INVALID, "bad sizes");
   MORB_ENTER(st, o, stream);
-  size_t pitch = 0;
-  char* ws = nullptr;
-  if (cap > MP_LDS_N) {   // only problems with more than MP_LDS_N correspondences use it
-    pitch = mp_bytes_per_problem(cap);
-    const int rc = morb::grow(o->mlpnpCorr, pitch * (size_t)nprob, &ws);
-    if (rc != MORB_OK) return rc;
-  }
+  size_t pitch;
+  char* ws;
+  const int rc = morb::grow_beyond_lds(o->mlpnpCorr, nprob, cap, MP_LDS_N, MP_W, &ws, &pitch);
+  if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_mlpnp_solver, dim3(nprob), dim3(MP_NT), 0, st, cap, d_params, d_entry, d_uv, d_sigma2, d_Xw, nIterations, d_rand,
                      randCap, d_state, d_bestInliers, d_inliers, d_hypInliers, hypCap, ws, pitch);
   MORB_HIP_CHECK(hipGetLastError());

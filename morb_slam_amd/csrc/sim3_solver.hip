@@ -1,9 +1,9 @@
 // Sim3Solver (reference src/Sim3Solver.cc) for MI355X (gfx950), batched: one 256-thread workgroup per problem (pKF1, pKF2,
 // vpMatched12, vpKeyFrameMatchedMP).  Each call restates, operation for operation in float:
-//   * the constructor (:34-120): the kept correspondences compacted in KF1 feature order (wave ballots), camera-frame points
-//     Rcw * Xw + tcw, FromCameraToImage of the MAP POINTS with each side's camera (Pinhole / KannalaBrandt8 project(Vector3f),
-//     glibc's atan2f / sinf / cosf via kb8.h), the truncated size_t thresholds 9.210 * sigma2;
-//   * SetRansacParameters (:122-146) from the device-side N (include/morb/sim3_solver_math.h);
+//   * the constructor (:34-120): the kept correspondences compacted in KF1 feature order (ransac_block.h), camera-frame points
+//     Rcw * Xw + tcw, FromCameraToImage of the MAP POINTS with each side's camera (Pinhole / KannalaBrandt8 project(Vector3f):
+//     cam_project of kb8.h, with glibc's atan2f / sinf / cosf), the truncated size_t thresholds 9.210 * sigma2;
+//   * SetRansacParameters (:122-146) from the device-side N (include/morb/sim3_solver_math.h, ransac_math.h);
 //   * iterate (:148-278) from state.iterations on: DUtils::Random::RandomInt + swap-with-back sampling on the caller's rand()
 //     values (three per iteration, indexed by the global iteration number), ComputeSim3 (:285-392), CheckInliers (:394-414),
 //     the running best with >= and the return at the first iteration with more than minInliers inliers.
@@ -22,6 +22,7 @@
 #include "libm_f32.h"
 #include "morb_hip.h"
 #include "morb/sim3_solver_math.h"
+#include "ransac_block.h"
 
 #ifndef MORB_SIM3_SOLVER_BATCH
 #define MORB_SIM3_SOLVER_BATCH 64
@@ -33,20 +34,14 @@ constexpr int SS_NT = 256;
 constexpr int SS_NW = SS_NT / 64;
 constexpr int SS_B = MORB_SIM3_SOLVER_BATCH;   // hypotheses built per batch (chosen by measurement)
 constexpr int SS_LDS_N = 1024;                 // correspondences held in LDS; beyond, the global workspace
+constexpr int SS_W = 13;                       // words per correspondence
 constexpr int SS_HW = 40;                      // floats per hypothesis: T12 [12] (sR row-major, t), T21 [12], R [9], t [3], s
 static_assert(SS_B % SS_NW == 0 && SS_B <= SS_NT, "batch");
 
-struct Cam { int kb8; morbkb8::KB8 k; };
+using morbkb8::Cam;
+using morbkb8::cam_project;
+using namespace morbransac;
 
-// Pinhole::project(Vector3f) (Pinhole.cpp:46-52), KannalaBrandt8::project(Vector3f) (KannalaBrandt8.cpp:68-86)
-__device__ __forceinline__ void cam_project(const Cam& c, const float* v, float* uv) {
-  if (!c.kb8) {
-    uv[0] = c.k.p[0] * v[0] / v[2] + c.k.p[2];
-    uv[1] = c.k.p[1] * v[1] / v[2] + c.k.p[3];
-    return;
-  }
-  morbkb8::kb8_project_f(c.k, v, uv);
-}
 // R * x + t, R row-major: Eigen's 3-term sums taken left to right
 __device__ __forceinline__ void affine(const float* R, const float* t, const float* x, float* o) {
 #pragma unroll
@@ -196,7 +191,6 @@ struct Corr {   // structure of arrays, `stride` entries each
   int* id;
   int stride;
 };
-__host__ __device__ inline size_t ss_bytes_per_problem(int cap) { return ((size_t)cap * 13 * 4 + 255) / 256 * 256; }
 __device__ inline Corr ss_carve(float* base, int stride) {
   Corr c;
   c.x1 = base; c.x2 = base + 3 * stride; c.p1 = base + 6 * stride; c.p2 = base + 8 * stride;
@@ -223,7 +217,7 @@ __device__ __forceinline__ bool is_inlier(const Corr& C, int i, const float* T12
 }
 
 struct SsShared {
-  float corr[SS_LDS_N * 13];
+  float corr[SS_LDS_N * SS_W];
   float hyp[SS_B][SS_HW];
   float best[SS_HW];
   int cnt[SS_B];
@@ -247,14 +241,8 @@ __device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n,
   for (int base = 0; base < n; base += SS_NT) {
     const int i = base + t;
     const bool valid = i < n && kept(d_entry[pc + i]);
-    const unsigned long long bal = __ballot(valid);
-    const int below = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) sh.wcount[wv] = __popcll(bal);
-    __syncthreads();
-    int off = sh.nc;
-    for (int k = 0; k < wv; ++k) off += sh.wcount[k];
+    const int c = ordered_slot(valid, lane, wv, sh.wcount, &sh.nc);
     if (valid) {
-      const int c = off + below;
       float X1[3], X2[3], uv[2];
       affine(prm.T1w, prm.T1w + 9, d_Xw1 + (pc + i) * 3, X1);
       affine(prm.T2w, prm.T2w + 9, d_Xw2 + (pc + i) * 3, X2);
@@ -268,9 +256,7 @@ __device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n,
       C.e2[c] = morbs3::sim3s_max_error(d_s2_2[pc + i]);
       C.id[c] = i;
     }
-    __syncthreads();
-    if (t == 0) { int tot = 0; for (int k = 0; k < SS_NW; ++k) tot += sh.wcount[k]; sh.nc += tot; }
-    __syncthreads();
+    ordered_commit<SS_NW>(sh.wcount, &sh.nc);
   }
   const int N = sh.N;
   const int budget = morbs3::sim3s_budget(N, prm.minInliers, prm.probability, prm.maxIterations);
@@ -285,7 +271,7 @@ __device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n,
     if (t == 0) {
       morb_sim3_solver_state& st = d_state[p];
       st.N = N; st.budget = budget; st.converged = 0; st.noMore = 1; st.nInliers = 0; st.convergedAt = -1;
-      for (int k = 0; k < 16; ++k) st.sim3[k] = (k % 5 == 0) ? 1.f : 0.f;
+      identity16(st.sim3);
     }
     return;
   }
@@ -298,9 +284,9 @@ __device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n,
     if (t < nb) {   // one lane per hypothesis: sampling (RandomInt + swap with back) and ComputeSim3
       const int g = b0 + t;
       const int* r = d_rand + (size_t)p * randCap + 3 * (size_t)g;
-      const int a1 = morbs3::sim3s_random_int(r[0], N);
-      const int a2 = morbs3::sim3s_random_int(r[1], N - 1);
-      const int a3 = morbs3::sim3s_random_int(r[2], N - 2);
+      const int a1 = random_int(r[0], N);
+      const int a2 = random_int(r[1], N - 1);
+      const int a3 = random_int(r[2], N - 2);
       const int last1 = (a1 == N - 2) ? N - 1 : N - 2;   // vAvailableIndices[N - 2] after the first removal
       const int idx[3] = {a1, (a2 == a1) ? N - 1 : a2, (a3 == a2) ? last1 : ((a3 == a1) ? N - 1 : a3)};
       float P1[3][3], P2[3][3];
@@ -385,7 +371,7 @@ __global__ __launch_bounds__(SS_NT) void k_sim3_solver(int cap, const morb_sim3_
                                                        uint8_t* __restrict__ d_inliers, int* __restrict__ d_hyp, int hypCap,
                                                        char* __restrict__ ws, size_t wsPitch) {
   __shared__ SsShared sh;
-  const int p = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int p = blockIdx.x, t = threadIdx.x;
   const morb_sim3_solver_params prm = d_params[p];
   const int n = min(max(prm.n, 0), cap);
   const size_t pc = (size_t)p * cap;
@@ -396,13 +382,7 @@ __global__ __launch_bounds__(SS_NT) void k_sim3_solver(int cap, const morb_sim3_
   for (int i = t; i < cap; i += SS_NT) d_inliers[pc + i] = 0;
   if (t == 0) { sh.N = 0; sh.nc = 0; }
   __syncthreads();
-  int cnt = 0;
-  for (int base = 0; base < n; base += SS_NT) {
-    const int i = base + t;
-    cnt += __popcll(__ballot(i < n && kept(d_entry[pc + i])));
-  }
-  if (lane == 0) atomicAdd(&sh.N, cnt);
-  __syncthreads();
+  block_count<SS_NT>(n, &sh.N, [=](int i) { return kept(d_entry[pc + i]); });
   // two inlined call sites: in the first the correspondence arrays are known to be LDS, so it addresses them with ds_* instructions
   if (sh.N <= SS_LDS_N)
     solve(sh, ss_carve(sh.corr, SS_LDS_N), p, n, cap, prm, c1, c2, d_entry, d_Xw1, d_Xw2, d_s2_1, d_s2_2, nIterations, d_rand, randCap,
@@ -423,13 +403,10 @@ extern "C" int morb_sim3_solver_batch(morb_optimizer* o, int nprob, int cap, con
   MORB_REQUIRE(nprob > 0 && cap > 0 && randCap >= 0 && (d_rand || randCap == 0) && (d_hypInliers == nullptr || hypCap >= 0),
                MORB_ERR_INVALID, "bad sizes");
   MORB_ENTER(st, o, stream);
-  size_t pitch = 0;
-  char* ws = nullptr;
-  if (cap > SS_LDS_N) {   // only problems with more than SS_LDS_N correspondences use it
-    pitch = ss_bytes_per_problem(cap);
-    const int rc = morb::grow(o->spill, pitch * (size_t)nprob, &ws);
-    if (rc != MORB_OK) return rc;
-  }
+  size_t pitch;
+  char* ws;
+  const int rc = morb::grow_beyond_lds(o->spill, nprob, cap, SS_LDS_N, SS_W, &ws, &pitch);
+  if (rc != MORB_OK) return rc;
   hipLaunchKernelGGL(k_sim3_solver, dim3(nprob), dim3(SS_NT), 0, st, cap, d_params, d_entry, d_Xw1, d_Xw2, d_sigma2_1, d_sigma2_2,
                      nIterations, d_rand, randCap, d_state, d_inliers, d_hypInliers, hypCap, ws, pitch);
   MORB_HIP_CHECK(hipGetLastError());

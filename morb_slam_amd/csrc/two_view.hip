@@ -1,14 +1,14 @@
 // TwoViewReconstruction (reference src/TwoViewReconstruction.cc, GeometricTools::Triangulate of src/GeometricTools.cc:48-72, called by
 // Pinhole::ReconstructWithTwoViews, src/CameraModels/Pinhole.cpp:85-98) for MI355X (gfx950), batched: one 256-thread workgroup per
 // problem (two frames of the keypoint pool and the vnMatches12 row morb_search_for_initialization_batch wrote).  Each problem restates
-//   * Reconstruct (:41-130): mvMatches12 compacted in frame-1 order (wave ballots), the sets of eight by DUtils::Random::RandomInt and
+//   * Reconstruct (:41-130): mvMatches12 compacted in frame-1 order (ransac_block.h), the sets of eight by DUtils::Random::RandomInt and
 //     swap-with-back on the caller's rand() values (include/morb/two_view_math.h), the choice by RH > 0.50;
 //   * Normalize (:723-768) over ALL keypoints of each frame, FindHomography / FindFundamental (:132-225), ComputeH21 / ComputeF21
 //     (:227-303), CheckHomography / CheckFundamental (:305-471), ReconstructF / DecomposeE (:473-560, :882-905), ReconstructH
 //     (:562-721), CheckRT (:770-880) and Triangulate, every float expression in the reference's order (-ffp-contract=off).
 // Mapping.  The matches (u1 v1 u2 v2, frame-1 index, flags, cosParallax: TV_W words) live in LDS up to TV_LDS_N, in the handle's
 // twoViewCorr workspace beyond.  Iterations run TV_ROUND at a time: a row of 16 lanes per iteration builds both hypotheses (A^T A in
-// FP64 in LDS, lane k owning row / column k of a Jacobi rotation), then one LANE per hypothesis walks all N matches and adds its score
+// FP64 in LDS, lane k owning row / column k of a Jacobi rotation: row_jacobi.h), then one LANE per hypothesis walks all N matches and adds its score
 // terms one after the other, so the float sum is the reference's sequential sum bit for bit (waves 0-1 score H, waves 2-3 F); the
 // running best is then taken in iteration order with the strict >.  The four sums of Normalize are chains as well: the workgroup
 // stages one keypoint per thread at a time in LDS and one lane per sum adds them in index order.  CheckRT runs one match per thread (the
@@ -37,6 +37,8 @@
 #include "libm_f32.h"
 #include "morb_hip.h"
 #include "morb/two_view_math.h"
+#include "ransac_block.h"
+#include "row_jacobi.h"
 
 #ifndef MORB_TWO_VIEW_THREADS
 #define MORB_TWO_VIEW_THREADS 256
@@ -45,10 +47,11 @@
 namespace {
 
 using namespace morbtv;
+using namespace morbransac;
 
 constexpr int TV_NT = MORB_TWO_VIEW_THREADS;
 constexpr int TV_NW = TV_NT / 64;
-constexpr int TV_GL = 16;               // lanes per hypothesis row
+constexpr int TV_GL = morbrow::ROW_LANES;   // lanes per hypothesis row
 constexpr int TV_G = TV_NT / TV_GL;     // rows
 constexpr int TV_ROUND = TV_NT / 2;     // iterations per round: one scoring lane per (iteration, model)
 constexpr int TV_LDS_N = 512;           // matches held in LDS; beyond, the global workspace
@@ -57,14 +60,11 @@ constexpr int TV_CHUNK = TV_NT;         // keypoints staged per step of Normaliz
 // 128 and 256 are the shapes built and measured; 512 would need 92 KB of LDS
 static_assert(TV_NT == 128 || TV_NT == 256, "two scoring halves of whole waves, TvShared within 64 KB");
 
-#define TV_GSYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-
 struct Corr {   // structure of arrays, `stride` entries each
   float *u1, *v1, *u2, *v2, *cs;
   int *i1, *fl;   // fl: bit 0 inlier of the chosen model, bit 1 counted by the current CheckRT
   int stride;
 };
-__host__ __device__ inline size_t tv_bytes_per_problem(int cap) { return ((size_t)cap * TV_W * 4 + 255) / 256 * 256; }
 __device__ inline Corr tv_carve(float* base, int stride) {
   Corr c;
   c.u1 = base; c.v1 = base + stride; c.u2 = base + 2 * stride; c.v2 = base + 3 * stride; c.cs = base + 4 * stride;
@@ -234,68 +234,10 @@ __device__ __forceinline__ void svd3(const float* M, float* U, float* w, float* 
   }
 }
 
-// ---- the 9 x 9 Jacobi of one 16-lane row (the arithmetic of jacobi_reg, lane k owning row / column k) --------------------------------
-__device__ __forceinline__ double g_colsum(Grp& g, const double* A, int m, int l, bool upper) {
-  double c = 0;
-  if (l < m) {
-    const int rows = upper ? l : m;
-    for (int i = 0; i < rows; ++i) c += A[i * m + l] * A[i * m + l];
-  }
-  g.red[l] = c;
-  TV_GSYNC();
-  double s = 0;
-  for (int j = 0; j < m; ++j) s += g.red[j];
-  TV_GSYNC();
-  return s;
-}
-__device__ __forceinline__ void g_jacobi9(Grp& g, int l) {
-  constexpr int m = 9;
-  double* A = g.W;
-  double* V = g.W + 81;
-  for (int e = l; e < m * m; e += TV_GL) V[e] = (e / m == e % m) ? 1.0 : 0.0;
-  TV_GSYNC();
-  const double fro = g_colsum(g, A, m, l, false);
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    const double off = g_colsum(g, A, m, l, true);
-    if (!(off > 1e-30 * fro)) break;
-    for (int p = 0; p < m - 1; ++p)
-      for (int q = p + 1; q < m; ++q) {
-        const double apq = A[p * m + q];
-        if (apq == 0.0) continue;
-        const double app = A[p * m + p], aqq = A[q * m + q];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        if (l < m) {
-          const int k = l;
-          double np_ = 0, nq = 0;
-          const bool mid = k != p && k != q;
-          if (mid) {
-            const double akp = A[k * m + p], akq = A[k * m + q];
-            np_ = c * akp - s * akq;
-            nq = s * akp + c * akq;
-          }
-          const double vkp = V[k * m + p], vkq = V[k * m + q];
-          if (mid) {
-            A[k * m + p] = np_; A[p * m + k] = np_;
-            A[k * m + q] = nq; A[q * m + k] = nq;
-          }
-          V[k * m + p] = c * vkp - s * vkq;
-          V[k * m + q] = s * vkp + c * vkq;
-          if (k == p) {
-            A[p * m + p] = app - t * apq;
-            A[q * m + q] = aqq + t * apq;
-            A[p * m + q] = 0.0;
-            A[q * m + p] = 0.0;
-          }
-        }
-        TV_GSYNC();
-      }
-  }
-}
+// ---- the 9 x 9 Jacobi of one 16-lane row (row_jacobi.h: the arithmetic of jacobi_reg, lane k owning row / column k) ------------------
 // the eigenvector of the first smallest |eigenvalue|, rounded to float; every lane of the row returns it
 __device__ __forceinline__ void g_null9(Grp& g, int l, float* x) {
-  g_jacobi9(g, l);
+  morbrow::g_jacobi(g.W, g.W + 81, g.red, 9, l);
   int kmin = 0;
   double best = fabs(g.W[0]);
   for (int k = 1; k < 9; ++k) {
@@ -304,7 +246,7 @@ __device__ __forceinline__ void g_null9(Grp& g, int l, float* x) {
   }
 #pragma unroll
   for (int k = 0; k < 9; ++k) x[k] = (float)g.W[81 + k * 9 + kmin];
-  TV_GSYNC();
+  MORB_ROW_SYNC();
 }
 // lane l (< 9) adds column l of A^T A: acc[i] += a[i] * a[l] for one row a of A
 __device__ __forceinline__ void ata_row(const float* a, int l, double* acc) {
@@ -333,7 +275,7 @@ __device__ __forceinline__ void g_hypotheses(Grp& g, int l, const float* T1, con
 #pragma unroll
     for (int i = 0; i < 9; ++i) g.W[i * 9 + l] = acc[i];
   }
-  TV_GSYNC();
+  MORB_ROW_SYNC();
   g_null9(g, l, x);
   mul33(T2inv, x, tmp);
   mul33(tmp, T1, out);
@@ -350,7 +292,7 @@ __device__ __forceinline__ void g_hypotheses(Grp& g, int l, const float* T1, con
 #pragma unroll
     for (int i = 0; i < 9; ++i) g.W[i * 9 + l] = acc[i];
   }
-  TV_GSYNC();
+  MORB_ROW_SYNC();
   g_null9(g, l, x);
   float U[9], w[3], V[9], Fn[9];
   svd3(x, U, w, V);
@@ -652,20 +594,12 @@ __device__ __forceinline__ void solve(TvShared& sh, const Corr& C, int p, const 
     int m = -1;
     if (i < n1) m = a.matches12[pc + i];
     const bool valid = m >= 0 && m < n2;
-    const unsigned long long bal = __ballot(valid);
-    const int below = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) sh.wcount[wv] = __popcll(bal);
-    __syncthreads();
-    int off = sh.nc;
-    for (int k = 0; k < wv; ++k) off += sh.wcount[k];
+    const int c = ordered_slot(valid, lane, wv, sh.wcount, &sh.nc);
     if (valid) {
-      const int c = off + below;
       C.u1[c] = k1[i].x; C.v1[c] = k1[i].y; C.u2[c] = k2[m].x; C.v2[c] = k2[m].y;
       C.i1[c] = i; C.fl[c] = 0;
     }
-    __syncthreads();
-    if (t == 0) { int tot = 0; for (int k = 0; k < TV_NW; ++k) tot += sh.wcount[k]; sh.nc += tot; }
-    __syncthreads();
+    ordered_commit<TV_NW>(sh.wcount, &sh.nc);
   }
   // ---- Normalize (:723-768): the four sums of each pass are chains over all keypoints in index order ----
   for (int pass = 0; pass < 2; ++pass) {
@@ -728,7 +662,7 @@ __device__ __forceinline__ void solve(TvShared& sh, const Corr& C, int p, const 
             g.pn[j * 4 + 2] = (C.u2[c] - mX2) * sX2; g.pn[j * 4 + 3] = (C.v2[c] - mY2) * sY2;
           }
         }
-        TV_GSYNC();
+        MORB_ROW_SYNC();
         float out[27];
         g_hypotheses(g, gl, T1, T2inv, T2t, out);
         if (gl == 0) {
@@ -879,7 +813,7 @@ __global__ __launch_bounds__(TV_NT) void k_two_view(Args a, char* __restrict__ w
   if (t < 12) a.T21[(size_t)p * 12 + t] = 0.f;
   if (t == 0) { sh.N = 0; sh.nc = 0; }
   __syncthreads();
-  int cnt = 0;
+  int cnt = 0;   // (block_count of ransac_block.h, written out: the test of m sits outside the guard of the load here)
   for (int base = 0; base < n1; base += TV_NT) {
     const int i = base + t;
     int m = -1;
@@ -913,13 +847,10 @@ extern "C" int morb_two_view_reconstruction_batch(morb_optimizer* o, int nprob, 
   MORB_REQUIRE(maxIterations >= 1, MORB_ERR_INVALID, "maxIterations < 1");
   MORB_REQUIRE((long long)randCap >= 8ll * (long long)maxIterations, MORB_ERR_INVALID, "randCap < 8 * maxIterations");
   MORB_ENTER(st, o, stream);
-  size_t pitch = 0;
-  char* ws = nullptr;
-  if (cap > TV_LDS_N) {   // only problems with more than TV_LDS_N matches use it
-    pitch = tv_bytes_per_problem(cap);
-    const int rc = morb::grow(o->twoViewCorr, pitch * (size_t)nprob, &ws);
-    if (rc != MORB_OK) return rc;
-  }
+  size_t pitch;
+  char* ws;
+  const int rc = morb::grow_beyond_lds(o->twoViewCorr, nprob, cap, TV_LDS_N, TV_W, &ws, &pitch);
+  if (rc != MORB_OK) return rc;
   Args a;
   a.cap = cap; a.maxIterations = maxIterations; a.randCap = randCap;
   a.img1 = d_img1; a.img2 = d_img2; a.count = d_count; a.matches12 = d_matches12; a.rnd = d_rand;

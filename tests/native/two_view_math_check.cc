@@ -1,7 +1,8 @@
-// Stand-alone host check of include/morb/two_view_math.h (its own main; tests/test_two_view_cpu.py builds it with
-// -fsanitize=address,undefined and runs it): tv_sample8 against the reference's vector form (:83-94) over many sizes and rand() values,
-// tv_random_int against DUtils::Random::RandomInt's double expression, tv_min_good, tv_parallax_deg, and the two enums, which it
-// prints by name for the test to compare with the Python front's tuples.
+// Stand-alone host check of include/morb/two_view_math.h and, through tv_sample8, of ransac_math.h's random_int (its own main;
+// tests/test_two_view_cpu.py builds it with -fsanitize=address,undefined and runs it): tv_sample8 against the reference's vector form
+// (:83-94, with DUtils::Random::RandomInt's double expression) over many sizes and rand() values, tv_min_good, tv_parallax_deg, and the
+// two enums, which it prints by name for the test to compare with the Python front's tuples.  (random_int alone against that
+// expression, over these sizes and rand() values too: test_random_int_matches_dutils of tests/test_sim3_solver_cpu.py.)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +26,6 @@ int main() {
       for (int j = 0; j < TV_SET; ++j) {
         const int d = (int)avail.size();
         const int randi = int(((double)r[j] / ((double)2147483647 + 1.0)) * d);
-        if (randi != tv_random_int(r[j], d)) { if (bad++ < 5) printf("random_int(%d, %d)\n", r[j], d); }
         if ((int)avail[randi] != idx[j]) { if (bad++ < 5) printf("sample N %d rep %d j %d: %d != %d\n", N, rep, j, idx[j], (int)avail[randi]); }
         avail[randi] = avail.back();
         avail.pop_back();

@@ -139,9 +139,34 @@ def test_budget_does_not_hang_on_the_last_bits_of_log_and_pow(ssm):
             assert abs(x - 2.0 ** 31) > 1e-5 * x, (N, m, x)
 
 
+def _two_view_sampling_pairs():
+    """The (rand() value, size) pairs of tests/native/two_view_math_check.cc: its sizes, its xorshift stream, eight draws per set."""
+    s, N, pairs = 88172645463325252, 8, []
+    while N <= 2000:
+        for rep in range(200):
+            for j in range(8):
+                if rep < 2:
+                    r = 0 if rep == 0 else 2 ** 31 - 1
+                else:
+                    s ^= (s << 13) & (2 ** 64 - 1)
+                    s ^= s >> 7
+                    s ^= (s << 17) & (2 ** 64 - 1)
+                    r = s >> 33
+                pairs.append((r, N - j))
+        N = N + 1 if N < 40 else N * 3 // 2
+    return pairs
+
+
 def test_random_int_matches_dutils(ssm):
+    """morbransac::random_int (include/morb/ransac_math.h), the one RandomInt of the three solvers, against the reference's double
+    expression: the inputs each solver's own check used (Sim3Solver's, MLPnPsolver's, the sampling sets of TwoViewReconstruction)."""
     rng = np.random.default_rng(0)
-    for r, d in list(zip(rng.integers(0, 2 ** 31, 20000), rng.integers(1, 8193, 20000))) + [(2 ** 31 - 1, 8192), (0, 1), (2 ** 31 - 1, 1)]:
+    pairs = list(zip(rng.integers(0, 2 ** 31, 20000), rng.integers(1, 8193, 20000))) + [(2 ** 31 - 1, 8192), (0, 1), (2 ** 31 - 1, 1)]
+    rng = np.random.default_rng(0)
+    pairs += list(zip(rng.integers(0, 2 ** 31, 5000), rng.integers(1, 4097, 5000))) + [(2 ** 31 - 1, 4096), (0, 1)]
+    pairs += _two_view_sampling_pairs()
+    assert len(pairs) > 90000
+    for r, d in pairs:
         assert ssm.ssm_random_int(int(r), int(d)) == int((float(r) / (2147483647 + 1.0)) * int(d))
 
 
