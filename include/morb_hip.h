@@ -220,6 +220,44 @@ int morb_bow_vector_batch(morb_matcher*, int nimg, const int* d_leaf, const int*
                           const double* d_nodeWeight, int weighting, int scoring, int* d_bowWord, double* d_bowValue, int* d_bowCount,
                           void* stream);
 
+/* void KeyFrameDatabase::DetectNBestCandidates(KeyFrame* pKF, vector<KeyFrame*>& vpLoopCand, vector<KeyFrame*>& vpMergeCand,
+ * int nNumCandidates) (src/KeyFrameDatabase.cc:579-705; the call of LoopClosing.cc:484) for nq queries at once, with DBoW2's L1
+ * score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  Only the L1 score is built, so there is no scoring argument: it is
+ * ORBvoc.txt's and the only one the reference runs.  No inverted file is kept (add / erase / clear / clearMap, :37-93, become d_dbRank).
+ *   pool      d_bowWord / d_bowValue [nimg][cap], d_bowCount [nimg]: exactly what morb_bow_vector_batch writes.
+ *   d_qImg    [nq] pool row of each query (pKF->mBowVec is a pool row too); the query's map is d_mapId[d_qImg[q]].
+ *   d_dbRank  [nimg] the keyframe's position in `add` order (unique among the rows that have one), negative = not in the database.
+ *   d_connStart [nq + 1], d_conn: CSR of pKF->GetConnectedKeyFrames() per query, as pool rows.
+ *   d_covis   [nimg][ncovis] GetBestCovisibilityKeyFrames(10) of each row, in its order, as pool rows, padded with -1.
+ *   d_mapId   [nimg] the map of each row; d_flags [nimg]: bit 0 = isBad(), bit 1 = GetMap()->IsBad().
+ *   d_prevScore [nimg] mPlaceRecognitionScore on entry, NULL = zeros; it must not be d_score.  EVERY query of the batch sees this
+ *             entry state: a batch of one equals the reference call, a batch of n equals n independent calls on that state.
+ * A keyframe is "stamped" by a query when it is in the database, shares a word with it and is not connected to it.  The entry takes
+ * as given that a query id (pKF->mnId) never equals a stamp an earlier query left, nor the initial 0: ids are unique per query and
+ * nonzero wherever the reference calls this.
+ * Outputs: d_loopCand / d_mergeCand [nq][nNumCandidates] pool rows padded with -1, d_nLoop / d_nMerge [nq]; d_words [nq][nimg] =
+ * mnPlaceRecognitionWords of a stamped keyframe, -1 otherwise; d_score [nq][nimg] = mPlaceRecognitionScore after the query (a
+ * stamped keyframe that was not scored keeps d_prevScore's).  d_words and d_score may be NULL.  The candidate rows can be passed on
+ * the device as d_kf2Img of morb_search_by_bow_kfkf_batch.  MORB_ERR_INVALID for a negative size, cap < 1, ncovis < 0 or
+ * nNumCandidates < 1; nq == 0 or nimg == 0 is MORB_OK with nothing written. */
+int morb_detect_n_best_candidates_batch(morb_matcher*, int nq, const int* d_qImg, int nimg, int cap, const int* d_bowWord,
+                                        const double* d_bowValue, const int* d_bowCount, const int* d_dbRank, const int* d_connStart,
+                                        const int* d_conn, const int* d_covis, int ncovis, const int* d_mapId, const uint8_t* d_flags,
+                                        const float* d_prevScore, int nNumCandidates, int* d_loopCand, int* d_nLoop, int* d_mergeCand,
+                                        int* d_nMerge, int* d_words, float* d_score, void* stream);
+
+/* vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame* F, Map* pMap) (src/KeyFrameDatabase.cc:707-814; the call
+ * of Tracking.cc:3369) for nq queries: as above with no connected set, d_qMap [nq] = pMap (a frame has no identity as a keyframe of
+ * the pool), no sort, the entries with accScore > 0.75f * bestAccScore whose best keyframe lies in d_qMap[q], first occurrences, in
+ * accumulation order.  d_cand [nq][nimg] pool rows padded with -1 (usable as d_kfImg of morb_search_by_bow_batch), d_nCand [nq];
+ * d_words / d_score = mnRelocWords / mRelocScore (the reference's constructor leaves mRelocScore uninitialised: 0 here).  L1 only.
+ * The same assumption on the query id (F->mnId against mnRelocQuery) and the same error codes. */
+int morb_detect_relocalization_candidates_batch(morb_matcher*, int nq, const int* d_qImg, const int* d_qMap, int nimg, int cap,
+                                                const int* d_bowWord, const double* d_bowValue, const int* d_bowCount,
+                                                const int* d_dbRank, const int* d_covis, int ncovis, const int* d_mapId,
+                                                const float* d_prevScore, int* d_cand, int* d_nCand, int* d_words, float* d_score,
+                                                void* stream);
+
 /* int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)
  * ORBmatcher.h:68, ORBmatcher.cc:218-395 (non-fisheye branch) for npairs (keyframe, frame) pairs drawn from a
  * pool of nimg images: pair p matches image d_kfImg[p] (as pKF) against image d_fImg[p] (as F).

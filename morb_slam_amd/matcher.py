@@ -106,6 +106,50 @@ class ORBmatcher:
                                             int(scoring), ptr(out[0]), ptr(out[1]), ptr(out[2]), self._st(stream)))
         return out
 
+    def DetectNBestCandidates(self, q_img, bow, db_rank, conn_start, conn, covis, map_id, flags, nNumCandidates, prev_score=None,
+                              out=None, stream=None):
+        """KeyFrameDatabase::DetectNBestCandidates (morb_detect_n_best_candidates_batch) for the query keyframes q_img i32 [nq] (pool
+        rows).  bow = bow_vector's (word, value, count); db_rank i32 [nimg] (add order, negative = not in the database); conn_start
+        i32 [nq + 1] / conn i32: CSR of the queries' connected keyframes; covis i32 [nimg, ncovis] (-1 padded); map_id i32 [nimg]; flags
+        u8 [nimg] (bit 0 isBad, bit 1 the map is bad); prev_score f32 [nimg] or None (zeros): the stored scores every query of the batch
+        starts from.  L1 score only.  Returns (loop i32 [nq, nNumCandidates], nLoop i32 [nq], merge, nMerge, words i32 [nq, nimg],
+        score f32 [nq, nimg]): pool rows padded with -1; words = -1 where the keyframe is not stamped by the query.  out = the same
+        six tensors to write into."""
+        import torch
+        word, value, count = bow
+        nq, (nimg, cap) = int(q_img.shape[0]), word.shape
+        ncovis = int(covis.shape[1]) if covis is not None else 0
+        N = int(nNumCandidates)
+        assert value.dtype == torch.float64 and flags.dtype == torch.uint8
+        if out is None:
+            dev, i32 = word.device, torch.int32
+            out = (torch.empty((nq, max(N, 0)), dtype=i32, device=dev), torch.empty((nq,), dtype=i32, device=dev),
+                   torch.empty((nq, max(N, 0)), dtype=i32, device=dev), torch.empty((nq,), dtype=i32, device=dev),
+                   torch.empty((nq, nimg), dtype=i32, device=dev), torch.empty((nq, nimg), dtype=torch.float32, device=dev))
+        check(self._L.morb_detect_n_best_candidates_batch(self._h, nq, ptr(q_img), nimg, cap, ptr(word), ptr(value), ptr(count), ptr(db_rank),
+                                                          ptr(conn_start), ptr(conn), ptr(covis), ncovis, ptr(map_id), ptr(flags),
+                                                          ptr(prev_score), N, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]),
+                                                          ptr(out[4]), ptr(out[5]), self._st(stream)))
+        return out
+
+    def DetectRelocalizationCandidates(self, q_img, q_map, bow, db_rank, covis, map_id, prev_score=None, out=None, stream=None):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (morb_detect_relocalization_candidates_batch) for the frames whose BoW
+        vectors are pool rows q_img i32 [nq], searched in the maps q_map i32 [nq].  The other arguments as DetectNBestCandidates.
+        Returns (cand i32 [nq, nimg] pool rows padded with -1, nCand i32 [nq], words i32 [nq, nimg], score f32 [nq, nimg])."""
+        import torch
+        word, value, count = bow
+        nq, (nimg, cap) = int(q_img.shape[0]), word.shape
+        ncovis = int(covis.shape[1]) if covis is not None else 0
+        assert value.dtype == torch.float64
+        if out is None:
+            dev, i32 = word.device, torch.int32
+            out = (torch.empty((nq, nimg), dtype=i32, device=dev), torch.empty((nq,), dtype=i32, device=dev),
+                   torch.empty((nq, nimg), dtype=i32, device=dev), torch.empty((nq, nimg), dtype=torch.float32, device=dev))
+        check(self._L.morb_detect_relocalization_candidates_batch(self._h, nq, ptr(q_img), ptr(q_map), nimg, cap, ptr(word), ptr(value),
+                                                                  ptr(count), ptr(db_rank), ptr(covis), ncovis, ptr(map_id), ptr(prev_score),
+                                                                  ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), self._st(stream)))
+        return out
+
     def bow_transform_tree(self, desc, count, voc_desc, voc_first, voc_nchild, L, levelsup=4, stream=None):
         """DBoW2 transform on a trained (possibly incomplete) tree: children of n = [first[n], first[n] + nchild[n])."""
         import torch

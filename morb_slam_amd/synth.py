@@ -883,3 +883,93 @@ def pack_two_view_problems(probs, device, rand=None, cap=None):
             a[k, :len(r)] = r
         t["rand"] = torch.from_numpy(a).to(device)
     return t
+
+
+def make_keyframe_database_scene(seed=0, nKF=70, nwords_voc=1000, words_per_kf=(20, 100), nmaps=2, cap=None, ncovis=10, nplaces=None,
+                                 place_frac=0.85, place_words=None, dup_groups=0, dup_size=3, erased_frac=0.1, disjoint=2, bad_frac=0.08, bad_maps=(),
+                                 nconn=4):
+    """A keyframe database for KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates: nKF pool rows whose BoW
+    vectors are L1-normalised TF-IDF-like doubles over a vocabulary of nwords_voc words, words ascending, as morb_bow_vector_batch
+    leaves them.  The trajectory visits each of nplaces places twice (keyframe i is at place (2 i nplaces // nKF) % nplaces), the maps
+    split it into nmaps consecutive parts; a place owns a pool of place_words (default hi) words, and a keyframe draws place_frac of its words_per_kf =
+    (lo, hi) words from it and the rest from the whole vocabulary, so keyframes of one place share many words and all share a few.  Knobs: dup_groups groups of dup_size keyframes with IDENTICAL vectors (exact score ties), erased_frac of the
+    rows outside the database (db_rank < 0), `disjoint` keyframes on words of their own that nobody else has (the top of the
+    vocabulary is reserved for them), bad_frac bad keyframes, bad_maps = the maps that are bad.
+    Returns a dict: word i32 [nKF, cap], value f64 [nKF, cap], count i32 [nKF], db_rank i32 [nKF] (a shuffled add order with holes),
+    covis i32 [nKF, ncovis] (-1 padded, rows of every length from 0, neighbours by decreasing shared place), connected (a list of i32
+    arrays: each keyframe's GetConnectedKeyFrames()), map_id i32 [nKF], flags u8 [nKF] (bit 0 bad, bit 1 the map is bad), and
+    nwords_voc, nmaps, cap, ncovis."""
+    rng = np.random.default_rng(seed)
+    lo, hi = words_per_kf
+    cap = cap or hi
+    nplaces = nplaces or max(nKF // 16, 1)
+    reserve = disjoint * hi
+    common = nwords_voc - reserve
+    assert common >= hi and cap >= hi
+    idf = rng.uniform(0.5, 9.0, nwords_voc)
+    place_pool = [rng.choice(common, size=min(common, place_words or hi), replace=False) for _ in range(nplaces)]
+    word = np.zeros((nKF, cap), np.int32)
+    value = np.zeros((nKF, cap), np.float64)
+    count = np.zeros(nKF, np.int32)
+    place = (np.arange(nKF) * 2 * nplaces // max(nKF, 1)) % nplaces     # every place is visited twice: loops, and merges across maps
+    lonely = set(rng.choice(nKF, size=min(disjoint, nKF), replace=False).tolist())
+    for i in range(nKF):
+        n = int(rng.integers(lo, hi + 1))
+        if i in lonely:
+            k = sorted(lonely).index(i)
+            w = common + k * hi + rng.choice(hi, size=n, replace=False)
+        else:
+            pool = place_pool[place[i]]
+            n_place = min(int(round(place_frac * n)), len(pool))
+            chosen = rng.choice(pool, size=n_place, replace=False)
+            extra = rng.integers(0, common, 2 * (n - n_place) + 8)
+            extra = extra[~np.isin(extra, chosen)]
+            extra = extra[np.sort(np.unique(extra, return_index=True)[1])][:n - n_place]
+            w = np.concatenate([chosen, extra]).astype(np.int64)
+            n = len(w)
+        w = np.sort(w)
+        tf = rng.integers(1, 5, n).astype(np.float64)
+        v = tf * idf[w]
+        v = v / np.abs(v).sum()
+        word[i, :n], value[i, :n], count[i] = w, v, n
+    for g in range(dup_groups):     # identical vectors: the members of a group tie exactly, on any query
+        members = [m for m in rng.choice(nKF, size=min(dup_size, nKF), replace=False).tolist() if m not in lonely]
+        for m in members[1:]:
+            word[m], value[m], count[m] = word[members[0]], value[members[0]], count[members[0]]
+    in_db = np.ones(nKF, bool)
+    in_db[rng.choice(nKF, size=min(int(np.ceil(erased_frac * nKF)), nKF), replace=False)] = False
+    order = rng.permutation(nKF)
+    db_rank = np.full(nKF, -1, np.int32)
+    db_rank[order] = np.arange(nKF, dtype=np.int32)
+    db_rank[~in_db] = -1
+    map_id = (np.arange(nKF) * nmaps // max(nKF, 1)).astype(np.int32)
+    flags = np.zeros(nKF, np.uint8)
+    flags[rng.choice(nKF, size=min(int(np.ceil(bad_frac * nKF)), nKF), replace=False)] = 1
+    for mp in bad_maps:
+        flags[map_id == mp] |= 2
+    covis = np.full((nKF, max(ncovis, 1)), -1, np.int32)[:, :ncovis]
+    connected = []
+    for i in range(nKF):
+        near = [j for d in range(1, 2 * ncovis + nconn + 2) for j in (i - d, i + d) if 0 <= j < nKF]   # by index distance
+        ncv = int(rng.integers(0, ncovis + 1)) if ncovis else 0
+        pick = near[:max(2 * ncv, 1)]
+        rng.shuffle(pick)
+        if ncv and pick and rng.random() < 0.3:                       # now and then a far neighbour: the best keyframe of another map
+            pick[0] = int(rng.integers(0, nKF))
+            if pick[0] == i:
+                pick[0] = (i + 1) % nKF
+        row = list(dict.fromkeys(pick))[:ncv]
+        covis[i, :len(row)] = row
+        connected.append(np.array(sorted(set(near[:int(rng.integers(0, nconn + 1))])), np.int32))
+    return dict(word=word, value=value, count=count, db_rank=db_rank, covis=np.ascontiguousarray(covis), connected=connected, map_id=map_id,
+                flags=flags, nwords_voc=nwords_voc, nmaps=nmaps, cap=cap, ncovis=ncovis)
+
+
+def keyframe_database_connected_csr(scene, queries):
+    """The CSR (conn_start i32 [nq + 1], conn i32) of the connected sets of the query keyframes `queries` of a
+    make_keyframe_database_scene dict, as morb_detect_n_best_candidates_batch reads them."""
+    sets = [scene["connected"][int(q)] for q in queries]
+    start = np.zeros(len(sets) + 1, np.int32)
+    start[1:] = np.cumsum([len(s) for s in sets])
+    conn = np.concatenate(sets).astype(np.int32) if sets and start[-1] else np.zeros(0, np.int32)
+    return start, conn
