@@ -1142,7 +1142,7 @@ struct IbaDev {
   const int2* sBlocks;
   const int* sBlkIndex;
   int sMp, sNb, sNblk, sNsplit;
-  // device-side LM control (see optimizer.hip, grid-mode LocalBA): the loop state, its mirror in mapped host memory, the backups
+  // device-side LM control (see local_ba.hip, grid mode): the loop state, its mirror in mapped host memory, the backups
   double* lmd;                                  // IBA_LMD_*: currentChi, lambda, ni, iniChi, chi2 of the last evaluated trial
   int* lmi;                                     // IBA_LM_*
   int* lmHost;                                  // [0] decided trials, [1] done
@@ -2086,7 +2086,7 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   double chi = 0;
   if (!errors(&chi)) return fail("k_iba_errors failed");
   const float err0 = (float)chi;
-  // ---- Levenberg-Marquardt with the control flow on the device (as grid-mode LocalBA, optimizer.hip): one slot = one trial; the host queues
+  // ---- Levenberg-Marquardt with the control flow on the device (as grid-mode LocalBA, local_ba.hip): one slot = one trial; the host queues
   // slots one ahead of the decisions and stops when the mapped `done` word appears; kernels queued behind the last decision return at once
   int trials = 0, outer = 0;
   {

@@ -1,0 +1,1417 @@
+// Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:1053-1441) for MI355X (gfx950), device-resident: g2o's
+// OptimizationAlgorithmLevenberg (Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-194) over
+// BlockSolver_6_3 (core/block_solver.hpp:354-590) with the reference's edges (src/OptimizableTypes.cpp,
+// g2o/types/types_six_dof_expmap.cpp), on the handle of optimizer.hip and the device helpers of optimizer_device.h, in two modes:
+//   * Grid mode (default): one launch per LM phase over the whole chip.  Hpp blocks per keyframe by a
+//     wave per 64-edge chunk, Hll per map point by a thread; the Schur complement of the landmarks is ONE dense FP64 product
+//     WD^T W on the matrix cores (schur_mfma.h: v_mfma_f64_16x16x4_f64, split-K with fixed-order partial sums); the reduced
+//     camera system is factorised in LDS (dense_ldlt.h); back-substitution per map point.  The LM control flow
+//     (optimization_algorithm_levenberg.cpp:61-169: rho, lambda schedule, <= 10 trials, the ORB-SLAM stop rule) runs ON THE
+//     DEVICE in a one-workgroup decision kernel; every phase kernel reads the LM state and returns at once when the solve
+//     is finished or the phase is not due, so the host only keeps the queue one trial ahead and watches a mapped flag.
+//   * Persistent mode: one 1024-thread workgroup runs the whole loop (many small problems side by side).
+// All arithmetic is FP64 like g2o; the reference's float leaks (float camera parameters, `const float invz` in
+// the stereo projection, float Huber deltas, float chi2 tests) are reproduced.
+#include <hip/hip_runtime.h>
+
+#include <sched.h>
+#include <time.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "common.h"
+#include "internal_abi.h"
+#include "dense_ldlt.h"
+#include "schur_mfma.h"
+#include "wave.h"
+#include "optimizer_device.h"
+
+using namespace morb;
+
+namespace {
+
+// point Jacobian (d x 3)
+__device__ __forceinline__ void jac_point(const Cam& cam, bool stereo, const double* xc, const double* R, double* Jl) {
+  const double x = xc[0], y = xc[1], z = xc[2];
+  const double fx = cam.fx, fy = cam.fy, bf = cam.bf;
+  if (!stereo) {  // -projectJac * R
+    const double a = fx / z, b = -fx * x / (z * z), c = fy / z, d = -fy * y / (z * z);
+    for (int k = 0; k < 3; ++k) { Jl[k] = -(a * R[k] + b * R[6 + k]); Jl[3 + k] = -(c * R[3 + k] + d * R[6 + k]); Jl[6 + k] = 0; }
+  } else {
+    const double z_2 = z * z;
+    for (int k = 0; k < 3; ++k) {
+      Jl[k] = -fx * R[k] / z + fx * x * R[6 + k] / z_2;
+      Jl[3 + k] = -fy * R[3 + k] / z + fy * y * R[6 + k] / z_2;
+      Jl[6 + k] = Jl[k] - bf * R[6 + k] / z_2;
+    }
+  }
+}
+
+// ---- binary edges of LocalBundleAdjustment, pinhole or fisheye rig ---------------------------------------------
+// obs[2] >= 0: EdgeStereoSE3ProjectXYZ; -1: EdgeSE3ProjectXYZ with the pinhole camera; -2: EdgeSE3ProjectXYZ with the
+// left KB8 camera; -3: EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl).  (Optimizer.cc:1244-1351)
+__device__ __forceinline__ bool edge_is_kb8(const Rig* rig, const float* o) { return rig != nullptr && o[2] < -1.5f; }
+__device__ __forceinline__ double ba_edge_error(const Cam& cam, const Rig* rig, bool st, const double* xc, const float* o,
+                                                double info, double* err) {
+  if (!edge_is_kb8(rig, o)) return edge_error(cam, st, xc, o, info, err);
+  double uv[2];
+  if (o[2] > -2.5f) kb8_project_d(rig->kbL, xc, uv);
+  else { double xr[3]; se3_map(rig->Trl, xc, xr); kb8_project_d(rig->kbR, xr, uv); }   // (mTrl * T).map(Xw) = mTrl.map(T.map(Xw))
+  err[0] = (double)o[0] - uv[0]; err[1] = (double)o[1] - uv[1]; err[2] = 0;
+  return err[0] * (info * err[0]) + err[1] * (info * err[1]);
+}
+// Jp (d x 6) and / or Jl (d x 3); R = rotation of the keyframe pose.  OptimizableTypes.cpp:134-156 / :185-208
+// RIG = false: the problem has no fisheye rig.  The KannalaBrandt8 branch (its float libm, the right camera's extrinsics) otherwise costs
+// the pinhole build kernel 100 VGPRs (220 instead of 119) and puts the pose Jacobian into scratch memory — for a branch it never takes.
+template <bool RIG>
+__device__ __forceinline__ void ba_edge_jac(const Cam& cam, const Rig* rig, bool st, const double* xc, const float* o,
+                                            const double* R, double* Jp, double* Jl) {
+  // RIG = true: EVERY edge of the problem is a KannalaBrandt8 edge (morb_ba_problem_create_fisheye writes obs[2] = -2 / -3 for all of them),
+  // so the choice is made at compile time: with a run-time `edge_is_kb8` both branches wrote Jp and the array went to scratch memory (160 B)
+  if (!RIG) {
+    if (Jp) jac_pose(cam, st, false, xc, Jp);
+    if (Jl) jac_point(cam, st, xc, R, Jl);
+    return;
+  }
+  const double x = xc[0], y = xc[1], z = xc[2];
+  double pj[6], pjM[6];
+  if (o[2] > -2.5f) {
+    kb8_project_jac(rig->kbL, xc, pj);
+    _Pragma("unroll") for (int k = 0; k < 6; ++k) pjM[k] = pj[k];
+  } else {
+    double xr[3], M[9];
+    se3_map(rig->Trl, xc, xr);
+    kb8_project_jac(rig->kbR, xr, pj);
+    q_to_R(rig->Trl.q, M);
+    _Pragma("unroll") for (int r = 0; r < 2; ++r)
+      _Pragma("unroll") for (int c = 0; c < 3; ++c) pjM[r * 3 + c] = pj[r * 3] * M[c] + pj[r * 3 + 1] * M[3 + c] + pj[r * 3 + 2] * M[6 + c];
+  }
+  _Pragma("unroll") for (int r = 0; r < 2; ++r) {
+    const double a = pjM[r * 3], b = pjM[r * 3 + 1], c = pjM[r * 3 + 2];
+    if (Jp) {
+      Jp[r * 6 + 0] = -(b * -z + c * y); Jp[r * 6 + 1] = -(a * z + c * -x); Jp[r * 6 + 2] = -(a * -y + b * x);
+      Jp[r * 6 + 3] = -a; Jp[r * 6 + 4] = -b; Jp[r * 6 + 5] = -c;
+    }
+    if (Jl) _Pragma("unroll") for (int k = 0; k < 3; ++k) Jl[r * 3 + k] = -(a * R[k] + b * R[3 + k] + c * R[6 + k]);
+  }
+  if (Jp) _Pragma("unroll") for (int k = 12; k < 18; ++k) Jp[k] = 0;
+  if (Jl) _Pragma("unroll") for (int k = 6; k < 9; ++k) Jl[k] = 0;
+}
+// isDepthPositive (OptimizableTypes.h:117-123 / :152-158)
+__device__ __forceinline__ bool ba_depth_positive(const Rig* rig, const float* o, const double* xc) {
+  if (edge_is_kb8(rig, o) && !(o[2] > -2.5f)) { double xr[3]; se3_map(rig->Trl, xc, xr); return xr[2] > 0.0; }
+  return xc[2] > 0.0;
+}
+
+// =====================================================================================================
+// LocalBundleAdjustment: one 1024-thread workgroup per problem
+// =====================================================================================================
+struct BaDev {
+  int nKF, nMP, nE, nFree, P;           // P = 6 * nFree
+  const int* kfCol;                     // [nKF] column of a free keyframe, -1 if fixed
+  const int *eKF, *eMP;                 // [nE]
+  const float *eObs, *eInfo;            // [nE][3], [nE]
+  const int *mpStart, *mpEdges;         // CSR by map point
+  const int *kfStart, *kfEdges;         // CSR by keyframe
+  int nPairs;                           // upper-triangular block pairs (i1 <= i2) of the reduced system that occur
+  const int *pairBlock;                 // [nPairs] i1 * nFree + i2
+  const int *pairStart;                 // [nPairs + 1]
+  const int2 *pairEntries;              // (e1, e2): two observations of one map point, col(e1) = i1, col(e2) = i2
+  double *pose, *poseBk, *poseEval;     // [nKF][7]
+  double *pt, *ptBk, *ptEval;           // [nMP][3]
+  double *Hpp;                          // [nFree][36]
+  double *Hll, *Dinv;                   // [nMP][9]
+  double *Hpl;                          // [nE][18]
+  double *b, *x;                        // [P + 3 nMP]
+  double *HsG;                          // [P*P] global fallback for the reduced system
+  float *poseIO, *ptIO;                 // results (float)
+  uint8_t* erase;                       // [nE]
+  int* stats;                           // [2]
+  const int* stop;                      // device-visible abort flag (may be NULL)
+  Cam cam;
+  const struct Rig* rig;                // fisheye rig (KB8 cameras + mTrl) or NULL; its edges carry obs[2] = -2 (left camera) / -3 (right, "ToBody")
+  double userLambda;
+  // grid mode (one launch per LM phase across the whole chip)
+  int nChunks;                          // keyframe edge lists cut into chunks of <= 64 edges (one wave each)
+  const int *chunkKF, *chunkStart, *chunkEnd;   // [nChunks]
+  const int *kfChunkStart;              // [nKF + 1]
+  double *kfPart;                       // [nChunks][27]
+  double *redPart;                      // [2][redBlocks] block partial sums (chi2, scale)
+  double *scal;                         // [8] device scalars: chi2, scale, ok, maxdiag
+  // device-side LM control (k_g_lm_*): the state of optimization_algorithm_levenberg.cpp's loop, and its mirror in mapped host memory
+  double *lmd;                          // [4] LMD_*: currentChi, lambda, ni, iniChi
+  int *lmi;                             // [16] LM_*
+  int *lmHost;                          // [4] mapped host memory: decided trials, done, outer iterations, trials
+  int *kfTicket;                        // [nKF] chunks of the keyframe that have delivered their partial blocks (k_g_build)
+  int dupPairs;                         // some (keyframe, landmark) pair carries two edges (fisheye rig: both cameras)
+  // Schur complement on the FP64 matrix cores (schur_mfma.h): dense K-major operands, partial products, block directory
+  double *sW, *sWD, *sPart;
+  const int2* sBlocks;
+  const int* sBlkIndex;
+  int sMp, sNb, sNblk, sNsplit;
+};
+
+__device__ __forceinline__ SE3 load_se3(const double* p) {
+  SE3 s;
+  for (int i = 0; i < 4; ++i) s.q[i] = p[i];
+  for (int i = 0; i < 3; ++i) s.t[i] = p[4 + i];
+  return s;
+}
+__device__ __forceinline__ void store_se3(double* p, const SE3& s) {
+  for (int i = 0; i < 4; ++i) p[i] = s.q[i];
+  for (int i = 0; i < 3; ++i) p[4 + i] = s.t[i];
+}
+__device__ __forceinline__ void inv3(const double* m, double* o) {
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+  const double id = 1.0 / (m[0] * c00 + m[1] * c01 + m[2] * c02);
+  o[0] = c00 * id; o[1] = (m[2] * m[7] - m[1] * m[8]) * id; o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
+  o[3] = c01 * id; o[4] = (m[0] * m[8] - m[2] * m[6]) * id; o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
+  o[6] = c02 * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
+}
+
+constexpr int BA_T = 512, BA_W = BA_T / 64;
+
+__global__ __launch_bounds__(BA_T) void k_local_ba(const BaDev* __restrict__ probs, int useLds) {
+  extern __shared__ double sHs[];  // reduced camera system when it fits
+  __shared__ double red[BA_W];
+  __shared__ int sFlag;
+  const BaDev pb = probs[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int P = pb.P, nMP = pb.nMP, nE = pb.nE, nKF = pb.nKF;
+  double* Hs = useLds ? sHs : pb.HsG;
+  const double deltaMono = (double)(float)sqrt(5.991), deltaStereo = (double)(float)sqrt(7.815);
+  const Cam cam = pb.cam;
+
+  auto terminate = [&]() -> bool {
+    if (!pb.stop) return false;
+    __syncthreads();
+    if (tid == 0) sFlag = __hip_atomic_load(pb.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // host-written, pinned
+    __syncthreads();
+    return sFlag != 0;
+  };
+  // errors at the current estimate -> robust chi2; remembers the evaluation state (for the final chi2 test)
+  auto chi2All = [&]() -> double {
+    for (int i = tid; i < nKF * 7; i += BA_T) pb.poseEval[i] = pb.pose[i];
+    for (int i = tid; i < nMP * 3; i += BA_T) pb.ptEval[i] = pb.pt[i];
+    double s = 0;
+    for (int e = tid; e < nE; e += BA_T) {
+      const SE3 T = load_se3(pb.pose + 7 * pb.eKF[e]);
+      double xc[3], err[3], w;
+      se3_map(T, pb.pt + 3 * pb.eMP[e], xc);
+      const float* o = pb.eObs + 3 * e;
+      const bool st = !(o[2] < 0);
+      const double c = ba_edge_error(cam, pb.rig, st, xc, o, (double)pb.eInfo[e], err);
+      s += huber(st ? deltaStereo : deltaMono, c, &w);
+    }
+    return block_sum_d<BA_W>(s, red);
+  };
+
+  if (terminate()) {  // Optimizer.cc:1355-1356
+    if (tid == 0) { pb.stats[0] = 0; pb.stats[1] = 0; }
+    return;
+  }
+  double lambda = 0, ni = 2;
+  int nBad = 0, its = 0, trials = 0;
+  for (int iter = 0; iter < 10; ++iter) {
+    if (terminate()) break;
+    ++its;
+    double currentChi = chi2All();
+    const double iniChi = currentChi;
+    // ---- buildSystem ----
+    // (1) per map point: Hll, bl
+    for (int m = tid; m < nMP; m += BA_T) {
+      double Hl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
+      const double* X = pb.pt + 3 * m;
+      for (int k = pb.mpStart[m]; k < pb.mpStart[m + 1]; ++k) {
+        const int e = pb.mpEdges[k];
+        const SE3 T = load_se3(pb.pose + 7 * pb.eKF[e]);
+        double xc[3], err[3], w, R[9], Jl[9];
+        se3_map(T, X, xc);
+        const float* o = pb.eObs + 3 * e;
+        const bool st = !(o[2] < 0);
+        const double info = (double)pb.eInfo[e];
+        const double c = ba_edge_error(cam, pb.rig, st, xc, o, info, err);
+        huber(st ? deltaStereo : deltaMono, c, &w);
+        q_to_R(T.q, R);
+        if (pb.rig) ba_edge_jac<true>(cam, pb.rig, st, xc, o, R, nullptr, Jl); else ba_edge_jac<false>(cam, pb.rig, st, xc, o, R, nullptr, Jl);   // (persistent mode: one kernel for both cameras)
+        const double wo = w * info;
+        for (int r = 0; r < 3; ++r) {
+          double s = 0;
+          _Pragma("unroll") for (int i = 0; i < 3; ++i) s += Jl[i * 3 + r] * (-info * err[i] * w);
+          bl[r] += s;
+          for (int cc = 0; cc < 3; ++cc) {
+            double h = 0;
+            _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jl[i * 3 + r] * wo * Jl[i * 3 + cc];
+            Hl[r * 3 + cc] += h;
+          }
+        }
+      }
+      for (int k = 0; k < 9; ++k) pb.Hll[(size_t)m * 9 + k] = Hl[k];
+      for (int k = 0; k < 3; ++k) pb.b[P + 3 * m + k] = bl[k];
+    }
+    // (2) per free keyframe (one wave each): Hpp, bp; per edge: Hpl
+    for (int kf = wv; kf < nKF; kf += BA_W) {
+      const int col = pb.kfCol[kf];
+      if (col < 0) continue;
+      const SE3 T = load_se3(pb.pose + 7 * kf);
+      double R[9];
+      q_to_R(T.q, R);
+      double acc[27];
+#pragma unroll
+      for (int k = 0; k < 27; ++k) acc[k] = 0;
+      for (int k = pb.kfStart[kf] + lane; k < pb.kfStart[kf + 1]; k += 64) {
+        const int e = pb.kfEdges[k];
+        double xc[3], err[3], w, Jp[18], Jl[9];
+        se3_map(T, pb.pt + 3 * pb.eMP[e], xc);
+        const float* o = pb.eObs + 3 * e;
+        const bool st = !(o[2] < 0);
+        const double info = (double)pb.eInfo[e];
+        const double c = ba_edge_error(cam, pb.rig, st, xc, o, info, err);
+        huber(st ? deltaStereo : deltaMono, c, &w);
+        if (pb.rig) ba_edge_jac<true>(cam, pb.rig, st, xc, o, R, Jp, Jl); else ba_edge_jac<false>(cam, pb.rig, st, xc, o, R, Jp, Jl);
+        const double wo = w * info;
+        int q = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          double s = 0;
+          _Pragma("unroll") for (int i = 0; i < 3; ++i) s += Jp[i * 6 + r] * (-info * err[i] * w);
+          acc[21 + r] += s;
+#pragma unroll
+          for (int cc = r; cc < 6; ++cc) {
+            double h = 0;
+            _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jp[i * 6 + r] * wo * Jp[i * 6 + cc];
+            acc[q++] += h;
+          }
+          for (int cc = 0; cc < 3; ++cc) {
+            double h = 0;
+            _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jp[i * 6 + r] * wo * Jl[i * 3 + cc];
+            pb.Hpl[(size_t)e * 18 + r * 3 + cc] = h;
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 27; ++k) acc[k] = wave_sum_d(acc[k]);
+      if (lane == 0) {
+        int q = 0;
+        for (int r = 0; r < 6; ++r)
+          for (int cc = r; cc < 6; ++cc) { pb.Hpp[(size_t)col * 36 + r * 6 + cc] = acc[q]; pb.Hpp[(size_t)col * 36 + cc * 6 + r] = acc[q]; ++q; }
+        for (int r = 0; r < 6; ++r) pb.b[6 * col + r] = acc[21 + r];
+      }
+    }
+    __syncthreads();
+    if (iter == 0) {  // computeLambdaInit
+      if (pb.userLambda > 0) lambda = pb.userLambda;
+      else {
+        double m = 0;
+        for (int i = tid; i < pb.nFree * 6; i += BA_T) m = fmax(m, fabs(pb.Hpp[(size_t)(i / 6) * 36 + (i % 6) * 7]));
+        for (int i = tid; i < nMP * 3; i += BA_T) m = fmax(m, fabs(pb.Hll[(size_t)(i / 3) * 9 + (i % 3) * 4]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+        __syncthreads();
+        if (lane == 0) red[wv] = m;
+        __syncthreads();
+        m = 0;
+        for (int i = 0; i < BA_W; ++i) m = fmax(m, red[i]);
+        lambda = 1e-5 * m;
+      }
+      ni = 2; nBad = 0;
+    }
+    double rho = 0;
+    int qmax = 0;
+    do {
+      // push()
+      for (int i = tid; i < nKF * 7; i += BA_T) pb.poseBk[i] = pb.pose[i];
+      for (int i = tid; i < nMP * 3; i += BA_T) pb.ptBk[i] = pb.pt[i];
+      // ---- BlockSolver::solve (Schur) with lambda on every diagonal (block_solver.hpp:354-480) ----
+      // (a) per map point: Dinv = (Hll + lambda I)^-1
+      for (int m = tid; m < nMP; m += BA_T) {
+        double D[9], Di[9];
+        for (int k = 0; k < 9; ++k) D[k] = pb.Hll[(size_t)m * 9 + k];
+        D[0] += lambda; D[4] += lambda; D[8] += lambda;
+        inv3(D, Di);
+        for (int k = 0; k < 9; ++k) pb.Dinv[(size_t)m * 9 + k] = Di[k];
+      }
+      for (int i = tid; i < P * P; i += BA_T) Hs[i] = 0;
+      __syncthreads();
+      // (b) one wave per block pair (i1 <= i2): Hschur(i1,i2) = [Hpp + lambda I] - sum_l (Hpl_i1 Dinv_l) Hpl_i2^T,
+      //     entries summed in a fixed order (deterministic), mirrored into the lower triangle
+      for (int bp = wv; bp < pb.nPairs; bp += BA_W) {
+        const int i1 = pb.pairBlock[bp] / pb.nFree, i2 = pb.pairBlock[bp] % pb.nFree;
+        double acc[36];
+#pragma unroll
+        for (int k = 0; k < 36; ++k) acc[k] = 0;
+        for (int k = pb.pairStart[bp] + lane; k < pb.pairStart[bp + 1]; k += 64) {
+          const int2 en = pb.pairEntries[k];
+          const double* B1 = pb.Hpl + (size_t)en.x * 18;
+          const double* B2 = pb.Hpl + (size_t)en.y * 18;
+          const double* Di = pb.Dinv + (size_t)pb.eMP[en.x] * 9;
+          double BD[18];
+#pragma unroll
+          for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) BD[r * 3 + c] = B1[r * 3] * Di[c] + B1[r * 3 + 1] * Di[3 + c] + B1[r * 3 + 2] * Di[6 + c];
+#pragma unroll
+          for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) acc[r * 6 + c] += BD[r * 3] * B2[c * 3] + BD[r * 3 + 1] * B2[c * 3 + 1] + BD[r * 3 + 2] * B2[c * 3 + 2];
+        }
+#pragma unroll
+        for (int k = 0; k < 36; ++k) acc[k] = wave_sum_d(acc[k]);
+        if (lane < 36) {
+          const int r = lane / 6, c = lane % 6;
+          double a = 0;
+#pragma unroll
+          for (int k = 0; k < 36; ++k) if (k == lane) a = acc[k];
+          double v = -a;
+          if (i1 == i2) { v += pb.Hpp[(size_t)i1 * 36 + lane]; if (r == c) v += lambda; }
+          Hs[(size_t)(6 * i1 + r) * P + 6 * i2 + c] = v;
+          if (i1 != i2) Hs[(size_t)(6 * i2 + c) * P + 6 * i1 + r] = v;
+        }
+      }
+      // (c) bschur = bp - sum Hpl Dinv bl, one wave per free keyframe over its CSR edge list
+      for (int kf = wv; kf < nKF; kf += BA_W) {
+        const int col = pb.kfCol[kf];
+        if (col < 0) continue;
+        double a6[6] = {0, 0, 0, 0, 0, 0};
+        for (int k = pb.kfStart[kf] + lane; k < pb.kfStart[kf + 1]; k += 64) {
+          const int e = pb.kfEdges[k];
+          const int m = pb.eMP[e];
+          const double* Di = pb.Dinv + (size_t)m * 9;
+          const double* bl = pb.b + P + 3 * m;
+          double db[3];
+          for (int r = 0; r < 3; ++r) db[r] = Di[r * 3] * bl[0] + Di[r * 3 + 1] * bl[1] + Di[r * 3 + 2] * bl[2];
+          const double* B1 = pb.Hpl + (size_t)e * 18;
+          for (int r = 0; r < 6; ++r) a6[r] += B1[r * 3] * db[0] + B1[r * 3 + 1] * db[1] + B1[r * 3 + 2] * db[2];
+        }
+        for (int r = 0; r < 6; ++r) a6[r] = wave_sum_d(a6[r]);
+        if (lane == 0) for (int r = 0; r < 6; ++r) pb.x[6 * col + r] = pb.b[6 * col + r] - a6[r];
+      }
+      __syncthreads();
+      // (d) reduced system: right-looking LDL^T by the whole workgroup (LinearSolverEigen / SimplicialLDLT:
+      //     fails only on a zero pivot), then the two triangular solves by wave 0
+      if (tid == 0) sFlag = 1;
+      __syncthreads();
+      for (int j = 0; j < P; ++j) {
+        const double d = Hs[(size_t)j * P + j];
+        if (d == 0 || d != d) { if (tid == 0) sFlag = 0; break; }   // uniform: every thread reads the same d
+        __syncthreads();
+        // trailing update with the UNSCALED column: A_ik -= A_ij * A_kj / d  (i >= k > j), then scale column j
+        const int nrem = P - j - 1;
+        for (int t = tid; t < nrem * nrem; t += BA_T) {
+          const int i = j + 1 + t / nrem, k = j + 1 + t % nrem;
+          if (k <= i) Hs[(size_t)i * P + k] -= Hs[(size_t)i * P + j] * Hs[(size_t)k * P + j] / d;
+        }
+        __syncthreads();
+        for (int i = j + 1 + tid; i < P; i += BA_T) Hs[(size_t)i * P + j] /= d;
+      }
+      __syncthreads();
+      if (sFlag != 0 && wv == 0) {
+        for (int j = 0; j < P; ++j) {           // forward: L y = b
+          const double xj = pb.x[j];
+          for (int i = j + 1 + lane; i < P; i += 64) pb.x[i] -= Hs[(size_t)i * P + j] * xj;
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+          __builtin_amdgcn_wave_barrier();
+        }
+        for (int i = lane; i < P; i += 64) pb.x[i] /= Hs[(size_t)i * P + i];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        for (int j = P - 1; j >= 0; --j) {      // backward: L^T x = y
+          const double xj = pb.x[j];
+          for (int i = lane; i < j; i += 64) pb.x[i] -= Hs[(size_t)j * P + i] * xj;
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+      __syncthreads();
+      const bool ok2 = sFlag != 0;
+      if (ok2) {
+        // xl = Dinv * (bl - Hpl^T xp)
+        for (int m = tid; m < nMP; m += BA_T) {
+          double cl[3] = {pb.b[P + 3 * m], pb.b[P + 3 * m + 1], pb.b[P + 3 * m + 2]};
+          for (int a = pb.mpStart[m]; a < pb.mpStart[m + 1]; ++a) {
+            const int e = pb.mpEdges[a];
+            const int i1 = pb.kfCol[pb.eKF[e]];
+            if (i1 < 0) continue;
+            const double* B = pb.Hpl + (size_t)e * 18;
+            for (int c = 0; c < 3; ++c)
+              for (int r = 0; r < 6; ++r) cl[c] -= B[r * 3 + c] * pb.x[6 * i1 + r];
+          }
+          const double* Di = pb.Dinv + (size_t)m * 9;
+          for (int r = 0; r < 3; ++r) pb.x[P + 3 * m + r] = Di[r * 3] * cl[0] + Di[r * 3 + 1] * cl[1] + Di[r * 3 + 2] * cl[2];
+        }
+      } else {
+        for (int i = tid; i < P + 3 * nMP; i += BA_T) pb.x[i] = 0;
+      }
+      __syncthreads();
+      // update (oplus)
+      for (int kf = tid; kf < nKF; kf += BA_T) {
+        const int col = pb.kfCol[kf];
+        if (col < 0) continue;
+        double u[6];
+        for (int r = 0; r < 6; ++r) u[r] = pb.x[6 * col + r];
+        store_se3(pb.pose + 7 * kf, se3_mul(se3_exp(u), load_se3(pb.pose + 7 * kf)));
+      }
+      for (int i = tid; i < nMP * 3; i += BA_T) pb.pt[i] += pb.x[P + i];
+      __syncthreads();
+      double tempChi = chi2All();
+      if (!ok2) tempChi = 1.7976931348623157e308;
+      rho = currentChi - tempChi;
+      double part = 0;
+      for (int i = tid; i < P + 3 * nMP; i += BA_T) part += pb.x[i] * (lambda * pb.x[i] + pb.b[i]);
+      double scale = block_sum_d<BA_W>(part, red) + 1e-3;
+      rho /= scale;
+      if (rho > 0 && isfinite(tempChi)) {
+        double alpha = 1. - cube_rn(2 * rho - 1);
+        alpha = fmin(alpha, 2. / 3.);
+        lambda *= fmax(1. / 3., alpha);
+        ni = 2;
+        currentChi = tempChi;
+      } else {
+        lambda *= ni;
+        ni *= 2;
+        __syncthreads();
+        for (int i = tid; i < nKF * 7; i += BA_T) pb.pose[i] = pb.poseBk[i];
+        for (int i = tid; i < nMP * 3; i += BA_T) pb.pt[i] = pb.ptBk[i];
+        __syncthreads();
+      }
+      ++qmax; ++trials;
+    } while (rho < 0 && qmax < 10 && !terminate());
+    if (qmax == 10 || rho == 0) break;
+    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
+    if (nBad >= 3) break;
+  }
+  __syncthreads();
+  // ---- post: chi2 / depth gates on the stored errors (state of the last evaluation), write-back as float ----
+  for (int e = tid; e < nE; e += BA_T) {
+    const float* o = pb.eObs + 3 * e;
+    const bool st = !(o[2] < 0);
+    double xc[3], err[3];
+    se3_map(load_se3(pb.poseEval + 7 * pb.eKF[e]), pb.ptEval + 3 * pb.eMP[e], xc);
+    const double c = ba_edge_error(cam, pb.rig, st, xc, o, (double)pb.eInfo[e], err);
+    se3_map(load_se3(pb.pose + 7 * pb.eKF[e]), pb.pt + 3 * pb.eMP[e], xc);
+    pb.erase[e] = (c > (st ? 7.815 : 5.991) || !ba_depth_positive(pb.rig, o, xc)) ? 1 : 0;
+  }
+  for (int kf = tid; kf < nKF; kf += BA_T)
+    if (pb.kfCol[kf] >= 0) for (int k = 0; k < 7; ++k) pb.poseIO[7 * kf + k] = (float)pb.pose[7 * kf + k];
+  for (int i = tid; i < nMP * 3; i += BA_T) pb.ptIO[i] = (float)pb.pt[i];
+  if (tid == 0) { pb.stats[0] = its; pb.stats[1] = trials; }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Grid mode: the same LM, one launch per phase over the whole chip; the accept/reject decision is taken on the
+// host from three doubles read back once per trial (chi2, scale, ok).  Every reduction has a fixed order
+// (block partials summed by one block; chunk partials summed per keyframe), so results are deterministic.
+constexpr int GB = 256;
+
+// LM state (grid mode, device-side control).  A phase kernel launched with gated = 1 returns at once when the solve has finished
+// (launches are queued one trial ahead of the decisions) or, for the build kernels, when this trial re-solves the same system
+// with a larger lambda (the previous trial was rejected).
+enum { LM_ITER, LM_QMAX, LM_NBAD, LM_ITS, LM_TRIALS, LM_DONE, LM_NEEDBUILD, LM_REJECTED, LM_TICKET };
+enum { LMD_CHI, LMD_LAMBDA, LMD_NI, LMD_INICHI };
+__device__ __forceinline__ bool lm_skip(const BaDev& pb, int gated) { return gated && pb.lmi[LM_DONE] != 0; }
+__device__ __forceinline__ bool lm_skip_build(const BaDev& pb, int gated) { return gated && (pb.lmi[LM_DONE] != 0 || pb.lmi[LM_NEEDBUILD] == 0); }
+__device__ __forceinline__ bool lm_stop_requested(const BaDev& pb) {   // morb_ba_set_stop's flag and the caller's *pbStopFlag as the host loop forwards it
+  return pb.stop && (__hip_atomic_load(pb.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 ||
+                     __hip_atomic_load(pb.stop + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0);
+}
+
+// after the first chi2 (sum s): currentChi, and the state at the top of the first iteration.  One thread.
+__device__ void lm_init(const BaDev& pb, double s) {
+  const bool stop = lm_stop_requested(pb);
+  pb.scal[0] = s;
+  pb.lmd[LMD_CHI] = s; pb.lmd[LMD_LAMBDA] = 0; pb.lmd[LMD_NI] = 2; pb.lmd[LMD_INICHI] = s;
+  pb.lmi[LM_ITER] = 0; pb.lmi[LM_QMAX] = 0; pb.lmi[LM_NBAD] = 0; pb.lmi[LM_ITS] = stop ? 0 : 1; pb.lmi[LM_TRIALS] = 0;
+  pb.lmi[LM_DONE] = stop ? 1 : 0; pb.lmi[LM_NEEDBUILD] = 1; pb.lmi[LM_REJECTED] = 0;
+  __hip_atomic_store(pb.lmHost + 2, stop ? 0 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 3, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 1, stop ? 1 : 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// after a trial's chi2 (s0) and linear-model gain (s1): rho, accept / reject, the lambda schedule, and whether another trial /
+// iteration follows (optimization_algorithm_levenberg.cpp:99-169 with ORB-SLAM's stop rule).  One thread.
+__device__ void lm_decide(const BaDev& pb, double s0, double s1) {
+  pb.scal[0] = s0; pb.scal[1] = s1;
+  double currentChi = pb.lmd[LMD_CHI], lambda = pb.lmd[LMD_LAMBDA], ni = pb.lmd[LMD_NI];
+  const double iniChi = pb.lmd[LMD_INICHI];
+  int iter = pb.lmi[LM_ITER], qmax = pb.lmi[LM_QMAX], nBad = pb.lmi[LM_NBAD], its = pb.lmi[LM_ITS];
+  double tempChi = s0;
+  if (pb.scal[2] == 0.0) tempChi = 1.7976931348623157e308;   // the linear solve failed
+  const double rho = (currentChi - tempChi) / (s1 + 1e-3);
+  const bool accept = rho > 0 && isfinite(tempChi);
+  if (accept) {
+    double alpha = 1. - cube_rn(2 * rho - 1);
+    alpha = fmin(alpha, 2. / 3.);
+    lambda *= fmax(1. / 3., alpha);
+    ni = 2;
+    currentChi = tempChi;
+  } else {
+    lambda *= ni;
+    ni *= 2;
+  }
+  ++qmax;
+  const int trials = pb.lmi[LM_TRIALS] + 1;
+  const bool stop = lm_stop_requested(pb);
+  int done = 0, needBuild = 0;
+  if (!(rho < 0 && qmax < 10 && !stop)) {   // the trial loop ends (:139)
+    bool fin = (qmax == 10 || rho == 0);
+    if (!fin) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; fin = nBad >= 3; }   // the stop rule of ORB-SLAM's g2o (:146-151)
+    if (!fin) { ++iter; fin = iter >= 10 || stop; }
+    if (fin) done = 1;
+    else { ++its; qmax = 0; needBuild = 1; pb.lmd[LMD_INICHI] = currentChi; }
+  }
+  pb.lmd[LMD_CHI] = currentChi; pb.lmd[LMD_LAMBDA] = lambda; pb.lmd[LMD_NI] = ni;
+  pb.lmi[LM_ITER] = iter; pb.lmi[LM_QMAX] = qmax; pb.lmi[LM_NBAD] = nBad; pb.lmi[LM_ITS] = its; pb.lmi[LM_TRIALS] = trials;
+  pb.lmi[LM_DONE] = done; pb.lmi[LM_NEEDBUILD] = needBuild; pb.lmi[LM_REJECTED] = accept ? 0 : 1;
+  __hip_atomic_store(pb.lmHost + 2, its, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 3, trials, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 0, trials, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided trials: the host queues trial k + 2 when it sees k
+}
+// In-launch hand-off of partial sums to the workgroup that draws the last ticket (guide, guideline 16): the payload is stored write-through
+// at agent scope (sc1), the storing wave waits for its stores (s_waitcnt vmcnt(0)) and only then draws its ticket with a relaxed agent-scope
+// add; the last arriver reads every handed-off word at agent scope (load_l2).  No __threadfence(): on this chip an agent-scope release is a
+// write-back of the XCD's L2, and one per wave (k_g_build: 324 of them, beside the landmark half's stores) was ~8 of the kernel's 18 us.
+__device__ __forceinline__ void store_l2(double* p, double v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ int draw_ticket(int* counter) { return __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double load_l2(const double* p) {   // another workgroup of this launch wrote it: read at agent scope
+  return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+// mode 0: block partial sums only (host-side LM control).  mode 1 / 2 (device-side control): the last workgroup to finish adds the
+// partials up in k_g_reduce's order and takes the LM decision of this trial (1) or sets up the first iteration (2).
+__global__ __launch_bounds__(GB) void k_g_chi2(const BaDev* __restrict__ pbp, double* __restrict__ part, const double* __restrict__ part1, int mode) {
+  __shared__ double red[4];
+  __shared__ int isLast;
+  const BaDev pb = *pbp;
+  if (lm_skip(pb, mode == 1)) return;
+  const int gid = blockIdx.x * GB + threadIdx.x;
+  if (gid < pb.nKF * 7) pb.poseEval[gid] = pb.pose[gid];
+  if (gid < pb.nMP * 3) pb.ptEval[gid] = pb.pt[gid];
+  double s = 0;
+  if (gid < pb.nE) {
+    const SE3 T = load_se3(pb.pose + 7 * pb.eKF[gid]);
+    double xc[3], err[3], w;
+    se3_map(T, pb.pt + 3 * pb.eMP[gid], xc);
+    const float* o = pb.eObs + 3 * gid;
+    const bool st = !(o[2] < 0);
+    const double c = ba_edge_error(pb.cam, pb.rig, st, xc, o, (double)pb.eInfo[gid], err);
+    s = huber(st ? (double)(float)sqrt(7.815) : (double)(float)sqrt(5.991), c, &w);
+  }
+  s = block_sum_d<4>(s, red);
+  if (threadIdx.x == 0) store_l2(part + blockIdx.x, s);
+  if (mode == 0) return;
+  if (threadIdx.x == 0) {
+    wait_stores();
+    isLast = draw_ticket(&pb.lmi[LM_TICKET]) == (int)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!isLast) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (every handed-off word is read with load_l2)
+  const int n = gridDim.x;
+  double s0 = 0, s1 = 0;
+  for (int i = threadIdx.x; i < n; i += GB) { s0 += load_l2(part + i); if (mode == 1) s1 += load_l2(part1 + i); }
+  s0 = block_sum_d<4>(s0, red);
+  s1 = block_sum_d<4>(s1, red);
+  if (threadIdx.x != 0) return;
+  pb.lmi[LM_TICKET] = 0;
+  if (mode == 1) lm_decide(pb, s0, s1); else lm_init(pb, s0);
+}
+// The landmark blocks Hll / bl of map point m (block_solver.hpp:354-480 reads them): EIGHT lanes per point, one edge each and chunk by chunk
+// (a point has 5 - 8 observations here; a thread per point walked them one after the other: 20 of k_g_build's 23 us).  Each lane leaves its
+// edge's twelve contributions in the wave's LDS slice and the group's first lane adds them up IN EDGE ORDER — the sums are bit for bit those
+// of the serial walk.  Lanes of one wave only: no workgroup barrier.  -> max |diag Hll| of the point (first lane of the group; 0 elsewhere)
+constexpr int MP_LANES = 8;
+template <bool RIG>
+__device__ __forceinline__ double build_mp_point(const BaDev& pb, int m, int sub, double* __restrict__ slot /* [MP_LANES][12] of the group */) {
+  const double deltaMono = (double)(float)sqrt(5.991), deltaStereo = (double)(float)sqrt(7.815);
+  double Hl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
+  const bool live = m < pb.nMP;
+  const double* X = pb.pt + 3 * (live ? m : 0);
+  const int k0 = live ? pb.mpStart[m] : 0, k1 = live ? pb.mpStart[m + 1] : 0;
+  for (int kb = k0; kb < k1; kb += MP_LANES) {
+    const int k = kb + sub;
+    double c12[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) c12[q] = 0;
+    if (k < k1) {
+      const int e = pb.mpEdges[k];
+      const SE3 T = load_se3(pb.pose + 7 * pb.eKF[e]);
+      double xc[3], err[3], w, R[9], Jl[9];
+      se3_map(T, X, xc);
+      const float* o = pb.eObs + 3 * e;
+      const bool st = !(o[2] < 0);
+      const double info = (double)pb.eInfo[e];
+      const double c = ba_edge_error(pb.cam, pb.rig, st, xc, o, info, err);
+      huber(st ? deltaStereo : deltaMono, c, &w);
+      q_to_R(T.q, R);
+      ba_edge_jac<RIG>(pb.cam, pb.rig, st, xc, o, R, nullptr, Jl);
+      const double wo = w * info;   // (mono edges: third Jacobian row and err[2] are zero, so the 3-row form is exact)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double sacc = 0;
+        _Pragma("unroll") for (int i = 0; i < 3; ++i) sacc += Jl[i * 3 + r] * (-info * err[i] * w);
+        c12[9 + r] = sacc;
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+          double h = 0;
+          _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jl[i * 3 + r] * wo * Jl[i * 3 + cc];
+          c12[r * 3 + cc] = h;
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) slot[sub * 12 + q] = c12[q];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (sub == 0) {
+      const int cnt = k1 - kb < MP_LANES ? k1 - kb : MP_LANES;
+      for (int j = 0; j < cnt; ++j) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Hl[q] += slot[j * 12 + q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) bl[q] += slot[j * 12 + 9 + q];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // (the slice is rewritten by the next chunk)
+  }
+  if (!live || sub != 0) return 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pb.Hll[(size_t)m * 9 + k] = Hl[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pb.b[pb.P + 3 * m + k] = bl[k];
+  return fmax(fmax(fabs(Hl[0]), fabs(Hl[4])), fabs(Hl[8]));
+}
+template <bool RIG>
+__device__ __forceinline__ void build_kf_chunk(const BaDev& pb, int c, int lane) {
+  const int kf = pb.chunkKF[c];
+  const double deltaMono = (double)(float)sqrt(5.991), deltaStereo = (double)(float)sqrt(7.815);
+  const SE3 T = load_se3(pb.pose + 7 * kf);
+  double R[9];
+  q_to_R(T.q, R);
+  double acc[27];
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = 0;
+  const int k = pb.chunkStart[c] + lane;
+  if (k < pb.chunkEnd[c]) {
+    const int e = pb.kfEdges[k];
+    double xc[3], err[3], w, Jp[18], Jl[9];
+    se3_map(T, pb.pt + 3 * pb.eMP[e], xc);
+    const float* o = pb.eObs + 3 * e;
+    const bool st = !(o[2] < 0);
+    const double info = (double)pb.eInfo[e];
+    const double ch = ba_edge_error(pb.cam, pb.rig, st, xc, o, info, err);
+    huber(st ? deltaStereo : deltaMono, ch, &w);
+    ba_edge_jac<RIG>(pb.cam, pb.rig, st, xc, o, R, Jp, Jl);
+    const double wo = w * info;   // (mono edges: third Jacobian row and err[2] are zero, so the 3-row form is exact)
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double sacc = 0;
+      _Pragma("unroll") for (int i = 0; i < 3; ++i) sacc += Jp[i * 6 + r] * (-info * err[i] * w);
+      acc[21 + r] = sacc;
+#pragma unroll
+      for (int cc = r; cc < 6; ++cc) {
+        double h = 0;
+        _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jp[i * 6 + r] * wo * Jp[i * 6 + cc];
+        acc[q++] = h;
+      }
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) {
+        double h = 0;
+        _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jp[i * 6 + r] * wo * Jl[i * 3 + cc];
+        pb.Hpl[(size_t)e * 18 + r * 3 + cc] = h;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 27; ++q) acc[q] = wave_sum_d(acc[q]);
+  if (lane < 27) {
+    double v = 0;
+#pragma unroll
+    for (int q = 0; q < 27; ++q) if (q == lane) v = acc[q];
+    store_l2(pb.kfPart + (size_t)c * 27 + lane, v);
+  }
+}
+// buildSystem in ONE launch (device-side LM control): workgroups [0, kfBlocks) take the keyframe chunks, the rest the map points;
+// the last chunk of a keyframe to deliver its partial blocks adds them up in chunk order (k_g_kf_reduce's sum, whoever runs it).
+// Two launches on two streams cost more in cross-stream events (~25 us per trial) than running side by side saved.
+template <bool RIG>
+__global__ __launch_bounds__(GB) void k_g_build(const BaDev* __restrict__ pbp, int kfBlocks) {
+  const BaDev pb = *pbp;
+  if (lm_skip_build(pb, 1)) return;
+  // first iteration: the largest diagonal entry of the system for computeLambdaInit (:186-194) — a max is order-independent, so an
+  // atomic on the bit pattern of the non-negative double keeps the result deterministic
+  const bool first = pb.lmi[LM_TRIALS] == 0;
+  unsigned long long* maxDiag = reinterpret_cast<unsigned long long*>(pb.scal + 3);
+  if ((int)blockIdx.x >= kfBlocks) {
+    __shared__ double sMp[GB * 12];
+    const int g = threadIdx.x / MP_LANES, sub = threadIdx.x % MP_LANES;
+    const int m = (blockIdx.x - kfBlocks) * (GB / MP_LANES) + g;
+    double dm = build_mp_point<RIG>(pb, m, sub, sMp + (size_t)g * MP_LANES * 12);
+    if (first) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) dm = fmax(dm, __shfl_xor(dm, off, 64));
+      if ((threadIdx.x & 63) == 0) atomicMax(maxDiag, __builtin_bit_cast(unsigned long long, dm));
+    }
+    return;
+  }
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= pb.nChunks) return;
+  build_kf_chunk<RIG>(pb, c, lane);
+  const int kf = pb.chunkKF[c];
+  int last = 0;
+  wait_stores();   // (the wave's partial sums have left for memory)
+  if (lane == 0) {
+    const int nc = pb.kfChunkStart[kf + 1] - pb.kfChunkStart[kf];
+    last = draw_ticket(&pb.kfTicket[kf]) == nc - 1;
+    if (last) pb.kfTicket[kf] = 0;
+  }
+  if (!__builtin_amdgcn_readfirstlane(last)) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (every handed-off word is read with load_l2)
+  const int col = pb.kfCol[kf];
+  if (lane >= 27) return;
+  double s = 0;
+  for (int cc = pb.kfChunkStart[kf]; cc < pb.kfChunkStart[kf + 1]; ++cc) s += load_l2(pb.kfPart + (size_t)cc * 27 + lane);
+  if (lane < 21) {
+    int r = 0, q = lane;
+    while (q >= 6 - r) { q -= 6 - r; ++r; }
+    const int c2 = r + q;
+    pb.Hpp[(size_t)col * 36 + r * 6 + c2] = s;
+    pb.Hpp[(size_t)col * 36 + c2 * 6 + r] = s;
+    if (first && r == c2) atomicMax(maxDiag, __builtin_bit_cast(unsigned long long, fabs(s)));
+  } else {
+    pb.b[6 * col + (lane - 21)] = s;
+  }
+}
+// Hpl of (keyframe column i, landmark m) as the MFMA operands need it: a fisheye rig may observe a landmark with both cameras
+// of one keyframe, i.e. through two edges — the first of them (lowest edge index) carries the sum, the others nothing.
+__device__ __forceinline__ bool pair_block(const BaDev& pb, int e, int i, int m, double* __restrict__ B) {
+  for (int q = 0; q < 18; ++q) B[q] = pb.Hpl[(size_t)e * 18 + q];
+  if (!pb.dupPairs) return true;
+  for (int k = pb.mpStart[m]; k < pb.mpStart[m + 1]; ++k) {
+    const int e2 = pb.mpEdges[k];
+    if (e2 == e || pb.kfCol[pb.eKF[e2]] != i) continue;
+    if (e2 < e) return false;
+    for (int q = 0; q < 18; ++q) B[q] += pb.Hpl[(size_t)e2 * 18 + q];
+  }
+  return true;
+}
+// Start of a trial.  gated (device-side LM control): lambda comes from the LM state; a rejected previous trial is undone here
+// (pose / point backup restored instead of taken), and after an accepted one the operand W is packed too (k_g_pack_w's work).
+__global__ __launch_bounds__(GB) void k_g_dinv_push(const BaDev* __restrict__ pbp, double lambda, double* __restrict__ Hs, int valuSchur, int gated) {
+  const BaDev pb = *pbp;
+  if (lm_skip(pb, gated)) return;
+  bool restore = false, packW = false;
+  const int gid = blockIdx.x * GB + threadIdx.x;
+  if (gated) {
+    lambda = pb.lmd[LMD_LAMBDA]; restore = pb.lmi[LM_REJECTED] != 0; packW = pb.lmi[LM_NEEDBUILD] != 0;
+    if (pb.lmi[LM_TRIALS] == 0) {   // first trial: computeLambdaInit (:186-194) from the build's max diagonal; later kernels read it from the state
+      lambda = pb.userLambda > 0 ? pb.userLambda : 1e-5 * pb.scal[3];
+      if (gid == 0) pb.lmd[LMD_LAMBDA] = lambda;
+    }
+  }
+  if (restore) {
+    if (gid < pb.nKF * 7) pb.pose[gid] = pb.poseBk[gid];
+    if (gid < pb.nMP * 3) pb.pt[gid] = pb.ptBk[gid];
+  } else {
+    if (gid < pb.nKF * 7) pb.poseBk[gid] = pb.pose[gid];
+    if (gid < pb.nMP * 3) pb.ptBk[gid] = pb.pt[gid];
+  }
+  if (valuSchur && gid < pb.P * pb.P) Hs[gid] = 0;
+  if (gid < pb.nMP) {
+    double D[9], Di[9];
+    for (int k = 0; k < 9; ++k) D[k] = pb.Hll[(size_t)gid * 9 + k];
+    D[0] += lambda; D[4] += lambda; D[8] += lambda;
+    inv3(D, Di);
+    for (int k = 0; k < 9; ++k) pb.Dinv[(size_t)gid * 9 + k] = Di[k];
+  }
+  if (!valuSchur && gid < pb.nE) {
+    // the MFMA operand WD = Hpl (Hll + lambda I)^-1 of this observation (rows 3 m + c, columns 6 i + r); the inverse is
+    // recomputed per observation so that the pack needs no second launch behind the per-point loop above
+    const int i = pb.kfCol[pb.eKF[gid]];
+    const int m = pb.eMP[gid];
+    double B1[18];
+    if (i >= 0 && pair_block(pb, gid, i, m, B1)) {
+      double D[9], Di[9];
+      for (int k = 0; k < 9; ++k) D[k] = pb.Hll[(size_t)m * 9 + k];
+      D[0] += lambda; D[4] += lambda; D[8] += lambda;
+      inv3(D, Di);
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          pb.sWD[(size_t)(3 * m + c) * pb.sMp + 6 * i + r] = B1[r * 3] * Di[c] + B1[r * 3 + 1] * Di[3 + c] + B1[r * 3 + 2] * Di[6 + c];
+          if (packW) pb.sW[(size_t)(3 * m + c) * pb.sMp + 6 * i + r] = B1[r * 3 + c];
+        }
+    }
+  }
+  if (packW && gid < pb.nMP * 3) pb.sW[(size_t)gid * pb.sMp + pb.P] = pb.b[pb.P + gid];
+}
+// reduced system from the partial products: Hs = Hpp + lambda I - C (C symmetric: the upper blocks serve both triangles),
+// x[0:P] = b_p - C[:, P]
+__global__ __launch_bounds__(GB) void k_g_schur_finish(const BaDev* __restrict__ pbp, double lambda, double* __restrict__ Hs, int gated) {
+  const BaDev pb = *pbp;
+  if (lm_skip(pb, gated)) return;
+  if (gated) lambda = pb.lmd[LMD_LAMBDA];
+  const int t = blockIdx.x * GB + threadIdx.x, gid = t >> 2, q = t & 3, P = pb.P;   // four lanes per element (schur_sum4)
+  const bool mat = gid < P * P, rhs = !mat && gid < P * P + P;
+  int r = 0, c = P;
+  if (mat) { r = gid / P; c = gid - r * P; } else if (rhs) r = gid - P * P;
+  const int i = r < c ? r : c, j = r < c ? c : r;
+  const double cs = morbschur::schur_sum4(pb.sPart, pb.sBlkIndex, pb.sNb, pb.sNblk, pb.sNsplit, (mat || rhs) ? i : 0, (mat || rhs) ? j : 0, q);
+  if (q != 0) return;
+  if (mat) {
+    double v = -cs;
+    if (r / 6 == c / 6) { v += pb.Hpp[(size_t)(r / 6) * 36 + (r % 6) * 6 + (c % 6)]; if (r == c) v += lambda; }
+    Hs[gid] = v;
+  } else if (rhs) {
+    pb.x[r] = pb.b[r] - cs;
+  }
+}
+// the reduced camera system beyond ~176 unknowns (30 free keyframes and more: the reference takes every covisible keyframe,
+// Optimizer.cc:1058-1070): the matrix stays in global memory, one 16-column panel at a time in LDS (dense_ldlt.h: ldlt_solve_global);
+// HsG is overwritten by the factors (k_g_schur_finish rebuilds it for every trial); x = Hs^-1 x in place
+__global__ __launch_bounds__(morbdense::GT) void k_g_ldlt_global(const BaDev* __restrict__ pbp, double* __restrict__ HsG, double* __restrict__ pnlG,
+                                                                 int panelInLds, int gated) {
+  extern __shared__ double sLd[];   // dblk | y | (the panel copies when they fit)
+  __shared__ int sOk;
+  const BaDev pb = *pbp;
+  if (lm_skip(pb, gated)) return;
+  double* pnl = panelInLds ? sLd + morbdense::global_lds_doubles(pb.P) : pnlG;
+  const bool ok = morbdense::ldlt_solve_global<false>(HsG, pb.x, pb.x, pb.P, pnl, sLd, &sOk);
+  if (threadIdx.x == 0) pb.scal[2] = ok ? 1.0 : 0.0;
+}
+// the reduced camera system with its lower triangle resident in LDS (dense_ldlt.h); x = Hs^-1 x in place
+__global__ __launch_bounds__(morbdense::LT) void k_g_ldlt_lds(const BaDev* __restrict__ pbp, const double* __restrict__ HsG, int gated) {
+  extern __shared__ double sLd[];
+  __shared__ int sOk;
+  const BaDev pb = *pbp;
+  if (lm_skip(pb, gated)) return;
+  const bool ok = morbdense::ldlt_solve<false>(HsG, pb.x, pb.x, pb.P, sLd, &sOk);
+  if (threadIdx.x == 0) pb.scal[2] = ok ? 1.0 : 0.0;
+}
+// The same step with the landmark part read from the MFMA operand W (dense rows [3 nMP][Mp], column P = b_l): 16 lanes per point,
+// lane q takes columns q, q + 16, ... of the point's three rows (coalesced 128-byte reads, all in flight at once) and the row sums are
+// DPP reductions in a fixed order — round 2's first form walked the point's edges one dependent load chain after the other (21 us).
+__global__ __launch_bounds__(GB) void k_g_backsub_update_w(const BaDev* __restrict__ pbp, double* __restrict__ part) {
+  __shared__ double red[4];
+  const BaDev pb = *pbp;
+  if (lm_skip(pb, 1)) return;
+  const double lambda = pb.lmd[LMD_LAMBDA];
+  const int gid = blockIdx.x * GB + threadIdx.x, m = gid >> 4, q = gid & 15;
+  const int P = pb.P;
+  const bool ok = pb.scal[2] != 0.0;
+  double sc = 0;
+  {
+    const bool live = m < pb.nMP;
+    const size_t row = (size_t)3 * (live ? m : 0) * pb.sMp;
+    double a0 = 0, a1 = 0, a2 = 0;
+    for (int j = q; j < P; j += 16) {
+      const double xj = pb.x[j];
+      a0 += pb.sW[row + j] * xj; a1 += pb.sW[row + pb.sMp + j] * xj; a2 += pb.sW[row + 2 * (size_t)pb.sMp + j] * xj;
+    }
+    a0 = morbwave::row_sum_f64(a0); a1 = morbwave::row_sum_f64(a1); a2 = morbwave::row_sum_f64(a2);
+    if (live && q < 3) {
+      double xl = 0;
+      if (ok) {
+        const double cl[3] = {pb.sW[row + P] - a0, pb.sW[row + pb.sMp + P] - a1, pb.sW[row + 2 * (size_t)pb.sMp + P] - a2};
+        const double* Di = pb.Dinv + (size_t)m * 9;
+        xl = Di[q * 3] * cl[0] + Di[q * 3 + 1] * cl[1] + Di[q * 3 + 2] * cl[2];
+      }
+      pb.x[P + 3 * m + q] = xl;
+      pb.pt[3 * m + q] += xl;
+      sc += xl * (lambda * xl + pb.b[P + 3 * m + q]);
+    }
+  }
+  if (gid < pb.nKF) {
+    const int col = pb.kfCol[gid];
+    if (col >= 0) {
+      double u[6];
+      for (int r = 0; r < 6; ++r) { u[r] = ok ? pb.x[6 * col + r] : 0.0; sc += u[r] * (lambda * u[r] + pb.b[6 * col + r]); }
+      store_se3(pb.pose + 7 * gid, se3_mul(se3_exp(u), load_se3(pb.pose + 7 * gid)));
+    }
+  }
+  sc = block_sum_d<4>(sc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = sc;
+}
+__global__ __launch_bounds__(GB) void k_g_finish(const BaDev* __restrict__ pbp, int its, int trials) {
+  const BaDev pb = *pbp;
+  const double *pose = pb.pose, *pt = pb.pt;
+  if (its < 0) {   // device-side LM control keeps the counters; a rejected last trial is undone by reading its backup
+    its = pb.lmi[LM_ITS]; trials = pb.lmi[LM_TRIALS];
+    if (pb.lmi[LM_REJECTED]) { pose = pb.poseBk; pt = pb.ptBk; }
+  }
+  const int gid = blockIdx.x * GB + threadIdx.x;
+  if (gid < pb.nE) {
+    const int e = gid;
+    const float* o = pb.eObs + 3 * e;
+    const bool st = !(o[2] < 0);
+    double xc[3], err[3];
+    se3_map(load_se3(pb.poseEval + 7 * pb.eKF[e]), pb.ptEval + 3 * pb.eMP[e], xc);
+    const double c = ba_edge_error(pb.cam, pb.rig, st, xc, o, (double)pb.eInfo[e], err);
+    se3_map(load_se3(pose + 7 * pb.eKF[e]), pt + 3 * pb.eMP[e], xc);
+    pb.erase[e] = (c > (st ? 7.815 : 5.991) || !ba_depth_positive(pb.rig, o, xc)) ? 1 : 0;
+  }
+  if (gid < pb.nKF && pb.kfCol[gid] >= 0) for (int k = 0; k < 7; ++k) pb.poseIO[7 * gid + k] = (float)pose[7 * gid + k];
+  if (gid < pb.nMP * 3) pb.ptIO[gid] = (float)pt[gid];
+  if (gid == 0) { pb.stats[0] = its; pb.stats[1] = trials; }
+}
+
+// ---- device-side LM control (optimization_algorithm_levenberg.cpp:61-169 as morb_ba_solve's host loop used to run it) ----
+__global__ void k_ba_reset(BaDev pb, const float* __restrict__ pose0, const float* __restrict__ pt0) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < pb.nKF) {
+    const SE3 s = se3_from_float(pose0 + 7 * i);
+    store_se3(pb.pose + 7 * i, s);
+    for (int k = 0; k < 7; ++k) pb.poseIO[7 * i + k] = pose0[7 * i + k];
+  }
+  if (i < pb.nMP * 3) pb.pt[i] = (double)pt0[i];
+  if (i == 0) { pb.lmi[LM_TICKET] = 0; pb.scal[3] = 0; }
+}
+
+}  // namespace
+
+// =====================================================================================================
+struct morb_ba_problem {
+  morb_optimizer* opt = nullptr;
+  BaDev h;                 // host copy of the device descriptor
+  BaDev* d_desc = nullptr;
+  float *d_pose0 = nullptr, *d_pt0 = nullptr;
+  // a persistent problem (three-step API) owns its device block and pinned words; a one-shot problem borrows them from the optimizer handle
+  morb::DeviceArray<> mem;
+  morb::PinnedArray<int> words;
+  int* h_stop = nullptr;   // [16] pinned, device-mapped host words: [0] abort flag (morb_ba_set_stop writes it without any HIP call, kernels poll it), [1] forwarded *pbStopFlag, [4..7] LM state mirror
+  const volatile unsigned char* userStop = nullptr;   // the caller's *pbStopFlag (one-shot entry points), polled by the host LM loop
+  int useLds = 1;
+  size_t ldsBytes = 0;
+  size_t denseLds = 0;     // LDS bytes of the triangle-resident solver (0: the system is too large for it)
+  int mode = 0;            // 0 = grid (one launch per LM phase, host-side accept/reject), 1 = one persistent workgroup
+  morb::Event solved;            // recorded behind the last morb_ba_solve on whatever stream it ran on: morb_ba_results waits for the EVENT — not for
+                                 // the device, and not through the caller's stream handle, which the caller may have destroyed since
+  int redBlocks = 0;
+  morbschur::Plan schur;
+  size_t nPairEntries = 0;   // (e1, e2) observation pairs of the sparse block-pair Schur form (flop accounting only)
+  double* d_ldws = nullptr;  // panel copies of the global-memory LDL^T when they do not fit LDS (dense_ldlt.h: global_panel_doubles)
+  size_t globalLds = 0;      // dynamic LDS of k_g_ldlt_global
+  int panelInLds = 1;
+};
+
+extern "C" {
+
+// morb_ba_problem_create, with the fisheye rig of morb_ba_problem_create_fisheye (nullptr: pinhole).  arena: the problem of a one-shot
+// entry point, carved from the handle's `work` / `stage` / `lmWords` for the duration of that call (it owns no memory of its own)
+static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                             int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
+                             const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
+                             int lambdaInit100, const Rig* rig, bool arena) {
+  MORB_REQUIRE(o && out && kfPose && kfFixed && mpPos && eKF && eMP && eObs && eInvSigma2, MORB_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
+  for (int e = 0; e < nE; ++e)
+    MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
+  MORB_HIP_CHECK(hipSetDevice(o->device));
+  std::unique_ptr<morb_ba_problem> p(new morb_ba_problem());
+  p->opt = o;
+  BaDev& h = p->h;
+  memset(&h, 0, sizeof h);
+  h.nKF = nKF; h.nMP = nMP; h.nE = nE;
+  std::vector<int> kfCol(nKF, -1);
+  // free keyframes that actually carry an edge get a column (initializeOptimization drops isolated vertices)
+  std::vector<char> used(nKF, 0);
+  for (int e = 0; e < nE; ++e) used[eKF[e]] = 1;
+  int nFree = 0;
+  for (int i = 0; i < nKF; ++i) if (!kfFixed[i] && used[i]) kfCol[i] = nFree++;
+  h.nFree = nFree; h.P = 6 * nFree;
+  // CSR lists in edge-id order
+  std::vector<int> mpStart(nMP + 1, 0), kfStart(nKF + 1, 0), mpEdges(nE), kfEdges(nE);
+  for (int e = 0; e < nE; ++e) { mpStart[eMP[e] + 1]++; kfStart[eKF[e] + 1]++; }
+  for (int i = 0; i < nMP; ++i) mpStart[i + 1] += mpStart[i];
+  for (int i = 0; i < nKF; ++i) kfStart[i + 1] += kfStart[i];
+  {
+    std::vector<int> a(mpStart.begin(), mpStart.end() - 1), b(kfStart.begin(), kfStart.end() - 1);
+    for (int e = 0; e < nE; ++e) { mpEdges[a[eMP[e]]++] = e; kfEdges[b[eKF[e]]++] = e; }
+  }
+  h.dupPairs = 0;
+  for (int m = 0; m < nMP && !h.dupPairs; ++m)
+    for (int a = mpStart[m]; a < mpStart[m + 1] && !h.dupPairs; ++a)
+      for (int b2 = a + 1; b2 < mpStart[m + 1]; ++b2)
+        if (eKF[mpEdges[a]] == eKF[mpEdges[b2]]) { h.dupPairs = 1; break; }
+  // block pairs of the reduced camera system and, per pair, the (observation, observation) entries that feed it: operands of the
+  // persistent-workgroup mode.  The one-shot entry points always solve in grid
+  // mode on the matrix cores, which only needs the number of entries (flop accounting): they skip the lists (0.3 ms of host work, 0.6 MB).
+  std::vector<int> pairBlock, pairStart;
+  std::vector<int2> pairEntries;
+  const bool wantPairs = !arena;
+  size_t nPairEntriesCount = 0;
+  if (!wantPairs) {
+    for (int m = 0; m < nMP; ++m) {
+      size_t nf = 0;
+      for (int a = mpStart[m]; a < mpStart[m + 1]; ++a) nf += kfCol[eKF[mpEdges[a]]] >= 0 ? 1 : 0;
+      nPairEntriesCount += nf * (nf + 1) / 2;   // (pairs with column(e1) <= column(e2), as the lists would hold them; approximate for duplicate columns)
+    }
+    pairBlock.push_back(0); pairStart.assign(2, 0); pairEntries.assign(1, make_int2(0, 0));
+  } else {
+    const int nb = std::max(nFree, 1) * std::max(nFree, 1);
+    std::vector<int> cnt(nb + 1, 0);
+    auto forPairs = [&](auto&& fn) {
+      for (int m = 0; m < nMP; ++m)
+        for (int a = mpStart[m]; a < mpStart[m + 1]; ++a) {
+          const int ea = mpEdges[a], ca = kfCol[eKF[ea]];
+          if (ca < 0) continue;
+          for (int b2 = mpStart[m]; b2 < mpStart[m + 1]; ++b2) {
+            const int eb = mpEdges[b2], cb = kfCol[eKF[eb]];
+            if (cb < 0 || cb < ca) continue;
+            fn(ca * nFree + cb, ea, eb);
+          }
+        }
+    };
+    forPairs([&](int key, int, int) { cnt[key + 1]++; });
+    std::vector<int> slot(nb, -1);
+    int total = 0;
+    for (int k = 0; k < nb; ++k) {
+      if (cnt[k + 1] > 0) { slot[k] = (int)pairBlock.size(); pairBlock.push_back(k); pairStart.push_back(total); total += cnt[k + 1]; }
+    }
+    pairStart.push_back(total);
+    pairEntries.resize(std::max(total, 1));
+    std::vector<int> fill(pairStart.begin(), pairStart.end());
+    forPairs([&](int key, int ea, int eb) { pairEntries[fill[slot[key]]++] = make_int2(ea, eb); });
+  }
+  h.nPairs = wantPairs ? (int)pairBlock.size() : 0;
+  std::vector<int> chunkKF, chunkStart, chunkEnd, kfChunkStart(nKF + 1, 0);
+  for (int kf = 0; kf < nKF; ++kf) {
+    kfChunkStart[kf] = (int)chunkKF.size();
+    if (kfCol[kf] >= 0)
+      for (int k = kfStart[kf]; k < kfStart[kf + 1]; k += 64) { chunkKF.push_back(kf); chunkStart.push_back(k); chunkEnd.push_back(std::min(k + 64, kfStart[kf + 1])); }
+  }
+  kfChunkStart[nKF] = (int)chunkKF.size();
+  h.nChunks = (int)chunkKF.size();
+  bool fail = false;
+  // Memory: every array is carved from ONE device block — uploads first, gathered in a host staging buffer and sent in ONE copy, device-only
+  // arrays behind them — because ~45 hipMalloc / hipFree pairs and ~25 synchronous copies were 3.5 ms of a 4.7 ms call.  A dry run of the carve
+  // sizes the block.  The one-shot entry points (arena mode) take the block, the pinned staging buffer and the pinned words from the optimizer
+  // handle; a persistent problem (three-step API) owns its block and words.
+  bool dry = true;
+  size_t upOff = 0, devOff = 0, upCap = 0, devCap = 0;
+  char *aBase = nullptr, *stage = nullptr;
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    const size_t sz = (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255;
+    size_t& off = src ? upOff : devOff;
+    const size_t at = off;
+    off += sz;
+    if (dry) return nullptr;
+    if (off > (src ? upCap : devCap)) { fail = true; return nullptr; }
+    if (src) { memcpy(stage + at, src, bytes); return aBase + at; }
+    return aBase + upCap + at;
+  };
+  hipStream_t cst = o->stream;
+  auto carve = [&]() {
+  h.kfCol = (const int*)up(kfCol.data(), sizeof(int) * nKF);
+  h.eKF = (const int*)up(eKF, sizeof(int) * nE);
+  h.eMP = (const int*)up(eMP, sizeof(int) * nE);
+  h.eObs = (const float*)up(eObs, sizeof(float) * 3 * nE);
+  h.eInfo = (const float*)up(eInvSigma2, sizeof(float) * nE);
+  h.mpStart = (const int*)up(mpStart.data(), sizeof(int) * (nMP + 1));
+  h.mpEdges = (const int*)up(mpEdges.data(), sizeof(int) * nE);
+  h.kfStart = (const int*)up(kfStart.data(), sizeof(int) * (nKF + 1));
+  h.kfEdges = (const int*)up(kfEdges.data(), sizeof(int) * nE);
+  h.pairBlock = (const int*)up(pairBlock.data(), sizeof(int) * std::max<size_t>(pairBlock.size(), 1));
+  h.pairStart = (const int*)up(pairStart.data(), sizeof(int) * pairStart.size());
+  h.pairEntries = (const int2*)up(pairEntries.data(), sizeof(int2) * pairEntries.size());
+  p->nPairEntries = wantPairs ? pairEntries.size() : nPairEntriesCount;
+  h.chunkKF = (const int*)up(chunkKF.data(), sizeof(int) * std::max<size_t>(chunkKF.size(), 1));
+  h.chunkStart = (const int*)up(chunkStart.data(), sizeof(int) * std::max<size_t>(chunkStart.size(), 1));
+  h.chunkEnd = (const int*)up(chunkEnd.data(), sizeof(int) * std::max<size_t>(chunkEnd.size(), 1));
+  h.kfChunkStart = (const int*)up(kfChunkStart.data(), sizeof(int) * (nKF + 1));
+  h.kfPart = (double*)up(nullptr, sizeof(double) * 27 * std::max<size_t>(chunkKF.size(), 1));
+  p->d_ldws = (double*)up(nullptr, sizeof(double) * morbdense::global_panel_doubles(std::max(h.P, 1)));
+  p->redBlocks = div_up(std::max(std::max(nE, nMP * 16), std::max(nKF * 7, 1)), GB);   // (16 lanes per point in k_g_backsub_update_w)
+  h.redPart = (double*)up(nullptr, sizeof(double) * 2 * p->redBlocks);
+  h.scal = (double*)up(nullptr, sizeof(double) * 8);
+  {
+    const morbschur::Plan sp = morbschur::make_plan(h.P + 1, 3 * nMP);
+    p->schur = sp;
+    std::vector<int2> blocks; std::vector<int> blkIndex((size_t)sp.nb * sp.nb, 0);
+    for (int bi = 0; bi < sp.nb; ++bi) for (int bj = bi; bj < sp.nb; ++bj) { blkIndex[(size_t)bi * sp.nb + bj] = (int)blocks.size(); blocks.push_back(make_int2(bi, bj)); }
+    h.sW = (double*)up(nullptr, sizeof(double) * sp.wElems());
+    h.sWD = (double*)up(nullptr, sizeof(double) * sp.wElems());
+    if (!dry && !fail && (hipMemsetAsync(h.sW, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
+                          hipMemsetAsync(h.sWD, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess)) fail = true;
+    h.sPart = (double*)up(nullptr, sizeof(double) * sp.partElems());
+    h.sBlocks = (const int2*)up(blocks.data(), sizeof(int2) * blocks.size());
+    h.sBlkIndex = (const int*)up(blkIndex.data(), sizeof(int) * blkIndex.size());
+    h.sMp = sp.Mp; h.sNb = sp.nb; h.sNblk = sp.nblk; h.sNsplit = sp.nsplit;
+  }
+  const size_t nx = (size_t)h.P + 3 * (size_t)nMP;
+  h.pose = (double*)up(nullptr, sizeof(double) * 7 * nKF);
+  h.poseBk = (double*)up(nullptr, sizeof(double) * 7 * nKF);
+  h.poseEval = (double*)up(nullptr, sizeof(double) * 7 * nKF);
+  h.pt = (double*)up(nullptr, sizeof(double) * 3 * nMP);
+  h.ptBk = (double*)up(nullptr, sizeof(double) * 3 * nMP);
+  h.ptEval = (double*)up(nullptr, sizeof(double) * 3 * nMP);
+  h.Hpp = (double*)up(nullptr, sizeof(double) * 36 * std::max(nFree, 1));
+  h.Hll = (double*)up(nullptr, sizeof(double) * 9 * nMP);
+  h.Dinv = (double*)up(nullptr, sizeof(double) * 9 * nMP);
+  h.Hpl = (double*)up(nullptr, sizeof(double) * 18 * nE);
+  h.b = (double*)up(nullptr, sizeof(double) * nx);
+  h.x = (double*)up(nullptr, sizeof(double) * nx);
+  h.HsG = (double*)up(nullptr, sizeof(double) * std::max<size_t>((size_t)h.P * h.P, 1));
+  h.poseIO = (float*)up(nullptr, sizeof(float) * 7 * nKF);
+  h.ptIO = (float*)up(nullptr, sizeof(float) * 3 * nMP);
+  h.erase = (uint8_t*)up(nullptr, nE);
+  h.stats = (int*)up(nullptr, sizeof(int) * 2);
+  h.lmd = (double*)up(nullptr, sizeof(double) * 4);
+  h.kfTicket = (int*)up(nullptr, sizeof(int) * std::max(nKF, 1));
+  if (!dry && !fail && hipMemsetAsync(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1), cst) != hipSuccess) fail = true;
+  h.lmi = (int*)up(nullptr, sizeof(int) * 16);
+  // mapped host words: [0] morb_ba_set_stop, [1] the caller's *pbStopFlag as the host loop forwards it, [4..7] the LM state mirror
+  if (!dry) {
+    int *hw = nullptr, *dv = nullptr;
+    if (arena) { if (morb_optimizer_lm_words(o, &hw, &dv) != MORB_OK) fail = true; }
+    else if (p->words.alloc(sizeof(int) * 16, hipHostMallocMapped) != hipSuccess) fail = true;
+    else { hw = p->words; dv = p->words.dev(); }
+    if (hw) { memset(hw, 0, sizeof(int) * 16); p->h_stop = hw; h.stop = dv; h.lmHost = dv + 4; }
+  }
+  h.cam = Cam{fx, fy, cx, cy, bf};
+  h.rig = rig ? (const Rig*)up(rig, sizeof(Rig)) : nullptr;
+  h.userLambda = lambdaInit100 ? 100.0 : 0.0;
+  p->d_pose0 = (float*)up(kfPose, sizeof(float) * 7 * nKF);
+  p->d_pt0 = (float*)up(mpPos, sizeof(float) * 3 * nMP);
+  p->d_desc = (BaDev*)up(&h, sizeof(BaDev));
+  };   // carve
+  carve();   // (dry: sizes)
+  upCap = upOff; devCap = devOff; upOff = devOff = 0; dry = false;
+  std::vector<char> hostStage;   // a persistent problem's staging: pageable, the upload is waited for below
+  if (arena) {
+    if (grow(o->work, upCap + devCap, &aBase) != MORB_OK || grow(o->stage, upCap, &stage) != MORB_OK) fail = true;
+  } else {
+    if (p->mem.alloc(upCap + devCap) != hipSuccess) fail = true;
+    hostStage.resize(upCap);
+    aBase = (char*)p->mem.get(); stage = hostStage.data();
+  }
+  if (!fail) {
+    carve();
+    if (!fail && hipMemcpyAsync(aBase, stage, upCap, hipMemcpyHostToDevice, cst) != hipSuccess) fail = true;   // the one upload
+    // a persistent problem is complete when create returns (like the synchronous copies it was once made with): it may be solved on any stream
+    if (!fail && !arena && hipStreamSynchronize(cst) != hipSuccess) fail = true;
+  }
+  p->ldsBytes = sizeof(double) * (size_t)h.P * (h.P + 1);
+  p->useLds = (p->ldsBytes <= 136 * 1024 && h.P <= 192) ? 1 : 0;
+  if (!p->useLds) p->ldsBytes = 0;
+  p->denseLds = sizeof(double) * morbdense::lds_doubles(h.P);
+  if (p->denseLds > 156 * 1024 || h.P < 1) p->denseLds = 0;   // larger systems: the global-memory solver
+  if (!fail && p->denseLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_g_ldlt_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) fail = true;
+  p->globalLds = sizeof(double) * (morbdense::global_lds_doubles(std::max(h.P, 1)) + morbdense::global_panel_doubles(std::max(h.P, 1)));
+  p->panelInLds = p->globalLds <= 150 * 1024 ? 1 : 0;
+  if (!p->panelInLds) p->globalLds = sizeof(double) * morbdense::global_lds_doubles(std::max(h.P, 1));
+  if (!fail && !p->denseLds && (p->globalLds > 150 * 1024 ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_g_ldlt_global), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)) fail = true;
+  if (!fail && p->useLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_ba), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024) != hipSuccess)
+    fail = true;
+  if (fail) {
+    set_error("device allocation/copy failed while creating the BA problem");
+    return MORB_ERR_HIP;
+  }
+  *out = p.release();
+  return MORB_OK;
+}
+
+int morb_ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                           int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
+                           const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
+                           int lambdaInit100) {
+  return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf, lambdaInit100, nullptr, false);
+}
+
+void morb_ba_problem_destroy(morb_ba_problem* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->opt->device);
+  (void)hipStreamSynchronize(p->opt->stream);
+  if (p->solved) (void)hipEventSynchronize(p->solved);
+  delete p;
+}
+
+static int ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                                     int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs2,
+                                     const uint8_t* eRight, const float* eInvSigma2, const float* camL8, const float* camR8,
+                                     const float* Trl7, int lambdaInit100, bool arena) {
+  MORB_REQUIRE(out && eObs2 && eRight && camL8 && camR8 && Trl7, MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nE > 0, MORB_ERR_INVALID, "empty problem");
+  // the edge kind travels in the third observation slot: -2 = EdgeSE3ProjectXYZ with the left KB8 camera,
+  // -3 = EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl)
+  std::vector<float> obs3((size_t)nE * 3);
+  for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = eRight[e] ? -3.0f : -2.0f; }
+  const Rig rig = make_rig(camL8, camR8, Trl7);
+  return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, 0.f, 0.f, 0.f, 0.f, 0.f,
+                           lambdaInit100, &rig, arena);
+}
+
+int morb_ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
+                                   int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs2,
+                                   const uint8_t* eRight, const float* eInvSigma2, const float* camL8, const float* camR8,
+                                   const float* Trl7, int lambdaInit100) {
+  return ba_problem_create_fisheye(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs2, eRight, eInvSigma2, camL8, camR8, Trl7,
+                                   lambdaInit100, false);
+}
+
+int morb_ba_set_mode(morb_ba_problem* p, int mode) {
+  MORB_REQUIRE(p && (mode == 0 || mode == 1), MORB_ERR_INVALID, "mode must be 0 (grid) or 1 (persistent workgroup)");
+  p->mode = mode;
+  return MORB_OK;
+}
+
+int morb_ba_set_stop(morb_ba_problem* p, int stop) {
+  MORB_REQUIRE(p, MORB_ERR_INVALID, "NULL problem");
+  // No HIP call: the flag lives in pinned host memory that the device maps, so it lands while a solve is running on any
+  // stream (a copy on the null stream would wait for the very kernels it is meant to stop) and from any thread.
+  __atomic_store_n(p->h_stop, stop ? 1 : 0, __ATOMIC_RELEASE);
+  return MORB_OK;
+}
+
+int morb_ba_solve(morb_ba_problem* p, void* stream) {
+  MORB_REQUIRE(p, MORB_ERR_INVALID, "NULL problem");
+  MORB_ENTER(st, p->opt, stream);
+  MORB_HIP_CHECK(p->solved.create(hipEventDisableTiming));
+  struct RecordOnExit { hipEvent_t ev; hipStream_t st; ~RecordOnExit() { (void)hipEventRecord(ev, st); } } recordOnExit{p->solved, st};
+  const int n = std::max(p->h.nKF, p->h.nMP * 3);
+  hipLaunchKernelGGL(k_ba_reset, dim3(div_up(n, 256)), dim3(256), 0, st, p->h, p->d_pose0, p->d_pt0);
+  if (p->mode == 1) {
+    hipLaunchKernelGGL(k_local_ba, dim3(1), dim3(BA_T), p->ldsBytes, st, p->d_desc, p->useLds);
+    MORB_HIP_CHECK(hipGetLastError());
+    return MORB_OK;
+  }
+  const BaDev& h = p->h;
+  const BaDev* d = p->d_desc;
+  const int rb = p->redBlocks;
+  double* part0 = h.redPart;
+  double* part1 = h.redPart + rb;
+  {
+    // ---- grid mode, LM control flow on the device: the host queues trial after trial, one trial ahead of the decisions, and
+    // stops when the mapped `done` word says so; kernels queued behind the last decision return at once ----
+    const int kfBlocks = div_up(std::max(h.nChunks, 1), 4);
+    volatile int* hostw = p->h_stop;
+    auto forwardStop = [&]() { if (p->userStop && *p->userStop) __atomic_store_n(p->h_stop + 1, 1, __ATOMIC_RELEASE); };
+    __atomic_store_n(p->h_stop + 1, 0, __ATOMIC_RELAXED);
+    for (int k = 4; k < 8; ++k) __atomic_store_n(p->h_stop + k, 0, __ATOMIC_RELAXED);
+    forwardStop();
+    hipLaunchKernelGGL(k_g_chi2, dim3(rb), dim3(GB), 0, st, d, part0, (const double*)part1, 2);
+    constexpr int kAhead = 1;   // trials queued beyond the last decided one (the seven launches of a trial as one hipGraph: 0.89 -> 0.95 ms per solve, profiles/r04/README.md)
+    for (int slot = 0; slot < 100; ++slot) {
+      // buildSystem (runs only when the previous trial was accepted): keyframe chunks and map points in one launch
+      if (h.rig) hipLaunchKernelGGL(k_g_build<true>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, d, kfBlocks);
+      else hipLaunchKernelGGL(k_g_build<false>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, d, kfBlocks);
+      hipLaunchKernelGGL(k_g_dinv_push, dim3(rb > div_up(h.P * h.P, GB) ? rb : div_up(h.P * h.P, GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 0, 1);
+      hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(p->schur.nblk, p->schur.nsplit), dim3(64), 0, st, (const double*)h.sWD,
+                         (const double*)h.sW, p->schur.Mp, p->schur.ksteps, p->schur.stepsPerSplit, h.sBlocks, h.sPart, (const int*)(h.lmi + LM_DONE));
+      hipLaunchKernelGGL(k_g_schur_finish, dim3(div_up(4 * (h.P * h.P + h.P), GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 1);
+      if (p->denseLds) hipLaunchKernelGGL(k_g_ldlt_lds, dim3(1), dim3(morbdense::LT), p->denseLds, st, d, (const double*)h.HsG, 1);
+      else hipLaunchKernelGGL(k_g_ldlt_global, dim3(1), dim3(morbdense::GT), p->globalLds, st, d, h.HsG, p->d_ldws, p->panelInLds, 1);
+      hipLaunchKernelGGL(k_g_backsub_update_w, dim3(rb), dim3(GB), 0, st, d, part1);
+      hipLaunchKernelGGL(k_g_chi2, dim3(rb), dim3(GB), 0, st, d, part0, (const double*)part1, 1);
+      MORB_HIP_CHECK(hipGetLastError());
+      // wait until all but the last kAhead queued trials are decided (or the solve is done) on the mapped host words, backing off in tiers: a
+      // trial takes ~110 us, so the first ~30 us are `pause` spins (the decision of a short trial is picked up at once), then the thread yields
+      // its core between looks (LocalMapping's thread no longer holds a core against Tracking's for the whole solve), and a wait that outlasts
+      // 2 ms — a solve stuck behind other work on the device — sleeps 50 us at a time
+      unsigned spins = 0;
+      const auto tWait = std::chrono::steady_clock::now();
+      while (!__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 4, __ATOMIC_ACQUIRE) < slot + 1 - kAhead) {
+        forwardStop();
+        if ((++spins & 0x3FFu) == 0) {
+          const hipError_t q = hipStreamQuery(st);
+          if (q == hipSuccess) break;   // (everything queued has run: the words are final)
+          if (q != hipErrorNotReady) {  // a kernel fault: the words will never change
+            set_error("LocalBundleAdjustment: %s while waiting for the LM decision", hipGetErrorString(q));
+            return MORB_ERR_HIP;
+          }
+        }
+        if (spins < 2048) __builtin_ia32_pause();
+        else if ((spins & 0xFF) != 0 || std::chrono::steady_clock::now() - tWait < std::chrono::milliseconds(2)) sched_yield();
+        else { struct timespec ts = {0, 50000}; nanosleep(&ts, nullptr); }
+      }
+      if (__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE)) break;
+    }
+    hipLaunchKernelGGL(k_g_finish, dim3(rb), dim3(GB), 0, st, d, -1, -1);
+    MORB_HIP_CHECK(hipGetLastError());
+    // slot limit reached without a `done`: decisions of this solve may still be on their way — let them land before the next solve resets
+    // the mirror words (the usual exit has seen `done`, after which no kernel writes them)
+    if (!__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE)) MORB_HIP_CHECK(hipStreamSynchronize(st));
+    return MORB_OK;
+  }
+}
+
+int morb_ba_schur_profile(morb_ba_problem* p, int iters, float* msPerLaunch, double* flops, double* usefulFlops) {
+  MORB_REQUIRE(p && iters > 0 && msPerLaunch && flops && usefulFlops, MORB_ERR_INVALID, "bad argument");
+  MORB_HIP_CHECK(hipSetDevice(p->opt->device));
+  hipStream_t st = p->opt->stream;
+  morb::Event e0, e1;
+  MORB_HIP_CHECK(e0.create(hipEventDefault)); MORB_HIP_CHECK(e1.create(hipEventDefault));
+  const morbschur::Plan& sp = p->schur;
+  auto launch = [&]() { hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(sp.nblk, sp.nsplit), dim3(64), 0, st, (const double*)p->h.sWD, (const double*)p->h.sW, sp.Mp, sp.ksteps, sp.stepsPerSplit, p->h.sBlocks, p->h.sPart, (const int*)nullptr); };
+  launch();
+  MORB_HIP_CHECK(hipEventRecord(e0, st));
+  for (int i = 0; i < iters; ++i) launch();
+  MORB_HIP_CHECK(hipEventRecord(e1, st));
+  MORB_HIP_CHECK(hipEventSynchronize(e1));
+  float ms = 0;
+  MORB_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  *msPerLaunch = ms / iters;
+  *flops = 2.0 * sp.nblk * morbschur::SB * morbschur::SB * (double)sp.nsplit * sp.stepsPerSplit * 4;
+  *usefulFlops = 2.0 * 6 * 3 * (3 + 6) * (double)p->nPairEntries;   // per (e1, e2) entry: B1 D^-1 (6x3x3) and (B1 D^-1) B2^T (6x3x6)
+  return MORB_OK;
+}
+
+int morb_ba_results(morb_ba_problem* p, float* kfPose, float* mpPos, uint8_t* eraseFlag, int* stats2) {
+  MORB_REQUIRE(p, MORB_ERR_INVALID, "NULL problem");
+  MORB_HIP_CHECK(hipSetDevice(p->opt->device));
+  // the solve may have run on a caller's stream: wait for THAT stream (not for the device: with the reference's threading a tracked
+  // frame's optimisation on another handle must not wait for this solve, nor this copy for it), then copy on the handle's own stream
+  // (a copy on the null stream would also wait for, and hold up, every other handle's blocking stream)
+  if (p->solved) MORB_HIP_CHECK(hipEventSynchronize(p->solved));
+  hipStream_t st = p->opt->stream;
+  if (kfPose) MORB_HIP_CHECK(hipMemcpyAsync(kfPose, p->h.poseIO, sizeof(float) * 7 * p->h.nKF, hipMemcpyDeviceToHost, st));
+  if (mpPos) MORB_HIP_CHECK(hipMemcpyAsync(mpPos, p->h.ptIO, sizeof(float) * 3 * p->h.nMP, hipMemcpyDeviceToHost, st));
+  if (eraseFlag) MORB_HIP_CHECK(hipMemcpyAsync(eraseFlag, p->h.erase, p->h.nE, hipMemcpyDeviceToHost, st));
+  if (stats2) MORB_HIP_CHECK(hipMemcpyAsync(stats2, p->h.stats, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipStreamSynchronize(st));
+  return MORB_OK;
+}
+
+// the one-shot LocalBundleAdjustment behind its create call (p lives in the handle's workspace for the duration of the call)
+static int local_ba_solve_once(morb_ba_problem* p, const unsigned char* stopFlag, float* kfPose, float* mpPos, uint8_t* eraseFlag, int* stats2) {
+  p->userStop = stopFlag;   // optimizer.setForceStopFlag(pbStopFlag) (:1142): the LM loop polls the caller's flag at every iteration and trial
+  int rc = morb_ba_solve(p, nullptr);
+  if (rc == MORB_OK) rc = morb_ba_results(p, kfPose, mpPos, eraseFlag, stats2);
+  morb_ba_problem_destroy(p);
+  return rc;
+}
+
+int morb_local_bundle_adjustment(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
+                                 int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                                 float fx, float fy, float cx, float cy, float bf, int lambdaInit100,
+                                 const unsigned char* stopFlag, uint8_t* eraseFlag, int* stats2) {
+  if (stopFlag && *(const volatile unsigned char*)stopFlag) { if (stats2) stats2[0] = stats2[1] = 0; return MORB_OK; }  // :1355-1356
+  morb_ba_problem* p = nullptr;
+  const int rc = ba_problem_create(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, fx, fy, cx, cy, bf, lambdaInit100,
+                                   nullptr, true);
+  return rc != MORB_OK ? rc : local_ba_solve_once(p, stopFlag, kfPose, mpPos, eraseFlag, stats2);
+}
+
+int morb_local_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
+                                         int nE, const int* eKF, const int* eMP, const float* eObs2, const uint8_t* eRight,
+                                         const float* eInvSigma2, const float* camL8, const float* camR8, const float* Trl7,
+                                         int lambdaInit100, const unsigned char* stopFlag, uint8_t* eraseFlag, int* stats2) {
+  if (stopFlag && *(const volatile unsigned char*)stopFlag) { if (stats2) stats2[0] = stats2[1] = 0; return MORB_OK; }  // :1355-1356
+  morb_ba_problem* p = nullptr;
+  const int rc = ba_problem_create_fisheye(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs2, eRight, eInvSigma2, camL8, camR8, Trl7,
+                                           lambdaInit100, true);
+  return rc != MORB_OK ? rc : local_ba_solve_once(p, stopFlag, kfPose, mpPos, eraseFlag, stats2);
+}
+
+}  // extern "C"

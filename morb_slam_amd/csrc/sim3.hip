@@ -23,6 +23,7 @@
 #include "handles.h"
 #include "libm_f32.h"
 #include "libm_f64.h"
+#include "quat_huber.h"
 
 namespace {
 
@@ -37,14 +38,6 @@ struct Sim3d { double q[4]; double t[3]; double s; };   // q = x y z w
 struct Cam9 { int kb8; float p[8]; };                   // pinhole: fx fy cx cy; KB8: fx fy cx cy k1 k2 k3 k4
 
 // ---- Eigen / g2o Sim3 algebra ------------------------------------------------------------------------------
-__device__ __forceinline__ void q_rotate(const double* q, const double* v, double* out) {   // QuaternionBase::_transformVector
-  const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-  double a = uy * v[2] - uz * v[1], b = uz * v[0] - ux * v[2], c = ux * v[1] - uy * v[0];
-  a += a; b += b; c += c;
-  out[0] = v[0] + w * a + (uy * c - uz * b);
-  out[1] = v[1] + w * b + (uz * a - ux * c);
-  out[2] = v[2] + w * c + (ux * b - uy * a);
-}
 __device__ __forceinline__ void q_mul(const double* p, const double* o, double* r) {   // quat_product (generic)
   r[3] = p[3] * o[3] - p[0] * o[0] - p[1] * o[1] - p[2] * o[2];
   r[0] = p[3] * o[0] + p[0] * o[3] + p[1] * o[2] - p[2] * o[1];
@@ -94,12 +87,6 @@ __device__ __forceinline__ Sim3d sim3_inverse(const Sim3d& S) {   // Sim3(r.conj
   q_rotate(r.q, v, r.t);
   r.s = 1. / S.s;
   return r;
-}
-// pow(x, 3) as glibc rounds it (~0.52 ulp): error-free products through FMA, then one sum (x * x * x carries two roundings)
-__device__ __forceinline__ double cube_rn(double x) {
-  const double p = x * x, e = __builtin_fma(x, x, -p);
-  const double q = p * x, f = __builtin_fma(p, x, -q);
-  return q + (f + e * x);
 }
 // Sim3(const Vector7d& update) (types/sim3.h); s = exp(update[6]) is passed in
 __device__ Sim3d sim3_exp(const double* u, double s) {
@@ -185,14 +172,6 @@ __device__ __forceinline__ void edge_error(const Sim3d& S, int dir, const double
   }
 }
 __device__ __forceinline__ double chi2_of(const double* e, double info) { return e[0] * (info * e[0]) + e[1] * (info * e[1]); }
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): returns rho[0], *w = rho[1]
-__device__ __forceinline__ double huber(double delta, double e, double* w) {
-  const double dsqr = delta * delta;
-  if (e <= dsqr) { *w = 1.0; return e; }
-  const double sqrte = sqrt(e);
-  *w = delta / sqrte;
-  return 2 * sqrte * delta - dsqr;
-}
 // the perturbed estimate Sim3(+-delta e_d) * S of linearizeOplus (VertexSim3Expmap::oplusImpl: update[6] = 0 with a fixed scale)
 __device__ __forceinline__ Sim3d perturbed(const Sim3d& S, int d, bool plus, bool fixScale) {
   double u[7] = {0, 0, 0, 0, 0, 0, 0};
