@@ -77,11 +77,14 @@ int morb_extract_batch(morb_extractor*, const uint8_t* d_images, int nimg, int w
 
 /* std::vector<cv::Mat> mvImagePyramid (public member, ORBextractor.h:76; read by
  * Frame::ComputeStereoMatches, Frame.cc:895,974,987).  Level `lvl` of image `img` of the last batch:
- * *d_ptr points at the interior origin (the cv::Mat ROI), the 19-px BORDER_REFLECT_101 pad surrounds it in
- * the same allocation, *stride is the row pitch. */
+ * *d_ptr points at the interior origin (the cv::Mat ROI), *stride is the row pitch.  Of the reference's 19-px
+ * BORDER_REFLECT_101 pad only the innermost 3 pixels — the ones the 7 x 7 blur reads — surround the interior in the
+ * allocation; the other 16 are read by nothing and are not stored. */
 int morb_extractor_pyramid_level(const morb_extractor*, int img, int lvl, const uint8_t** d_ptr, int* width,
                                  int* height, int* stride);
-/* Same, copied to host, including the pad: out is (height+38) x (width+38) contiguous. */
+/* Same, copied to host with the reference's full pad: out is (height+38) x (width+38) contiguous.  The stored
+ * (height+6) x (width+6) block is copied into the middle as it is; the outer 16-px ring is reconstructed on the host
+ * by BORDER_REFLECT_101 of the interior. */
 int morb_extractor_pyramid_level_host(const morb_extractor*, int img, int lvl, uint8_t* out_padded);
 /* Debug/parity taps on the last batch (host copies): blurred level (height x width contiguous), FAST
  * candidates of a level in vToDistributeKeys order, keypoints of a level after DistributeOctTree. */

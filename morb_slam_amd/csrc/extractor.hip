@@ -6,8 +6,9 @@
 // rotation, pt *= scale) must round exactly like the reference's separate mul/add.
 //
 // HBM layout (level-major slabs; one batch = nimg images of one size):
-//   pyramid : for level l, image i : (h_l + 38) rows x pstride_l bytes, 19-px BORDER_REFLECT_101 pad included
-//             (= mvImagePyramid[l] with its pad, ORBextractor.cc:1088-1112); pstride_l is a multiple of 64.
+//   pyramid : for level l, image i : (h_l + 6) rows x pstride_l bytes = mvImagePyramid[l] (ORBextractor.cc:1088-1112) with the
+//             innermost kPyrPad = 3 pixels of its 19-px BORDER_REFLECT_101 pad, the only ones anything reads (pyramid_layout.h);
+//             pstride_l is a multiple of 64.
 //   blur    : for level l, image i : h_l rows x bstride_l bytes (GaussianBlur 7x7 s=2 of the level, :1049-1050)
 //   cand    : per image, per FAST cell (all levels, flat cell index): cellCap packed keys + a count
 //   sel     : per image, per level: keys chosen by DistributeOctTree, in the reference's list order
@@ -74,7 +75,7 @@ __constant__ int c_umax[16];
 // ---------------------------------------------------------------------------------------------------
 // K1a: level 0 = copyMakeBorder(image, BORDER_REFLECT_101)  (ORBextractor.cc:1108)
 __device__ __forceinline__ int reflect101(int p, int len) {
-  // one reflection is enough for |pad| = 19 < len
+  // one reflection is enough for |pad| <= 19 < len
   if (p < 0) p = -p;
   if (p >= len) p = 2 * (len - 1) - p;
   return p;
@@ -106,8 +107,8 @@ __device__ __forceinline__ PyTile py_tile() {
   return r;
 }
 // K1b: level l = resize(level l-1, INTER_LINEAR) + copyMakeBorder(BORDER_REFLECT_101|ISOLATED)
-// (ORBextractor.cc:1101-1104).  Every padded pixel is computed directly from level l-1 through tables that
-// already fold the reflection, so one launch writes interior and pad.
+// (ORBextractor.cc:1101-1104).  Every stored pixel — the interior and the kPyrPad border pixels around it — is computed
+// directly from level l-1 through tables that already fold the reflection, so one launch writes interior and pad.
 __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
   uint32_t v;
   __builtin_memcpy(&v, p, 4);
@@ -119,13 +120,13 @@ __global__ __launch_bounds__(256) void k_resize_gather(uint8_t* __restrict__ pyr
                                                        const ResizeTab* __restrict__ xtab, const ResizeTab* __restrict__ ytab, int img0) {
   PyTile pt = py_tile();
   pt.img += img0;   // (the launch covers images img0 .. img0 + gridDim.z - 1)
-  const uint8_t* sbase = pyr + gs.pyrOff + (size_t)pt.img * gs.pyrImg + (size_t)EDGE * gs.pstride + EDGE;
+  const uint8_t* sbase = pyr + gs.pyrOff + (size_t)pt.img * gs.pyrImg + (size_t)kPyrPad * gs.pstride + kPyrPad;
   const int px = (pt.bx * 64 + (threadIdx.x & 63)) * 4;
   const int py0 = (pt.by * 4 + (threadIdx.x >> 6)) * PY_ROWS;
-  const int H = gd.h + 2 * EDGE;
+  const int H = gd.h + 2 * kPyrPad;
   if (px >= gd.pstride || py0 >= H) return;
   ResizeTab tx[4];
-  const int pxc = px < gd.w + 2 * EDGE ? px : gd.w + 2 * EDGE - 1;
+  const int pxc = px < gd.w + 2 * kPyrPad ? px : gd.w + 2 * kPyrPad - 1;
 #pragma unroll
   for (int k = 0; k < 4; ++k) tx[k] = xtab[pxc + k];
   uint8_t* dbase = pyr + gd.pyrOff + (size_t)pt.img * gd.pyrImg + px;
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(256) void k_resize(uint8_t* __restrict__ pyr, unsig
   resize_items(pyr + sOff + (size_t)pt.img * sImg, sstride, pyr + a.dOff + (size_t)pt.img * a.dImg, a, pt.bx, reinterpret_cast<PyrRow*>(pyr_smem));
 }
 
-// Level 0 = copyMakeBorder(image, 19, BORDER_REFLECT_101), as items of two kinds: "interior" = one aligned 16-byte destination chunk
+// Level 0 = the stored part (kPyrPad pixels) of copyMakeBorder(image, 19, BORDER_REFLECT_101), as items of two kinds: "interior" = one aligned 16-byte destination chunk
 // whose sixteen source pixels are consecutive (one unaligned 16-byte load — the caller's image has whatever alignment it has —, one 16-byte store) x P0R rows, and "edge" = one destination
 // dword of the reflected pad (or of the ragged ends of the interior) x P0R rows, a dword load + v_perm_b32 with a host-made selector.
 struct Level0Args {
@@ -243,7 +244,7 @@ __device__ __forceinline__ void level0_items(const uint8_t* __restrict__ src, in
 #pragma unroll
       for (int r = 0; r < P0R; ++r) {
         const int py = min(g * P0R + r, a.H - 1);
-        __builtin_memcpy(&v[r], src + (uint32_t)(__umul24(reflect101(py - EDGE, a.h), stride) + 16 * j - EDGE), 16);
+        __builtin_memcpy(&v[r], src + (uint32_t)(__umul24(reflect101(py - kPyrPad, a.h), stride) + 16 * j - kPyrPad), 16);
       }
 #pragma unroll
       for (int r = 0; r < P0R; ++r)
@@ -256,7 +257,7 @@ __device__ __forceinline__ void level0_items(const uint8_t* __restrict__ src, in
 #pragma unroll
       for (int r = 0; r < P0R; ++r) {
         const int py = min(g * P0R + r, a.H - 1);
-        __builtin_memcpy(&w[r], src + (uint32_t)(__umul24(reflect101(py - EDGE, a.h), stride) + pe.base), 4);
+        __builtin_memcpy(&w[r], src + (uint32_t)(__umul24(reflect101(py - kPyrPad, a.h), stride) + pe.base), 4);
       }
 #pragma unroll
       for (int r = 0; r < P0R; ++r)
@@ -271,12 +272,12 @@ __global__ __launch_bounds__(256) void k_level0(const uint8_t* __restrict__ src,
 
 // ---------------------------------------------------------------------------------------------------
 // K5: GaussianBlur(7x7, sigma 2, BORDER_REFLECT_101), OpenCV fixed-point path: 8.8 kernel
-// {18,34,48,56,48,34,18}, row pass exact, column pass rounded (+0.5) to u8.  The level's own 19-px
+// {18,34,48,56,48,34,18}, row pass exact, column pass rounded (+0.5) to u8.  The level's stored 3-px
 // reflect-101 pad is exactly the border the blur needs, so the tile loads straight from the padded pyramid.
 // v2: no LDS.  A thread owns a 4-pixel-wide column strip and walks down BT_ROWS rows keeping the last seven
 // row-pass results (4 x u16, packed in two dwords) in registers; every output dword (4 pixels) needs three
-// aligned dword loads of the source row (bytes x-3 .. x+8; the interior starts 19 bytes into the padded row and
-// 19 - 3 = 16, so x % 4 == 0 makes the window 4-byte aligned).  HBM traffic = read P (+halo rows) + write P.
+// aligned dword loads of the source row (bytes x-3 .. x+8; the interior starts kPyrPad = 3 bytes into the stored row and
+// 3 - 3 = 0, so x % 4 == 0 makes the window 4-byte aligned).  HBM traffic = read P (+halo rows) + write P.
 #ifndef MORB_BT_ROWS
 #define MORB_BT_ROWS 24   // rows per strip (round 4, B = 512, blur underneath the quadtree: 16 / 24 / 32 rows -> 131.9 / 132.9 / 132.0 k frames/s: fewer halo rows against emptier tiles)
 #endif
@@ -359,8 +360,8 @@ __global__ __launch_bounds__(256, MORB_BLUR_MIN_WAVES) void k_blur(const LevelGe
   const int x = tx * BT_W + (threadIdx.x & 31) * 8;
   const int y0 = ty * BT_H + (threadIdx.x >> 5) * BT_ROWS;
   if (x >= g.w || y0 >= g.h) return;
-  // padded-row origin of this strip: row (y + 19 - 3), byte (19 + x - 3) = 16 + x
-  const uint8_t* src = pyr + g.pyrOff + (size_t)img * g.pyrImg + (size_t)(EDGE + y0 - 3) * g.pstride + (EDGE - 3) + x;
+  // stored-row origin of this strip: row (y + kPyrPad - 3), byte (kPyrPad + x - 3) = x
+  const uint8_t* src = pyr + g.pyrOff + (size_t)img * g.pyrImg + (size_t)(kPyrPad + y0 - 3) * g.pstride + (kPyrPad - 3) + x;
   uint8_t* dst = blur + g.blurOff + (size_t)img * g.blurImg + (size_t)y0 * g.bstride + x;
   uint32_t P[5][8], hl[8];   // P[j] = rows (y + j, y + j + 1) of the horizontal sums, hl = row y + 5
   {
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(256, MORB_BLUR_MIN_WAVES) void k_blur(const LevelGe
   // Rows past the bottom of the level (the last strip of a tile column) are computed like the others — from the last padded row, so no
   // load leaves the level — and only their store is skipped: with the whole row body under `if (r < rows)` (per-lane: the two halves of a
   // wave work different strips) the compiler merged the rotating row window through 688 v_mov per wave, a third of the kernel's VALU work.
-  const int lastRow = g.h + 2 * EDGE - 1 - (EDGE + y0 - 3);   // last padded row, relative to src
+  const int lastRow = g.h + 2 * kPyrPad - 1 - (kPyrPad + y0 - 3);   // last stored row, relative to src
   // The source rows are requested BT_AHEAD rows before they are used: with the load at the top of the row that needs it the wave sat
   // through a full memory round trip per row (load, s_waitcnt vmcnt(0), 75 VALU instructions, store — sixteen times), at five waves per SIMD.
   uint4 wq[BT_AHEAD];
@@ -814,7 +815,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     cx[kk] = morbqt::key_x(key) + MINB; cy[kk] = morbqt::key_y(key) + MINB;
     // top-left corners of the 31 x 31 moment patch and of the (2 * EDGE + 1)^2 window the rotated pattern stays inside:
     // the lanes add unsigned 32-bit offsets (scalar base + vector offset addressing)
-    ctr[kk] = pyr + dg.pyrOff[l] + (size_t)img * dg.pyrImg[l] + (size_t)(EDGE + cy[kk] - HALF_PATCH) * pstride[kk] + EDGE + cx[kk] - HALF_PATCH;
+    ctr[kk] = pyr + dg.pyrOff[l] + (size_t)img * dg.pyrImg[l] + (size_t)(kPyrPad + cy[kk] - HALF_PATCH) * pstride[kk] + kPyrPad + cx[kk] - HALF_PATCH;
     center[kk] = blur + dg.blurOff[l] + (size_t)img * dg.blurImg[l] + (ptrdiff_t)(cy[kk] - DESC_R) * bstride[kk] + cx[kk] - DESC_R;
 #if MORB_DESC_STAGED
     // the window is fetched from the dword boundary below its left edge (blurred rows are 64-byte aligned, a keypoint sits at x >= 19):
@@ -1010,23 +1011,24 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
   std::vector<ResizeTab> tabs;
   std::vector<PyrCol> pcols; std::vector<PyrRow> prows; std::vector<PyrEdge> pedges;
   bool pyrPacked = true;
-  size_t pyrOff = 0, blurOff = 0, qtOff = 0;
+  size_t blurOff = 0, qtOff = 0;
   int cellBase = 0, selBase = 0, blurTileBase = 0;
   e->cellCap = 0; e->maxCells = 0; e->maxNodeCap = 0; e->maxListCap = 0;
   std::vector<FastSeg> segs;
   LevelGeom teamGeom[kMaxLevels];
   memset(teamGeom, 0, sizeof teamGeom);
+  PyrLevelLayout pyrLay[kMaxLevels];
+  const unsigned long long pyrTotal = pyr_layout(W, H, e->invScale.data(), L, nimg, pyrLay);   // d_pyr: pyramid_layout.h
   for (int l = 0; l < L; ++l) {
     LevelGeom& g = e->geom[l];
     memset(&g, 0, sizeof g);
-    const float s = e->invScale[l];
-    g.w = cvRoundF((float)W * s);  // ORBextractor.cc:1091-1092
-    g.h = cvRoundF((float)H * s);
+    g.w = pyrLay[l].w;  // ORBextractor.cc:1091-1092
+    g.h = pyrLay[l].h;
     MORB_REQUIRE(g.w >= 2 * EDGE + 35 + 3 && g.h >= 2 * EDGE + 35 + 3 && g.w <= 4095 && g.h <= 4095, MORB_ERR_UNSUPPORTED,
                  "image size unsupported: every pyramid level must be between 76 and 4095 px in each dimension");
-    g.pstride = (int)align_up((size_t)g.w + 2 * EDGE, 64);
+    g.pstride = pyrLay[l].pstride;
     g.bstride = (int)align_up((size_t)g.w, 64);
-    g.pyrOff = pyrOff; g.pyrImg = (size_t)(g.h + 2 * EDGE) * g.pstride; pyrOff += g.pyrImg * nimg;
+    g.pyrOff = pyrLay[l].off; g.pyrImg = pyrLay[l].img;
     g.blurOff = blurOff; g.blurImg = (size_t)g.h * g.bstride; blurOff += g.blurImg * nimg;
     g.maxBorderX = g.w - EDGE + 3; g.maxBorderY = g.h - EDGE + 3;  // :748-749
     const float width = (float)(g.maxBorderX - MINB), height = (float)(g.maxBorderY - MINB);
@@ -1043,7 +1045,7 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
         int tw = std::min(X0 + g.wCell + 6, g.maxBorderX) - X0, th = std::min(iniY + g.hCell + 6, g.maxBorderY) - iniY;
         if (iniY >= g.maxBorderY - 3 || tw <= 6 || th <= 6) tw = th = 0;   // ORBextractor.cc:770, :775
         FastSeg sd;
-        sd.winOff = (unsigned)((size_t)(EDGE + iniY) * g.pstride + EDGE + X0);
+        sd.winOff = (unsigned)((size_t)(kPyrPad + iniY) * g.pstride + kPyrPad + X0);
         sd.cell0 = g.cellBase + ci * g.nCols + c0;
         sd.geo = l | (1 << 8) | (tw << 16) | (int)((unsigned)th << 24);
         sd.key0 = (c0 * g.wCell) | ((ci * g.hCell) << 16);
@@ -1071,7 +1073,7 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
     g.qtImg = 2ull * g.nCols * g.nRows * e->cellCap;
     g.qtOff = qtOff; qtOff += g.qtImg * nimg;
   }
-  // resize tables in padded destination coordinates (imgproc/resize.cpp coefficient set-up, see oracle)
+  // resize tables in stored destination coordinates: interior + kPyrPad on either side (imgproc/resize.cpp coefficient set-up, see oracle)
   for (int l = 1; l < L; ++l) {
     LevelGeom& g = e->geom[l];
     const LevelGeom& gs = e->geom[l - 1];
@@ -1096,8 +1098,8 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
         t.c1 = (short)std::min(std::max(cvRoundF(f * ONE), -32768), 32767);
         interior[d] = t;
       }
-      for (int p = 0; p < dn + 2 * EDGE + PY_ROWS; ++p) {   // (PY_ROWS repeats of the last entry: k_resize reads whole groups unclamped)
-        int q = std::min(p, dn + 2 * EDGE - 1) - EDGE;
+      for (int p = 0; p < dn + 2 * kPyrPad + PY_ROWS; ++p) {   // (PY_ROWS repeats of the last entry: k_resize reads whole groups unclamped)
+        int q = std::min(p, dn + 2 * kPyrPad - 1) - kPyrPad;
         if (q < 0) q = -q;
         if (q >= dn) q = 2 * (dn - 1) - q;
         out.push_back(interior[q]);
@@ -1107,7 +1109,7 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
     g.ytabOff = (int)tabs.size(); build(g.h, gs.h, false, tabs);
     // k_resize's item tables: one PyrCol per destination dword, one PyrRow per destination row (padded to whole groups of PR)
     PyrLevel& pl = e->pyrLv[l];
-    pl.nC = div_up(g.w + 2 * EDGE, 4); pl.nG = div_up(g.h + 2 * EDGE, PR); pl.nItems = pl.nC * pl.nG;
+    pl.nC = div_up(g.w + 2 * kPyrPad, 4); pl.nG = div_up(g.h + 2 * kPyrPad, PR); pl.nItems = pl.nC * pl.nG;
     pl.magicC = (uint32_t)((1ull << 32) / (unsigned)pl.nC + 1);
     MORB_REQUIRE((unsigned long long)pl.nItems * (unsigned)pl.nC < (1ull << 32), MORB_ERR_UNSUPPORTED, "pyramid level too large for the item index arithmetic");
     pl.ldsRows = (255 / pl.nC + 2) * PR;
@@ -1115,12 +1117,13 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
     const ResizeTab* xt = tabs.data() + g.xtabOff; const ResizeTab* yt = tabs.data() + g.ytabOff;
     for (int c = 0; c < pl.nC; ++c) {
       ResizeTab t4[4];
-      for (int k = 0; k < 4; ++k) t4[k] = xt[std::min(4 * c + k, g.w + 2 * EDGE - 1)];
+      for (int k = 0; k < 4; ++k) t4[k] = xt[std::min(4 * c + k, g.w + 2 * kPyrPad - 1)];
       int base = t4[0].s0, top = t4[0].s0;
       for (int k = 0; k < 4; ++k) { base = std::min(base, (int)std::min(t4[k].s0, t4[k].s1)); top = std::max(top, (int)std::max(t4[k].s0, t4[k].s1)); }
       if (top - base >= 8) pyrPacked = false;
-      // the window as three aligned dwords of the source's padded row (the interior starts EDGE bytes into it; rows are 64-byte aligned)
-      PyrCol pc; pc.base = (EDGE + base) & ~3; pc.sh = (EDGE + base) & 3; pc.pad_[0] = pc.pad_[1] = 0;
+      // the window as three aligned dwords of the source's stored row (the interior starts kPyrPad bytes into it; rows are 64-byte aligned)
+      PyrCol pc; pc.base = (kPyrPad + base) & ~3; pc.sh = (kPyrPad + base) & 3; pc.pad_[0] = pc.pad_[1] = 0;
+      MORB_REQUIRE(base >= 0 && base < gs.w, MORB_ERR_UNSUPPORTED, "resize window outside the source level");   // (pyr_resize_extent assumes it)
       for (int k = 0; k < 4; ++k) {
         pc.sel[k] = (uint32_t)((t4[k].s0 - base) & 7) | 0x0C00u | (uint32_t)((t4[k].s1 - base) & 7) << 16 | 0x0C000000u;
         pc.coef[k] = (uint32_t)(uint16_t)t4[k].c0 | (uint32_t)(uint16_t)t4[k].c1 << 16;
@@ -1129,25 +1132,25 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
       pcols.push_back(pc);
     }
     for (int r = 0; r < pl.nG * PR; ++r) {
-      const ResizeTab t = yt[std::min(r, g.h + 2 * EDGE - 1)];
+      const ResizeTab t = yt[std::min(r, g.h + 2 * kPyrPad - 1)];
       PyrRow pr; pr.s0 = t.s0; pr.s1 = t.s1; pr.c0s = (uint32_t)t.c0 << 12; pr.c1s = (uint32_t)t.c1 << 12;
       if (t.c0 < 0 || t.c1 < 0) pyrPacked = false;
       prows.push_back(pr);
     }
   }
   {
-    // level 0 = the image plus its reflected pad: interior 16-byte chunks and edge dwords (k_level0)
+    // level 0 = the image plus the stored part of its reflected pad: interior 16-byte chunks and edge dwords (k_level0)
     const LevelGeom& g0 = e->geom[0];
     PyrLevel0& p0 = e->pyrL0;
-    const int nC0 = div_up(g0.w + 2 * EDGE, 4);               // destination dwords per row
-    p0.j0 = div_up(EDGE, 16);                                  // first 16-byte chunk that lies wholly inside the image
-    p0.nInt = std::max(0, (EDGE + g0.w) / 16 - p0.j0);
-    p0.nG = div_up(g0.h + 2 * EDGE, P0R);
+    const int nC0 = div_up(g0.w + 2 * kPyrPad, 4);            // destination dwords per row
+    p0.j0 = div_up(kPyrPad, 16);                                 // first 16-byte chunk that lies wholly inside the image
+    p0.nInt = std::max(0, (kPyrPad + g0.w) / 16 - p0.j0);
+    p0.nG = div_up(g0.h + 2 * kPyrPad, P0R);
     for (int d = 0; d < nC0; ++d) {
       if (d >= 4 * p0.j0 && d < 4 * (p0.j0 + p0.nInt)) continue;
       int xs[4], base = 1 << 30;
       for (int k = 0; k < 4; ++k) {
-        int q = 4 * d + k - EDGE;
+        int q = 4 * d + k - kPyrPad;
         if (q < 0) q = -q;
         if (q >= g0.w) q = 2 * (g0.w - 1) - q;
         xs[k] = q; base = std::min(base, q);
@@ -1187,7 +1190,7 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
 
   e->selPerImg = selBase;
   e->blurTiles = blurTileBase;
-  e->pyrBytes = pyrOff; e->blurBytes = blurOff; e->qtElems = qtOff;
+  e->pyrBytes = pyrTotal; e->blurBytes = blurOff; e->qtElems = qtOff;
   e->outCap = selBase;
   // Candidate keys of a level live in LDS (two arrays) when they fit, else in the global scratch (much slower: every partition pass goes
   // through the L2).  Level 0's capacity scales with its area — twice the ~1 candidate per 233 px the benchmark images give, i.e. the
@@ -1297,8 +1300,8 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
   if (!prows.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_prow, prows.data(), sizeof(PyrRow) * prows.size(), hipMemcpyHostToDevice));
   MORB_HIP_CHECK(e->d_pedge.alloc(sizeof(PyrEdge) * std::max<size_t>(pedges.size(), 1)));
   if (!pedges.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_pedge, pedges.data(), sizeof(PyrEdge) * pedges.size(), hipMemcpyHostToDevice));
-  MORB_HIP_CHECK(e->d_pyr.alloc(e->pyrBytes + 256));
-  MORB_HIP_CHECK(hipMemset(e->d_pyr, 0, e->pyrBytes + 256));   // (the alignment slack behind each row is never written; other kernels' wide loads may touch it)
+  MORB_HIP_CHECK(e->d_pyr.alloc(e->pyrBytes + kPyrTail));
+  MORB_HIP_CHECK(hipMemset(e->d_pyr, 0, e->pyrBytes + kPyrTail));   // (the alignment slack behind each row is never written; other kernels' wide loads may touch it)
   MORB_HIP_CHECK(e->d_blur.alloc(e->blurBytes + 256));
   MORB_HIP_CHECK(e->d_cand.alloc(sizeof(uint32_t) * (size_t)nimg * e->totalCells * e->cellCap));
   MORB_HIP_CHECK(e->d_candCnt.alloc(sizeof(int) * (size_t)nimg * e->totalCells));
@@ -1327,6 +1330,8 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
                    : reinterpret_cast<const void*>(k_fastw<80>);
     MORB_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
   }
+  // no reader of d_pyr leaves [d_pyr, d_pyr + pyrBytes + kPyrTail): the wide loads that run past a row end in the next row, block or the tail
+  MORB_REQUIRE(pyr_extents_ok(pyrLay, L, nimg, e->pyrBytes, e->fastP, !e->pyrPacked), MORB_ERR_UNSUPPORTED, "pyramid layout: a kernel's loads would leave the buffer");
   e->W = W; e->H = H; e->nimgCap = nimg;
   return MORB_OK;
 }
@@ -1523,12 +1528,12 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
     const PyrLevel0& p0 = e->pyrL0;
     Level0Args a0;
     a0.edge = e->d_pedge; a0.nInt = p0.nInt; a0.j0 = p0.j0; a0.nEdge = p0.nEdge; a0.nIntItems = p0.nIntItems; a0.nItems = p0.nItems;
-    a0.H = g0.h + 2 * EDGE; a0.h = g0.h; a0.dpstride = g0.pstride; a0.magicInt = p0.magicInt; a0.magicEdge = p0.magicEdge; a0.dOff = g0.pyrOff; a0.dImg = g0.pyrImg;
+    a0.H = g0.h + 2 * kPyrPad; a0.h = g0.h; a0.dpstride = g0.pstride; a0.magicInt = p0.magicInt; a0.magicEdge = p0.magicEdge; a0.dOff = g0.pyrOff; a0.dImg = g0.pyrImg;
     auto resize_args = [&](int l) {
       const LevelGeom& g = e->geom[l];
       const PyrLevel& pl = e->pyrLv[l];
       ResizeArgs a;
-      a.col = e->d_pcol + pl.colOff; a.row = e->d_prow + pl.rowOff; a.nC = pl.nC; a.nItems = pl.nItems; a.H = g.h + 2 * EDGE; a.dpstride = g.pstride;
+      a.col = e->d_pcol + pl.colOff; a.row = e->d_prow + pl.rowOff; a.nC = pl.nC; a.nItems = pl.nItems; a.H = g.h + 2 * kPyrPad; a.dpstride = g.pstride;
       a.magicC = pl.magicC; a.dOff = g.pyrOff; a.dImg = g.pyrImg;
       return a;
     };
@@ -1553,13 +1558,13 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
           ResizeArgs ra = resize_args(l);
           ra.dOff += (unsigned long long)i0 * ra.dImg;
           hipLaunchKernelGGL(k_resize, dim3(div_up(pl.nItems, 256), 1, ni), dim3(256), sizeof(PyrRow) * pl.ldsRows, st, e->d_pyr,
-                             gs.pyrOff + (unsigned long long)i0 * gs.pyrImg + (unsigned long long)EDGE * gs.pstride, gs.pyrImg, gs.pstride, ra);
+                             gs.pyrOff + (unsigned long long)i0 * gs.pyrImg + (unsigned long long)kPyrPad * gs.pstride, gs.pyrImg, gs.pstride, ra);
         }
       } else {
         hipLaunchKernelGGL(k_level0, dim3(div_up(p0.nItems, 256), 1, ni), dim3(256), 0, st, src, stride, image_pitch, e->d_pyr, a0c);
         for (int l = 1; l < L; ++l) {
           const LevelGeom& g = e->geom[l];
-          dim3 gr(div_up(g.pstride / 4, 64), div_up(g.h + 2 * EDGE, 4 * PY_ROWS), ni);
+          dim3 gr(div_up(g.pstride / 4, 64), div_up(g.h + 2 * kPyrPad, 4 * PY_ROWS), ni);
           hipLaunchKernelGGL(k_resize_gather, gr, dim3(256), 0, st, e->d_pyr, e->geom[l - 1], g, e->d_tabs + g.xtabOff, e->d_tabs + g.ytabOff, i0);
         }
       }
@@ -1697,7 +1702,7 @@ int morb_extractor_pyramid_level(const morb_extractor* e, int img, int lvl, cons
   MORB_REQUIRE(e && e->W > 0, MORB_ERR_INVALID, "no batch has been extracted yet");
   MORB_REQUIRE(lvl >= 0 && lvl < e->nlevels && img >= 0 && img < e->nimgLast, MORB_ERR_INVALID, "bad level/image");
   const LevelGeom& g = e->geom[lvl];
-  if (d_ptr) *d_ptr = e->d_pyr + g.pyrOff + (size_t)img * g.pyrImg + (size_t)EDGE * g.pstride + EDGE;
+  if (d_ptr) *d_ptr = e->d_pyr + g.pyrOff + (size_t)img * g.pyrImg + (size_t)kPyrPad * g.pstride + kPyrPad;
   if (width) *width = g.w;
   if (height) *height = g.h;
   if (stride) *stride = g.pstride;
@@ -1710,7 +1715,18 @@ int morb_extractor_pyramid_level_host(const morb_extractor* e, int img, int lvl,
   if (rc != MORB_OK) return rc;
   MORB_HIP_CHECK(hipSetDevice(e->device));
   MORB_HIP_CHECK(hipStreamSynchronize(e->stream));
-  MORB_HIP_CHECK(hipMemcpy2D(out, w + 2 * EDGE, p - (size_t)EDGE * s - EDGE, s, w + 2 * EDGE, h + 2 * EDGE, hipMemcpyDeviceToHost));
+  // `out` is the level with the reference's full 19-px pad.  The stored block — interior and kPyrPad border pixels, the bytes the blur
+  // reads — goes into its middle as it is; the outer ring, which no kernel computes, is filled here by BORDER_REFLECT_101 of the interior.
+  const int sw = w + 2 * kPyrPad, sh = h + 2 * kPyrPad, ow = w + 2 * EDGE, oh = h + 2 * EDGE, ring = EDGE - kPyrPad;
+  std::vector<uint8_t> stored((size_t)sw * sh);
+  MORB_HIP_CHECK(hipMemcpy2D(stored.data(), sw, p - (size_t)kPyrPad * s - kPyrPad, s, sw, sh, hipMemcpyDeviceToHost));
+  auto refl = [](int q, int len) { if (q < 0) q = -q; if (q >= len) q = 2 * (len - 1) - q; return q; };
+  for (int r = 0; r < oh; ++r)
+    for (int c = 0; c < ow; ++c) {
+      const bool isStored = r >= ring && r < ring + sh && c >= ring && c < ring + sw;
+      out[(size_t)r * ow + c] = isStored ? stored[(size_t)(r - ring) * sw + (c - ring)]
+                                         : stored[(size_t)(refl(r - EDGE, h) + kPyrPad) * sw + refl(c - EDGE, w) + kPyrPad];
+    }
   return MORB_OK;
 }
 

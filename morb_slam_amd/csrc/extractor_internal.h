@@ -8,10 +8,10 @@
 
 #include "hip_owned.h"
 #include "morb_hip.h"
+#include "pyramid_layout.h"   // EDGE (the algorithmic border), kPyrPad (the stored one), the layout of d_pyr
 
 namespace morb {
 constexpr int kMaxLevels = 16;
-constexpr int EDGE = 19;        // EDGE_THRESHOLD  ORBextractor.cc:73
 constexpr int HALF_PATCH = 15;  // HALF_PATCH_SIZE :72
 constexpr int PATCH = 31;       // PATCH_SIZE :71
 constexpr int MINB = 16;        // minBorderX/Y = EDGE_THRESHOLD - 3 (:746-747)
@@ -50,7 +50,7 @@ struct FastGeom {
 // k_fastw works cell by cell.  One descriptor per FAST cell of an image (all levels), built on the host, read with one scalar load
 // (the "segment" of round 2's kernel, which ran up to three cells per workgroup; the cell count field stays at 1).
 struct FastSeg {
-  unsigned winOff;   // byte offset of the window's top-left pixel inside the level's (padded) image
+  unsigned winOff;   // byte offset of the window's top-left pixel inside the level's stored block (pyramid_layout.h)
   int cell0;         // flat index of the segment's first cell within the image (cellBase + ci * nCols + c0)
   int geo;           // level | cells << 8 | window width << 16 | window height << 24 (width 0: nothing to evaluate)
   int key0;          // added to window coordinates to form candidate keys: c0 * wCell | (ci * hCell) << 16
@@ -63,7 +63,7 @@ struct DescGeom {
   float scale[kMaxLevels], kpSize[kMaxLevels];
 };
 
-struct alignas(8) ResizeTab {  // one entry per padded destination column / row (8-byte aligned: scalar loads need dword alignment)
+struct alignas(8) ResizeTab {  // one entry per stored destination column / row (interior + kPyrPad on either side) (8-byte aligned: scalar loads need dword alignment)
   short s0, s1, c0, c1;  // source index (clipped), source index + 1 (clipped), fixed-point weights (2048 = 1)
 };
 

@@ -27,7 +27,6 @@ using namespace morb;
 namespace {
 
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;  // ORBmatcher.cc:35-37
-constexpr int EDGE_ = 19;
 
 struct Desc { uint32_t w[8]; };
 
@@ -397,14 +396,14 @@ __global__ __launch_bounds__(256) void k_stereo_match(const StereoGeom sg, const
         const float iniu = scaleduR0 + 5 - 5, endu = scaleduR0 + 5 + 5 + 1;
         if (!(iniu < 0 || endu >= (float)w)) {
           cDo = true; cUL = uL; cUR0 = scaleduR0; cLvl = levelL; cPs = pstride;
-          cOffL = pyrOff + (size_t)imgL * pyrImg + (size_t)(EDGE_ + (int)scaledvL) * pstride + EDGE_ + (int)scaleduL;
-          cOffR = pyrOff + (size_t)imgR * pyrImg + (size_t)(EDGE_ + (int)scaledvL) * pstride + EDGE_ + (int)scaleduR0;
+          cOffL = pyrOff + (size_t)imgL * pyrImg + (size_t)(kPyrPad + (int)scaledvL) * pstride + kPyrPad + (int)scaleduL;
+          cOffR = pyrOff + (size_t)imgR * pyrImg + (size_t)(kPyrPad + (int)scaledvL) * pstride + kPyrPad + (int)scaleduR0;
         }
       }
     }
   }
   // a lane's two patch dwords: 11 x 3 dwords of the left patch + 11 x 6 dwords of the right strip = 99 dword loads (the bytes past the
-  // 11 / 21 used columns lie inside the level's 19-pixel pad); which dword a lane takes does not depend on the keypoint
+  // 11 / 21 used columns are loaded and not used: pyramid_layout.h, pyr_stereo_extent); which dword a lane takes does not depend on the keypoint
   int pRow[2], pCol[2], pLds[2];
   bool pLeft[2], pAct[2];
 #pragma unroll
@@ -1280,6 +1279,7 @@ int morb_stereo_match_batch(morb_matcher* m, const morb_extractor* e, int nframe
   MORB_REQUIRE(e->W > 0 && e->nimgLast >= 2 * nframes, MORB_ERR_INVALID,
                "the extractor must have processed the 2*nframes images (left = 2f, right = 2f+1) of this batch");
   MORB_REQUIRE(e->device == m->device, MORB_ERR_INVALID, "extractor and matcher live on different devices");
+  MORB_REQUIRE(pyr_stereo_scale_ok(e->scaleFactor), MORB_ERR_UNSUPPORTED, "scale factor too large for the stereo refinement (the SAD strip would leave the stored pyramid border)");
   MORB_ENTER(st, m, stream);
   int* sad = nullptr;
   uint8_t* stereoRec = nullptr;
