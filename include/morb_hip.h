@@ -486,6 +486,46 @@ int morb_search_for_triangulation_fisheye_batch(morb_matcher* m, const morb_fram
                                                 const float* T4, int bOnlyStereo, int bCoarse, int checkOri, int* d_match12,
                                                 int* d_nmatches, void* stream);
 
+/* The body of LocalMapping::CreateNewMapPoints between SearchForTriangulation and Fuse (LocalMapping.cc:489-709) for npairs keyframe
+ * pairs (current keyframe d_img1[p], neighbour d_img2[p]) of a pool of nimg pinhole images, mono or stereo (d_uRight / d_depth =
+ * mvuRight / mvDepth, both NULL = monocular; d_kpsRaw = mvKeys for UnprojectStereo, NULL = d_kps, which is mvKeysUn).  d_match12
+ * [npairs][cap] as morb_search_for_triangulation_batch wrote it; an entry at or beyond keyframe 2's count is no match.  Callers do not
+ * submit the pairs the baseline gate rejects (:454-466, nmp_pair_gate of morb/new_map_points_math.h).
+ * HOST arrays, as R12 / t12 of the search: poses [npairs][4][12] = Tcw1, Twc1, Tcw2, Twc2, each a 3 x 4 row-major [R | t] (GetPose() and
+ * GetPoseInverse(); Ow = the translation of Twc); kf2First [npairs] != 0 <=> std::less<KeyFrame*>()(pKF2, mpCurrentKeyFrame), the order of
+ * the new point's observation map, which decides the descriptor ComputeDistinctiveDescriptors keeps.  ratioFactor = 1.5f * mfScaleFactor.
+ * Outputs per pair: d_status [npairs][cap] (NewMapPointStatus of morb/new_map_points_math.h, one code per `continue` of the reference),
+ * d_stats [npairs][5] = created, totalStereoPts, countStereoAttempt, countStereoGoodProj, countStereo.
+ * Outputs into the caller's tables [nrows][cap], pair p writing row d_row[p] (the current keyframe's feature-indexed point table, the
+ * layout morb_fuse_batch takes with mpCap = cap) and only at accepted i: d_Xw [..][3], d_normal [..][3], d_maxDist, d_minDist
+ * (UpdateNormalAndDepth), d_mpDesc [..][32] (ComputeDistinctiveDescriptors), d_obsImg2 / d_obsIdx2 (the second observation).
+ * d_hasMP [nimg][cap] is updated in place by plain byte stores of 1 at [img1][i] and [img2][idx2] of accepted matches (AddMapPoint,
+ * :700-701), so that the next neighbour's search skips those features: the reference's order is one launch per neighbour rank, rank k
+ * of every current keyframe of a batch.  Pairs of one launch should not share an image; sharing one is harmless, the stores being
+ * idempotent, but such a pair does not see the other's points.  A pair whose image or row index lies outside the tables writes -1 to
+ * its stats and nothing else.  MORB_ERR_INVALID before any launch for a NULL array, a size below 1, nlevels outside [1, 16], only one of
+ * d_uRight / d_depth, or mbFarPoints without a positive mThFarPoints; MORB_ERR_UNSUPPORTED for cap > 32768. */
+int morb_create_new_map_points_batch(morb_matcher* m, const morb_frame_params* P, int npairs, const int* d_img1, const int* d_img2,
+                                     int nimg, int cap, const int* d_count, const morb_keypoint* d_kps, const morb_keypoint* d_kpsRaw,
+                                     const uint8_t* d_desc, const float* d_uRight, const float* d_depth, const int* d_match12,
+                                     const float* poses, const uint8_t* kf2First, float ratioFactor, int mbInertial, int mbFarPoints,
+                                     float mThFarPoints, int* d_status, int* d_stats, int nrows, const int* d_row, float* d_Xw,
+                                     float* d_normal, float* d_maxDist, float* d_minDist, uint8_t* d_mpDesc, int* d_obsImg2,
+                                     int* d_obsIdx2, uint8_t* d_hasMP, void* stream);
+
+/* The same between two keyframes of a KannalaBrandt8 rig (:520-567), in the layout of morb_search_for_triangulation_fisheye_batch: left
+ * features, then right.  Camera, pose and centre are those of the sides of idx1 and idx2; bStereo is false on a rig; mfMaxDistance is
+ * still measured from the current keyframe's LEFT centre.  poses [npairs][8][12] = Tcw1, Twc1, Trw1, Twr1, Tcw2, Twc2, Trw2, Twr2
+ * (GetPose(), its inverse, GetRightPose(), its inverse). */
+int morb_create_new_map_points_fisheye_batch(morb_matcher* m, const morb_frame_params* P, int npairs, const int* d_img1,
+                                             const int* d_img2, const int* d_nLeft1, const int* d_nLeft2, int nimg, int cap,
+                                             const int* d_count, const morb_keypoint* d_kps, const uint8_t* d_desc, const float* camL8,
+                                             const float* camR8, const int* d_match12, const float* poses, const uint8_t* kf2First,
+                                             float ratioFactor, int mbInertial, int mbFarPoints, float mThFarPoints, int* d_status,
+                                             int* d_stats, int nrows, const int* d_row, float* d_Xw, float* d_normal, float* d_maxDist,
+                                             float* d_minDist, uint8_t* d_mpDesc, int* d_obsImg2, int* d_obsIdx2, uint8_t* d_hasMP,
+                                             void* stream);
+
 /* ---- M7: loop-closing / local-mapping searches ---------------------------------------------------------
  * Common inputs: problem f searches keyframe image d_kfImg[f] of the pool; map points are [nprob][mpCap] arrays;
  * d_valid[f][i] != 0 <=> the point passes the reference's state checks at the top of its loop (non-null, !isBad(),

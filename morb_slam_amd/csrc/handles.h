@@ -25,6 +25,7 @@ struct morb_matcher {
   morb::DeviceGrow evictJ;       // k_resolve's eviction chain, features.  Also: rotation bins of SearchForTriangulation (k_rot_filter12)
   morb::DeviceGrow evictB;       // k_resolve's eviction chain, displaced queries
   morb::DeviceGrow pairTables;   // SearchForTriangulation's per-pair tables (F12 and epipoles, or the rig's cameras and transforms)
+  morb::DeviceGrow newPointPairs;  // CreateNewMapPoints' per-pair poses and descriptor-order flags (new_map_points.hip); its own buffer: the search before it on the stream reads pairTables
   morb::DeviceGrow queries;      // the Query records of a search.  Also: fisheye stereo's per-frame counts and offsets
   morb::DeviceGrow queryCount;   // queries per frame / pair
   morb::DeviceGrow kfdbPair;     // k_kfdb_intersect's per-(query, keyframe) first-word ranks, scores and common-word counts (keyframe_database.hip)

@@ -9,6 +9,13 @@ from .capi import check, lib, ptr, stream_arg
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30   # ORBmatcher.cc:35-37
 
+# d_status values and the d_stats row of morb_create_new_map_points_batch: the enums NewMapPointStatus / NewMapPointStat of
+# include/morb/new_map_points_math.h, index by index (tests/test_new_map_points_cpu.py compares them with the header)
+NEW_MAP_POINT_STATUS = ("NONE", "TRIANGULATED", "STEREO1", "STEREO2", "LOW_PARALLAX", "TRIANGULATE_FALSE", "UNPROJECT_FALSE", "Z1", "Z2",
+                        "REPROJ1", "REPROJ2", "ZERO_DIST", "FAR_POINT", "SCALE")
+NEW_MAP_POINT_CREATED = (1, 2, 3)
+NEW_MAP_POINT_STATS = ("CREATED", "TOTAL_STEREO_PTS", "STEREO_ATTEMPT", "STEREO_GOOD_PROJ", "COUNT_STEREO")
+
 
 class ORBmatcher:
     TH_HIGH, TH_LOW, HISTO_LENGTH = TH_HIGH, TH_LOW, HISTO_LENGTH
@@ -424,6 +431,47 @@ class ORBmatcher:
             ptr(hasMP), ptr(uRight), ptr(R12), ptr(t12), ptr(ep), 1 if bOnlyStereo else 0, 1 if bCoarse else 0,
             1 if self.mbCheckOrientation else 0, ptr(m12), ptr(nm), self._st(stream)))
         return m12, nm
+
+    @staticmethod
+    def new_map_point_tables(nrows, cap, device):
+        """The caller's feature-indexed point tables CreateNewMapPoints writes into (rows = current keyframes): a dict of device tensors."""
+        import torch
+        f32, i32 = torch.float32, torch.int32
+        return dict(Xw=torch.zeros((nrows, cap, 3), dtype=f32, device=device), normal=torch.zeros((nrows, cap, 3), dtype=f32, device=device),
+                    maxDist=torch.zeros((nrows, cap), dtype=f32, device=device), minDist=torch.zeros((nrows, cap), dtype=f32, device=device),
+                    desc=torch.zeros((nrows, cap, 32), dtype=torch.uint8, device=device),
+                    img2=torch.full((nrows, cap), -1, dtype=i32, device=device), idx2=torch.full((nrows, cap), -1, dtype=i32, device=device))
+
+    def CreateNewMapPoints(self, params, img1, img2, kps, desc, count, match12, poses, kf2First, row, tables, hasMP, uRight=None, depth=None,
+                           kpsRaw=None, ratioFactor=1.5 * 1.2, mbInertial=False, mbFarPoints=False, mThFarPoints=0.0, nLeft1=None,
+                           nLeft2=None, camL8=None, camR8=None, out=None, stream=None):
+        """The body of LocalMapping::CreateNewMapPoints for pairs (current keyframe img1[p], neighbour img2[p]) whose match tables
+        match12 [npairs, cap] SearchForTriangulation wrote (morb_create_new_map_points_batch; with nLeft1 / nLeft2 / camL8 / camR8 the
+        KannalaBrandt8 rig form).  poses: host [npairs, 4, 12] (Tcw1, Twc1, Tcw2, Twc2 as 3 x 4 row-major; rig: [npairs, 8, 12]);
+        kf2First: host u8 [npairs]; row i32 [npairs]: the row of `tables` (new_map_point_tables) pair p writes; hasMP u8 [nimg, cap] is
+        updated in place.  Returns (status i32 [npairs, cap], stats i32 [npairs, 5])."""
+        import torch
+        npairs, (nimg, cap) = int(img1.shape[0]), kps.shape[:2]
+        if out is None:
+            out = (torch.empty((npairs, cap), dtype=torch.int32, device=kps.device),
+                   torch.empty((npairs, len(NEW_MAP_POINT_STATS)), dtype=torch.int32, device=kps.device))
+        rig = nLeft1 is not None
+        poses = np.ascontiguousarray(poses, np.float32)
+        kf2First = np.ascontiguousarray(kf2First, np.uint8)
+        assert poses.shape == (npairs, 8 if rig else 4, 12) and kf2First.shape == (npairs,) and hasMP.dtype == torch.uint8
+        t = tables
+        tail = (ptr(match12), ptr(poses), ptr(kf2First), float(ratioFactor), 1 if mbInertial else 0, 1 if mbFarPoints else 0,
+                float(mThFarPoints), ptr(out[0]), ptr(out[1]), int(t["Xw"].shape[0]), ptr(row), ptr(t["Xw"]), ptr(t["normal"]),
+                ptr(t["maxDist"]), ptr(t["minDist"]), ptr(t["desc"]), ptr(t["img2"]), ptr(t["idx2"]), ptr(hasMP), self._st(stream))
+        if rig:
+            cams = [np.ascontiguousarray(c, np.float32) for c in (camL8, camR8)]
+            check(self._L.morb_create_new_map_points_fisheye_batch(self._h, C.byref(params), npairs, ptr(img1), ptr(img2), ptr(nLeft1),
+                                                                   ptr(nLeft2), nimg, cap, ptr(count), ptr(kps), ptr(desc), ptr(cams[0]),
+                                                                   ptr(cams[1]), *tail))
+            return out
+        check(self._L.morb_create_new_map_points_batch(self._h, C.byref(params), npairs, ptr(img1), ptr(img2), nimg, cap, ptr(count), ptr(kps),
+                                                       ptr(kpsRaw), ptr(desc), ptr(uRight), ptr(depth), *tail))
+        return out
 
     def SearchByProjectionKeyFrame(self, params, curImg, kfImg, kps, desc, count, curHasMP, Tcw, Ow, kfValid, Xw, maxDist, minDist,
                                    mpDesc, th, ORBdist, matchCur=None, stream=None, cam8=None, nLeftCur=None):

@@ -973,3 +973,277 @@ def keyframe_database_connected_csr(scene, queries):
     start[1:] = np.cumsum([len(s) for s in sets])
     conn = np.concatenate(sets).astype(np.int32) if sets and start[-1] else np.zeros(0, np.int32)
     return start, conn
+
+
+# ---- LocalMapping::CreateNewMapPoints ---------------------------------------------------------------------------------------------------
+NEW_MAP_POINT_KINDS = ("mono", "stereo1", "stereo2", "rig")
+# what a match of the scene was built to be; the status it gets is the oracle's business
+NEW_MAP_POINT_CATEGORIES = ("good", "low_parallax", "behind_both", "behind_2", "reproj1", "reproj2", "far", "scale", "stereo_close",
+                            "stereo_bad_depth", "stereo_noisy")
+
+
+def _pose34(R, O):
+    """[R | t] with t = -R O, 3 x 4."""
+    return np.concatenate([R, (-R @ O)[:, None]], 1)
+
+
+def _pose34_inv(T):
+    return np.concatenate([T[:, :3].T, (-T[:, :3].T @ T[:, 3])[:, None]], 1)
+
+
+def make_new_map_points_scene(seed=0, kind="mono", npairs=4, cap=96, nfeat=(40, 96), cam=EUROC_CAM, mb=0.11, nlevels=8, scale_factor=1.2,
+                              th_far=30.0, dense=False):
+    """Keyframe pairs with known poses and points for CreateNewMapPoints: pair p = (image 2 p, image 2 p + 1), synthetic keypoints and a
+    match table as SearchForTriangulation would leave it.  Even pairs move sideways, odd pairs forwards (low ray parallax near the axis,
+    and points in front of keyframe 1 but behind keyframe 2).  Matches cycle through NEW_MAP_POINT_CATEGORIES, so that every way the
+    reference's loop body ends occurs: points far away, behind the cameras, keypoints off by pixels, a far threshold, octaves that
+    disagree with the distances, stereo features whose own parallax wins, stereo depths <= 0.  kind: "mono", "stereo1" / "stereo2"
+    (stereo features in keyframe 1 / 2 only: mvuRight >= 0 and mvDepth), "rig" (KannalaBrandt8 pair, left then right features).
+    A few idx2 are shared by two idx1.  dense: every feature of image 1 matched to a good point (the largest compaction).
+    Returns a dict of numpy arrays; X [npairs, cap, 3] = the true point of each match (NaN where none), category [npairs, cap]."""
+    assert kind in NEW_MAP_POINT_KINDS
+    rng = np.random.default_rng(0x4E4D50 + 7919 * seed + NEW_MAP_POINT_KINDS.index(kind))
+    rig = kind == "rig"
+    nimg = 2 * npairs
+    fx, fy, cx, cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
+    mbf = fx * mb
+    sf = np.array([scale_factor ** l for l in range(nlevels)], np.float32)
+    sigma2 = (sf * sf).astype(np.float32)
+    if rig:
+        r28 = tumvi_rig28().astype(np.float64)
+        camL8, camR8 = r28[:8], r28[8:16]
+        Trl = np.concatenate([r28[16:25].reshape(3, 3), r28[25:28, None]], 1)
+    else:
+        camL8 = camR8 = np.array([fx, fy, cx, cy, 0, 0, 0, 0], np.float64)
+
+    def project(side_right, Xc):
+        if rig:
+            return kb8_project(camR8 if side_right else camL8, Xc[None])[0]
+        return np.array([fx * Xc[0] / Xc[2] + cx, fy * Xc[1] / Xc[2] + cy])
+
+    def compose(Ta, Tb):   # Ta o Tb
+        return np.concatenate([Ta[:, :3] @ Tb[:, :3], (Ta[:, :3] @ Tb[:, 3] + Ta[:, 3])[:, None]], 1)
+
+    count = np.zeros(nimg, np.int32)
+    nLeft = np.full(nimg, -1, np.int32)
+    xy = rng.uniform([20, 20], [730, 460], (nimg, cap, 2))
+    octave = rng.integers(0, nlevels, (nimg, cap)).astype(np.int32)
+    desc = rng.integers(0, 256, (nimg, cap, 32), dtype=np.uint8)
+    uRight = np.full((nimg, cap), -1.0, np.float32)
+    depth = np.full((nimg, cap), -1.0, np.float32)
+    match12 = np.full((npairs, cap), -1, np.int32)
+    X = np.full((npairs, cap, 3), np.nan)
+    category = np.full((npairs, cap), -1, np.int32)
+    poses = np.zeros((npairs, 8 if rig else 4, 12), np.float32)
+    kf2First = (rng.random(npairs) < 0.5).astype(np.uint8)
+    cats = list(NEW_MAP_POINT_CATEGORIES)
+    # what SearchForTriangulation reads besides: a vocabulary node per feature (a matched pair shares one), and per pinhole pair R12, t12
+    # (T1w * Tw2) and the epipole of keyframe 1's centre in keyframe 2
+    node = rng.integers(0, 40, (nimg, cap)).astype(np.int32)
+    R12, t12, ep = np.zeros((npairs, 9), np.float32), np.zeros((npairs, 3), np.float32), np.zeros((npairs, 2), np.float32)
+    for p in range(npairs):
+        forward = p % 2 == 1
+        n1, n2 = (cap, cap) if dense else (int(v) for v in rng.integers(nfeat[0], nfeat[1] + 1, 2))
+        count[2 * p], count[2 * p + 1] = n1, n2
+        R1 = _rot_from_rotvec(rng.normal(0, 0.04, 3))
+        O1 = rng.uniform(-1, 1, 3)
+        b = np.array([0.3, 0.05, 1.2]) if forward else np.array([rng.uniform(1.0, 1.5), rng.uniform(-0.1, 0.1), rng.uniform(-0.1, 0.1)])
+        R2 = _rot_from_rotvec(rng.normal(0, 0.02, 3)) @ R1
+        O2 = O1 + R1.T @ b
+        # the float poses are the scene: everything below is computed from them
+        T = [_pose34(R1, O1).astype(np.float32).astype(np.float64), _pose34(R2, O2).astype(np.float32).astype(np.float64)]
+        if rig:
+            TR = [compose(Trl, T[0]).astype(np.float32).astype(np.float64), compose(Trl, T[1]).astype(np.float32).astype(np.float64)]
+            blocks = [T[0], _pose34_inv(T[0]), TR[0], _pose34_inv(TR[0]), T[1], _pose34_inv(T[1]), TR[1], _pose34_inv(TR[1])]
+            nl1, nl2 = int(0.6 * n1), int(0.6 * n2)
+            nLeft[2 * p], nLeft[2 * p + 1] = nl1, nl2
+        else:
+            blocks = [T[0], _pose34_inv(T[0]), T[1], _pose34_inv(T[1])]
+            nl1, nl2 = n1, n2
+        poses[p] = np.stack(blocks).reshape(len(blocks), 12)
+        Rr = T[0][:, :3] @ T[1][:, :3].T
+        R12[p], t12[p] = Rr.ravel(), T[0][:, 3] - Rr @ T[1][:, 3]
+        C1 = T[1][:, :3] @ (-T[0][:, :3].T @ T[0][:, 3]) + T[1][:, 3]
+        ep[p] = [fx * C1[0] / C1[2] + cx, fy * C1[1] / C1[2] + cy]
+        nm = n1 if dense else int(rng.integers(min(n1, n2) // 2, min(n1, n2) - 2))
+        idx1 = np.sort(rng.permutation(n1)[:nm])
+        idx2 = rng.integers(0, n2, nm) if dense else rng.permutation(n2)[:nm]
+        shared = set() if dense else {5, 17}     # match k reuses match k - 1's feature of image 2 (and its point)
+        prev = None
+        for k in range(nm):
+            i1, i2 = int(idx1[k]), int(idx2[k])
+            cat = "good" if dense or k % 3 == 0 else cats[(k // 3 * 2 + k % 3) % len(cats)]
+            if k in shared and prev is not None:
+                i2, cat = prev[0], prev[2]
+            right1, right2 = rig and i1 >= nl1, rig and i2 >= nl2
+            Ta, Tb = (TR[0] if right1 else T[0]), (TR[1] if right2 else T[1])
+            stereo_side = {"stereo1": 1, "stereo2": 2}.get(kind, 0)
+            if cat in ("stereo_close", "stereo_bad_depth") and not (stereo_side and forward):
+                cat = "good"
+            if cat == "stereo_noisy" and not stereo_side:
+                cat = "good"
+            if cat in ("behind_both", "behind_2") and rig:
+                cat = "good"
+            if cat == "behind_2" and not forward:
+                cat = "behind_both"
+            if cat == "far" and forward:
+                cat = "good"
+            o1 = int(rng.integers(0, 4)); o2 = o1
+            sgn = rng.choice([-1.0, 1.0], 2)
+            tx, ty = sgn[0] * rng.uniform(0.25, 0.55), sgn[1] * rng.uniform(0.1, 0.35)
+            z = rng.uniform(4.0, 9.0)
+            if cat == "low_parallax":
+                z = 400.0
+            elif cat == "behind_both":
+                z = -6.0
+            elif cat == "behind_2":
+                tx, ty, z = 0.25, 0.1, 0.6
+            elif cat == "far":
+                z = rng.uniform(36.0, 45.0)
+            elif cat in ("stereo_close", "stereo_bad_depth"):
+                # next to the line of motion: the rays are almost parallel, the stereo feature's own parallax is the larger one
+                tx, ty, z = b[0] / b[2] + rng.uniform(-0.002, 0.002), b[1] / b[2] + rng.uniform(-0.002, 0.002), rng.uniform(3.5, 5.0)
+            elif cat == "scale":
+                o1, o2 = 0, 4
+            elif cat == "reproj1":
+                o1 = o2 = 0
+            elif cat == "reproj2":
+                o1, o2 = 5, 0
+            if k in shared and prev is not None:
+                Xw = prev[1]
+            else:
+                Xa = np.array([tx * z, ty * z, z])
+                Xw = Ta[:, :3].T @ (Xa - Ta[:, 3])
+            Xa, Xb = Ta[:, :3] @ Xw + Ta[:, 3], Tb[:, :3] @ Xw + Tb[:, 3]
+            if rig and (Xb[2] < 0.5 or Xa[2] < 0.5):
+                continue   # (a KB8 camera does not see behind itself here: leave the feature unmatched)
+            kpa, kpb = project(right1, Xa), project(right2, Xb)
+            if cat in ("reproj1", "reproj2") and not (k in shared and prev is not None):
+                # off the epipolar line by 8 px (6 px in image 2): the line through the keypoint and the image of a point moved towards
+                # the other camera's centre
+                Oa, Ob = -Ta[:, :3].T @ Ta[:, 3], -Tb[:, :3].T @ Tb[:, 3]
+                if cat == "reproj1":
+                    d = project(right1, Xa + 0.05 * (Ta[:, :3] @ (Ob - Xw))) - kpa
+                    kpa = kpa + 8.0 * np.array([-d[1], d[0]]) / np.linalg.norm(d)
+                else:
+                    d = project(right2, Xb + 0.05 * (Tb[:, :3] @ (Oa - Xw))) - kpb
+                    kpb = kpb + 6.0 * np.array([-d[1], d[0]]) / np.linalg.norm(d)
+            xy[2 * p, i1], octave[2 * p, i1] = kpa, o1
+            if not (k in shared and prev is not None):
+                xy[2 * p + 1, i2], octave[2 * p + 1, i2] = kpb, o2
+            if stereo_side and (cat in ("stereo_close", "stereo_bad_depth", "stereo_noisy") or rng.random() < 0.6):
+                img, i, Xs, kps_ = (2 * p, i1, Xa, kpa) if stereo_side == 1 else (2 * p + 1, i2, Xb, kpb)
+                if Xs[2] > 0 and not (stereo_side == 2 and k in shared):
+                    uRight[img, i] = kps_[0] - mbf / Xs[2] + (10.0 if cat == "stereo_noisy" else 0.0)
+                    depth[img, i] = -1.0 if cat == "stereo_bad_depth" else Xs[2]
+                    if uRight[img, i] < 0:
+                        uRight[img, i], depth[img, i] = -1.0, -1.0
+            match12[p, i1] = i2
+            flips = (1 << rng.integers(0, 8, 32)).astype(np.uint8) * (rng.random(32) < 0.08)
+            if k in shared and prev is not None:
+                desc[2 * p, i1] = desc[2 * p + 1, i2] ^ flips
+                node[2 * p, i1] = node[2 * p + 1, i2]
+            else:
+                desc[2 * p + 1, i2] = desc[2 * p, i1] ^ flips
+                node[2 * p + 1, i2] = node[2 * p, i1]
+            X[p, i1] = Xw
+            category[p, i1] = cats.index(cat)
+            prev = (i2, Xw, cat)
+    return dict(kind=kind, rig=rig, npairs=npairs, nimg=nimg, cap=cap, count=count, nLeft=nLeft, xy=xy.astype(np.float32),
+                # mvKeys beside mvKeysUn: a fixed offset stands for the undistortion (read by UnprojectStereo only)
+                xyRaw=(xy + np.array([0.3, -0.2])).astype(np.float32), octave=octave, desc=desc, uRight=uRight, depth=depth,
+                node=node, R12=R12, t12=t12, ep=ep, match12=match12, img1=np.arange(0, nimg, 2, dtype=np.int32), img2=np.arange(1, nimg, 2, dtype=np.int32), poses=poses,
+                kf2First=kf2First, X=X, category=category, scaleFactors=sf, levelSigma2=sigma2, camL8=camL8.astype(np.float32),
+                camR8=camR8.astype(np.float32), cam=dict(fx=fx, fy=fy, cx=cx, cy=cy), mb=float(mb), mbf=float(mbf),
+                ratioFactor=float(np.float32(1.5) * np.float32(scale_factor)), inertial=kind in ("stereo1", "rig"), farPoints=True,
+                thFarPoints=float(th_far), width=752, height=480)
+
+
+def new_map_points_frame_params(scene):
+    from .capi import make_frame_params
+    c = scene["cam"]
+    return make_frame_params(scene["width"], scene["height"], c["fx"], c["fy"], c["cx"], c["cy"], scene["mbf"], scene["mb"],
+                             [float(v) for v in scene["scaleFactors"]], [float(v) for v in scene["levelSigma2"]])
+
+
+def pack_new_map_points_scene(scene, device):
+    """make_new_map_points_scene -> the torch tensors of ORBmatcher.CreateNewMapPoints on `device` (kps / kpsRaw as u8 views of KP_DTYPE
+    records [nimg, cap]; uRight / depth None for the kinds without stereo features; hasMP zeros)."""
+    import torch
+    from .capi import KP_DTYPE
+    nimg, cap = scene["nimg"], scene["cap"]
+
+    def records(xy):
+        k = np.zeros((nimg, cap), KP_DTYPE)
+        k["x"], k["y"], k["size"], k["octave"] = xy[..., 0], xy[..., 1], 31.0, scene["octave"]
+        return torch.from_numpy(k.view(np.uint8).reshape(nimg, cap, KP_DTYPE.itemsize).copy()).to(device)
+    stereo = scene["kind"] in ("stereo1", "stereo2")
+    t = {k: torch.from_numpy(np.ascontiguousarray(scene[k])).to(device) for k in ("count", "desc", "match12", "img1", "img2")}
+    t.update(kps=records(scene["xy"]), kpsRaw=records(scene["xyRaw"]) if stereo else None,
+             uRight=torch.from_numpy(scene["uRight"]).to(device) if stereo else None,
+             depth=torch.from_numpy(scene["depth"]).to(device) if stereo else None,
+             nLeft1=torch.from_numpy(scene["nLeft"][scene["img1"]].copy()).to(device) if scene["rig"] else None,
+             nLeft2=torch.from_numpy(scene["nLeft"][scene["img2"]].copy()).to(device) if scene["rig"] else None,
+             hasMP=torch.zeros((nimg, cap), dtype=torch.uint8, device=device),
+             row=torch.arange(scene["npairs"], dtype=torch.int32).to(device))
+    return t
+
+
+def make_local_mapping_scene(seed=0, B=2, K=3, cap=128, npts=100, cam=EUROC_CAM, mb=0.11, nlevels=8, scale_factor=1.2):
+    """B new keyframes with K neighbours each for the local-mapping chain (search, create, Fuse per neighbour rank): image b (K + 1) is
+    current keyframe b, the K images behind it are its neighbours by rank.  Every current keyframe sees npts points; each neighbour
+    sees about two thirds of them at features of its own, so that a point is matched in several ranks and only the first creates it;
+    five features of a current keyframe are there twice, so that two idx1 share one idx2.
+    Pinhole, monocular.  Returns the pool (count, xy, octave, desc, node) and per rank k and keyframe b: img1 [B], img2 [K, B], R12,
+    t12, ep, poses [K, B, 4, 12], kf2First [K, B], and the neighbour's pose as Fuse takes it: Tcw7 [K, B, 7], Ow [K, B, 3]."""
+    rng = np.random.default_rng(0x4C4D43 + seed)
+    fx, fy, cx, cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
+    nimg = B * (K + 1)
+    sf = np.array([scale_factor ** l for l in range(nlevels)], np.float32)
+    count = np.zeros(nimg, np.int32)
+    xy = rng.uniform([20, 20], [730, 460], (nimg, cap, 2))
+    octave = np.zeros((nimg, cap), np.int32)
+    desc = rng.integers(0, 256, (nimg, cap, 32), dtype=np.uint8)
+    node = rng.integers(0, 40, (nimg, cap)).astype(np.int32)
+    img2 = np.zeros((K, B), np.int32)
+    R12, t12, ep = np.zeros((K, B, 9), np.float32), np.zeros((K, B, 3), np.float32), np.zeros((K, B, 2), np.float32)
+    poses, kf2First = np.zeros((K, B, 4, 12), np.float32), (rng.random((K, B)) < 0.5).astype(np.uint8)
+    Tcw7, Ow = np.zeros((K, B, 7), np.float32), np.zeros((K, B, 3), np.float32)
+    for b in range(B):
+        c = b * (K + 1)
+        R1, O1 = _rot_from_rotvec(rng.normal(0, 0.03, 3)), rng.uniform(-1, 1, 3)
+        T1 = _pose34(R1, O1).astype(np.float32).astype(np.float64)
+        count[c] = npts + 10
+        Xc = np.stack([rng.uniform(-0.5, 0.5, npts), rng.uniform(-0.3, 0.3, npts), np.ones(npts)], 1) * rng.uniform(4, 9, (npts, 1))
+        Xw = (Xc - T1[:, 3]) @ T1[:, :3]
+        xy[c, :npts] = np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
+        octave[c, :npts] = rng.integers(0, 3, npts)
+        # five features twice in the current keyframe: both copies match the same feature of a neighbour (a shared idx2)
+        for a in (xy, octave, desc, node):
+            a[c, npts:npts + 5] = a[c, :5]
+        for k in range(K):
+            j = c + 1 + k
+            img2[k, b] = j
+            ang = 2 * np.pi * k / K + 0.3
+            O2 = O1 + R1.T @ np.array([1.2 * np.cos(ang), 1.2 * np.sin(ang), rng.uniform(-0.1, 0.1)])
+            T2 = _pose34(_rot_from_rotvec(rng.normal(0, 0.02, 3)) @ R1, O2).astype(np.float32).astype(np.float64)
+            seen = np.nonzero(rng.random(npts) < 0.66)[0]
+            slot = rng.permutation(npts + 10)[:len(seen)]
+            count[j] = npts + 10
+            X2 = Xw[seen] @ T2[:, :3].T + T2[:, 3]
+            xy[j, slot] = np.stack([fx * X2[:, 0] / X2[:, 2] + cx, fy * X2[:, 1] / X2[:, 2] + cy], 1)
+            octave[j, slot] = octave[c, seen]
+            flips = (1 << rng.integers(0, 8, (len(seen), 32))).astype(np.uint8) * (rng.random((len(seen), 32)) < 0.08)
+            desc[j, slot] = desc[c, seen] ^ flips
+            node[j, slot] = node[c, seen]
+            Rr = T1[:, :3] @ T2[:, :3].T
+            R12[k, b], t12[k, b] = Rr.ravel(), T1[:, 3] - Rr @ T2[:, 3]
+            C1 = T2[:, :3] @ O1 + T2[:, 3]
+            ep[k, b] = [fx * C1[0] / C1[2] + cx, fy * C1[1] / C1[2] + cy]
+            poses[k, b] = np.stack([T1, _pose34_inv(T1), T2, _pose34_inv(T2)]).reshape(4, 12)
+            Tcw7[k, b] = np.concatenate([_quat_from_R(T2[:, :3]), T2[:, 3]])
+            Ow[k, b] = _pose34_inv(T2)[:, 3]
+    return dict(kind="mono", rig=False, B=B, K=K, nimg=nimg, cap=cap, count=count, xy=xy.astype(np.float32), octave=octave, desc=desc, node=node,
+                img1=np.arange(0, nimg, K + 1, dtype=np.int32), img2=img2, R12=R12, t12=t12, ep=ep, poses=poses, kf2First=kf2First, Tcw7=Tcw7,
+                Ow=Ow, scaleFactors=sf, levelSigma2=(sf * sf).astype(np.float32), cam=dict(fx=fx, fy=fy, cx=cx, cy=cy), mb=float(mb),
+                mbf=float(fx * mb), ratioFactor=float(np.float32(1.5) * np.float32(scale_factor)), width=752, height=480)

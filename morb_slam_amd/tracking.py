@@ -179,6 +179,73 @@ class KeyframeSearches:
         self.stream.synchronize()
 
 
+class LocalMappingChain:
+    """Local mapping's per-keyframe chain on the device, for B new keyframes with K neighbours each: for every neighbour rank k
+    SearchForTriangulation and then CreateNewMapPoints (rank k of every keyframe is one launch, as the reference visits its neighbours in
+    order: a feature that received a point at rank k is skipped by the search of rank k + 1), then SearchInNeighbors' Fuse of the new
+    points into every neighbour.  One stream, no host copy: the match tables, the point tables and hasMP stay on the device, and the
+    Fuse valid mask is formed there from the table's img2: a point is not fused into the keyframe it was created with."""
+
+    def __init__(self, params, kps, desc, node, count, scene, uRight=None, depth=None, kpsRaw=None, mbInertial=False, mbFarPoints=False,
+                 mThFarPoints=0.0, th=3.0, device=0):
+        """scene: host arrays as synth.make_local_mapping_scene returns them (img1 [B]; per rank img2 [K, B], R12, t12, ep, poses
+        [K, B, 4, 12], kf2First [K, B], Tcw7 [K, B, 7], Ow [K, B, 3]; ratioFactor).  Optional hasMP [nimg, cap]."""
+        import torch
+        self.torch = torch
+        dev = torch.device("cuda", device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self.P, self.kps, self.desc, self.node, self.count = params, kps, desc, node, count
+        self.uRight, self.depth, self.kpsRaw = uRight, depth, kpsRaw
+        self.inertial, self.far, self.thFar, self.th, self.ratioFactor = mbInertial, mbFarPoints, mThFarPoints, th, scene["ratioFactor"]
+        self.K, self.B = scene["img2"].shape
+        nimg, cap = kps.shape[:2]
+        self.img1 = t(scene["img1"].astype(np.int32))
+        self.img2 = [t(scene["img2"][k].astype(np.int32)) for k in range(self.K)]
+        self.host = [{n: np.ascontiguousarray(scene[n][k], np.float32) for n in ("R12", "t12", "ep", "poses")} for k in range(self.K)]
+        self.kf2First = [np.ascontiguousarray(scene["kf2First"][k], np.uint8) for k in range(self.K)]
+        self.Tcw7, self.Ow = [t(scene["Tcw7"][k]) for k in range(self.K)], [t(scene["Ow"][k]) for k in range(self.K)]
+        # Fuse takes mvuRight per problem, not per pool image
+        self.fuseUR = [None if uRight is None else uRight.index_select(0, i.long()).contiguous() for i in self.img2]
+        self.hasMP = t(scene["hasMP"].astype(np.uint8)) if "hasMP" in scene else torch.zeros((nimg, cap), dtype=torch.uint8, device=dev)
+        self.row = torch.arange(self.B, dtype=torch.int32, device=dev)
+        self.nMP = torch.full((self.B,), cap, dtype=torch.int32, device=dev)
+        self.m = ORBmatcher(0.6, False, device=device)         # CreateNewMapPoints: ORBmatcher(0.6, false)
+        # the chain's default stream is its matcher handle's own: the chain adds no stream to the process (a pooled torch stream is never
+        # given back and keeps a hardware queue), and close() releases it with the handle
+        self.stream = torch.cuda.ExternalStream(int(lib().morb_matcher_stream(self.m._h)), device=dev)
+        self.tables = self.m.new_map_point_tables(self.B, cap, dev)
+        i32 = torch.int32
+        self.tri = [(torch.empty((self.B, cap), dtype=i32, device=dev), torch.zeros((self.B,), dtype=i32, device=dev)) for _ in range(self.K)]
+        self.created = [(torch.empty((self.B, cap), dtype=i32, device=dev), torch.empty((self.B, 5), dtype=i32, device=dev)) for _ in range(self.K)]
+        self.fused = [(torch.empty((self.B, cap), dtype=i32, device=dev), torch.empty((self.B, cap), dtype=i32, device=dev)) for _ in range(self.K)]
+        self.valid = [torch.empty((self.B, cap), dtype=torch.uint8, device=dev) for _ in range(self.K)]
+
+    def close(self):
+        self.stream.synchronize()
+        self.m.close()
+
+    def step(self, stream=None):
+        s = self.stream if stream is None else stream
+        st = s.cuda_stream
+        torch, T = self.torch, self.tables
+        with torch.cuda.stream(s):
+            for k in range(self.K):
+                h = self.host[k]
+                self.m.SearchForTriangulation(self.P, self.img1, self.img2[k], self.kps, self.desc, self.node, self.count, self.hasMP,
+                                              self.uRight, h["R12"], h["t12"], h["ep"], False, False, out=self.tri[k], stream=st)
+                self.m.CreateNewMapPoints(self.P, self.img1, self.img2[k], self.kps, self.desc, self.count, self.tri[k][0], h["poses"],
+                                          self.kf2First[k], self.row, T, self.hasMP, uRight=self.uRight, depth=self.depth,
+                                          kpsRaw=self.kpsRaw, ratioFactor=self.ratioFactor, mbInertial=self.inertial, mbFarPoints=self.far,
+                                          mThFarPoints=self.thFar, out=self.created[k], stream=st)
+            for k in range(self.K):
+                torch.logical_and(T["img2"] >= 0, T["img2"] != self.img2[k][:, None], out=self.valid[k].view(torch.bool))
+                self.m.Fuse(self.P, self.img2[k], self.kps, self.desc, self.count, self.fuseUR[k], self.Tcw7[k], self.Ow[k], self.nMP,
+                            self.valid[k], T["Xw"], T["normal"], T["maxDist"], T["minDist"], T["desc"], self.th, out=self.fused[k], stream=st)
+
+    def sync(self):
+        self.stream.synchronize()
+
+
 # ---- synthetic scenes (host side, set-up only) --------------------------------------------------------------------------------
 def _backproject(P, x, y, z):
     return np.stack([(x - P.cx) * z / P.fx, (y - P.cy) * z / P.fy, z], 1).astype(np.float32)
