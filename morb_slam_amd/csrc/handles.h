@@ -58,11 +58,11 @@ struct morb_optimizer {
   morb::Event evFork, evJoin;
   // grow-only buffers (hip_owned.h: growth neither waits nor frees — Optimizer.h:46-139 is all-static and entered from three threads, and a
   // tracking-thread call must not wait for the LocalBundleAdjustment another thread has running on this device)
-  morb::DeviceGrow work;       // device workspace of the one-shot entry points (morb_local_inertial_ba, the one-shot LocalBundleAdjustment)
+  morb::DeviceGrow work;       // device workspace of the one-shot entry points (morb_local_inertial_ba, the one-shot LocalBundleAdjustment): carved anew at every call by ba_host.h's ArenaCarver
   morb::DeviceGrow spill;      // device buffer of the BATCH entry points: edge lists (k_pose_inertial) and correspondences (OptimizeSim3, Sim3Solver) that do not fit the LDS
   morb::DeviceGrow mlpnpCorr;  // MLPnPsolver's correspondences of problems that do not fit the LDS (k_mlpnp_solver); its own buffer, so that no other entry point's launch shares it
   morb::DeviceGrow twoViewCorr;  // TwoViewReconstruction's matches of problems that do not fit the LDS (k_two_view); its own buffer, as mlpnpCorr is
-  morb::PinnedGrow stage;      // pinned host buffer: the one-shot entry points gather their inputs here for a single upload
+  morb::PinnedGrow stage;      // pinned host buffer: the one-shot entry points gather their inputs here for a single upload (ba_host.h: the mirror of `work`'s upload region)
   morb::PinnedArray<int> lmWords;   // 16 pinned, device-mapped ints: LM state mirror of the one-shot entry points (optimizer.hip: morb_optimizer_lm_words)
   int exactOrder = 1;             // PoseOptimization: 1 (default) = edge-order sums, the LM path of g2o decision for decision; 0 = tree sums
   int mfmaChain = 0;              // ... carried by the FP64 matrix core (this device passed k_mfma_order_selftest) instead of dependent v_add_f64

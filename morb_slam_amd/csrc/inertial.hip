@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "internal_abi.h"
+#include "ba_host.h"
 #include "libm_f32.h"
 #include "kb8.h"
 #include "dense_ldlt.h"
@@ -1892,6 +1893,99 @@ int morb_pose_inertial_optimization_last_frame_fisheye_batch(morb_optimizer* o, 
                               d_preFrame, d_preKF, d_prevPrior, bRecInit, d_state, d_outlier, d_nInliers, d_prior, stream, d_nLeft, rig28);
 }
 
+static int iba_fail(const char* what) { set_error("%s", what); return MORB_ERR_HIP; }
+
+// What LocalInertialBA uploads besides the caller's arrays: CSR lists (ba_host.h), 64-edge chunks of the optimizable keyframes'
+// edges, the inertial links by colour, and the Schur product's block lists.
+struct IbaLayout {
+  std::vector<int> col, ptStart, ptEdges, kfStart, kfEdges, chunkKF, chunkStart, chunkEnd, linkOrder, colourStart, blkIndex;
+  std::vector<int2> blocks;
+  int nOpt = 0;
+  morbschur::Plan splan;
+};
+
+static int iba_layout(int nKF, const uint8_t* kfKind, int nMP, int nE, const int* eKF, const int* eMP, int nI, const int* iKF1, const int* iKF2,
+                      IbaLayout& L) {
+  L.col.assign(nKF, -1);
+  for (int k = 0; k < nKF; ++k) if (kfKind[k] == 0) L.col[k] = L.nOpt++;
+  MORB_REQUIRE(L.nOpt > 0, MORB_ERR_INVALID, "no optimizable keyframe");
+  for (int e = 0; e < nE; ++e) MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
+  for (int i = 0; i < nI; ++i) MORB_REQUIRE(iKF1[i] >= 0 && iKF1[i] < nKF && iKF2[i] >= 0 && iKF2[i] < nKF, MORB_ERR_INVALID, "link index out of range");
+  csr_by_key(eMP, nE, nMP, L.ptStart, L.ptEdges);
+  csr_by_key(eKF, nE, nKF, L.kfStart, L.kfEdges, L.col.data());   // (compact: the optimizable keyframes' edges only)
+  chunks_of(L.kfStart, L.col.data(), 64, L.chunkKF, L.chunkStart, L.chunkEnd);
+  // colour the inertial links so that links of one colour share no keyframe (greedy; a chain of consecutive keyframes alternates 0 / 1)
+  std::vector<int> colour(nI, 0);
+  int nColours = 0;
+  for (int i = 0; i < nI; ++i) {
+    int c = 0;
+    for (bool clash = true; clash; ) {
+      clash = false;
+      for (int j = 0; j < i && !clash; ++j)
+        clash = colour[j] == c && (iKF1[j] == iKF1[i] || iKF1[j] == iKF2[i] || iKF2[j] == iKF1[i] || iKF2[j] == iKF2[i]);
+      if (clash) ++c;
+    }
+    colour[i] = c; nColours = std::max(nColours, c + 1);
+  }
+  for (int c = 0; c < nColours; ++c) { L.colourStart.push_back((int)L.linkOrder.size()); for (int i = 0; i < nI; ++i) if (colour[i] == c) L.linkOrder.push_back(i); }
+  L.colourStart.push_back((int)L.linkOrder.size());
+  L.splan = morbschur::make_plan(6 * L.nOpt + 1, 3 * nMP);
+  schur_block_lists(L.splan.nb, L.blocks, L.blkIndex);
+  return MORB_OK;
+}
+
+// Levenberg-Marquardt with the control flow on the device (as grid-mode LocalBA, local_ba.hip): one slot = one trial; the host queues
+// slots one ahead of the decisions and stops when the mapped `done` word appears; kernels queued behind the last decision return at once.
+// Leaves the loop's counters in *outer / *trials and the chi2 of the last evaluated trial in *lastChi.
+static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLayout& L, double chi, int bLarge, size_t denseLds, size_t blockedLds,
+                       int panelInLds, int* outer, int* trials, double* lastChi) {
+  const int nKF = D.nKF, nMP = D.nMP, nE = D.nE, nI = D.nI, P = D.P, nChunks = D.nChunks, Mpose = 6 * L.nOpt;
+  const size_t nS = (size_t)D.nS, nPts = (size_t)D.nPts;
+  int *hostw = nullptr, *hostwDev = nullptr;
+  MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
+  D.lmHost = hostwDev;
+  D.optIt = bLarge ? 4 : 10;
+  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  hipLaunchKernelGGL(k_iba_lm_init, dim3(1), dim3(1), 0, st, D, chi, bLarge ? 1e-2 : 1e0);
+  const int beginGrid = div_up((int)std::max<size_t>(std::max<size_t>(std::max<size_t>(nS, nPts), (size_t)nMP * 8 /* k_iba_points: eight lanes per point */), std::max<size_t>((size_t)P * P, (size_t)18 * nE)), 256);
+  for (int slot = 0; slot < 120; ++slot) {
+    // backup / restore, then buildSystem (which runs only when the previous trial was accepted)
+    hipLaunchKernelGGL(k_iba_points, dim3(beginGrid), dim3(256), 0, st, D);
+    if (nChunks) hipLaunchKernelGGL(k_iba_kf, dim3(div_up(nChunks, 4)), dim3(256), 0, st, D);
+    for (size_t c = 0; c + 1 < L.colourStart.size(); ++c)
+      hipLaunchKernelGGL(k_iba_links, dim3(L.colourStart[c + 1] - L.colourStart[c]), dim3(64), 0, st, D, L.colourStart[c]);
+    hipLaunchKernelGGL(k_iba_pack_w, dim3(div_up(std::max(nE, 3 * nMP), 256)), dim3(256), 0, st, D);
+    // the trial: Schur complement of the points on the FP64 matrix cores, one dense product for matrix and right-hand side
+    hipLaunchKernelGGL(k_iba_pack_wd, dim3(div_up(std::max(nE, P * P + P), 256)), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(L.splan.nblk, L.splan.nsplit), dim3(64), 0, st, (const double*)D.sWD, (const double*)D.sW,
+                       L.splan.Mp, L.splan.ksteps, L.splan.stepsPerSplit, D.sBlocks, D.sPart, (const int*)(D.lmi + IBA_LM_DONE));
+    hipLaunchKernelGGL(k_iba_schur_finish, dim3(div_up(4 * (Mpose * Mpose + Mpose), 256)), dim3(256), 0, st, D);
+    if (denseLds) hipLaunchKernelGGL(k_iba_solve_lds, dim3(1), dim3(morbdense::LT), denseLds, st, D);
+    else hipLaunchKernelGGL(k_iba_solve_blocked, dim3(1), dim3(morbdense::GT), blockedLds, st, D, panelInLds);
+    // a failed solve leaves x as it was (zero at the first trial): g2o still applies the update
+    hipLaunchKernelGGL(k_iba_update, dim3(div_up(nMP + nKF, 256)), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 1);
+    if (hipGetLastError() != hipSuccess) return iba_fail("LocalInertialBA trial failed");
+    unsigned spins = 0;
+    while (!__atomic_load_n(hostw + 1, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 0, __ATOMIC_ACQUIRE) < slot) {   // one slot ahead
+      if ((++spins & 0x3FFu) == 0) {
+        const hipError_t q = hipStreamQuery(st);
+        if (q == hipSuccess) break;   // (everything queued has run: the words are final)
+        if (q != hipErrorNotReady) return iba_fail("LocalInertialBA: device error while waiting for the LM decision");
+      }
+      __builtin_ia32_pause();
+    }
+    if (__atomic_load_n(hostw + 1, __ATOMIC_ACQUIRE)) break;
+  }
+  hipLaunchKernelGGL(k_iba_end, dim3(div_up((int)std::max<size_t>(nS, nPts), 256)), dim3(256), 0, st, D);
+  int hi[16]; double hd[8];
+  if (hipMemcpyAsync(hi, D.lmi, sizeof hi, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hd, D.lmd, sizeof hd, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess)
+    return iba_fail("LocalInertialBA failed");
+  *outer = hi[IBA_LM_ITS]; *trials = hi[IBA_LM_TRIALS]; *lastChi = hd[IBA_LMD_LASTCHI];
+  return MORB_OK;
+}
+
 // static void Optimizer::LocalInertialBA(KeyFrame*, bool* pbStopFlag, Map*, int&, int&, int&, int&, bool bLarge, bool bRecInit)
 // on the flattened graph (see include/morb_hip.h).  HOST pointers.  eRight / rig28 != NULL: fisheye rig.
 static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
@@ -1905,175 +1999,69 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0 && nI >= 0, MORB_ERR_INVALID, "bad sizes");
   MORB_ENTER(st, o, nullptr);
   // ---- host-side graph layout
-  std::vector<int> col(nKF, -1);
-  int nOpt = 0;
-  for (int k = 0; k < nKF; ++k) if (kfKind[k] == 0) col[k] = nOpt++;
-  MORB_REQUIRE(nOpt > 0, MORB_ERR_INVALID, "no optimizable keyframe");
-  const int P = 15 * nOpt;
-  for (int e = 0; e < nE; ++e) MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
-  for (int i = 0; i < nI; ++i) MORB_REQUIRE(iKF1[i] >= 0 && iKF1[i] < nKF && iKF2[i] >= 0 && iKF2[i] < nKF, MORB_ERR_INVALID, "link index out of range");
-  std::vector<int> ptStart(nMP + 1, 0), ptEdges(nE);
-  for (int e = 0; e < nE; ++e) ++ptStart[eMP[e] + 1];
-  for (int l = 0; l < nMP; ++l) ptStart[l + 1] += ptStart[l];
-  { std::vector<int> fill(ptStart.begin(), ptStart.end() - 1); for (int e = 0; e < nE; ++e) ptEdges[fill[eMP[e]]++] = e; }
-  std::vector<std::vector<int>> byKF(nKF);
-  for (int e = 0; e < nE; ++e) if (col[eKF[e]] >= 0) byKF[eKF[e]].push_back(e);
-  std::vector<int> kfEdges, chunkKF, chunkStart, chunkEnd;
-  for (int k = 0; k < nKF; ++k)
-    for (size_t s0 = 0; s0 < byKF[k].size(); s0 += 64) {
-      chunkKF.push_back(k); chunkStart.push_back((int)kfEdges.size() + 0);
-      const size_t s1 = std::min(byKF[k].size(), s0 + 64);
-      for (size_t q = s0; q < s1; ++q) kfEdges.push_back(byKF[k][q]);
-      chunkEnd.push_back((int)kfEdges.size());
-    }
-  const int nChunks = (int)chunkKF.size();
+  IbaLayout L;
+  { const int rc = iba_layout(nKF, kfKind, nMP, nE, eKF, eMP, nI, iKF1, iKF2, L); if (rc != MORB_OK) return rc; }
+  const int nOpt = L.nOpt, P = 15 * nOpt, nChunks = (int)L.chunkKF.size();
 
-  // ---- device memory: one arena carved from the handle's grow-only workspace
-  const size_t nS = (size_t)33 * nKF, nPts = (size_t)3 * nMP, nX = (size_t)P + 3 * nMP;
-  const int nI1 = std::max(nI, 1);
-  const morbschur::Plan splan = morbschur::make_plan(6 * nOpt + 1, 3 * nMP);
-  size_t arenaBytes = 0;
-  auto reserve = [&](size_t bytes) { arenaBytes += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255; };
-  for (size_t b : {sizeof(int) * (size_t)nE, sizeof(int) * (size_t)nE, sizeof(float) * 3 * (size_t)nE, sizeof(float) * (size_t)nE,
-                   sizeof(int) * (size_t)(nMP + 1), sizeof(int) * (size_t)nE, sizeof(int) * kfEdges.size(), sizeof(int) * (size_t)nChunks,
-                   sizeof(int) * (size_t)nChunks, sizeof(int) * (size_t)nChunks, sizeof(int) * (size_t)nKF, sizeof(int) * (size_t)nI,
-                   sizeof(int) * (size_t)nI, sizeof(morb_imu_preintegrated) * (size_t)nI, (size_t)nI, (size_t)nMP, sizeof(float) * (size_t)nI,
-                   sizeof(float) * 21 * (size_t)nKF, sizeof(float) * 3 * (size_t)nMP,
-                   sizeof(double) * nS, sizeof(double) * nS, sizeof(double) * nPts, sizeof(double) * nPts, sizeof(double) * 3 * (size_t)nE,
-                   sizeof(double) * 9 * (size_t)nI1, sizeof(double) * 3 * (size_t)nI1, sizeof(double) * 3 * (size_t)nI1,
-                   sizeof(double) * 81 * (size_t)nI1, sizeof(double) * 9 * (size_t)nI1, sizeof(double) * 9 * (size_t)nI1,
-                   sizeof(double) * (size_t)P * P, sizeof(double) * (size_t)P * P, sizeof(double) * nX, sizeof(double) * (size_t)P,
-                   sizeof(double) * nX, sizeof(double) * 9 * (size_t)nMP, sizeof(double) * 18 * (size_t)nE, sizeof(double) * 4,
-                   (size_t)nE, (size_t)nE, sizeof(double) * splan.wElems(), sizeof(double) * splan.wElems(), sizeof(double) * splan.partElems(), sizeof(double) * morbdense::global_panel_doubles(P),
-                   sizeof(int2) * (size_t)splan.nblk, sizeof(int) * (size_t)splan.nb * splan.nb, sizeof(double) * 8, sizeof(int) * 16,
-                   sizeof(int) * (size_t)nI, sizeof(double) * 27 * (size_t)nChunks, sizeof(int) * (size_t)nKF,
-                   sizeof(double) * (size_t)div_up(nE + nI, 256), sizeof(double) * (size_t)div_up(nMP + nKF, 256)})
-    reserve(b);
-  char* arena = nullptr;
-  { const int rc = grow(o->work, arenaBytes, &arena); if (rc != MORB_OK) return rc; }
-  size_t arenaOff = 0;
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = arena + arenaOff;
-    arenaOff += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
-    return arenaOff <= arenaBytes ? p : nullptr;
-  };
-  auto cleanup = [&]() {};
-  // host -> device: every array goes into a pinned mirror of the arena's upload prefix first and crosses PCIe in ONE copy (twenty
-  // pageable hipMemcpyAsync calls, each staged and synchronised by the runtime, were ~0.25 ms of a 1.8 ms call)
-  char* stage = nullptr;
-  size_t stageCap = 0;
-  {
-    size_t upBytes = 0;
-    for (size_t b : {sizeof(int) * (size_t)nE, sizeof(int) * (size_t)nE, sizeof(float) * 3 * (size_t)nE, sizeof(float) * (size_t)nE,
-                     sizeof(int) * (size_t)(nMP + 1), sizeof(int) * (size_t)nE, sizeof(int) * kfEdges.size(), sizeof(int) * (size_t)nChunks,
-                     sizeof(int) * (size_t)nChunks, sizeof(int) * (size_t)nChunks, sizeof(int) * (size_t)nKF, sizeof(int) * (size_t)nI,
-                     sizeof(int) * (size_t)nI, sizeof(morb_imu_preintegrated) * (size_t)nI, (size_t)nI, (size_t)nMP, sizeof(float) * (size_t)nI,
-                     sizeof(float) * 21 * (size_t)nKF, sizeof(float) * 3 * (size_t)nMP, (size_t)nE, sizeof(int2) * (size_t)splan.nblk,
-                     sizeof(int) * (size_t)splan.nb * splan.nb, sizeof(int) * (size_t)nI})
-      upBytes += (std::max<size_t>(b, 16) + 255) & ~(size_t)255;
-    const int rc = grow(o->stage, upBytes, &stage);
-    if (rc != MORB_OK) return rc;
-    stageCap = upBytes;
-  }
-  size_t upHi = 0;
-  auto up = [&](const void* h, size_t bytes) -> void* {
-    const size_t off = arenaOff;
-    void* d = dalloc(bytes);
-    if (d && bytes) {
-      if (off + bytes > stageCap) return nullptr;   // (cannot happen: the uploads are the arena's first allocations, sized above)
-      memcpy(stage + off, h, bytes); upHi = off + bytes;
-    }
-    return d;
-  };
+  // ---- device memory: every array is carved from the handle's grow-only workspace (ba_host.h): host -> device arrays first, each
+  // copied into a pinned mirror of that region which crosses PCIe in ONE copy (twenty pageable hipMemcpyAsync calls, each staged and
+  // synchronised by the runtime, were ~0.25 ms of a 1.8 ms call), the device-only arrays behind them
+  const size_t nS = (size_t)33 * nKF, nPts = (size_t)3 * nMP, nX = (size_t)P + 3 * nMP, nI1 = (size_t)std::max(nI, 1);
   IbaDev D;
   memset(&D, 0, sizeof D);
   D.nKF = nKF; D.nMP = nMP; D.nE = nE; D.nI = nI; D.P = P; D.nChunks = nChunks;
-  D.eKF = (const int*)up(eKF, sizeof(int) * nE); D.eMP = (const int*)up(eMP, sizeof(int) * nE);
-  D.eObs = (const float*)up(eObs, sizeof(float) * 3 * nE); D.eInfo = (const float*)up(eInvSigma2, sizeof(float) * nE);
-  D.ptStart = (const int*)up(ptStart.data(), sizeof(int) * (nMP + 1)); D.ptEdges = (const int*)up(ptEdges.data(), sizeof(int) * nE);
-  D.kfEdges = (const int*)up(kfEdges.data(), sizeof(int) * kfEdges.size());
-  D.chunkKF = (const int*)up(chunkKF.data(), sizeof(int) * nChunks); D.chunkStart = (const int*)up(chunkStart.data(), sizeof(int) * nChunks);
-  D.chunkEnd = (const int*)up(chunkEnd.data(), sizeof(int) * nChunks);
-  D.col = (const int*)up(col.data(), sizeof(int) * nKF);
-  D.iKF1 = (const int*)up(iKF1, sizeof(int) * nI); D.iKF2 = (const int*)up(iKF2, sizeof(int) * nI);
-  D.iPre = (const morb_imu_preintegrated*)up(iPre, sizeof(morb_imu_preintegrated) * nI);
-  D.iRobust = (const uint8_t*)up(iRobust, nI); D.mpClose = (const uint8_t*)up(mpClose, nMP);
-  float* d_scale = (float*)up(iInfoScale, sizeof(float) * nI);
-  float* d_kfIn = (float*)up(kfState21, sizeof(float) * 21 * nKF);
-  float* d_mpIn = (float*)up(mpPos, sizeof(float) * 3 * nMP);
-  D.eRight = eRight ? (const uint8_t*)up(eRight, nE) : nullptr;
-  {
-    std::vector<int2> blocks; std::vector<int> blkIndex((size_t)splan.nb * splan.nb, 0);
-    for (int bi = 0; bi < splan.nb; ++bi) for (int bj = bi; bj < splan.nb; ++bj) { blkIndex[(size_t)bi * splan.nb + bj] = (int)blocks.size(); blocks.push_back(make_int2(bi, bj)); }
-    D.sBlocks = (const int2*)up(blocks.data(), sizeof(int2) * blocks.size()); D.sBlkIndex = (const int*)up(blkIndex.data(), sizeof(int) * blkIndex.size());
-  }
-  // colour the inertial links so that links of one colour share no keyframe (greedy; a chain of consecutive keyframes alternates 0 / 1)
-  std::vector<int> linkOrder, colourStart;
-  {
-    std::vector<int> colour(nI, 0);
-    int nColours = 0;
-    for (int i = 0; i < nI; ++i) {
-      int c = 0;
-      for (bool clash = true; clash; ) {
-        clash = false;
-        for (int j = 0; j < i && !clash; ++j)
-          clash = colour[j] == c && (iKF1[j] == iKF1[i] || iKF1[j] == iKF2[i] || iKF2[j] == iKF1[i] || iKF2[j] == iKF2[i]);
-        if (clash) ++c;
-      }
-      colour[i] = c; nColours = std::max(nColours, c + 1);
-    }
-    for (int c = 0; c < nColours; ++c) { colourStart.push_back((int)linkOrder.size()); for (int i = 0; i < nI; ++i) if (colour[i] == c) linkOrder.push_back(i); }
-    colourStart.push_back((int)linkOrder.size());
-  }
-  D.linkOrder = (const int*)up(linkOrder.data(), sizeof(int) * nI);
-  MORB_REQUIRE(D.sBlkIndex != nullptr && D.linkOrder != nullptr && arenaOff <= arenaBytes, MORB_ERR_HIP, "workspace carve-up overflow in morb_local_inertial_ba");
-  if (hipMemcpyAsync(arena, stage, upHi, hipMemcpyHostToDevice, st) != hipSuccess) return MORB_ERR_HIP;   // the one upload
-  D.kfPart = (double*)dalloc(sizeof(double) * 27 * (size_t)nChunks); D.kfTicket = (int*)dalloc(sizeof(int) * (size_t)nKF);
-  MORB_REQUIRE(D.kfTicket != nullptr, MORB_ERR_HIP, "workspace carve-up overflow in morb_local_inertial_ba");
-  (void)hipMemsetAsync(D.kfTicket, 0, sizeof(int) * (size_t)nKF, st);   // (the last chunk of a keyframe to arrive resets its counter)
-  D.S = (double*)dalloc(sizeof(double) * nS); D.Sbk = (double*)dalloc(sizeof(double) * nS);
-  D.pts = (double*)dalloc(sizeof(double) * nPts); D.ptsBk = (double*)dalloc(sizeof(double) * nPts);
-  D.nS = (int)nS; D.nPts = (int)nPts;
-  D.lmd = (double*)dalloc(sizeof(double) * 8); D.lmi = (int*)dalloc(sizeof(int) * 16);
-  if (D.lmi) (void)hipMemsetAsync(D.lmi, 0, sizeof(int) * 16, st);   // (k_iba_errors' arrival counter is live before k_iba_lm_init)
-  D.vErr = (double*)dalloc(sizeof(double) * 3 * nE); D.iErr = (double*)dalloc(sizeof(double) * 9 * std::max(nI, 1));
-  D.gErr = (double*)dalloc(sizeof(double) * 3 * std::max(nI, 1)); D.aErr = (double*)dalloc(sizeof(double) * 3 * std::max(nI, 1));
-  D.InfoI = (double*)dalloc(sizeof(double) * 81 * std::max(nI, 1)); D.InfoG = (double*)dalloc(sizeof(double) * 9 * std::max(nI, 1));
-  D.InfoA = (double*)dalloc(sizeof(double) * 9 * std::max(nI, 1));
-  D.H = (double*)dalloc(sizeof(double) * (size_t)P * P); D.Hs = (double*)dalloc(sizeof(double) * (size_t)P * P);
-  D.b = (double*)dalloc(sizeof(double) * nX); D.bs = (double*)dalloc(sizeof(double) * P); D.x = (double*)dalloc(sizeof(double) * nX);
-  D.Hll = (double*)dalloc(sizeof(double) * 9 * nMP); D.Hpl = (double*)dalloc(sizeof(double) * 18 * nE);
-  D.scal = (double*)dalloc(sizeof(double) * 4);
-  D.partChi = (double*)dalloc(sizeof(double) * div_up(nE + nI, 256)); D.partScale = (double*)dalloc(sizeof(double) * div_up(nMP + nKF, 256)); D.nbUpdate = div_up(nMP + nKF, 256);
-  D.pnlG = (double*)dalloc(sizeof(double) * morbdense::global_panel_doubles(P));
-  uint8_t* d_erase = (uint8_t*)dalloc(nE);
-  MORB_REQUIRE(d_erase != nullptr && arenaOff <= arenaBytes, MORB_ERR_HIP, "workspace carve-up overflow in morb_local_inertial_ba");
-  (void)hipMemsetAsync(D.x, 0, sizeof(double) * nX, st);   // the solver's x before the first solve
+  D.nS = (int)nS; D.nPts = (int)nPts; D.nbUpdate = div_up(nMP + nKF, 256);
+  D.sMp = L.splan.Mp; D.sNb = L.splan.nb; D.sNblk = L.splan.nblk; D.sNsplit = L.splan.nsplit;
   make_geom(Tbc12, fx, fy, cx, cy, bf, rig28, D.g);
-  {
-    D.sW = (double*)dalloc(sizeof(double) * splan.wElems()); D.sWD = (double*)dalloc(sizeof(double) * splan.wElems());
-    D.sPart = (double*)dalloc(sizeof(double) * splan.partElems());
-    MORB_REQUIRE(D.sPart != nullptr && arenaOff <= arenaBytes, MORB_ERR_HIP, "workspace carve-up overflow in morb_local_inertial_ba");
-    D.sMp = splan.Mp; D.sNb = splan.nb; D.sNblk = splan.nblk; D.sNsplit = splan.nsplit;
-    // the operands' zero pattern is this graph's: the workspace is reused from call to call
-    (void)hipMemsetAsync(D.sW, 0, sizeof(double) * splan.wElems(), st);
-    (void)hipMemsetAsync(D.sWD, 0, sizeof(double) * splan.wElems(), st);
-  }
-
-  auto fail = [&](const char* what) { cleanup(); set_error("%s", what); return MORB_ERR_HIP; };
-  double h[4];
-  auto errors = [&](double* chi) -> bool {   // computeActiveErrors + activeRobustChi2
-    if (hipMemsetAsync(D.scal, 0, sizeof(double) * 4, st) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 0);
-    if (hipMemcpyAsync(h, D.scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
-    if (hipStreamSynchronize(st) != hipSuccess) return false;
-    *chi = h[0];
-    return true;
+  float *d_scale = nullptr, *d_kfIn = nullptr, *d_mpIn = nullptr; uint8_t* d_erase = nullptr;
+  ArenaCarver A;
+  auto carve = [&]() {
+    D.eKF = (const int*)A.take(eKF, sizeof(int) * nE); D.eMP = (const int*)A.take(eMP, sizeof(int) * nE);
+    D.eObs = (const float*)A.take(eObs, sizeof(float) * 3 * nE); D.eInfo = (const float*)A.take(eInvSigma2, sizeof(float) * nE);
+    D.ptStart = (const int*)A.take(L.ptStart.data(), sizeof(int) * (nMP + 1)); D.ptEdges = (const int*)A.take(L.ptEdges.data(), sizeof(int) * nE);
+    D.kfEdges = (const int*)A.take(L.kfEdges.data(), sizeof(int) * L.kfEdges.size());
+    D.chunkKF = (const int*)A.take(L.chunkKF.data(), sizeof(int) * nChunks); D.chunkStart = (const int*)A.take(L.chunkStart.data(), sizeof(int) * nChunks);
+    D.chunkEnd = (const int*)A.take(L.chunkEnd.data(), sizeof(int) * nChunks); D.col = (const int*)A.take(L.col.data(), sizeof(int) * nKF);
+    D.iKF1 = (const int*)A.take(iKF1, sizeof(int) * nI); D.iKF2 = (const int*)A.take(iKF2, sizeof(int) * nI);
+    D.iPre = (const morb_imu_preintegrated*)A.take(iPre, sizeof(morb_imu_preintegrated) * nI);
+    D.iRobust = (const uint8_t*)A.take(iRobust, nI); D.mpClose = (const uint8_t*)A.take(mpClose, nMP);
+    d_scale = (float*)A.take(iInfoScale, sizeof(float) * nI); d_kfIn = (float*)A.take(kfState21, sizeof(float) * 21 * nKF);
+    d_mpIn = (float*)A.take(mpPos, sizeof(float) * 3 * nMP);
+    D.eRight = eRight ? (const uint8_t*)A.take(eRight, nE) : nullptr;
+    D.sBlocks = (const int2*)A.take(L.blocks.data(), sizeof(int2) * L.blocks.size()); D.sBlkIndex = (const int*)A.take(L.blkIndex.data(), sizeof(int) * L.blkIndex.size());
+    D.linkOrder = (const int*)A.take(L.linkOrder.data(), sizeof(int) * nI);
+    D.kfPart = (double*)A.take(nullptr, sizeof(double) * 27 * (size_t)nChunks); D.kfTicket = (int*)A.take(nullptr, sizeof(int) * (size_t)nKF);
+    D.S = (double*)A.take(nullptr, sizeof(double) * nS); D.Sbk = (double*)A.take(nullptr, sizeof(double) * nS);
+    D.pts = (double*)A.take(nullptr, sizeof(double) * nPts); D.ptsBk = (double*)A.take(nullptr, sizeof(double) * nPts);
+    D.lmd = (double*)A.take(nullptr, sizeof(double) * 8); D.lmi = (int*)A.take(nullptr, sizeof(int) * 16);
+    D.vErr = (double*)A.take(nullptr, sizeof(double) * 3 * nE); D.iErr = (double*)A.take(nullptr, sizeof(double) * 9 * nI1);
+    D.gErr = (double*)A.take(nullptr, sizeof(double) * 3 * nI1); D.aErr = (double*)A.take(nullptr, sizeof(double) * 3 * nI1);
+    D.InfoI = (double*)A.take(nullptr, sizeof(double) * 81 * nI1); D.InfoG = (double*)A.take(nullptr, sizeof(double) * 9 * nI1);
+    D.InfoA = (double*)A.take(nullptr, sizeof(double) * 9 * nI1); D.H = (double*)A.take(nullptr, sizeof(double) * (size_t)P * P); D.Hs = (double*)A.take(nullptr, sizeof(double) * (size_t)P * P);
+    D.b = (double*)A.take(nullptr, sizeof(double) * nX); D.bs = (double*)A.take(nullptr, sizeof(double) * P); D.x = (double*)A.take(nullptr, sizeof(double) * nX);
+    D.Hll = (double*)A.take(nullptr, sizeof(double) * 9 * nMP); D.Hpl = (double*)A.take(nullptr, sizeof(double) * 18 * nE); D.scal = (double*)A.take(nullptr, sizeof(double) * 4);
+    D.partChi = (double*)A.take(nullptr, sizeof(double) * div_up(nE + nI, 256)); D.partScale = (double*)A.take(nullptr, sizeof(double) * D.nbUpdate);
+    D.pnlG = (double*)A.take(nullptr, sizeof(double) * morbdense::global_panel_doubles(P)); d_erase = (uint8_t*)A.take(nullptr, nE);
+    D.sW = (double*)A.take(nullptr, sizeof(double) * L.splan.wElems()); D.sWD = (double*)A.take(nullptr, sizeof(double) * L.splan.wElems());
+    D.sPart = (double*)A.take(nullptr, sizeof(double) * L.splan.partElems());
   };
+  carve();   // (dry: sizes)
+  char *arena = nullptr, *stage = nullptr;
+  { const int rc = grow(o->work, A.uploadBytes() + A.deviceBytes(), &arena); if (rc != MORB_OK) return rc; }
+  { const int rc = grow(o->stage, A.uploadBytes(), &stage); if (rc != MORB_OK) return rc; }
+  A.bind(arena, stage);
+  carve();
+  MORB_REQUIRE(A.ok(), MORB_ERR_HIP, "the two carve passes of morb_local_inertial_ba differ");
+  if (hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st) != hipSuccess) return MORB_ERR_HIP;   // the one upload
+  // the workspace is reused from call to call: what the first kernels expect to find zero is cleared behind the carve
+  (void)hipMemsetAsync(D.kfTicket, 0, sizeof(int) * (size_t)nKF, st);   // (the last chunk of a keyframe to arrive resets its counter)
+  (void)hipMemsetAsync(D.lmi, 0, sizeof(int) * 16, st);   // (k_iba_errors' arrival counter is live before k_iba_lm_init)
+  (void)hipMemsetAsync(D.x, 0, sizeof(double) * nX, st);   // the solver's x before the first solve
+  (void)hipMemsetAsync(D.sW, 0, sizeof(double) * L.splan.wElems(), st); (void)hipMemsetAsync(D.sWD, 0, sizeof(double) * L.splan.wElems(), st);   // the operands' zero pattern is this graph's
+
   hipLaunchKernelGGL(k_iba_setup_kf, dim3(div_up(nKF, 64)), dim3(64), 0, st, D, d_kfIn);
   if (nI) hipLaunchKernelGGL(k_iba_setup_links, dim3(nI), dim3(64), 0, st, D, d_scale);
   hipLaunchKernelGGL(k_iba_setup_pts, dim3(div_up((int)nPts, 256)), dim3(256), 0, st, D, (const float*)d_mpIn);   // points to FP64
-  const int Mpose = 6 * nOpt;
   size_t blockedLds = sizeof(double) * (morbdense::global_lds_doubles(P) + morbdense::global_panel_doubles(P));
   const int panelInLds = blockedLds <= 150 * 1024 ? 1 : 0;
   if (!panelInLds) blockedLds = sizeof(double) * morbdense::global_lds_doubles(P);
@@ -2083,61 +2071,16 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   size_t denseLds = sizeof(double) * morbdense::lds_doubles(P);
   if (denseLds > 156 * 1024) denseLds = 0;   // larger windows (bLarge) use the global-memory solver
   if (denseLds) MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-  double chi = 0;
-  if (!errors(&chi)) return fail("k_iba_errors failed");
+  double h[4];   // computeActiveErrors + activeRobustChi2
+  if (hipMemsetAsync(D.scal, 0, sizeof(double) * 4, st) != hipSuccess) return iba_fail("k_iba_errors failed");
+  hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 0);
+  if (hipMemcpyAsync(h, D.scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return iba_fail("k_iba_errors failed");
+  const double chi = h[0];
   const float err0 = (float)chi;
-  // ---- Levenberg-Marquardt with the control flow on the device (as grid-mode LocalBA, local_ba.hip): one slot = one trial; the host queues
-  // slots one ahead of the decisions and stops when the mapped `done` word appears; kernels queued behind the last decision return at once
   int trials = 0, outer = 0;
-  {
-    int* hostw = nullptr;
-    int* hostwDev = nullptr;
-    MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
-    D.lmHost = hostwDev;
-    D.optIt = bLarge ? 4 : 10;
-    __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
-    hipLaunchKernelGGL(k_iba_lm_init, dim3(1), dim3(1), 0, st, D, chi, bLarge ? 1e-2 : 1e0);
-    const int beginGrid = div_up((int)std::max<size_t>(std::max<size_t>(std::max<size_t>(nS, nPts), (size_t)nMP * 8 /* k_iba_points: eight lanes per point */), std::max<size_t>((size_t)P * P, (size_t)18 * nE)), 256);
-    for (int slot = 0; slot < 120; ++slot) {
-      // backup / restore, then buildSystem (which runs only when the previous trial was accepted)
-      hipLaunchKernelGGL(k_iba_points, dim3(beginGrid), dim3(256), 0, st, D);
-      if (nChunks) hipLaunchKernelGGL(k_iba_kf, dim3(div_up(nChunks, 4)), dim3(256), 0, st, D);
-      for (size_t c = 0; c + 1 < colourStart.size(); ++c)
-        hipLaunchKernelGGL(k_iba_links, dim3(colourStart[c + 1] - colourStart[c]), dim3(64), 0, st, D, colourStart[c]);
-      hipLaunchKernelGGL(k_iba_pack_w, dim3(div_up(std::max(nE, 3 * nMP), 256)), dim3(256), 0, st, D);
-      // the trial: Schur complement of the points on the FP64 matrix cores, one dense product for matrix and right-hand side
-      hipLaunchKernelGGL(k_iba_pack_wd, dim3(div_up(std::max(nE, P * P + P), 256)), dim3(256), 0, st, D);
-      hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(splan.nblk, splan.nsplit), dim3(64), 0, st, (const double*)D.sWD, (const double*)D.sW,
-                         splan.Mp, splan.ksteps, splan.stepsPerSplit, D.sBlocks, D.sPart, (const int*)(D.lmi + IBA_LM_DONE));
-      hipLaunchKernelGGL(k_iba_schur_finish, dim3(div_up(4 * (Mpose * Mpose + Mpose), 256)), dim3(256), 0, st, D);
-      if (denseLds) hipLaunchKernelGGL(k_iba_solve_lds, dim3(1), dim3(morbdense::LT), denseLds, st, D);
-      else hipLaunchKernelGGL(k_iba_solve_blocked, dim3(1), dim3(morbdense::GT), blockedLds, st, D, panelInLds);
-      // a failed solve leaves x as it was (zero at the first trial): g2o still applies the update
-      hipLaunchKernelGGL(k_iba_update, dim3(div_up(nMP + nKF, 256)), dim3(256), 0, st, D);
-      hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 1);
-      if (hipGetLastError() != hipSuccess) return fail("LocalInertialBA trial failed");
-      unsigned spins = 0;
-      while (!__atomic_load_n(hostw + 1, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 0, __ATOMIC_ACQUIRE) < slot) {   // one slot ahead
-        if ((++spins & 0x3FFu) == 0) {
-          const hipError_t q = hipStreamQuery(st);
-          if (q == hipSuccess) break;   // (everything queued has run: the words are final)
-          if (q != hipErrorNotReady) return fail("LocalInertialBA: device error while waiting for the LM decision");
-        }
-        __builtin_ia32_pause();
-      }
-      if (__atomic_load_n(hostw + 1, __ATOMIC_ACQUIRE)) break;
-    }
-    hipLaunchKernelGGL(k_iba_end, dim3(div_up((int)std::max<size_t>(nS, nPts), 256)), dim3(256), 0, st, D);
-    // the loop's counters and the chi2 of the last evaluated trial (h[0] below)
-    int hi[16];
-    double hd[8];
-    if (hipMemcpyAsync(hi, D.lmi, sizeof hi, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hd, D.lmd, sizeof hd, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess)
-      return fail("LocalInertialBA failed");
-    outer = hi[IBA_LM_ITS]; trials = hi[IBA_LM_TRIALS];
-    h[0] = hd[IBA_LMD_LASTCHI];
-  }
-  // activeRobustChi2 of the last computed errors = h[0] of the last trial (or the initial one)
+  { const int rc = iba_lm_loop(o, st, D, L, chi, bLarge, denseLds, blockedLds, panelInLds, &outer, &trials, &h[0]); if (rc != MORB_OK) return rc; }
+  // ---- read-back.  activeRobustChi2 of the last computed errors = h[0] of the last trial (or the initial one)
   const float errEnd = (float)(trials ? h[0] : chi);
   int okFlag = 1;
   if ((2 * err0 < errEnd || std::isnan(err0) || std::isnan(errEnd)) && !bLarge) okFlag = 0;   // "FAIL LOCAL-INERTIAL BA" (:2808-2813)
@@ -2147,10 +2090,9 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
     (void)hipMemcpyAsync(eraseFlag, d_erase, nE, hipMemcpyDeviceToHost, st);
     (void)hipMemcpyAsync(kfState21, d_kfIn, sizeof(float) * 21 * nKF, hipMemcpyDeviceToHost, st);
     (void)hipMemcpyAsync(mpPos, d_mpIn, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail("LocalInertialBA read-back failed");
+    if (hipStreamSynchronize(st) != hipSuccess) return iba_fail("LocalInertialBA read-back failed");
   }
   if (stats3) { stats3[0] = outer; stats3[1] = trials; stats3[2] = okFlag; }
-  cleanup();
   return MORB_OK;
 }
 

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "internal_abi.h"
+#include "ba_host.h"
 #include "dense_ldlt.h"
 #include "schur_mfma.h"
 #include "wave.h"
@@ -1030,14 +1031,9 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
   for (int i = 0; i < nKF; ++i) if (!kfFixed[i] && used[i]) kfCol[i] = nFree++;
   h.nFree = nFree; h.P = 6 * nFree;
   // CSR lists in edge-id order
-  std::vector<int> mpStart(nMP + 1, 0), kfStart(nKF + 1, 0), mpEdges(nE), kfEdges(nE);
-  for (int e = 0; e < nE; ++e) { mpStart[eMP[e] + 1]++; kfStart[eKF[e] + 1]++; }
-  for (int i = 0; i < nMP; ++i) mpStart[i + 1] += mpStart[i];
-  for (int i = 0; i < nKF; ++i) kfStart[i + 1] += kfStart[i];
-  {
-    std::vector<int> a(mpStart.begin(), mpStart.end() - 1), b(kfStart.begin(), kfStart.end() - 1);
-    for (int e = 0; e < nE; ++e) { mpEdges[a[eMP[e]]++] = e; kfEdges[b[eKF[e]]++] = e; }
-  }
+  std::vector<int> mpStart, kfStart, mpEdges, kfEdges;
+  csr_by_key(eMP, nE, nMP, mpStart, mpEdges);
+  csr_by_key(eKF, nE, nKF, kfStart, kfEdges);
   h.dupPairs = 0;
   for (int m = 0; m < nMP && !h.dupPairs; ++m)
     for (int a = mpStart[m]; a < mpStart[m + 1] && !h.dupPairs; ++a)
@@ -1084,109 +1080,79 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
     forPairs([&](int key, int ea, int eb) { pairEntries[fill[slot[key]]++] = make_int2(ea, eb); });
   }
   h.nPairs = wantPairs ? (int)pairBlock.size() : 0;
-  std::vector<int> chunkKF, chunkStart, chunkEnd, kfChunkStart(nKF + 1, 0);
-  for (int kf = 0; kf < nKF; ++kf) {
-    kfChunkStart[kf] = (int)chunkKF.size();
-    if (kfCol[kf] >= 0)
-      for (int k = kfStart[kf]; k < kfStart[kf + 1]; k += 64) { chunkKF.push_back(kf); chunkStart.push_back(k); chunkEnd.push_back(std::min(k + 64, kfStart[kf + 1])); }
-  }
-  kfChunkStart[nKF] = (int)chunkKF.size();
+  std::vector<int> chunkKF, chunkStart, chunkEnd, kfChunkStart;
+  chunks_of(kfStart, kfCol.data(), 64, chunkKF, chunkStart, chunkEnd, &kfChunkStart);
   h.nChunks = (int)chunkKF.size();
+  const morbschur::Plan sp = p->schur = morbschur::make_plan(h.P + 1, 3 * nMP);
+  std::vector<int2> blocks; std::vector<int> blkIndex;
+  schur_block_lists(sp.nb, blocks, blkIndex);
   bool fail = false;
   // Memory: every array is carved from ONE device block — uploads first, gathered in a host staging buffer and sent in ONE copy, device-only
   // arrays behind them — because ~45 hipMalloc / hipFree pairs and ~25 synchronous copies were 3.5 ms of a 4.7 ms call.  A dry run of the carve
-  // sizes the block.  The one-shot entry points (arena mode) take the block, the pinned staging buffer and the pinned words from the optimizer
-  // handle; a persistent problem (three-step API) owns its block and words.
-  bool dry = true;
-  size_t upOff = 0, devOff = 0, upCap = 0, devCap = 0;
-  char *aBase = nullptr, *stage = nullptr;
-  auto up = [&](const void* src, size_t bytes) -> void* {
-    const size_t sz = (std::max<size_t>(bytes, 8) + 255) & ~(size_t)255;
-    size_t& off = src ? upOff : devOff;
-    const size_t at = off;
-    off += sz;
-    if (dry) return nullptr;
-    if (off > (src ? upCap : devCap)) { fail = true; return nullptr; }
-    if (src) { memcpy(stage + at, src, bytes); return aBase + at; }
-    return aBase + upCap + at;
-  };
+  // sizes the block (ba_host.h).  The one-shot entry points (arena mode) take the block, the pinned staging buffer and the pinned words from the
+  // optimizer handle; a persistent problem (three-step API) owns its block and words.
+  ArenaCarver A;
   hipStream_t cst = o->stream;
   auto carve = [&]() {
-  h.kfCol = (const int*)up(kfCol.data(), sizeof(int) * nKF);
-  h.eKF = (const int*)up(eKF, sizeof(int) * nE);
-  h.eMP = (const int*)up(eMP, sizeof(int) * nE);
-  h.eObs = (const float*)up(eObs, sizeof(float) * 3 * nE);
-  h.eInfo = (const float*)up(eInvSigma2, sizeof(float) * nE);
-  h.mpStart = (const int*)up(mpStart.data(), sizeof(int) * (nMP + 1));
-  h.mpEdges = (const int*)up(mpEdges.data(), sizeof(int) * nE);
-  h.kfStart = (const int*)up(kfStart.data(), sizeof(int) * (nKF + 1));
-  h.kfEdges = (const int*)up(kfEdges.data(), sizeof(int) * nE);
-  h.pairBlock = (const int*)up(pairBlock.data(), sizeof(int) * std::max<size_t>(pairBlock.size(), 1));
-  h.pairStart = (const int*)up(pairStart.data(), sizeof(int) * pairStart.size());
-  h.pairEntries = (const int2*)up(pairEntries.data(), sizeof(int2) * pairEntries.size());
+  h.kfCol = (const int*)A.take(kfCol.data(), sizeof(int) * nKF);
+  h.eKF = (const int*)A.take(eKF, sizeof(int) * nE);
+  h.eMP = (const int*)A.take(eMP, sizeof(int) * nE);
+  h.eObs = (const float*)A.take(eObs, sizeof(float) * 3 * nE);
+  h.eInfo = (const float*)A.take(eInvSigma2, sizeof(float) * nE);
+  h.mpStart = (const int*)A.take(mpStart.data(), sizeof(int) * (nMP + 1));
+  h.mpEdges = (const int*)A.take(mpEdges.data(), sizeof(int) * nE);
+  h.kfStart = (const int*)A.take(kfStart.data(), sizeof(int) * (nKF + 1));
+  h.kfEdges = (const int*)A.take(kfEdges.data(), sizeof(int) * nE);
+  h.pairBlock = (const int*)A.take(pairBlock.data(), sizeof(int) * std::max<size_t>(pairBlock.size(), 1));
+  h.pairStart = (const int*)A.take(pairStart.data(), sizeof(int) * pairStart.size());
+  h.pairEntries = (const int2*)A.take(pairEntries.data(), sizeof(int2) * pairEntries.size());
   p->nPairEntries = wantPairs ? pairEntries.size() : nPairEntriesCount;
-  h.chunkKF = (const int*)up(chunkKF.data(), sizeof(int) * std::max<size_t>(chunkKF.size(), 1));
-  h.chunkStart = (const int*)up(chunkStart.data(), sizeof(int) * std::max<size_t>(chunkStart.size(), 1));
-  h.chunkEnd = (const int*)up(chunkEnd.data(), sizeof(int) * std::max<size_t>(chunkEnd.size(), 1));
-  h.kfChunkStart = (const int*)up(kfChunkStart.data(), sizeof(int) * (nKF + 1));
-  h.kfPart = (double*)up(nullptr, sizeof(double) * 27 * std::max<size_t>(chunkKF.size(), 1));
-  p->d_ldws = (double*)up(nullptr, sizeof(double) * morbdense::global_panel_doubles(std::max(h.P, 1)));
+  h.chunkKF = (const int*)A.take(chunkKF.data(), sizeof(int) * std::max<size_t>(chunkKF.size(), 1));
+  h.chunkStart = (const int*)A.take(chunkStart.data(), sizeof(int) * std::max<size_t>(chunkStart.size(), 1));
+  h.chunkEnd = (const int*)A.take(chunkEnd.data(), sizeof(int) * std::max<size_t>(chunkEnd.size(), 1));
+  h.kfChunkStart = (const int*)A.take(kfChunkStart.data(), sizeof(int) * (nKF + 1));
+  h.kfPart = (double*)A.take(nullptr, sizeof(double) * 27 * std::max<size_t>(chunkKF.size(), 1));
+  p->d_ldws = (double*)A.take(nullptr, sizeof(double) * morbdense::global_panel_doubles(std::max(h.P, 1)));
   p->redBlocks = div_up(std::max(std::max(nE, nMP * 16), std::max(nKF * 7, 1)), GB);   // (16 lanes per point in k_g_backsub_update_w)
-  h.redPart = (double*)up(nullptr, sizeof(double) * 2 * p->redBlocks);
-  h.scal = (double*)up(nullptr, sizeof(double) * 8);
-  {
-    const morbschur::Plan sp = morbschur::make_plan(h.P + 1, 3 * nMP);
-    p->schur = sp;
-    std::vector<int2> blocks; std::vector<int> blkIndex((size_t)sp.nb * sp.nb, 0);
-    for (int bi = 0; bi < sp.nb; ++bi) for (int bj = bi; bj < sp.nb; ++bj) { blkIndex[(size_t)bi * sp.nb + bj] = (int)blocks.size(); blocks.push_back(make_int2(bi, bj)); }
-    h.sW = (double*)up(nullptr, sizeof(double) * sp.wElems());
-    h.sWD = (double*)up(nullptr, sizeof(double) * sp.wElems());
-    if (!dry && !fail && (hipMemsetAsync(h.sW, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
-                          hipMemsetAsync(h.sWD, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess)) fail = true;
-    h.sPart = (double*)up(nullptr, sizeof(double) * sp.partElems());
-    h.sBlocks = (const int2*)up(blocks.data(), sizeof(int2) * blocks.size());
-    h.sBlkIndex = (const int*)up(blkIndex.data(), sizeof(int) * blkIndex.size());
-    h.sMp = sp.Mp; h.sNb = sp.nb; h.sNblk = sp.nblk; h.sNsplit = sp.nsplit;
-  }
+  h.redPart = (double*)A.take(nullptr, sizeof(double) * 2 * p->redBlocks);
+  h.scal = (double*)A.take(nullptr, sizeof(double) * 8);
+  h.sW = (double*)A.take(nullptr, sizeof(double) * sp.wElems());
+  h.sWD = (double*)A.take(nullptr, sizeof(double) * sp.wElems());
+  h.sPart = (double*)A.take(nullptr, sizeof(double) * sp.partElems());
+  h.sBlocks = (const int2*)A.take(blocks.data(), sizeof(int2) * blocks.size());
+  h.sBlkIndex = (const int*)A.take(blkIndex.data(), sizeof(int) * blkIndex.size());
+  h.sMp = sp.Mp; h.sNb = sp.nb; h.sNblk = sp.nblk; h.sNsplit = sp.nsplit;
   const size_t nx = (size_t)h.P + 3 * (size_t)nMP;
-  h.pose = (double*)up(nullptr, sizeof(double) * 7 * nKF);
-  h.poseBk = (double*)up(nullptr, sizeof(double) * 7 * nKF);
-  h.poseEval = (double*)up(nullptr, sizeof(double) * 7 * nKF);
-  h.pt = (double*)up(nullptr, sizeof(double) * 3 * nMP);
-  h.ptBk = (double*)up(nullptr, sizeof(double) * 3 * nMP);
-  h.ptEval = (double*)up(nullptr, sizeof(double) * 3 * nMP);
-  h.Hpp = (double*)up(nullptr, sizeof(double) * 36 * std::max(nFree, 1));
-  h.Hll = (double*)up(nullptr, sizeof(double) * 9 * nMP);
-  h.Dinv = (double*)up(nullptr, sizeof(double) * 9 * nMP);
-  h.Hpl = (double*)up(nullptr, sizeof(double) * 18 * nE);
-  h.b = (double*)up(nullptr, sizeof(double) * nx);
-  h.x = (double*)up(nullptr, sizeof(double) * nx);
-  h.HsG = (double*)up(nullptr, sizeof(double) * std::max<size_t>((size_t)h.P * h.P, 1));
-  h.poseIO = (float*)up(nullptr, sizeof(float) * 7 * nKF);
-  h.ptIO = (float*)up(nullptr, sizeof(float) * 3 * nMP);
-  h.erase = (uint8_t*)up(nullptr, nE);
-  h.stats = (int*)up(nullptr, sizeof(int) * 2);
-  h.lmd = (double*)up(nullptr, sizeof(double) * 4);
-  h.kfTicket = (int*)up(nullptr, sizeof(int) * std::max(nKF, 1));
-  if (!dry && !fail && hipMemsetAsync(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1), cst) != hipSuccess) fail = true;
-  h.lmi = (int*)up(nullptr, sizeof(int) * 16);
-  // mapped host words: [0] morb_ba_set_stop, [1] the caller's *pbStopFlag as the host loop forwards it, [4..7] the LM state mirror
-  if (!dry) {
-    int *hw = nullptr, *dv = nullptr;
-    if (arena) { if (morb_optimizer_lm_words(o, &hw, &dv) != MORB_OK) fail = true; }
-    else if (p->words.alloc(sizeof(int) * 16, hipHostMallocMapped) != hipSuccess) fail = true;
-    else { hw = p->words; dv = p->words.dev(); }
-    if (hw) { memset(hw, 0, sizeof(int) * 16); p->h_stop = hw; h.stop = dv; h.lmHost = dv + 4; }
-  }
+  h.pose = (double*)A.take(nullptr, sizeof(double) * 7 * nKF);
+  h.poseBk = (double*)A.take(nullptr, sizeof(double) * 7 * nKF);
+  h.poseEval = (double*)A.take(nullptr, sizeof(double) * 7 * nKF);
+  h.pt = (double*)A.take(nullptr, sizeof(double) * 3 * nMP);
+  h.ptBk = (double*)A.take(nullptr, sizeof(double) * 3 * nMP);
+  h.ptEval = (double*)A.take(nullptr, sizeof(double) * 3 * nMP);
+  h.Hpp = (double*)A.take(nullptr, sizeof(double) * 36 * std::max(nFree, 1));
+  h.Hll = (double*)A.take(nullptr, sizeof(double) * 9 * nMP);
+  h.Dinv = (double*)A.take(nullptr, sizeof(double) * 9 * nMP);
+  h.Hpl = (double*)A.take(nullptr, sizeof(double) * 18 * nE);
+  h.b = (double*)A.take(nullptr, sizeof(double) * nx);
+  h.x = (double*)A.take(nullptr, sizeof(double) * nx);
+  h.HsG = (double*)A.take(nullptr, sizeof(double) * std::max<size_t>((size_t)h.P * h.P, 1));
+  h.poseIO = (float*)A.take(nullptr, sizeof(float) * 7 * nKF);
+  h.ptIO = (float*)A.take(nullptr, sizeof(float) * 3 * nMP);
+  h.erase = (uint8_t*)A.take(nullptr, nE);
+  h.stats = (int*)A.take(nullptr, sizeof(int) * 2);
+  h.lmd = (double*)A.take(nullptr, sizeof(double) * 4);
+  h.kfTicket = (int*)A.take(nullptr, sizeof(int) * std::max(nKF, 1));
+  h.lmi = (int*)A.take(nullptr, sizeof(int) * 16);
   h.cam = Cam{fx, fy, cx, cy, bf};
-  h.rig = rig ? (const Rig*)up(rig, sizeof(Rig)) : nullptr;
+  h.rig = rig ? (const Rig*)A.take(rig, sizeof(Rig)) : nullptr;
   h.userLambda = lambdaInit100 ? 100.0 : 0.0;
-  p->d_pose0 = (float*)up(kfPose, sizeof(float) * 7 * nKF);
-  p->d_pt0 = (float*)up(mpPos, sizeof(float) * 3 * nMP);
-  p->d_desc = (BaDev*)up(&h, sizeof(BaDev));
+  p->d_pose0 = (float*)A.take(kfPose, sizeof(float) * 7 * nKF);
+  p->d_pt0 = (float*)A.take(mpPos, sizeof(float) * 3 * nMP);
+  p->d_desc = (BaDev*)A.take(&h, sizeof(BaDev));
   };   // carve
   carve();   // (dry: sizes)
-  upCap = upOff; devCap = devOff; upOff = devOff = 0; dry = false;
+  const size_t upCap = A.uploadBytes(), devCap = A.deviceBytes();
+  char *aBase = nullptr, *stage = nullptr;
   std::vector<char> hostStage;   // a persistent problem's staging: pageable, the upload is waited for below
   if (arena) {
     if (grow(o->work, upCap + devCap, &aBase) != MORB_OK || grow(o->stage, upCap, &stage) != MORB_OK) fail = true;
@@ -1195,8 +1161,19 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
     hostStage.resize(upCap);
     aBase = (char*)p->mem.get(); stage = hostStage.data();
   }
+  if (!fail) {   // mapped host words: [0] morb_ba_set_stop, [1] the caller's *pbStopFlag as the host loop forwards it, [4..7] the LM state mirror
+    int *hw = nullptr, *dv = nullptr;
+    if (arena) { if (morb_optimizer_lm_words(o, &hw, &dv) != MORB_OK) fail = true; }
+    else if (p->words.alloc(sizeof(int) * 16, hipHostMallocMapped) != hipSuccess) fail = true;
+    else { hw = p->words; dv = p->words.dev(); }
+    if (hw) { memset(hw, 0, sizeof(int) * 16); p->h_stop = hw; h.stop = dv; h.lmHost = dv + 4; }
+  }
   if (!fail) {
-    carve();
+    A.bind(aBase, stage);
+    carve();   // (the descriptor it stages last holds the pointers it has just assigned, and the words above)
+    if (!A.ok() || hipMemsetAsync(h.sW, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
+        hipMemsetAsync(h.sWD, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
+        hipMemsetAsync(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1), cst) != hipSuccess) fail = true;
     if (!fail && hipMemcpyAsync(aBase, stage, upCap, hipMemcpyHostToDevice, cst) != hipSuccess) fail = true;   // the one upload
     // a persistent problem is complete when create returns (like the synchronous copies it was once made with): it may be solved on any stream
     if (!fail && !arena && hipStreamSynchronize(cst) != hipSuccess) fail = true;
