@@ -9,27 +9,19 @@
 //   * nmp_point_fields, nmp_descriptor_from_kf2: mNormalVector, mfMaxDistance, mfMinDistance and which descriptor wins;
 //   * nmp_pair_gate (host): the baseline test in front of the search (:454-466).
 // Conventions: a pose is a 3 x 4 row-major [R | t]; 3 x 3 products sum k = 0, 1, 2 left to right; the null vector
-// of the 4 x 4 system is the FP64 cyclic Jacobi of A^T A that two_view.hip and fisheye.hip use in place of Eigen's JacobiSVD.  The device
-// takes atan2f / cosf / sinf / tanf from csrc/libm_f32.h (glibc's results bit for bit); the host takes them from its libm.
+// of the 4 x 4 system, the two camera models and the float libm they call are camera_math.h's.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
+#include "camera_math.h"
+
 #if defined(__HIPCC__)
-#include "libm_f32.h"   // (csrc/ is on the include path of the library's build)
 #define MORB_NMP_FN __host__ __device__ __forceinline__
 #define MORB_NMP_UNROLL _Pragma("unroll")
-#define MORB_NMP_ATAN2F(y, x) ::morbm::atan2f_glibc(y, x)
-#define MORB_NMP_COSF(x) ::morbm::cosf_glibc(x)
-#define MORB_NMP_SINF(x) ::morbm::sinf_glibc(x)
-#define MORB_NMP_TANF(x) ::morbm::tanf_glibc(x)
 #else
 #define MORB_NMP_FN inline
 #define MORB_NMP_UNROLL
-#define MORB_NMP_ATAN2F(y, x) std::atan2((float)(y), (float)(x))
-#define MORB_NMP_COSF(x) std::cos((float)(x))
-#define MORB_NMP_SINF(x) std::sin((float)(x))
-#define MORB_NMP_TANF(x) std::tan((float)(x))
 #endif
 
 // X(name): one list for the enum and for the Python front's tuple (matcher.NEW_MAP_POINT_STATUS)
@@ -60,103 +52,13 @@ enum NewMapPointStatus { MORB_NMP_STATUS(MORB_NMP_X) NMP_STATUS_LEN };
 enum NewMapPointStat { MORB_NMP_STATS(MORB_NMP_X) NMP_STATS_LEN };
 #undef MORB_NMP_X
 
+using morbcam::Camera;   // the camera of a Side, as this namespace's users name it
+
 MORB_NMP_FN bool nmp_created(int status) { return status == NMP_TRIANGULATED || status == NMP_STEREO1 || status == NMP_STEREO2; }
 
 constexpr int NMP_POSE = 12;              // floats of one 3 x 4 pose
 constexpr int NMP_PAIR_POSES = 4;         // pinhole pair: Tcw1, Twc1, Tcw2, Twc2
 constexpr int NMP_PAIR_POSES_RIG = 8;     // rig pair: Tcw1, Twc1, Trw1, Twr1, Tcw2, Twc2, Trw2, Twr2 (left pose, its inverse, right pose, its inverse)
-
-// GeometricCamera as one record: p = fx fy cx cy (Pinhole), then k0..k3 (KannalaBrandt8)
-struct Camera { int kb8; float p[8]; };
-
-// unprojectEig(cv::Point2f): Pinhole.cpp:60-63, KannalaBrandt8.cpp:100-137
-MORB_NMP_FN void nmp_unproject(const Camera& c, float px, float py, float* ray) {
-  if (!c.kb8) {
-    ray[0] = (px - c.p[2]) / c.p[0];
-    ray[1] = (py - c.p[3]) / c.p[1];
-    ray[2] = 1.f;
-    return;
-  }
-  const float pwx = (px - c.p[2]) / c.p[0], pwy = (py - c.p[3]) / c.p[1];
-  float scale = 1.f;
-  float theta_d = sqrtf(pwx * pwx + pwy * pwy);
-  theta_d = fminf(fmaxf((float)(-3.14159265358979323846 / 2.f), theta_d), (float)(3.14159265358979323846 / 2.f));
-  if (theta_d > 1e-8f) {
-    float theta = theta_d;
-    for (int j = 0; j < 10; j++) {
-      const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
-      const float k0 = c.p[4] * theta2, k1 = c.p[5] * theta4, k2 = c.p[6] * theta6, k3 = c.p[7] * theta8;
-      const float fix = (theta * (1 + k0 + k1 + k2 + k3) - theta_d) / (1 + 3 * k0 + 5 * k1 + 7 * k2 + 9 * k3);
-      theta = theta - fix;
-      if (fabsf(fix) < 1e-6f) break;
-    }
-    scale = MORB_NMP_TANF(theta) / theta_d;
-  }
-  ray[0] = pwx * scale; ray[1] = pwy * scale; ray[2] = 1.f;
-}
-
-// project(cv::Point3f): Pinhole.cpp:46-52, KannalaBrandt8.cpp:49-67
-MORB_NMP_FN void nmp_project(const Camera& c, float x, float y, float z, float* uv) {
-  if (!c.kb8) {
-    uv[0] = c.p[0] * x / z + c.p[2];
-    uv[1] = c.p[1] * y / z + c.p[3];
-    return;
-  }
-  const float x2_plus_y2 = x * x + y * y;
-  const float theta = MORB_NMP_ATAN2F(sqrtf(x2_plus_y2), z);
-  const float psi = MORB_NMP_ATAN2F(y, x);
-  const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2, theta9 = theta7 * theta2;
-  const float r = theta + c.p[4] * theta3 + c.p[5] * theta5 + c.p[6] * theta7 + c.p[7] * theta9;
-  uv[0] = c.p[0] * r * MORB_NMP_COSF(psi) + c.p[2];
-  uv[1] = c.p[1] * r * MORB_NMP_SINF(psi) + c.p[3];
-}
-
-// The right singular vector of the smallest singular value of the 4 x 4 float A (row-major): A^T A in FP64, cyclic Jacobi, 30 sweeps,
-// rotations skipped when a_pq == 0, the eigenvector of the first smallest eigenvalue.  Every index is a constant once unrolled, so
-// that on the device M and V are 32 FP64 registers and not scratch memory.
-MORB_NMP_FN void nmp_null_vector4(const float* A, double* out) {
-  double M[16], V[16];
-  MORB_NMP_UNROLL
-  for (int i = 0; i < 4; ++i) {
-    MORB_NMP_UNROLL
-    for (int j = 0; j < 4; ++j) {
-      double s = 0;
-      MORB_NMP_UNROLL
-      for (int k = 0; k < 4; ++k) s += (double)A[k * 4 + i] * (double)A[k * 4 + j];
-      M[i * 4 + j] = s;
-      V[i * 4 + j] = i == j ? 1.0 : 0.0;
-    }
-  }
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    MORB_NMP_UNROLL
-    for (int p = 0; p < 3; ++p) {
-      MORB_NMP_UNROLL
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = M[p * 4 + q];
-        if (apq == 0.0) continue;
-        const double tau = (M[q * 4 + q] - M[p * 4 + p]) / (2.0 * apq);
-        const double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-        const double cs = 1.0 / sqrt(1.0 + t * t), sn = t * cs;
-        MORB_NMP_UNROLL
-        for (int k = 0; k < 4; ++k) { const double a = M[k * 4 + p], b = M[k * 4 + q]; M[k * 4 + p] = cs * a - sn * b; M[k * 4 + q] = sn * a + cs * b; }
-        MORB_NMP_UNROLL
-        for (int k = 0; k < 4; ++k) { const double a = M[p * 4 + k], b = M[q * 4 + k]; M[p * 4 + k] = cs * a - sn * b; M[q * 4 + k] = sn * a + cs * b; }
-        MORB_NMP_UNROLL
-        for (int k = 0; k < 4; ++k) { const double a = V[k * 4 + p], b = V[k * 4 + q]; V[k * 4 + p] = cs * a - sn * b; V[k * 4 + q] = sn * a + cs * b; }
-      }
-    }
-  }
-  double bestVal = M[0];
-  MORB_NMP_UNROLL
-  for (int k = 0; k < 4; ++k) out[k] = V[k * 4];
-  MORB_NMP_UNROLL
-  for (int i = 1; i < 4; ++i)
-    if (M[i * 4 + i] < bestVal) {
-      bestVal = M[i * 4 + i];
-      MORB_NMP_UNROLL
-      for (int k = 0; k < 4; ++k) out[k] = V[k * 4 + i];
-    }
-}
 
 // GeometricTools::Triangulate: x3Dh is a Vector4f, the test and the division are float
 MORB_NMP_FN bool nmp_triangulate(const float* x_c1, const float* x_c2, const float* Tc1w, const float* Tc2w, float* x3D) {
@@ -169,7 +71,7 @@ MORB_NMP_FN bool nmp_triangulate(const float* x_c1, const float* x_c2, const flo
     A[12 + k] = x_c2[1] * Tc2w[8 + k] - Tc2w[4 + k];
   }
   double xh[4];
-  nmp_null_vector4(A, xh);
+  morbcam::null_vector4(A, xh);
   const float w = (float)xh[3];
   if (w == 0) return false;
   x3D[0] = (float)xh[0] / w; x3D[1] = (float)xh[1] / w; x3D[2] = (float)xh[2] / w;
@@ -225,8 +127,8 @@ MORB_NMP_FN int nmp_decide(const Params& P, const Side& s1, const Side& s2, floa
   const float* Tcw1 = s1.Tcw;
   const float* Tcw2 = s2.Tcw;
   float xn1[3], xn2[3], ray1[3], ray2[3];
-  nmp_unproject(s1.cam, s1.x, s1.y, xn1);
-  nmp_unproject(s2.cam, s2.x, s2.y, xn2);
+  morbcam::unproject(s1.cam, s1.x, s1.y, xn1);
+  morbcam::unproject(s2.cam, s2.x, s2.y, xn2);
   // ray = Rwc * xn with Rwc = Rcw.transpose()
   MORB_NMP_UNROLL
   for (int i = 0; i < 3; ++i) {
@@ -241,9 +143,9 @@ MORB_NMP_FN int nmp_decide(const Params& P, const Side& s1, const Side& s2, floa
   const bool bStereo1 = s1.bStereo != 0, bStereo2 = s2.bStereo != 0;
   // cos(2 * atan2(mb / 2, mvDepth[idx])): float overloads (mpCurrentKeyFrame->mb, then pKF2->mb)
   if (bStereo1)
-    cosParallaxStereo1 = MORB_NMP_COSF(2 * MORB_NMP_ATAN2F(P.mb / 2, s1.depth));
+    cosParallaxStereo1 = MORB_CAM_COSF(2 * MORB_CAM_ATAN2F(P.mb / 2, s1.depth));
   else if (bStereo2)
-    cosParallaxStereo2 = MORB_NMP_COSF(2 * MORB_NMP_ATAN2F(P.mb / 2, s2.depth));
+    cosParallaxStereo2 = MORB_CAM_COSF(2 * MORB_CAM_ATAN2F(P.mb / 2, s2.depth));
   int flags = (bStereo1 || bStereo2) ? 1 : 0;
   cosParallaxStereo = fminf(cosParallaxStereo1, cosParallaxStereo2);
 
@@ -284,8 +186,9 @@ MORB_NMP_FN int nmp_decide(const Params& P, const Side& s1, const Side& s2, floa
   const float y1 = nmp_row_dot(Tcw1, 1, x3D) + Tcw1[7];
   const float invz1 = (float)(1.0 / (double)z1);
   if (!bStereo1) {
+    const float Xc1[3] = {x1, y1, z1};
     float uv1[2];
-    nmp_project(s1.cam, x1, y1, z1, uv1);
+    morbcam::project(s1.cam, Xc1, uv1[0], uv1[1]);
     const float errX1 = uv1[0] - s1.x;
     const float errY1 = uv1[1] - s1.y;
     if ((double)(errX1 * errX1 + errY1 * errY1) > 5.991 * (double)sigmaSquare1) return NMP_REPROJ1;
@@ -305,8 +208,9 @@ MORB_NMP_FN int nmp_decide(const Params& P, const Side& s1, const Side& s2, floa
   const float y2 = nmp_row_dot(Tcw2, 1, x3D) + Tcw2[7];
   const float invz2 = (float)(1.0 / (double)z2);
   if (!bStereo2) {
+    const float Xc2[3] = {x2, y2, z2};
     float uv2[2];
-    nmp_project(s2.cam, x2, y2, z2, uv2);
+    morbcam::project(s2.cam, Xc2, uv2[0], uv2[1]);
     const float errX2 = uv2[0] - s2.x;
     const float errY2 = uv2[1] - s2.y;
     if ((double)(errX2 * errX2 + errY2 * errY2) > 5.991 * (double)sigmaSquare2) return NMP_REPROJ2;

@@ -11,20 +11,17 @@
 
 #include "common.h"
 #include "handles.h"
-#include "kb8.h"
+#include "morb/camera_math.h"
 
 using namespace morb;
 
 namespace {
 
-using morbkb8::KB8;
-using morbkb8::kb8_project_f;
-using morbkb8::kb8_unproject;
-struct RigF { KB8 cl, cr; float Rlr[9], tlr[3]; float sigma2[16]; };
+struct RigF { float cl[8], cr[8]; float Rlr[9], tlr[3]; float sigma2[16]; };
 
 __device__ __forceinline__ float triangulate_matches(const RigF& g, float x1, float y1, float x2, float y2, float sigma1, float unc,
                                                       float* p3D) {
-  return morbkb8::triangulate_matches(g.cl, g.cr, g.Rlr, g.tlr, x1, y1, x2, y2, sigma1, unc, p3D);
+  return morbcam::triangulate_matches(g.cl, g.cr, g.Rlr, g.tlr, x1, y1, x2, y2, sigma1, unc, p3D);
 }
 
 __global__ void k_fe_prepare(const int* __restrict__ count, const int* __restrict__ mono, int nframes, int* __restrict__ nq,
@@ -78,7 +75,7 @@ extern "C" int morb_stereo_fisheye_match_batch(morb_matcher* m, int nframes, con
   MORB_ENTER(st, m, stream);
   RigF g;
   memset(&g, 0, sizeof g);
-  memcpy(g.cl.p, camL8, 32); memcpy(g.cr.p, camR8, 32);
+  memcpy(g.cl, camL8, 32); memcpy(g.cr, camR8, 32);
   memcpy(g.Rlr, Rlr9, 36); memcpy(g.tlr, tlr3, 12);
   memcpy(g.sigma2, levelSigma2, sizeof(float) * nlevels);
   // (queries / candKeys / candCount hold these across morb_hamming_knn2_batch below, which takes no workspace)

@@ -23,7 +23,7 @@
 #include "internal_abi.h"
 #include "ba_host.h"
 #include "libm_f32.h"
-#include "kb8.h"
+#include "morb/camera_math.h"
 #include "dense_ldlt.h"
 #include "schur_mfma.h"
 #include "wave.h"
@@ -457,7 +457,7 @@ __device__ __forceinline__ double vis_error_t(const CamGeom& g, const VIState& S
   if (RIG && cam) { mul3v(S.Rcw1, X, Xc); for (int k = 0; k < 3; ++k) Xc[k] += S.tcw1[k]; }
   else { mul3v(S.Rcw, X, Xc); for (int k = 0; k < 3; ++k) Xc[k] += S.tcw[k]; }
   double u, v;
-  if (RIG) { double uv[2]; float kp[8]; kb_of(g, cam, kp); morbkb8::kb8_project_d(kp, Xc, uv); u = uv[0]; v = uv[1]; }   // KannalaBrandt8::project(Vector3d)
+  if (RIG) { double uv[2]; float kp[8]; kb_of(g, cam, kp); morbcam::kb8_project_d(kp, Xc, uv); u = uv[0]; v = uv[1]; }   // KannalaBrandt8::project(Vector3d)
   else { u = g.fx * Xc[0] / Xc[2] + g.cx; v = g.fy * Xc[1] / Xc[2] + g.cy; }                       // Pinhole.cpp:38-44
   err[0] = (double)o[0] - u; err[1] = (double)o[1] - v; err[2] = 0;
   double c = err[0] * info * err[0] + err[1] * info * err[1];
@@ -471,7 +471,7 @@ __device__ __forceinline__ double vis_error(const CamGeom& g, const VIState& S, 
 // projectJac of the edge's camera (2 x 3 in pj[0..5]); pinhole: Pinhole.cpp:76-86
 template <bool RIG>
 __device__ __forceinline__ void cam_project_jac_t(const CamGeom& g, const double* Xc, int cam, double* pj) {
-  if (RIG) { float kp[8]; kb_of(g, cam, kp); morbkb8::kb8_project_jac(kp, Xc, pj); return; }
+  if (RIG) { float kp[8]; kb_of(g, cam, kp); morbcam::kb8_project_jac(kp, Xc, pj); return; }
   pj[0] = g.fx / Xc[2]; pj[1] = 0; pj[2] = -g.fx * Xc[0] / (Xc[2] * Xc[2]);
   pj[3] = 0; pj[4] = g.fy / Xc[2]; pj[5] = -g.fy * Xc[1] / (Xc[2] * Xc[2]);
 }

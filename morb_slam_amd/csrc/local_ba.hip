@@ -60,8 +60,8 @@ __device__ __forceinline__ double ba_edge_error(const Cam& cam, const Rig* rig, 
                                                 double info, double* err) {
   if (!edge_is_kb8(rig, o)) return edge_error(cam, st, xc, o, info, err);
   double uv[2];
-  if (o[2] > -2.5f) kb8_project_d(rig->kbL, xc, uv);
-  else { double xr[3]; se3_map(rig->Trl, xc, xr); kb8_project_d(rig->kbR, xr, uv); }   // (mTrl * T).map(Xw) = mTrl.map(T.map(Xw))
+  if (o[2] > -2.5f) morbcam::kb8_project_d(rig->kbL, xc, uv);
+  else { double xr[3]; se3_map(rig->Trl, xc, xr); morbcam::kb8_project_d(rig->kbR, xr, uv); }   // (mTrl * T).map(Xw) = mTrl.map(T.map(Xw))
   err[0] = (double)o[0] - uv[0]; err[1] = (double)o[1] - uv[1]; err[2] = 0;
   return err[0] * (info * err[0]) + err[1] * (info * err[1]);
 }
@@ -81,12 +81,12 @@ __device__ __forceinline__ void ba_edge_jac(const Cam& cam, const Rig* rig, bool
   const double x = xc[0], y = xc[1], z = xc[2];
   double pj[6], pjM[6];
   if (o[2] > -2.5f) {
-    kb8_project_jac(rig->kbL, xc, pj);
+    morbcam::kb8_project_jac(rig->kbL, xc, pj);
     _Pragma("unroll") for (int k = 0; k < 6; ++k) pjM[k] = pj[k];
   } else {
     double xr[3], M[9];
     se3_map(rig->Trl, xc, xr);
-    kb8_project_jac(rig->kbR, xr, pj);
+    morbcam::kb8_project_jac(rig->kbR, xr, pj);
     q_to_R(rig->Trl.q, M);
     _Pragma("unroll") for (int r = 0; r < 2; ++r)
       _Pragma("unroll") for (int c = 0; c < 3; ++c) pjM[r * 3 + c] = pj[r * 3] * M[c] + pj[r * 3 + 1] * M[3 + c] + pj[r * 3 + 2] * M[6 + c];

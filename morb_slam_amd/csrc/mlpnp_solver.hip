@@ -1,7 +1,7 @@
 // MLPnPsolver (reference src/MLPnPsolver.cpp) for MI355X (gfx950), batched: one 256-thread workgroup per problem (a frame and the map
 // points one relocalisation candidate matched to it).  Each call restates
 //   * the constructor (:55-97): the kept matches compacted in feature order (ransac_block.h), bearing vectors unproject(kp.pt) / z
-//     in float (cam_unproject of kb8.h: Pinhole, or KannalaBrandt8's Newton unprojection), world points, sigma2;
+//     in float (unproject of morb/camera_math.h: Pinhole, or KannalaBrandt8's Newton unprojection), world points, sigma2;
 //   * SetRansacParameters (:225-260) from the device-side N (include/morb/mlpnp_solver_math.h, ransac_math.h);
 //   * iterate (:100-223) from state.iterations on: DUtils::Random::RandomInt + swap-with-back sampling on the caller's rand() values
 //     (minSet per iteration, indexed by the global iteration number), computePose (:356-658) in FP64, CheckInliers (:262-293) in
@@ -19,7 +19,7 @@
 
 #include "common.h"
 #include "handles.h"
-#include "kb8.h"
+#include "morb/camera_math.h"
 #include "libm_f32.h"
 #include "morb_hip.h"
 #include "morb/mlpnp_solver_math.h"
@@ -43,9 +43,7 @@ constexpr int MP_MAXSET = 16;          // largest minSet
 constexpr double MP_EPS = 2.220446049250313e-16;
 static_assert(MP_NT % 64 == 0 && MP_NT >= 64, "whole waves");
 
-using morbkb8::Cam;
-using morbkb8::cam_project;
-using morbkb8::cam_unproject;
+using morbcam::Camera;
 using namespace morbransac;
 using morbrow::g_jacobi;
 
@@ -507,13 +505,13 @@ __device__ __forceinline__ void g_compute_pose(Grp& g, const Corr& C, const int*
 struct Pose { double R[9], t[3]; };
 
 // CheckInliers' test of correspondence i (:265-292): R X + t in double, rounded to float, projected in float
-__device__ __forceinline__ bool is_inlier(const Corr& C, int i, const Pose& P, const Cam& cam) {
+__device__ __forceinline__ bool is_inlier(const Corr& C, int i, const Pose& P, const Camera& cam) {
   const int S = C.stride;
   const double x = (double)C.X[i], y = (double)C.X[S + i], z = (double)C.X[2 * S + i];
   float Pc[3], uv[2];
 #pragma unroll
   for (int r = 0; r < 3; ++r) Pc[r] = (float)(P.R[r * 3] * x + P.R[r * 3 + 1] * y + P.R[r * 3 + 2] * z + P.t[r]);
-  cam_project(cam, Pc, uv);
+  morbcam::project(cam, Pc, uv[0], uv[1]);
   const float dx = C.uv[i] - uv[0], dy = C.uv[S + i] - uv[1];
   const float e2 = dx * dx + dy * dy;
   return e2 < C.err[i];
@@ -538,7 +536,7 @@ __device__ __forceinline__ void pose_to_tcw(const Pose& P, float* T) {   // Rcw 
   }
 }
 
-__device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n, int cap, const morb_mlpnp_solver_params& prm, const Cam& cam,
+__device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n, int cap, const morb_mlpnp_solver_params& prm, const Camera& cam,
                                       const uint8_t* __restrict__ d_entry, const float* __restrict__ d_uv, const float* __restrict__ d_sigma2,
                                       const float* __restrict__ d_Xw, int nIterations, const int* __restrict__ d_rand, int randCap,
                                       morb_mlpnp_solver_state* __restrict__ d_state, uint8_t* d_best, uint8_t* __restrict__ d_inliers,
@@ -554,7 +552,7 @@ __device__ __forceinline__ void solve(MpShared& sh, const Corr& C, int p, int n,
     if (valid) {
       const float u = d_uv[(pc + i) * 2], v = d_uv[(pc + i) * 2 + 1];
       float ray[3];
-      cam_unproject(cam, u, v, ray);
+      morbcam::unproject(cam, u, v, ray);
       C.br[c] = ray[0] / ray[2]; C.br[S + c] = ray[1] / ray[2];   // cv_br /= cv_br.z: not a unit vector
 #pragma unroll
       for (int r = 0; r < 3; ++r) C.X[r * S + c] = d_Xw[(pc + i) * 3 + r];
@@ -731,9 +729,9 @@ __global__ __launch_bounds__(MP_NT) void k_mlpnp_solver(int cap, const morb_mlpn
     }
     return;
   }
-  Cam cam;
+  Camera cam;
   cam.kb8 = prm.cam[0] != 0.f;
-  for (int i = 0; i < 8; ++i) cam.k.p[i] = prm.cam[1 + i];
+  for (int i = 0; i < 8; ++i) cam.p[i] = prm.cam[1 + i];
   // vbInliers = vector<bool>(size, false); mvbBestInliers is empty until an iteration reaches minInliers
   const bool firstBest = d_state[p].bestInliers == 0;
   for (int i = t; i < cap; i += MP_NT) {

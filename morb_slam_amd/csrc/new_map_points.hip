@@ -1,7 +1,7 @@
 // LocalMapping::CreateNewMapPoints between SearchForTriangulation and Fuse (reference src/LocalMapping.cc:489-709): per match the
 // parallax test, Triangulate or UnprojectStereo, the depth, reprojection and scale tests, and the fields a new MapPoint gets from
-// ComputeDistinctiveDescriptors and UpdateNormalAndDepth.  The arithmetic is include/morb/new_map_points_math.h, which the CPU oracle
-// compiles too; this file is the mapping onto the device.
+// ComputeDistinctiveDescriptors and UpdateNormalAndDepth.  The arithmetic is include/morb/new_map_points_math.h (over
+// morb/camera_math.h), which the CPU oracle compiles too; this file is the mapping onto the device.
 //
 // k_new_map_points: one workgroup of 256 threads per keyframe pair.
 //   phase 1  the non-negative entries of the pair's match12 row are compacted into LDS in ascending i (ballot + prefix per wave, wave
@@ -11,7 +11,7 @@
 //            byte stores of 1 into d_hasMP (AddMapPoint, :700-701).
 //   counters per-thread integers, summed by a DPP wave reduction and then over the four waves: no atomics, a rerun is bit-identical.
 // 256 threads: a neighbour pair has a few hundred matches at most, so one pass of phase 2 covers it; the kernel's registers (the
-// Jacobi's 32 doubles, the poses, the KB8 polynomial: 223 VGPRs) allow two waves per SIMD whatever the block size, i.e. two such
+// Jacobi's 32 doubles, the poses, the KB8 polynomial: 185 VGPRs) allow two waves per SIMD whatever the block size, i.e. two such
 // workgroups per CU.  LDS is 4 * cap bytes of list.  DESIGN.md section 6 has the code object's figures and the timings.
 #include <vector>
 

@@ -114,8 +114,8 @@ __device__ __forceinline__ double pose_edge_error(const Cam& cam, const Rig& rig
   }
   st = false;
   double uv[2];
-  if (!right) kb8_project_d(rig.kbL, xc, uv);                       // EdgeSE3ProjectXYZOnlyPose, pCamera = left KB8
-  else { double xr[3]; se3_map(Pr, X, xr); kb8_project_d(rig.kbR, xr, uv); }   // ...ToBody: (mTrl * T).map(Xw)
+  if (!right) morbcam::kb8_project_d(rig.kbL, xc, uv);                       // EdgeSE3ProjectXYZOnlyPose, pCamera = left KB8
+  else { double xr[3]; se3_map(Pr, X, xr); morbcam::kb8_project_d(rig.kbR, xr, uv); }   // ...ToBody: (mTrl * T).map(Xw)
   err[0] = (double)o[0] - uv[0]; err[1] = (double)o[1] - uv[1]; err[2] = 0;
   return err[0] * (info * err[0]) + err[1] * (info * err[1]);
 }
@@ -126,12 +126,12 @@ __device__ __forceinline__ void pose_edge_jac(const Cam& cam, const Rig& rig, bo
   const double x = xc[0], y = xc[1], z = xc[2];
   double pj[6], pjM[6];
   if (!right) {
-    kb8_project_jac(rig.kbL, xc, pj);
+    morbcam::kb8_project_jac(rig.kbL, xc, pj);
     for (int k = 0; k < 6; ++k) pjM[k] = pj[k];
   } else {  // -projectJac(X_r) * R_rl * SE3deriv(X_l), X_r = mTrl.map(T.map(Xw))  (OptimizableTypes.cpp:88-104)
     double xr[3], M[9];
     se3_map(rig.Trl, xc, xr);
-    kb8_project_jac(rig.kbR, xr, pj);
+    morbcam::kb8_project_jac(rig.kbR, xr, pj);
     q_to_R(rig.Trl.q, M);
     for (int r = 0; r < 2; ++r)
       for (int c = 0; c < 3; ++c) pjM[r * 3 + c] = pj[r * 3] * M[c] + pj[r * 3 + 1] * M[3 + c] + pj[r * 3 + 2] * M[6 + c];

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "kb8.h"
+#include "morb/camera_math.h"
 #include "quat_huber.h"
 #include "wave.h"
 
@@ -203,8 +203,6 @@ struct Rig {            // fisheye stereo rig: left / right KB8 cameras and mTrl
   float kbL[8], kbR[8];
   SE3 Trl;
 };
-using morbkb8::kb8_project_d;
-using morbkb8::kb8_project_jac;
 
 // the fisheye rig of a call: KB8 cameras and Trl7 = (qx, qy, qz, qw, tx, ty, tz)
 inline Rig make_rig(const float* camL8, const float* camR8, const float* Trl7) {

@@ -21,10 +21,10 @@
 
 #include "common.h"
 #include "internal_abi.h"
-#include "libm_f32.h"
+#include "quat_huber.h"
 #include "search_tier.h"
 #include "wave.h"
-#include "kb8.h"
+#include "morb/camera_math.h"
 
 using namespace morb;
 
@@ -150,15 +150,8 @@ __global__ __launch_bounds__(256) void k_frustum(morb_frame_params P, const floa
   do {
     if (Pc[2] < 0.0f) break;
     float u, v;
-    if (kb8) {   // KannalaBrandt8::project(Vector3f) (KannalaBrandt8.cpp:49-67): isInFrustumChecks, Frame.cc:1304-1309
-      const float x2_plus_y2 = Pc[0] * Pc[0] + Pc[1] * Pc[1];
-      const float theta = morbm::atan2f_glibc(sqrtf(x2_plus_y2), Pc[2]);
-      const float psi = morbm::atan2f_glibc(Pc[1], Pc[0]);
-      const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2,
-                  theta9 = theta7 * theta2;
-      const float r = theta + kb8[4] * theta3 + kb8[5] * theta5 + kb8[6] * theta7 + kb8[7] * theta9;
-      u = kb8[0] * r * morbm::cosf_glibc(psi) + kb8[2];
-      v = kb8[1] * r * morbm::sinf_glibc(psi) + kb8[3];
+    if (kb8) {   // KannalaBrandt8::project(Vector3f): isInFrustumChecks, Frame.cc:1304-1309
+      morbcam::kb8_project(kb8, Pc, u, v);
     } else {
       u = P.fx * Pc[0] / Pc[2] + P.cx; v = P.fy * Pc[1] / Pc[2] + P.cy;
     }
@@ -244,15 +237,6 @@ __global__ __launch_bounds__(256) void k_prep_mps_fisheye(morb_frame_params P, i
   qs[2 * o + 1] = qr;
 }
 
-__device__ __forceinline__ void q_rotate_f(const float* q, const float* v, float* out) {
-  const float ux = q[0], uy = q[1], uz = q[2], w = q[3];
-  float a = uy * v[2] - uz * v[1], b = uz * v[0] - ux * v[2], c = ux * v[1] - uy * v[0];
-  a += a; b += b; c += c;
-  out[0] = v[0] + w * a + (uy * c - uz * b);
-  out[1] = v[1] + w * b + (uz * a - ux * c);
-  out[2] = v[2] + w * c + (ux * b - uy * a);
-}
-
 __global__ __launch_bounds__(256) void k_prep_last(morb_frame_params P, int cap, const int* __restrict__ count,
                                                    const int* __restrict__ lastImg, const morb_keypoint* __restrict__ kps,
                                                    const uint8_t* __restrict__ lastValid, const float* __restrict__ lastXw,
@@ -268,7 +252,7 @@ __global__ __launch_bounds__(256) void k_prep_last(morb_frame_params P, int cap,
   if (i < count[img] && lastValid[o]) {
     const float* T = Tcw + 7 * f;
     float x3Dc[3];
-    q_rotate_f(T, lastXw + o * 3, x3Dc);
+    q_rotate(T, lastXw + o * 3, x3Dc);
     x3Dc[0] += T[4]; x3Dc[1] += T[5]; x3Dc[2] += T[6];
     const float invzc = (float)(1.0 / (double)x3Dc[2]);
     const float u = P.fx * x3Dc[0] / x3Dc[2] + P.cx, v = P.fy * x3Dc[1] / x3Dc[2] + P.cy;
@@ -288,16 +272,6 @@ __global__ __launch_bounds__(256) void k_prep_last(morb_frame_params P, int cap,
 // Fisheye current frame (CurrentFrame.Nleft != -1, ORBmatcher.cc:1521-1733): query 2i = left pass, 2i + 1 = right pass
 // of last-frame feature i.  Both project with the LEFT camera model (mpCamera; the right pass after
 // GetRelativePoseTrl() — the reference's quirk); the right pass has no bounds / depth test of its own.
-__device__ __forceinline__ void kb8_project_dev(const float* c, const float* v3, float& u, float& v) {   // KannalaBrandt8.cpp:49-67
-  const float x2_plus_y2 = v3[0] * v3[0] + v3[1] * v3[1];
-  const float theta = morbm::atan2f_glibc(sqrtf(x2_plus_y2), v3[2]);
-  const float psi = morbm::atan2f_glibc(v3[1], v3[0]);
-  const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2,
-              theta9 = theta7 * theta2;
-  const float r = theta + c[4] * theta3 + c[5] * theta5 + c[6] * theta7 + c[7] * theta9;
-  u = c[0] * r * morbm::cosf_glibc(psi) + c[2];
-  v = c[1] * r * morbm::sinf_glibc(psi) + c[3];
-}
 __global__ __launch_bounds__(256) void k_prep_last_fisheye(morb_frame_params P, int cap, const int* __restrict__ count,
                                                            const int* __restrict__ lastImg, const int* __restrict__ curImg,
                                                            const int* __restrict__ nLeftCur, const morb_keypoint* __restrict__ kps,
@@ -315,11 +289,11 @@ __global__ __launch_bounds__(256) void k_prep_last_fisheye(morb_frame_params P, 
   if (i < count[img] && lastValid[o]) {
     const float* T = Tcw + 7 * f;
     float x3Dc[3];
-    q_rotate_f(T, lastXw + o * 3, x3Dc);
+    q_rotate(T, lastXw + o * 3, x3Dc);
     x3Dc[0] += T[4]; x3Dc[1] += T[5]; x3Dc[2] += T[6];
     const float invzc = (float)(1.0 / (double)x3Dc[2]);
     float u, v;
-    kb8_project_dev(camTrl, x3Dc, u, v);
+    morbcam::kb8_project(camTrl, x3Dc, u, v);
     if (!(invzc < 0) && !(u < P.minX || u > P.maxX) && !(v < P.minY || v > P.maxY)) {
       const morb_keypoint kp = kps[(size_t)img * cap + i];
       const int oct = kp.octave;
@@ -333,9 +307,9 @@ __global__ __launch_bounds__(256) void k_prep_last_fisheye(morb_frame_params P, 
       qr = ql;
       const float* Trl = camTrl + 8;
       float x3Dr[3];
-      q_rotate_f(Trl, x3Dc, x3Dr);
+      q_rotate(Trl, x3Dc, x3Dr);
       x3Dr[0] += Trl[4]; x3Dr[1] += Trl[5]; x3Dr[2] += Trl[6];
-      kb8_project_dev(camTrl, x3Dr, qr.x, qr.y);
+      morbcam::kb8_project(camTrl, x3Dr, qr.x, qr.y);
       qr.jLo = nLeft; qr.jHi = N; qr.valid = (ql.valid && N > nLeft) ? 1 : 0;
     }
   }
@@ -377,12 +351,12 @@ __global__ __launch_bounds__(256) void k_prep_kfproj(morb_frame_params P, int mp
     if (i >= nMPv[f] || !valid[o]) break;
     const float* X = Pw + o * 3;
     float p[3];
-    q_rotate_f(T + 7 * f, X, p);
+    q_rotate(T + 7 * f, X, p);
     p[0] += T[7 * f + 4]; p[1] += T[7 * f + 5]; p[2] += T[7 * f + 6];
     if (sim) { float p2[3]; sim3_map_f(sim + 7 * f, p, p2); p[0] = p2[0]; p[1] = p2[1]; p[2] = p2[2]; }
     if (p[2] < 0.0f) break;
     float u, v;
-    if (kb8) kb8_project_dev(kb8, p, u, v);
+    if (kb8) morbcam::kb8_project(kb8, p, u, v);
     else if (projMode == 0) { u = P.fx * p[0] / p[2] + P.cx; v = P.fy * p[1] / p[2] + P.cy; }
     else {
       const float invz = projMode == 1 ? 1 / p[2] : (float)(1.0 / (double)p[2]);
@@ -1184,10 +1158,10 @@ __global__ __launch_bounds__(256) void k_prep_kf(morb_frame_params P, int cap, c
     const float* T = Tcw + 7 * f;
     const float* X = Xw + o * 3;
     float x3Dc[3];
-    q_rotate_f(T, X, x3Dc);
+    q_rotate(T, X, x3Dc);
     x3Dc[0] += T[4]; x3Dc[1] += T[5]; x3Dc[2] += T[6];
     float u, v;
-    if (kb8) kb8_project_dev(kb8, x3Dc, u, v);
+    if (kb8) morbcam::kb8_project(kb8, x3Dc, u, v);
     else { u = P.fx * x3Dc[0] / x3Dc[2] + P.cx; v = P.fy * x3Dc[1] / x3Dc[2] + P.cy; }
     const float PO[3] = {X[0] - Ow[3 * f], X[1] - Ow[3 * f + 1], X[2] - Ow[3 * f + 2]};
     const float dist3D = sqrtf(PO[0] * PO[0] + PO[1] * PO[1] + PO[2] * PO[2]);
@@ -1295,10 +1269,11 @@ __global__ __launch_bounds__(256) void k_triangulation(const unsigned long long*
                 if (!bCoarse) {
                   const bool bRight1 = !(idx1 < nLeft1v[pair]), bRight2 = !(idx2 < nLeft2v[pair]);
                   const float* T = rig + 16 + (size_t)pair * 48 + 12 * ((bRight1 ? 2 : 0) + (bRight2 ? 1 : 0));
-                  morbkb8::KB8 c1, c2;
+                  morbcam::Camera c1, c2;   // (records, not two float[8]: those reorder the operands of eight multiplications below)
+                  c1.kb8 = c2.kb8 = 1;
                   for (int q = 0; q < 8; ++q) { c1.p[q] = rig[(bRight1 ? 8 : 0) + q]; c2.p[q] = rig[(bRight2 ? 8 : 0) + q]; }
                   float p3D[3];
-                  ok = morbkb8::triangulate_matches(c1, c2, T, T + 9, kp1.x, kp1.y, kp2.x, kp2.y, P.levelSigma2[kp1.octave],
+                  ok = morbcam::triangulate_matches(c1.p, c2.p, T, T + 9, kp1.x, kp1.y, kp2.x, kp2.y, P.levelSigma2[kp1.octave],
                                                     P.levelSigma2[kp2.octave], p3D) > 0.0001f;
                 }
               } else if (!bStereo1 && !bStereo2) {

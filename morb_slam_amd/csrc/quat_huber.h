@@ -1,13 +1,15 @@
-// The three device functions the SE3 optimisers (optimizer_device.h) and OptimizeSim3 (sim3.hip) both need, restated from Eigen and g2o.
+// The three device functions the SE3 optimisers (optimizer_device.h) and OptimizeSim3 (sim3.hip) both need, restated from Eigen and g2o;
+// the projection searches (projection.hip) rotate with the first, in float.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace {
 
 // QuaternionBase::_transformVector; q = x y z w
-__device__ __forceinline__ void q_rotate(const double* q, const double* v, double* out) {
-  const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-  double a = uy * v[2] - uz * v[1], b = uz * v[0] - ux * v[2], c = ux * v[1] - uy * v[0];
+template <class T>
+__device__ __forceinline__ void q_rotate(const T* q, const T* v, T* out) {
+  const T ux = q[0], uy = q[1], uz = q[2], w = q[3];
+  T a = uy * v[2] - uz * v[1], b = uz * v[0] - ux * v[2], c = ux * v[1] - uy * v[0];
   a += a; b += b; c += c;
   out[0] = v[0] + w * a + (uy * c - uz * b);
   out[1] = v[1] + w * b + (uz * a - ux * c);

@@ -23,6 +23,7 @@
 #include "handles.h"
 #include "libm_f32.h"
 #include "libm_f64.h"
+#include "morb/camera_math.h"
 #include "quat_huber.h"
 
 namespace {
@@ -35,7 +36,7 @@ constexpr double S3_EXP_M = 0x1.fffffff768fa1p-1;    // glibc exp(-1e-9)
 constexpr int S3_CORR = 12;                     // doubles per correspondence: X2c[3] X1c[3] obs1[2] obs2[2] info1 info2
 
 struct Sim3d { double q[4]; double t[3]; double s; };   // q = x y z w
-struct Cam9 { int kb8; float p[8]; };                   // pinhole: fx fy cx cy; KB8: fx fy cx cy k1 k2 k3 k4
+using morbcam::Camera;
 
 // ---- Eigen / g2o Sim3 algebra ------------------------------------------------------------------------------
 __device__ __forceinline__ void q_mul(const double* p, const double* o, double* r) {   // quat_product (generic)
@@ -140,7 +141,7 @@ __device__ Sim3d sim3_exp(const double* u, double s) {
 }
 
 // ---- cameras (Pinhole.cpp:38-44, KannalaBrandt8.cpp:48-64) ----------------------------------------------------
-__device__ __forceinline__ void cam_project(const Cam9& c, const double* v, double* uv) {
+__device__ __forceinline__ void cam_project(const Camera& c, const double* v, double* uv) {
   if (!c.kb8) {
     uv[0] = (double)c.p[0] * v[0] / v[2] + (double)c.p[2];
     uv[1] = (double)c.p[1] * v[1] / v[2] + (double)c.p[3];
@@ -159,7 +160,7 @@ __device__ __forceinline__ void cam_project(const Cam9& c, const double* v, doub
 }
 
 // error of edge `dir` (0: e12 = obs1 - cam1(S.map(X2c)), 1: e21 = obs2 - cam2(S^-1.map(X1c))) of correspondence `cr`
-__device__ __forceinline__ void edge_error(const Sim3d& S, int dir, const double* cr, const Cam9& c1, const Cam9& c2, double* e) {
+__device__ __forceinline__ void edge_error(const Sim3d& S, int dir, const double* cr, const Camera& c1, const Camera& c2, double* e) {
   double x[3], uv[2];
   if (dir == 0) {
     sim3_map(S, cr, x);
@@ -268,8 +269,8 @@ struct S3Shared {
 
 // errors (and, with build, linearizeOplus + constructQuadraticForm) of every active edge at S; edge order 2 c + dir
 template <bool BUILD>
-__device__ void eval_edges(const S3Work& w, int nc, int E2, const Sim3d& S, bool robust, double delta, bool fixScale, const Cam9& c1,
-                           const Cam9& c2) {
+__device__ void eval_edges(const S3Work& w, int nc, int E2, const Sim3d& S, bool robust, double delta, bool fixScale, const Camera& c1,
+                           const Camera& c2) {
   for (int e = threadIdx.x; e < 2 * nc; e += S3_NT) {
     const int c = e >> 1, dir = e & 1;
     if (!w.act[c]) continue;
@@ -314,8 +315,8 @@ __device__ double ordered_sum(const S3Work& w, int nc, int E2, int k) {
 }
 
 // SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg, after initializeOptimization (lambda restarts)
-__device__ void lm_optimize(S3Shared& sh, const S3Work& w, int E2, int iterations, bool robust, double delta, bool fixScale, const Cam9& c1,
-                            const Cam9& c2) {
+__device__ void lm_optimize(S3Shared& sh, const S3Work& w, int E2, int iterations, bool robust, double delta, bool fixScale, const Camera& c1,
+                            const Camera& c2) {
   const int t = threadIdx.x;
   const int nc = sh.nc;
   if (t == 0) { sh.iters = 0; sh.trials = 0; for (int i = 0; i < 7; ++i) sh.x[i] = 0; }
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(S3_NT) void k_optimize_sim3(
   const int n = d_count ? min(max(d_count[p], 0), cap) : cap;
   const S3Work w = s3_carve(ws + (size_t)p * wsPitch, cap);
   const size_t pc = (size_t)p * cap;
-  Cam9 c1, c2;
+  Camera c1, c2;
   c1.kb8 = d_cam1[p * 9] != 0.f; c2.kb8 = d_cam2[p * 9] != 0.f;
   for (int i = 0; i < 8; ++i) { c1.p[i] = d_cam1[p * 9 + 1 + i]; c2.p[i] = d_cam2[p * 9 + 1 + i]; }
   float T1[12], T2[12];

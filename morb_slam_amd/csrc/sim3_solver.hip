@@ -2,7 +2,7 @@
 // vpMatched12, vpKeyFrameMatchedMP).  Each call restates, operation for operation in float:
 //   * the constructor (:34-120): the kept correspondences compacted in KF1 feature order (ransac_block.h), camera-frame points
 //     Rcw * Xw + tcw, FromCameraToImage of the MAP POINTS with each side's camera (Pinhole / KannalaBrandt8 project(Vector3f):
-//     cam_project of kb8.h, with glibc's atan2f / sinf / cosf), the truncated size_t thresholds 9.210 * sigma2;
+//     project of morb/camera_math.h, with glibc's atan2f / sinf / cosf), the truncated size_t thresholds 9.210 * sigma2;
 //   * SetRansacParameters (:122-146) from the device-side N (include/morb/sim3_solver_math.h, ransac_math.h);
 //   * iterate (:148-278) from state.iterations on: DUtils::Random::RandomInt + swap-with-back sampling on the caller's rand()
 //     values (three per iteration, indexed by the global iteration number), ComputeSim3 (:285-392), CheckInliers (:394-414),
@@ -18,7 +18,7 @@
 
 #include "common.h"
 #include "handles.h"
-#include "kb8.h"
+#include "morb/camera_math.h"
 #include "libm_f32.h"
 #include "morb_hip.h"
 #include "morb/sim3_solver_math.h"
@@ -38,8 +38,7 @@ constexpr int SS_W = 13;                       // words per correspondence
 constexpr int SS_HW = 40;                      // floats per hypothesis: T12 [12] (sR row-major, t), T21 [12], R [9], t [3], s
 static_assert(SS_B % SS_NW == 0 && SS_B <= SS_NT, "batch");
 
-using morbkb8::Cam;
-using morbkb8::cam_project;
+using morbcam::Camera;
 using namespace morbransac;
 
 // R * x + t, R row-major: Eigen's 3-term sums taken left to right
@@ -200,17 +199,17 @@ __device__ inline Corr ss_carve(float* base, int stride) {
 }
 
 // CheckInliers' test of correspondence i against hypothesis h (:394-414)
-__device__ __forceinline__ bool is_inlier(const Corr& C, int i, const float* T12, const float* T21, const Cam& c1, const Cam& c2) {
+__device__ __forceinline__ bool is_inlier(const Corr& C, int i, const float* T12, const float* T21, const Camera& c1, const Camera& c2) {
   const int S = C.stride;
   const float X2[3] = {C.x2[i], C.x2[S + i], C.x2[2 * S + i]};
   float P[3], uv[2];
   affine(T12, T12 + 9, X2, P);
-  cam_project(c1, P, uv);
+  morbcam::project(c1, P, uv[0], uv[1]);
   const float d0 = C.p1[i] - uv[0], d1 = C.p1[S + i] - uv[1];
   const float err1 = d0 * d0 + d1 * d1;
   const float X1[3] = {C.x1[i], C.x1[S + i], C.x1[2 * S + i]};
   affine(T21, T21 + 9, X1, P);
-  cam_project(c2, P, uv);
+  morbcam::project(c2, P, uv[0], uv[1]);
   const float f0 = uv[0] - C.p2[i], f1 = uv[1] - C.p2[S + i];
   const float err2 = f0 * f0 + f1 * f1;
   return err1 < C.e1[i] && err2 < C.e2[i];
@@ -229,7 +228,7 @@ __device__ inline bool kept(uint8_t en) {   // matched, pMP1 present, neither ba
   return (en & 1) && (en & 2) && !(en & 4) && !(en & 8) && !(en & 16) && !(en & 32);
 }
 
-__device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n, int cap, const morb_sim3_solver_params& prm, const Cam& c1, const Cam& c2,
+__device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n, int cap, const morb_sim3_solver_params& prm, const Camera& c1, const Camera& c2,
                       const uint8_t* __restrict__ d_entry, const float* __restrict__ d_Xw1, const float* __restrict__ d_Xw2,
                       const float* __restrict__ d_s2_1, const float* __restrict__ d_s2_2, int nIterations, const int* __restrict__ d_rand,
                       int randCap, morb_sim3_solver_state* __restrict__ d_state, uint8_t* __restrict__ d_inliers, int* __restrict__ d_hyp,
@@ -248,9 +247,9 @@ __device__ __forceinline__ void solve(SsShared& sh, const Corr& C, int p, int n,
       affine(prm.T2w, prm.T2w + 9, d_Xw2 + (pc + i) * 3, X2);
 #pragma unroll
       for (int r = 0; r < 3; ++r) { C.x1[r * S + c] = X1[r]; C.x2[r * S + c] = X2[r]; }
-      cam_project(c1, X1, uv);
+      morbcam::project(c1, X1, uv[0], uv[1]);
       C.p1[c] = uv[0]; C.p1[S + c] = uv[1];
-      cam_project(c2, X2, uv);
+      morbcam::project(c2, X2, uv[0], uv[1]);
       C.p2[c] = uv[0]; C.p2[S + c] = uv[1];
       C.e1[c] = morbs3::sim3s_max_error(d_s2_1[pc + i]);
       C.e2[c] = morbs3::sim3s_max_error(d_s2_2[pc + i]);
@@ -375,9 +374,9 @@ __global__ __launch_bounds__(SS_NT) void k_sim3_solver(int cap, const morb_sim3_
   const morb_sim3_solver_params prm = d_params[p];
   const int n = min(max(prm.n, 0), cap);
   const size_t pc = (size_t)p * cap;
-  Cam c1, c2;
+  Camera c1, c2;
   c1.kb8 = prm.cam1[0] != 0.f; c2.kb8 = prm.cam2[0] != 0.f;
-  for (int i = 0; i < 8; ++i) { c1.k.p[i] = prm.cam1[1 + i]; c2.k.p[i] = prm.cam2[1 + i]; }
+  for (int i = 0; i < 8; ++i) { c1.p[i] = prm.cam1[1 + i]; c2.p[i] = prm.cam2[1 + i]; }
   // vbInliers = vector<bool>(mN1, false), and N
   for (int i = t; i < cap; i += SS_NT) d_inliers[pc + i] = 0;
   if (t == 0) { sh.N = 0; sh.nc = 0; }
