@@ -53,10 +53,6 @@ namespace {
 #define MORB_TEAM_MAX_IMAGES 64   // (round 6, teams of 16 waves + the full sweeps at once: 16 -> 64 images.  tools/r06_team_max.sh: 752 x 480, 32 / 64 images per call +6.6 / +6 - 8 %
 #endif                            //  end to end; 1920 x 1080, 32 / 64 images +67 / +29 % (12.8 -> 21.4 k frames/s at 16 stereo frames per step); at 128 images the teams lose 11 %)
 constexpr int kTeamMaxImages = MORB_TEAM_MAX_IMAGES;
-#ifndef MORB_PYR_CHUNK_IMAGES
-#define MORB_PYR_CHUNK_IMAGES (1 << 30)
-#endif
-constexpr int kPyrChunkImages = MORB_PYR_CHUNK_IMAGES;   // images per group of pyramid launches (morb_extract_batch)
 #ifndef MORB_TEAM_MIN_PIXELS
 #define MORB_TEAM_MIN_PIXELS 160000   // k_distribute: levels of at least this many pixels are worked by a team of waves in the team packing
 #endif
@@ -65,8 +61,9 @@ constexpr int kPyrChunkImages = MORB_PYR_CHUNK_IMAGES;   // images per group of 
 #endif   // k_distribute: calls with at most this many images use the team packing of the big levels
 
 // bit_pattern_31_ (ORBextractor.cc:147-404) as floats: k_describe multiplies the coordinates by cos / sin (the conversion of 16 integers per wave was 16 of its ~575
-// vector instructions, and the kernel — like the whole step — is bound by vector-instruction issue)
-__constant__ __align__(16) float c_pattern[256 * 4] = {
+// vector instructions, and the kernel — like the whole step — is bound by vector-instruction issue).  Aligned to the 128-byte cache line: a lane's four
+// float4 are a 64-byte row, so the table is 32 whole lines (at 64 mod 128, where the linker may otherwise put it, 33; k_describe measured 0.5 % slower there)
+__constant__ __align__(128) float c_pattern[256 * 4] = {
 #include "orb_pattern.inc"
 };
 __constant__ int c_umax[16];
@@ -117,9 +114,8 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
 // General form (any scale factor): four byte gathers per output pixel.  Used only when a level's four-pixel chunks do not fit the
 // 8-byte source windows of k_resize (scale factors above ~1.75).
 __global__ __launch_bounds__(256) void k_resize_gather(uint8_t* __restrict__ pyr, LevelGeom gs, LevelGeom gd,
-                                                       const ResizeTab* __restrict__ xtab, const ResizeTab* __restrict__ ytab, int img0) {
-  PyTile pt = py_tile();
-  pt.img += img0;   // (the launch covers images img0 .. img0 + gridDim.z - 1)
+                                                       const ResizeTab* __restrict__ xtab, const ResizeTab* __restrict__ ytab) {
+  const PyTile pt = py_tile();
   const uint8_t* sbase = pyr + gs.pyrOff + (size_t)pt.img * gs.pyrImg + (size_t)kPyrPad * gs.pstride + kPyrPad;
   const int px = (pt.bx * 64 + (threadIdx.x & 63)) * 4;
   const int py0 = (pt.by * 4 + (threadIdx.x >> 6)) * PY_ROWS;
@@ -214,9 +210,6 @@ __device__ __forceinline__ void resize_items(const uint8_t* __restrict__ sbase, 
     lo >>= 2; hi >>= 2;
     const uint32_t v = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u);
     // rows past the bottom of the last group: the row table repeats its last entry, the store rewrites the last row with the same bytes
-#if MORB_EXP == 4
-    if (v == 0x12345678u)
-#endif
     *reinterpret_cast<uint32_t*>(dimg + (uint32_t)(__umul24(min(row0 + r, a.H - 1), a.dpstride) + c * 4)) = v;
   }
 }
@@ -288,11 +281,8 @@ constexpr int BT_H = BT_ROWS * BT_TY;
 #endif
 constexpr int BT_AHEAD = MORB_BT_AHEAD;   // source rows in flight ahead of the row being filtered
 typedef unsigned short blur_u16x2 __attribute__((ext_vector_type(2)));
-#ifndef MORB_BLUR_SHIFTED_WEIGHTS
-#define MORB_BLUR_SHIFTED_WEIGHTS 1
-#endif
-// Horizontal 7-tap of eight neighbouring pixels: v_dot4_u32_u8 against the packed kernel weights (18 34 48 56 | 48 34 18 0),
-// the byte windows cut out of the four loaded dwords with v_alignbyte.  Results are exact integers <= 255 * 256.
+// Horizontal 7-tap of eight neighbouring pixels: v_dot4_u32_u8 of the four loaded dwords against the packed kernel weights
+// (18 34 48 56 | 48 34 18 0), shifted per pixel (blur_h8).  Results are exact integers <= 255 * 256.
 __device__ __forceinline__ uint4 blur_load16(const uint8_t* __restrict__ row) {
   // row points at byte (x - 3) of the padded row (8-byte aligned): 16 bytes = pixels x-3 .. x+12, ONE vector-memory instruction
   uint4 w;
@@ -300,7 +290,6 @@ __device__ __forceinline__ uint4 blur_load16(const uint8_t* __restrict__ row) {
   return w;
 }
 __device__ __forceinline__ void blur_h8(const uint4 w, uint32_t h[8]) {
-#if MORB_BLUR_SHIFTED_WEIGHTS
   // Round 4: the seven taps of pixel s of a dword group sit on bytes s .. s + 6 of the loaded dwords; instead of cutting that window out with
   // v_alignbyte the WEIGHTS are shifted (constants): pixel 0 and 1 are two v_dot4_u32_u8, pixel 2 and 3 three — 20 instructions per eight
   // pixels instead of 16 + 9.
@@ -318,18 +307,6 @@ __device__ __forceinline__ void blur_h8(const uint4 w, uint32_t h[8]) {
     h[4 * g + 2] = __builtin_amdgcn_udot4(w0, A2, __builtin_amdgcn_udot4(w1, B2, __builtin_amdgcn_udot4(w2, C2, 0u, false), false), false);
     h[4 * g + 3] = __builtin_amdgcn_udot4(w0, A3, __builtin_amdgcn_udot4(w1, B3, __builtin_amdgcn_udot4(w2, C3, 0u, false), false), false);
   }
-#else
-  constexpr uint32_t WA = 18u | (34u << 8) | (48u << 16) | (56u << 24), WB = 48u | (34u << 8) | (18u << 16);
-  const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const uint32_t w0 = ws[g], w1 = ws[g + 1], w2 = ws[g + 2];
-    h[4 * g + 0] = __builtin_amdgcn_udot4(w0, WA, __builtin_amdgcn_udot4(w1, WB, 0u, false), false);
-    h[4 * g + 1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), WA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 1), WB, 0u, false), false);
-    h[4 * g + 2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), WA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 2), WB, 0u, false), false);
-    h[4 * g + 3] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), WA, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w2, w1, 3), WB, 0u, false), false);
-  }
-#endif
 }
 __device__ __forceinline__ uint32_t blur_dot2(uint32_t pair, uint32_t w, uint32_t acc) {   // v_dot2_u32_u16
   return __builtin_amdgcn_udot2(__builtin_bit_cast(blur_u16x2, pair), __builtin_bit_cast(blur_u16x2, w), acc, false);
@@ -708,9 +685,6 @@ using morbm::sincosf_glibc;
 // The wave's lifetime is a chain of dependent global-memory round trips, so the chain is kept short: one record
 // per keypoint from k_layout (slot, level, key), level geometry from the kernarg segment, and the (keypoint-
 // independent) rBRIEF pattern rows of the lane requested before anything else.
-#ifndef MORB_DESC_STAGED
-#define MORB_DESC_STAGED 1
-#endif
 #ifndef MORB_DESC_KPW
 #define MORB_DESC_KPW 2   // (round 3, with the window in LDS: 2 / 3 / 4 / 8 keypoints per wave = 469 / 473 / 486 / 628 us per 512 images; 1: 519)
 #endif
@@ -724,17 +698,12 @@ constexpr int DESC_WIN = 2 * DESC_R + 1, DESC_WP = 48;   // window rows / LDS pi
 #ifndef MORB_DESC_WAVES
 #define MORB_DESC_WAVES 4
 #endif
-#ifndef MORB_DESC_ANGLE_WG
-#define MORB_DESC_ANGLE_WG 1   // fastAtan2 + sincosf of the workgroup's keypoints in one pass of wave 0 (0: each wave for its own two)
-#endif
 constexpr int DESC_WAVES = MORB_DESC_WAVES;   // waves (of DESC_KPW keypoints each) per workgroup
 __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGeom dg, const uint8_t* __restrict__ pyr,
                                                   const uint8_t* __restrict__ blur, const int2* __restrict__ kref,
                                                   int selPerImg, morb_keypoint* __restrict__ kps,
                                                   uint8_t* __restrict__ desc, int cap, int imgRev) {
-#if MORB_DESC_STAGED
   __shared__ __align__(16) uint8_t s_win[DESC_WAVES * DESC_KPW * DESC_WIN * DESC_WP];
-#endif
   // Workgroup -> (image, keypoint chunk).  Hardware deals consecutive workgroup ids round-robin over the 8 XCDs, each with its own L2: with the
   // plain (chunk, image) order the chunks of one image — whose patches cover the image's whole pyramid and blur between them — are spread
   // over all eight L2s and every XCD fetches (nearly) every line (PMC r02: 2.2 x the gather bytes fetched, 4.4 x with the FETCH_SIZE
@@ -748,7 +717,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
   }
   const int img = imgRev ? gridDim.y - 1 - imgIdx : imgIdx, lane = threadIdx.x & 63;
   const int gi0 = (chunk * DESC_WAVES + (threadIdx.x >> 6)) * DESC_KPW;
-#if MORB_DESC_ANGLE_WG
   // (round 5) the workgroup's waves meet at two barriers (the angles of all its keypoints are computed in ONE pass of wave 0): a wave without
   // work goes through them and leaves
   __shared__ int s_mom[DESC_WAVES * DESC_KPW][2];
@@ -771,9 +739,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     __syncthreads();
   };
   if (gi0 >= selPerImg) { leave(); return; }
-#else
-  if (gi0 >= selPerImg) return;
-#endif
   // (the pattern fetched once per workgroup into LDS instead — one 16-byte load per thread, a barrier, four ds_read_b128 per lane later —
   // measured no faster: 2016 - 2058 against 2002 - 2015 us per 512 images for the whole extraction, three runs each on one box)
   float4 pat[4];
@@ -790,11 +755,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     ok[kk] = gi0 + kk < selPerImg && ref[kk].x >= 0;
     if (ok[kk]) { firstRef = ref[kk]; any = true; }
   }
-#if MORB_DESC_ANGLE_WG
   if (!any) { leave(); return; }   // wave-uniform
-#else
-  if (!any) return;   // wave-uniform
-#endif
 #pragma unroll
   for (int kk = 0; kk < DESC_KPW; ++kk) {
     if (!ok[kk]) ref[kk] = firstRef;
@@ -806,7 +767,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
   int lvl[DESC_KPW], cx[DESC_KPW], cy[DESC_KPW], pstride[DESC_KPW], bstride[DESC_KPW];
   const uint8_t* ctr[DESC_KPW];
   const uint8_t* center[DESC_KPW];
-  int wsh[DESC_KPW] = {};
+  int wsh[DESC_KPW];
 #pragma unroll
   for (int kk = 0; kk < DESC_KPW; ++kk) {
     const int l = ref[kk].x >> 24;
@@ -817,13 +778,11 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     // the lanes add unsigned 32-bit offsets (scalar base + vector offset addressing)
     ctr[kk] = pyr + dg.pyrOff[l] + (size_t)img * dg.pyrImg[l] + (size_t)(kPyrPad + cy[kk] - HALF_PATCH) * pstride[kk] + kPyrPad + cx[kk] - HALF_PATCH;
     center[kk] = blur + dg.blurOff[l] + (size_t)img * dg.blurImg[l] + (ptrdiff_t)(cy[kk] - DESC_R) * bstride[kk] + cx[kk] - DESC_R;
-#if MORB_DESC_STAGED
     // the window is fetched from the dword boundary below its left edge (blurred rows are 64-byte aligned, a keypoint sits at x >= 19):
     // a wave's 16-byte load costs the memory pipe 64 cycles at a byte-granular address and 16 at a dword-aligned one
     // (tools/micro/ta_rate.hip); the 37 columns + the shift still fit the 48-byte rows, the gathers add the shift
     wsh[kk] = (cx[kk] - DESC_R) & 3;
     center[kk] -= wsh[kk];
-#endif
   }
   // IC_Angle on the un-blurred level.  The texture path handles a byte load of a wave no faster than a dword load, so the
   // 31 x 31 patch is read as 31 rows x 8 unaligned dwords = 248 dword loads, four per lane.
@@ -841,7 +800,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
   // stay inside the row's slack or the next row), and goes to LDS, where the 512 byte gathers of the tests cost a fraction of what they
   // cost the vector cache: PMC showed the kernel at 1.13 cache-line accesses per cycle per CU (TCP_TOTAL_CACHE_ACCESSES: 692 per keypoint,
   // 512 of them the byte gathers), i.e. bound by the L1's one tag lookup per clock; the window's row loads are ~60 accesses.
-#if MORB_DESC_STAGED
   uint4 ww[DESC_KPW][2];
 #pragma unroll
   for (int kk = 0; kk < DESC_KPW; ++kk)
@@ -851,7 +809,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
       const int row = (int)(((unsigned)t * 21846u) >> 16), seg = t - row * 3;
       __builtin_memcpy(&ww[kk][j], __builtin_assume_aligned(center[kk] + (uint32_t)(__umul24(row, bstride[kk]) + seg * 16), 4), 16);
     }
-#endif
   // The circular mask and the column weights of a lane's four dwords do not depend on the keypoint: byte masks and the
   // biased weights (u + 15, so that v_dot4_u32_u8 applies) are built once, and per keypoint a dword costs one AND, two
   // dot products and a multiply-add: m10 = sum (u + 15) I - 15 sum I, m01 = sum v (row sum of I).
@@ -877,7 +834,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
   float angle[DESC_KPW];
   int t0v[DESC_KPW][4], t1v[DESC_KPW][4];
   int m10k[DESC_KPW], m01k[DESC_KPW];
-#if MORB_DESC_STAGED
   uint8_t* win = s_win + (threadIdx.x >> 6) * (DESC_KPW * DESC_WIN * DESC_WP);   // this wave's windows: [DESC_KPW][37 rows][48 bytes]
 #pragma unroll
   for (int kk = 0; kk < DESC_KPW; ++kk)
@@ -888,7 +844,6 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-#endif
 #pragma unroll
   for (int kk = 0; kk < DESC_KPW; ++kk) {
     uint32_t usumB = 0, sumAll = 0;
@@ -905,11 +860,7 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     m10k[kk] = morbwave::sum_i32(m10);   // DPP reductions (wave.h): all 64 lanes are active here
     m01k[kk] = morbwave::sum_i32(m01);
   }
-  // fastAtan2 and sincosf are one number per keypoint: lane kk computes keypoint kk's (as wave-uniform code the four of them cost four
-  // serial passes of ~70 instructions, the FP64 polynomial of glibc's sincosf included, on all 64 lanes), and every keypoint's gathers
-  // can be issued as soon as that one pass is through
-#if MORB_DESC_ANGLE_WG
-  // Round 5: ONE pass for the whole workgroup.  fastAtan2 + glibc's sincosf (~90 instructions, FP64 polynomial included) occupy all 64 lanes of a
+  // fastAtan2 and sincosf are one number per keypoint, computed in ONE pass for the whole workgroup (round 5).  fastAtan2 + glibc's sincosf (~90 instructions, FP64 polynomial included) occupy all 64 lanes of a
   // wave for the two numbers its two keypoints need; the kernel is bound by vector-instruction issue (634 VALU per wave, 5.3 SIMD cycles each,
   // profiles/r05/pmc_issue_table_b512.txt), so the four waves' passes become one: moments to LDS, wave 0 computes lane k = keypoint k of the
   // workgroup, everybody picks its two (cos, sin, angle) up again.  The same instructions on the same inputs: identical bits.
@@ -931,36 +882,15 @@ __global__ __launch_bounds__(64 * DESC_WAVES) void k_describe(const morb::DescGe
     angle[kk] = s_trig[ws][0];
     const float a = s_trig[ws][1];
     const float bsin = s_trig[ws][2];
-#else
-  float angL, aL, bL;
-  {
-    int m10 = m10k[DESC_KPW - 1], m01 = m01k[DESC_KPW - 1];
-#pragma unroll
-    for (int kk = DESC_KPW - 2; kk >= 0; --kk) { m10 = lane == kk ? m10k[kk] : m10; m01 = lane == kk ? m01k[kk] : m01; }
-    angL = fast_atan2_deg((float)m01, (float)m10);
-    const float factorPI = (float)(3.14159265358979323846 / 180.f);
-    sincosf_glibc(angL * factorPI, &bL, &aL);
-  }
-#pragma unroll
-  for (int kk = 0; kk < DESC_KPW; ++kk) {
-    angle[kk] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, angL), kk));
     // rBRIEF on the blurred level: lane k evaluates tests 4k..4k+3
-    const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, aL), kk));
-    const float bsin = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bL), kk));
-#endif
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float x0 = pat[q].x, y0 = pat[q].y, x1 = pat[q].z, y1 = pat[q].w;
       const int r0 = __float2int_rn(x0 * bsin + y0 * a), c0 = __float2int_rn(x0 * a - y0 * bsin);
       const int r1 = __float2int_rn(x1 * bsin + y1 * a), c1 = __float2int_rn(x1 * a - y1 * bsin);
-#if MORB_DESC_STAGED
       // (24-bit multiplies: the plain `* 48` compiled to the quarter-rate v_mad_u64_u32, sixteen of them per pair of keypoints)
       t0v[kk][q] = win[kk * (DESC_WIN * DESC_WP) + __mul24(r0 + DESC_R, DESC_WP) + c0 + DESC_R + wsh[kk]];
       t1v[kk][q] = win[kk * (DESC_WIN * DESC_WP) + __mul24(r1 + DESC_R, DESC_WP) + c1 + DESC_R + wsh[kk]];
-#else
-      t0v[kk][q] = center[kk][(uint32_t)((r0 + DESC_R) * bstride[kk] + c0 + DESC_R)];   // (unstaged build: center is the window's own corner)
-      t1v[kk][q] = center[kk][(uint32_t)((r1 + DESC_R) * bstride[kk] + c1 + DESC_R)];
-#endif
     }
   }
 #pragma unroll
@@ -1537,36 +1467,24 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
       a.magicC = pl.magicC; a.dOff = g.pyrOff; a.dImg = g.pyrImg;
       return a;
     };
-    // Round 6: the eight dependent launches run over CHUNKS of images.  Level l reads level l - 1 back: with all 1024 images of a bench step in one
-    // launch the producer's 400 MB have long left the L2 / Infinity Cache (256 MB) when the consumer starts and every level is read from HBM again;
-    // chunk by chunk the previous level of the chunk is still on chip (profiles/r06/pyramid_chunk_sweep.txt).
-    static const int pyrChunkEnv = [] { const char* v = getenv("MORB_PYR_CHUNK"); return v ? atoi(v) : 0; }();
-    const int chunk = pyrChunkEnv > 0 ? pyrChunkEnv : kPyrChunkImages;
-    for (int i0 = 0; i0 < nimg; i0 += chunk) {
-      const int ni = nimg - i0 < chunk ? nimg - i0 : chunk;
-      Level0Args a0c = a0;
-      a0c.dOff += (unsigned long long)i0 * a0.dImg;
-      const uint8_t* src = d_images + (size_t)i0 * image_pitch;
-      if (e->pyrPacked) {
-        // level 0 first, in its own launch: level 1 reads it back from the pyramid (dword-aligned rows with slack behind them — the wide
-        // aligned window loads of k_resize cannot be pointed at a caller-owned buffer; the fused level-0 + level-1 kernel of round 2 did
-        // that with byte-granular 8-byte loads at twice the memory-pipe cost)
-        hipLaunchKernelGGL(k_level0, dim3(div_up(p0.nItems, 256), 1, ni), dim3(256), 0, st, src, stride, image_pitch, e->d_pyr, a0c);
-        for (int l = 1; l < L; ++l) {
-          const LevelGeom& gs = e->geom[l - 1];
-          const PyrLevel& pl = e->pyrLv[l];
-          ResizeArgs ra = resize_args(l);
-          ra.dOff += (unsigned long long)i0 * ra.dImg;
-          hipLaunchKernelGGL(k_resize, dim3(div_up(pl.nItems, 256), 1, ni), dim3(256), sizeof(PyrRow) * pl.ldsRows, st, e->d_pyr,
-                             gs.pyrOff + (unsigned long long)i0 * gs.pyrImg + (unsigned long long)kPyrPad * gs.pstride, gs.pyrImg, gs.pstride, ra);
-        }
-      } else {
-        hipLaunchKernelGGL(k_level0, dim3(div_up(p0.nItems, 256), 1, ni), dim3(256), 0, st, src, stride, image_pitch, e->d_pyr, a0c);
-        for (int l = 1; l < L; ++l) {
-          const LevelGeom& g = e->geom[l];
-          dim3 gr(div_up(g.pstride / 4, 64), div_up(g.h + 2 * kPyrPad, 4 * PY_ROWS), ni);
-          hipLaunchKernelGGL(k_resize_gather, gr, dim3(256), 0, st, e->d_pyr, e->geom[l - 1], g, e->d_tabs + g.xtabOff, e->d_tabs + g.ytabOff, i0);
-        }
+    // (the dependent launches cover the whole batch: running them over groups of images gained nothing, profiles/r06/pyramid_chunk_sweep.txt)
+    if (e->pyrPacked) {
+      // level 0 first, in its own launch: level 1 reads it back from the pyramid (dword-aligned rows with slack behind them — the wide
+      // aligned window loads of k_resize cannot be pointed at a caller-owned buffer; the fused level-0 + level-1 kernel of round 2 did
+      // that with byte-granular 8-byte loads at twice the memory-pipe cost)
+      hipLaunchKernelGGL(k_level0, dim3(div_up(p0.nItems, 256), 1, nimg), dim3(256), 0, st, d_images, stride, image_pitch, e->d_pyr, a0);
+      for (int l = 1; l < L; ++l) {
+        const LevelGeom& gs = e->geom[l - 1];
+        const PyrLevel& pl = e->pyrLv[l];
+        hipLaunchKernelGGL(k_resize, dim3(div_up(pl.nItems, 256), 1, nimg), dim3(256), sizeof(PyrRow) * pl.ldsRows, st, e->d_pyr,
+                           gs.pyrOff + (unsigned long long)kPyrPad * gs.pstride, gs.pyrImg, gs.pstride, resize_args(l));
+      }
+    } else {
+      hipLaunchKernelGGL(k_level0, dim3(div_up(p0.nItems, 256), 1, nimg), dim3(256), 0, st, d_images, stride, image_pitch, e->d_pyr, a0);
+      for (int l = 1; l < L; ++l) {
+        const LevelGeom& g = e->geom[l];
+        dim3 gr(div_up(g.pstride / 4, 64), div_up(g.h + 2 * kPyrPad, 4 * PY_ROWS), nimg);
+        hipLaunchKernelGGL(k_resize_gather, gr, dim3(256), 0, st, e->d_pyr, e->geom[l - 1], g, e->d_tabs + g.xtabOff, e->d_tabs + g.ytabOff);
       }
     }
   }
@@ -1595,13 +1513,8 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
   // the quadtree is enqueued first so that its long-running waves get their slots before the blur fills the chip;
   // the workgroups with level 0 (the longest wave) first: grid x = image, y = group of levels
   // (which of the two is enqueued first makes no difference: measured both ways)
-  // (developer switch MORB_TEAM_MID=n: calls of up to n images take the team packing with FOUR waves per team; measured, off — see profiles/r06/README.md)
-  static const int teamMid = [] { const char* v = getenv("MORB_TEAM_MID"); return v ? atoi(v) : 0; }();
   if (nimg <= kTeamMaxImages && e->distGroupsTeam > 0)   // few images: latency matters, the big levels are worked by teams of waves
     hipLaunchKernelGGL(k_distribute, dim3(nimg, e->distGroupsTeam), dim3(64 * QT_TEAM_WAVES), e->distSmemTeam, st, e->d_geomTeam, e->d_cand, e->d_candCnt,
-                       e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->status.dev());
-  else if (nimg <= teamMid && e->distGroupsTeam > 0)
-    hipLaunchKernelGGL(k_distribute, dim3(nimg, e->distGroupsTeam), dim3(64 * QT_MAX_WAVES), e->distSmemTeam, st, e->d_geomTeam, e->d_cand, e->d_candCnt,
                        e->totalCells, e->cellCap, e->d_qt, e->d_sel, e->d_selCnt, e->selPerImg, L, 0, e->status.dev());
   else
     // (one launch per bin of levels, each with its own LDS size — all bins of one launch get the largest bin's — measured: the launches

@@ -60,9 +60,6 @@ extern "C" int morb_fw_stats(unsigned long long* out, int reset) {
 #endif
 #define FW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
-#ifndef MORB_FW_PADLDS
-#define MORB_FW_PADLDS 0   // (occupancy experiments: extra LDS bytes per wave)
-#endif
 constexpr int FW_SH = 1;       // window column c = tile column c + FW_SH
 constexpr int FW_QCAP = 320;   // survivor queue: < 64 left over + 256 of a reject round's flags (a fuller round is queued in several pieces)
 constexpr int FW_CQ = 512;     // corner list of a pass (~50 per cell on the benchmark images); more -> strip mode
@@ -81,7 +78,7 @@ template <int P> struct FwQueueEntry { typedef uint32_t type; };
 template <> struct FwQueueEntry<48> { typedef uint16_t type; };
 constexpr int FW_ROWS16 = 85;   // rows a P = 48 tile may have (85 * 48 / 4 < 1024)
 template <int P> __host__ __device__ constexpr int fw_region_bytes(int rows) {   // LDS of one wave
-  return (rows * P + 16) + FW_QCAP * (int)sizeof(typename FwQueueEntry<P>::type) + FW_CQ * 2 + FW_CQ + FW_KC * 4 + MORB_FW_PADLDS;
+  return (rows * P + 16) + FW_QCAP * (int)sizeof(typename FwQueueEntry<P>::type) + FW_CQ * 2 + FW_CQ + FW_KC * 4;
 }
 // pixels [0, o) of a 16-px block as a mask in the reject's flag layout: pixel o -> bits f, f + 1 (dark, bright), f = o[0] << 1 | o[2] << 2 | o[3] << 3 | o[1] << 4
 struct FwPixMask { unsigned m[17]; constexpr FwPixMask() : m() { unsigned a = 0; for (int o = 0; o < 16; ++o) { m[o] = a; a |= 3u << (((o & 1) << 1) | (o & 4) | (o & 8) | ((o & 2) << 3)); } m[16] = a; } };
@@ -217,10 +214,7 @@ __global__ __launch_bounds__(64 * FW_WAVES, P == 48 ? ((FW_WAVES * 8 + 3) / 4 > 
       // 12-px items per evaluated row.  A row of 37 - 39 evaluated columns (a quarter of the cells: the grid's cell width is 35 - 39 px) would need a
       // fourth item for its last 1 - 3 pixels — a third reject round for the cell; there the row's LAST item takes up to 15 pixels instead (the flag
       // layout has room for 16): a fourth dword per item, two more packed pairs, and the cell stays at two rounds.
-#ifndef MORB_FW_WIDE
-#define MORB_FW_WIDE 1
-#endif
-      const bool wide = MORB_FW_WIDE && xb - xa > 36 && xb - xa <= 39;   // (wave-uniform)
+      const bool wide = xb - xa > 36 && xb - xa <= 39;   // (wave-uniform)
       const int nIt = wide ? 3 : (xb - xa + 11) / 12;
       const unsigned itMagic = c_magic20.m[nIt];
       const int nItems = (th - 6) * nIt;

@@ -576,9 +576,6 @@ __host__ __device__ constexpr int po2_rows(bool mfma) { return mfma ? PO2_NT : p
 #ifndef MORB_PO2_SKIP_ROUNDS
 #define MORB_PO2_SKIP_ROUNDS 1   // a round that would repeat the one before it bit for bit is not run
 #endif
-#ifndef MORB_PO2_FIRST_PREVIEW
-#define MORB_PO2_FIRST_PREVIEW 2   // first trials are previewed after a rejection: 1 in this round, 2 in this call (measured best: 318 k against 312 / 317 k frames/s), 3 always
-#endif
 #ifndef MORB_PO2_SPEC
 #define MORB_PO2_SPEC 1      // matrix-core chain: an iteration's first solve carries the nine trials that can follow it (one lambda per lane)
 #endif
@@ -712,7 +709,7 @@ __global__ __launch_bounds__(PO2_NT) void k_pose_opt2(int cap, const int* __rest
   const int nL = FISH ? nLeft[f] : n;   // features >= nL are right-camera observations (fisheye rig)
   PoEdge ed[PO2_EPT];
   int nAct = 0;
-  bool sawReject = MORB_PO2_FIRST_PREVIEW == 3;
+  bool sawReject = false;   // first trials are previewed once a trial of this call was rejected (measured best: 318 k frames/s against 312 k per round, 317 k always)
 
   auto load_edge = [&](int i, PoEdge& e) {
     e.o[0] = obs[(base + i) * 3]; e.o[1] = obs[(base + i) * 3 + 1]; e.o[2] = obs[(base + i) * 3 + 2];
@@ -880,9 +877,6 @@ __global__ __launch_bounds__(PO2_NT) void k_pose_opt2(int cap, const int* __rest
     int cur = 0;
     pass(T, cur);
     double lambda = 0, ni = 2;
-#if MORB_PO2_FIRST_PREVIEW == 1
-    sawReject = false;   // (per round: a round's first iterations accept their first trials; after its first rejection most first trials are rejected too)
-#endif
     int nBad = 0;
     for (int iter = 0; iter < 10; ++iter) {
       ++outerIts;
@@ -919,7 +913,7 @@ __global__ __launch_bounds__(PO2_NT) void k_pose_opt2(int cap, const int* __rest
         // too: rejected, for certain, without the edge-order sums, the Jacobians or the LDS hand-over (measured on the oracle's traces: 90 % of the
         // rejections, half of all trials).  Otherwise the trial runs its pass as before.  (Its pose has been waiting since the iteration's first trial.)
         bool certainlyRejected = false;
-        if (spec && MORB_PO2_PREVIEW && (qmax > 0 || sawReject) && ok2 && scale > 0) {   // (an iteration's first trial too once this round has rejected one)
+        if (spec && MORB_PO2_PREVIEW && (qmax > 0 || sawReject) && ok2 && scale > 0) {   // (an iteration's first trial too once this call has rejected one)
           const int par = trials & 1;
           double part = 0;
           {
@@ -1072,12 +1066,12 @@ static int launch_pose_opt2(bool ordered, bool mfmaChain, int nframes, hipStream
 
 }  // namespace
 
-// PoseOptimization's dispatch: k_pose_opt2 where it has a form of this mode and size and the caller allows it, else the old k_pose_opt
+// PoseOptimization's dispatch: k_pose_opt2 where it has a form of this mode and size and the caller allows it, else k_pose_opt
 template <bool FISH>
 static int pose_optimization(const morb_optimizer* o, bool allowOpt2, int nframes, hipStream_t st, int cap, const int* d_count, const uint8_t* d_hasMP,
                              const float* d_obs, const float* d_invSigma2, const float* d_Xw, const Cam& cam, const Rig& rig, const int* d_nLeft,
                              float* d_pose, uint8_t* d_outlier, int* d_nInliers, int* d_stats) {
-  if (pose_opt2_covers(o->exactOrder != 0, o->mfmaChain != 0, cap) && allowOpt2 && !getenv("MORB_PO_OLD")) {
+  if (pose_opt2_covers(o->exactOrder != 0, o->mfmaChain != 0, cap) && allowOpt2) {
     const int rc = launch_pose_opt2<FISH>(o->exactOrder != 0, o->mfmaChain != 0, nframes, st, cap, d_count, d_hasMP, d_obs, d_invSigma2, d_Xw, cam, rig, d_nLeft, d_pose,
                                           d_outlier, d_nInliers, d_stats);
     if (rc != MORB_OK) return rc;

@@ -93,11 +93,6 @@ __device__ __forceinline__ double sin_glibc_small(double x) {
   }
   return sin(x);
 }
-#ifdef XP_TRIG
-
-__device__ __forceinline__ double xp_sin(double x) { const double xx = x * x; return x * (1.0 + xx * (-1.0 / 6 + xx * (1.0 / 120 + xx * (-1.0 / 5040 + xx * (1.0 / 362880 + xx * (-1.0 / 39916800)))))); }
-__device__ __forceinline__ double xp_cos(double x) { const double xx = x * x; return 1.0 + xx * (-0.5 + xx * (1.0 / 24 + xx * (-1.0 / 720 + xx * (1.0 / 40320 + xx * (-1.0 / 3628800 + xx * (1.0 / 479001600)))))); }
-#endif
 __device__ __forceinline__ SE3 se3_exp(const double* u) {
   const double wx = u[0], wy = u[1], wz = u[2];
   const double theta = sqrt(wx * wx + wy * wy + wz * wz);
@@ -112,13 +107,8 @@ __device__ __forceinline__ SE3 se3_exp(const double* u) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) { R[i] = (i % 4 == 0 ? 1.0 : 0.0) + Om[i] + Om2[i]; V[i] = R[i]; }
   } else {
-#ifdef XP_TRIG
-    const double s = xp_sin(theta), c = xp_cos(theta);
-    const double a = s / theta, b = (1 - c) / (theta * theta), cc = (theta - s) / (theta * theta * theta);
-#else
     const double s = sin_glibc_small(theta), c = cos(theta);
     const double a = s / theta, b = (1 - c) / (theta * theta), cc = (theta - s) / cube_rn(theta);
-#endif
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
       R[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * Om[i] + b * Om2[i];

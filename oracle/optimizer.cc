@@ -98,17 +98,6 @@ static void mat3mul(const double A[9], const double B[9], double C[9]) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
 }
-#ifdef XP_TRIG
-static inline double xp_sin(double x) { const double xx = x * x; return x * (1.0 + xx * (-1.0 / 6 + xx * (1.0 / 120 + xx * (-1.0 / 5040 + xx * (1.0 / 362880 + xx * (-1.0 / 39916800)))))); }
-static inline double xp_cos(double x) { const double xx = x * x; return 1.0 + xx * (-0.5 + xx * (1.0 / 24 + xx * (-1.0 / 720 + xx * (1.0 / 40320 + xx * (-1.0 / 3628800 + xx * (1.0 / 479001600)))))); }
-#define XSIN xp_sin
-#define XCOS xp_cos
-#define XPOW3(t) ((t) * (t) * (t))
-#else
-#define XSIN std::sin
-#define XCOS std::cos
-#define XPOW3(t) std::pow(t, 3)
-#endif
 static SE3Quat expSE3(const double u[6]) {  // se3quat.h:219-250
   const double omega[3] = {u[0], u[1], u[2]}, upsilon[3] = {u[3], u[4], u[5]};
   const double theta = std::sqrt(omega[0] * omega[0] + omega[1] * omega[1] + omega[2] * omega[2]);
@@ -120,8 +109,8 @@ static SE3Quat expSE3(const double u[6]) {  // se3quat.h:219-250
     for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + Om[i] + Om2[i];
     memcpy(V, R, sizeof R);
   } else {
-    const double a = XSIN(theta) / theta, b = (1 - XCOS(theta)) / (theta * theta);
-    const double c = (theta - XSIN(theta)) / XPOW3(theta);
+    const double a = std::sin(theta) / theta, b = (1 - std::cos(theta)) / (theta * theta);
+    const double c = (theta - std::sin(theta)) / std::pow(theta, 3);
     for (int i = 0; i < 9; ++i) {
       R[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * Om[i] + b * Om2[i];
       V[i] = (i % 4 == 0 ? 1.0 : 0.0) + b * Om[i] + c * Om2[i];

@@ -216,3 +216,21 @@ def test_reader_refuses_what_it_does_not_understand(decl, named):
     with pytest.raises(ValueError) as e:
         cdecl.parse(good + decl + "\n")
     assert named in str(e.value), str(e.value)
+
+
+def test_developer_switch_table_lists_exactly_what_the_library_reads():
+    """INTEGRATION.md's "Developer switches" table against the getenv("MORB_...") calls of the library's sources: neither may name a
+    variable the other does not (rows whose "read by" column is a file under tests/ belong to a test helper, not to the library)."""
+    read = set()
+    for d in (os.path.join(PKG, "csrc"), INCLUDE):
+        for path in glob.glob(os.path.join(d, "**", "*"), recursive=True):
+            if os.path.isfile(path):
+                read |= set(re.findall(r'getenv\(\s*"(MORB_\w+)"', open(path, encoding="utf-8", errors="replace").read()))
+    text = open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8").read()
+    table = text[text.index("### Developer switches"):].split("\n## ")[0]
+    listed = set()
+    for row in re.findall(r"^\|(.+)\|\s*$", table, re.M)[2:]:   # (without the header and its rule)
+        variable, read_by = re.split(r"(?<!\\)\|", row)[:2]
+        if "tests/" not in read_by:
+            listed |= set(re.findall(r"MORB_\w+", variable))
+    assert read and read == listed

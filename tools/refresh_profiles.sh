@@ -74,7 +74,6 @@ for l in sys.stdin:
         d=json.loads(l); s=d['extract_stage_ms_per_step']
         print('$m', round(d['value']), 'frames/s', round(d['ms_per_step'],3), 'ms |', ' '.join(f'{k} {v:.3f}' for k,v in s.items()))
 "; done; done > "$O/matcher_placement_ab.txt"
-$T bash tools/r06_pyr_chunk.sh > "$O/pyramid_chunk_sweep.txt" 2>/dev/null
 # does v_mfma_f64_4x4x4 add its four products in order, each rounded?  (the probe the edge-order PoseOptimization rests on; the handle repeats a short form of it at creation)
 { hipcc --offload-arch=gfx950 -O3 -o /tmp/mfma_chain tools/micro/mfma_chain.hip 2>&1 && /tmp/mfma_chain; } > "$O/mfma_chain_probe.txt" 2>&1
 MORB_DIST_BACKEND=gloo $T python3 bench.py --gpus 2 --batch 64 --steps 10 --full --no-extras --no-cpu-baseline --sustained-s 0 > "$O/bench_gpus2_gloo_one_gpu.json" 2>/dev/null
