@@ -267,19 +267,14 @@ __global__ __launch_bounds__(256) void k_level0(const uint8_t* __restrict__ src,
 // K5: GaussianBlur(7x7, sigma 2, BORDER_REFLECT_101), OpenCV fixed-point path: 8.8 kernel
 // {18,34,48,56,48,34,18}, row pass exact, column pass rounded (+0.5) to u8.  The level's stored 3-px
 // reflect-101 pad is exactly the border the blur needs, so the tile loads straight from the padded pyramid.
-// v2: no LDS.  A thread owns a 4-pixel-wide column strip and walks down BT_ROWS rows keeping the last seven
-// row-pass results (4 x u16, packed in two dwords) in registers; every output dword (4 pixels) needs three
-// aligned dword loads of the source row (bytes x-3 .. x+8; the interior starts kPyrPad = 3 bytes into the stored row and
-// 3 - 3 = 0, so x % 4 == 0 makes the window 4-byte aligned).  HBM traffic = read P (+halo rows) + write P.
-#ifndef MORB_BT_ROWS
-#define MORB_BT_ROWS 24   // rows per strip (round 4, B = 512, blur underneath the quadtree: 16 / 24 / 32 rows -> 131.9 / 132.9 / 132.0 k frames/s: fewer halo rows against emptier tiles)
-#endif
-constexpr int BT_W = 256, BT_ROWS = MORB_BT_ROWS, BT_TY = 8;   // workgroup: 32 lanes x 8 px wide, 8 half-waves x BT_ROWS rows tall -> 256 px x 192 rows per tile
-constexpr int BT_H = BT_ROWS * BT_TY;
-#ifndef MORB_BT_AHEAD
-#define MORB_BT_AHEAD 4   // (1 / 2 / 3 / 4 / 6 rows ahead: 440 / 372 / 363 / 359 / 374 us per 512 images on one box)
-#endif
-constexpr int BT_AHEAD = MORB_BT_AHEAD;   // source rows in flight ahead of the row being filtered
+// No LDS.  A lane owns a strip of 8 columns x BT_ROWS rows (blur_items.h numbers the strips of an image linearly, so every lane of
+// every wave but an image's last has one) and walks down it keeping the row-pass results of eight source rows in registers, two
+// rows to a dword.  A source row is one 16-byte load (bytes x - 3 .. x + 12 of the level; the interior starts kPyrPad = 3 bytes
+// into the 64-byte-aligned stored row, so the load is 8-byte aligned), an output row one 8-byte store.
+// HBM traffic = read P (+ 6 halo rows per strip) + write P.
+constexpr int BT_WG = 256;   // lanes per workgroup: 256 consecutive items
+static_assert(BT_ROWS % 2 == 0, "k_blur produces two rows per step");
+constexpr int BT_AHEAD = 4;   // source rows in flight ahead of the rows being filtered (2 / 4 / 6 rows ahead: 313 / 295 / 292 us per 512 images alone on the chip, 4 and 6 the same 3.632 ms step)
 typedef unsigned short blur_u16x2 __attribute__((ext_vector_type(2)));
 // Horizontal 7-tap of eight neighbouring pixels: v_dot4_u32_u8 of the four loaded dwords against the packed kernel weights
 // (18 34 48 56 | 48 34 18 0), shifted per pixel (blur_h8).  Results are exact integers <= 255 * 256.
@@ -311,79 +306,91 @@ __device__ __forceinline__ void blur_h8(const uint4 w, uint32_t h[8]) {
 __device__ __forceinline__ uint32_t blur_dot2(uint32_t pair, uint32_t w, uint32_t acc) {   // v_dot2_u32_u16
   return __builtin_amdgcn_udot2(__builtin_bit_cast(blur_u16x2, pair), __builtin_bit_cast(blur_u16x2, w), acc, false);
 }
-// Vertical pass: consecutive rows' horizontal sums are kept as 16-bit pairs (row r | row r+1 << 16), so the 7 taps are three
-// v_dot2_u32_u16 and one multiply-add.  Round 2: 8 pixels per thread — one 16-byte load and one 8-byte store per row instead of
+// Vertical pass: the rows' horizontal sums are kept as 16-bit pairs (row 2k | row 2k + 1 << 16) and the 7 taps of two output rows
+// are eight v_dot2_u32_u16.  Round 2: 8 pixels per thread — one 16-byte load and one 8-byte store per row instead of
 // 3 + 1 dword accesses per 4 pixels (the texture path is priced per instruction).
-#ifndef MORB_BLUR_MIN_WAVES
-#define MORB_BLUR_MIN_WAVES 1
-#endif
-__global__ __launch_bounds__(256, MORB_BLUR_MIN_WAVES) void k_blur(const LevelGeom* __restrict__ geom, int nlevels,
-                                              const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur) {
-  // Workgroup -> (image, tile).  Consecutive workgroup ids go round-robin to the 8 XCDs: in the plain (tile, image) order the 256-px-wide
-  // neighbours of a tile row — whose 264-byte row segments start 16 bytes into a 128-byte line and so share a line with each neighbour —
-  // and the tiles above / below (6 halo rows) sit on different L2s, and the stage fetched 1.9 x the pyramid.  Remapped (image counts that
-  // are multiples of 8), XCD k works through images k, k + 8, ... tile by tile.
-  int tileId = blockIdx.x, img = blockIdx.y;
+// Five waves per SIMD (at most 96 VGPRs): left to itself the register allocator takes 97 and falls to four.  Six (80 VGPRs) costs a
+// spill, or three rows ahead instead of four without one: 296 us per 512 images against 295.
+__global__ __launch_bounds__(BT_WG) __attribute__((amdgpu_waves_per_eu(5))) void k_blur(const BlurSeg* __restrict__ seg, int nseg, int nitems,
+                                                const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur) {
+  // Workgroup -> (image, 256 consecutive items).  Consecutive workgroup ids go round-robin to the 8 XCDs: in the plain (workgroup, image)
+  // order neighbouring strips — whose row segments share 128-byte lines — and the strips above / below (6 halo rows) sit on different
+  // L2s, and the stage fetched 1.9 x the pyramid.  Remapped (image counts that are multiples of 8), XCD k works through images
+  // k, k + 8, ... in memory order.
+  int wg = blockIdx.x, img = blockIdx.y;
   if ((gridDim.y & 7) == 0) {
     const unsigned n = blockIdx.x + gridDim.x * blockIdx.y;
     const unsigned xcd = n & 7u, slot = n >> 3, grp = slot / gridDim.x;
-    tileId = __builtin_amdgcn_readfirstlane((int)(slot - grp * gridDim.x)); img = __builtin_amdgcn_readfirstlane((int)(xcd + 8u * grp));
+    wg = __builtin_amdgcn_readfirstlane((int)(slot - grp * gridDim.x)); img = __builtin_amdgcn_readfirstlane((int)(xcd + 8u * grp));
   }
-  int l = 0;
-  while (l + 1 < nlevels && tileId >= geom[l + 1].blurTileBase) ++l;
-  const LevelGeom g = geom[l];
-  const int t = tileId - g.blurTileBase;
-  const int tx = t % g.blurTilesX, ty = t / g.blurTilesX;
-  const int x = tx * BT_W + (threadIdx.x & 31) * 8;
-  const int y0 = ty * BT_H + (threadIdx.x >> 5) * BT_ROWS;
-  if (x >= g.w || y0 >= g.h) return;
+  // Item -> span: the wave's first item finds it with scalar loads; the lanes behind a span boundary inside the wave step on.
+  const int item0 = __builtin_amdgcn_readfirstlane(wg * BT_WG + (int)(threadIdx.x & ~63u));
+  const int item = item0 + (int)(threadIdx.x & 63u);
+  if (item >= nitems) return;
+  int s0 = 0;
+  while (s0 + 1 < nseg && item0 >= seg[s0 + 1].itemBase) ++s0;
+  int s = s0;
+  for (int k = s0 + 1; k < nseg && seg[k].itemBase <= item0 + 63; ++k) s += item >= seg[k].itemBase;
+  const BlurSeg g = seg[s];
+  const unsigned j = (unsigned)(item - g.itemBase);
+  const unsigned sy = blur_div(j, g.magic, g.shift);
+  const int x = (int)(j - __umul24(sy, (unsigned)g.nsx)) * BT_PX;
+  const int y0 = g.y0 + (int)sy * BT_ROWS;
   // stored-row origin of this strip: row (y + kPyrPad - 3), byte (kPyrPad + x - 3) = x
-  const uint8_t* src = pyr + g.pyrOff + (size_t)img * g.pyrImg + (size_t)(kPyrPad + y0 - 3) * g.pstride + (kPyrPad - 3) + x;
-  uint8_t* dst = blur + g.blurOff + (size_t)img * g.blurImg + (size_t)y0 * g.bstride + x;
-  uint32_t P[5][8], hl[8];   // P[j] = rows (y + j, y + j + 1) of the horizontal sums, hl = row y + 5
+  const uint8_t* src = pyr + g.pyrOff + (size_t)img * g.pyrImg + (uint32_t)((kPyrPad + y0 - 3) * g.pstride + (kPyrPad - 3) + x);
+  uint8_t* dst = blur + g.blurOff + (size_t)img * g.blurImg + (uint32_t)(y0 * g.bstride + x);
+  // Row-pass results as pairs of one parity, (source row 2k | source row 2k + 1 << 16) relative to src; output row r takes source
+  // rows r .. r + 6.  With A, B, C, D the pairs from source row r (r even) on,
+  //   out[r]     = A . (18, 34) + B . (48, 56) + C . (48, 34) + D . (18,  0)
+  //   out[r + 1] = A . ( 0, 18) + B . (34, 48) + C . (56, 48) + D . (34, 18)
+  // four v_dot2_u32_u16 per pixel and row and one pack per pixel and TWO rows; the same integer sums as seven multiply-adds.
+  uint32_t A[8], B[8], C[8];
   {
     uint32_t h[6][8];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) blur_h8(blur_load16(src + (size_t)k * g.pstride), h[k]);
+    for (int k = 0; k < 6; ++k) blur_h8(blur_load16(src + (uint32_t)(k * g.pstride)), h[k]);
 #pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) P[j][k] = h[j][k] | (h[j + 1][k] << 16);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hl[k] = h[5][k];
+    for (int k = 0; k < 8; ++k) { A[k] = h[0][k] | (h[1][k] << 16); B[k] = h[2][k] | (h[3][k] << 16); C[k] = h[4][k] | (h[5][k] << 16); }
   }
-  const int rows = (g.h - y0) < BT_ROWS ? (g.h - y0) : BT_ROWS;
-  constexpr uint32_t W01 = 18u | (34u << 16), W23 = 48u | (56u << 16), W45 = 48u | (34u << 16);
-  // Rows past the bottom of the level (the last strip of a tile column) are computed like the others — from the last padded row, so no
-  // load leaves the level — and only their store is skipped: with the whole row body under `if (r < rows)` (per-lane: the two halves of a
+  const size_t bstep = (size_t)g.bstride;
+  constexpr uint32_t WA0 = 18u | (34u << 16), WB0 = 48u | (56u << 16), WC0 = 48u | (34u << 16), WD0 = 18u;
+  constexpr uint32_t WA1 = 18u << 16, WB1 = 34u | (48u << 16), WC1 = 56u | (48u << 16), WD1 = 34u | (18u << 16);
+  // Rows past the bottom of the level (the last strip of a column) are computed like the others — from the last padded row, so no
+  // load leaves the level — and only their store is skipped: with the whole row body under `if (r < rows)` (per-lane: the lanes of a
   // wave work different strips) the compiler merged the rotating row window through 688 v_mov per wave, a third of the kernel's VALU work.
-  const int lastRow = g.h + 2 * kPyrPad - 1 - (kPyrPad + y0 - 3);   // last stored row, relative to src
+  const int lastRow = g.h - y0 + 5;   // last stored row relative to src (row y0 - 3): h + 2 * kPyrPad - 1 - (kPyrPad + y0 - 3); output row r exists while r + 5 < lastRow
   // The source rows are requested BT_AHEAD rows before they are used: with the load at the top of the row that needs it the wave sat
   // through a full memory round trip per row (load, s_waitcnt vmcnt(0), 75 VALU instructions, store — sixteen times), at five waves per SIMD.
   uint4 wq[BT_AHEAD];
 #pragma unroll
   for (int d = 0; d < BT_AHEAD; ++d) wq[d] = blur_load16(src + (uint32_t)__umul24(min(6 + d, lastRow), g.pstride));
 #pragma unroll
-  for (int r = 0; r < BT_ROWS; ++r) {
-    {   // (fully unrolled: the row window rotates by renaming)
-    uint32_t hn[8], acc[8];
-    const uint4 wcur = wq[r % BT_AHEAD];
+  for (int r = 0; r < BT_ROWS; r += 2) {
+    {   // (fully unrolled: the window rotates by renaming)
+    uint32_t h0[8], h1[8], D[8], acc0[8], acc1[8];
+    const uint4 w0 = wq[r % BT_AHEAD];
     if (r + BT_AHEAD < BT_ROWS) wq[r % BT_AHEAD] = blur_load16(src + (uint32_t)__umul24(min(r + 6 + BT_AHEAD, lastRow), g.pstride));
-    blur_h8(wcur, hn);
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      acc[k] = blur_dot2(P[0][k], W01, blur_dot2(P[2][k], W23, blur_dot2(P[4][k], W45, __umul24(18u, hn[k]) + 32768u)));   // (hn < 2^16: v_mad_u32_u24, full rate)
-    // acc < 2^24: the rounded output is byte 2 of each accumulator
-    uint2 o;
-    o.x = __builtin_amdgcn_perm(acc[1], acc[0], 0x0c0c0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020c0cu);
-    o.y = __builtin_amdgcn_perm(acc[5], acc[4], 0x0c0c0602u) | __builtin_amdgcn_perm(acc[7], acc[6], 0x06020c0cu);
-    if (r < rows) *reinterpret_cast<uint2*>(dst + (size_t)r * g.bstride) = o;   // columns >= w land in the row's alignment slack
+    const uint4 w1 = wq[(r + 1) % BT_AHEAD];
+    if (r + 1 + BT_AHEAD < BT_ROWS) wq[(r + 1) % BT_AHEAD] = blur_load16(src + (uint32_t)__umul24(min(r + 7 + BT_AHEAD, lastRow), g.pstride));
+    blur_h8(w0, h0);
+    blur_h8(w1, h1);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      P[0][k] = P[1][k]; P[1][k] = P[2][k]; P[2][k] = P[3][k]; P[3][k] = P[4][k];
-      P[4][k] = hl[k] | (hn[k] << 16);
-      hl[k] = hn[k];
+      D[k] = h0[k] | (h1[k] << 16);   // (v_lshl_or_b32)
+      acc0[k] = blur_dot2(A[k], WA0, blur_dot2(B[k], WB0, blur_dot2(C[k], WC0, blur_dot2(D[k], WD0, 32768u))));
+      acc1[k] = blur_dot2(A[k], WA1, blur_dot2(B[k], WB1, blur_dot2(C[k], WC1, blur_dot2(D[k], WD1, 32768u))));
     }
+    // acc < 2^24: the rounded output is byte 2 of each accumulator
+    uint2 o0, o1;
+    o0.x = __builtin_amdgcn_perm(acc0[1], acc0[0], 0x0c0c0602u) | __builtin_amdgcn_perm(acc0[3], acc0[2], 0x06020c0cu);
+    o0.y = __builtin_amdgcn_perm(acc0[5], acc0[4], 0x0c0c0602u) | __builtin_amdgcn_perm(acc0[7], acc0[6], 0x06020c0cu);
+    o1.x = __builtin_amdgcn_perm(acc1[1], acc1[0], 0x0c0c0602u) | __builtin_amdgcn_perm(acc1[3], acc1[2], 0x06020c0cu);
+    o1.y = __builtin_amdgcn_perm(acc1[5], acc1[4], 0x0c0c0602u) | __builtin_amdgcn_perm(acc1[7], acc1[6], 0x06020c0cu);
+    if (r + 5 < lastRow) *reinterpret_cast<uint2*>(dst) = o0;   // (row r is inside the level; columns >= w land in the row's alignment slack)
+    if (r + 6 < lastRow) *reinterpret_cast<uint2*>(dst + bstep) = o1;
+    dst += 2 * bstep;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { A[k] = B[k]; B[k] = C[k]; C[k] = D[k]; }
     }
   }
 }
@@ -942,7 +949,7 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
   std::vector<PyrCol> pcols; std::vector<PyrRow> prows; std::vector<PyrEdge> pedges;
   bool pyrPacked = true;
   size_t blurOff = 0, qtOff = 0;
-  int cellBase = 0, selBase = 0, blurTileBase = 0;
+  int cellBase = 0, selBase = 0;
   e->cellCap = 0; e->maxCells = 0; e->maxNodeCap = 0; e->maxListCap = 0;
   std::vector<FastSeg> segs;
   LevelGeom teamGeom[kMaxLevels];
@@ -993,8 +1000,25 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
     g.selBase = selBase; selBase += g.selCap;
     g.scale = e->scale[l];
     g.kpSize = (float)(int)(PATCH * e->scale[l]);
-    g.blurTilesX = div_up(g.w, BT_W); g.blurTilesY = div_up(g.h, BT_H);
-    g.blurTileBase = blurTileBase; blurTileBase += g.blurTilesX * g.blurTilesY;
+  }
+  // k_blur's items: strips numbered across the levels of an image (blur_items.h), one table entry per span
+  std::vector<BlurSeg> blurSegs;
+  {
+    int lw[kMaxLevels], lh[kMaxLevels];
+    for (int l = 0; l < L; ++l) { lw[l] = e->geom[l].w; lh[l] = e->geom[l].h; }
+    BlurSpan spans[4 * kMaxLevels];
+    const int ns = blur_build_spans(lw, lh, L, spans, 4 * kMaxLevels, &e->blurItems);
+    MORB_REQUIRE(ns > 0, MORB_ERR_UNSUPPORTED, "pyramid too large for the blur's item numbering");
+    for (int k = 0; k < ns; ++k) {
+      const LevelGeom& g = e->geom[spans[k].level];
+      MORB_REQUIRE(g.pyrImg < (1ull << 32) && g.blurImg < (1ull << 32), MORB_ERR_UNSUPPORTED, "pyramid level too large");
+      BlurSeg s = {};
+      s.itemBase = spans[k].itemBase; s.nsx = spans[k].nsx; s.magic = spans[k].magic; s.shift = spans[k].shift;
+      s.y0 = spans[k].sy0 * BT_ROWS; s.w = g.w; s.h = g.h; s.pstride = g.pstride; s.bstride = g.bstride;
+      s.pyrImg = (unsigned)g.pyrImg; s.blurImg = (unsigned)g.blurImg; s.pyrOff = g.pyrOff; s.blurOff = g.blurOff;
+      blurSegs.push_back(s);
+    }
+    e->blurSegs = ns;
   }
   e->cellCap = (std::max(e->cellCap, QT_GATHER) + 3) / 4 * 4;   // (k_distribute's team gather reads a cell's list as 16-byte words)
   // global key scratch: 2 x (cells x cellCap) per (level, image), used only when a level has > kLdsKeys candidates
@@ -1119,7 +1143,6 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
   }
 
   e->selPerImg = selBase;
-  e->blurTiles = blurTileBase;
   e->pyrBytes = pyrTotal; e->blurBytes = blurOff; e->qtElems = qtOff;
   e->outCap = selBase;
   // Candidate keys of a level live in LDS (two arrays) when they fit, else in the global scratch (much slower: every partition pass goes
@@ -1222,6 +1245,8 @@ int configure(morb_extractor* e, int W, int H, int nimg) {
   }
   MORB_HIP_CHECK(e->d_segTab.alloc(sizeof(FastSeg) * segs.size()));
   MORB_HIP_CHECK(hipMemcpy(e->d_segTab, segs.data(), sizeof(FastSeg) * segs.size(), hipMemcpyHostToDevice));
+  MORB_HIP_CHECK(e->d_blurSeg.alloc(sizeof(BlurSeg) * blurSegs.size()));
+  MORB_HIP_CHECK(hipMemcpy(e->d_blurSeg, blurSegs.data(), sizeof(BlurSeg) * blurSegs.size(), hipMemcpyHostToDevice));
   MORB_HIP_CHECK(e->d_tabs.alloc(sizeof(ResizeTab) * std::max<size_t>(tabs.size(), 1)));
   if (!tabs.empty()) MORB_HIP_CHECK(hipMemcpy(e->d_tabs, tabs.data(), sizeof(ResizeTab) * tabs.size(), hipMemcpyHostToDevice));
   MORB_HIP_CHECK(e->d_pcol.alloc(sizeof(PyrCol) * std::max<size_t>(pcols.size(), 1)));
@@ -1525,7 +1550,7 @@ int morb_extract_batch(morb_extractor* e, const uint8_t* d_images, int nimg, int
   hipStream_t sideStream = e->sideStream;
   MORB_HIP_CHECK(hipStreamWaitEvent(sideStream, e->evFork, 0));
   if (evs) (void)hipEventRecord(evs[6], sideStream);
-  hipLaunchKernelGGL(k_blur, dim3(e->blurTiles, nimg), dim3(256), 0, sideStream, e->d_geom, L, e->d_pyr, e->d_blur);
+  hipLaunchKernelGGL(k_blur, dim3(div_up(e->blurItems, BT_WG), nimg), dim3(BT_WG), 0, sideStream, e->d_blurSeg, e->blurSegs, e->blurItems, e->d_pyr, e->d_blur);
   if (evs) (void)hipEventRecord(evs[7], sideStream);
   MORB_HIP_CHECK(hipEventRecord(e->evJoin, sideStream));
   mark(3);

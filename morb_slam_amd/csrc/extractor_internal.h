@@ -8,6 +8,7 @@
 
 #include "hip_owned.h"
 #include "morb_hip.h"
+#include "blur_items.h"       // k_blur's work items: BT_ROWS, the spans of the item numbering
 #include "pyramid_layout.h"   // EDGE (the algorithmic border), kPyrPad (the stored one), the layout of d_pyr
 
 namespace morb {
@@ -28,7 +29,6 @@ struct LevelGeom {
   int nodeCap, listCap;
   int selBase, selCap;                  // per-image offsets into sel[]
   unsigned long long qtOff, qtImg;      // element offsets into the global key scratch
-  int blurTileBase, blurTilesX, blurTilesY;
   int xtabOff, ytabOff;                 // offsets (entries) into the resize tables
   float scale;                          // mvScaleFactor[l]
   float kpSize;                         // (float)(int)(PATCH_SIZE * mvScaleFactor[l])  (:831)
@@ -36,6 +36,15 @@ struct LevelGeom {
   // level, the byte offset of its LDS region inside the workgroup's allocation, and the candidate keys its LDS arrays hold
   int distGroup, distWave, distLdsOff, distKeyCap;
   int distTeam;                         // all waves of the workgroup work this level as a team (quadtree.h: Team)
+};
+
+// k_blur: one entry per span of the item numbering (blur_items.h) with what a lane needs of the span's level.  A wave can straddle
+// spans and levels, so the lanes read their entry with vector loads (five 16-byte words).
+struct alignas(16) BlurSeg {
+  int itemBase, nsx; unsigned magic, shift;
+  int y0, w, h, pstride;                // y0: first row of the span
+  int bstride; unsigned pyrImg, blurImg; int pad_;   // per-image sizes in bytes (a level of one image is far below 4 GB)
+  unsigned long long pyrOff, blurOff;
 };
 
 // What k_fastw needs of every level, passed by value: the kernarg segment is read with scalar loads, so looking a
@@ -97,7 +106,7 @@ struct morb_extractor {
   int totalCells = 0, cellCap = 0, maxCells = 0, maxNodeCap = 0, maxListCap = 0;
   int fastSegs[2] = {0, 0}, fastRows[2] = {0, 0};   // k_fastw launch groups (cells, LDS window rows)
   int fastP = 128;                                  // k_fastw: LDS pitch of the segment windows
-  int selPerImg = 0, blurTiles = 0, outCap = 0;
+  int selPerImg = 0, blurItems = 0, blurSegs = 0, outCap = 0;   // blurItems: k_blur's items per image, blurSegs: entries of d_blurSeg
   size_t pyrBytes = 0, blurBytes = 0, qtElems = 0, distSmem = 0, fastSmem[2] = {0, 0};
   int distKeyCap = 0;                        // candidate keys of level 0 that fit the quadtree's LDS arrays (smaller levels: scaled by area)
   int distGroups = 0, distWaves = 1;         // k_distribute grid: workgroups per image, waves per workgroup
@@ -117,6 +126,7 @@ struct morb_extractor {
   morb::PyrLevel pyrLv[morb::kMaxLevels] = {}; morb::PyrLevel0 pyrL0 = {};
   bool pyrPacked = true;   // every level's four-pixel chunks fit k_resize's 8-byte source windows (scale factors up to ~1.75)
   morb::DeviceArray<morb::FastSeg> d_segTab;
+  morb::DeviceArray<morb::BlurSeg> d_blurSeg;
   morb::DeviceArray<uint8_t> d_pyr, d_blur;
   morb::DeviceArray<uint32_t> d_cand, d_qt, d_sel;
   morb::DeviceArray<int> d_candCnt, d_selCnt, d_lap;
