@@ -58,10 +58,27 @@ def build_oracle():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
 
 
-def build_test_native():
+def build_test_native(probe=False):
+    """tests/native/libqt_host.so (returned); probe=True (build()) also builds tests/native/libdense_probe.so, which its own tests load through
+    build_dense_probe() — the host quadtree's tests do not depend on a device compile."""
     nat = os.path.join(ROOT, "tests", "native")
     out = os.path.join(nat, "libqt_host.so")
     src = os.path.join(nat, "qt_host.cc")
     if _stale(out, [src, os.path.join(CSRC, "quadtree.h")]):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
+    if probe:
+        build_dense_probe()
     return out
+
+
+PROBE_OUT = os.path.join(ROOT, "tests", "native", "libdense_probe.so")
+
+
+def build_dense_probe():
+    """tests/native/libdense_probe.so: the dense LDL^T solvers and the MFMA Schur product behind thin test-only entry points, compiled with
+    the library's own HIPCC_FLAGS so that the headers build exactly as they do in libmorb_hip.so (which gains no export from it)."""
+    src = os.path.join(ROOT, "tests", "native", "dense_probe.hip")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("dense_ldlt.h", "schur_mfma.h", "ba_host.h", "wave.h")]
+    if _stale(PROBE_OUT, deps):
+        subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + HIPCC_FLAGS + ["-o", PROBE_OUT, src])
+    return PROBE_OUT

@@ -1,5 +1,5 @@
-// Dense symmetric solve H x = b by LDL^T for the reduced camera systems (n <= ~160: LocalBundleAdjustment's 6 nFree, LocalInertialBA's
-// 15 nOpt), ONE workgroup with the whole lower triangle resident in LDS.
+// Dense symmetric solve H x = b by LDL^T for the reduced camera systems (n <= 163: LocalBundleAdjustment's 6 nFree up to 27 free
+// keyframes, LocalInertialBA's 15 nOpt up to 10), ONE workgroup with the whole lower triangle resident in LDS.
 //
 // Round 1 factorised in global memory (LocalInertialBA: ~230 us at n = 150) or with a one-thread diagonal block and
 // column-at-a-time substitutions (LocalBA: 98 us at n = 120); with a single workgroup nothing hides a global round trip.  Here:
@@ -24,6 +24,10 @@ namespace morbdense {
 namespace {
 
 constexpr int NB = 16, NBP = 17, LT = 512;   // 512 threads: two waves per SIMD
+// Dynamic LDS the callers may ask for (160 KB per CU on gfx950), named once: the size tiers of both bundle adjusters follow from them.
+constexpr size_t LDS_SOLVER_LIMIT = 156 * 1024;      // ldlt_solve: 8 lds_doubles(n) must fit (n <= 163), else ldlt_solve_global
+constexpr size_t GLOBAL_SOLVER_LIMIT = 150 * 1024;   // ldlt_solve_global: dblk | y | panel copies (n <= 525), else the copies go to global scratch
+constexpr size_t PERSISTENT_HS_LIMIT = 136 * 1024;   // k_local_ba (local_ba.hip) keeps Hs | x, 8 P (P + 1) bytes, in LDS (P <= 131: 21 free keyframes)
 typedef double ld_d4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int tri(int r, int c) { return (int)(__umul24((unsigned)r, (unsigned)(r + 1)) >> 1) + c; }   // c <= r; r < 4096: a 24-bit multiply (v_mul_lo_u32 is quarter rate)
 
@@ -331,8 +335,8 @@ __device__ bool ldlt_solve(const double* __restrict__ Hs, const double* b, doubl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The same factorisation for systems whose packed triangle does not fit LDS (n > ~176: LocalBundleAdjustment beyond 29 free keyframes —
-// the reference takes every covisible keyframe, Optimizer.cc:1058-1070 — and LocalInertialBA beyond 11): the matrix stays in global
+// The same factorisation for systems whose packed triangle does not fit LDS (n > 163: LocalBundleAdjustment beyond 27 free keyframes —
+// the reference takes every covisible keyframe, Optimizer.cc:1058-1070 — and LocalInertialBA beyond 10): the matrix stays in global
 // memory (L2), only the current 16-column panel lives in LDS.  ONE workgroup of 1024 threads, blocked right-looking LDL^T:
 // the 16 x 16 diagonal block is factorised by one wave in registers, every row below it by sixteen lanes (PanelStage), then one
 // trailing update of the matrix per panel on the FP64 matrix cores, TWO tiles per wave in flight so that eight global loads per lane

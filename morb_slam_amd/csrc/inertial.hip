@@ -1682,7 +1682,7 @@ __global__ __launch_bounds__(256) void k_iba_schur_finish(IbaDev D) {
   if (mat) D.Hs[(size_t)(15 * (r / 6) + r % 6) * D.P + 15 * (c / 6) + c % 6] -= cs;
   else if (rhs) D.bs[15 * (r / 6) + r % 6] -= cs;
 }
-// dense LDL^T + solve with the lower triangle resident in LDS (dense_ldlt.h): windows up to 15 N = 165
+// dense LDL^T + solve with the lower triangle resident in LDS (dense_ldlt.h): windows up to 15 N = 150 (n <= 163 fits)
 __global__ __launch_bounds__(morbdense::LT) void k_iba_solve_lds(IbaDev D) {
   extern __shared__ double sLd[];
   __shared__ int sOk;
@@ -1690,8 +1690,8 @@ __global__ __launch_bounds__(morbdense::LT) void k_iba_solve_lds(IbaDev D) {
   const bool ok = morbdense::ldlt_solve<true>(D.Hs, D.bs, D.x, D.P, sLd, &sOk);
   if (threadIdx.x == 0) D.scal[2] = ok ? 1.0 : 0.0;
 }
-// larger windows (bLarge, or more than 11 optimizable keyframes): the matrix stays in global memory, one 16-column panel at a time in LDS
-// (dense_ldlt.h: ldlt_solve_global; the panel copies move to a global scratch when even they do not fit LDS, P > ~530)
+// larger windows (bLarge, or more than 10 optimizable keyframes): the matrix stays in global memory, one 16-column panel at a time in LDS
+// (dense_ldlt.h: ldlt_solve_global; the panel copies move to a global scratch when even they do not fit LDS, P > 525)
 __global__ __launch_bounds__(morbdense::GT) void k_iba_solve_blocked(IbaDev D, int panelInLds) {
   extern __shared__ double sm[];   // dblk[NB * NBP] | y[n] | (pnlL | pnlU when they fit)
   __shared__ int sOk;
@@ -2063,14 +2063,14 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   if (nI) hipLaunchKernelGGL(k_iba_setup_links, dim3(nI), dim3(64), 0, st, D, d_scale);
   hipLaunchKernelGGL(k_iba_setup_pts, dim3(div_up((int)nPts, 256)), dim3(256), 0, st, D, (const float*)d_mpIn);   // points to FP64
   size_t blockedLds = sizeof(double) * (morbdense::global_lds_doubles(P) + morbdense::global_panel_doubles(P));
-  const int panelInLds = blockedLds <= 150 * 1024 ? 1 : 0;
+  const int panelInLds = blockedLds <= morbdense::GLOBAL_SOLVER_LIMIT ? 1 : 0;
   if (!panelInLds) blockedLds = sizeof(double) * morbdense::global_lds_doubles(P);
-  MORB_REQUIRE(blockedLds <= 150 * 1024, MORB_ERR_CAPACITY, "window too large for the dense solver");
+  MORB_REQUIRE(blockedLds <= morbdense::GLOBAL_SOLVER_LIMIT, MORB_ERR_CAPACITY, "window too large for the dense solver");
   if (blockedLds > 48 * 1024)
     MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iba_solve_blocked), hipFuncAttributeMaxDynamicSharedMemorySize, (int)blockedLds));
   size_t denseLds = sizeof(double) * morbdense::lds_doubles(P);
-  if (denseLds > 156 * 1024) denseLds = 0;   // larger windows (bLarge) use the global-memory solver
-  if (denseLds) MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+  if (denseLds > morbdense::LDS_SOLVER_LIMIT) denseLds = 0;   // larger windows (bLarge) use the global-memory solver
+  if (denseLds) MORB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iba_solve_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)morbdense::LDS_SOLVER_LIMIT));
   double h[4];   // computeActiveErrors + activeRobustChi2
   if (hipMemsetAsync(D.scal, 0, sizeof(double) * 4, st) != hipSuccess) return iba_fail("k_iba_errors failed");
   hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 0);

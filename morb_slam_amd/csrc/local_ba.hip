@@ -876,7 +876,7 @@ __global__ __launch_bounds__(GB) void k_g_schur_finish(const BaDev* __restrict__
     pb.x[r] = pb.b[r] - cs;
   }
 }
-// the reduced camera system beyond ~176 unknowns (30 free keyframes and more: the reference takes every covisible keyframe,
+// the reduced camera system beyond 163 unknowns (28 free keyframes and more: the reference takes every covisible keyframe,
 // Optimizer.cc:1058-1070): the matrix stays in global memory, one 16-column panel at a time in LDS (dense_ldlt.h: ldlt_solve_global);
 // HsG is overwritten by the factors (k_g_schur_finish rebuilds it for every trial); x = Hs^-1 x in place
 __global__ __launch_bounds__(morbdense::GT) void k_g_ldlt_global(const BaDev* __restrict__ pbp, double* __restrict__ HsG, double* __restrict__ pnlG,
@@ -1179,17 +1179,17 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
     if (!fail && !arena && hipStreamSynchronize(cst) != hipSuccess) fail = true;
   }
   p->ldsBytes = sizeof(double) * (size_t)h.P * (h.P + 1);
-  p->useLds = (p->ldsBytes <= 136 * 1024 && h.P <= 192) ? 1 : 0;
+  p->useLds = (p->ldsBytes <= morbdense::PERSISTENT_HS_LIMIT && h.P <= 192) ? 1 : 0;
   if (!p->useLds) p->ldsBytes = 0;
   p->denseLds = sizeof(double) * morbdense::lds_doubles(h.P);
-  if (p->denseLds > 156 * 1024 || h.P < 1) p->denseLds = 0;   // larger systems: the global-memory solver
-  if (!fail && p->denseLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_g_ldlt_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) fail = true;
+  if (p->denseLds > morbdense::LDS_SOLVER_LIMIT || h.P < 1) p->denseLds = 0;   // larger systems: the global-memory solver
+  if (!fail && p->denseLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_g_ldlt_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)morbdense::LDS_SOLVER_LIMIT) != hipSuccess) fail = true;
   p->globalLds = sizeof(double) * (morbdense::global_lds_doubles(std::max(h.P, 1)) + morbdense::global_panel_doubles(std::max(h.P, 1)));
-  p->panelInLds = p->globalLds <= 150 * 1024 ? 1 : 0;
+  p->panelInLds = p->globalLds <= morbdense::GLOBAL_SOLVER_LIMIT ? 1 : 0;
   if (!p->panelInLds) p->globalLds = sizeof(double) * morbdense::global_lds_doubles(std::max(h.P, 1));
-  if (!fail && !p->denseLds && (p->globalLds > 150 * 1024 ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k_g_ldlt_global), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)) fail = true;
-  if (!fail && p->useLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_ba), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024) != hipSuccess)
+  if (!fail && !p->denseLds && (p->globalLds > morbdense::GLOBAL_SOLVER_LIMIT ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_g_ldlt_global), hipFuncAttributeMaxDynamicSharedMemorySize, (int)morbdense::GLOBAL_SOLVER_LIMIT) != hipSuccess)) fail = true;
+  if (!fail && p->useLds && hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_ba), hipFuncAttributeMaxDynamicSharedMemorySize, (int)morbdense::PERSISTENT_HS_LIMIT) != hipSuccess)
     fail = true;
   if (fail) {
     set_error("device allocation/copy failed while creating the BA problem");

@@ -461,7 +461,7 @@ def make_inertial_ba_problem(n_opt=10, n_fixed_vis=6, n_points=1500, n_imu=40, s
         start.append(len(dts))
     # visual-only fixed keyframes: near the start of the chain, slightly displaced
     for k in range(n_fixed_vis):
-        R0, p0, _ = states[rng.integers(0, 3)]
+        R0, p0, _ = states[rng.integers(0, min(3, len(states)))]   # (a one-keyframe window has two states)
         states.append((R0 @ _rot_from_rotvec(rng.normal(0, 0.05, 3)), p0 + rng.normal(0, 0.15, 3), np.zeros(3)))
     nKF = len(states)
     kind = np.array([1] + [0] * n_opt + [2] * n_fixed_vis, np.uint8)

@@ -164,8 +164,8 @@ def test_local_ba_matches_oracle(kw):
 
 @pytest.mark.parametrize("n_free", [30, 45, 60])
 def test_local_ba_large_windows(n_free):
-    """The reference takes EVERY covisible keyframe (Optimizer.cc:1058-1070, no cap): beyond 29 free keyframes the reduced camera system
-    (6 n > 176 unknowns) no longer fits the LDS-resident LDL^T and is factorised in global memory, one 16-column panel in LDS at a time
+    """The reference takes EVERY covisible keyframe (Optimizer.cc:1058-1070, no cap): beyond 27 free keyframes the reduced camera system
+    (6 n > 163 unknowns) no longer fits the LDS-resident LDL^T and is factorised in global memory, one 16-column panel in LDS at a time
     (dense_ldlt.h: ldlt_solve_global) — same LM path, poses / points within 1e-4, identical erase flags."""
     from morb_slam_amd import Optimizer
     b = make_ba_problem(seed=5, n_free=n_free, n_fixed=6, n_points=3000)

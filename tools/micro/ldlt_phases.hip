@@ -21,7 +21,7 @@ int main(int argc, char** argv) {
   (void)hipMalloc(&dH, H.size() * 8); (void)hipMalloc(&dx, n * 8); (void)hipMalloc(&dd, 64);
   (void)hipMemcpy(dH, H.data(), H.size() * 8, hipMemcpyHostToDevice);
   const size_t lds = morbdense::lds_doubles(n) * 8;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)morbdense::LDS_SOLVER_LIMIT);
   hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   float best = 1e9;
   for (int it = 0; it < 20; ++it) {
