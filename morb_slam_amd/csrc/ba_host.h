@@ -1,4 +1,4 @@
-// Host side shared by the two bundle adjusters (local_ba.hip: ba_problem_create, inertial.hip: local_inertial_ba_impl): the carve
+// Host side shared by the two bundle adjusters (local_ba.hip: ba_problem_create, inertial_ba.hip: local_inertial_ba_impl): the carve
 // of one device block into arrays, and the flattened graph's lists.  Host only (no HIP header) and nothing here allocates device or
 // pinned memory: tests/native/ba_host_check.cc compiles it alone, with sanitizers.
 #pragma once

@@ -43,13 +43,13 @@ def sizes(n):
 
 
 def fits_lds_solver(n):
-    """ldlt_solve is the solver of an n x n system (local_ba.hip: denseLds, inertial.hip: denseLds)."""
+    """ldlt_solve is the solver of an n x n system (local_ba.hip: denseLds, inertial_ba.hip: denseLds)."""
     s = sizes(n)
     return 8 * s["lds_doubles"] <= s["LDS_SOLVER_LIMIT"]
 
 
 def panel_in_lds(n):
-    """ldlt_solve_global keeps its panel copies in LDS (local_ba.hip / inertial.hip: panelInLds)."""
+    """ldlt_solve_global keeps its panel copies in LDS (local_ba.hip / inertial_ba.hip: panelInLds)."""
     s = sizes(n)
     return 8 * (s["global_lds_doubles"] + s["global_panel_doubles"]) <= s["GLOBAL_SOLVER_LIMIT"]
 

@@ -1,6 +1,6 @@
 // Test-only probe of the dense FP64 building blocks: morbdense::ldlt_solve / ldlt_solve_global (dense_ldlt.h) and
 // morbschur::k_schur_mfma + schur_sum4 (schur_mfma.h), each launched ALONE with the sizes and limits the product launches them with
-// (local_ba.hip: k_g_ldlt_lds / k_g_ldlt_global / k_g_schur_finish, inertial.hip: k_iba_solve_lds / k_iba_solve_blocked).
+// (local_ba.hip: k_g_ldlt_lds / k_g_ldlt_global / k_g_schur_finish, inertial_ba.hip: k_iba_solve_lds / k_iba_solve_blocked).
 // Built by morb_slam_amd/build.py: build_test_native() with the library's own flags into tests/native/libdense_probe.so; it is not part of
 // libmorb_hip.so.  Nothing here allocates device memory: every buffer is the caller's (a torch tensor's data_ptr()).  Every launch is on
 // the null stream and is waited for; the return value is 0, a HIP error code, or one of the negative refusals below (nothing launched).

@@ -1,4 +1,4 @@
-"""Register / scratch / LDS use of the kernels in a built libmorb_hip*.so (no GPU needed): python tools/kmeta.py [lib] [name-substring ...]"""
+"""Register / spill / scratch / LDS use of the kernels in a built libmorb_hip*.so (no GPU needed): python tools/kmeta.py [lib] [name-substring ...]"""
 import os, re, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,4 +20,4 @@ for i, st in enumerate(starts):
         name = g("name")
         if args and not any(a in name for a in args):
             continue
-        print(f"{name[:70]:70s} vgpr {g('vgpr_count'):>4s} sgpr {g('sgpr_count'):>4s} scratch {g('private_segment_fixed_size'):>5s} lds {g('group_segment_fixed_size'):>6s}")
+        print(f"{name[:70]:70s} vgpr {g('vgpr_count'):>4s} sgpr {g('sgpr_count'):>4s} spill v {g('vgpr_spill_count'):>3s} s {g('sgpr_spill_count'):>3s} scratch {g('private_segment_fixed_size'):>5s} lds {g('group_segment_fixed_size'):>6s}")
