@@ -74,6 +74,22 @@ struct LocalInertialBAView {
   int outerIterations = 0, lmTrials = 0;
   bool ok = false;                     // false = "FAIL LOCAL-INERTIAL BA" (nothing to write back)
 };
+// What the three Optimizer::InertialOptimization overloads read and write (Optimizer.cc:2979-3428), flattened as
+// morb_inertial_optimization_batch takes one problem: the keyframes in temporal order (every link joins neighbours), their IMU states, which
+// of them carry an EdgeInertialGS to their predecessor and its preintegration, the flags and priors, and Rwg / scale / bg / ba.
+struct InertialOptimizationView {
+  int nKF = 0;
+  float* kfState = nullptr;                        // [nKF][21] in / out: Rwb row-major, twb, velocity, gyro bias, acc bias
+  const uint8_t* hasLink = nullptr;                // [nKF]
+  const morb_imu_preintegrated* pre = nullptr;     // [nKF]; pre[k] is read where hasLink[k] != 0
+  bool bMono = false, bFixedVel = false;           // first overload only
+  float priorG = 1e2f, priorA = 1e6f;              // first and second overload
+  double global16[16] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0};   // in / out: Rwg (row-major), scale, bg, ba
+  std::vector<uint8_t> reintegrate;                // out [nKF]: 1 where the reference calls mpImuPreintegrated->Reintegrate()
+  int outerIterations = 0, lmTrials = 0, nLinks = 0;
+  bool ok = false;                                 // false: fewer than two keyframes or no link, nothing written
+  double chi2[2] = {0, 0};                         // activeRobustChi2 before and after
+};
 // The graph Optimizer::LocalBundleAdjustment assembles (Optimizer.cc:1058-1351), flattened.
 struct LocalBAView {
   int nKF = 0, nMP = 0, nE = 0;
@@ -190,6 +206,38 @@ class Optimizer {
     g.outerIterations = stats[0]; g.lmTrials = stats[1]; g.ok = stats[2] != 0;
   }
 
+  // void static InertialOptimization(Map*, ...)  Optimizer.h:103-112 in its three overloads: mode 0 = (Rwg, scale, bg, ba, bMono, covInertial,
+  // bFixedVel, bGauss, priorG, priorA), 1 = (bg, ba, priorG, priorA), 2 = (Rwg, scale).  One problem through morb_inertial_optimization_batch:
+  // modes 0 and 2 (LocalMapping) on the mapping handle, mode 1 (LoopClosing's merge) on the loop-closing handle.
+  static void InertialOptimization(InertialOptimizationView& v, int mode, int device = 0) {
+    v.reintegrate.assign(v.nKF > 0 ? v.nKF : 0, 0);
+    v.outerIterations = v.lmTrials = v.nLinks = 0; v.ok = false; v.chi2[0] = v.chi2[1] = 0;
+    if (v.nKF < 2) return;
+    const int N = v.nKF;
+    Slot& o = slot(device, mode == 1 ? kLoopClosing : kMapping);
+    std::lock_guard<std::mutex> lock(o.mu);
+    Call c(device, morb_optimizer_stream(o.h));
+    const int start[2] = {0, N}, flags = (v.bMono ? 1 : 0) | (v.bFixedVel ? 2 : 0);
+    const float prior2[2] = {v.priorG, v.priorA};
+    const int *d_start = c.in(start, 2), *d_flags = c.in(&flags, 1);
+    float* d_state = c.in(v.kfState, (size_t)N * 21);
+    const uint8_t* d_hasLink = c.in(v.hasLink, N);
+    const morb_imu_preintegrated* d_pre = c.in(v.pre, N);
+    const float* d_prior2 = c.in(prior2, 2);
+    double* d_global = c.in(v.global16, 16);
+    uint8_t* d_reint = c.out_filled<uint8_t>(N, 0);
+    int* d_stats = c.out<int>(4);
+    double* d_chi2 = c.out_filled<double>(2, 0);
+    check(morb_inertial_optimization_batch(o.h, 1, N, d_start, d_state, d_hasLink, d_pre, mode, d_flags, d_prior2, d_global, d_reint, d_stats, d_chi2,
+                                           nullptr));
+    c.wait();
+    const std::vector<int> st = c.fetch(d_stats, 4);
+    v.outerIterations = st[0]; v.lmTrials = st[1]; v.ok = st[2] != 0; v.nLinks = st[3];
+    if (!v.ok) return;
+    c.fetch(d_state, v.kfState, (size_t)N * 21); c.fetch(d_global, v.global16, 16); c.fetch(d_chi2, v.chi2, 2);
+    v.reintegrate = c.fetch(d_reint, N);
+  }
+
   // static int OptimizeSim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, g2o::Sim3&, float th2, bool bFixScale, Matrix<double,7,7>&, bool bAllPoints)
   // Optimizer.h:97-101 -> nIn (0 on the early return).  One problem through morb_optimize_sim3_batch on the loop-closing handle.
   static int OptimizeSim3(OptimizeSim3View& v, int device = 0) {
@@ -236,6 +284,15 @@ class Optimizer {
   static int OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale, Mat77& mAcumHessian,
                           const bool bAllPoints = false);
 
+  // (include/Optimizer.h:103-112; call sites LocalMapping.cc:1205, :1391 and LoopClosing.cc:1902)
+  template <class MapT, class Mat3d, class Vec3d, class MatXd>
+  static void InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale, Vec3d& bg, Vec3d& ba, bool bMono, MatXd& covInertial, bool bFixedVel = false,
+                                   bool bGauss = false, float priorG = 1e2, float priorA = 1e6);
+  template <class MapT, class Vec3d>
+  static void InertialOptimization(MapT* pMap, Vec3d& bg, Vec3d& ba, float priorG = 1e2, float priorA = 1e6);
+  template <class MapT, class Mat3d>
+  static void InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale);
+
   // The reference's Optimizer is a stateless static class entered concurrently from Tracking (PoseOptimization, every frame) and from
   // LocalMapping (LocalBundleAdjustment, hundreds of milliseconds of LM trials): each role has its own handle — own stream, own
   // workspace — per device, created once (std::call_once), so a tracked frame never queues behind local-mapping trials; a mutex per
@@ -245,6 +302,7 @@ class Optimizer {
 
  private:
   template <class FrameT> static void write_back_inertial(FrameT* pFrame, const PoseInertialView& v);
+  template <class MapT, class Fill, class Back> static void inertial_optimization_on_map(MapT* pMap, int mode, Fill fill, Back back);
   template <class SE3> static SE3 se3_from_matrix(const double R[9], const double t[3]);
   // rotation (9, row-major) + translation (3) -> unit quaternion xyzw + translation (the *_fisheye pose entries take Trl that way)
   static void rot_to_pose7(const float* Rt12, float out[7]) {

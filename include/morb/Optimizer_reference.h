@@ -566,6 +566,106 @@ int Optimizer::OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Si
   return nIn;
 }
 
+// The three Optimizer::InertialOptimization overloads (Optimizer.cc:2979-3428) around one flattening: GetAllKeyFrames() without the keyframes
+// beyond GetMaxKFid() (:3007, :3191, :3339), ordered by walking the mPrevKF chains so that every link joins neighbours (a keyframe without a
+// link starts a chain, in GetAllKeyFrames() order); a link under the conditions of :3077-3078 (mPrevKF set, not isBad(), mPrevKF not beyond
+// maxKFid, its vertex present); vpKFs.front()'s bias as the initial bias.  fill sets what the overload passes in, back hands its by-reference
+// results out.  Modes 0 and 1 then write SetVelocity / SetNewBias on every keyframe and Reintegrate() where flagged (:3131-3155, :3292-3313).
+template <class MapT, class Fill, class Back>
+void Optimizer::inertial_optimization_on_map(MapT* pMap, int mode, Fill fill, Back back) {
+  const long unsigned int maxKFid = pMap->GetMaxKFid();
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  if (vpKFs.empty()) return;
+  using KF = typename std::remove_pointer<typename std::decay<decltype(vpKFs[0])>::type>::type;
+  using Bias = typename std::decay<decltype(vpKFs[0]->GetImuBias())>::type;
+  std::vector<KF*> kept;
+  std::map<KF*, int> index;
+  for (KF* k : vpKFs)
+    if (k->mnId <= maxKFid) { index[k] = (int)kept.size(); kept.push_back(k); }
+  const int n = (int)kept.size();
+  std::vector<int> pred(n, -1), succ(n, -1);
+  for (int i = 0; i < n; ++i) {
+    KF* k = kept[i];
+    if (!k->mPrevKF) continue;
+    if (k->isBad() || k->mPrevKF->mnId > maxKFid) continue;
+    if (!k->mpImuPreintegrated) continue;                                            // ("Not preintegrated measurement", :3079-3080)
+    if (mode != 2) k->mpImuPreintegrated->SetNewBias(k->mPrevKF->GetImuBias());       // :3082, :3263
+    const auto a = index.find(k->mPrevKF);
+    if (a == index.end() || succ[a->second] >= 0) continue;                           // (a vertex is missing; mPrevKF chains do not branch)
+    pred[i] = a->second; succ[a->second] = i;
+  }
+  std::vector<KF*> order;
+  std::vector<uint8_t> hasLink;
+  for (int i = 0; i < n; ++i) {
+    if (pred[i] >= 0) continue;
+    for (int j = i; j >= 0; j = succ[j]) { order.push_back(kept[j]); hasLink.push_back(j == i ? 0 : 1); }
+  }
+  std::vector<float> kfState((size_t)21 * n);
+  std::vector<morb_imu_preintegrated> pre(n);
+  for (int i = 0; i < n; ++i) {
+    morb_glue::imu_state21(order[i], &kfState[(size_t)21 * i]);
+    morb_glue::bias6(order[i]->GetImuBias(), &kfState[(size_t)21 * i + 15]);
+    if (hasLink[i]) morb_glue::fill_pre(pre[i], order[i]->mpImuPreintegrated);
+  }
+  InertialOptimizationView v;
+  v.nKF = n; v.kfState = kfState.data(); v.hasLink = hasLink.data(); v.pre = pre.data();
+  { float b6[6]; morb_glue::bias6(vpKFs.front()->GetImuBias(), b6); for (int k = 0; k < 6; ++k) v.global16[10 + k] = b6[k]; }   // VertexGyroBias / VertexAccBias(vpKFs.front())
+  fill(v);
+  InertialOptimization(v, mode);
+  if (!v.ok) return;
+  back(v);
+  if (mode == 2) return;
+  for (int i = 0; i < n; ++i) {
+    KF* k = order[i];
+    const float* s = &kfState[(size_t)21 * i];
+    typename std::decay<decltype(k->GetVelocity())>::type vel;
+    for (int c = 0; c < 3; ++c) vel(c) = s[12 + c];
+    k->SetVelocity(vel);
+    k->SetNewBias(Bias(s[18], s[19], s[20], s[15], s[16], s[17]));
+    if (v.reintegrate[i] && k->mpImuPreintegrated) k->mpImuPreintegrated->Reintegrate();
+  }
+}
+
+// void Optimizer::InertialOptimization(Map* pMap, Eigen::Matrix3d& Rwg, double& scale, Eigen::Vector3d& bg, Eigen::Vector3d& ba, bool bMono,
+//                                      Eigen::MatrixXd& covInertial, bool bFixedVel, bool bGauss, float priorG, float priorA)  Optimizer.cc:2979-3156
+// (covInertial and bGauss are unused there and here)
+template <class MapT, class Mat3d, class Vec3d, class MatXd>
+void Optimizer::InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale, Vec3d& bg, Vec3d& ba, bool bMono, MatXd& /*covInertial*/, bool bFixedVel,
+                                     bool /*bGauss*/, float priorG, float priorA) {
+  inertial_optimization_on_map(
+      pMap, 0,
+      [&](InertialOptimizationView& v) {
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) v.global16[3 * r + c] = Rwg(r, c);
+        v.global16[9] = scale; v.bMono = bMono; v.bFixedVel = bFixedVel; v.priorG = priorG; v.priorA = priorA;
+      },
+      [&](const InertialOptimizationView& v) {
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rwg(r, c) = v.global16[3 * r + c];
+        scale = v.global16[9];
+        for (int k = 0; k < 3; ++k) { bg(k) = v.global16[10 + k]; ba(k) = v.global16[13 + k]; }
+      });
+}
+// void Optimizer::InertialOptimization(Map* pMap, Eigen::Vector3d& bg, Eigen::Vector3d& ba, float priorG, float priorA)  Optimizer.cc:3158-3314
+template <class MapT, class Vec3d>
+void Optimizer::InertialOptimization(MapT* pMap, Vec3d& bg, Vec3d& ba, float priorG, float priorA) {
+  inertial_optimization_on_map(
+      pMap, 1, [&](InertialOptimizationView& v) { v.priorG = priorG; v.priorA = priorA; },
+      [&](const InertialOptimizationView& v) { for (int k = 0; k < 3; ++k) { bg(k) = v.global16[10 + k]; ba(k) = v.global16[13 + k]; } });
+}
+// void Optimizer::InertialOptimization(Map* pMap, Eigen::Matrix3d& Rwg, double& scale)  Optimizer.cc:3316-3428
+template <class MapT, class Mat3d>
+void Optimizer::InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale) {
+  inertial_optimization_on_map(
+      pMap, 2,
+      [&](InertialOptimizationView& v) {
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) v.global16[3 * r + c] = Rwg(r, c);
+        v.global16[9] = scale;
+      },
+      [&](const InertialOptimizationView& v) {
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rwg(r, c) = v.global16[3 * r + c];
+        scale = v.global16[9];
+      });
+}
+
 template <class SE3>
 SE3 Optimizer::se3_from_matrix(const double R[9], const double t[3]) {
   typename std::decay<decltype(std::declval<SE3>().rotationMatrix())>::type Rm;

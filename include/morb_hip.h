@@ -918,6 +918,29 @@ int morb_local_inertial_ba_fisheye(morb_optimizer*, int nKF, float* kfState21, c
                                    const uint8_t* iRobust, const float* iInfoScale, const float* rig28, const float* Tbc12, int bLarge,
                                    uint8_t* eraseFlag, int* stats3);
 
+/* void static Optimizer::InertialOptimization in its three overloads (Optimizer.h:103-112), the steps behind LocalMapping::InitializeIMU /
+ * ScaleRefinement (LocalMapping.cc:1205, :1391) and the bias re-estimation after a map merge (LoopClosing.cc:1902), for nprob problems at
+ * once (DEVICE pointers).  Problem p owns the keyframes [d_kfStart[p], d_kfStart[p+1]) in temporal order; cap (HOST) bounds the keyframes of
+ * any one problem (workspace and LDS / global tier; above 4096: MORB_ERR_CAPACITY before any launch).  d_kfState21[k] = Rwb (9, row-major),
+ * twb, velocity, gyro bias, acc bias; poses are read only.  d_hasLink[k] != 0: keyframe k carries an EdgeInertialGS (G2oTypes.cc:587-727)
+ * to keyframe k - 1 of its problem with d_pre[k] = its mpImuPreintegrated (the conditions of Optimizer.cc:3077-3078); a problem's first
+ * keyframe never has one, a zero in the middle is a broken chain (isBad() or no mPrevKF).  mode (HOST): 0 = InertialOptimization(pMap, Rwg,
+ * scale, bg, ba, bMono, covInertial, bFixedVel, bGauss, priorG, priorA) (Optimizer.cc:2979-3156), 1 = (pMap, bg, ba, priorG, priorA)
+ * (:3158-3314), 2 = (pMap, Rwg, scale) (:3316-3428).  d_flags[p]: bit 0 bMono, bit 1 bFixedVel (mode 0 only); d_prior2[p] = {priorG, priorA}.
+ * d_global16[p] (FP64, in / out) = Rwg (9, row-major), scale, bg (3), ba (3): on entry bg / ba are the initial estimate of the bias vertices
+ * (vpKFs.front()'s bias in every mode; in mode 2 the fixed bias of every link).  Modes 0 and 1 write every keyframe's velocity
+ * (Vw.cast<float>()) and bias fields (SetNewBias(b)), d_reintegrate[k] = 1 where the reference calls Reintegrate() (float norm of the old gyro
+ * bias minus bg.cast<float>() above 0.01, on a keyframe with a link), bg, ba and, in mode 0, Rwg and scale; mode 1 works with Rwg = I and
+ * scale = 1 whatever the array holds and leaves those ten values untouched; mode 2 writes Rwg and scale only.  d_stats4[p] = {outer
+ * iterations, LM trials (0 for Gauss-Newton), ok, links}; d_chi2[p] = activeRobustChi2 before and after.  A problem with fewer than two
+ * keyframes or without a link: ok = 0, nothing else written.  g2o Levenberg-Marquardt (200 iterations, lambda 1e3 when priorG != 0 in mode 0
+ * and always in mode 1) or, mode 2, Gauss-Newton (10 iterations, Huber delta 1 on every link) in one launch, one workgroup per problem
+ * ("InertialOptimization"). */
+int morb_inertial_optimization_batch(morb_optimizer*, int nprob, int cap, const int* d_kfStart, float* d_kfState21,
+                                     const uint8_t* d_hasLink, const morb_imu_preintegrated* d_pre, int mode,
+                                     const int* d_flags, const float* d_prior2, double* d_global16,
+                                     uint8_t* d_reintegrate, int* d_stats4, double* d_chi2, void* stream);
+
 /* static void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF,
  * int& num_OptKF, int& num_MPs, int& num_edges)  Optimizer.h:67-69, Optimizer.cc:1053-1441, on the graph the
  * reference assembles at :1058-1351, flattened (HOST pointers): nKF keyframes (local ones first or in any

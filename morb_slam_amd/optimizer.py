@@ -1,6 +1,6 @@
 """Optimizer — host-side mirror of the reference's static Optimizer functions on the hot path
 (include/Optimizer.h:46-139): PoseOptimization, LocalBundleAdjustment and the inertial functions of SURVEY 8(f) N1
-(IMU preintegration, PoseInertialOptimizationLastKeyFrame / LastFrame, LocalInertialBA), over the device-resident kernels."""
+(IMU preintegration, PoseInertialOptimizationLastKeyFrame / LastFrame, LocalInertialBA, InertialOptimization), over the device-resident kernels."""
 import ctypes as C
 
 import numpy as np
@@ -184,6 +184,31 @@ class Optimizer:
                     hypScores=hyp)
 
     # ---- visual-inertial tracking and mapping ---------------------------------------------------
+    def InertialOptimization(self, kfStart, kfState, hasLink, pre, mode, flags=None, prior2=None, global16=None, cap=None, out=None,
+                             stream=None):
+        """Batched Optimizer::InertialOptimization (morb_inertial_optimization_batch).  Device tensors, P problems: kfStart i32 [P + 1]
+        (problem p owns the keyframe rows [kfStart[p], kfStart[p + 1]) in temporal order), kfState f32 [K, 21] (Rwb, twb, velocity, gyro
+        bias, acc bias; in / out), hasLink u8 [K], pre f32 [K, 310] (morb_imu_preintegrated records; row k = the link k - 1 -> k), flags
+        i32 [P] (bit 0 bMono, bit 1 bFixedVel; mode 0), prior2 f32 [P, 2] (priorG, priorA; modes 0 and 1), global16 f64 [P, 16] (Rwg,
+        scale, bg, ba; in / out).  mode: 0 = (Rwg, scale, bg, ba, bMono, ..., priorG, priorA), 1 = (bg, ba, priorG, priorA), 2 = (Rwg,
+        scale).  cap = an upper bound of the keyframes of one problem (default: read back from kfStart, which waits for the device).
+        Returns (reintegrate u8 [K], stats i32 [P, 4] = outer iterations, LM trials, ok, links; chi2 f64 [P, 2] = before, after); kfState
+        and global16 are updated in place."""
+        import torch
+        P = kfStart.shape[0] - 1
+        K = kfState.shape[0]
+        if cap is None:
+            ks = kfStart.cpu().numpy()
+            cap = max(1, int((ks[1:] - ks[:-1]).max()))
+        if out is None:
+            out = (torch.zeros((K,), dtype=torch.uint8, device=kfState.device),
+                   torch.zeros((P, 4), dtype=torch.int32, device=kfState.device),
+                   torch.zeros((P, 2), dtype=torch.float64, device=kfState.device))
+        st = stream_arg(stream)
+        check(self._L.morb_inertial_optimization_batch(self._h, P, int(cap), ptr(kfStart), ptr(kfState), ptr(hasLink), ptr(pre), int(mode),
+                                                       ptr(flags), ptr(prior2), ptr(global16), ptr(out[0]), ptr(out[1]), ptr(out[2]), st))
+        return out
+
     def PreintegrateIMU(self, start, acc, gyro, dt, bias, nga, walk, out=None, stream=None):
         """IMU::Preintegrated::Initialize + IntegrateNewMeasurement for many measurement sequences at once.
         Device tensors: start i32 [S+1] (sequence s owns measurements start[s]:start[s+1]), acc / gyro f32 [M, 3],

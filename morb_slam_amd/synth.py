@@ -521,6 +521,105 @@ def make_inertial_ba_problem(n_opt=10, n_fixed_vis=6, n_points=1500, n_imu=40, s
                 eRight=np.array(eRight, np.uint8), rig28=tumvi_rig28() if rig else None)
 
 
+# ---- Optimizer::InertialOptimization (IMU initialisation: velocities, biases, gravity direction, scale) ----------------------
+def make_inertial_optimization_problem(n_kf=20, seed=0, mono=True, s_true=1.0, n_imu=40, imu_freq=IMU_FREQ, noise=True, fixed_vel=False,
+                                       prior_g=1e2, prior_a=1e10, broken=(), outlier_links=(), gyro_bias_offset=None, bias_sigma=(0.01, 0.05),
+                                       rwg_deg=25.0):
+    """One InertialOptimization input: n_kf keyframes, n_imu IMU samples apart, on a smooth trajectory with acceleration and rotation
+    excitation (sinusoidal position, integrated sinusoidal body rate).  The IMU samples (imu_freq, known biases, noise from IMU_NOISE when
+    `noise`) were integrated with the bias `bias` (zero, as LocalMapping::InitializeIMU has it); the world frame is rotated off gravity by a
+    random Rwg_true of about rwg_deg degrees; positions (and so velocities) are divided by s_true, the monocular map's unknown scale.
+    Initial velocities by finite differences and the initial Rwg from the summed delta-velocities, as LocalMapping.cc:1165-1193 prepares
+    them.  broken: keyframes whose link to their predecessor is missing; outlier_links: keyframes whose link's samples are grossly wrong;
+    gyro_bias_offset: the norm (rad/s) of the true gyro bias instead of a random one.
+    Keys: kfState [n, 21] f32 (Rwb, twb, velocity, gyro bias, acc bias), hasLink [n] u8, imuStart [n + 1] i32 with acc / gyro / dt (keyframe k
+    owns the samples since keyframe k - 1; keyframe 0 owns one unused sample), bias [6] f32 (IMU::Bias order: acc, gyro), flags (bit 0 bMono,
+    bit 1 bFixedVel), prior2 f32 [2], global16 f64 [16] (Rwg, scale, bg, ba), and the truth: Rwg_true, s_true, bg_true, ba_true, v_true."""
+    rng = np.random.default_rng([0x10A7, seed, n_kf])
+    dt = 1.0 / imu_freq
+    G = 9.81
+    Rwg_true = _rot_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(rwg_deg))
+    g_w = Rwg_true @ np.array([0, 0, -G])
+    bg_t = rng.normal(0, bias_sigma[0], 3); ba_t = rng.normal(0, bias_sigma[1], 3)
+    if gyro_bias_offset is not None:
+        d = rng.normal(0, 1, 3)
+        bg_t = d / np.linalg.norm(d) * gyro_bias_offset
+    amp = rng.uniform(0.3, 0.8, 3); om = rng.uniform(1.5, 3.5, 3); ph = rng.uniform(0, 2 * np.pi, 3)
+    wamp = rng.uniform(0.2, 0.6, 3); wom = rng.uniform(1.0, 3.0, 3); wph = rng.uniform(0, 2 * np.pi, 3)
+    pos = lambda t: amp * np.sin(om * t + ph)
+    vel = lambda t: amp * om * np.cos(om * t + ph)
+    accw = lambda t: -amp * om * om * np.sin(om * t + ph)
+    wb = lambda t: wamp * np.sin(wom * t + wph)
+    ng, na = (noise_v * np.sqrt(imu_freq) for noise_v in (IMU_NOISE["ng"], IMU_NOISE["na"]))
+    R = _rot_from_rotvec(rng.normal(0, 0.3, 3))
+    Rs, ps, vs = [R], [pos(0.0)], [vel(0.0)]
+    acc, gyro, dts, start = [np.zeros(3)], [np.zeros(3)], [dt], [0, 1]
+    for k in range(1, n_kf):
+        for i in range(n_imu):
+            tm = ((k - 1) * n_imu + i + 0.5) * dt
+            w = wb(tm)
+            Rm = R @ _rot_from_rotvec(w * dt / 2)
+            a = Rm.T @ (accw(tm) - g_w) + ba_t
+            gy = w + bg_t
+            if noise:
+                a = a + rng.normal(0, na, 3); gy = gy + rng.normal(0, ng, 3)
+            if k in outlier_links:
+                a = a + np.array([3.0, -2.0, 2.5])
+            acc.append(a); gyro.append(gy); dts.append(dt)
+            R = R @ _rot_from_rotvec(w * dt)
+        tk = k * n_imu * dt
+        Rs.append(R); ps.append(pos(tk)); vs.append(vel(tk))
+        start.append(len(dts))
+    P = np.array(ps) / s_true
+    V = np.zeros((n_kf, 3))
+    has = np.ones(n_kf, np.uint8); has[0] = 0
+    for k in broken:
+        has[k] = 0
+    acc, gyro, dts = np.array(acc, np.float32), np.array(gyro, np.float32), np.array(dts, np.float32)
+    # LocalMapping.cc:1165-1193: dirG -= Rwb(prev) * dV, velocities by finite differences; dV of the zero-bias integration
+    dirG = np.zeros(3)
+    for k in range(1, n_kf):
+        if not has[k]:
+            continue
+        dR, dV = np.eye(3), np.zeros(3)
+        for i in range(start[k], start[k + 1]):
+            dV = dV + dR @ acc[i].astype(np.float64) * dts[i]
+            dR = dR @ _rot_from_rotvec(gyro[i].astype(np.float64) * dts[i])
+        dirG -= Rs[k - 1] @ dV
+        T = float(dts[start[k]:start[k + 1]].sum())
+        V[k] = (P[k] - P[k - 1]) / T
+        V[k - 1] = V[k]
+    dirG = dirG / np.linalg.norm(dirG)
+    gI = np.array([0, 0, -1.0])
+    vx = np.cross(gI, dirG)
+    Rwg0 = _rot_from_rotvec(vx * np.arccos(np.clip(gI @ dirG, -1, 1)) / max(np.linalg.norm(vx), 1e-12))
+    st = np.zeros((n_kf, 21), np.float32)
+    for k in range(n_kf):
+        st[k, :9] = Rs[k].ravel(); st[k, 9:12] = P[k]; st[k, 12:15] = V[k]
+    g16 = np.concatenate([Rwg0.ravel(), [1.0], np.zeros(3), np.zeros(3)])
+    return dict(kfState=st, hasLink=has, imuStart=np.array(start, np.int32), acc=acc, gyro=gyro, dt=dts, bias=np.zeros(6, np.float32),
+                flags=(1 if mono else 0) | (2 if fixed_vel else 0), prior2=np.array([prior_g, prior_a], np.float32), global16=g16,
+                Rwg_true=Rwg_true, s_true=float(s_true), bg_true=bg_t, ba_true=ba_t, v_true=np.array(vs) / s_true)
+
+
+def pack_inertial_optimization_problems(probs, pres, device, pad_rows=0):
+    """Problems of make_inertial_optimization_problem with their preintegrations (pres[p]: [n_p, 310] f32, or one device tensor of all rows)
+    as the device tensors of Optimizer.InertialOptimization: (kfStart, kfState, hasLink, pre, flags, prior2, global16); pad_rows extra
+    keyframe rows (filled with a pattern) follow the last problem."""
+    import torch
+    ns = [p["kfState"].shape[0] for p in probs]
+    start = np.cumsum([0] + ns).astype(np.int32)
+    st = np.concatenate([p["kfState"] for p in probs] + [np.full((pad_rows, 21), 7.25, np.float32)])
+    hl = np.concatenate([p["hasLink"] for p in probs] + [np.ones(pad_rows, np.uint8)])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    if isinstance(pres, (list, tuple)):
+        pre = t(np.concatenate(list(pres) + [np.zeros((pad_rows, pres[0].shape[1]), np.float32)]).astype(np.float32))
+    else:
+        pre = pres
+    return (t(start), t(st), t(hl), pre, t(np.array([p["flags"] for p in probs], np.int32)),
+            t(np.stack([p["prior2"] for p in probs]).astype(np.float32)), t(np.stack([p["global16"] for p in probs]).astype(np.float64)))
+
+
 # ---- Optimizer::OptimizeSim3 (two keyframes of one scene under a known Sim3) -----------------------------------
 SIM3_PINHOLE9 = np.array([0, EUROC_CAM["fx"], EUROC_CAM["fy"], EUROC_CAM["cx"], EUROC_CAM["cy"], 0, 0, 0, 0], np.float32)
 
