@@ -2,6 +2,7 @@
 // hot path, PoseOptimization and LocalBundleAdjustment.  As in ORBmatcher.h the arguments are plain views of what the reference
 // methods read from Frame / KeyFrame / MapPoint / Map and write back to them; INTEGRATION.md shows the glue inside the reference tree.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <mutex>
@@ -124,6 +125,32 @@ struct OptimizeSim3View {
   double S12[8] = {0, 0, 0, 1, 0, 0, 0, 1};   // in / out (written only when the function reaches its end)
   std::vector<uint8_t> keep;                 // out: vpMatches1[i] != NULL on return
   int stats[8] = {0};                        // out: as morb_optimize_sim3_batch's d_stats (stats[4] = reached the end)
+};
+
+// What Tracking::CreateInitialMapMonocular hands its numeric part (Tracking.cc:2345-2430) and gets back, flattened as
+// morb_create_initial_map_monocular_batch takes one problem: the two frames' mvKeysUn, vnMatches12 and TwoViewReconstruction's T21, vP3D,
+// vbTriangulated; mvLevelSigma2 / mvScaleFactors and the camera; out: keyframe 2's pose and, by frame-1 keypoint, the map points' fields.
+struct InitialMapView {
+  int n1 = 0, n2 = 0;
+  const morb_keypoint *keysUn1 = nullptr, *keysUn2 = nullptr;   // [n1], [n2]
+  const int* matches12 = nullptr;                               // [n1]: frame-2 keypoint or negative
+  const uint8_t* triangulated = nullptr;                        // [n1]
+  const float* P3D = nullptr;                                   // [n1][3]
+  float T21[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};         // in: R row-major, then t
+  int nlevels = 0;
+  float scaleFactors[16] = {0}, levelSigma2[16] = {0};
+  float cam8[8] = {0};                                          // fx fy cx cy, then k0..k3 when kb8
+  bool kb8 = false;
+  float depthScale = 1.f;                                       // 1; 4 for IMU-monocular; 0 = no scaling (what BundleAdjustment itself leaves)
+  int minTracked = 50;
+  int status = 0;                                               // out: 1 = ok, else the reset reasons as bits (2 negative median, 4 too few points)
+  float Tcw2[12] = {0};
+  std::vector<float> mpPos, mpNormal, mpDist;                   // [n1][3], [n1][3], [n1][2] (mfMaxDistance, mfMinDistance)
+  std::vector<uint8_t> hasMP;                                   // [n1]
+  int nPoints = 0, outerIterations = 0, lmTrials = 0;
+  bool stopSeen = false;
+  double chi2[2] = {0, 0};
+  float medianDepth = 0.f;
 };
 
 class Optimizer {
@@ -270,6 +297,58 @@ class Optimizer {
     return c.fetch(d_nIn, 1)[0];
   }
 
+  // void static BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)  Optimizer.h:46-50 on the map of a monocular
+  // initialisation: two keyframes, the first fixed, every point seen by both.  One problem through morb_create_initial_map_monocular_batch with
+  // the view's depthScale and minTracked (0 = the bare bundle adjustment), on the tracking handle: Tracking::CreateInitialMapMonocular calls it.
+  static void BundleAdjustment(InitialMapView& v, int nIterations, bool bRobust, int device = 0, const bool* pbStopFlag = nullptr) {
+    const int n1 = v.n1 > 0 ? v.n1 : 0, n2 = v.n2 > 0 ? v.n2 : 0, cap = std::max(std::max(n1, n2), 1);
+    v.mpPos.assign((size_t)n1 * 3, 0.f); v.mpNormal.assign((size_t)n1 * 3, 0.f); v.mpDist.assign((size_t)n1 * 2, 0.f); v.hasMP.assign(n1, 0);
+    morb_frame_params P = {};
+    P.fx = v.cam8[0]; P.fy = v.cam8[1]; P.cx = v.cam8[2]; P.cy = v.cam8[3];
+    P.nlevels = v.nlevels;
+    for (int k = 0; k < 16; ++k) { P.scaleFactors[k] = v.scaleFactors[k]; P.levelSigma2[k] = v.levelSigma2[k]; }
+    std::vector<morb_keypoint> pool((size_t)2 * cap);
+    for (int i = 0; i < n1; ++i) pool[i] = v.keysUn1[i];
+    for (int i = 0; i < n2; ++i) pool[(size_t)cap + i] = v.keysUn2[i];
+    std::vector<int> m12(cap, -1);
+    std::vector<uint8_t> tri(cap, 0);
+    std::vector<float> p3d((size_t)cap * 3, 0.f);
+    for (int i = 0; i < n1; ++i) { m12[i] = v.matches12[i]; tri[i] = v.triangulated[i]; for (int k = 0; k < 3; ++k) p3d[3 * (size_t)i + k] = v.P3D[3 * (size_t)i + k]; }
+    const int img[2] = {0, 1}, count[2] = {n1, n2}, ok = 1;
+    const unsigned char stop = pbStopFlag && *pbStopFlag ? 1 : 0;   // (sampled at the call: the device reads its copy)
+    Slot& o = slot(device, kTracking);
+    std::lock_guard<std::mutex> lock(o.mu);
+    Call c(device, morb_optimizer_stream(o.h));
+    const int *d_img = c.in(img, 2), *d_count = c.in(count, 2), *d_m12 = c.in(m12.data(), cap), *d_ok = c.in(&ok, 1);
+    const morb_keypoint* d_kps = c.in(pool.data(), pool.size());
+    const float *d_T21 = c.in(v.T21, 12), *d_P3D = c.in(p3d.data(), p3d.size());
+    const uint8_t* d_tri = c.in(tri.data(), cap);
+    const unsigned char* d_stop = pbStopFlag ? c.in(&stop, 1) : nullptr;
+    int *d_status = c.out<int>(1), *d_stats = c.out<int>(4);
+    float *d_Tcw2 = c.out<float>(12), *d_pos = c.out<float>((size_t)cap * 3), *d_nrm = c.out<float>((size_t)cap * 3), *d_dist = c.out<float>((size_t)cap * 2),
+          *d_median = c.out<float>(1);
+    uint8_t* d_has = c.out<uint8_t>(cap);
+    double* d_chi2 = c.out<double>(2);
+    check(morb_create_initial_map_monocular_batch(o.h, &P, v.cam8, v.kb8 ? 1 : 0, 1, cap, d_img, d_img + 1, d_count, d_kps, d_m12, d_ok, d_T21, d_P3D, d_tri,
+                                                  nIterations, bRobust ? 1 : 0, v.depthScale, v.minTracked, d_stop, d_status, d_Tcw2, d_pos, d_nrm, d_dist,
+                                                  d_has, d_stats, d_chi2, d_median, nullptr));
+    c.wait();
+    v.status = c.fetch(d_status, 1)[0];
+    const std::vector<int> st = c.fetch(d_stats, 4);
+    v.nPoints = st[0]; v.outerIterations = st[1]; v.lmTrials = st[2]; v.stopSeen = st[3] != 0;
+    c.fetch(d_Tcw2, v.Tcw2, 12); c.fetch(d_chi2, v.chi2, 2); c.fetch(d_median, &v.medianDepth, 1);
+    if (n1 > 0) { c.fetch(d_pos, v.mpPos.data(), (size_t)n1 * 3); c.fetch(d_nrm, v.mpNormal.data(), (size_t)n1 * 3); c.fetch(d_dist, v.mpDist.data(), (size_t)n1 * 2);
+                  c.fetch(d_has, v.hasMP.data(), n1); }
+  }
+  // The numeric part of void Tracking::CreateInitialMapMonocular() (Tracking.cc:2394-2429) in one call: GlobalBundleAdjustemnt(map, 20), the median
+  // depth, the reset test, the rescaling and UpdateNormalAndDepth.  Returns false for "Wrong initialization, reseting..." (v.status says why).
+  static bool CreateInitialMapMonocular(InitialMapView& v, bool bImuMonocular = false, int device = 0) {
+    v.depthScale = bImuMonocular ? 4.f : 1.f;
+    v.minTracked = 50;
+    BundleAdjustment(v, 20, true, device);
+    return v.status == 1;
+  }
+
   // ---- the reference's own signatures (include/Optimizer.h:67-101) as static member templates: the call sites of src/Tracking.cc and
   // src/LocalMapping.cc compile unchanged (definitions: Optimizer_reference.h, included below) ----
   template <class FrameT> static int PoseOptimization(FrameT* pFrame);
@@ -283,6 +362,13 @@ class Optimizer {
   template <class KF, class MP, class Sim3T, class Mat77>
   static int OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale, Mat77& mAcumHessian,
                           const bool bAllPoints = false);
+
+  // (include/Optimizer.h:46-53; call site Tracking.cc:2398) on the map of a monocular initialisation; any other map shape throws
+  template <class MapT>
+  static void GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
+  template <class KF, class MP>
+  static void BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations = 5, bool* pbStopFlag = NULL,
+                               const unsigned long nLoopKF = 0, const bool bRobust = true);
 
   // (include/Optimizer.h:103-112; call sites LocalMapping.cc:1205, :1391 and LoopClosing.cc:1902)
   template <class MapT, class Mat3d, class Vec3d, class MatXd>

@@ -666,6 +666,101 @@ void Optimizer::InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale) {
       });
 }
 
+// void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust)  Optimizer.cc:47-54
+template <class MapT>
+void Optimizer::GlobalBundleAdjustemnt(MapT* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMP = pMap->GetAllMapPoints();
+  BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust);
+}
+// void Optimizer::BundleAdjustment(const vector<KeyFrame*>& vpKFs, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag, const unsigned long
+//                                  nLoopKF, const bool bRobust)  Optimizer.cc:56-362, for the one map shape that is built: the map Tracking::
+// CreateInitialMapMonocular has just made — two keyframes, the one with GetInitKFid() fixed (at the identity), every point observed by both
+// through mono edges.  Flattened into an InitialMapView and solved with the scaling switched off (depthScale 0, minTracked 0); written back as
+// :276-361 does for both nLoopKF cases (the `dist > 1` block of :297-340 only counts and is left out).  Any other map throws std::runtime_error:
+// GlobalBundleAdjustemnt over a whole map after a loop closure is not built.
+template <class KF, class MP>
+void Optimizer::BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
+                                 const bool bRobust) {
+  const char* what = "Optimizer::BundleAdjustment: only the map of a monocular initialisation is built (two keyframes, the initial one fixed at the identity, "
+                     "every point seen by both through monocular observations); ";
+  std::vector<KF*> kfs;
+  for (KF* k : vpKFs) if (!k->isBad()) kfs.push_back(k);
+  if (kfs.size() != 2) throw std::runtime_error(std::string(what) + "this map has " + std::to_string(kfs.size()) + " keyframes");
+  auto* pMap = vpKFs[0]->GetMap();
+  const unsigned long initId = pMap->GetInitKFid();
+  if ((kfs[0]->mnId == initId) == (kfs[1]->mnId == initId)) throw std::runtime_error(std::string(what) + "exactly one keyframe must be the initial one");
+  KF* k1 = kfs[0]->mnId == initId ? kfs[0] : kfs[1];
+  KF* k2 = kfs[0]->mnId == initId ? kfs[1] : kfs[0];
+  if (k1->mpCamera2 || k2->mpCamera2) throw std::runtime_error(std::string(what) + "a keyframe has a second camera");
+  {
+    const auto T1 = k1->GetPose();
+    const auto R1 = T1.rotationMatrix();
+    const auto t1 = T1.translation();
+    for (int r = 0; r < 3; ++r) {
+      if (t1(r) != 0.f) throw std::runtime_error(std::string(what) + "the fixed keyframe is not at the origin");
+      for (int c = 0; c < 3; ++c) if (R1(r, c) != (r == c ? 1.f : 0.f)) throw std::runtime_error(std::string(what) + "the fixed keyframe is rotated");
+    }
+  }
+  InitialMapView v;
+  const int n1 = (int)k1->mvKeysUn.size(), n2 = (int)k2->mvKeysUn.size();
+  std::vector<morb_keypoint> keys1(n1), keys2(n2);
+  auto conv = [](const auto& kp, morb_keypoint& o) { o.x = kp.pt.x; o.y = kp.pt.y; o.size = kp.size; o.angle = kp.angle; o.response = kp.response; o.octave = kp.octave; o.class_id = kp.class_id; };
+  for (int i = 0; i < n1; ++i) conv(k1->mvKeysUn[i], keys1[i]);
+  for (int i = 0; i < n2; ++i) conv(k2->mvKeysUn[i], keys2[i]);
+  std::vector<int> m12(n1, -1);
+  std::vector<uint8_t> tri(n1, 0);
+  std::vector<float> p3d((size_t)n1 * 3, 0.f);
+  std::vector<MP*> owner(n1, nullptr);
+  for (MP* pMP : vpMP) {
+    if (pMP->isBad()) continue;
+    const auto obs = pMP->GetObservations();
+    int i1 = -1, i2 = -1, others = 0;
+    for (const auto& ob : obs) {
+      const int left = std::get<0>(ob.second);
+      if (ob.first == k1) i1 = left; else if (ob.first == k2) i2 = left; else if (!ob.first->isBad()) ++others;
+    }
+    if (others || i1 < 0 || i2 < 0 || i1 >= n1 || i2 >= n2) throw std::runtime_error(std::string(what) + "a point is not observed by exactly the two keyframes");
+    if (!(k1->mvuRight[i1] < 0) || !(k2->mvuRight[i2] < 0)) throw std::runtime_error(std::string(what) + "a point has a stereo observation");
+    if (owner[i1]) throw std::runtime_error(std::string(what) + "two points share a keypoint");
+    owner[i1] = pMP; m12[i1] = i2; tri[i1] = 1;
+    const auto X = pMP->GetWorldPos();
+    for (int k = 0; k < 3; ++k) p3d[3 * (size_t)i1 + k] = X(k);
+  }
+  v.n1 = n1; v.n2 = n2; v.keysUn1 = keys1.data(); v.keysUn2 = keys2.data(); v.matches12 = m12.data(); v.triangulated = tri.data(); v.P3D = p3d.data();
+  {
+    const auto T2 = k2->GetPose();
+    const auto R2 = T2.rotationMatrix();
+    const auto t2 = T2.translation();
+    for (int r = 0; r < 3; ++r) { v.T21[9 + r] = t2(r); for (int c = 0; c < 3; ++c) v.T21[3 * r + c] = R2(r, c); }
+  }
+  v.nlevels = k2->mnScaleLevels;
+  for (int l = 0; l < 16 && l < (int)k2->mvScaleFactors.size(); ++l) { v.scaleFactors[l] = k2->mvScaleFactors[l]; v.levelSigma2[l] = k2->mvLevelSigma2[l]; }
+  const int np = (int)k2->mpCamera->size();
+  v.kb8 = np == 8;
+  for (int k = 0; k < np && k < 8; ++k) v.cam8[k] = k2->mpCamera->getParameter(k);
+  v.depthScale = 0.f; v.minTracked = 0;
+  BundleAdjustment(v, nIterations, bRobust, 0, pbStopFlag);
+  using SE3 = typename std::decay<decltype(k2->GetPose())>::type;
+  double R[9], t[3];
+  for (int k = 0; k < 9; ++k) R[k] = v.Tcw2[k];
+  for (int k = 0; k < 3; ++k) t[k] = v.Tcw2[9 + k];
+  const bool own = nLoopKF == pMap->GetOriginKF()->mnId;
+  if (own) k2->SetPose(se3_from_matrix<SE3>(R, t));                                    // :285-287 (the fixed keyframe keeps the pose it has)
+  else {
+    k1->mTcwGBA = k1->GetPose(); k1->mnBAGlobalForKF = nLoopKF;                         // :289-291
+    k2->mTcwGBA = se3_from_matrix<SE3>(R, t); k2->mnBAGlobalForKF = nLoopKF;
+  }
+  for (int i = 0; i < n1; ++i) {                                                        // :345-361
+    MP* pMP = owner[i];
+    if (!pMP) continue;
+    typename std::decay<decltype(pMP->GetWorldPos())>::type X;
+    for (int k = 0; k < 3; ++k) X(k) = v.mpPos[3 * (size_t)i + k];
+    if (own) { pMP->SetWorldPos(X); pMP->UpdateNormalAndDepth(); }
+    else { pMP->mPosGBA = X; pMP->mnBAGlobalForKF = nLoopKF; }
+  }
+}
+
 template <class SE3>
 SE3 Optimizer::se3_from_matrix(const double R[9], const double t[3]) {
   typename std::decay<decltype(std::declval<SE3>().rotationMatrix())>::type Rm;

@@ -826,6 +826,35 @@ int morb_two_view_reconstruction_batch(morb_optimizer*, int nprob, int cap, cons
                                        uint8_t* d_triangulated, int* d_stats, float* d_fstats, uint8_t* d_inliersH, uint8_t* d_inliersF,
                                        float* d_hypScores, void* stream);
 
+/* The numeric rest of void Tracking::CreateInitialMapMonocular(), src/Tracking.cc:2345-2430, behind the two entries above:
+ * Optimizer::GlobalBundleAdjustemnt(map, 20) -> BundleAdjustment over the two new keyframes and their points (src/Optimizer.cc:47-362),
+ * KeyFrame::ComputeSceneMedianDepth(2) of the first keyframe (src/KeyFrame.cc:796-826), the reset test (:2407-2408), the rescaling of the
+ * baseline and of every point (:2416-2429) and MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:464-519).  nprob problems, one workgroup
+ * each, one launch, asynchronous on the stream, no host synchronisation.  Inputs as the two entries above leave them: the keypoint pool
+ * [nimg][cap] with its counts (mvKeysUn), d_matches12 [nprob][cap], d_ok [nprob], d_T21 [nprob][12] (R21 row-major, then t21), d_P3D
+ * [nprob][cap][3], d_triangulated [nprob][cap].  The map points of a problem are the frame-1 keypoints i with d_matches12[i] in
+ * [0, count of image 2) and d_triangulated[i] set (:2318-2323).  P (HOST) gives mvInvLevelSigma2 = 1 / levelSigma2[octave] and
+ * mvScaleFactors; cam8 (HOST, fx fy cx cy k0..k3; NULL = the pinhole camera of P) with kb8 != 0 for KannalaBrandt8 (cam8 required).
+ * Graph (:113-268): keyframe 1 fixed at the identity, keyframe 2 free from d_T21, two EdgeSE3ProjectXYZ per point on mvKeysUn[idx].pt,
+ * Huber delta (float) sqrt(5.99) when robust != 0.  g2o Levenberg-Marquardt over BlockSolver_6_3 in FP64, nIterations outer iterations (20
+ * at the call site), lambda from the largest diagonal entry of the pose and of every point.  d_stop (optional, NULL = none): [nprob]
+ * bytes in device memory, pbStopFlag per problem, read at entry and at every iteration and trial.  After the solve: median = the depth
+ * of rank (n - 1) / 2 in keyframe 1, in float; invMedianDepth = depthScale / median (depthScale 1; 4 for IMU-monocular; 0 = do not
+ * scale: the state BundleAdjustment itself leaves); reset when median < 0 or fewer than minTracked (50) points, nothing scaled then.
+ * Outputs: d_status [nprob] (0 = ok was 0 and nothing ran, 1 = ok, else the reset reasons as bits: 2 = negative median or no point,
+ * 4 = too few points); d_Tcw2 [nprob][12]; by frame-1 keypoint and zero elsewhere d_mpPos [nprob][cap][3], d_mpNormal [nprob][cap][3],
+ * d_mpDist [nprob][cap][2] (mfMaxDistance, mfMinDistance; observers keyframe 1 and 2, reference keyframe 2, level = the octave of its
+ * keypoint) and d_hasMP [nprob][cap]; d_stats [nprob][4] = points, outer iterations, LM trials, stop seen; d_chi2 [nprob][2] = first
+ * and last active chi2; d_median [nprob].  A problem whose ok is 0 gets zero rows.  MORB_ERR_INVALID before any launch for cap < 1,
+ * nIterations < 0, nprob < 0 or a NULL required pointer.  Points are bounded by cap alone: their records live in LDS up to cap 512, in
+ * a grow-only workspace of the handle beyond ("Initial map"). */
+int morb_create_initial_map_monocular_batch(morb_optimizer*, const morb_frame_params* P, const float* cam8, int kb8, int nprob, int cap,
+                                            const int* d_img1, const int* d_img2, const int* d_count, const morb_keypoint* d_kpsUn,
+                                            const int* d_matches12, const int* d_ok, const float* d_T21, const float* d_P3D,
+                                            const uint8_t* d_triangulated, int nIterations, int robust, float depthScale, int minTracked,
+                                            const unsigned char* d_stop, int* d_status, float* d_Tcw2, float* d_mpPos, float* d_mpNormal,
+                                            float* d_mpDist, uint8_t* d_hasMP, int* d_stats, double* d_chi2, float* d_median, void* stream);
+
 /* ---- visual-inertial tracking and mapping ----
  * IMU::Preintegrated as plain data (include/ImuTypes.h:154-263): 3 x 3 blocks row-major, C = the 15 x 15 covariance
  * row-major, b = the bias the measurements were integrated with in IMU::Bias order (bax bay baz bwx bwy bwz),

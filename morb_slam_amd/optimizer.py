@@ -22,6 +22,8 @@ TWO_VIEW_STATS = ("N", "MODEL", "BEST_IT_H", "BEST_IT_F", "NINLIERS", "NHYP", "C
 TWO_VIEW_FSTATS = ("SH", "SF", "RH") + tuple(f"H21_{k}" for k in range(9)) + tuple(f"F21_{k}" for k in range(9)) + \
     tuple(f"PARALLAX{k}" for k in range(8))
 TWO_VIEW_FAIL = ("NONE", "FEW_MATCHES", "ZERO_SCORE", "DEGENERATE_H", "AMBIGUOUS", "PARALLAX")
+# d_status of morb_create_initial_map_monocular_batch (InitialMapStatus of include/morb/initial_map_math.h): the reset reasons are bits
+INITIAL_MAP_STATUS = {"NOT_RUN": 0, "OK": 1, "RESET_MEDIAN": 2, "RESET_COUNT": 4}
 
 
 class Optimizer:
@@ -182,6 +184,37 @@ class Optimizer:
                                                          st))
         return dict(ok=out[0], T21=out[1], P3D=out[2], triangulated=out[3], stats=out[4], fstats=out[5], inliersH=inlH, inliersF=inlF,
                     hypScores=hyp)
+
+    def CreateInitialMapMonocular(self, params, img1, img2, count, kps, matches12, ok, T21, P3D, triangulated, nIterations=20, robust=True,
+                                  depthScale=1.0, minTracked=50, cam8=None, kb8=False, stop=None, out=None, stream=None):
+        """The numeric rest of Tracking::CreateInitialMapMonocular behind TwoViewReconstruction (morb_create_initial_map_monocular_batch):
+        GlobalBundleAdjustemnt over the two keyframes and their points, the median depth of keyframe 1, the reset test, the rescaling
+        and UpdateNormalAndDepth.  Device tensors, P problems over a keypoint pool: params = FrameParams (mvLevelSigma2, mvScaleFactors,
+        the pinhole camera), img1 / img2 i32 [P], count i32 [nimg], kps [nimg, cap] KP_DTYPE records (mvKeysUn), matches12 i32 [P, cap],
+        and what TwoViewReconstruction returned: ok i32 [P], T21 f32 [P, 12], P3D f32 [P, cap, 3], triangulated u8 [P, cap].  cam8 (host,
+        8 floats) replaces the camera of params; kb8 selects KannalaBrandt8.  stop u8 [P] on the device or None.  depthScale: 1, 4 for
+        IMU-monocular, 0 = no scaling.  Returns a dict: status i32 [P] (INITIAL_MAP_STATUS), Tcw2 f32 [P, 12], mpPos / mpNormal f32
+        [P, cap, 3], mpDist f32 [P, cap, 2], hasMP u8 [P, cap], stats i32 [P, 4] (points, outer iterations, trials, stop seen), chi2 f64
+        [P, 2], median f32 [P]."""
+        import torch
+        P, cap = matches12.shape
+        dev = matches12.device
+        if out is None:
+            f32, i32 = torch.float32, torch.int32
+            out = dict(status=torch.zeros((P,), dtype=i32, device=dev), Tcw2=torch.zeros((P, 12), dtype=f32, device=dev),
+                       mpPos=torch.zeros((P, cap, 3), dtype=f32, device=dev), mpNormal=torch.zeros((P, cap, 3), dtype=f32, device=dev),
+                       mpDist=torch.zeros((P, cap, 2), dtype=f32, device=dev), hasMP=torch.zeros((P, cap), dtype=torch.uint8, device=dev),
+                       stats=torch.zeros((P, 4), dtype=i32, device=dev), chi2=torch.zeros((P, 2), dtype=torch.float64, device=dev),
+                       median=torch.zeros((P,), dtype=f32, device=dev))
+        c8 = None if cam8 is None else np.ascontiguousarray(cam8, np.float32)
+        assert c8 is None or c8.size == 8
+        st = stream_arg(stream)
+        check(self._L.morb_create_initial_map_monocular_batch(
+            self._h, C.byref(params), ptr(c8), int(bool(kb8)), P, cap, ptr(img1), ptr(img2), ptr(count), ptr(kps), ptr(matches12), ptr(ok),
+            ptr(T21), ptr(P3D), ptr(triangulated), int(nIterations), int(bool(robust)), float(depthScale), int(minTracked), ptr(stop),
+            ptr(out["status"]), ptr(out["Tcw2"]), ptr(out["mpPos"]), ptr(out["mpNormal"]), ptr(out["mpDist"]), ptr(out["hasMP"]),
+            ptr(out["stats"]), ptr(out["chi2"]), ptr(out["median"]), st))
+        return out
 
     # ---- visual-inertial tracking and mapping (SURVEY 8(f) N1) ---------------------------------------------------
     def InertialOptimization(self, kfStart, kfState, hasLink, pre, mode, flags=None, prior2=None, global16=None, cap=None, out=None,

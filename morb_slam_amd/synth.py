@@ -1346,3 +1346,116 @@ def make_local_mapping_scene(seed=0, B=2, K=3, cap=128, npts=100, cam=EUROC_CAM,
                 img1=np.arange(0, nimg, K + 1, dtype=np.int32), img2=img2, R12=R12, t12=t12, ep=ep, poses=poses, kf2First=kf2First, Tcw7=Tcw7,
                 Ow=Ow, scaleFactors=sf, levelSigma2=(sf * sf).astype(np.float32), cam=dict(fx=fx, fy=fy, cx=cx, cy=cy), mb=float(mb),
                 mbf=float(fx * mb), ratioFactor=float(np.float32(1.5) * np.float32(scale_factor)), width=752, height=480)
+
+
+# ---- CreateInitialMapMonocular (the two frames of a monocular initialisation behind TwoViewReconstruction) ----------------------
+def make_initial_map_problem(seed=0, n_points=150, n_extra=(20, 15), n_untriangulated=6, cam="pinhole", depth=(2.5, 9.0), baseline=0.4,
+                             noise_px=0.5, outlier_frac=0.0, point_noise=0.03, pose_noise=(0.01, 0.03), nlevels=8, scale_factor=1.2,
+                             behind=False, width=752, height=480):
+    """One input of morb_create_initial_map_monocular_batch as the two upstream entries would leave it, seeded.  Keyframe 1 sits at the
+    origin and sees n_points points in the depth slab `depth` (behind=True: the slab lies behind the camera, so that the median depth is
+    negative); keyframe 2 sits `baseline` away.  Every point is observed in both frames with Gaussian pixel noise noise_px * 1.2^octave
+    (the octave drawn per keypoint), a share outlier_frac of the frame-2 observations is moved by 25 .. 80 pixels.  n_extra unmatched
+    keypoints per frame and n_untriangulated matched ones that TwoViewReconstruction left out (triangulated 0) are mixed in, in a seeded
+    order.  cam: "pinhole" (EuRoC) or "kb8" (TUM-VI left).  P3D and T21 are the truth moved by point_noise (relative) and pose_noise
+    (rotation in radians, translation relative to the baseline).  Returns kp1 / kp2 (x, y, octave) f32 [n1 / n2, 3], matches12 i32 [n1],
+    triangulated u8 [n1], P3D f32 [n1, 3], T21 f32 [12] (R row-major, t), ok, cam8 f32 [8], kb8, scaleFactors / levelSigma2 f32 [nlevels],
+    and the truth T21_true f64 [12], X_true f64 [n1, 3]."""
+    assert cam in ("pinhole", "kb8")
+    rng = np.random.default_rng(0x1A17 + seed)
+    kb8 = cam == "kb8"
+    c8 = TUMVI_CAM_L.astype(np.float32) if kb8 else np.array([EUROC_CAM[k] for k in ("fx", "fy", "cx", "cy")] + [0, 0, 0, 0], np.float32)
+    w, h = (512, 512) if kb8 else (width, height)
+    sf = np.float32(scale_factor) ** np.arange(nlevels, dtype=np.float32)
+    m = n_points + n_untriangulated
+    n1, n2 = m + n_extra[0], m + n_extra[1]
+
+    def proj(X):
+        if kb8:
+            return kb8_project(c8.astype(np.float64), X)
+        return np.stack([c8[0] * X[:, 0] / X[:, 2] + c8[2], c8[1] * X[:, 1] / X[:, 2] + c8[3]], 1)
+
+    def backproject(u, z):
+        if not kb8:
+            return np.stack([(u[:, 0] - c8[2]) / c8[0] * z, (u[:, 1] - c8[3]) / c8[1] * z, z], 1)
+        # a ray per pixel by bisection on theta (the polynomial is monotonic over the field of view)
+        px, py = (u[:, 0] - c8[2]) / c8[0], (u[:, 1] - c8[3]) / c8[1]
+        rd = np.sqrt(px * px + py * py)
+        lo, hi = np.zeros_like(rd), np.full_like(rd, 1.5)
+        for _ in range(60):
+            th = 0.5 * (lo + hi)
+            f = th + c8[4] * th ** 3 + c8[5] * th ** 5 + c8[6] * th ** 7 + c8[7] * th ** 9
+            lo, hi = np.where(f < rd, th, lo), np.where(f < rd, hi, th)
+        th = 0.5 * (lo + hi)
+        s = np.where(rd > 1e-12, np.tan(th) / np.maximum(rd, 1e-12), 1.0)
+        return np.stack([px * s * z, py * s * z, z], 1)
+
+    margin = 0.22 if kb8 else 0.06
+    u1 = np.stack([rng.uniform(margin * w, (1 - margin) * w, m), rng.uniform(margin * h, (1 - margin) * h, m)], 1)
+    z = rng.uniform(depth[0], depth[1], m) * (-1.0 if behind else 1.0)
+    X = backproject(u1, z)
+    R = _rot_from_rotvec(rng.normal(0, 0.04, 3))
+    tdir = np.array([rng.choice([-1.0, 1.0]) * rng.uniform(0.8, 1.0), rng.normal(0, 0.2), rng.normal(0, 0.1)])
+    t = tdir / np.linalg.norm(tdir) * baseline
+    X2 = X @ R.T + t
+    u2 = proj(X2)
+    oct1, oct2 = rng.integers(0, nlevels, n1), rng.integers(0, nlevels, n2)
+    i1 = np.sort(rng.permutation(n1)[:m])
+    i2 = rng.permutation(n2)[:m]
+    kp1 = np.stack([rng.uniform(0, w, n1), rng.uniform(0, h, n1), oct1], 1)
+    kp2 = np.stack([rng.uniform(0, w, n2), rng.uniform(0, h, n2), oct2], 1)
+    kp1[i1, :2] = u1 + rng.normal(0, 1, (m, 2)) * (noise_px * sf[oct1[i1]])[:, None]
+    kp2[i2, :2] = u2 + rng.normal(0, 1, (m, 2)) * (noise_px * sf[oct2[i2]])[:, None]
+    out = rng.random(m) < outlier_frac
+    ang = rng.uniform(0, 2 * np.pi, m)
+    kp2[i2[out], :2] += (rng.uniform(25, 80, m)[:, None] * np.stack([np.cos(ang), np.sin(ang)], 1))[out]
+    matches = np.full(n1, -1, np.int32)
+    matches[i1] = i2
+    tri = np.zeros(n1, np.uint8)
+    keep = np.ones(m, bool)
+    keep[rng.permutation(m)[:n_untriangulated]] = False
+    tri[i1[keep]] = 1
+    P3D = np.zeros((n1, 3), np.float32)
+    P3D[i1[keep]] = (X * (1 + rng.normal(0, point_noise, (m, 1))) + rng.normal(0, point_noise * 0.2, (m, 3)))[keep]
+    Xt = np.zeros((n1, 3))
+    Xt[i1[keep]] = X[keep]
+    Rn = _rot_from_rotvec(rng.normal(0, pose_noise[0], 3)) @ R
+    tn = t + rng.normal(0, pose_noise[1], 3) * baseline
+    return dict(n1=n1, n2=n2, kp1=kp1.astype(np.float32), kp2=kp2.astype(np.float32), matches12=matches, triangulated=tri, P3D=P3D,
+                T21=np.concatenate([Rn.ravel(), tn]).astype(np.float32), ok=1, cam8=c8, kb8=int(kb8), scaleFactors=sf,
+                levelSigma2=(sf * sf).astype(np.float32), nlevels=nlevels, width=w, height=h, T21_true=np.concatenate([R.ravel(), t]), X_true=Xt,
+                outlier=out)
+
+
+def initial_map_frame_params(prob):
+    from .capi import make_frame_params
+    c = prob["cam8"]
+    return make_frame_params(prob["width"], prob["height"], float(c[0]), float(c[1]), float(c[2]), float(c[3]), 0.0, 0.0,
+                             [float(v) for v in prob["scaleFactors"]], [float(v) for v in prob["levelSigma2"]])
+
+
+def pack_initial_map_problems(probs, device, cap=None):
+    """make_initial_map_problem dicts -> the torch tensors of Optimizer.CreateInitialMapMonocular on `device`: a keypoint pool kps (u8 view
+    of KP_DTYPE records [2 P, cap]; problem p owns images 2 p and 2 p + 1), img1 / img2 i32 [P], count i32 [2 P], matches12 i32 [P, cap]
+    (-1 padded), ok i32 [P], T21 f32 [P, 12], P3D f32 [P, cap, 3], triangulated u8 [P, cap].  cap = the largest frame unless given."""
+    import torch
+    from .capi import KP_DTYPE
+    P = len(probs)
+    cap = cap or max(max(max(p["n1"], p["n2"]) for p in probs), 1)
+    kps = np.zeros((2 * P, cap), KP_DTYPE)
+    count = np.zeros(2 * P, np.int32)
+    m12 = np.full((P, cap), -1, np.int32)
+    tri = np.zeros((P, cap), np.uint8)
+    P3D = np.zeros((P, cap, 3), np.float32)
+    for k, p in enumerate(probs):
+        for j, (key, n) in enumerate((("kp1", p["n1"]), ("kp2", p["n2"]))):
+            r = kps[2 * k + j, :n]
+            r["x"], r["y"], r["octave"], r["size"] = p[key][:, 0], p[key][:, 1], p[key][:, 2].astype(np.int32), 31.0
+            count[2 * k + j] = n
+        m12[k, :p["n1"]] = p["matches12"]
+        tri[k, :p["n1"]] = p["triangulated"]
+        P3D[k, :p["n1"]] = p["P3D"]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return {"kps": t(kps.view(np.uint8).reshape(2 * P, cap, KP_DTYPE.itemsize).copy()), "img1": t(np.arange(0, 2 * P, 2, dtype=np.int32)),
+            "img2": t(np.arange(1, 2 * P, 2, dtype=np.int32)), "count": t(count), "matches12": t(m12), "triangulated": t(tri), "P3D": t(P3D),
+            "ok": t(np.array([p["ok"] for p in probs], np.int32)), "T21": t(np.stack([p["T21"] for p in probs]).astype(np.float32))}

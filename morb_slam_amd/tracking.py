@@ -13,6 +13,9 @@ features, map points and poses stay in HBM:
 and LocalMapping's two per-keyframe searches (`KeyframeSearches`): SearchForTriangulation (LocalMapping.cc:473,
 ORBmatcher.cc:821-1042) and Fuse (LocalMapping.cc:771-802, ORBmatcher.cc:1044-1183) over keyframe pairs.
 
+`MonocularInitializationChain` is Tracking::MonocularInitialization's: SearchForInitialization, TwoViewReconstruction and the numeric rest
+of CreateInitialMapMonocular (Tracking.cc:2285-2430) over frame pairs.
+
 One `step()` enqueues the whole chain on one stream through the C ABI (libmorb_hip.so); the marshalling between the stages
 (morb_pose_edges_batch, morb_track_discard_outliers_batch, morb_frame_set_pose_batch) runs on the device.  This is the object
 `bench.py --extras` times (`extra_metrics.tracking_chain`) and `tests/test_tracking_gpu.py` compares with the oracle stage by stage.
@@ -241,6 +244,63 @@ class LocalMappingChain:
                 torch.logical_and(T["img2"] >= 0, T["img2"] != self.img2[k][:, None], out=self.valid[k].view(torch.bool))
                 self.m.Fuse(self.P, self.img2[k], self.kps, self.desc, self.count, self.fuseUR[k], self.Tcw7[k], self.Ow[k], self.nMP,
                             self.valid[k], T["Xw"], T["normal"], T["maxDist"], T["minDist"], T["desc"], self.th, out=self.fused[k], stream=st)
+
+    def sync(self):
+        self.stream.synchronize()
+
+
+class MonocularInitializationChain:
+    """Tracking::MonocularInitialization's device chain (Tracking.cc:2285-2343, :2345-2430) for B frame pairs of a keypoint pool, on one
+    stream with no host round trip: ORBmatcher(0.9, true).SearchForInitialization writes vnMatches12, TwoViewReconstruction turns it into
+    T21, vP3D and vbTriangulated, and the initial-map entry (GlobalBundleAdjustemnt, median depth, rescaling, UpdateNormalAndDepth)
+    finishes the map.  Every table is allocated once here; step() only enqueues."""
+
+    def __init__(self, params, kps, desc, count, img1, img2, prevMatched, K4, rand, sigma=1.0, windowSize=100, maxIterations=200,
+                 nIterations=20, robust=True, depthScale=1.0, minTracked=50, cam8=None, kb8=False, device=0):
+        """params: FrameParams; kps [nimg, cap] KP_DTYPE records (mvKeysUn), desc u8 [nimg, cap, 32], count i32 [nimg], img1 / img2 i32
+        [B], prevMatched f32 [B, cap, 2] (vbPrevMatched, in / out), K4 f32 [B, 4], rand i32 [B, >= 8 maxIterations]: device tensors."""
+        import torch
+        self.torch = torch
+        dev = torch.device("cuda", device)
+        self.P, self.kps, self.desc, self.count, self.img1, self.img2 = params, kps, desc, count, img1, img2
+        self.prev, self.K4, self.rand = prevMatched, K4, rand
+        self.win, self.maxIt = int(windowSize), int(maxIterations)
+        self.ba = dict(nIterations=nIterations, robust=robust, depthScale=depthScale, minTracked=minTracked, cam8=cam8, kb8=kb8)
+        self.B, cap = img1.shape[0], kps.shape[1]
+        self.cap = cap
+        self.m = ORBmatcher(0.9, True, device=device)
+        self.o = Optimizer(device)
+        # the chain's default stream is its matcher handle's own (no stream is added to the process); close() releases it with the handle
+        self.stream = torch.cuda.ExternalStream(int(lib().morb_matcher_stream(self.m._h)), device=dev)
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        B = self.B
+        self.sigma = torch.full((B,), float(sigma), dtype=f32, device=dev)
+        self.matches12, self.nmatches = z((B, cap), i32), z((B,), i32)
+        from .optimizer import TWO_VIEW_FSTATS, TWO_VIEW_STATS
+        self.two_view = (z((B,), i32), z((B, 12), f32), z((B, cap, 3), f32), z((B, cap), u8), z((B, len(TWO_VIEW_STATS)), i32),
+                         z((B, len(TWO_VIEW_FSTATS)), f32))
+        self.map = dict(status=z((B,), i32), Tcw2=z((B, 12), f32), mpPos=z((B, cap, 3), f32), mpNormal=z((B, cap, 3), f32),
+                        mpDist=z((B, cap, 2), f32), hasMP=z((B, cap), u8), stats=z((B, 4), i32), chi2=z((B, 2), torch.float64),
+                        median=z((B,), f32))
+
+    def close(self):
+        self.stream.synchronize()
+        self.o.close()
+        self.m.close()
+
+    def step(self, stream=None):
+        s = self.stream if stream is None else stream
+        st = s.cuda_stream
+        L = lib()
+        check(L.morb_search_for_initialization_batch(self.m._h, C.byref(self.P), self.B, ptr(self.img1), ptr(self.img2), self.cap, ptr(self.count),
+                                                     ptr(self.kps), ptr(self.desc), ptr(self.prev), self.win, self.m.mfNNratio,
+                                                     1 if self.m.mbCheckOrientation else 0, ptr(self.matches12), ptr(self.nmatches),
+                                                     C.c_void_p(st)))
+        tv = self.o.TwoViewReconstruction(self.img1, self.img2, self.count, self.kps, self.matches12, self.K4, self.sigma, self.rand, self.maxIt,
+                                          out=self.two_view, stream=st)
+        self.o.CreateInitialMapMonocular(self.P, self.img1, self.img2, self.count, self.kps, self.matches12, tv["ok"], tv["T21"], tv["P3D"],
+                                         tv["triangulated"], out=self.map, stream=st, **self.ba)
 
     def sync(self):
         self.stream.synchronize()
