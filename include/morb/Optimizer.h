@@ -108,6 +108,22 @@ struct LocalBAView {
   std::vector<uint8_t> eraseFlag;   // out [nE]: observations the reference erases (:1366-1401)
   int outerIterations = 0, lmTrials = 0;
 };
+// The graph the welding bundle adjustment of map merging assembles (Optimizer.cc:3459-3648), flattened as morb_merge_bundle_adjustment takes it.
+struct MergeBAView {
+  int nKF = 0, nMP = 0, nE = 0;
+  float* kfPose = nullptr;          // [nKF][7] in / out (free keyframes)
+  const uint8_t* kfFixed = nullptr; // [nKF] 1 = vpFixedKF, 0 = vpAdjustKF
+  float* mpPos = nullptr;           // [nMP][3] in / out
+  const int* eKF = nullptr;         // [nE]
+  const int* eMP = nullptr;         // [nE]
+  const float* eObs = nullptr;      // [nE][3] (x, y, uRight or < 0); with camL8 every edge is monocular and the third slot is not read
+  const float* eInvSigma2 = nullptr;
+  float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  const float* camL8 = nullptr;     // KannalaBrandt8 left camera (fx fy cx cy k0..k3): pKF->mpCamera of every edge
+  std::vector<uint8_t> eraseFlag;   // out [nE]: observations the reference erases (:3705-3739)
+  std::vector<uint8_t> levelFlag;   // out [nE]: edges put on level 1 between the rounds (:3662-3690)
+  int stats[6] = {0, 0, 0, 0, 0, 0};   // out: as morb_merge_bundle_adjustment's stats6
+};
 
 // What Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) reads and writes
 // (Optimizer.cc:2065-2322), per KF1 feature i < N as morb_optimize_sim3_batch (include/morb_hip.h) takes it: entry bits (matched, pMP1
@@ -210,6 +226,26 @@ class Optimizer {
                                        g.fy, g.cx, g.cy, g.mbf, g.inertialMap ? 1 : 0, reinterpret_cast<const unsigned char*>(pbStopFlag),
                                        g.eraseFlag.data(), stats));
     g.outerIterations = stats[0]; g.lmTrials = stats[1];
+  }
+
+  // void static LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF, vector<KeyFrame*> vpFixedKF, bool* pbStopFlag)  Optimizer.h:115-118:
+  // the welding bundle adjustment of LoopClosing::MergeLocal (LoopClosing.cc:1652), on the loop-closing handle.  pbStopFlag is the caller's own bool,
+  // read at entry, polled at every LM iteration and trial and between the two rounds.
+  static void LocalBundleAdjustment(MergeBAView& g, bool* pbStopFlag, int device = 0) {
+    static_assert(sizeof(bool) == 1, "pbStopFlag is read as one byte");
+    g.eraseFlag.assign(g.nE, 0); g.levelFlag.assign(g.nE, 0);
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    const uint8_t* stop = reinterpret_cast<const uint8_t*>(pbStopFlag);
+    if (g.camL8) {
+      std::vector<float> obs2((size_t)g.nE * 2);
+      for (int e = 0; e < g.nE; ++e) { obs2[2 * e] = g.eObs[3 * e]; obs2[2 * e + 1] = g.eObs[3 * e + 1]; }
+      check(morb_merge_bundle_adjustment_fisheye(o.h, g.nKF, g.kfPose, g.kfFixed, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, obs2.data(), g.eInvSigma2, g.camL8,
+                                                 stop, g.eraseFlag.data(), g.levelFlag.data(), g.stats));
+    } else
+    check(morb_merge_bundle_adjustment(o.h, g.nKF, g.kfPose, g.kfFixed, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.fx, g.fy, g.cx,
+                                       g.cy, g.mbf, stop, g.eraseFlag.data(), g.levelFlag.data(), g.stats));
   }
 
   // static int PoseInertialOptimizationLastKeyFrame(Frame* pFrame, bool bRecInit)  Optimizer.h:87 / ...LastFrame  Optimizer.h:88: one frame per call
@@ -356,6 +392,9 @@ class Optimizer {
   template <class FrameT> static int PoseInertialOptimizationLastFrame(FrameT* pFrame, bool bRecInit = false);
   template <class KF, class MapT>
   static void LocalBundleAdjustment(KF* pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges);
+  // (include/Optimizer.h:115-118; call site LoopClosing.cc:1652-1653)
+  template <class KF>
+  static void LocalBundleAdjustment(KF* pMainKF, std::vector<KF*> vpAdjustKF, std::vector<KF*> vpFixedKF, bool* pbStopFlag);
   template <class KF, class MapT>
   static void LocalInertialBA(KF* pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges, bool bLarge = false,
                               bool bRecInit = false);

@@ -5,6 +5,7 @@
 //     Optimizer::PoseInertialOptimizationLastFrame(&mCurrentFrame) / ...LastKeyFrame(&mCurrentFrame)  Tracking.cc:3032-3041
 //     Optimizer::LocalBundleAdjustment(mpCurrentKeyFrame, &mbAbortBA, mpCurrentKeyFrame->GetMap(), a, b, c, d);              LocalMapping.cc:181
 //     Optimizer::LocalInertialBA(mpCurrentKeyFrame, &mbAbortBA, mpCurrentKeyFrame->GetMap(), a, b, c, d, bLarge, !...GetIniertialBA2());  :173
+//     Optimizer::LocalBundleAdjustment(mpCurrentKF, vpLocalCurrentWindowKFs, vpMergeConnectedKFs, &bStop);                 LoopClosing.cc:1652
 // compile unchanged.  Each member assembles the graph exactly as the reference's method does (same selection loops, same flags written to
 // mnBALocalForKF / mnBAFixedForKF, same locks), hands it flattened to the C ABI, and writes the result back as the reference does.
 // KannalaBrandt8 rigs (mpCamera2 != NULL) dispatch to the *_fisheye entry points.  See reference_glue.h for what has been compiled.
@@ -758,6 +759,102 @@ void Optimizer::BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vecto
     for (int k = 0; k < 3; ++k) X(k) = v.mpPos[3 * (size_t)i + k];
     if (own) { pMP->SetWorldPos(X); pMP->UpdateNormalAndDepth(); }
     else { pMP->mPosGBA = X; pMP->mnBAGlobalForKF = nLoopKF; }
+  }
+}
+
+// void Optimizer::LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF, vector<KeyFrame*> vpFixedKF, bool* pbStopFlag)
+// Optimizer.cc:3430-3851, the welding bundle adjustment of LoopClosing::MergeLocal (call site LoopClosing.cc:1652-1653).  The graph selection
+// with its marks (mnBALocalForMerge), flattened; the erase list, the poses and the points written back under mMutexMapUpdate.  The per-keyframe
+// counters and the mpObs* maps of the reference only count and are not kept.  One deviation: on a KannalaBrandt8 rig an observation by the
+// right camera alone (left index -1) is skipped — the reference indexes mvpMapPoints[-1] there.
+template <class KF>
+void Optimizer::LocalBundleAdjustment(KF* pMainKF, std::vector<KF*> vpAdjustKF, std::vector<KF*> vpFixedKF, bool* pbStopFlag) {
+  using SE3 = typename std::decay<decltype(pMainKF->GetPose())>::type;
+  using MP = typename std::remove_pointer<typename std::decay<decltype(*pMainKF->GetMapPoints().begin())>::type>::type;
+  auto* pCurrentMap = pMainKF->GetMap();
+  const auto mainId = pMainKF->mnId;
+  std::vector<MP*> vpMPs;
+  std::map<KF*, int> kfIndex;
+  std::vector<KF*> kfs;
+  std::vector<float> kfPose;
+  std::vector<uint8_t> kfFixed;
+  long unsigned int maxKFid = 0;
+  auto add_window = [&](const std::vector<KF*>& window, bool fixed) {   // :3459-3492 (fixed), :3494-3524 (free)
+    for (KF* pKFi : window) {
+      if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;
+      pKFi->mnBALocalForMerge = mainId;
+      if (!kfIndex.count(pKFi)) {   // (a keyframe of both windows keeps its first vertex: g2o refuses the second id)
+        kfIndex[pKFi] = (int)kfs.size(); kfs.push_back(pKFi);
+        float p[7];
+        morb_glue::pose7(pKFi->GetPose(), p);
+        kfPose.insert(kfPose.end(), p, p + 7);
+        kfFixed.push_back(fixed ? 1 : 0);
+      }
+      if (pKFi->mnId > maxKFid) maxKFid = pKFi->mnId;
+      for (MP* pMPi : pKFi->GetMapPoints())
+        if (pMPi && !pMPi->isBad() && pMPi->GetMap() == pCurrentMap && pMPi->mnBALocalForMerge != mainId) {
+          vpMPs.push_back(pMPi);
+          pMPi->mnBALocalForMerge = mainId;
+        }
+    }
+  };
+  add_window(vpFixedKF, true);
+  add_window(vpAdjustKF, false);
+  // :3550-3648 — points and edges
+  const bool kb8 = pMainKF->mpCamera && pMainKF->mpCamera->size() == 8;
+  std::vector<MP*> mps;
+  std::vector<float> mpPos, eObs, eInv;
+  std::vector<int> eKF, eMP;
+  std::vector<std::pair<KF*, MP*>> eOwner;
+  for (MP* pMPi : vpMPs) {
+    if (pMPi->isBad()) continue;
+    const int j = (int)mps.size();
+    mps.push_back(pMPi);
+    const auto X = pMPi->GetWorldPos();
+    mpPos.push_back(X(0)); mpPos.push_back(X(1)); mpPos.push_back(X(2));
+    for (const auto& ob : pMPi->GetObservations()) {
+      KF* pKF = ob.first;
+      const int leftIndex = std::get<0>(ob.second);
+      if (leftIndex < 0) continue;   // (the deviation named above)
+      if (pKF->isBad() || pKF->mnId > maxKFid || pKF->mnBALocalForMerge != mainId || !pKF->GetMapPoint(leftIndex)) continue;
+      const auto it = kfIndex.find(pKF);
+      if (it == kfIndex.end()) continue;   // (marked by an earlier call with this main keyframe, no vertex now: optimizer.vertex(id) would be NULL)
+      const auto& kpUn = pKF->mvKeysUn[leftIndex];
+      eKF.push_back(it->second); eMP.push_back(j);
+      eObs.push_back(kpUn.pt.x); eObs.push_back(kpUn.pt.y); eObs.push_back(pKF->mvuRight[leftIndex] < 0 ? -1.f : pKF->mvuRight[leftIndex]);
+      eInv.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+      eOwner.emplace_back(pKF, pMPi);
+    }
+  }
+  if (pbStopFlag && *pbStopFlag) return;   // :3650-3651
+  MergeBAView g;
+  g.nKF = (int)kfs.size(); g.nMP = (int)mps.size(); g.nE = (int)eKF.size();
+  if (g.nKF == 0 || g.nMP == 0 || g.nE == 0) return;   // (an empty graph: g2o optimises nothing and every write-back is the identity)
+  g.kfPose = kfPose.data(); g.kfFixed = kfFixed.data(); g.mpPos = mpPos.data(); g.eKF = eKF.data(); g.eMP = eMP.data();
+  g.eObs = eObs.data(); g.eInvSigma2 = eInv.data();
+  g.fx = pMainKF->fx; g.fy = pMainKF->fy; g.cx = pMainKF->cx; g.cy = pMainKF->cy; g.mbf = pMainKF->mbf;
+  float camL[8];
+  if (kb8) { morb_glue::cam8(pMainKF->mpCamera, camL); g.camL8 = camL; }
+  LocalBundleAdjustment(g, pbStopFlag);
+  if (g.stats[5] == 0) return;             // (the flag was raised between the check above and the entry's own)
+  std::unique_lock<std::mutex> lock(pMainKF->GetMap()->mMutexMapUpdate);   // :3747
+  for (size_t e = 0; e < eOwner.size(); ++e)                               // :3749-3756
+    if (g.eraseFlag[e] && !eOwner[e].second->isBad()) {
+      eOwner[e].first->EraseMapPointMatch(eOwner[e].second);
+      eOwner[e].second->EraseObservation(eOwner[e].first);
+    }
+  for (KF* pKFi : vpAdjustKF) {                                            // :3784-3840
+    if (pKFi->isBad()) continue;
+    const auto it = kfIndex.find(pKFi);
+    if (it == kfIndex.end() || kfFixed[it->second]) continue;
+    pKFi->SetPose(morb_glue::make_se3<SE3>(&kfPose[(size_t)7 * it->second]));
+  }
+  for (int j = 0; j < (int)mps.size(); ++j) {                              // :3843-3850
+    if (mps[j]->isBad()) continue;
+    typename std::decay<decltype(mps[j]->GetWorldPos())>::type X;
+    for (int k = 0; k < 3; ++k) X(k) = mpPos[3 * j + k];
+    mps[j]->SetWorldPos(X);
+    mps[j]->UpdateNormalAndDepth();
   }
 }
 

@@ -1024,6 +1024,33 @@ int morb_ba_results(morb_ba_problem*, float* kfPose, float* mpPos, uint8_t* eras
  * 354-480 on the operands the last morb_ba_solve left behind.  flops = MFMA flops issued per launch, usefulFlops = the sparse form's. */
 int morb_ba_schur_profile(morb_ba_problem*, int iters, float* msPerLaunch, double* flops, double* usefulFlops);
 
+/* void static Optimizer::LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF, vector<KeyFrame*> vpFixedKF,
+ * bool* pbStopFlag)  Optimizer.h:115-118, Optimizer.cc:3430-3851: the "welding" bundle adjustment LoopClosing::MergeLocal runs over the
+ * current window and the matched map's window (LoopClosing.cc:1652), on the graph the reference assembles at :3459-3648, flattened (HOST
+ * pointers) like morb_local_bundle_adjustment: kfFixed[i] != 0 for vpFixedKF, 0 for vpAdjustKF (the map's initial keyframe is not special
+ * here); one edge per observation, eObs = (x, y, uRight) with uRight < 0 for a monocular observation (EdgeSE3ProjectXYZ, else
+ * EdgeStereoSE3ProjectXYZ); information eInvSigma2 * I; Huber deltas (float)sqrt(5.99) and (float)sqrt(7.815) (:3547-3548); no user lambda.
+ * stopFlag = pbStopFlag itself (one byte; NULL = none): set at entry (:3650) the call returns MORB_OK with stats6 all zero and nothing else
+ * written; it is polled at every LM iteration and trial (:3452), and set after round 1 (:3658) it skips round 2.  Round 1 is optimize(5)
+ * with the Huber kernels; then every edge with chi2() > 5.991 (7.815 stereo) or a non-positive depth goes to level 1, every edge loses its
+ * kernel, and round 2 is initializeOptimization(0); optimize(10) over the level-0 edges (:3662-3698) with the Levenberg-Marquardt state of
+ * a fresh start.  Outputs: kfPose of the free keyframes and mpPos in place (:3784-3850; fixed keyframes keep their bytes), eraseFlag[e] = 1
+ * where the reference erases the observation (:3705-3739: the same test, on the chi2() the edge holds — for a level-1 edge the value of the
+ * end of round 1 — and on the depth at the final estimate), levelFlag[e] = 1 for the edges excluded from round 2 (may be NULL), stats6 =
+ * {round-1 outer iterations, round-1 trials, round-2 outer iterations, round-2 trials, edges put on level 1, rounds run (0: the flag was set
+ * at entry, else 1 or 2)}.  Both rounds, the classification between them and the flags are one queue of launches with the LM control on the
+ * device ("Welding bundle adjustment"). */
+int morb_merge_bundle_adjustment(morb_optimizer*, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
+                                 int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                                 float fx, float fy, float cx, float cy, float bf, const uint8_t* stopFlag,
+                                 uint8_t* eraseFlag, uint8_t* levelFlag, int* stats6);
+/* The same on a KannalaBrandt8 rig: mvuRight < 0 there, so every edge is an EdgeSE3ProjectXYZ with pKF->mpCamera, the left camera
+ * (:3582-3602; this function makes no right-camera "ToBody" edge).  eObs2 = [nE][2]; camL8 = fx fy cx cy k0..k3. */
+int morb_merge_bundle_adjustment_fisheye(morb_optimizer*, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
+                                         int nE, const int* eKF, const int* eMP, const float* eObs2, const float* eInvSigma2,
+                                         const float* camL8, const uint8_t* stopFlag, uint8_t* eraseFlag, uint8_t* levelFlag,
+                                         int* stats6);
+
 #ifdef __cplusplus
 }
 #endif

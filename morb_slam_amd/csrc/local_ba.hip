@@ -12,6 +12,8 @@
 //   * Persistent mode: one 1024-thread workgroup runs the whole loop (many small problems side by side).
 // All arithmetic is FP64 like g2o; the reference's float leaks (float camera parameters, `const float invz` in
 // the stereo projection, float Huber deltas, float chi2 tests) are reproduced.
+// The welding bundle adjustment of map merging (Optimizer.cc:3430-3851: two rounds with an edge level between them) runs on the same graph,
+// workspace and solver phases in grid mode; its own kernels (k_mg_*) and entry points are at the end of each half of this file.
 #include <hip/hip_runtime.h>
 
 #include <sched.h>
@@ -977,6 +979,346 @@ __global__ void k_ba_reset(BaDev pb, const float* __restrict__ pose0, const floa
   if (i == 0) { pb.lmi[LM_TICKET] = 0; pb.scal[3] = 0; }
 }
 
+// =====================================================================================================
+// The welding bundle adjustment of map merging: Optimizer::LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF,
+// vector<KeyFrame*> vpFixedKF, bool* pbStopFlag) (reference src/Optimizer.cc:3430-3851, called at src/LoopClosing.cc:1652).  Grid mode only,
+// LM control on the device.  Two rounds in ONE queue of launches: optimize(5) with Huber kernels (deltas (float)sqrt(5.99) / (float)sqrt(7.815),
+// :3547-3548), then every edge with chi2() > 5.991 / 7.815 or a non-positive depth goes to level 1, every edge loses its kernel, and
+// initializeOptimization(0); optimize(10) runs over the level-0 edges (:3662-3698).  The graph, the workspace and the phases that do not look at an
+// edge's error (k_g_dinv_push, k_schur_mfma, k_g_schur_finish, k_g_ldlt_*, k_g_backsub_update_w) are LocalBundleAdjustment's; the three that do —
+// chi2, build, finish — are restated here with the round state and the level mask.
+//   * A level-1 edge contributes exact zeros wherever a level-0 edge contributes its terms: chi2, Hll / bl, the chunk sums of Hpp / bp, and its
+//     Hpl block is stored as zeros, so the Schur operands W / WD (packed from Hpl) and the back-substitution (which reads W) carry zeros too.
+//     Sums keep LocalBundleAdjustment's fixed order; x + 0 is x, so the blocks are those of the graph without the edge.
+//   * A vertex whose edges are all on level 1 (g2o drops it from the active set) keeps H = 0, b = 0: its damped block is lambda I, its right-hand
+//     side 0, its update exactly 0 (0 / lambda; nothing divides by the empty block itself), and |diag| = 0 leaves computeLambdaInit's maximum alone.
+//   * chiEdge[e] is chi2() of the edge as g2o holds it: written by every evaluation of an active edge (computeActiveErrors), i.e. after a rejected
+//     last trial the rejected trial's value, and for a level-1 edge the value it had when it was classified (it is never active again, :3705-3739).
+//   * The decision that ends round 1 (mlm_decide) raises RS_TRANSITION and closes the gate of the phase kernels (LM_DONE) without telling the host:
+//     the next slot of the queue is then empty except for its k_mg_chi2, which classifies, undoes a rejected last trial, evaluates the level-0
+//     edges without kernels and starts round 2's LM (iteration 0: lambda = tau max diag of the NEW system, ni = 2, nBad = 0,
+//     optimization_algorithm_levenberg.cpp:93-96).  The host only counts slots and watches `done`.
+struct MergeDev {
+  BaDev ba;                 // first member: the phase kernels shared with LocalBundleAdjustment take this descriptor's address
+  uint8_t* level;           // [nE] 1 = the edge is on level 1 (excluded from round 2)
+  double* chiEdge;          // [nE]
+  int* rs;                  // [16] RS_*: the round state, beside ba.lmi
+  int* stats6;              // [6]
+  double deltaMono, deltaStereo;   // Huber deltas of this optimiser
+};
+enum { RS_ROUND, RS_CAP, RS_ROBUST, RS_TRANSITION, RS_SLOTS, RS_ITS1, RS_TRIALS1, RS_NLEVEL1 };
+
+// the state at the top of a round's first iteration, after its first chi2 (sum s).  One thread.
+__device__ void mlm_init(const MergeDev& md, double s, int round) {
+  const BaDev& pb = md.ba;
+  const bool stop = lm_stop_requested(pb);
+  pb.scal[0] = s; pb.scal[3] = 0;   // (round 2's computeLambdaInit: the maximum starts again)
+  pb.lmd[LMD_CHI] = s; pb.lmd[LMD_LAMBDA] = 0; pb.lmd[LMD_NI] = 2; pb.lmd[LMD_INICHI] = s;
+  pb.lmi[LM_ITER] = 0; pb.lmi[LM_QMAX] = 0; pb.lmi[LM_NBAD] = 0; pb.lmi[LM_ITS] = stop ? 0 : 1; pb.lmi[LM_TRIALS] = 0;
+  pb.lmi[LM_DONE] = stop ? 1 : 0; pb.lmi[LM_NEEDBUILD] = 1; pb.lmi[LM_REJECTED] = 0;
+  md.rs[RS_ROUND] = round; md.rs[RS_CAP] = round ? 10 : 5; md.rs[RS_ROBUST] = round ? 0 : 1; md.rs[RS_TRANSITION] = 0;
+  const int slots = round ? md.rs[RS_SLOTS] + 1 : 0;   // (the hand-over took a slot of the queue)
+  md.rs[RS_SLOTS] = slots;
+  __hip_atomic_store(pb.lmHost + 1, stop ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 0, slots, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// lm_decide with the round's iteration cap, and the end of round 1 handing over to round 2 (Optimizer.cc:3654-3698).  One thread.
+__device__ void mlm_decide(const MergeDev& md, double s0, double s1) {
+  const BaDev& pb = md.ba;
+  pb.scal[0] = s0; pb.scal[1] = s1;
+  double currentChi = pb.lmd[LMD_CHI], lambda = pb.lmd[LMD_LAMBDA], ni = pb.lmd[LMD_NI];
+  const double iniChi = pb.lmd[LMD_INICHI];
+  int iter = pb.lmi[LM_ITER], qmax = pb.lmi[LM_QMAX], nBad = pb.lmi[LM_NBAD], its = pb.lmi[LM_ITS];
+  const int cap = md.rs[RS_CAP], round = md.rs[RS_ROUND];
+  double tempChi = s0;
+  if (pb.scal[2] == 0.0) tempChi = 1.7976931348623157e308;   // the linear solve failed
+  const double rho = (currentChi - tempChi) / (s1 + 1e-3);
+  const bool accept = rho > 0 && isfinite(tempChi);
+  if (accept) {
+    double alpha = 1. - cube_rn(2 * rho - 1);
+    alpha = fmin(alpha, 2. / 3.);
+    lambda *= fmax(1. / 3., alpha);
+    ni = 2;
+    currentChi = tempChi;
+  } else {
+    lambda *= ni;
+    ni *= 2;
+  }
+  ++qmax;
+  const int trials = pb.lmi[LM_TRIALS] + 1;
+  const bool stop = lm_stop_requested(pb);
+  int gate = 0, done = 0, needBuild = 0;
+  if (!(rho < 0 && qmax < 10 && !stop)) {   // the trial loop ends (:139)
+    bool fin = (qmax == 10 || rho == 0);
+    if (!fin) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; fin = nBad >= 3; }
+    if (!fin) { ++iter; fin = iter >= cap || stop; }
+    if (fin) {
+      gate = 1;
+      if (round == 0 && !stop) { md.rs[RS_ITS1] = its; md.rs[RS_TRIALS1] = trials; md.rs[RS_TRANSITION] = 1; }   // *pbStopFlag clear at :3658: round 2 follows
+      else done = 1;
+    } else { ++its; qmax = 0; needBuild = 1; pb.lmd[LMD_INICHI] = currentChi; }
+  }
+  pb.lmd[LMD_CHI] = currentChi; pb.lmd[LMD_LAMBDA] = lambda; pb.lmd[LMD_NI] = ni;
+  pb.lmi[LM_ITER] = iter; pb.lmi[LM_QMAX] = qmax; pb.lmi[LM_NBAD] = nBad; pb.lmi[LM_ITS] = its; pb.lmi[LM_TRIALS] = trials;
+  pb.lmi[LM_DONE] = gate; pb.lmi[LM_NEEDBUILD] = needBuild; pb.lmi[LM_REJECTED] = accept ? 0 : 1;
+  const int slots = md.rs[RS_SLOTS] + 1;
+  md.rs[RS_SLOTS] = slots;
+  __hip_atomic_store(pb.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(pb.lmHost + 0, slots, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided slots: the host queues slot k + 2 when it sees k
+}
+__global__ void k_mg_reset(MergeDev md) {
+  if (threadIdx.x < 16) md.rs[threadIdx.x] = threadIdx.x == RS_CAP ? 5 : threadIdx.x == RS_ROBUST ? 1 : 0;
+  if (threadIdx.x < 6) md.stats6[threadIdx.x] = 0;
+}
+// mode 2: the first chi2 of round 1.  mode 1: a trial's chi2 and its LM decision — or, in the slot behind round 1's last decision, the hand-over:
+// every edge is classified on chiEdge and on its depth at the estimate the round left (the backup when its last trial was rejected, which is
+// restored here), and the level-0 edges' plain chi2 there opens round 2.
+__global__ __launch_bounds__(GB) void k_mg_chi2(const MergeDev* __restrict__ mdp, double* __restrict__ part, const double* __restrict__ part1, int mode) {
+  __shared__ double red[4];
+  __shared__ int isLast;
+  const MergeDev md = *mdp;
+  const BaDev& pb = md.ba;
+  const bool trans = mode == 1 && md.rs[RS_TRANSITION] != 0;
+  if (!trans && lm_skip(pb, mode == 1)) return;
+  const bool robust = !trans && md.rs[RS_ROBUST] != 0;
+  const bool undo = trans && pb.lmi[LM_REJECTED] != 0;
+  const double *pose = undo ? pb.poseBk : pb.pose, *pt = undo ? pb.ptBk : pb.pt;
+  const int gid = blockIdx.x * GB + threadIdx.x;
+  double s = 0;
+  bool bad = false;
+  if (gid < pb.nE) {
+    const float* o = pb.eObs + 3 * gid;
+    const bool st = !(o[2] < 0);
+    double xc[3], err[3], w;
+    se3_map(load_se3(pose + 7 * pb.eKF[gid]), pt + 3 * pb.eMP[gid], xc);
+    if (trans) {
+      bad = md.chiEdge[gid] > (st ? 7.815 : 5.991) || !ba_depth_positive(pb.rig, o, xc);   // :3671 / :3684
+      md.level[gid] = bad ? 1 : 0;
+    }
+    if (trans ? !bad : md.level[gid] == 0) {
+      const double c = ba_edge_error(pb.cam, pb.rig, st, xc, o, (double)pb.eInfo[gid], err);
+      md.chiEdge[gid] = c;
+      s = robust ? huber(st ? md.deltaStereo : md.deltaMono, c, &w) : c;
+    }
+  }
+  if (trans) {
+    const int nb = __popcll(__ballot(bad));
+    if ((threadIdx.x & 63) == 0 && nb) atomicAdd(&md.rs[RS_NLEVEL1], nb);   // (an integer count: any order gives the same sum; read by k_mg_finish)
+    if (undo) {   // (the readers of this launch take the backup itself)
+      if (gid < pb.nKF * 7) pb.pose[gid] = pb.poseBk[gid];
+      if (gid < pb.nMP * 3) pb.pt[gid] = pb.ptBk[gid];
+    }
+  }
+  s = block_sum_d<4>(s, red);
+  if (threadIdx.x == 0) {
+    store_l2(part + blockIdx.x, s);
+    wait_stores();
+    isLast = draw_ticket(&pb.lmi[LM_TICKET]) == (int)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!isLast) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (every handed-off word is read with load_l2)
+  const int n = gridDim.x;
+  const bool decide = mode == 1 && !trans;
+  double s0 = 0, s1 = 0;
+  for (int i = threadIdx.x; i < n; i += GB) { s0 += load_l2(part + i); if (decide) s1 += load_l2(part1 + i); }
+  s0 = block_sum_d<4>(s0, red);
+  s1 = block_sum_d<4>(s1, red);
+  if (threadIdx.x != 0) return;
+  pb.lmi[LM_TICKET] = 0;
+  if (decide) mlm_decide(md, s0, s1); else mlm_init(md, s0, trans ? 1 : 0);
+}
+// build_mp_point / build_kf_chunk / k_g_build with the level mask and the round's kernels
+template <bool RIG>
+__device__ __forceinline__ double mg_build_mp_point(const MergeDev& md, bool robust, int m, int sub, double* __restrict__ slot) {
+  const BaDev& pb = md.ba;
+  double Hl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
+  const bool live = m < pb.nMP;
+  const double* X = pb.pt + 3 * (live ? m : 0);
+  const int k0 = live ? pb.mpStart[m] : 0, k1 = live ? pb.mpStart[m + 1] : 0;
+  for (int kb = k0; kb < k1; kb += MP_LANES) {
+    const int k = kb + sub;
+    double c12[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) c12[q] = 0;
+    const int e = k < k1 ? pb.mpEdges[k] : 0;
+    if (k < k1 && md.level[e] == 0) {
+      const SE3 T = load_se3(pb.pose + 7 * pb.eKF[e]);
+      double xc[3], err[3], w = 1.0, R[9], Jl[9];
+      se3_map(T, X, xc);
+      const float* o = pb.eObs + 3 * e;
+      const bool st = !(o[2] < 0);
+      const double info = (double)pb.eInfo[e];
+      const double c = ba_edge_error(pb.cam, pb.rig, st, xc, o, info, err);
+      if (robust) huber(st ? md.deltaStereo : md.deltaMono, c, &w);
+      q_to_R(T.q, R);
+      ba_edge_jac<RIG>(pb.cam, pb.rig, st, xc, o, R, nullptr, Jl);
+      const double wo = w * info;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double sacc = 0;
+        _Pragma("unroll") for (int i = 0; i < 3; ++i) sacc += Jl[i * 3 + r] * (-info * err[i] * w);
+        c12[9 + r] = sacc;
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+          double h = 0;
+          _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jl[i * 3 + r] * wo * Jl[i * 3 + cc];
+          c12[r * 3 + cc] = h;
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) slot[sub * 12 + q] = c12[q];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (sub == 0) {
+      const int cnt = k1 - kb < MP_LANES ? k1 - kb : MP_LANES;
+      for (int j = 0; j < cnt; ++j) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Hl[q] += slot[j * 12 + q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) bl[q] += slot[j * 12 + 9 + q];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // (the slice is rewritten by the next chunk)
+  }
+  if (!live || sub != 0) return 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pb.Hll[(size_t)m * 9 + k] = Hl[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pb.b[pb.P + 3 * m + k] = bl[k];
+  return fmax(fmax(fabs(Hl[0]), fabs(Hl[4])), fabs(Hl[8]));
+}
+template <bool RIG>
+__device__ __forceinline__ void mg_build_kf_chunk(const MergeDev& md, bool robust, int c, int lane) {
+  const BaDev& pb = md.ba;
+  const int kf = pb.chunkKF[c];
+  const SE3 T = load_se3(pb.pose + 7 * kf);
+  double R[9];
+  q_to_R(T.q, R);
+  double acc[27];
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = 0;
+  const int k = pb.chunkStart[c] + lane;
+  if (k < pb.chunkEnd[c]) {
+    const int e = pb.kfEdges[k];
+    if (md.level[e] != 0) {
+#pragma unroll
+      for (int q = 0; q < 18; ++q) pb.Hpl[(size_t)e * 18 + q] = 0.0;
+    } else {
+      double xc[3], err[3], w = 1.0, Jp[18], Jl[9];
+      se3_map(T, pb.pt + 3 * pb.eMP[e], xc);
+      const float* o = pb.eObs + 3 * e;
+      const bool st = !(o[2] < 0);
+      const double info = (double)pb.eInfo[e];
+      const double ch = ba_edge_error(pb.cam, pb.rig, st, xc, o, info, err);
+      if (robust) huber(st ? md.deltaStereo : md.deltaMono, ch, &w);
+      ba_edge_jac<RIG>(pb.cam, pb.rig, st, xc, o, R, Jp, Jl);
+      const double wo = w * info;
+      int q = 0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+        double sacc = 0;
+        _Pragma("unroll") for (int i = 0; i < 3; ++i) sacc += Jp[i * 6 + r] * (-info * err[i] * w);
+        acc[21 + r] = sacc;
+#pragma unroll
+        for (int cc = r; cc < 6; ++cc) {
+          double h = 0;
+          _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jp[i * 6 + r] * wo * Jp[i * 6 + cc];
+          acc[q++] = h;
+        }
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+          double h = 0;
+          _Pragma("unroll") for (int i = 0; i < 3; ++i) h += Jp[i * 6 + r] * wo * Jl[i * 3 + cc];
+          pb.Hpl[(size_t)e * 18 + r * 3 + cc] = h;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 27; ++q) acc[q] = wave_sum_d(acc[q]);
+  if (lane < 27) {
+    double v = 0;
+#pragma unroll
+    for (int q = 0; q < 27; ++q) if (q == lane) v = acc[q];
+    store_l2(pb.kfPart + (size_t)c * 27 + lane, v);
+  }
+}
+template <bool RIG>
+__global__ __launch_bounds__(GB) void k_mg_build(const MergeDev* __restrict__ mdp, int kfBlocks) {
+  const MergeDev md = *mdp;
+  const BaDev& pb = md.ba;
+  if (lm_skip_build(pb, 1)) return;
+  const bool robust = md.rs[RS_ROBUST] != 0;
+  const bool first = pb.lmi[LM_TRIALS] == 0;   // (of this round)
+  unsigned long long* maxDiag = reinterpret_cast<unsigned long long*>(pb.scal + 3);
+  if ((int)blockIdx.x >= kfBlocks) {
+    __shared__ double sMp[GB * 12];
+    const int g = threadIdx.x / MP_LANES, sub = threadIdx.x % MP_LANES;
+    const int m = (blockIdx.x - kfBlocks) * (GB / MP_LANES) + g;
+    double dm = mg_build_mp_point<RIG>(md, robust, m, sub, sMp + (size_t)g * MP_LANES * 12);
+    if (first) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) dm = fmax(dm, __shfl_xor(dm, off, 64));
+      if ((threadIdx.x & 63) == 0) atomicMax(maxDiag, __builtin_bit_cast(unsigned long long, dm));
+    }
+    return;
+  }
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= pb.nChunks) return;
+  mg_build_kf_chunk<RIG>(md, robust, c, lane);
+  const int kf = pb.chunkKF[c];
+  int last = 0;
+  wait_stores();
+  if (lane == 0) {
+    const int nc = pb.kfChunkStart[kf + 1] - pb.kfChunkStart[kf];
+    last = draw_ticket(&pb.kfTicket[kf]) == nc - 1;
+    if (last) pb.kfTicket[kf] = 0;
+  }
+  if (!__builtin_amdgcn_readfirstlane(last)) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int col = pb.kfCol[kf];
+  if (lane >= 27) return;
+  double s = 0;
+  for (int cc = pb.kfChunkStart[kf]; cc < pb.kfChunkStart[kf + 1]; ++cc) s += load_l2(pb.kfPart + (size_t)cc * 27 + lane);
+  if (lane < 21) {
+    int r = 0, q = lane;
+    while (q >= 6 - r) { q -= 6 - r; ++r; }
+    const int c2 = r + q;
+    pb.Hpp[(size_t)col * 36 + r * 6 + c2] = s;
+    pb.Hpp[(size_t)col * 36 + c2 * 6 + r] = s;
+    if (first && r == c2) atomicMax(maxDiag, __builtin_bit_cast(unsigned long long, fabs(s)));
+  } else {
+    pb.b[6 * col + (lane - 21)] = s;
+  }
+}
+// the erase rule (:3705-3739) on chiEdge and the depth at the final estimate, the write-back as float, stats6
+__global__ __launch_bounds__(GB) void k_mg_finish(const MergeDev* __restrict__ mdp) {
+  const MergeDev md = *mdp;
+  const BaDev& pb = md.ba;
+  const bool undo = pb.lmi[LM_REJECTED] != 0;   // a rejected last trial is undone by reading its backup
+  const double *pose = undo ? pb.poseBk : pb.pose, *pt = undo ? pb.ptBk : pb.pt;
+  const int gid = blockIdx.x * GB + threadIdx.x;
+  if (gid < pb.nE) {
+    const float* o = pb.eObs + 3 * gid;
+    const bool st = !(o[2] < 0);
+    double xc[3];
+    se3_map(load_se3(pose + 7 * pb.eKF[gid]), pt + 3 * pb.eMP[gid], xc);
+    pb.erase[gid] = (md.chiEdge[gid] > (st ? 7.815 : 5.991) || !ba_depth_positive(pb.rig, o, xc)) ? 1 : 0;
+  }
+  if (gid < pb.nKF && pb.kfCol[gid] >= 0) for (int k = 0; k < 7; ++k) pb.poseIO[7 * gid + k] = (float)pose[7 * gid + k];
+  if (gid < pb.nMP * 3) pb.ptIO[gid] = (float)pt[gid];
+  if (gid == 0) {
+    const int round = md.rs[RS_ROUND];
+    md.stats6[0] = round ? md.rs[RS_ITS1] : pb.lmi[LM_ITS]; md.stats6[1] = round ? md.rs[RS_TRIALS1] : pb.lmi[LM_TRIALS];
+    md.stats6[2] = round ? pb.lmi[LM_ITS] : 0; md.stats6[3] = round ? pb.lmi[LM_TRIALS] : 0;
+    md.stats6[4] = md.rs[RS_NLEVEL1]; md.stats6[5] = round + 1;
+  }
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1011,7 +1353,7 @@ extern "C" {
 static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, const float* kfPose, const uint8_t* kfFixed,
                              int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
                              const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
-                             int lambdaInit100, const Rig* rig, bool arena) {
+                             int lambdaInit100, const Rig* rig, bool arena, MergeDev* merge = nullptr) {
   MORB_REQUIRE(o && out && kfPose && kfFixed && mpPos && eKF && eMP && eObs && eInvSigma2, MORB_ERR_INVALID, "NULL argument");
   *out = nullptr;
   MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
@@ -1148,7 +1490,16 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
   h.userLambda = lambdaInit100 ? 100.0 : 0.0;
   p->d_pose0 = (float*)A.take(kfPose, sizeof(float) * 7 * nKF);
   p->d_pt0 = (float*)A.take(mpPos, sizeof(float) * 3 * nMP);
-  p->d_desc = (BaDev*)A.take(&h, sizeof(BaDev));
+  if (merge) {   // the welding BA's descriptor: this one, then the level mask, the edges' chi2 and the round state
+    merge->level = (uint8_t*)A.take(nullptr, nE);
+    merge->chiEdge = (double*)A.take(nullptr, sizeof(double) * nE);
+    merge->rs = (int*)A.take(nullptr, sizeof(int) * 16);
+    merge->stats6 = (int*)A.take(nullptr, sizeof(int) * 6);
+    merge->ba = h;
+    p->d_desc = (BaDev*)A.take(merge, sizeof(MergeDev));
+  } else {
+    p->d_desc = (BaDev*)A.take(&h, sizeof(BaDev));
+  }
   };   // carve
   carve();   // (dry: sizes)
   const size_t upCap = A.uploadBytes(), devCap = A.deviceBytes();
@@ -1174,6 +1525,7 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
     if (!A.ok() || hipMemsetAsync(h.sW, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
         hipMemsetAsync(h.sWD, 0, sizeof(double) * sp.wElems(), cst) != hipSuccess ||
         hipMemsetAsync(h.kfTicket, 0, sizeof(int) * std::max(nKF, 1), cst) != hipSuccess) fail = true;
+    if (!fail && merge && hipMemsetAsync(merge->level, 0, nE, cst) != hipSuccess) fail = true;
     if (!fail && hipMemcpyAsync(aBase, stage, upCap, hipMemcpyHostToDevice, cst) != hipSuccess) fail = true;   // the one upload
     // a persistent problem is complete when create returns (like the synchronous copies it was once made with): it may be solved on any stream
     if (!fail && !arena && hipStreamSynchronize(cst) != hipSuccess) fail = true;
@@ -1389,6 +1741,118 @@ int morb_local_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPo
   const int rc = ba_problem_create_fisheye(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs2, eRight, eInvSigma2, camL8, camR8, Trl7,
                                            lambdaInit100, true);
   return rc != MORB_OK ? rc : local_ba_solve_once(p, stopFlag, kfPose, mpPos, eraseFlag, stats2);
+}
+
+// ---- the welding BA of map merging (k_mg_*): both rounds, the classification between them and the flags as one queue of launches ----
+static int merge_ba_solve(morb_ba_problem* p, const MergeDev& mh) {
+  MORB_ENTER(st, p->opt, nullptr);
+  const BaDev& h = p->h;
+  const BaDev* d = p->d_desc;
+  const MergeDev* dm = reinterpret_cast<const MergeDev*>(p->d_desc);   // (its first member is the BaDev the shared phase kernels read)
+  const int rb = p->redBlocks;
+  double* part0 = h.redPart;
+  double* part1 = h.redPart + rb;
+  const int n = std::max(h.nKF, h.nMP * 3);
+  hipLaunchKernelGGL(k_ba_reset, dim3(div_up(n, 256)), dim3(256), 0, st, p->h, p->d_pose0, p->d_pt0);
+  hipLaunchKernelGGL(k_mg_reset, dim3(1), dim3(64), 0, st, mh);
+  const int kfBlocks = div_up(std::max(h.nChunks, 1), 4);
+  volatile int* hostw = p->h_stop;
+  auto forwardStop = [&]() { if (p->userStop && *p->userStop) __atomic_store_n(p->h_stop + 1, 1, __ATOMIC_RELEASE); };
+  __atomic_store_n(p->h_stop + 1, 0, __ATOMIC_RELAXED);
+  for (int k = 4; k < 8; ++k) __atomic_store_n(p->h_stop + k, 0, __ATOMIC_RELAXED);
+  forwardStop();
+  hipLaunchKernelGGL(k_mg_chi2, dim3(rb), dim3(GB), 0, st, dm, part0, (const double*)part1, 2);
+  constexpr int kAhead = 1;
+  // a slot is one trial, or the hand-over between the rounds: at most 5 x 10 trials, the hand-over, 10 x 10 trials
+  for (int slot = 0; slot < 160; ++slot) {
+    if (h.rig) hipLaunchKernelGGL(k_mg_build<true>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, dm, kfBlocks);
+    else hipLaunchKernelGGL(k_mg_build<false>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, dm, kfBlocks);
+    hipLaunchKernelGGL(k_g_dinv_push, dim3(rb > div_up(h.P * h.P, GB) ? rb : div_up(h.P * h.P, GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 0, 1);
+    hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(p->schur.nblk, p->schur.nsplit), dim3(64), 0, st, (const double*)h.sWD,
+                       (const double*)h.sW, p->schur.Mp, p->schur.ksteps, p->schur.stepsPerSplit, h.sBlocks, h.sPart, (const int*)(h.lmi + LM_DONE));
+    hipLaunchKernelGGL(k_g_schur_finish, dim3(div_up(4 * (h.P * h.P + h.P), GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 1);
+    if (p->denseLds) hipLaunchKernelGGL(k_g_ldlt_lds, dim3(1), dim3(morbdense::LT), p->denseLds, st, d, (const double*)h.HsG, 1);
+    else hipLaunchKernelGGL(k_g_ldlt_global, dim3(1), dim3(morbdense::GT), p->globalLds, st, d, h.HsG, p->d_ldws, p->panelInLds, 1);
+    hipLaunchKernelGGL(k_g_backsub_update_w, dim3(rb), dim3(GB), 0, st, d, part1);
+    hipLaunchKernelGGL(k_mg_chi2, dim3(rb), dim3(GB), 0, st, dm, part0, (const double*)part1, 1);
+    MORB_HIP_CHECK(hipGetLastError());
+    unsigned spins = 0;   // (the wait of morb_ba_solve)
+    const auto tWait = std::chrono::steady_clock::now();
+    while (!__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 4, __ATOMIC_ACQUIRE) < slot + 1 - kAhead) {
+      forwardStop();
+      if ((++spins & 0x3FFu) == 0) {
+        const hipError_t q = hipStreamQuery(st);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) {
+          set_error("merge LocalBundleAdjustment: %s while waiting for the LM decision", hipGetErrorString(q));
+          return MORB_ERR_HIP;
+        }
+      }
+      if (spins < 2048) __builtin_ia32_pause();
+      else if ((spins & 0xFF) != 0 || std::chrono::steady_clock::now() - tWait < std::chrono::milliseconds(2)) sched_yield();
+      else { struct timespec ts = {0, 50000}; nanosleep(&ts, nullptr); }
+    }
+    if (__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE)) break;
+  }
+  hipLaunchKernelGGL(k_mg_finish, dim3(rb), dim3(GB), 0, st, dm);
+  MORB_HIP_CHECK(hipGetLastError());
+  return MORB_OK;
+}
+
+static int merge_ba_once(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos, int nE, const int* eKF,
+                         const int* eMP, const float* eObs3, const float* eInvSigma2, const Cam& cam, const Rig* rig, const uint8_t* stopFlag,
+                         uint8_t* eraseFlag, uint8_t* levelFlag, int* stats6) {
+  // (ba_problem_create's checks, ahead of the stop flag: a refused call is refused whatever the flag says, and before any upload or launch)
+  MORB_REQUIRE(o && kfPose && kfFixed && mpPos && eKF && eMP && eObs3 && eInvSigma2 && eraseFlag && stats6, MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
+  for (int e = 0; e < nE; ++e)
+    MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
+  if (stopFlag && *(const volatile uint8_t*)stopFlag) {   // :3650-3651: nothing is optimised, nothing written
+    for (int k = 0; k < 6; ++k) stats6[k] = 0;
+    return MORB_OK;
+  }
+  MergeDev mh;
+  memset(&mh, 0, sizeof mh);
+  mh.deltaMono = (double)(float)sqrt(5.99); mh.deltaStereo = (double)(float)sqrt(7.815);   // thHuber2D / thHuber3D (:3547-3548)
+  morb_ba_problem* p = nullptr;
+  int rc = ba_problem_create(o, &p, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs3, eInvSigma2, cam.fx, cam.fy, cam.cx, cam.cy, cam.bf, 0,
+                             rig, true, &mh);
+  if (rc != MORB_OK) return rc;
+  p->userStop = stopFlag;   // optimizer.setForceStopFlag(pbStopFlag) (:3452)
+  rc = merge_ba_solve(p, mh);
+  hipStream_t st = o->stream;
+  if (rc == MORB_OK) {
+    hipError_t e = hipMemcpyAsync(kfPose, p->h.poseIO, sizeof(float) * 7 * nKF, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(mpPos, p->h.ptIO, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(eraseFlag, p->h.erase, nE, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && levelFlag) e = hipMemcpyAsync(levelFlag, mh.level, nE, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stats6, mh.stats6, sizeof(int) * 6, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("merge LocalBundleAdjustment: %s", hipGetErrorString(e)); rc = MORB_ERR_HIP; }
+  }
+  morb_ba_problem_destroy(p);   // (waits for the handle's stream: the workspace is free for the next call)
+  return rc;
+}
+
+int morb_merge_bundle_adjustment(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos, int nE,
+                                 const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2, float fx, float fy, float cx,
+                                 float cy, float bf, const uint8_t* stopFlag, uint8_t* eraseFlag, uint8_t* levelFlag, int* stats6) {
+  return merge_ba_once(o, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, Cam{fx, fy, cx, cy, bf}, nullptr, stopFlag,
+                       eraseFlag, levelFlag, stats6);
+}
+
+int morb_merge_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos, int nE,
+                                         const int* eKF, const int* eMP, const float* eObs2, const float* eInvSigma2, const float* camL8,
+                                         const uint8_t* stopFlag, uint8_t* eraseFlag, uint8_t* levelFlag, int* stats6) {
+  MORB_REQUIRE(eObs2 && camL8, MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nE > 0, MORB_ERR_INVALID, "empty problem");
+  // every edge is an EdgeSE3ProjectXYZ with pKF->mpCamera, the left KB8 camera (:3582-3602): kind -2 in the third observation slot
+  std::vector<float> obs3((size_t)nE * 3);
+  for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = -2.0f; }
+  const float Trl7[7] = {0, 0, 0, 1, 0, 0, 0};   // (no right-camera edge reads the second camera or mTrl)
+  const Rig rig = make_rig(camL8, camL8, Trl7);
+  return merge_ba_once(o, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, Cam{0.f, 0.f, 0.f, 0.f, 0.f}, &rig, stopFlag,
+                       eraseFlag, levelFlag, stats6);
 }
 
 }  // extern "C"

@@ -351,6 +351,29 @@ class Optimizer:
         p.solve()
         return p.results()
 
+    def MergeBundleAdjustment(self, kfPose, kfFixed, mpPos, eKF, eMP, eObs, eInvSigma2, cam, stop_flag=None, camL=None):
+        """Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag), the welding bundle adjustment of map merging, on
+        host numpy arrays (see morb_merge_bundle_adjustment).  camL = 8 floats selects the KannalaBrandt8 left camera (eObs is then
+        [nE, 2]; cam is ignored).  stop_flag: a one-byte numpy array standing for `bool* pbStopFlag`.
+        Returns (kfPose, mpPos, eraseFlag, levelFlag, stats6)."""
+        a = [np.ascontiguousarray(kfPose, np.float32).copy(), np.ascontiguousarray(kfFixed, np.uint8),
+             np.ascontiguousarray(mpPos, np.float32).copy(), np.ascontiguousarray(eKF, np.int32), np.ascontiguousarray(eMP, np.int32),
+             np.ascontiguousarray(eObs, np.float32), np.ascontiguousarray(eInvSigma2, np.float32)]
+        nE = len(a[3])
+        erase = np.zeros(nE, np.uint8); level = np.zeros(nE, np.uint8); stats = np.zeros(6, np.int32)
+        st = ptr(stop_flag) if stop_flag is not None else None
+        if camL is not None:
+            c8 = np.ascontiguousarray(camL, np.float32)
+            assert c8.size == 8 and a[5].shape == (nE, 2)
+            check(self._L.morb_merge_bundle_adjustment_fisheye(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]),
+                                                               ptr(a[4]), ptr(a[5]), ptr(a[6]), ptr(c8), st, ptr(erase), ptr(level), ptr(stats)))
+            return a[0], a[2], erase, level, stats
+        assert a[5].shape == (nE, 3)
+        check(self._L.morb_merge_bundle_adjustment(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]),
+                                                   ptr(a[5]), ptr(a[6]), cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["bf"], st,
+                                                   ptr(erase), ptr(level), ptr(stats)))
+        return a[0], a[2], erase, level, stats
+
 
 def local_bundle_adjustment_oneshot(opt, kfPose, kfFixed, mpPos, eKF, eMP, eObs, eInvSigma2, cam, inertial=False, stop_flag=None):
     """The one-shot ABI entry (`morb_local_bundle_adjustment`), as the reference binding calls it: `stop_flag` is a one-byte

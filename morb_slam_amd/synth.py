@@ -1459,3 +1459,101 @@ def pack_initial_map_problems(probs, device, cap=None):
     return {"kps": t(kps.view(np.uint8).reshape(2 * P, cap, KP_DTYPE.itemsize).copy()), "img1": t(np.arange(0, 2 * P, 2, dtype=np.int32)),
             "img2": t(np.arange(1, 2 * P, 2, dtype=np.int32)), "count": t(count), "matches12": t(m12), "triangulated": t(tri), "P3D": t(P3D),
             "ok": t(np.array([p["ok"] for p in probs], np.int32)), "T21": t(np.stack([p["T21"] for p in probs]).astype(np.float32))}
+
+
+# ---- map merging: the welding bundle adjustment (Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag)) ----------
+def make_merge_ba_problem(n_free=25, n_fixed=25, n_points=3500, seed=0, mono_frac=0.3, kb8=False, outlier_frac=0.04, rigid_deg=0.6,
+                          rigid_trans=0.03, kf_deg=0.15, kf_trans=0.005, point_noise=0.02, noise_px=1.0, obs_per_point=(4, 11), bad_points=0,
+                          bad_kf=None, stuck_kf=None, stuck_deg=2.5, stuck_trans=0.08, kf_edges=None, cam=EUROC_CAM):
+    """Input of the welding BA of LoopClosing::MergeLocal: a free window (keyframes 0 .. n_free - 1, vpAdjustKF) and a fixed window (the
+    matched map's, vpFixedKF) on one arc looking at common points.  The free window is displaced rigidly by what a Sim3 alignment leaves
+    (rigid_deg, rigid_trans), each of its keyframes by a little more (kf_deg, kf_trans); a fraction of the observations are gross
+    outliers (wrong fusions).  mono_frac: the share of monocular observations (1.0: none stereo); kb8: every observation monocular on the
+    TUM-VI left KannalaBrandt8 camera (eObs is [nE, 2], `camL` the camera).  bad_points: that many points have ONLY gross observations;
+    bad_kf: a free keyframe whose observations are ALL gross; stuck_kf: a free keyframe with a pose error of its own (stuck_deg,
+    stuck_trans) that a few robust iterations do not remove; kf_edges = {keyframe: count}: that keyframe observes exactly `count` points."""
+    rng = np.random.default_rng(0x3E26E + seed)
+    nkf = n_free + n_fixed
+    poses = []
+    for i in range(nkf):
+        ang = (i / max(nkf - 1, 1) - 0.5) * 0.5
+        c = np.array([2.0 * np.sin(ang) * 2, rng.normal(0, 0.05), -2.0 * (1 - np.cos(ang))])
+        q_wc = _quat_from_rotvec(np.array([0, -ang * 0.8, 0]) + rng.normal(0, 0.01, 3))
+        q_cw = q_wc * np.array([-1, -1, -1, 1])
+        poses.append(np.concatenate([q_cw, -_quat_rot(q_cw, c)]))
+    poses = np.array(poses)
+    zr = (2.0, 8.0) if kb8 else (3.0, 10.0)
+    X = np.stack([rng.uniform(-3, 3, n_points), rng.uniform(-2, 2, n_points), rng.uniform(*zr, n_points)], 1)
+
+    def observe(kf, j):
+        """(observation, 1 / sigma^2) of point j in keyframe kf, or None when it is not in the image"""
+        Xc = _quat_rot(poses[kf][:4], X[j]) + poses[kf][4:]
+        if kb8:
+            if Xc[2] <= 0.4:
+                return None
+            uv = kb8_project(TUMVI_CAM_L, Xc[None])[0]
+            if not (5 < uv[0] < 507 and 5 < uv[1] < 507):
+                return None
+            o = uv
+        else:
+            if Xc[2] <= 0.5:
+                return None
+            u = cam["fx"] * Xc[0] / Xc[2] + cam["cx"]; v = cam["fy"] * Xc[1] / Xc[2] + cam["cy"]
+            if not (0 <= u < 752 and 0 <= v < 480):
+                return None
+            o = np.array([u, v, u - cam["bf"] / Xc[2]])
+        s = 1.2 ** int(rng.integers(0, 8))
+        o = o + rng.normal(0, noise_px, len(o)) * s
+        if not kb8 and rng.random() < mono_frac:
+            o[2] = -1
+        return o, 1.0 / s ** 2
+
+    fixed_count = dict(kf_edges or {})
+    seen = set()
+    eKF, eMP, eObs, eInv = [], [], [], []
+    for j in range(n_points):
+        k = int(rng.integers(*obs_per_point))
+        for kf in rng.choice(nkf, size=min(k, nkf), replace=False):
+            if int(kf) in fixed_count:
+                continue
+            r = observe(int(kf), j)
+            if r is not None:
+                eKF.append(int(kf)); eMP.append(j); eObs.append(r[0]); eInv.append(r[1]); seen.add((int(kf), j))
+    for kf, count in fixed_count.items():
+        got = 0
+        for j in rng.permutation(n_points):
+            if got == count:
+                break
+            r = observe(kf, int(j))
+            if r is not None:
+                eKF.append(kf); eMP.append(int(j)); eObs.append(r[0]); eInv.append(r[1]); got += 1
+        assert got == count, (kf, got, count)
+    eKF, eMP, eObs, eInv = np.array(eKF, np.int32), np.array(eMP, np.int32), np.array(eObs, np.float64), np.array(eInv, np.float32)
+    order = np.lexsort((eKF, eMP))          # (edges by point, as the reference walks its points' observations)
+    eKF, eMP, eObs, eInv = eKF[order], eMP[order], eObs[order], eInv[order]
+    gross = rng.random(len(eKF)) < outlier_frac
+    if bad_points:
+        gross |= np.isin(eMP, rng.choice(n_points, bad_points, replace=False))
+    if bad_kf is not None:
+        gross |= eKF == bad_kf
+    off = rng.choice([-1, 1], (len(eKF), 2)) * rng.uniform(15, 30, (len(eKF), 2))
+    eObs[gross, :2] += off[gross]
+    # the free window: a rigid displacement of the whole window in the world, then per-keyframe noise
+    dq = _quat_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(rigid_deg))
+    dt = rng.normal(0, 1, 3) / np.sqrt(3) * rigid_trans
+    pose0 = poses.copy()
+    for i in range(n_free):
+        q = _quat_mul(poses[i][:4], dq)                                    # Tcw' = Tcw * D,  D = (dq, dt) acting on the world
+        t = _quat_rot(poses[i][:4], dt) + poses[i][4:]
+        deg, tr = (stuck_deg, stuck_trans) if i == stuck_kf else (kf_deg, kf_trans)
+        nq = _quat_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(deg))
+        pose0[i] = np.concatenate([_quat_mul(nq, q), _quat_rot(nq, t) + rng.normal(0, 1, 3) / np.sqrt(3) * tr])
+    X0 = X + rng.normal(0, point_noise, X.shape)
+    fixed = np.zeros(nkf, np.uint8); fixed[n_free:] = 1
+    out = dict(kfPose=pose0.astype(np.float32), kfFixed=fixed, mpPos=X0.astype(np.float32), eKF=eKF, eMP=eMP, eInvSigma2=eInv,
+               true_poses=poses, true_points=X, gross=gross, cam=cam, camL=None)
+    if kb8:
+        out.update(eObs=eObs[:, :2].astype(np.float32), camL=TUMVI_CAM_L)
+    else:
+        out["eObs"] = eObs.astype(np.float32)
+    return out
