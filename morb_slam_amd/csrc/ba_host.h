@@ -1,8 +1,11 @@
-// Host side shared by the two bundle adjusters (local_ba.hip: ba_problem_create, inertial_ba.hip: local_inertial_ba_impl): the carve
-// of one device block into arrays, and the flattened graph's lists.  Host only (no HIP header) and nothing here allocates device or
-// pinned memory: tests/native/ba_host_check.cc compiles it alone, with sanitizers.
+// Host side shared by the three bundle adjusters (local_ba.hip: LocalBA and the welding BA of map merging; inertial_ba.hip: LocalInertialBA):
+// the carve of one device block into arrays, the flattened graph's lists, and the host loop that queues Levenberg-Marquardt trials ahead of the
+// device's decisions.  Host only (no HIP header), nothing here allocates: tests/native/ba_host_check.cc compiles it alone, with sanitizers.
 #pragma once
+#include <sched.h>
+#include <time.h>
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <vector>
 
@@ -73,6 +76,40 @@ inline void schur_block_lists(int nb, std::vector<I2>& blocks, std::vector<int>&
   index.assign((size_t)nb * nb, 0);
   for (int bi = 0; bi < nb; ++bi)
     for (int bj = bi; bj < nb; ++bj) { index[(size_t)bi * nb + bj] = (int)blocks.size(); I2 b; b.x = bi; b.y = bj; blocks.push_back(b); }
+}
+
+// Levenberg-Marquardt with the control flow on the device, the host's part.  The device decides every trial and mirrors `decided` (trials
+// decided so far) and `done` to mapped host memory; kernels queued behind the last decision return at once.  The host queues slot after slot
+// (queueSlot(slot): one trial's launches; non-zero: a launch error), one ahead of the decisions: slot s + 1 once `decided` >= s, `done` is set,
+// or look() — hipStreamQuery, asked at every 1024th look at the words — finds the stream idle.  tick() runs before every look at the words.
+// Returns 1: `done` seen; 0: maxSlots queued without it (decisions may still be on their way: drain the stream before the words are reset);
+// negative: queueSlot's error, or -1 when look() said Failed — nothing is queued behind either.  sleeps: counts the 50 us sleeps (tests).
+enum class StreamLook { Busy, Idle, Failed };
+
+template <class QueueSlot, class Look, class Tick>
+int lm_slot_queue(int maxSlots, const int* decided, const int* done, QueueSlot&& queueSlot, Look&& look, Tick&& tick, int* sleeps = nullptr) {
+  for (int slot = 0; slot < maxSlots; ++slot) {
+    if (const int rc = queueSlot(slot)) return rc < 0 ? rc : -rc;
+    // wait until all but the last queued trial are decided (or the solve is done) on the mapped host words, backing off in tiers: a
+    // trial takes ~110 us, so the first ~30 us are `pause` spins (the decision of a short trial is picked up at once), then the thread yields
+    // its core between looks (LocalMapping's thread no longer holds a core against Tracking's for the whole solve), and a wait that outlasts
+    // 2 ms — a solve stuck behind other work on the device — sleeps 50 us at a time
+    unsigned spins = 0;
+    const auto tWait = std::chrono::steady_clock::now();
+    while (!__atomic_load_n(done, __ATOMIC_ACQUIRE) && __atomic_load_n(decided, __ATOMIC_ACQUIRE) < slot) {
+      tick();
+      if ((++spins & 0x3FFu) == 0) {
+        const StreamLook q = look();
+        if (q == StreamLook::Idle) break;          // (everything queued has run: the words are final)
+        if (q == StreamLook::Failed) return -1;    // a kernel fault: the words will never change
+      }
+      if (spins < 2048) __builtin_ia32_pause();
+      else if ((spins & 0xFF) != 0 || std::chrono::steady_clock::now() - tWait < std::chrono::milliseconds(2)) sched_yield();
+      else { struct timespec ts = {0, 50000}; nanosleep(&ts, nullptr); if (sleeps) ++*sleeps; }
+    }
+    if (__atomic_load_n(done, __ATOMIC_ACQUIRE)) return 1;
+  }
+  return 0;
 }
 
 }  // namespace morb

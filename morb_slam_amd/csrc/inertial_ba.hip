@@ -733,7 +733,7 @@ static int iba_layout(int nKF, const uint8_t* kfKind, int nMP, int nE, const int
 }
 
 // Levenberg-Marquardt with the control flow on the device (as grid-mode LocalBA, local_ba.hip): one slot = one trial; the host queues
-// slots one ahead of the decisions and stops when the mapped `done` word appears; kernels queued behind the last decision return at once.
+// slots one ahead of the decisions and stops when the mapped `done` word appears (ba_host.h); kernels queued behind the last decision return at once.
 // Leaves the loop's counters in *outer / *trials and the chi2 of the last evaluated trial in *lastChi.
 static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLayout& L, double chi, int bLarge, size_t denseLds, size_t blockedLds,
                        int panelInLds, int* outer, int* trials, double* lastChi) {
@@ -746,7 +746,7 @@ static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLa
   __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
   hipLaunchKernelGGL(k_iba_lm_init, dim3(1), dim3(1), 0, st, D, chi, bLarge ? 1e-2 : 1e0);
   const int beginGrid = div_up((int)std::max<size_t>(std::max<size_t>(std::max<size_t>(nS, nPts), (size_t)nMP * 8 /* k_iba_points: eight lanes per point */), std::max<size_t>((size_t)P * P, (size_t)18 * nE)), 256);
-  for (int slot = 0; slot < 120; ++slot) {
+  const int q = lm_slot_queue(120, hostw + 0, hostw + 1, [&](int) {
     // backup / restore, then buildSystem (which runs only when the previous trial was accepted)
     hipLaunchKernelGGL(k_iba_points, dim3(beginGrid), dim3(256), 0, st, D);
     if (nChunks) hipLaunchKernelGGL(k_iba_kf, dim3(div_up(nChunks, 4)), dim3(256), 0, st, D);
@@ -763,18 +763,14 @@ static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLa
     // a failed solve leaves x as it was (zero at the first trial): g2o still applies the update
     hipLaunchKernelGGL(k_iba_update, dim3(div_up(nMP + nKF, 256)), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 1);
-    if (hipGetLastError() != hipSuccess) return iba_fail("LocalInertialBA trial failed");
-    unsigned spins = 0;
-    while (!__atomic_load_n(hostw + 1, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 0, __ATOMIC_ACQUIRE) < slot) {   // one slot ahead
-      if ((++spins & 0x3FFu) == 0) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) break;   // (everything queued has run: the words are final)
-        if (q != hipErrorNotReady) return iba_fail("LocalInertialBA: device error while waiting for the LM decision");
-      }
-      __builtin_ia32_pause();
-    }
-    if (__atomic_load_n(hostw + 1, __ATOMIC_ACQUIRE)) break;
-  }
+    return hipGetLastError() != hipSuccess ? iba_fail("LocalInertialBA trial failed") : MORB_OK;
+  }, [&]() {
+    const hipError_t e = hipStreamQuery(st);
+    if (e != hipSuccess && e != hipErrorNotReady) iba_fail("LocalInertialBA: device error while waiting for the LM decision");
+    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
+  }, []() {});   // (no stop flag: LocalInertialBA's caller has none to forward)
+  if (q < 0) return MORB_ERR_HIP;
+  // (a queue that ran out of slots without `done` is drained by the read-back below, before the words are reset again)
   hipLaunchKernelGGL(k_iba_end, dim3(div_up((int)std::max<size_t>(nS, nPts), 256)), dim3(256), 0, st, D);
   int hi[16]; double hd[8];
   if (hipMemcpyAsync(hi, D.lmi, sizeof hi, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hd, D.lmd, sizeof hd, hipMemcpyDeviceToHost, st) != hipSuccess ||

@@ -16,11 +16,7 @@
 // workspace and solver phases in grid mode; its own kernels (k_mg_*) and entry points are at the end of each half of this file.
 #include <hip/hip_runtime.h>
 
-#include <sched.h>
-#include <time.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -1346,7 +1342,68 @@ struct morb_ba_problem {
   int panelInLds = 1;
 };
 
+// ---- the host side of a grid-mode solve that LocalBA and the welding BA share ----
+// the launches of a slot between its build and its chi2: landmark inverses, Schur complement on the matrix cores, LDL^T, back-substitution
+static void ba_launch_solve_phases(const morb_ba_problem* p, hipStream_t st) {
+  const BaDev& h = p->h; const BaDev* d = p->d_desc; const int rb = p->redBlocks;
+  hipLaunchKernelGGL(k_g_dinv_push, dim3(rb > div_up(h.P * h.P, GB) ? rb : div_up(h.P * h.P, GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 0, 1);
+  hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(p->schur.nblk, p->schur.nsplit), dim3(64), 0, st, (const double*)h.sWD,
+                     (const double*)h.sW, p->schur.Mp, p->schur.ksteps, p->schur.stepsPerSplit, h.sBlocks, h.sPart, (const int*)(h.lmi + LM_DONE));
+  hipLaunchKernelGGL(k_g_schur_finish, dim3(div_up(4 * (h.P * h.P + h.P), GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 1);
+  if (p->denseLds) hipLaunchKernelGGL(k_g_ldlt_lds, dim3(1), dim3(morbdense::LT), p->denseLds, st, d, (const double*)h.HsG, 1);
+  else hipLaunchKernelGGL(k_g_ldlt_global, dim3(1), dim3(morbdense::GT), p->globalLds, st, d, h.HsG, p->d_ldws, p->panelInLds, 1);
+  hipLaunchKernelGGL(k_g_backsub_update_w, dim3(rb), dim3(GB), 0, st, d, h.redPart + rb);
+}
+
+// A solve on st behind its reset kernels, through the queue of ba_host.h (lm_slot_queue): clears the forwarded stop flag and the LM state
+// mirror (morb_ba_set_stop's word stays), lets launchSlot(slot) queue up to maxSlots slots, forwarding the caller's *pbStopFlag to the word
+// the decision kernels poll before the first launch and at every look, then lets launchFinish() queue the adjuster's last kernel.
+template <class LaunchSlot, class LaunchFinish>
+static int ba_queue_solve(morb_ba_problem* p, hipStream_t st, int maxSlots, const char* who, LaunchSlot&& launchSlot, LaunchFinish&& launchFinish) {
+  auto forwardStop = [&]() { if (p->userStop && *p->userStop) __atomic_store_n(p->h_stop + 1, 1, __ATOMIC_RELEASE); };
+  __atomic_store_n(p->h_stop + 1, 0, __ATOMIC_RELAXED);
+  for (int k = 4; k < 8; ++k) __atomic_store_n(p->h_stop + k, 0, __ATOMIC_RELAXED);
+  forwardStop();
+  const int q = lm_slot_queue(maxSlots, p->h_stop + 4, p->h_stop + 5, [&](int slot) { launchSlot(slot); MORB_HIP_CHECK(hipGetLastError()); return MORB_OK; }, [&]() {
+    const hipError_t e = hipStreamQuery(st);
+    if (e != hipSuccess && e != hipErrorNotReady) set_error("%s: %s while waiting for the LM decision", who, hipGetErrorString(e));
+    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
+  }, forwardStop);
+  if (q < 0) return MORB_ERR_HIP;
+  launchFinish();
+  MORB_HIP_CHECK(hipGetLastError());
+  // slot limit reached without a `done`: decisions of this solve may still be on their way — let them land before the next solve resets
+  // the mirror words (the usual exit has seen `done`, after which no kernel writes them)
+  if (!q) MORB_HIP_CHECK(hipStreamSynchronize(st));
+  return MORB_OK;
+}
+
+// the read-back of the poses, the points and the erase flags, queued on st (null: not wanted); the caller adds its own and synchronises
+static hipError_t ba_queue_results(const morb_ba_problem* p, hipStream_t st, float* kfPose, float* mpPos, uint8_t* eraseFlag) {
+  hipError_t e = kfPose ? hipMemcpyAsync(kfPose, p->h.poseIO, sizeof(float) * 7 * p->h.nKF, hipMemcpyDeviceToHost, st) : hipSuccess;
+  if (e == hipSuccess && mpPos) e = hipMemcpyAsync(mpPos, p->h.ptIO, sizeof(float) * 3 * p->h.nMP, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && eraseFlag) e = hipMemcpyAsync(eraseFlag, p->h.erase, p->h.nE, hipMemcpyDeviceToHost, st);
+  return e;
+}
+
 extern "C" {
+
+// what every entry point refuses before anything else: a missing array, an empty graph, an edge that names no keyframe or map point
+static int ba_check_graph(const morb_optimizer* o, int nKF, const float* kfPose, const uint8_t* kfFixed, int nMP, const float* mpPos, int nE,
+                          const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2) {
+  MORB_REQUIRE(o && kfPose && kfFixed && mpPos && eKF && eMP && eObs && eInvSigma2, MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
+  for (int e = 0; e < nE; ++e) MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
+  return MORB_OK;
+}
+
+// the two-float observations of a fisheye entry point in the three-float form of the graph: the edge kind travels in the third slot,
+// -2 = EdgeSE3ProjectXYZ with the left KB8 camera, -3 = EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl; eRight == null: no such edge)
+static std::vector<float> fisheye_obs3(int nE, const float* eObs2, const uint8_t* eRight) {
+  std::vector<float> obs3((size_t)nE * 3);
+  for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = eRight && eRight[e] ? -3.0f : -2.0f; }
+  return obs3;
+}
 
 // morb_ba_problem_create, with the fisheye rig of morb_ba_problem_create_fisheye (nullptr: pinhole).  arena: the problem of a one-shot
 // entry point, carved from the handle's `work` / `stage` / `lmWords` for the duration of that call (it owns no memory of its own)
@@ -1354,11 +1411,9 @@ static int ba_problem_create(morb_optimizer* o, morb_ba_problem** out, int nKF, 
                              int nMP, const float* mpPos, int nE, const int* eKF, const int* eMP, const float* eObs,
                              const float* eInvSigma2, float fx, float fy, float cx, float cy, float bf,
                              int lambdaInit100, const Rig* rig, bool arena, MergeDev* merge = nullptr) {
-  MORB_REQUIRE(o && out && kfPose && kfFixed && mpPos && eKF && eMP && eObs && eInvSigma2, MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(out, MORB_ERR_INVALID, "NULL argument");
   *out = nullptr;
-  MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
-  for (int e = 0; e < nE; ++e)
-    MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
+  if (const int rc = ba_check_graph(o, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2)) return rc;
   MORB_HIP_CHECK(hipSetDevice(o->device));
   std::unique_ptr<morb_ba_problem> p(new morb_ba_problem());
   p->opt = o;
@@ -1572,10 +1627,7 @@ static int ba_problem_create_fisheye(morb_optimizer* o, morb_ba_problem** out, i
                                      const float* Trl7, int lambdaInit100, bool arena) {
   MORB_REQUIRE(out && eObs2 && eRight && camL8 && camR8 && Trl7, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nE > 0, MORB_ERR_INVALID, "empty problem");
-  // the edge kind travels in the third observation slot: -2 = EdgeSE3ProjectXYZ with the left KB8 camera,
-  // -3 = EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl)
-  std::vector<float> obs3((size_t)nE * 3);
-  for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = eRight[e] ? -3.0f : -2.0f; }
+  const std::vector<float> obs3 = fisheye_obs3(nE, eObs2, eRight);
   const Rig rig = make_rig(camL8, camR8, Trl7);
   return ba_problem_create(o, out, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, 0.f, 0.f, 0.f, 0.f, 0.f,
                            lambdaInit100, &rig, arena);
@@ -1615,64 +1667,18 @@ int morb_ba_solve(morb_ba_problem* p, void* stream) {
     MORB_HIP_CHECK(hipGetLastError());
     return MORB_OK;
   }
+  // ---- grid mode, LM control flow on the device: a slot is one trial (its seven launches as one hipGraph: 0.89 -> 0.95 ms per solve, profiles/r04/README.md) ----
   const BaDev& h = p->h;
   const BaDev* d = p->d_desc;
-  const int rb = p->redBlocks;
-  double* part0 = h.redPart;
-  double* part1 = h.redPart + rb;
-  {
-    // ---- grid mode, LM control flow on the device: the host queues trial after trial, one trial ahead of the decisions, and
-    // stops when the mapped `done` word says so; kernels queued behind the last decision return at once ----
-    const int kfBlocks = div_up(std::max(h.nChunks, 1), 4);
-    volatile int* hostw = p->h_stop;
-    auto forwardStop = [&]() { if (p->userStop && *p->userStop) __atomic_store_n(p->h_stop + 1, 1, __ATOMIC_RELEASE); };
-    __atomic_store_n(p->h_stop + 1, 0, __ATOMIC_RELAXED);
-    for (int k = 4; k < 8; ++k) __atomic_store_n(p->h_stop + k, 0, __ATOMIC_RELAXED);
-    forwardStop();
-    hipLaunchKernelGGL(k_g_chi2, dim3(rb), dim3(GB), 0, st, d, part0, (const double*)part1, 2);
-    constexpr int kAhead = 1;   // trials queued beyond the last decided one (the seven launches of a trial as one hipGraph: 0.89 -> 0.95 ms per solve, profiles/r04/README.md)
-    for (int slot = 0; slot < 100; ++slot) {
-      // buildSystem (runs only when the previous trial was accepted): keyframe chunks and map points in one launch
-      if (h.rig) hipLaunchKernelGGL(k_g_build<true>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, d, kfBlocks);
-      else hipLaunchKernelGGL(k_g_build<false>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, d, kfBlocks);
-      hipLaunchKernelGGL(k_g_dinv_push, dim3(rb > div_up(h.P * h.P, GB) ? rb : div_up(h.P * h.P, GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 0, 1);
-      hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(p->schur.nblk, p->schur.nsplit), dim3(64), 0, st, (const double*)h.sWD,
-                         (const double*)h.sW, p->schur.Mp, p->schur.ksteps, p->schur.stepsPerSplit, h.sBlocks, h.sPart, (const int*)(h.lmi + LM_DONE));
-      hipLaunchKernelGGL(k_g_schur_finish, dim3(div_up(4 * (h.P * h.P + h.P), GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 1);
-      if (p->denseLds) hipLaunchKernelGGL(k_g_ldlt_lds, dim3(1), dim3(morbdense::LT), p->denseLds, st, d, (const double*)h.HsG, 1);
-      else hipLaunchKernelGGL(k_g_ldlt_global, dim3(1), dim3(morbdense::GT), p->globalLds, st, d, h.HsG, p->d_ldws, p->panelInLds, 1);
-      hipLaunchKernelGGL(k_g_backsub_update_w, dim3(rb), dim3(GB), 0, st, d, part1);
-      hipLaunchKernelGGL(k_g_chi2, dim3(rb), dim3(GB), 0, st, d, part0, (const double*)part1, 1);
-      MORB_HIP_CHECK(hipGetLastError());
-      // wait until all but the last kAhead queued trials are decided (or the solve is done) on the mapped host words, backing off in tiers: a
-      // trial takes ~110 us, so the first ~30 us are `pause` spins (the decision of a short trial is picked up at once), then the thread yields
-      // its core between looks (LocalMapping's thread no longer holds a core against Tracking's for the whole solve), and a wait that outlasts
-      // 2 ms — a solve stuck behind other work on the device — sleeps 50 us at a time
-      unsigned spins = 0;
-      const auto tWait = std::chrono::steady_clock::now();
-      while (!__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 4, __ATOMIC_ACQUIRE) < slot + 1 - kAhead) {
-        forwardStop();
-        if ((++spins & 0x3FFu) == 0) {
-          const hipError_t q = hipStreamQuery(st);
-          if (q == hipSuccess) break;   // (everything queued has run: the words are final)
-          if (q != hipErrorNotReady) {  // a kernel fault: the words will never change
-            set_error("LocalBundleAdjustment: %s while waiting for the LM decision", hipGetErrorString(q));
-            return MORB_ERR_HIP;
-          }
-        }
-        if (spins < 2048) __builtin_ia32_pause();
-        else if ((spins & 0xFF) != 0 || std::chrono::steady_clock::now() - tWait < std::chrono::milliseconds(2)) sched_yield();
-        else { struct timespec ts = {0, 50000}; nanosleep(&ts, nullptr); }
-      }
-      if (__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE)) break;
-    }
-    hipLaunchKernelGGL(k_g_finish, dim3(rb), dim3(GB), 0, st, d, -1, -1);
-    MORB_HIP_CHECK(hipGetLastError());
-    // slot limit reached without a `done`: decisions of this solve may still be on their way — let them land before the next solve resets
-    // the mirror words (the usual exit has seen `done`, after which no kernel writes them)
-    if (!__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE)) MORB_HIP_CHECK(hipStreamSynchronize(st));
-    return MORB_OK;
-  }
+  const int rb = p->redBlocks, kfBlocks = div_up(std::max(h.nChunks, 1), 4);
+  return ba_queue_solve(p, st, 100, "LocalBundleAdjustment", [&](int slot) {
+    if (!slot) hipLaunchKernelGGL(k_g_chi2, dim3(rb), dim3(GB), 0, st, d, h.redPart, (const double*)(h.redPart + rb), 2);   // the first chi2 and lambda
+    // buildSystem (runs only when the previous trial was accepted): keyframe chunks and map points in one launch
+    if (h.rig) hipLaunchKernelGGL(k_g_build<true>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, d, kfBlocks);
+    else hipLaunchKernelGGL(k_g_build<false>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, d, kfBlocks);
+    ba_launch_solve_phases(p, st);
+    hipLaunchKernelGGL(k_g_chi2, dim3(rb), dim3(GB), 0, st, d, h.redPart, (const double*)(h.redPart + rb), 1);
+  }, [&]() { hipLaunchKernelGGL(k_g_finish, dim3(rb), dim3(GB), 0, st, d, -1, -1); });
 }
 
 int morb_ba_schur_profile(morb_ba_problem* p, int iters, float* msPerLaunch, double* flops, double* usefulFlops) {
@@ -1704,9 +1710,7 @@ int morb_ba_results(morb_ba_problem* p, float* kfPose, float* mpPos, uint8_t* er
   // (a copy on the null stream would also wait for, and hold up, every other handle's blocking stream)
   if (p->solved) MORB_HIP_CHECK(hipEventSynchronize(p->solved));
   hipStream_t st = p->opt->stream;
-  if (kfPose) MORB_HIP_CHECK(hipMemcpyAsync(kfPose, p->h.poseIO, sizeof(float) * 7 * p->h.nKF, hipMemcpyDeviceToHost, st));
-  if (mpPos) MORB_HIP_CHECK(hipMemcpyAsync(mpPos, p->h.ptIO, sizeof(float) * 3 * p->h.nMP, hipMemcpyDeviceToHost, st));
-  if (eraseFlag) MORB_HIP_CHECK(hipMemcpyAsync(eraseFlag, p->h.erase, p->h.nE, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(ba_queue_results(p, st, kfPose, mpPos, eraseFlag));
   if (stats2) MORB_HIP_CHECK(hipMemcpyAsync(stats2, p->h.stats, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
   MORB_HIP_CHECK(hipStreamSynchronize(st));
   return MORB_OK;
@@ -1747,66 +1751,28 @@ int morb_local_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPo
 static int merge_ba_solve(morb_ba_problem* p, const MergeDev& mh) {
   MORB_ENTER(st, p->opt, nullptr);
   const BaDev& h = p->h;
-  const BaDev* d = p->d_desc;
   const MergeDev* dm = reinterpret_cast<const MergeDev*>(p->d_desc);   // (its first member is the BaDev the shared phase kernels read)
   const int rb = p->redBlocks;
-  double* part0 = h.redPart;
-  double* part1 = h.redPart + rb;
   const int n = std::max(h.nKF, h.nMP * 3);
   hipLaunchKernelGGL(k_ba_reset, dim3(div_up(n, 256)), dim3(256), 0, st, p->h, p->d_pose0, p->d_pt0);
   hipLaunchKernelGGL(k_mg_reset, dim3(1), dim3(64), 0, st, mh);
   const int kfBlocks = div_up(std::max(h.nChunks, 1), 4);
-  volatile int* hostw = p->h_stop;
-  auto forwardStop = [&]() { if (p->userStop && *p->userStop) __atomic_store_n(p->h_stop + 1, 1, __ATOMIC_RELEASE); };
-  __atomic_store_n(p->h_stop + 1, 0, __ATOMIC_RELAXED);
-  for (int k = 4; k < 8; ++k) __atomic_store_n(p->h_stop + k, 0, __ATOMIC_RELAXED);
-  forwardStop();
-  hipLaunchKernelGGL(k_mg_chi2, dim3(rb), dim3(GB), 0, st, dm, part0, (const double*)part1, 2);
-  constexpr int kAhead = 1;
   // a slot is one trial, or the hand-over between the rounds: at most 5 x 10 trials, the hand-over, 10 x 10 trials
-  for (int slot = 0; slot < 160; ++slot) {
+  return ba_queue_solve(p, st, 160, "merge LocalBundleAdjustment", [&](int slot) {
+    if (!slot) hipLaunchKernelGGL(k_mg_chi2, dim3(rb), dim3(GB), 0, st, dm, h.redPart, (const double*)(h.redPart + rb), 2);
     if (h.rig) hipLaunchKernelGGL(k_mg_build<true>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, dm, kfBlocks);
     else hipLaunchKernelGGL(k_mg_build<false>, dim3(kfBlocks + div_up(h.nMP, GB / MP_LANES)), dim3(GB), 0, st, dm, kfBlocks);
-    hipLaunchKernelGGL(k_g_dinv_push, dim3(rb > div_up(h.P * h.P, GB) ? rb : div_up(h.P * h.P, GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 0, 1);
-    hipLaunchKernelGGL(morbschur::k_schur_mfma, dim3(p->schur.nblk, p->schur.nsplit), dim3(64), 0, st, (const double*)h.sWD,
-                       (const double*)h.sW, p->schur.Mp, p->schur.ksteps, p->schur.stepsPerSplit, h.sBlocks, h.sPart, (const int*)(h.lmi + LM_DONE));
-    hipLaunchKernelGGL(k_g_schur_finish, dim3(div_up(4 * (h.P * h.P + h.P), GB)), dim3(GB), 0, st, d, 0.0, h.HsG, 1);
-    if (p->denseLds) hipLaunchKernelGGL(k_g_ldlt_lds, dim3(1), dim3(morbdense::LT), p->denseLds, st, d, (const double*)h.HsG, 1);
-    else hipLaunchKernelGGL(k_g_ldlt_global, dim3(1), dim3(morbdense::GT), p->globalLds, st, d, h.HsG, p->d_ldws, p->panelInLds, 1);
-    hipLaunchKernelGGL(k_g_backsub_update_w, dim3(rb), dim3(GB), 0, st, d, part1);
-    hipLaunchKernelGGL(k_mg_chi2, dim3(rb), dim3(GB), 0, st, dm, part0, (const double*)part1, 1);
-    MORB_HIP_CHECK(hipGetLastError());
-    unsigned spins = 0;   // (the wait of morb_ba_solve)
-    const auto tWait = std::chrono::steady_clock::now();
-    while (!__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE) && __atomic_load_n(hostw + 4, __ATOMIC_ACQUIRE) < slot + 1 - kAhead) {
-      forwardStop();
-      if ((++spins & 0x3FFu) == 0) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) {
-          set_error("merge LocalBundleAdjustment: %s while waiting for the LM decision", hipGetErrorString(q));
-          return MORB_ERR_HIP;
-        }
-      }
-      if (spins < 2048) __builtin_ia32_pause();
-      else if ((spins & 0xFF) != 0 || std::chrono::steady_clock::now() - tWait < std::chrono::milliseconds(2)) sched_yield();
-      else { struct timespec ts = {0, 50000}; nanosleep(&ts, nullptr); }
-    }
-    if (__atomic_load_n(hostw + 5, __ATOMIC_ACQUIRE)) break;
-  }
-  hipLaunchKernelGGL(k_mg_finish, dim3(rb), dim3(GB), 0, st, dm);
-  MORB_HIP_CHECK(hipGetLastError());
-  return MORB_OK;
+    ba_launch_solve_phases(p, st);
+    hipLaunchKernelGGL(k_mg_chi2, dim3(rb), dim3(GB), 0, st, dm, h.redPart, (const double*)(h.redPart + rb), 1);
+  }, [&]() { hipLaunchKernelGGL(k_mg_finish, dim3(rb), dim3(GB), 0, st, dm); });
 }
 
 static int merge_ba_once(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos, int nE, const int* eKF,
                          const int* eMP, const float* eObs3, const float* eInvSigma2, const Cam& cam, const Rig* rig, const uint8_t* stopFlag,
                          uint8_t* eraseFlag, uint8_t* levelFlag, int* stats6) {
-  // (ba_problem_create's checks, ahead of the stop flag: a refused call is refused whatever the flag says, and before any upload or launch)
-  MORB_REQUIRE(o && kfPose && kfFixed && mpPos && eKF && eMP && eObs3 && eInvSigma2 && eraseFlag && stats6, MORB_ERR_INVALID, "NULL argument");
-  MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0, MORB_ERR_INVALID, "empty problem");
-  for (int e = 0; e < nE; ++e)
-    MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
+  // (ahead of the stop flag: a refused call is refused whatever the flag says, and before any upload or launch)
+  MORB_REQUIRE(eraseFlag && stats6, MORB_ERR_INVALID, "NULL argument");
+  if (const int rc = ba_check_graph(o, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, eObs3, eInvSigma2)) return rc;
   if (stopFlag && *(const volatile uint8_t*)stopFlag) {   // :3650-3651: nothing is optimised, nothing written
     for (int k = 0; k < 6; ++k) stats6[k] = 0;
     return MORB_OK;
@@ -1822,9 +1788,7 @@ static int merge_ba_once(morb_optimizer* o, int nKF, float* kfPose, const uint8_
   rc = merge_ba_solve(p, mh);
   hipStream_t st = o->stream;
   if (rc == MORB_OK) {
-    hipError_t e = hipMemcpyAsync(kfPose, p->h.poseIO, sizeof(float) * 7 * nKF, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(mpPos, p->h.ptIO, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(eraseFlag, p->h.erase, nE, hipMemcpyDeviceToHost, st);
+    hipError_t e = ba_queue_results(p, st, kfPose, mpPos, eraseFlag);
     if (e == hipSuccess && levelFlag) e = hipMemcpyAsync(levelFlag, mh.level, nE, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(stats6, mh.stats6, sizeof(int) * 6, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1846,9 +1810,8 @@ int morb_merge_bundle_adjustment_fisheye(morb_optimizer* o, int nKF, float* kfPo
                                          const uint8_t* stopFlag, uint8_t* eraseFlag, uint8_t* levelFlag, int* stats6) {
   MORB_REQUIRE(eObs2 && camL8, MORB_ERR_INVALID, "NULL argument");
   MORB_REQUIRE(nE > 0, MORB_ERR_INVALID, "empty problem");
-  // every edge is an EdgeSE3ProjectXYZ with pKF->mpCamera, the left KB8 camera (:3582-3602): kind -2 in the third observation slot
-  std::vector<float> obs3((size_t)nE * 3);
-  for (int e = 0; e < nE; ++e) { obs3[3 * e] = eObs2[2 * e]; obs3[3 * e + 1] = eObs2[2 * e + 1]; obs3[3 * e + 2] = -2.0f; }
+  // every edge is an EdgeSE3ProjectXYZ with pKF->mpCamera, the left KB8 camera (:3582-3602)
+  const std::vector<float> obs3 = fisheye_obs3(nE, eObs2, nullptr);
   const float Trl7[7] = {0, 0, 0, 1, 0, 0, 0};   // (no right-camera edge reads the second camera or mTrl)
   const Rig rig = make_rig(camL8, camL8, Trl7);
   return merge_ba_once(o, nKF, kfPose, kfFixed, nMP, mpPos, nE, eKF, eMP, obs3.data(), eInvSigma2, Cam{0.f, 0.f, 0.f, 0.f, 0.f}, &rig, stopFlag,

@@ -1,13 +1,19 @@
-// Host build of morb_slam_amd/csrc/ba_host.h (the two bundle adjusters' shared host side) for tests/test_ba_host_cpu.py, a program of
+// Host build of morb_slam_amd/csrc/ba_host.h (the bundle adjusters' shared host side) for tests/test_ba_host_cpu.py, a program of
 // its own so that it can run under sanitizers.  The carver works on heap blocks of exactly the sizes it reports, so a write or a read
 // outside them is AddressSanitizer's to find.  The graph lists are compared with a restatement, written here, of the loops the two
 // adjusters had before the header: the vector-of-vectors form of LocalInertialBA and the full CSR with chunk offsets of LocalBA.
+// The slot queue (lm_slot_queue) runs against a std::thread that plays the device: it "decides" the slots the host has queued by writing
+// the two mirror words with release stores, so ThreadSanitizer (a second build of this program) sees the same accesses as the real words get.
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
 #include <random>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "ba_host.h"
@@ -190,14 +196,145 @@ static void block_list_sweep() {
   }
 }
 
-int main() {
+// ---- lm_slot_queue ----
+struct Words {
+  int decided = 0, done = 0, stop = 0;   // the mapped words: the device's two, and the stop flag the host forwards
+  std::atomic<int> queued{0};            // slots the host has launched
+  std::atomic<bool> quit{false};
+};
+static void put(int* w, int v) { __atomic_store_n(w, v, __ATOMIC_RELEASE); }
+static int get(const int* w) { return __atomic_load_n(w, __ATOMIC_ACQUIRE); }
+
+// The device: decides the queued slots in order, each after usPerSlot; the decision of slot doneAt (if it is ever queued) raises `done`,
+// as the real decision kernels do: `done` first, then the count with release.  decides == false: it only watches the forwarded stop flag,
+// which raises `done` in either mode.
+static void device(Words& w, int doneAt, int usPerSlot, bool decides = true) {
+  for (int ran = 0; !w.quit.load();) {
+    if (get(&w.stop)) { put(&w.done, 1); return; }
+    if (!decides || ran >= w.queued.load()) { std::this_thread::yield(); continue; }
+    if (usPerSlot) std::this_thread::sleep_for(std::chrono::microseconds(usPerSlot));
+    if (ran == doneAt) put(&w.done, 1);
+    put(&w.decided, ++ran);
+    if (ran - 1 == doneAt) return;
+  }
+}
+
+struct QueueRun {
+  int ret = 0, looks = 0, sleeps = 0, queuedAtFailedLook = -1;
+  long ticks = 0;
+  std::vector<int> decidedSeen, idleSeen;   // per queued slot: `decided` as queueSlot read it, and whether the last look() before it said Idle
+};
+
+// the host: lm_slot_queue over w with `look` (called with the number of looks so far) and `tick`; queueSlot reports -7 at slot failAt
+template <class Look, class Tick>
+static QueueRun run_queue(Words& w, int maxSlots, Look&& look, Tick&& tick, int failAt = -1) {
+  QueueRun r;
+  bool idle = false;
+  r.ret = lm_slot_queue(maxSlots, &w.decided, &w.done, [&](int slot) {
+    CHECK(slot == (int)r.decidedSeen.size());
+    r.decidedSeen.push_back(get(&w.decided)); r.idleSeen.push_back(idle); idle = false;
+    w.queued.store(slot + 1);
+    return slot == failAt ? 7 : 0;   // (a positive code: the queue reports it negative)
+  }, [&]() {
+    const StreamLook q = look(r.looks++);
+    idle = q == StreamLook::Idle;
+    if (q == StreamLook::Failed) r.queuedAtFailedLook = w.queued.load();
+    return q;
+  }, [&]() { ++r.ticks; tick(); }, &r.sleeps);
+  CHECK(r.ticks >= 1024L * r.looks);   // tick() before every look at the words, look() at every 1024th
+  // no slot s + 1 was queued while decided < s, `done` was clear (the queue would have returned) and the stream was busy
+  for (size_t s = 1; s < r.decidedSeen.size(); ++s) CHECK(r.decidedSeen[s] >= (int)s - 1 || r.idleSeen[s]);
+  return r;
+}
+
+static void queue_sweep() {
+  const int maxSlots = 6;
+  const auto busy = [](int) { return StreamLook::Busy; };
+  const auto noTick = []() {};
+  // 1. the decision of slot k raises `done`, behind k decided slots, at three device speeds.  The host is one slot ahead, so slots k and
+  // perhaps k + 1 are queued.  k = maxSlots - 1: the last slot's decision is not waited for (the host only waits for the one before it), so
+  // the queue may end with 0 — then `done` is on its way, which is what the callers' drain is for.  k = maxSlots: that slot does not exist.
+  for (int us : {0, 20, 300})
+    for (int k = 0; k <= maxSlots; ++k) {
+      ++cases;
+      Words w;
+      std::thread dev(device, std::ref(w), k, us, true);
+      const QueueRun r = run_queue(w, maxSlots, busy, noTick);
+      if (k < maxSlots - 1) CHECK(r.ret == 1);
+      else CHECK(k == maxSlots ? r.ret == 0 : r.ret == 0 || r.ret == 1);
+      CHECK((int)r.decidedSeen.size() >= std::min(k + 1, maxSlots) && (int)r.decidedSeen.size() <= std::min(k + 2, maxSlots));
+      for (size_t s = 0; s < r.idleSeen.size(); ++s) CHECK(!r.idleSeen[s]);
+      if (us == 300 && k >= 2) CHECK(r.ticks >= k - 1);   // every wait but the last had to look more than once
+      if (k == maxSlots) w.quit.store(true);   // 2. `done` never set: exactly maxSlots slots
+      dev.join();
+      CHECK(get(&w.done) == (k < maxSlots));
+    }
+  {   // 3. the stream fails at the first look: the queue returns although the words never change, and queues nothing more
+    ++cases;
+    Words w;
+    const QueueRun r = run_queue(w, maxSlots, [](int) { return StreamLook::Failed; }, noTick);
+    CHECK(r.ret < 0 && r.looks == 1 && r.queuedAtFailedLook == 2 && w.queued.load() == 2);   // (slot 0 is not waited for: one ahead)
+  }
+  {   // 4. an idle stream without a decision: the queue goes on to the limit ...
+    ++cases;
+    Words w;
+    const QueueRun r = run_queue(w, maxSlots, [](int) { return StreamLook::Idle; }, noTick);
+    CHECK(r.ret == 0 && (int)r.decidedSeen.size() == maxSlots && r.looks == maxSlots - 1);
+    for (size_t s = 2; s < r.idleSeen.size(); ++s) CHECK(r.idleSeen[s] && r.decidedSeen[s] == 0);
+  }
+  {   // ... or to `done`: the second look finds the stream idle, the device then decides what is queued and slot 3 is the last
+    ++cases;
+    Words w;
+    std::thread dev;
+    const QueueRun r = run_queue(w, maxSlots, [&](int looks) {
+      if (looks == 1) dev = std::thread(device, std::ref(w), 3, 0, true);
+      return looks < 2 ? StreamLook::Idle : StreamLook::Busy;
+    }, noTick);
+    dev.join();
+    CHECK(r.ret == 1 && r.decidedSeen.size() >= 4 && r.decidedSeen.size() <= 5 && r.idleSeen[2] && r.idleSeen[3]);
+  }
+  {   // 5. a launch error at slot 2: three calls, its code negative
+    ++cases;
+    Words w;
+    std::thread dev(device, std::ref(w), -1, 0, true);
+    const QueueRun r = run_queue(w, maxSlots, busy, noTick, 2);
+    w.quit.store(true);
+    dev.join();
+    CHECK(r.ret == -7 && r.decidedSeen.size() == 3);
+  }
+  {   // 6. a stop the caller raises during a wait reaches the device through tick() before the wait ends: nothing else can end it
+    ++cases;
+    Words w;
+    std::atomic<int> callerStop{0};
+    std::thread dev(device, std::ref(w), -1, 0, false);
+    std::thread caller([&]() { std::this_thread::sleep_for(std::chrono::milliseconds(1)); callerStop.store(1); });
+    const QueueRun r = run_queue(w, maxSlots, busy, [&]() { if (callerStop.load()) put(&w.stop, 1); });
+    caller.join(); dev.join();
+    CHECK(r.ret == 1 && r.decidedSeen.size() == 2 && get(&w.decided) == 0 && r.ticks >= 1);
+  }
+  {   // 7. a decision that takes 5 ms, past the 2 ms tier, is still picked up, from the sleeping tier
+    ++cases;
+    Words w;
+    std::thread dev(device, std::ref(w), 1, 5000, true);
+    const QueueRun r = run_queue(w, maxSlots, busy, noTick);
+    dev.join();
+    CHECK(r.ret == 1 && r.sleeps >= 1 && r.decidedSeen.size() >= 2 && r.decidedSeen.size() <= 3);
+  }
+}
+
+// "queue" as the only argument: the slot queue's cases alone (the ThreadSanitizer build: the other sweeps have one thread)
+int main(int argc, char** argv) {
+  const bool all = !(argc == 2 && std::string(argv[1]) == "queue");
   std::mt19937 rng(20240611);
-  carver_sweep(rng);
+  if (all) carver_sweep(rng);
   const long carverCases = cases;
-  graph_sweep(rng);
+  if (all) graph_sweep(rng);
   const long graphCases = cases - carverCases;
-  block_list_sweep();
-  std::printf("carver cases %ld, graph cases %ld, block-list cases %ld\n", carverCases, graphCases, cases - carverCases - graphCases);
+  if (all) block_list_sweep();
+  const long blockCases = cases - carverCases - graphCases;
+  queue_sweep();
+  std::printf("carver cases %ld, graph cases %ld, block-list cases %ld, queue cases %ld\n", carverCases, graphCases, blockCases,
+              cases - carverCases - graphCases - blockCases);
   std::printf("cases %ld\nmismatches %ld\n", cases, bad);
   return bad ? 1 : 0;
 }
