@@ -124,6 +124,28 @@ struct MergeBAView {
   std::vector<uint8_t> levelFlag;   // out [nE]: edges put on level 1 between the rounds (:3662-3690)
   int stats[6] = {0, 0, 0, 0, 0, 0};   // out: as morb_merge_bundle_adjustment's stats6
 };
+// The graph Optimizer::MergeInertialBA assembles (Optimizer.cc:3985-4272), flattened as morb_merge_inertial_ba takes it.
+struct MergeInertialBAView {
+  int nKF = 0, nMP = 0, nE = 0, nI = 0;
+  float* kfState = nullptr;            // [nKF][21] in / out: Rwb row-major, twb, velocity, gyro bias, acc bias (kind 0: all; kind 3: Rwb, twb only)
+  const uint8_t* kfKind = nullptr;     // [nKF] 0 free, 15 unknowns (vpOptimizableKFs and the head of the current chain, vpOptimizableCovKFs[0]);
+                                       //       1 fixed with an IMU state that enters a link (lFixedKeyFrames); 2 fixed observer;
+                                       //       3 free in the pose only (the further vpOptimizableCovKFs, and keyframes with !bImu)
+  float* mpPos = nullptr;              // [nMP][3] in / out
+  const int* eKF = nullptr;            // [nE]
+  const int* eMP = nullptr;            // [nE]
+  const float* eObs = nullptr;         // [nE][3] (x, y, uRight or < 0); with rig28 every edge is an EdgeMono(0) and the third slot is not read
+  const float* eInvSigma2 = nullptr;   // [nE]
+  const int* iKF1 = nullptr;           // [nI] mPrevKF of the link's keyframe (kind 0 or 1)
+  const int* iKF2 = nullptr;           // [nI] the keyframe owning iPre[i] (kind 0 or 1)
+  const morb_imu_preintegrated* iPre = nullptr;   // [nI] mpImuPreintegrated, after SetNewBias(mPrevKF->GetImuBias()) (:4092)
+  float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  const float* rig28 = nullptr;        // KannalaBrandt8 rig (as LocalInertialBAView::rig28); this function makes left-camera edges only
+  float Tbc12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  std::vector<uint8_t> eraseFlag;      // out [nE]: observations the reference erases (:4287-4310)
+  int outerIterations = 0, lmTrials = 0;
+  bool ran = false;                    // false: *pbStopFlag was set at entry (:4276), nothing written
+};
 
 // What Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) reads and writes
 // (Optimizer.cc:2065-2322), per KF1 feature i < N as morb_optimize_sim3_batch (include/morb_hip.h) takes it: entry bits (matched, pMP1
@@ -269,6 +291,26 @@ class Optimizer {
     g.outerIterations = stats[0]; g.lmTrials = stats[1]; g.ok = stats[2] != 0;
   }
 
+  // void static MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbStopFlag, Map* pMap, LoopClosing::KeyFrameAndPose& corrPoses)
+  // Optimizer.h:110-112: the welding bundle adjustment of an inertial map merge (LoopClosing.cc:1649-1650, :2099), on the loop-closing handle.
+  // pbStopFlag is the caller's own bool, read at entry and polled at every LM iteration and trial.
+  static void MergeInertialBA(MergeInertialBAView& g, bool* pbStopFlag, int device = 0) {
+    static_assert(sizeof(bool) == 1, "pbStopFlag is read as one byte");
+    g.eraseFlag.assign(g.nE, 0);
+    int stats[3] = {0, 0, 0};
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    const uint8_t* stop = reinterpret_cast<const uint8_t*>(pbStopFlag);
+    if (g.rig28)
+      check(morb_merge_inertial_ba_fisheye(o.h, g.nKF, g.kfState, g.kfKind, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.nI, g.iKF1, g.iKF2,
+                                           g.iPre, g.rig28, g.Tbc12, stop, g.eraseFlag.data(), stats));
+    else
+      check(morb_merge_inertial_ba(o.h, g.nKF, g.kfState, g.kfKind, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.nI, g.iKF1, g.iKF2, g.iPre,
+                                   g.fx, g.fy, g.cx, g.cy, g.mbf, g.Tbc12, stop, g.eraseFlag.data(), stats));
+    g.outerIterations = stats[0]; g.lmTrials = stats[1]; g.ran = stats[2] != 0;
+  }
+
   // void static InertialOptimization(Map*, ...)  Optimizer.h:103-112 in its three overloads: mode 0 = (Rwg, scale, bg, ba, bMono, covInertial,
   // bFixedVel, bGauss, priorG, priorA), 1 = (bg, ba, priorG, priorA), 2 = (Rwg, scale).  One problem through morb_inertial_optimization_batch:
   // modes 0 and 2 (LocalMapping) on the mapping handle, mode 1 (LoopClosing's merge) on the loop-closing handle.
@@ -398,6 +440,9 @@ class Optimizer {
   template <class KF, class MapT>
   static void LocalInertialBA(KF* pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges, bool bLarge = false,
                               bool bRecInit = false);
+  // (include/Optimizer.h:110-112; call sites LoopClosing.cc:1649-1650, :2099)
+  template <class KF, class MapT, class CorrMap>
+  static void MergeInertialBA(KF* pCurrKF, KF* pMergeKF, bool* pbStopFlag, MapT* pMap, CorrMap& corrPoses);
   template <class KF, class MP, class Sim3T, class Mat77>
   static int OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale, Mat77& mAcumHessian,
                           const bool bAllPoints = false);

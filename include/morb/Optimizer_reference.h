@@ -858,6 +858,232 @@ void Optimizer::LocalBundleAdjustment(KF* pMainKF, std::vector<KF*> vpAdjustKF, 
   }
 }
 
+// void Optimizer::MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbStopFlag, Map* pMap, LoopClosing::KeyFrameAndPose& corrPoses)
+// Optimizer.cc:3853-4389, the welding bundle adjustment of an inertial map merge (call sites LoopClosing.cc:1649-1650, :2099).  The window
+// and covisible selection with its marks (:3856-3983), flattened: the 15-unknown keyframes are vpOptimizableKFs and vpOptimizableCovKFs[0]
+// when a link hangs on it (kind 0), the further covisible keyframes and every keyframe with !bImu are free in the pose only (kind 3), the
+// one keyframe of lFixedKeyFrames is kind 1 (kind 2 without an IMU state).  The erase list, poses, velocities, biases, corrPoses and the
+// points are written back under mMutexMapUpdate.  CorrMap = LoopClosing::KeyFrameAndPose (a map from KeyFrame* to g2o::Sim3).
+template <class KF, class MapT, class CorrMap>
+void Optimizer::MergeInertialBA(KF* pCurrKF, KF* pMergeKF, bool* pbStopFlag, MapT* pMap, CorrMap& corrPoses) {
+  using SE3 = typename std::decay<decltype(pCurrKF->GetPose())>::type;
+  using MP = typename std::remove_pointer<typename std::decay<decltype(pCurrKF->GetMapPointMatches()[0])>::type>::type;
+  using Bias = typename std::decay<decltype(pCurrKF->GetImuBias())>::type;
+  using Sim3T = typename CorrMap::mapped_type;
+  const int Nd = 6;                                                                     // :3856
+  const unsigned long maxKFid = pCurrKF->mnId;
+  const auto id = pCurrKF->mnId;
+  std::vector<KF*> vpOptimizableKFs, vpOptimizableCovKFs;
+  vpOptimizableKFs.reserve(2 * Nd);
+  const int maxCovKF = 30;                                                              // :3864
+  vpOptimizableCovKFs.reserve(maxCovKF);
+  vpOptimizableKFs.push_back(pCurrKF);                                                  // :3869-3877: the current keyframe's window
+  pCurrKF->mnBALocalForKF = id;
+  for (int i = 1; i < Nd; i++) {
+    if (vpOptimizableKFs.back()->mPrevKF) {
+      vpOptimizableKFs.push_back(vpOptimizableKFs.back()->mPrevKF);
+      vpOptimizableKFs.back()->mnBALocalForKF = id;
+    } else break;
+  }
+  std::list<KF*> lFixedKeyFrames;                                                       // :3879-3886: the head of the current chain
+  if (vpOptimizableKFs.back()->mPrevKF) {
+    vpOptimizableCovKFs.push_back(vpOptimizableKFs.back()->mPrevKF);
+    vpOptimizableKFs.back()->mPrevKF->mnBALocalForKF = id;
+  } else {
+    vpOptimizableCovKFs.push_back(vpOptimizableKFs.back());
+    vpOptimizableKFs.pop_back();
+  }
+  vpOptimizableKFs.push_back(pMergeKF);                                                 // :3889-3899: the merge keyframe and its predecessors
+  pMergeKF->mnBALocalForKF = id;
+  for (int i = 1; i < (Nd / 2); i++) {
+    if (vpOptimizableKFs.back()->mPrevKF) {
+      vpOptimizableKFs.push_back(vpOptimizableKFs.back()->mPrevKF);
+      vpOptimizableKFs.back()->mnBALocalForKF = id;
+    } else break;
+  }
+  if (vpOptimizableKFs.back()->mPrevKF) {                                               // :3902-3910: "we fix just once the old map"
+    lFixedKeyFrames.push_back(vpOptimizableKFs.back()->mPrevKF);
+    vpOptimizableKFs.back()->mPrevKF->mnBAFixedForKF = id;
+  } else {
+    vpOptimizableKFs.back()->mnBALocalForKF = 0;
+    vpOptimizableKFs.back()->mnBAFixedForKF = id;
+    lFixedKeyFrames.push_back(vpOptimizableKFs.back());
+    vpOptimizableKFs.pop_back();
+  }
+  if (pMergeKF->mNextKF) {                                                              // :3913-3924: its successors
+    vpOptimizableKFs.push_back(pMergeKF->mNextKF);
+    vpOptimizableKFs.back()->mnBALocalForKF = id;
+  }
+  while (vpOptimizableKFs.size() < (size_t)(2 * Nd)) {
+    if (vpOptimizableKFs.back()->mNextKF) {
+      vpOptimizableKFs.push_back(vpOptimizableKFs.back()->mNextKF);
+      vpOptimizableKFs.back()->mnBALocalForKF = id;
+    } else break;
+  }
+  int N = (int)vpOptimizableKFs.size();
+  std::list<MP*> lLocalMapPoints;                                                       // :3929-3950
+  std::map<MP*, int> mLocalObs;
+  for (int i = 0; i < N; i++)
+    for (MP* pMP : vpOptimizableKFs[i]->GetMapPointMatches())
+      if (pMP && !pMP->isBad()) {
+        if (pMP->mnBALocalForKF != id) { mLocalObs[pMP] = 1; lLocalMapPoints.push_back(pMP); pMP->mnBALocalForKF = id; }
+        else mLocalObs[pMP]++;
+      }
+  std::vector<std::pair<MP*, int>> pairs;                                               // :3952-3956
+  pairs.reserve(mLocalObs.size());
+  for (auto itr = mLocalObs.begin(); itr != mLocalObs.end(); ++itr) pairs.push_back(*itr);
+  std::sort(pairs.begin(), pairs.end(), [](const std::pair<MP*, int>& a, const std::pair<MP*, int>& b) { return a.second < b.second; });   // sortByVal (:43-45)
+  {                                                                                     // :3960-3983: one covisible keyframe per point, at most maxCovKF points
+    int i = 0;
+    for (auto lit = pairs.begin(), lend = pairs.end(); lit != lend; lit++, i++) {
+      auto observations = lit->first->GetObservations();
+      if (i >= maxCovKF) break;
+      for (auto mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+        KF* pKFi = mit->first;
+        if (pKFi->mnBALocalForKF != id && pKFi->mnBAFixedForKF != id) {
+          pKFi->mnBALocalForKF = id;
+          if (!pKFi->isBad()) { vpOptimizableCovKFs.push_back(pKFi); break; }
+        }
+      }
+    }
+  }
+  // inertial links (:4082-4150), found before the vertices so that a keyframe's width is known: a link needs bImu on both ends, the
+  // preintegration, and a vertex for its predecessor
+  std::map<KF*, int> kfIndex;
+  std::vector<KF*> kfs;
+  auto listed = [&](KF* k) {
+    if (std::find(vpOptimizableKFs.begin(), vpOptimizableKFs.end(), k) != vpOptimizableKFs.end()) return true;
+    if (std::find(vpOptimizableCovKFs.begin(), vpOptimizableCovKFs.end(), k) != vpOptimizableCovKFs.end()) return true;
+    return std::find(lFixedKeyFrames.begin(), lFixedKeyFrames.end(), k) != lFixedKeyFrames.end();
+  };
+  std::vector<std::pair<KF*, KF*>> links;
+  for (int i = 0; i < N; i++) {
+    KF* pKFi = vpOptimizableKFs[i];
+    if (!pKFi->mPrevKF) continue;
+    if (!(pKFi->bImu && pKFi->mPrevKF->bImu && pKFi->mpImuPreintegrated)) continue;
+    pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());                  // :4092
+    if (!listed(pKFi->mPrevKF)) continue;                                               // (:4108-4113: a vertex is missing)
+    links.emplace_back(pKFi->mPrevKF, pKFi);
+  }
+  auto linked = [&](KF* k) { for (const auto& l : links) if (l.first == k || l.second == k) return true; return false; };
+  // vertices (:4001-4076)
+  std::vector<float> kfState;
+  std::vector<uint8_t> kfKind;
+  auto add_kf = [&](KF* k, int kind) {
+    if (kfIndex.count(k)) return;   // (g2o refuses a second vertex with the same id)
+    kfIndex[k] = (int)kfs.size(); kfs.push_back(k);
+    float s[21];
+    morb_glue::imu_state21(k, s); morb_glue::bias6(k->GetImuBias(), s + 15);
+    kfState.insert(kfState.end(), s, s + 21);
+    kfKind.push_back((uint8_t)kind);
+  };
+  for (KF* k : vpOptimizableKFs) add_kf(k, k->bImu ? 0 : 3);
+  for (KF* k : vpOptimizableCovKFs) add_kf(k, k->bImu && linked(k) ? 0 : 3);   // (velocity and biases of the others carry no edge)
+  for (KF* k : lFixedKeyFrames) add_kf(k, k->bImu ? 1 : 2);
+  std::vector<int> iKF1, iKF2;
+  std::vector<morb_imu_preintegrated> iPre;
+  for (const auto& l : links) {
+    iKF1.push_back(kfIndex[l.first]); iKF2.push_back(kfIndex[l.second]);
+    iPre.emplace_back(); morb_glue::fill_pre(iPre.back(), l.second->mpImuPreintegrated);
+  }
+  // points and visual edges (:4185-4272)
+  std::vector<MP*> mps(lLocalMapPoints.begin(), lLocalMapPoints.end());
+  std::vector<float> mpPos, eObs, eInv;
+  std::vector<int> eKF, eMP;
+  std::vector<std::pair<KF*, MP*>> eOwner;
+  for (int j = 0; j < (int)mps.size(); ++j) {
+    MP* pMP = mps[j];
+    const auto X = pMP->GetWorldPos();
+    mpPos.push_back(X(0)); mpPos.push_back(X(1)); mpPos.push_back(X(2));
+    for (const auto& ob : pMP->GetObservations()) {
+      KF* pKFi = ob.first;
+      if (!pKFi) continue;
+      if (pKFi->mnBALocalForKF != id && pKFi->mnBAFixedForKF != id) continue;
+      if (pKFi->mnId > maxKFid) continue;                                               // :4214
+      const auto it = kfIndex.find(pKFi);
+      if (it == kfIndex.end() || pKFi->isBad()) continue;                               // :4218-4221
+      const int leftIndex = std::get<0>(ob.second);
+      if (leftIndex < 0) continue;   // (a right-camera-only observation: the reference indexes mvKeysUn[-1] there)
+      const auto& kpUn = pKFi->mvKeysUn[leftIndex];
+      eKF.push_back(it->second); eMP.push_back(j);
+      eObs.push_back(kpUn.pt.x); eObs.push_back(kpUn.pt.y); eObs.push_back(pKFi->mvuRight[leftIndex] < 0 ? -1.f : pKFi->mvuRight[leftIndex]);
+      eInv.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
+      eOwner.emplace_back(pKFi, pMP);
+    }
+  }
+  if (pbStopFlag && *pbStopFlag) return;                                                // :4276-4277
+  MergeInertialBAView g;
+  g.nKF = (int)kfs.size(); g.nMP = (int)mps.size(); g.nE = (int)eKF.size(); g.nI = (int)iKF1.size();
+  auto corr_of = [&](KF* pKFi) {   // corrPoses[pKFi] = g2o::Sim3(Tiw.unit_quaternion(), Tiw.translation(), 1.0) of the keyframe's float pose
+    using Quat = typename std::decay<decltype(std::declval<Sim3T>().rotation())>::type;
+    using Vec3 = typename std::decay<decltype(std::declval<Sim3T>().translation())>::type;
+    const auto Tiw = pKFi->GetPose();
+    const auto q = Tiw.unit_quaternion();
+    const auto t = Tiw.translation();
+    Vec3 tv;
+    for (int k = 0; k < 3; ++k) tv(k) = (double)t(k);
+    corrPoses[pKFi] = Sim3T(Quat((double)q.w(), (double)q.x(), (double)q.y(), (double)q.z()), tv, 1.0);
+  };
+  if (g.nMP == 0 || g.nE == 0) {   // no point, no edge: nothing for the device.  g2o optimises nothing there and the reference writes every estimate
+    // back as it stands — what a caller sees of that is corrPoses of every keyframe of the windows and the map's change index
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (KF* k : vpOptimizableKFs) corr_of(k);
+    for (KF* k : vpOptimizableCovKFs) corr_of(k);
+    pMap->IncreaseChangeIndex();
+    return;
+  }
+  g.kfState = kfState.data(); g.kfKind = kfKind.data(); g.mpPos = mpPos.data(); g.eKF = eKF.data(); g.eMP = eMP.data();
+  g.eObs = eObs.data(); g.eInvSigma2 = eInv.data();
+  const int noLink = 0; const morb_imu_preintegrated noPre{};
+  g.iKF1 = g.nI ? iKF1.data() : &noLink; g.iKF2 = g.nI ? iKF2.data() : &noLink; g.iPre = g.nI ? iPre.data() : &noPre;
+  g.fx = pCurrKF->fx; g.fy = pCurrKF->fy; g.cx = pCurrKF->cx; g.cy = pCurrKF->cy; g.mbf = pCurrKF->mbf;
+  morb_glue::tbc12(pCurrKF->mImuCalib.mTbc, g.Tbc12);
+  float rigp[28];
+  if (pCurrKF->mpCamera2) { morb_glue::rig28(pCurrKF, rigp); g.rig28 = rigp; }
+  MergeInertialBA(g, pbStopFlag);
+  if (!g.ran) return;                      // (the flag was raised between the check above and the entry's own)
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                             // :4313
+  for (size_t e = 0; e < eOwner.size(); ++e)                                            // :4287-4321
+    if (g.eraseFlag[e] && !eOwner[e].second->isBad()) {
+      eOwner[e].first->EraseMapPointMatch(eOwner[e].second);
+      eOwner[e].second->EraseObservation(eOwner[e].first);
+    }
+  // :4325-4375: Tcw = (Rcb Rwb^T, tcb - Rcb Rwb^T twb) (ImuCamPose, G2oTypes.cc:74-113), corrPoses, velocity, bias
+  float Tbc[12];
+  morb_glue::tbc12(pCurrKF->mImuCalib.mTbc, Tbc);
+  auto write_back = [&](KF* pKFi) {
+    const int row = kfIndex[pKFi];
+    const float* s = &kfState[(size_t)21 * row];
+    double Rcw[9], tcw[3];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) { double a = 0; for (int k = 0; k < 3; ++k) a += (double)Tbc[3 * k + r] * s[3 * c + k]; Rcw[3 * r + c] = a; }   // Rcb Rwb^T, Rcb = Rbc^T
+    for (int r = 0; r < 3; ++r) {
+      double a = 0;
+      for (int k = 0; k < 3; ++k) a -= (double)Tbc[3 * k + r] * Tbc[9 + k];            // tcb = -Rbc^T tbc
+      for (int c = 0; c < 3; ++c) a -= Rcw[3 * r + c] * s[9 + c];
+      tcw[r] = a;
+    }
+    pKFi->SetPose(se3_from_matrix<SE3>(Rcw, tcw));
+    corr_of(pKFi);   // (of the float pose just set)
+    if (pKFi->bImu && kfKind[row] == 0) {
+      typename std::decay<decltype(pKFi->GetVelocity())>::type vel;
+      for (int k = 0; k < 3; ++k) vel(k) = s[12 + k];
+      pKFi->SetVelocity(vel);
+      pKFi->SetNewBias(Bias(s[18], s[19], s[20], s[15], s[16], s[17]));
+    }
+    // (kind 3 with bImu: the reference writes the vertices' estimates back, which never left the keyframe's own velocity and bias)
+  };
+  for (KF* k : vpOptimizableKFs) write_back(k);
+  for (KF* k : vpOptimizableCovKFs) write_back(k);
+  for (int j = 0; j < (int)mps.size(); ++j) {                                           // :4378-4386
+    typename std::decay<decltype(mps[j]->GetWorldPos())>::type X;
+    for (int k = 0; k < 3; ++k) X(k) = mpPos[3 * j + k];
+    mps[j]->SetWorldPos(X);
+    mps[j]->UpdateNormalAndDepth();
+  }
+  pMap->IncreaseChangeIndex();                                                          // :4388
+}
+
 template <class SE3>
 SE3 Optimizer::se3_from_matrix(const double R[9], const double t[3]) {
   typename std::decay<decltype(std::declval<SE3>().rotationMatrix())>::type Rm;

@@ -1051,6 +1051,41 @@ int morb_merge_bundle_adjustment_fisheye(morb_optimizer*, int nKF, float* kfPose
                                          const float* camL8, const uint8_t* stopFlag, uint8_t* eraseFlag, uint8_t* levelFlag,
                                          int* stats6);
 
+/* void static Optimizer::MergeInertialBA(KeyFrame* pCurrKF, KeyFrame* pMergeKF, bool* pbStopFlag, Map* pMap,
+ * LoopClosing::KeyFrameAndPose& corrPoses)  Optimizer.h:110-112, Optimizer.cc:3853-4389: the welding bundle adjustment of an inertial map
+ * merge (LoopClosing::MergeLocal at LoopClosing.cc:1649-1650 for IMU_MONOCULAR / IMU_STEREO / IMU_RGBD, MergeLocal2 at :2099), on the graph
+ * the reference assembles at :3985-4272, flattened (HOST pointers) like morb_local_inertial_ba: nKF keyframes with states of 21 floats (Rwb
+ * row-major, twb, velocity, gyro bias, acc bias); kfKind[k]: 0 = free with 15 unknowns (vpOptimizableKFs, and vpOptimizableCovKFs[0], the
+ * head of the current map's chain, whose velocity and bias vertices hang on the first inertial edge), 1 = fixed with an IMU state that
+ * enters a link (lFixedKeyFrames, behind the merge map's chain), 2 = fixed keyframe that only observes points, 3 = free in the pose only,
+ * 6 unknowns (the further vpOptimizableCovKFs, and keyframes with !bImu: their velocity and bias vertices carry no edge, so g2o leaves them
+ * out of the active set).  nMP points, nE observations (eObs = x, y, uRight; uRight < 0 = EdgeMono(0), else EdgeStereo; information
+ * eInvSigma2 * I, Huber deltas (float)sqrt(5.991) / (float)sqrt(7.815)).  nI inertial links: iKF1 = mPrevKF, iKF2 = the keyframe owning
+ * iPre[i]; every link is an EdgeInertial with Huber delta sqrt(16.92) and its information unscaled (:4115-4128) plus EdgeGyroRW / EdgeAccRW
+ * (:4130-4146); the two temporal chains are told apart by nothing but their indices.  A link between two
+ * keyframes of kind 1 is taken as g2o takes an edge between fixed vertices: it moves nothing and adds its robust chi2, a constant, to every sum.  A link with an endpoint of kind 2 or 3, an index out
+ * of range, a NULL array (pbStopFlag may be NULL) or an empty graph: MORB_ERR_INVALID before any launch, nothing written.
+ * setUserLambdaInit(1e3), optimize(8) (:3995, :4280); no "FAIL" test.  pbStopFlag is the caller's flag itself (one byte): set at entry
+ * (:4276) the call returns MORB_OK with stats3 = {0, 0, 0} and nothing else written; it is polled at every LM iteration and trial (:4274).
+ * Outputs: kfState21 in place — all 21 floats of kind 0, the pose (Rwb, twb) of kind 3 whose velocity and bias floats keep their bytes, as
+ * do kinds 1 and 2 entirely; mpPos in place; eraseFlag[e] = 1 where the reference erases the observation (:4287-4310: chi2() > 5.991f,
+ * stereo 7.815f — no depth test, no mTrackDepth rule); stats3 = {outer LM iterations, LM trials, ran}.  The reduced system has 15 n15 +
+ * 6 n6 unknowns ("MergeInertialBA").  Left with the caller: the window selection (:3856-3983), SetNewBias on the
+ * preintegrations before the call (:4092) and on the keyframes after it, UpdateNormalAndDepth (:4385) and corrPoses (:4333-4335, :4359-4361)
+ * — include/morb/Optimizer_reference.h does all four on the reference's types. */
+int morb_merge_inertial_ba(morb_optimizer*, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
+                           int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                           int nI, const int* iKF1, const int* iKF2, const morb_imu_preintegrated* iPre,
+                           float fx, float fy, float cx, float cy, float bf, const float* Tbc12,
+                           const uint8_t* pbStopFlag, uint8_t* eraseFlag, int* stats3);
+/* The same on a KannalaBrandt8 rig (rig28 as morb_local_inertial_ba_fisheye takes it): every edge is an EdgeMono(0) on the left camera —
+ * this function creates no right-camera edge (:4224-4244); eObs = (x, y, unused). */
+int morb_merge_inertial_ba_fisheye(morb_optimizer*, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
+                                   int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                                   int nI, const int* iKF1, const int* iKF2, const morb_imu_preintegrated* iPre,
+                                   const float* rig28, const float* Tbc12,
+                                   const uint8_t* pbStopFlag, uint8_t* eraseFlag, int* stats3);
+
 #ifdef __cplusplus
 }
 #endif

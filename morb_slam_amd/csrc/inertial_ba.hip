@@ -3,6 +3,9 @@
 // inertial / random-walk edges.  g2o Levenberg-Marquardt semantics (optimization_algorithm_levenberg.cpp:61-194, block_solver.hpp) with
 // the control flow on the device, like the grid mode of LocalBundleAdjustment (local_ba.hip): the last workgroup of k_iba_errors takes a
 // trial's accept / reject decision (iba_lm_decide); the host queues trial slots one ahead and watches a mapped word (iba_lm_loop).
+// MergeInertialBA (:3853-4389), the welding bundle adjustment of an inertial map merge, is the same graph with another plan (IbaPlan) and
+// with keyframes that are free in the pose only: every free keyframe owns 15 or 6 columns of the reduced system (off / wid / colOff), two
+// temporal chains are nothing but link indices, and the caller's *pbStopFlag reaches the decision through a mapped word.
 // One launch per phase over the whole chip:
 //   k_iba_errors   computeActiveErrors + activeRobustChi2 (one thread per visual edge / per inertial link)
 //   k_iba_points   per point: Hll, bl                      k_iba_kf   per 64-edge chunk of a keyframe: Hpp, bp (wave sums), Hpl
@@ -39,7 +42,11 @@ struct IbaDev {
   const int *kfEdges, *chunkKF, *chunkStart, *chunkEnd;   // edges of free keyframes in chunks of <= 64
   double* kfPart; int* kfTicket;                          // per-chunk partial sums of k_iba_kf (27 each), arrival counter per keyframe
   const int* linkOrder;                                   // inertial links sorted by colour: links of one colour share no keyframe
-  const int* col;                               // [nKF] index of an optimizable keyframe or -1
+  const int* col;                               // [nKF] pose-block index of a free keyframe (the MFMA Schur operands' columns 6 c + r) or -1
+  const int* off;                               // [nKF] first column of a free keyframe in the reduced system (15 or 6 columns wide) or -1
+  const int* wid;                               // [nKF] 15: pose, velocity, biases | 6: free in the pose only | 0: fixed
+  const int* colOff;                            // [nFree] off[] by pose-block index (the inverse of col, for k_iba_schur_finish)
+  int nFree;                                    // free keyframes of either width: the Schur operands have M = 6 nFree + 1 columns
   const int *iKF1, *iKF2;
   const morb_imu_preintegrated* iPre;
   const uint8_t* iRobust;
@@ -53,7 +60,7 @@ struct IbaDev {
   double* scal;                                 // [0] robust chi2 of the last k_iba_errors, [2] solve ok
   double *partChi, *partScale; int nbUpdate;    // per-block partial sums of k_iba_errors / k_iba_update (added up in block order)
   // Schur complement on the FP64 matrix cores (schur_mfma.h): dense K-major operands (columns 6 c + r of the pose parts, plus
-  // the right-hand-side column 6 nOpt), partial products, block directory
+  // the right-hand-side column 6 nFree), partial products, block directory
   double *sW, *sWD, *sPart;
   const int2* sBlocks;
   const int* sBlkIndex;
@@ -64,13 +71,19 @@ struct IbaDev {
   int* lmHost;                                  // [0] decided trials, [1] done
   double *Sbk, *ptsBk;                          // state / points before the trial
   double* pnlG;                                 // panel copies of the global-memory LDL^T when they do not fit LDS
-  int nS, nPts, optIt;
+  int nS, nPts;
+  // the plan (LocalInertialBA | MergeInertialBA): iterations, the erase rule; robust / scaled links travel per link (iRobust, InfoI)
+  int optIt, eraseChi2Only;
+  const int* stopWord;                          // the caller's *pbStopFlag as the host loop forwards it (mapped host word), or NULL
   CamGeom g;
 };
 enum { IBA_LM_ITER, IBA_LM_QMAX, IBA_LM_NBAD, IBA_LM_ITS, IBA_LM_TRIALS, IBA_LM_DONE, IBA_LM_NEEDBUILD, IBA_LM_REJECTED, IBA_LM_TICKET };
 enum { IBA_LMD_CHI, IBA_LMD_LAMBDA, IBA_LMD_NI, IBA_LMD_INICHI, IBA_LMD_LASTCHI };
 __device__ __forceinline__ bool iba_done(const IbaDev& D) { return D.lmi[IBA_LM_DONE] != 0; }
 __device__ __forceinline__ bool iba_no_build(const IbaDev& D) { return D.lmi[IBA_LM_DONE] != 0 || D.lmi[IBA_LM_NEEDBUILD] == 0; }
+__device__ __forceinline__ bool iba_stop_requested(const IbaDev& D) {   // (as lm_stop_requested of local_ba.hip)
+  return D.stopWord && __hip_atomic_load(D.stopWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+}
 __device__ __forceinline__ void iba_load(const CamGeom& g, const double* s, VIState& V) {
   for (int k = 0; k < 9; ++k) { V.Rwb[k] = s[k]; V.Rcw[k] = s[21 + k]; }
   for (int k = 0; k < 3; ++k) { V.twb[k] = s[9 + k]; V.v[k] = s[12 + k]; V.bg[k] = s[15 + k]; V.ba[k] = s[18 + k]; V.tcw[k] = s[30 + k]; }
@@ -222,13 +235,14 @@ __device__ void iba_lm_decide(const IbaDev& D, double trialChi2, double gain) {
   }
   ++qmax;
   const int trials = D.lmi[IBA_LM_TRIALS] + 1;
+  const bool stop = iba_stop_requested(D);
   int done = 0, needBuild = 0;
-  if (!(rho < 0 && qmax < 10)) {   // the trial loop ends
+  if (!(rho < 0 && qmax < 10 && !stop)) {   // the trial loop ends
     // (a NaN rho — NaN errors — leaves the loop with the trial rejected: the host loop went on from the restored state; here the
     // solve ends, the stored errors belong to the rejected state)
     bool fin = (qmax == 10 || rho == 0 || !(rho == rho));
     if (!fin) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; fin = nBad >= 3; }
-    if (!fin) { ++iter; fin = iter >= D.optIt; }
+    if (!fin) { ++iter; fin = iter >= D.optIt || stop; }
     if (fin) done = 1;
     else { ++its; qmax = 0; needBuild = 1; D.lmd[IBA_LMD_INICHI] = currentChi; }
   }
@@ -248,8 +262,10 @@ __global__ __launch_bounds__(256) void k_iba_end(IbaDev D) {
 __global__ void k_iba_lm_init(IbaDev D, double chi, double lambda0) {
   D.lmd[IBA_LMD_CHI] = chi; D.lmd[IBA_LMD_LAMBDA] = lambda0; D.lmd[IBA_LMD_NI] = 2; D.lmd[IBA_LMD_INICHI] = chi; D.lmd[IBA_LMD_LASTCHI] = chi;
   for (int k = 0; k < 16; ++k) D.lmi[k] = 0;
-  D.lmi[IBA_LM_ITS] = 1; D.lmi[IBA_LM_NEEDBUILD] = 1;
+  const bool stop = iba_stop_requested(D);   // raised since the entry's own test: no iteration runs
+  D.lmi[IBA_LM_ITS] = stop ? 0 : 1; D.lmi[IBA_LM_DONE] = stop ? 1 : 0; D.lmi[IBA_LM_NEEDBUILD] = 1;
   D.scal[0] = 0.0; D.scal[1] = 0.0;
+  if (stop) __hip_atomic_store(D.lmHost + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // point side of buildSystem: Hll, bl (one thread per point over its edges, no atomics)
@@ -439,7 +455,7 @@ __global__ __launch_bounds__(256) void k_iba_kf(IbaDev D) {
     const double* part = D.kfPart + lane;
     for (int j = first; j < end; ++j)
       sum += __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(part + (size_t)j * 27), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const int o = 15 * D.col[kf];
+    const int o = D.off[kf];
     if (lane >= 21) D.b[o + lane - 21] += sum;
     else {
       int r = 0, q0 = 0;
@@ -479,14 +495,14 @@ __global__ __launch_bounds__(64) void k_iba_links(IbaDev D, int base) {
   }
   __syncthreads();
   const double w = sw;
-  const int c1 = D.col[k1], c2 = D.col[k2];
+  const int c1 = D.off[k1], c2 = D.off[k2];   // (a link's endpoints are fixed or 15 columns wide)
   for (int idx = tid; idx < 24 * 24 + 24; idx += 64) {
     const int a = idx < 576 ? idx / 24 : idx - 576;
-    const int ca = a < 15 ? (c1 >= 0 ? 15 * c1 + a : -1) : (c2 >= 0 ? 15 * c2 + (a - 15) : -1);
+    const int ca = a < 15 ? (c1 >= 0 ? c1 + a : -1) : (c2 >= 0 ? c2 + (a - 15) : -1);
     if (ca < 0) continue;
     if (idx < 576) {
       const int b2 = idx - a * 24;
-      const int cb = b2 < 15 ? (c1 >= 0 ? 15 * c1 + b2 : -1) : (c2 >= 0 ? 15 * c2 + (b2 - 15) : -1);
+      const int cb = b2 < 15 ? (c1 >= 0 ? c1 + b2 : -1) : (c2 >= 0 ? c2 + (b2 - 15) : -1);
       if (cb < 0) continue;
       double h = 0;
       for (int k = 0; k < 9; ++k) h += J[k * 24 + a] * OJ[k * 24 + b2];
@@ -502,7 +518,7 @@ __global__ __launch_bounds__(64) void k_iba_links(IbaDev D, int base) {
     const int t = tid / 9, r = (tid % 9) / 3, c = tid % 3;
     const double* I3 = (t == 0 ? D.InfoG : D.InfoA) + (size_t)i * 9;
     const double* e3 = (t == 0 ? D.gErr : D.aErr) + 3 * (size_t)i;
-    const int o1 = c1 >= 0 ? 15 * c1 + 9 + 3 * t : -1, o2 = c2 >= 0 ? 15 * c2 + 9 + 3 * t : -1;
+    const int o1 = c1 >= 0 ? c1 + 9 + 3 * t : -1, o2 = c2 >= 0 ? c2 + 9 + 3 * t : -1;
     const double v = I3[r * 3 + c];
     if (o2 >= 0) unsafeAtomicAdd(&D.H[(size_t)(o2 + r) * D.P + o2 + c], v);
     if (o1 >= 0) unsafeAtomicAdd(&D.H[(size_t)(o1 + r) * D.P + o1 + c], v);
@@ -543,7 +559,7 @@ __device__ __forceinline__ bool iba_pair_block(const IbaDev& D, int e, int c1, i
 __global__ __launch_bounds__(256) void k_iba_pack_w(IbaDev D) {
   if (iba_no_build(D)) return;
   const int t = blockIdx.x * 256 + threadIdx.x;
-  const int M = 6 * (D.P / 15);
+  const int M = 6 * D.nFree;
   if (t < D.nE) {
     const int c1 = D.col[D.eKF[t]];
     const int m = D.eMP[t];
@@ -587,15 +603,15 @@ __global__ __launch_bounds__(256) void k_iba_pack_wd(IbaDev D) {
 __global__ __launch_bounds__(256) void k_iba_schur_finish(IbaDev D) {
   if (iba_done(D)) return;
   const int t = blockIdx.x * 256 + threadIdx.x, gid = t >> 2, q = t & 3;
-  const int M = 6 * (D.P / 15);
+  const int M = 6 * D.nFree;
   const bool mat = gid < M * M, rhs = !mat && gid < M * M + M;
   int r = 0, c = M;
   if (mat) { r = gid / M; c = gid - r * M; } else if (rhs) r = gid - M * M;
   const int i = r < c ? r : c, j = r < c ? c : r;
   const double cs = morbschur::schur_sum4(D.sPart, D.sBlkIndex, D.sNb, D.sNblk, D.sNsplit, (mat || rhs) ? i : 0, (mat || rhs) ? j : 0, q);
   if (q != 0) return;
-  if (mat) D.Hs[(size_t)(15 * (r / 6) + r % 6) * D.P + 15 * (c / 6) + c % 6] -= cs;
-  else if (rhs) D.bs[15 * (r / 6) + r % 6] -= cs;
+  if (mat) D.Hs[(size_t)(D.colOff[r / 6] + r % 6) * D.P + D.colOff[c / 6] + c % 6] -= cs;
+  else if (rhs) D.bs[D.colOff[r / 6] + r % 6] -= cs;
 }
 // dense LDL^T + solve with the lower triangle resident in LDS (dense_ldlt.h): windows up to 15 N = 150 (n <= 163 fits)
 __global__ __launch_bounds__(morbdense::LT) void k_iba_solve_lds(IbaDev D) {
@@ -635,7 +651,7 @@ __global__ __launch_bounds__(256) void k_iba_update(IbaDev D) {
       const int c1 = D.col[D.eKF[e]];
       if (c1 < 0) continue;
       const double* B = D.Hpl + (size_t)e * 18;
-      const double* xp = D.x + 15 * c1;
+      const double* xp = D.x + D.colOff[c1];
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -649,12 +665,14 @@ __global__ __launch_bounds__(256) void k_iba_update(IbaDev D) {
     }
   } else if (t - D.nMP < D.nKF) {
     const int k = t - D.nMP;
-    const int c = D.col[k];
-    if (c >= 0) {
+    const int o = D.off[k];
+    if (o >= 0) {
       VIState V;
       iba_load(D.g, D.S + 33 * (size_t)k, V);
+      const int w = D.wid[k];   // a keyframe free in the pose only owns six columns: its velocity and biases do not move
       double dx[15];
-      for (int q = 0; q < 15; ++q) { dx[q] = D.x[15 * c + q]; sc += dx[q] * (lambda * dx[q] + D.b[15 * c + q]); }
+#pragma unroll
+      for (int q = 0; q < 15; ++q) { dx[q] = 0.0; if (q < w) { dx[q] = D.x[o + q]; sc += dx[q] * (lambda * dx[q] + D.b[o + q]); } }
       apply_update(D.g, V, dx);
       iba_store(V, D.S + 33 * (size_t)k);
     }
@@ -680,10 +698,14 @@ __global__ __launch_bounds__(256) void k_iba_finish(IbaDev D, uint8_t* __restric
       const double* X = D.pts + 3 * (size_t)D.eMP[t];
       const bool depthPos = (r6 * X[0] + r7 * X[1] + r8 * X[2] + tz) > 0.0;
       er = (c > (double)5.991f && !bClose) || (c > (double)(1.5f * 5.991f) && bClose) || !depthPos;
+      if (D.eraseChi2Only) er = c > (double)5.991f;   // MergeInertialBA (:4287-4310): no depth test, no mTrackDepth rule
     }
     erase[t] = er ? 1 : 0;
   }
-  if (t < D.nKF && D.col[t] >= 0) for (int k = 0; k < 21; ++k) kfOut[21 * (size_t)t + k] = (float)D.S[33 * (size_t)t + k];
+  if (t < D.nKF && D.off[t] >= 0) {   // (pose-only keyframes: Rwb, twb; their velocity and bias floats stay the caller's)
+    const int n = D.wid[t] == 15 ? 21 : 12;
+    for (int k = 0; k < n; ++k) kfOut[21 * (size_t)t + k] = (float)D.S[33 * (size_t)t + k];
+  }
   if (t < 3 * D.nMP) mpOut[t] = (float)D.pts[t];
 }
 
@@ -698,17 +720,33 @@ static int iba_fail(const char* what) { set_error("%s", what); return MORB_ERR_H
 struct IbaLayout {
   std::vector<int> col, ptStart, ptEdges, kfStart, kfEdges, chunkKF, chunkStart, chunkEnd, linkOrder, colourStart, blkIndex;
   std::vector<int2> blocks;
-  int nOpt = 0;
+  std::vector<int> off, wid, colOff;   // the reduced system's columns: per keyframe (first column or -1, width), per pose block
+  int nFree = 0, P = 0;
   morbschur::Plan splan;
 };
 
+// The plan of an optimiser on this graph, as data: LocalInertialBA (:2324-2897) and MergeInertialBA (:3853-4389) run the same kernels.
+struct IbaPlan {
+  int iterations; double lambda0;   // optimize(n), setUserLambdaInit
+  bool eraseChi2Only;               // erase by chi2 alone | LocalInertialBA's rule with the depth test and mTrackDepth
+  bool failTest;                    // "FAIL LOCAL-INERTIAL BA": nothing is written back when the error doubled
+  bool poseOnlyKinds;               // kfKind 3 (free in the pose only) is accepted
+  const char* who;
+};
+
 static int iba_layout(int nKF, const uint8_t* kfKind, int nMP, int nE, const int* eKF, const int* eMP, int nI, const int* iKF1, const int* iKF2,
-                      IbaLayout& L) {
-  L.col.assign(nKF, -1);
-  for (int k = 0; k < nKF; ++k) if (kfKind[k] == 0) L.col[k] = L.nOpt++;
-  MORB_REQUIRE(L.nOpt > 0, MORB_ERR_INVALID, "no optimizable keyframe");
+                      bool poseOnlyKinds, IbaLayout& L) {
+  L.col.assign(nKF, -1); L.off.assign(nKF, -1); L.wid.assign(nKF, 0);
+  for (int k = 0; k < nKF; ++k) {
+    const int w = kfKind[k] == 0 ? 15 : (poseOnlyKinds && kfKind[k] == 3) ? 6 : 0;   // (pose-only keyframes are not padded to 15 columns)
+    if (!w) continue;
+    L.col[k] = L.nFree++; L.off[k] = L.P; L.wid[k] = w; L.colOff.push_back(L.P); L.P += w;
+  }
+  MORB_REQUIRE(L.nFree > 0, MORB_ERR_INVALID, "no optimizable keyframe");
   for (int e = 0; e < nE; ++e) MORB_REQUIRE(eKF[e] >= 0 && eKF[e] < nKF && eMP[e] >= 0 && eMP[e] < nMP, MORB_ERR_INVALID, "edge index out of range");
   for (int i = 0; i < nI; ++i) MORB_REQUIRE(iKF1[i] >= 0 && iKF1[i] < nKF && iKF2[i] >= 0 && iKF2[i] < nKF, MORB_ERR_INVALID, "link index out of range");
+  if (poseOnlyKinds)   // a link's endpoints carry velocity and biases: free with 15 unknowns, or fixed with an IMU state
+    for (int i = 0; i < nI; ++i) MORB_REQUIRE(kfKind[iKF1[i]] <= 1 && kfKind[iKF2[i]] <= 1, MORB_ERR_INVALID, "link ends on a keyframe without velocity and biases");
   csr_by_key(eMP, nE, nMP, L.ptStart, L.ptEdges);
   csr_by_key(eKF, nE, nKF, L.kfStart, L.kfEdges, L.col.data());   // (compact: the optimizable keyframes' edges only)
   chunks_of(L.kfStart, L.col.data(), 64, L.chunkKF, L.chunkStart, L.chunkEnd);
@@ -727,7 +765,7 @@ static int iba_layout(int nKF, const uint8_t* kfKind, int nMP, int nE, const int
   }
   for (int c = 0; c < nColours; ++c) { L.colourStart.push_back((int)L.linkOrder.size()); for (int i = 0; i < nI; ++i) if (colour[i] == c) L.linkOrder.push_back(i); }
   L.colourStart.push_back((int)L.linkOrder.size());
-  L.splan = morbschur::make_plan(6 * L.nOpt + 1, 3 * nMP);
+  L.splan = morbschur::make_plan(6 * L.nFree + 1, 3 * nMP);
   schur_block_lists(L.splan.nb, L.blocks, L.blkIndex);
   return MORB_OK;
 }
@@ -735,16 +773,21 @@ static int iba_layout(int nKF, const uint8_t* kfKind, int nMP, int nE, const int
 // Levenberg-Marquardt with the control flow on the device (as grid-mode LocalBA, local_ba.hip): one slot = one trial; the host queues
 // slots one ahead of the decisions and stops when the mapped `done` word appears (ba_host.h); kernels queued behind the last decision return at once.
 // Leaves the loop's counters in *outer / *trials and the chi2 of the last evaluated trial in *lastChi.
-static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLayout& L, double chi, int bLarge, size_t denseLds, size_t blockedLds,
-                       int panelInLds, int* outer, int* trials, double* lastChi) {
-  const int nKF = D.nKF, nMP = D.nMP, nE = D.nE, nI = D.nI, P = D.P, nChunks = D.nChunks, Mpose = 6 * L.nOpt;
+// stopFlag: the caller's *pbStopFlag or NULL; the queue's tick forwards it to a spare mapped word ([2]) the decision kernels poll.
+static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLayout& L, double chi, const IbaPlan& plan, const volatile uint8_t* stopFlag,
+                       size_t denseLds, size_t blockedLds, int panelInLds, int* outer, int* trials, double* lastChi) {
+  const int nKF = D.nKF, nMP = D.nMP, nE = D.nE, nI = D.nI, P = D.P, nChunks = D.nChunks, Mpose = 6 * L.nFree;
   const size_t nS = (size_t)D.nS, nPts = (size_t)D.nPts;
   int *hostw = nullptr, *hostwDev = nullptr;
   MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
   D.lmHost = hostwDev;
-  D.optIt = bLarge ? 4 : 10;
+  D.optIt = plan.iterations; D.eraseChi2Only = plan.eraseChi2Only ? 1 : 0;
+  D.stopWord = stopFlag ? hostwDev + 2 : nullptr;
+  auto forwardStop = [&]() { if (stopFlag && *stopFlag) __atomic_store_n(hostw + 2, 1, __ATOMIC_RELEASE); };
+  __atomic_store_n(hostw + 2, 0, __ATOMIC_RELAXED);
   __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
-  hipLaunchKernelGGL(k_iba_lm_init, dim3(1), dim3(1), 0, st, D, chi, bLarge ? 1e-2 : 1e0);
+  forwardStop();
+  hipLaunchKernelGGL(k_iba_lm_init, dim3(1), dim3(1), 0, st, D, chi, plan.lambda0);
   const int beginGrid = div_up((int)std::max<size_t>(std::max<size_t>(std::max<size_t>(nS, nPts), (size_t)nMP * 8 /* k_iba_points: eight lanes per point */), std::max<size_t>((size_t)P * P, (size_t)18 * nE)), 256);
   const int q = lm_slot_queue(120, hostw + 0, hostw + 1, [&](int) {
     // backup / restore, then buildSystem (which runs only when the previous trial was accepted)
@@ -763,30 +806,33 @@ static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLa
     // a failed solve leaves x as it was (zero at the first trial): g2o still applies the update
     hipLaunchKernelGGL(k_iba_update, dim3(div_up(nMP + nKF, 256)), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 1);
-    return hipGetLastError() != hipSuccess ? iba_fail("LocalInertialBA trial failed") : MORB_OK;
+    if (hipGetLastError() != hipSuccess) { set_error("%s trial failed", plan.who); return (int)MORB_ERR_HIP; }
+    return (int)MORB_OK;
   }, [&]() {
     const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) iba_fail("LocalInertialBA: device error while waiting for the LM decision");
+    if (e != hipSuccess && e != hipErrorNotReady) set_error("%s: device error while waiting for the LM decision", plan.who);
     return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, []() {});   // (no stop flag: LocalInertialBA's caller has none to forward)
+  }, forwardStop);   // (LocalInertialBA's caller has no flag to forward)
   if (q < 0) return MORB_ERR_HIP;
   // (a queue that ran out of slots without `done` is drained by the read-back below, before the words are reset again)
   hipLaunchKernelGGL(k_iba_end, dim3(div_up((int)std::max<size_t>(nS, nPts), 256)), dim3(256), 0, st, D);
   int hi[16]; double hd[8];
   if (hipMemcpyAsync(hi, D.lmi, sizeof hi, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hd, D.lmd, sizeof hd, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess)
-    return iba_fail("LocalInertialBA failed");
+  { set_error("%s failed", plan.who); return MORB_ERR_HIP; }
   *outer = hi[IBA_LM_ITS]; *trials = hi[IBA_LM_TRIALS]; *lastChi = hd[IBA_LMD_LASTCHI];
   return MORB_OK;
 }
 
-// static void Optimizer::LocalInertialBA(KeyFrame*, bool* pbStopFlag, Map*, int&, int&, int&, int&, bool bLarge, bool bRecInit)
-// on the flattened graph (see include/morb_hip.h).  HOST pointers.  eRight / rig28 != NULL: fisheye rig.
-static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
-                           const uint8_t* mpClose, int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
-                           int nI, const int* iKF1, const int* iKF2, const morb_imu_preintegrated* iPre, const uint8_t* iRobust,
-                           const float* iInfoScale, float fx, float fy, float cx, float cy, float bf, const float* Tbc12, int bLarge,
-                           uint8_t* eraseFlag, int* stats3, const uint8_t* eRight, const float* rig28) {
+// static void Optimizer::LocalInertialBA(KeyFrame*, bool* pbStopFlag, Map*, int&, int&, int&, int&, bool bLarge, bool bRecInit) and
+// static void Optimizer::MergeInertialBA(KeyFrame*, KeyFrame*, bool* pbStopFlag, Map*, LoopClosing::KeyFrameAndPose&) on the flattened
+// graph (see include/morb_hip.h), told apart by the plan.  HOST pointers.  eRight / rig28 != NULL: fisheye rig.  stopFlag: the caller's
+// *pbStopFlag or NULL; set at entry, nothing runs and nothing is written (stats3[2] = 0).
+static int iba_impl(morb_optimizer* o, const IbaPlan& plan, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
+                    const uint8_t* mpClose, int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                    int nI, const int* iKF1, const int* iKF2, const morb_imu_preintegrated* iPre, const uint8_t* iRobust,
+                    const float* iInfoScale, float fx, float fy, float cx, float cy, float bf, const float* Tbc12,
+                    const volatile uint8_t* stopFlag, uint8_t* eraseFlag, int* stats3, const uint8_t* eRight, const float* rig28) {
   MORB_REQUIRE((eRight == nullptr) == (rig28 == nullptr), MORB_ERR_INVALID, "eRight and rig28 go together");
   MORB_REQUIRE(o && kfState21 && kfKind && mpPos && mpClose && eKF && eMP && eObs && eInvSigma2 && iKF1 && iKF2 && iPre && iRobust &&
                    iInfoScale && Tbc12 && eraseFlag, MORB_ERR_INVALID, "NULL argument");
@@ -794,8 +840,9 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   MORB_ENTER(st, o, nullptr);
   // ---- host-side graph layout
   IbaLayout L;
-  { const int rc = iba_layout(nKF, kfKind, nMP, nE, eKF, eMP, nI, iKF1, iKF2, L); if (rc != MORB_OK) return rc; }
-  const int nOpt = L.nOpt, P = 15 * nOpt, nChunks = (int)L.chunkKF.size();
+  { const int rc = iba_layout(nKF, kfKind, nMP, nE, eKF, eMP, nI, iKF1, iKF2, plan.poseOnlyKinds, L); if (rc != MORB_OK) return rc; }
+  const int P = L.P, nChunks = (int)L.chunkKF.size();
+  if (stopFlag && *stopFlag) { if (stats3) { stats3[0] = 0; stats3[1] = 0; stats3[2] = 0; } return MORB_OK; }   // `if (*pbStopFlag) return;` (:4276)
 
   // ---- device memory: every array is carved from the handle's grow-only workspace (ba_host.h): host -> device arrays first, each
   // copied into a pinned mirror of that region which crosses PCIe in ONE copy (twenty pageable hipMemcpyAsync calls, each staged and
@@ -803,7 +850,7 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   const size_t nS = (size_t)33 * nKF, nPts = (size_t)3 * nMP, nX = (size_t)P + 3 * nMP, nI1 = (size_t)std::max(nI, 1);
   IbaDev D;
   memset(&D, 0, sizeof D);
-  D.nKF = nKF; D.nMP = nMP; D.nE = nE; D.nI = nI; D.P = P; D.nChunks = nChunks;
+  D.nKF = nKF; D.nMP = nMP; D.nE = nE; D.nI = nI; D.P = P; D.nChunks = nChunks; D.nFree = L.nFree;
   D.nS = (int)nS; D.nPts = (int)nPts; D.nbUpdate = div_up(nMP + nKF, 256);
   D.sMp = L.splan.Mp; D.sNb = L.splan.nb; D.sNblk = L.splan.nblk; D.sNsplit = L.splan.nsplit;
   make_geom(Tbc12, fx, fy, cx, cy, bf, rig28, D.g);
@@ -816,6 +863,8 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
     D.kfEdges = (const int*)A.take(L.kfEdges.data(), sizeof(int) * L.kfEdges.size());
     D.chunkKF = (const int*)A.take(L.chunkKF.data(), sizeof(int) * nChunks); D.chunkStart = (const int*)A.take(L.chunkStart.data(), sizeof(int) * nChunks);
     D.chunkEnd = (const int*)A.take(L.chunkEnd.data(), sizeof(int) * nChunks); D.col = (const int*)A.take(L.col.data(), sizeof(int) * nKF);
+    D.off = (const int*)A.take(L.off.data(), sizeof(int) * nKF); D.wid = (const int*)A.take(L.wid.data(), sizeof(int) * nKF);
+    D.colOff = (const int*)A.take(L.colOff.data(), sizeof(int) * L.nFree);
     D.iKF1 = (const int*)A.take(iKF1, sizeof(int) * nI); D.iKF2 = (const int*)A.take(iKF2, sizeof(int) * nI);
     D.iPre = (const morb_imu_preintegrated*)A.take(iPre, sizeof(morb_imu_preintegrated) * nI);
     D.iRobust = (const uint8_t*)A.take(iRobust, nI); D.mpClose = (const uint8_t*)A.take(mpClose, nMP);
@@ -845,7 +894,7 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   { const int rc = grow(o->stage, A.uploadBytes(), &stage); if (rc != MORB_OK) return rc; }
   A.bind(arena, stage);
   carve();
-  MORB_REQUIRE(A.ok(), MORB_ERR_HIP, "the two carve passes of morb_local_inertial_ba differ");
+  if (!A.ok()) { set_error("the two carve passes of %s differ", plan.who); return MORB_ERR_HIP; }
   if (hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st) != hipSuccess) return MORB_ERR_HIP;   // the one upload
   // the workspace is reused from call to call: what the first kernels expect to find zero is cleared behind the carve
   (void)hipMemsetAsync(D.kfTicket, 0, sizeof(int) * (size_t)nKF, st);   // (the last chunk of a keyframe to arrive resets its counter)
@@ -873,30 +922,33 @@ static int local_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, 
   const double chi = h[0];
   const float err0 = (float)chi;
   int trials = 0, outer = 0;
-  { const int rc = iba_lm_loop(o, st, D, L, chi, bLarge, denseLds, blockedLds, panelInLds, &outer, &trials, &h[0]); if (rc != MORB_OK) return rc; }
+  { const int rc = iba_lm_loop(o, st, D, L, chi, plan, stopFlag, denseLds, blockedLds, panelInLds, &outer, &trials, &h[0]); if (rc != MORB_OK) return rc; }
   // ---- read-back.  activeRobustChi2 of the last computed errors = h[0] of the last trial (or the initial one)
   const float errEnd = (float)(trials ? h[0] : chi);
   int okFlag = 1;
-  if ((2 * err0 < errEnd || std::isnan(err0) || std::isnan(errEnd)) && !bLarge) okFlag = 0;   // "FAIL LOCAL-INERTIAL BA" (:2808-2813)
+  if ((2 * err0 < errEnd || std::isnan(err0) || std::isnan(errEnd)) && plan.failTest) okFlag = 0;   // "FAIL LOCAL-INERTIAL BA" (:2808-2813)
   memset(eraseFlag, 0, nE);
   if (okFlag) {
     hipLaunchKernelGGL(k_iba_finish, dim3(div_up(std::max(nE, std::max(nKF, 3 * nMP)), 256)), dim3(256), 0, st, D, d_erase, d_kfIn, d_mpIn);
     (void)hipMemcpyAsync(eraseFlag, d_erase, nE, hipMemcpyDeviceToHost, st);
     (void)hipMemcpyAsync(kfState21, d_kfIn, sizeof(float) * 21 * nKF, hipMemcpyDeviceToHost, st);
     (void)hipMemcpyAsync(mpPos, d_mpIn, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return iba_fail("LocalInertialBA read-back failed");
+    if (hipStreamSynchronize(st) != hipSuccess) { set_error("%s read-back failed", plan.who); return MORB_ERR_HIP; }
   }
   if (stats3) { stats3[0] = outer; stats3[1] = trials; stats3[2] = okFlag; }
   return MORB_OK;
 }
+
+// :2324-2897: optimize(10) from lambda 1 (bLarge: optimize(4) from 1e-2, and no FAIL test)
+static IbaPlan local_inertial_plan(int bLarge) { return IbaPlan{bLarge ? 4 : 10, bLarge ? 1e-2 : 1e0, false, !bLarge, false, "LocalInertialBA"}; }
 
 int morb_local_inertial_ba(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
                            const uint8_t* mpClose, int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
                            int nI, const int* iKF1, const int* iKF2, const morb_imu_preintegrated* iPre, const uint8_t* iRobust,
                            const float* iInfoScale, float fx, float fy, float cx, float cy, float bf, const float* Tbc12, int bLarge,
                            uint8_t* eraseFlag, int* stats3) {
-  return local_inertial_ba_impl(o, nKF, kfState21, kfKind, nMP, mpPos, mpClose, nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre, iRobust,
-                                iInfoScale, fx, fy, cx, cy, bf, Tbc12, bLarge, eraseFlag, stats3, nullptr, nullptr);
+  return iba_impl(o, local_inertial_plan(bLarge), nKF, kfState21, kfKind, nMP, mpPos, mpClose, nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre,
+                  iRobust, iInfoScale, fx, fy, cx, cy, bf, Tbc12, nullptr, eraseFlag, stats3, nullptr, nullptr);
 }
 int morb_local_inertial_ba_fisheye(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
                                    const uint8_t* mpClose, int nE, const int* eKF, const int* eMP, const float* eObs, const uint8_t* eRight,
@@ -904,8 +956,41 @@ int morb_local_inertial_ba_fisheye(morb_optimizer* o, int nKF, float* kfState21,
                                    const uint8_t* iRobust, const float* iInfoScale, const float* rig28, const float* Tbc12, int bLarge,
                                    uint8_t* eraseFlag, int* stats3) {
   MORB_REQUIRE(eRight && rig28, MORB_ERR_INVALID, "NULL argument");
-  return local_inertial_ba_impl(o, nKF, kfState21, kfKind, nMP, mpPos, mpClose, nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre, iRobust,
-                                iInfoScale, 0, 0, 0, 0, 0, Tbc12, bLarge, eraseFlag, stats3, eRight, rig28);
+  return iba_impl(o, local_inertial_plan(bLarge), nKF, kfState21, kfKind, nMP, mpPos, mpClose, nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre,
+                  iRobust, iInfoScale, 0, 0, 0, 0, 0, Tbc12, nullptr, eraseFlag, stats3, eRight, rig28);
+}
+
+
+// :3853-4389: setUserLambdaInit(1e3), optimize(8), Huber on every inertial edge with the information as it stands, erase by chi2 alone,
+// no FAIL test.  mpClose plays no part (zeros); rig28: every edge on the left KannalaBrandt8 camera (the function creates EdgeMono(0) only).
+static int merge_inertial_ba_impl(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos, int nE, const int* eKF,
+                                  const int* eMP, const float* eObs, const float* eInvSigma2, int nI, const int* iKF1, const int* iKF2,
+                                  const morb_imu_preintegrated* iPre, float fx, float fy, float cx, float cy, float bf, const float* rig28,
+                                  const float* Tbc12, const uint8_t* pbStopFlag, uint8_t* eraseFlag, int* stats3) {
+  MORB_REQUIRE(o && kfState21 && kfKind && mpPos && eKF && eMP && eObs && eInvSigma2 && iKF1 && iKF2 && iPre && Tbc12 && eraseFlag && stats3,
+               MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nKF > 0 && nMP > 0 && nE > 0 && nI >= 0, MORB_ERR_INVALID, "bad sizes");
+  for (int k = 0; k < nKF; ++k) MORB_REQUIRE(kfKind[k] <= 3, MORB_ERR_INVALID, "kfKind out of range");
+  const IbaPlan plan{8, 1e3, true, false, true, "MergeInertialBA"};
+  const std::vector<uint8_t> zeros((size_t)std::max(nMP, nE), 0), robust((size_t)std::max(nI, 1), 1);
+  const std::vector<float> scale((size_t)std::max(nI, 1), 1.0f);
+  return iba_impl(o, plan, nKF, kfState21, kfKind, nMP, mpPos, zeros.data(), nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre, robust.data(),
+                  scale.data(), fx, fy, cx, cy, bf, Tbc12, pbStopFlag, eraseFlag, stats3, rig28 ? zeros.data() : nullptr, rig28);
+}
+int morb_merge_inertial_ba(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos, int nE, const int* eKF,
+                           const int* eMP, const float* eObs, const float* eInvSigma2, int nI, const int* iKF1, const int* iKF2,
+                           const morb_imu_preintegrated* iPre, float fx, float fy, float cx, float cy, float bf, const float* Tbc12,
+                           const uint8_t* pbStopFlag, uint8_t* eraseFlag, int* stats3) {
+  return merge_inertial_ba_impl(o, nKF, kfState21, kfKind, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre, fx, fy, cx, cy, bf,
+                                nullptr, Tbc12, pbStopFlag, eraseFlag, stats3);
+}
+int morb_merge_inertial_ba_fisheye(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos, int nE,
+                                   const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2, int nI, const int* iKF1,
+                                   const int* iKF2, const morb_imu_preintegrated* iPre, const float* rig28, const float* Tbc12,
+                                   const uint8_t* pbStopFlag, uint8_t* eraseFlag, int* stats3) {
+  MORB_REQUIRE(rig28, MORB_ERR_INVALID, "NULL argument");
+  return merge_inertial_ba_impl(o, nKF, kfState21, kfKind, nMP, mpPos, nE, eKF, eMP, eObs, eInvSigma2, nI, iKF1, iKF2, iPre, 0, 0, 0, 0, 0, rig28,
+                                Tbc12, pbStopFlag, eraseFlag, stats3);
 }
 
 }  // extern "C"

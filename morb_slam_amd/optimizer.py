@@ -374,6 +374,33 @@ class Optimizer:
                                                    ptr(erase), ptr(level), ptr(stats)))
         return a[0], a[2], erase, level, stats
 
+    def MergeInertialBA(self, kfState, kfKind, mpPos, eKF, eMP, eObs, eInvSigma2, iKF1, iKF2, iPre, cam, Tbc, stop_flag=None, rig=None):
+        """Optimizer::MergeInertialBA(pCurrKF, pMergeKF, pbStopFlag, pMap, corrPoses), the welding bundle adjustment of an inertial map
+        merge, on host numpy arrays (see morb_merge_inertial_ba).  kfKind: 0 free (15 unknowns), 1 fixed with an IMU state, 2 fixed observer,
+        3 free in the pose only.  iPre: float32 [nI, PREINT_FLOATS].  rig = 28 floats puts every edge on the left KannalaBrandt8 camera
+        (cam is ignored).  stop_flag: a one-byte numpy array standing for `bool* pbStopFlag`.
+        Returns (kfState, mpPos, eraseFlag, stats3) with stats3 = (outer LM iterations, LM trials, ran)."""
+        a = [np.ascontiguousarray(kfState, np.float32).copy(), np.ascontiguousarray(kfKind, np.uint8),
+             np.ascontiguousarray(mpPos, np.float32).copy(), np.ascontiguousarray(eKF, np.int32), np.ascontiguousarray(eMP, np.int32),
+             np.ascontiguousarray(eObs, np.float32), np.ascontiguousarray(eInvSigma2, np.float32), np.ascontiguousarray(iKF1, np.int32),
+             np.ascontiguousarray(iKF2, np.int32), np.ascontiguousarray(iPre, np.float32).reshape(-1, PREINT_FLOATS),
+             np.ascontiguousarray(Tbc, np.float32)]
+        nE, nI = len(a[3]), len(a[7])
+        assert a[9].shape == (nI, PREINT_FLOATS) and a[0].shape[1] == 21 and a[5].shape == (nE, 3)
+        erase = np.zeros(nE, np.uint8); stats = np.zeros(3, np.int32)
+        st = ptr(stop_flag) if stop_flag is not None else None
+        if rig is not None:
+            r28 = np.ascontiguousarray(rig, np.float32)
+            assert r28.size == 28
+            check(self._L.morb_merge_inertial_ba_fisheye(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]),
+                                                         ptr(a[5]), ptr(a[6]), nI, ptr(a[7]), ptr(a[8]), ptr(a[9]), ptr(r28), ptr(a[10]), st,
+                                                         ptr(erase), ptr(stats)))
+            return a[0], a[2], erase, stats
+        check(self._L.morb_merge_inertial_ba(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]), ptr(a[5]),
+                                             ptr(a[6]), nI, ptr(a[7]), ptr(a[8]), ptr(a[9]), cam["fx"], cam["fy"], cam["cx"], cam["cy"],
+                                             cam["bf"], ptr(a[10]), st, ptr(erase), ptr(stats)))
+        return a[0], a[2], erase, stats
+
 
 def local_bundle_adjustment_oneshot(opt, kfPose, kfFixed, mpPos, eKF, eMP, eObs, eInvSigma2, cam, inertial=False, stop_flag=None):
     """The one-shot ABI entry (`morb_local_bundle_adjustment`), as the reference binding calls it: `stop_flag` is a one-byte

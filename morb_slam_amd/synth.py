@@ -1557,3 +1557,151 @@ def make_merge_ba_problem(n_free=25, n_fixed=25, n_points=3500, seed=0, mono_fra
     else:
         out["eObs"] = eObs.astype(np.float32)
     return out
+
+
+# ---- map merging with an IMU: Optimizer::MergeInertialBA(pCurrKF, pMergeKF, pbStopFlag, pMap, corrPoses) ------------------------------
+def make_merge_inertial_ba_problem(n_cur=5, n_merge=5, n_cov=4, n_points=300, seed=0, mono_frac=0.3, kb8=False, n_imu=40, n_fixed_vis=0,
+                                   outlier_frac=0.03, rigid_deg=0.3, rigid_trans=0.02, kf_deg=0.3, kf_trans=0.01, point_noise=0.03,
+                                   obs_per_point=(3, 9), noise_px=1.0, vel_noise=0.03, bias_noise=1.0, kf_edges=None, vel_kick=None, fixed_shift=0.0, fixed_pair=0.0,
+                                   n_behind=0,
+                                   n_cov_only=0, cam=EUROC_CAM):
+    """MergeInertialBA input (morb_merge_inertial_ba): chain A, the current map's window — one free head (vpOptimizableCovKFs[0]) then
+    n_cur free keyframes; chain B, the merge map's window — one fixed keyframe with an IMU state (lFixedKeyFrames) then n_merge free
+    keyframes; n_cov keyframes free in the pose only and n_fixed_vis fixed observers, all looking at the same points.  kfKind 0 / 1 / 2 /
+    3 as the entry takes them; every link carries n_imu IMU samples of a smooth motion as in make_inertial_ba_problem.  Chain A starts
+    displaced rigidly by what the Sim3 alignment leaves (rigid_deg, rigid_trans), every free keyframe by a little more.  kb8: every
+    observation monocular on the left camera of the TUM-VI rig (`rig28`).  Knobs: kf_edges = {keyframe: count}: that keyframe observes
+    exactly `count` points; vel_kick = {keyframe: m/s}: its initial velocity is off by that much (a link whose chi2 starts above the Huber
+    bar); fixed_shift: the fixed keyframe of chain B stands that many metres off along every axis; fixed_pair: chain B begins with TWO
+    fixed keyframes with an IMU state joined by a link, the first of them (which observes nothing) that many metres off — a link between
+    fixed vertices, a constant of the robust chi2 that no step changes; n_behind: extra points BEHIND every camera whose monocular
+    observations agree with them (a negative depth with a small chi2);
+    n_cov_only: extra points seen by pose-only keyframes alone; noise_px, vel_noise, bias_noise (a factor): the observation noise and
+    the initial error of the free keyframes' velocities and biases (all zero with the displacements: the graph starts at its optimum)."""
+    rng = np.random.default_rng(0x41BA0 + seed)
+    g = np.array([0, 0, -9.81])
+    dt = 1.0 / IMU_FREQ
+    bg = rng.normal(0, 0.01, 3); ba = rng.normal(0, 0.05, 3)
+    Tbc = EUROC_TBC
+    Rcb = Tbc[:3, :3].T; tcb = -Rcb @ Tbc[:3, 3]
+    acc, gyro, dts, start = [], [], [], [0]
+    states, iKF1, iKF2 = [], [], []
+
+    def chain(n_links, R, p, v):
+        states.append((R, p, v))
+        for _ in range(n_links):
+            w_b = rng.normal(0, 0.15, 3); a_w = rng.normal(0, 0.5, 3)
+            for i in range(n_imu):
+                Rm = R @ _rot_from_rotvec(w_b * (i + 0.5) * dt)
+                acc.append(Rm.T @ (a_w - g) + ba + rng.normal(0, 0.02, 3))
+                gyro.append(w_b + bg + rng.normal(0, 0.002, 3))
+                dts.append(dt)
+            T = n_imu * dt
+            R, p, v = R @ _rot_from_rotvec(w_b * T), p + v * T + 0.5 * a_w * T * T, v + a_w * T
+            iKF1.append(len(states) - 1); iKF2.append(len(states))
+            states.append((R, p, v))
+            start.append(len(dts))
+
+    R0 = _rot_from_rotvec(rng.normal(0, 0.1, 3)); p0 = rng.normal(0, 0.2, 3)
+    chain(n_cur, R0, p0, np.array([0.6, 0.1, 0.0]) + rng.normal(0, 0.1, 3))
+    nA = len(states)
+    nFix = 2 if fixed_pair else 1
+    chain(n_merge + nFix - 1, R0 @ _rot_from_rotvec(rng.normal(0, 0.05, 3)), p0 + rng.normal(0, 0.25, 3), np.array([0.5, -0.1, 0.0]) + rng.normal(0, 0.1, 3))
+    nChain = len(states)
+    for _ in range(n_cov + n_fixed_vis):
+        Rk, pk, _ = states[rng.integers(0, nChain)]
+        states.append((Rk @ _rot_from_rotvec(rng.normal(0, 0.05, 3)), pk + rng.normal(0, 0.15, 3), rng.normal(0, 0.3, 3)))
+    nKF = len(states)
+    kind = np.array([0] * nA + [1] * nFix + [0] * n_merge + [3] * n_cov + [2] * n_fixed_vis, np.uint8)
+    cams = [(Rcb @ Rk.T, Rcb @ (-Rk.T @ pk) + tcb) for Rk, pk, _ in states]
+    Rm, tm_ = cams[nA // 2]
+    zr = (2.0, 8.0) if kb8 else (2.0, 20.0)
+    n_all = n_points + n_behind + n_cov_only
+    Xc = np.stack([rng.uniform(-4, 4, n_all), rng.uniform(-2.5, 2.5, n_all), rng.uniform(*zr, n_all)], 1)
+    Xc[n_points:n_points + n_behind, 2] = -rng.uniform(3, 8, n_behind)
+    X = (Xc - tm_) @ Rm
+
+    def observe(k, j, mono=False):
+        """(observation x y uRight, 1 / sigma^2) of point j in keyframe k, or None when it is not in the image"""
+        Rcw, tcw = cams[k]
+        xc = Rcw @ X[j] + tcw
+        behind = n_points <= j < n_points + n_behind
+        if (xc[2] < 0.5) != behind or abs(xc[2]) < 0.5:
+            return None
+        s = 1.2 ** int(rng.integers(0, 8))
+        if kb8:
+            u, vv = kb8_project(TUMVI_CAM_L, xc[None])[0]
+            if not behind and not (5 < u < 507 and 5 < vv < 507):
+                return None
+            s *= 0.5
+            o = np.array([u, vv, -1.0]) + np.array([rng.normal(0, noise_px) * s, rng.normal(0, noise_px) * s, 0.0])
+        else:
+            u = cam["fx"] * xc[0] / xc[2] + cam["cx"]; vv = cam["fy"] * xc[1] / xc[2] + cam["cy"]
+            if not behind and not (0 <= u < 752 and 0 <= vv < 480):
+                return None
+            o = np.array([u, vv, u - cam["bf"] / xc[2]]) + rng.normal(0, noise_px, 3) * s
+            if mono or behind or rng.random() < mono_frac:
+                o[2] = -1
+        return o, 1.0 / (s * s)
+
+    counted = dict(kf_edges or {})
+    if fixed_pair:
+        counted[nA] = 0
+    cov = [k for k in range(nKF) if kind[k] == 3]
+    assert not n_cov_only or len(cov) >= 2
+    eKF, eMP, eObs, eInv = [], [], [], []
+    for j in range(n_all):
+        pool = cov if j >= n_points + n_behind else list(range(nKF))
+        for k in rng.choice(pool, size=min(int(rng.integers(*obs_per_point)), len(pool)), replace=False):
+            if int(k) in counted:
+                continue
+            r = observe(int(k), j)
+            if r is not None:
+                eKF.append(int(k)); eMP.append(j); eObs.append(r[0]); eInv.append(r[1])
+    for k, count in counted.items():
+        got = 0
+        for j in rng.permutation(n_points):
+            if got == count:
+                break
+            r = observe(k, int(j))
+            if r is not None:
+                eKF.append(k); eMP.append(int(j)); eObs.append(r[0]); eInv.append(r[1]); got += 1
+        assert got == count, (k, got, count)
+    eKF, eMP, eObs, eInv = np.array(eKF, np.int32), np.array(eMP, np.int32), np.array(eObs, np.float64), np.array(eInv, np.float32)
+    order = np.lexsort((eKF, eMP))          # (edges by point, as the reference walks its points' observations)
+    eKF, eMP, eObs, eInv = eKF[order], eMP[order], eObs[order], eInv[order]
+    gross = (rng.random(len(eKF)) < outlier_frac) & (eMP < n_points)
+    off = rng.choice([-1, 1], (len(eKF), 2)) * rng.uniform(15, 30, (len(eKF), 2))
+    eObs[gross, :2] += off[gross]
+    # every point is seen: points nobody observes are dropped (the reference builds its points from the keyframes' matches)
+    used = np.zeros(n_all, bool); used[eMP] = True
+    remap = np.cumsum(used) - 1
+    eMP = remap[eMP].astype(np.int32)
+    tags = np.zeros(n_all, np.uint8); tags[n_points:n_points + n_behind] = 1; tags[n_points + n_behind:] = 2
+    X, tags = X[used], tags[used]
+    true = np.stack([np.concatenate([Rk.ravel(), pk, vk, bg, ba]) for Rk, pk, vk in states])
+    init = true.copy()
+    DR = _rot_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(rigid_deg)); Dt = rng.normal(0, 1, 3) / np.sqrt(3) * rigid_trans
+    for k in range(nKF):
+        if kind[k] in (1, 2):
+            continue
+        Rk, pk, vk = states[k]
+        if k < nA:     # the current map's window, as the Sim3 alignment left it
+            Rk, pk, vk = DR @ Rk, DR @ pk + Dt, DR @ vk
+        Rk = Rk @ _rot_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(kf_deg))
+        init[k, :9] = Rk.ravel(); init[k, 9:12] = pk + rng.normal(0, kf_trans, 3)
+        if kind[k] == 0:
+            init[k, 12:15] = vk + rng.normal(0, vel_noise, 3)
+            init[k, 15:18] += rng.normal(0, 0.001, 3) * bias_noise; init[k, 18:21] += rng.normal(0, 0.005, 3) * bias_noise
+    for k, dv in (vel_kick or {}).items():
+        init[k, 12:15] += rng.normal(0, 1, 3) / np.sqrt(3) * dv
+    init[nA + nFix - 1, 9:12] += fixed_shift          # (the fixed keyframe of chain B contradicts its link: trials get rejected)
+    if fixed_pair:
+        init[nA, 9:12] += fixed_pair
+    out = dict(kfState=init.astype(np.float32), kfKind=kind, mpPos=(X + rng.normal(0, point_noise, X.shape)).astype(np.float32),
+               mpTag=tags, eKF=eKF, eMP=eMP, eObs=eObs.astype(np.float32), eInvSigma2=eInv, iKF1=np.array(iKF1, np.int32),
+               iKF2=np.array(iKF2, np.int32), imuStart=np.array(start, np.int32), acc=np.array(acc, np.float32),
+               gyro=np.array(gyro, np.float32), dt=np.array(dts, np.float32), bias=np.concatenate([ba, bg]).astype(np.float32),
+               Tbc12=np.concatenate([Tbc[:3, :3].ravel(), Tbc[:3, 3]]).astype(np.float32), cam=cam, true=true, truePts=X, gross=gross,
+               rig28=tumvi_rig28() if kb8 else None)
+    return out
