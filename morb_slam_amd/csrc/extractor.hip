@@ -414,6 +414,9 @@ __device__ __forceinline__ uint32_t pk_sub_sat(uint32_t a, uint32_t b) {   // v_
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {   // v_pk_add_u16
   return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b));
 }
+__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) {   // v_pk_sub_i16 (wraps)
+  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b));
+}
 
 // i / d == (i * ceil(2^20 / d)) >> 20 for i < 2^15, d < 40 (both factors fit v_mul_u32_u24)
 struct Magic20 { unsigned m[40]; constexpr Magic20() : m() { for (int d = 1; d < 40; ++d) m[d] = 0xFFFFFu / (unsigned)d + 1u; } };
@@ -434,6 +437,25 @@ __device__ __forceinline__ int arc9_maxmin(const int (&d)[16]) {
   const int a0 = vmax3(mn9[0], mn9[1], mn9[2]), a1 = vmax3(mn9[3], mn9[4], mn9[5]), a2 = vmax3(mn9[6], mn9[7], mn9[8]);
   const int a3 = vmax3(mn9[9], mn9[10], mn9[11]), a4 = vmax3(mn9[12], mn9[13], mn9[14]);
   return vmax3(vmax3(a0, a1, a2), vmax3(a3, a4, mn9[15]), -256);
+}
+// The same tree for two rings at once, one in each half of the registers: gfx950's only packed three-operand minimum / maximum are the f16
+// ones (v_pk_minimum3_f16 / v_pk_maximum3_f16).  Every half must be a positive normal f16 (k_fastw: 0x4400 | byte), whose order is the order of
+// its bits; the instructions return one operand's bits unchanged.
+__device__ __forceinline__ uint32_t vpkmin3(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+__device__ __forceinline__ uint32_t vpkmax3(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+// hi << 16 | lo, written out: left to itself the compiler folds the xor that follows into a v_bitop3_b32 behind a v_lshlrev_b32 — two 4-cycle
+// instructions where v_lshl_or_b32 + v_xor_b32 cost 4 + 2.4 (tools/micro/valu_rate.hip)
+__device__ __forceinline__ uint32_t pack_halves(uint32_t lo, uint32_t hi) { uint32_t r; asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(r) : "v"(hi), "v"(lo)); return r; }
+__device__ __forceinline__ uint32_t arc9_maxmin_pk(const uint32_t (&d)[16]) {
+  uint32_t mn3[16], mn9[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) mn3[k] = vpkmin3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) mn9[k] = vpkmin3(mn3[k], mn3[(k + 3) & 15], mn3[(k + 6) & 15]);
+  const uint32_t a0 = vpkmax3(mn9[0], mn9[1], mn9[2]), a1 = vpkmax3(mn9[3], mn9[4], mn9[5]), a2 = vpkmax3(mn9[6], mn9[7], mn9[8]);
+  const uint32_t a3 = vpkmax3(mn9[9], mn9[10], mn9[11]), a4 = vpkmax3(mn9[12], mn9[13], mn9[14]);
+  const uint32_t b1 = vpkmax3(a3, a4, mn9[15]);
+  return vpkmax3(vpkmax3(a0, a1, a2), b1, b1);
 }
 
 #ifdef MORB_FAST_TIMING

@@ -15,8 +15,9 @@
 //             v - T (dark) or min(max(p0, p8), max(p4, p12)) > v + T (bright) — stronger than round 2's "second smallest of the
 //             four compass pixels" and two packed operations shorter.  Flags outside the evaluated columns are masked, the rest
 //             are queued one entry per (pixel, polarity).
-//   strength  runs whenever 64 survivors are queued (all lanes busy but for the last round of a pass): exact max-min over the 16
-//             arcs (v_min3 / v_max3 trees) for the entry's polarity; corners (S > T) go to a list (position, S).
+//   strength  runs whenever 128 survivors are queued, two per lane in the halves of the lane's registers (all lanes busy but for the last
+//             round of a pass): exact max-min over the 16 arcs (packed three-operand f16 minimum / maximum trees on bytes dressed as f16;
+//             v_min3 / v_max3 for a last round of <= 64) for the entry's polarity; corners (S > T) go to a list (position, S).
 //   nms       the window is zeroed and the corners' strengths scattered into it; one corner per lane looks at its 8 neighbours.
 //   output    row-major (cv::FAST's order): a keypoint's slot = the number of keypoints before it, counted by broadcast.
 // More than 512 corners or more than 64 keypoints in one cell (noise images): the pass is redone row by row with a rolling
@@ -61,7 +62,9 @@ extern "C" int morb_fw_stats(unsigned long long* out, int reset) {
 #define FW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 constexpr int FW_SH = 1;       // window column c = tile column c + FW_SH
-constexpr int FW_QCAP = 320;   // survivor queue: < 64 left over + 256 of a reject round's flags (a fuller round is queued in several pieces)
+// (tests/test_fastw_emit_pairs_gpu.py replays the queue with copies of FW_QCAP and FW_PAIR_MIN: change them there too)
+constexpr int FW_QCAP = 384;   // survivor queue: < 128 left over + 256 of a reject round's flags (a fuller round is queued in several pieces)
+constexpr int FW_PAIR_MIN = 64;   // a strength round of more survivors than this runs two per lane (0, every round paired: +8 us per 512 images)
 constexpr int FW_CQ = 512;     // corner list of a pass (~50 per cell on the benchmark images); more -> strip mode
 constexpr int FW_KC = 64;      // keypoint list of a cell (~10); more -> strip mode
 #ifndef MORB_FW_WAVES
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(64 * FW_WAVES, P == 48 ? ((FW_WAVES * 8 + 3) / 4 > 
           int incl = cnt;
           MORB_DPP_SCAN(incl, 0, morbwave::op_add);   // inclusive prefix over the wave (all lanes active)
           int total = __builtin_amdgcn_readlane(incl, 63);
-          if (total > FW_QCAP - qn) {   // (wave-uniform, rare: qn < 64 here, so more than 256 flags in one round) queue a prefix of the lanes now
+          if (total > FW_QCAP - qn) {   // (wave-uniform, rare: qn < 128 here, so more than 256 flags in one round) queue a prefix of the lanes now
             FW_STAT(12, 1);
             const bool fits = incl <= FW_QCAP - qn;   // true for at least lane 0: a lane holds at most 32 flags
             total = __builtin_amdgcn_readlane(incl, __popcll(__ballot(fits)) - 1);
@@ -307,31 +310,59 @@ __global__ __launch_bounds__(64 * FW_WAVES, P == 48 ? ((FW_WAVES * 8 + 3) / 4 > 
           const bool more = __ballot(pend != 0u) != 0ull;   // (only after a partial take)
           const bool flush = lastRound && !more;
           FW_CYC(2);
-          // strength of the queued pixels, 64 at a time (fewer only when the pass's last survivors are flushed)
-          while (qn >= 64 || (flush && qn > 0)) {
+          // strength of the queued pixels, 128 at a time: TWO per lane, entries q0 + lane and q0 + 64 + lane, in the halves of the lane's
+          // registers — a ring pixel is a byte.  (The neighbours 2 lane, 2 lane + 1, one aligned read, measured 12 us per 512 images
+          // SLOWER, profiles/r17 — supposedly the LDS banks: a ring-pixel read of 64 lanes then gathers from 128 entries' worth of tile rows
+          // instead of 64, and rows 16 apart share their banks.)  Fewer only when the pass's last survivors are flushed; 64 or fewer of
+          // those take the one-per-lane form, which has no halves to put together.
+          while (qn >= 128 || (flush && qn > 0)) {
             FW_STAT(5, 1);
-            const int nq = imin(qn, 64), q0 = qn - nq;
+            const int nq = imin(qn, 128), q0 = qn - nq;
             qn = q0;
-            const bool act = lane < nq;
-            const unsigned e = act ? (unsigned)queue[q0 + lane] : (unsigned)(3 * P + xa) << 3;   // (inactive lanes: pixel (xa, 3))
+            const unsigned eIdle = (unsigned)(3 * P + xa) << 3;   // (inactive lanes and halves: pixel (xa, 3))
             // entry = (item's tile offset / 4) << 5 | f; f[0] = polarity, pixel offset in the 12-px item = f[3] f[2] f[4] f[1]
-            const int off = (int)(((e >> 3) & ~3u) + (((e >> 1) & 1u) | ((e >> 3) & 2u) | (e & 12u)));
-            int rr[16];
-            const int v = ring(off, rr);
+            auto entry_off = [](unsigned e) -> int { return (int)(((e >> 3) & ~3u) + (((e >> 1) & 1u) | ((e >> 3) & 2u) | (e & 12u))); };
+            auto list_corner = [&](bool isCorner, int off, int S) {
+              const uint64_t cm = __ballot(isCorner);
+              if (cm) {   // wave-uniform
+                const int idx = cn + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
+                if (isCorner && idx < FW_CQ) { cornerPos[idx] = (uint16_t)off; cornerS[idx] = (uint8_t)imin(S, 255); }
+                cn += __popcll(cm);
+              }
+            };
+            const bool paired = nq > FW_PAIR_MIN;   // (wave-uniform)
+            const bool actA = lane < nq, actB = paired && lane + 64 < nq;
+            const unsigned eA = actA ? (unsigned)queue[q0 + lane] : eIdle;
+            const int offA = entry_off(eA);
             // strength = max over the arcs of min over the arc of (v - p) for the dark polarity, of (p - v) for the bright one.  With
             // q = p ^ m (m = 255 for dark, 0 for bright) both are  maxmin(q) - (v ^ m):  sixteen v_xor_b32 in a row (half the cycles of the
             // v_xad_u32 per ring pixel of the (p ^ mask) + c form: tools/micro/valu_rate.hip) and one tree for both polarities
-            const int m8 = (int)(((e & 1u) - 1u) & 0xFFu);
-            int d[16];
+            const unsigned mA = ((eA & 1u) - 1u) & 0xFFu;
+            if (paired) {
+              const unsigned eB = actB ? (unsigned)queue[q0 + 64 + lane] : eIdle;
+              const int offB = entry_off(eB);
+              int rA[16], rB[16];
+              const int vA = ring(offA, rA), vB = ring(offB, rB);
+              // Both halves as positive normal f16 numbers 0x4400 | q (4.0 .. 4.996: ordered as q is, no denormal, no NaN), so that the packed
+              // three-operand f16 minimum / maximum — the only packed min3 / max3 of the ISA, and they return one operand's bits — run the same
+              // 16 + 16 + 8 tree for two survivors; one v_lshl_or_b32 per ring pixel joins the halves, the polarity xor sets the exponent too
+              const unsigned M = (((((eB & 1u) - 1u) & 0xFFu) | 0x4400u) << 16) | mA | 0x4400u;
+              unsigned d[16];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) d[k] = rr[k] ^ m8;
-            const int S = arc9_maxmin(d) - (v ^ m8);
-            const bool isCorner = act && S > T;
-            const uint64_t cm = __ballot(isCorner);
-            if (cm) {   // wave-uniform
-              const int idx = cn + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
-              if (isCorner && idx < FW_CQ) { cornerPos[idx] = (uint16_t)off; cornerS[idx] = (uint8_t)imin(S, 255); }
-              cn += __popcll(cm);
+              for (int k = 0; k < 16; ++k) d[k] = pack_halves((unsigned)rA[k], (unsigned)rB[k]) ^ M;
+              const unsigned c = pack_halves((unsigned)vA, (unsigned)vB) ^ M;
+              const unsigned S2 = pk_sub(arc9_maxmin_pk(d), c);   // maxmin(q) - (v ^ m) per half: -255 .. 255
+              const int SA = (int)(S2 << 16) >> 16, SB = (int)S2 >> 16;
+              list_corner(actA && SA > T, offA, SA);
+              list_corner(actB && SB > T, offB, SB);
+            } else {
+              int rr[16];
+              const int v = ring(offA, rr);
+              int d[16];
+#pragma unroll
+              for (int k = 0; k < 16; ++k) d[k] = rr[k] ^ (int)mA;
+              const int S = arc9_maxmin(d) - (v ^ (int)mA);
+              list_corner(actA && S > T, offA, S);
             }
           }
           FW_CYC(3);
