@@ -147,6 +147,20 @@ struct MergeInertialBAView {
   bool ran = false;                    // false: *pbStopFlag was set at entry (:4276), nothing written
 };
 
+// The graph Optimizer::OptimizeEssentialGraph assembles (Optimizer.cc:1477-1682; the second overload's at :1760-2020), flattened as
+// morb_optimize_essential_graph takes it.  Vertices in ascending mnId: the matrix is then a block band plus the loop edges' long rows.
+struct EssentialGraphView {
+  int nKF = 0, nE = 0, nMP = 0;
+  double* kfSim3 = nullptr;            // [nKF][8] in / out: qx qy qz qw tx ty tz s (CorrectedSim3's entry, or the pose with s = 1)
+  const uint8_t* kfFlags = nullptr;    // [nKF] bit 0 setFixed(true), bit 1 _fix_scale
+  const int* eI = nullptr;             // [nE] setVertex(0, .)
+  const int* eJ = nullptr;             // [nE] setVertex(1, .)
+  const double* eSji = nullptr;        // [nE][8] the measurement, in the reference's insertion order
+  float* mpPos = nullptr;              // [nMP][3] in / out: the point correction of :1707-1731 (nMP = 0: none)
+  const int* mpRef = nullptr;          // [nMP] vertex of mnCorrectedReference / of the reference keyframe, -1 = leave the point alone
+  int stats[4] = {0, 0, 0, 0};         // out: as morb_optimize_essential_graph's stats4
+  double chi2[2] = {0, 0};             // out: the active chi2 before and after
+};
 // What Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) reads and writes
 // (Optimizer.cc:2065-2322), per KF1 feature i < N as morb_optimize_sim3_batch (include/morb_hip.h) takes it: entry bits (matched, pMP1
 // present, pMP1 bad, pMP2 bad), world positions of pMP1 / pMP2, i2, the two keypoints and their mvInvLevelSigma2; the keyframe poses
@@ -268,6 +282,16 @@ class Optimizer {
     } else
     check(morb_merge_bundle_adjustment(o.h, g.nKF, g.kfPose, g.kfFixed, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.fx, g.fy, g.cx,
                                        g.cy, g.mbf, stop, g.eraseFlag.data(), g.levelFlag.data(), g.stats));
+  }
+
+  // static void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const
+  // KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool& bFixScale)  Optimizer.h:76-81, and the
+  // graph of the second overload (Optimizer.h:82-86), which differs in its per-vertex flags only.  The entry takes host arrays and stages them itself.
+  static void OptimizeEssentialGraph(EssentialGraphView& g, int device = 0) {
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    check(morb_optimize_essential_graph(o.h, g.nKF, g.kfSim3, g.kfFlags, g.nE, g.eI, g.eJ, g.eSji, g.nMP, g.mpPos, g.mpRef, g.stats, g.chi2));
   }
 
   // static int PoseInertialOptimizationLastKeyFrame(Frame* pFrame, bool bRecInit)  Optimizer.h:87 / ...LastFrame  Optimizer.h:88: one frame per call
@@ -446,6 +470,12 @@ class Optimizer {
   template <class KF, class MP, class Sim3T, class Mat77>
   static int OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale, Mat77& mAcumHessian,
                           const bool bAllPoints = false);
+
+  // (include/Optimizer.h:76-81; call site LoopClosing.cc:1206-1208): overload 1 of OptimizeEssentialGraph.  CorrMap = LoopClosing::KeyFrameAndPose
+  // (KeyFrame* -> g2o::Sim3), ConnMap = map<KeyFrame*, set<KeyFrame*>>
+  template <class MapT, class KF, class CorrMap, class ConnMap>
+  static void OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
+                                     const ConnMap& LoopConnections, const bool& bFixScale);
 
   // (include/Optimizer.h:46-53; call site Tracking.cc:2398) on the map of a monocular initialisation; any other map shape throws
   template <class MapT>

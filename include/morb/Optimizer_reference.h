@@ -13,6 +13,7 @@
 #include <cmath>
 #include <list>
 #include <map>
+#include <set>
 #include <tuple>
 
 #include "reference_glue.h"
@@ -565,6 +566,159 @@ int Optimizer::OptimizeSim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Si
     mAcumHessian.setZero();
   }
   return nIn;
+}
+
+// Optimizer::OptimizeEssentialGraph, overload 1 (Optimizer.cc:1443-1735), flattened for morb_optimize_essential_graph.  Vertices: the keyframes of
+// GetAllKeyFrames() that are not bad, in ascending mnId (the order of elimination); estimate = CorrectedSim3's entry or the pose with s = 1
+// (:1485-1495), fixed = the map's initial keyframe (:1497), _fix_scale = bFixScale (:1501).  Edges in the reference's insertion order and
+// under its conditions (:1514-1682); an edge whose endpoint has no vertex (a bad keyframe) is dropped, as g2o's addEdge drops it — its pair
+// still enters sInsertedEdges (:1548).  Points in GetAllMapPoints() order, mpRef = -1 for a bad one.
+struct EssentialGraphFlat {
+  std::vector<double> kfSim3, eSji;
+  std::vector<uint8_t> kfFlags;
+  std::vector<int> eI, eJ, mpRef;
+  std::vector<float> mpPos;
+  std::map<unsigned long, int> row;   // mnId -> vertex
+};
+namespace morb_glue {
+template <class S> inline void sim3_to8(const S& g, double* o) {
+  const auto q = g.rotation();
+  o[0] = q.x(); o[1] = q.y(); o[2] = q.z(); o[3] = q.w();
+  for (int k = 0; k < 3; ++k) o[4 + k] = g.translation()(k);
+  o[7] = g.scale();
+}
+template <class MapT, class KF, class CorrMap, class ConnMap>
+void flatten_essential_graph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3, const ConnMap& LoopConnections,
+                             bool bFixScale, EssentialGraphFlat& f) {
+  using Sim3T = typename CorrMap::mapped_type;
+  using Quat = typename std::decay<decltype(std::declval<Sim3T>().rotation())>::type;
+  using Vec3 = typename std::decay<decltype(std::declval<Sim3T>().translation())>::type;
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMPs = pMap->GetAllMapPoints();
+  const int minFeat = 100;
+  for (KF* pKF : vpKFs) if (!pKF->isBad()) f.row[pKF->mnId] = 0;
+  int n = 0;
+  for (auto& kv : f.row) kv.second = n++;
+  std::vector<Sim3T> vScw(n);
+  f.kfSim3.assign((size_t)n * 8, 0.0); f.kfFlags.assign(n, 0);
+  for (KF* pKF : vpKFs) {   // :1478-1507
+    if (pKF->isBad()) continue;
+    const int r = f.row[pKF->mnId];
+    const auto it = CorrectedSim3.find(pKF);
+    if (it != CorrectedSim3.end()) vScw[r] = it->second;
+    else {   // Sophus::SE3d Tcw = pKF->GetPose().cast<double>(); g2o::Sim3 Siw(Tcw.unit_quaternion(), Tcw.translation(), 1.0)
+      const auto Tcw = pKF->GetPose();
+      const auto q = Tcw.unit_quaternion();
+      const auto t = Tcw.translation();
+      Vec3 td;
+      for (int k = 0; k < 3; ++k) td(k) = (double)t(k);
+      vScw[r] = Sim3T(Quat((double)q.w(), (double)q.x(), (double)q.y(), (double)q.z()), td, 1.0);
+    }
+    sim3_to8(vScw[r], &f.kfSim3[(size_t)r * 8]);
+    f.kfFlags[r] = (pKF->mnId == pMap->GetInitKFid() ? 1 : 0) | (bFixScale ? 2 : 0);
+  }
+  auto rowOf = [&](unsigned long id) { const auto it = f.row.find(id); return it == f.row.end() ? -1 : it->second; };
+  auto add = [&](unsigned long idi, unsigned long idj, const Sim3T& Sji) {   // setVertex(0, i), setVertex(1, j); addEdge refuses a missing vertex
+    const int ri = rowOf(idi), rj = rowOf(idj);
+    if (ri < 0 || rj < 0) return;
+    f.eI.push_back(ri); f.eJ.push_back(rj);
+    f.eSji.resize(f.eSji.size() + 8);
+    sim3_to8(Sji, &f.eSji[f.eSji.size() - 8]);
+  };
+  auto nonCorrected = [&](KF* pKF, Sim3T& out) {   // NonCorrectedSim3's entry, else vScw (false: the keyframe has neither)
+    const auto it = NonCorrectedSim3.find(pKF);
+    if (it != NonCorrectedSim3.end()) { out = it->second; return true; }
+    const int r = rowOf(pKF->mnId);
+    if (r < 0) return false;
+    out = vScw[r];
+    return true;
+  };
+  std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+  for (auto mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {   // :1516-1550
+    KF* pKF = mit->first;
+    const unsigned long nIDi = pKF->mnId;
+    const int ri = rowOf(nIDi);
+    for (auto sit = mit->second.begin(); sit != mit->second.end(); ++sit) {
+      const unsigned long nIDj = (*sit)->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+      const int rj = rowOf(nIDj);
+      if (ri >= 0 && rj >= 0) add(nIDi, nIDj, vScw[rj] * vScw[ri].inverse());
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  for (KF* pKF : vpKFs) {   // :1553-1682
+    if (rowOf(pKF->mnId) < 0) continue;   // (every edge below has this keyframe as vertex 0)
+    Sim3T Siw;
+    nonCorrected(pKF, Siw);
+    const Sim3T Swi = Siw.inverse();
+    KF* pParentKF = pKF->GetParent();
+    Sim3T Sjw;
+    if (pParentKF && nonCorrected(pParentKF, Sjw)) add(pKF->mnId, pParentKF->mnId, Sjw * Swi);
+    const auto sLoopEdges = pKF->GetLoopEdges();
+    for (auto sit = sLoopEdges.begin(); sit != sLoopEdges.end(); ++sit) {
+      KF* pLKF = *sit;
+      if (pLKF->mnId < pKF->mnId && nonCorrected(pLKF, Sjw)) add(pKF->mnId, pLKF->mnId, Sjw * Swi);
+    }
+    const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); ++vit) {
+      KF* pKFn = *vit;
+      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn)) {
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+          if (nonCorrected(pKFn, Sjw)) add(pKF->mnId, pKFn->mnId, Sjw * Swi);
+        }
+      }
+    }
+    if (pKF->bImu && pKF->mPrevKF) {
+      KF* pPrev = static_cast<KF*>(pKF->mPrevKF);
+      if (nonCorrected(pPrev, Sjw)) add(pKF->mnId, pPrev->mnId, Sjw * Swi);
+    }
+  }
+  f.mpPos.assign(vpMPs.size() * 3, 0.f); f.mpRef.assign(vpMPs.size(), -1);
+  for (size_t i = 0; i < vpMPs.size(); ++i) {   // :1709-1723
+    auto* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    const unsigned long nIDr = pMP->mnCorrectedByKF == pCurKF->mnId ? (unsigned long)pMP->mnCorrectedReference : pMP->GetReferenceKeyFrame()->mnId;
+    f.mpRef[i] = rowOf(nIDr);
+    const auto X = pMP->GetWorldPos();
+    for (int k = 0; k < 3; ++k) f.mpPos[i * 3 + k] = X(k);
+  }
+}
+}  // namespace morb_glue
+
+template <class MapT, class KF, class CorrMap, class ConnMap>
+void Optimizer::OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
+                                       const ConnMap& LoopConnections, const bool& bFixScale) {
+  EssentialGraphFlat f;
+  morb_glue::flatten_essential_graph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale, f);
+  EssentialGraphView g;
+  g.nKF = (int)f.kfFlags.size(); g.nE = (int)f.eI.size(); g.nMP = (int)f.mpRef.size();
+  g.kfSim3 = f.kfSim3.data(); g.kfFlags = f.kfFlags.data(); g.eI = f.eI.data(); g.eJ = f.eJ.data(); g.eSji = f.eSji.data();
+  g.mpPos = g.nMP ? f.mpPos.data() : nullptr; g.mpRef = g.nMP ? f.mpRef.data() : nullptr;
+  if (g.nKF > 0) OptimizeEssentialGraph(g);   // optimize(20) (:1684-1687)
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);   // :1688
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  for (KF* pKFi : vpKFs) {   // SE3 pose recovering, Sim3 [sR t; 0 1] -> SE3 [R t / s; 0 1] (:1691-1705)
+    const auto it = f.row.find(pKFi->mnId);
+    if (it == f.row.end()) continue;   // (a bad keyframe has no vertex)
+    const double* S = &f.kfSim3[(size_t)it->second * 8];
+    // Sophus::SE3f Tiw(rotation().cast<float>(), translation().cast<float>() / s): the float vector divided by the scale as a float
+    const float s = (float)S[7];
+    const float p7[7] = {(float)S[0], (float)S[1], (float)S[2], (float)S[3], (float)S[4] / s, (float)S[5] / s, (float)S[6] / s};
+    pKFi->SetPose(morb_glue::make_se3<typename std::decay<decltype(pKFi->GetPose())>::type>(p7));
+  }
+  const auto vpMPs = pMap->GetAllMapPoints();
+  for (size_t i = 0; i < vpMPs.size(); ++i) {   // :1709-1731
+    auto* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    if (f.mpRef[i] >= 0) {
+      typename std::decay<decltype(pMP->GetWorldPos())>::type X;
+      for (int k = 0; k < 3; ++k) X(k) = f.mpPos[i * 3 + k];
+      pMP->SetWorldPos(X);
+    }
+    pMP->UpdateNormalAndDepth();
+  }
+  pMap->IncreaseChangeIndex();   // :1734
 }
 
 // The three Optimizer::InertialOptimization overloads (Optimizer.cc:2979-3428) around one flattening: GetAllKeyFrames() without the keyframes

@@ -1086,6 +1086,34 @@ int morb_merge_inertial_ba_fisheye(morb_optimizer*, int nKF, float* kfState21, c
                                    const float* rig28, const float* Tbc12,
                                    const uint8_t* pbStopFlag, uint8_t* eraseFlag, int* stats3);
 
+/* void static Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose&
+ * NonCorrectedSim3, const LoopClosing::KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool&
+ * bFixScale)  Optimizer.h:76-81, Optimizer.cc:1443-1735: the Sim3 pose graph LoopClosing::CorrectLoop optimises behind the fusion
+ * (LoopClosing.cc:1206-1208), on the graph the reference assembles at :1477-1682, flattened (HOST pointers); the graph of the second overload
+ * (:1737-2063, many fixed vertices) has the same form.  nKF vertices: kfSim3[k] = qx qy qz qw tx ty tz s, the g2o::Sim3 estimate
+ * (CorrectedSim3's entry, or the keyframe's pose with s = 1, :1485-1495), in and out; kfFlags[k] bit 0 = setFixed(true) (:1497), bit 1 =
+ * _fix_scale (:1501).  nE EdgeSim3 in insertion order: setVertex(0, eI), setVertex(1, eJ), measurement eSji[e] in the same eight doubles;
+ * information = identity, no robust kernel (:1537-1546).  Several edges may join one pair; an edge between two fixed vertices is a
+ * constant of chi2.  setUserLambdaInit(1e-16) (:1458), optimize(20) (:1686) with g2o's Levenberg-Marquardt over numeric Jacobians
+ * (EdgeSim3 has no linearizeOplus); H + lambda I is solved exactly by a block-sparse LDL^T over the envelope of the 7 x 7 block rows in
+ * the order of the vertices given (pass them by ascending mnId: the spanning tree and the covisibility edges then form a band, the loop
+ * edges a few long rows; DESIGN.md section 6, "Essential graph").  A vertex without an edge is not in g2o's active set: it is not in
+ * the system and keeps its bytes, as a fixed one does.  A free component with no path to a fixed vertex is gauge-free: it is neither
+ * detected nor repaired.  The point correction of :1707-1731 runs on the device behind the solve: mpRef[m] = the vertex of
+ * mnCorrectedReference or of the reference keyframe (:1714-1720), -1 = skip (a bad point); mpPos[m] becomes
+ * correctedSwr.map(Srw.map(P)) in FP64, then float, Srw being the vertex's value at entry.  nMP = 0 is allowed (mpPos, mpRef may be NULL).
+ * stats4 = {outer LM iterations, LM trials, vertices in the system, envelope blocks}; chi2 = the active chi2 before and after.
+ * MORB_ERR_INVALID: a NULL array, an index out of range, eI == eJ, a non-finite estimate or measurement or a scale <= 0;
+ * MORB_ERR_CAPACITY: the envelope exceeds what the handle may grow to (2^22 blocks); both before any launch, nothing written.  No free
+ * vertex has an edge (nE = 0 included; eI, eJ, eSji may then be NULL): MORB_OK, nothing written, stats4 and chi2 zero.  Left with the caller: the edge list itself (:1514-1682), SetPose
+ * with t / s (:1691-1705), UpdateNormalAndDepth and IncreaseChangeIndex (:1730-1734). */
+int morb_optimize_essential_graph(morb_optimizer*, int nKF, double* kfSim3, const uint8_t* kfFlags, int nE, const int* eI,
+                                  const int* eJ, const double* eSji, int nMP, float* mpPos, const int* mpRef, int* stats4,
+                                  double* chi2);
+/* acos(d[i]) and log(s[i]) as g2o::Sim3::log (types/sim3.h:151, :181) gets them inside morb_optimize_essential_graph: the device
+ * library's, for the tests that measure them against the host libm (HOST pointers, n > 0). */
+int morb_sim3_log_libm(morb_optimizer*, int n, const double* d, const double* s, double* acosOut, double* logOut);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,739 @@
+// Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1443-1735, and the graph of :1737-2063) for MI355X (gfx950): the Sim3 pose
+// graph of loop closing on the flattened graph.  Vertices are g2o::Sim3 estimates with a `fixed` and a `_fix_scale` flag each; edges are
+// EdgeSim3 (error log(Sji * Si * Sj^-1), types_seven_dof_expmap.h:106-114, information = identity, no robust kernel).
+//   * k_eg_linearize: the numeric Jacobians as BaseBinaryEdge::linearizeOplus takes them (base_binary_edge.hpp:131-205: central differences,
+//     delta = 1e-9, through VertexSim3Expmap::oplusImpl, which zeroes update[6] of a vertex with _fix_scale), one lane per (edge, vertex,
+//     column): 28 computeError calls per edge, grid-wide.  Sim3::log (types/sim3.h:148-230) with its eps branches on sigma and d and its
+//     3 x 3 partial-pivot LU; the product, inverse and exponential are sim3_math.h's, shared with OptimizeSim3.
+//   * k_eg_assemble: BaseBinaryEdge::constructQuadraticForm's non-robust branch.  Every 7 x 7 block and gradient is summed in edge
+//     insertion order over per-block lists (ba_host.h: csr_by_key), one lane per entry: no floating-point atomics.  A fixed endpoint
+//     contributes no block and no gradient; a scale column of a _fix_scale vertex is exactly zero and stays in the system (diagonal =
+//     lambda, right-hand side 0).
+//   * k_eg_factor: the block-sparse LDL^T.  7 unknowns per vertex over the whole map and no points to eliminate: in the caller's vertex order
+//     the matrix is a block band (spanning tree, covisibility) plus a few long rows (loop edges).  Storage is the block ENVELOPE: row i
+//     holds the blocks from its first non-zero column to i, and fill never leaves it.  One workgroup takes the block columns in sequence
+//     (left-looking); within a column the rows whose envelope covers it are parallel, one lane per (row, line of the block), the column's
+//     own row staged in LDS in panels of EG_PANEL blocks, scaled by D.  The forward substitution rides on the column loop.  No pivoting
+//     across blocks: H + lambda I is positive definite or the trial fails (ok2 = false), as the reference's Cholesky does.
+//   * k_eg_backsub: the backward substitution, scattering row by row, and the trial estimates exp(x) * S behind it.
+//   * k_eg_errors / k_eg_decide: the trial's chi2 per edge, summed in edge order by one lane; g2o's Levenberg-Marquardt decisions
+//     (lm_control.h) with setUserLambdaInit(1e-16) and optimize(20) on the device, the host queueing trials through ba_host.h's lm_slot_queue.
+//   * k_eg_finish: the point correction of :1707-1731 behind the solve.
+// A vertex without an edge is not in g2o's active set: it is not in the system and keeps its bytes.  A free component with no path to a
+// fixed vertex is gauge-free; it is neither detected nor repaired here (lambda keeps the factorisation defined, as it does in g2o).
+// acos and log inside Sim3::log are the device library's (tests/test_essential_graph_gpu.py measures them against the host libm).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "ba_host.h"
+#include "common.h"
+#include "handles.h"
+#include "internal_abi.h"
+#include "lm_control.h"
+#include "sim3_math.h"
+
+namespace {
+
+using namespace morb;
+
+constexpr int EG_NT = 256;
+constexpr int EG_PANEL = 32;                    // blocks of the column's own row staged in LDS at a time
+constexpr size_t EG_MAX_BLOCKS = (size_t)1 << 22;   // envelope blocks a handle may grow to (matrix and factor: 2 x 1.5 GiB)
+constexpr int EG_SUM = 2048;                    // values staged in LDS per pass of an ordered sum
+enum { EG_DONE = 0, EG_REBUILD, EG_ITS, EG_TRIALS, EG_OK2 };
+
+struct EgDev {
+  int nKF, nE, n, nBlocks, nMP, maxIts;
+  const int *eI, *eJ;        // [nE]
+  const double* eS;          // [nE][8] measurement Sji
+  const uint8_t* flags;      // [nKF] bit 0 fixed, bit 1 _fix_scale
+  const int* col;            // [nKF] block row of the system, -1: fixed or without an edge
+  const int* rowFirst;       // [n] first block column of row i's envelope
+  const int* rowOff;         // [n + 1] envelope block of (i, rowFirst[i])
+  const int* colStart;       // [n + 1] the rows below j whose envelope covers column j: colRows[colStart[j] .. colStart[j + 1]), ascending
+  const int* colRows;
+  const int* listStart;      // [nBlocks + 1] contributions of envelope block k, in edge order
+  const int* listItems;      // edge * 4 + kind: 0 / 1 diagonal block of vertex 0 / 1, 2 / 3 off-diagonal block whose row is vertex 0 / 1
+  double *S, *T;             // [nKF][8] current and trial estimates (qx qy qz qw tx ty tz s)
+  const double* S0;          // [nKF][8] the estimates at entry
+  double* J;                 // [nE][2][49] Jacobians, row-major (error component, unknown)
+  double* err;               // [nE][7] error at S
+  double* chiE;              // [nE] chi2 of the last computeError
+  double *H, *L;             // [nBlocks][49] H in the envelope; its factor (strictly lower blocks, unit-lower diagonal blocks)
+  double *b, *y, *x, *d;     // [7 n] right-hand side, work vector, solution, D of the factorisation
+  LmControl* lm;
+  double* chi2;              // [2] active chi2 before and after
+  int* lmi;                  // [8] EG_*
+  int* lmHost;               // mapped host words: [0] decided trials, [1] done
+  float* mp;                 // [nMP][3]
+  const int* mpRef;          // [nMP]
+};
+
+__device__ __forceinline__ Sim3d eg_load(const double* p) {
+  Sim3d s;
+  for (int i = 0; i < 4; ++i) s.q[i] = p[i];
+  for (int i = 0; i < 3; ++i) s.t[i] = p[4 + i];
+  s.s = p[7];
+  return s;
+}
+__device__ __forceinline__ void eg_store(double* p, const Sim3d& s) {
+  for (int i = 0; i < 4; ++i) p[i] = s.q[i];
+  for (int i = 0; i < 3; ++i) p[4 + i] = s.t[i];
+  p[7] = s.s;
+}
+
+// Sim3::log (types/sim3.h:148-230).  W.lu().solve(t) is Eigen's PartialPivLU of a 3 x 3 matrix: the row swaps are written out so that no
+// array is indexed by a run-time value.
+__device__ void sim3_log(const Sim3d& S, double* res) {
+  const double sigma = log(S.s);
+  const double x = S.q[0], y = S.q[1], z = S.q[2], w = S.q[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;   // Quaterniond::toRotationMatrix
+  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  const double R00 = 1 - (tyy + tzz), R01 = txy - twz, R02 = txz + twy, R10 = txy + twz, R11 = 1 - (txx + tzz), R12 = tyz - twx,
+               R20 = txz - twy, R21 = tyz + twx, R22 = 1 - (txx + tyy);
+  const double d = 0.5 * (R00 + R11 + R22 - 1);
+  const double dR[3] = {R21 - R12, R02 - R20, R10 - R01};   // deltaR(R)
+  const double eps = 0.00001;
+  double A, B, C, om[3];
+  if (fabs(sigma) < eps) {
+    C = 1;
+    if (d > 1 - eps) {
+      for (int i = 0; i < 3; ++i) om[i] = 0.5 * dR[i];
+      A = 1. / 2.; B = 1. / 6.;
+    } else {
+      const double theta = acos(d);
+      const double theta2 = theta * theta;
+      const double f = theta / (2 * sqrt(1 - d * d));
+      for (int i = 0; i < 3; ++i) om[i] = f * dR[i];
+      A = (1 - morbm64::cos_glibc(theta)) / (theta2);
+      B = (theta - morbm64::sin_glibc(theta)) / (theta2 * theta);
+    }
+  } else {
+    C = (S.s - 1) / sigma;
+    if (d > 1 - eps) {
+      const double sigma2 = sigma * sigma;
+      for (int i = 0; i < 3; ++i) om[i] = 0.5 * dR[i];
+      A = ((sigma - 1) * S.s + 1) / (sigma2);
+      B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+    } else {
+      const double theta = acos(d);
+      const double f = theta / (2 * sqrt(1 - d * d));
+      for (int i = 0; i < 3; ++i) om[i] = f * dR[i];
+      const double theta2 = theta * theta;
+      const double a = S.s * morbm64::sin_glibc(theta);
+      const double b = S.s * morbm64::cos_glibc(theta);
+      const double c = theta2 + sigma * sigma;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+    }
+  }
+  const double Om[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
+  double W[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double o2 = Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j] + Om[i * 3 + 2] * Om[6 + j];
+      W[i * 3 + j] = A * Om[i * 3 + j] + B * o2 + C * (i == j ? 1.0 : 0.0);
+    }
+  // PartialPivLU, rows a0 a1 a2 with their right-hand sides
+  double a0[4] = {W[0], W[1], W[2], S.t[0]}, a1[4] = {W[3], W[4], W[5], S.t[1]}, a2[4] = {W[6], W[7], W[8], S.t[2]};
+  auto swap4 = [](double* p, double* q) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const double v = p[i]; p[i] = q[i]; q[i] = v; }
+  };
+  {
+    int p = 0;
+    double big = fabs(a0[0]);
+    if (fabs(a1[0]) > big) { big = fabs(a1[0]); p = 1; }
+    if (fabs(a2[0]) > big) { big = fabs(a2[0]); p = 2; }
+    if (p == 1) swap4(a0, a1); else if (p == 2) swap4(a0, a2);
+  }
+  a1[0] /= a0[0]; a2[0] /= a0[0];
+  a1[1] -= a1[0] * a0[1]; a1[2] -= a1[0] * a0[2];
+  a2[1] -= a2[0] * a0[1]; a2[2] -= a2[0] * a0[2];
+  if (fabs(a2[1]) > fabs(a1[1])) swap4(a1, a2);
+  a2[1] /= a1[1];
+  a2[2] -= a2[1] * a1[2];
+  const double y0 = a0[3], y1 = a1[3] - a1[0] * y0, y2 = a2[3] - (a2[0] * y0 + a2[1] * y1);
+  const double u2 = y2 / a2[2];
+  const double u1 = (y1 - a1[2] * u2) / a1[1];
+  const double u0 = (y0 - (a0[1] * u1 + a0[2] * u2)) / a0[0];
+  res[0] = om[0]; res[1] = om[1]; res[2] = om[2];
+  res[3] = u0; res[4] = u1; res[5] = u2;
+  res[6] = sigma;
+}
+
+// EdgeSim3::computeError: log(C * v1 * v2^-1)
+__device__ __forceinline__ void eg_error(const Sim3d& M, const Sim3d& Si, const Sim3d& Sj, double* e) {
+  sim3_log(sim3_mul(sim3_mul(M, Si), sim3_inverse(Sj)), e);
+}
+// VertexSim3Expmap::oplusImpl with the update +-delta e_d (d in 0 .. 6), written without a run-time index; exp(+-1e-9) is glibc's (libm_f64.h)
+__device__ __forceinline__ Sim3d eg_perturbed(const Sim3d& S, int d, bool plus, bool fixScale) {
+  double u[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) u[i] = i == d ? (plus ? S3_DELTA : -S3_DELTA) : 0.0;
+  if (fixScale) u[6] = 0;
+  return sim3_mul(sim3_exp(u, u[6] == 0 ? 1.0 : morbm64::exp_glibc(u[6])), S);
+}
+
+// linearizeOplus of every edge at S: lanes 0 .. 6 of an edge's 16 take the columns of vertex 0, 7 .. 13 those of vertex 1, 14 the error
+__global__ __launch_bounds__(EG_NT) void k_eg_linearize(EgDev D) {
+  if (D.lmi[EG_DONE] || !D.lmi[EG_REBUILD]) return;
+  const int gid = blockIdx.x * EG_NT + threadIdx.x;
+  const int e = gid >> 4, k = gid & 15;
+  if (e >= D.nE || k >= 15) return;
+  const int vi = D.eI[e], vj = D.eJ[e];
+  const Sim3d M = eg_load(D.eS + (size_t)e * 8), Si = eg_load(D.S + (size_t)vi * 8), Sj = eg_load(D.S + (size_t)vj * 8);
+  if (k == 14) {
+    double er[7];
+    eg_error(M, Si, Sj, er);
+#pragma unroll
+    for (int r = 0; r < 7; ++r) D.err[(size_t)e * 7 + r] = er[r];
+    return;
+  }
+  const int side = k >= 7 ? 1 : 0, d = k - 7 * side;
+  const uint8_t fl = D.flags[side ? vj : vi];
+  if (fl & 1) return;   // (a fixed vertex has no Jacobian)
+  const bool fixScale = (fl & 2) != 0;
+  const Sim3d Sp = eg_perturbed(side ? Sj : Si, d, true, fixScale), Sm = eg_perturbed(side ? Sj : Si, d, false, fixScale);
+  double ep[7], em[7];
+  if (side) { eg_error(M, Si, Sp, ep); eg_error(M, Si, Sm, em); }
+  else { eg_error(M, Sp, Sj, ep); eg_error(M, Sm, Sj, em); }
+  const double scalar = 1.0 / (2 * S3_DELTA);
+  double* J = D.J + ((size_t)e * 2 + side) * 49;
+#pragma unroll
+  for (int r = 0; r < 7; ++r) J[r * 7 + d] = scalar * (ep[r] - em[r]);
+}
+
+// H in the envelope and b, every entry summed over its contributions in edge order
+__global__ __launch_bounds__(EG_NT) void k_eg_assemble(EgDev D) {
+  if (D.lmi[EG_DONE] || !D.lmi[EG_REBUILD]) return;
+  const size_t gid = (size_t)blockIdx.x * EG_NT + threadIdx.x;
+  const size_t nH = (size_t)D.nBlocks * 49;
+  if (gid < nH) {
+    const int blk = (int)(gid / 49), ent = (int)(gid % 49), r = ent / 7, c = ent % 7;
+    double acc = 0;
+    for (int q = D.listStart[blk]; q < D.listStart[blk + 1]; ++q) {
+      const int it = D.listItems[q], e = it >> 2, kind = it & 3;
+      // rows: the Jacobian of the block's row vertex; columns: that of its column vertex
+      const double* Jr = D.J + ((size_t)e * 2 + (kind & 1)) * 49;
+      const double* Jc = D.J + ((size_t)e * 2 + (kind < 2 ? (kind & 1) : 1 - (kind & 1))) * 49;
+      double v = 0;
+#pragma unroll
+      for (int k = 0; k < 7; ++k) v += Jr[k * 7 + r] * Jc[k * 7 + c];
+      acc += v;
+    }
+    D.H[gid] = acc;
+    return;
+  }
+  const size_t g = gid - nH;
+  if (g >= (size_t)D.n * 7) return;
+  const int a = (int)(g / 7), r = (int)(g % 7);
+  const int blk = D.rowOff[a + 1] - 1;   // the diagonal block's list names every edge of the vertex
+  double acc = 0;
+  for (int q = D.listStart[blk]; q < D.listStart[blk + 1]; ++q) {
+    const int it = D.listItems[q], e = it >> 2;
+    const double* Jr = D.J + ((size_t)e * 2 + (it & 1)) * 49;
+    const double* er = D.err + (size_t)e * 7;
+    double v = 0;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) v += Jr[k * 7 + r] * (-er[k]);
+    acc += v;
+  }
+  D.b[g] = acc;
+}
+
+// L_ij = S_ij L_jj^-T D_j^-1 for one line of a block below the diagonal (sL, sd: the diagonal block's factors in LDS); returns L_ij y_j
+__device__ __forceinline__ double eg_below_line(const double* s, const double* sL, const double* sd, const double* sy, double* l) {
+#pragma unroll
+  for (int c = 0; c < 7; ++c) {
+    double v = s[c];
+#pragma unroll
+    for (int p = 0; p < c; ++p) v -= (l[p] * sd[p]) * sL[c * 7 + p];
+    l[c] = v / sd[c];
+  }
+  double dot = 0;
+#pragma unroll
+  for (int c = 0; c < 7; ++c) dot += l[c] * sy[c];
+  return dot;
+}
+
+// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way.  One workgroup takes the block columns in sequence.
+__global__ __launch_bounds__(EG_NT) void k_eg_factor(EgDev D) {
+  __shared__ double sM[EG_PANEL * 49];
+  __shared__ double sS[49], sL[49], sd[7], sy[7];
+  __shared__ int sOk;
+  if (D.lmi[EG_DONE]) return;
+  const int t = threadIdx.x, n = D.n;
+  const double lambda = D.lm->lambda;
+  if (t == 0) sOk = 1;
+  for (int i = t; i < 7 * n; i += EG_NT) D.y[i] = D.b[i];
+  __threadfence_block();
+  __syncthreads();
+  for (int j = 0; j < n; ++j) {
+    const int fj = D.rowFirst[j];
+    const int cs = D.colStart[j];
+    const int nItems = (D.colStart[j + 1] - cs + 1) * 7;   // a lane per (row, line of its block); lines 0 .. 6 are the diagonal block's
+    const bool one = nItems <= EG_NT;                      // (the usual case: the lines stay in registers from the sums to the division)
+    const size_t rowJ = (size_t)D.rowOff[j];
+    const size_t diag = (rowJ + (j - fj)) * 49;
+    if (t >= 64 && t < 71) sy[t - 64] = D.y[(size_t)j * 7 + t - 64];   // (final since the last column's barrier)
+    double acc[7] = {0, 0, 0, 0, 0, 0, 0};
+    double* mine = nullptr;   // the line's place in the factor
+    int myRow = 0;
+    // ---- S_ij = H_ij - sum_k L_ik D_k L_jk^T, over the k both rows hold ----
+    for (int base = 0; base < nItems; base += EG_NT) {
+      const int item = base + t;
+      const bool valid = item < nItems;
+      int i = j, r = 0, fi = fj;
+      size_t rowI = rowJ;
+      if (valid) {
+        const int w = item / 7;
+        r = item - 7 * w;
+        if (w) { i = D.colRows[cs + w - 1]; fi = D.rowFirst[i]; rowI = (size_t)D.rowOff[i]; }
+        const double* h = D.H + (rowI + (j - fi)) * 49 + r * 7;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) acc[c] = h[c] + ((i == j && c == r) ? lambda : 0.0);
+        mine = D.L + (rowI + (j - fi)) * 49 + r * 7;
+        myRow = i;
+      }
+      for (int c0 = fj; c0 < j; c0 += EG_PANEL) {
+        const int c1 = min(c0 + EG_PANEL, j);
+        __syncthreads();
+        for (int q = t; q < (c1 - c0) * 49; q += EG_NT)   // M_jk = L_jk D_k
+          sM[q] = D.L[(rowJ + (c0 - fj)) * 49 + q] * D.d[(size_t)(c0 + q / 49) * 7 + q % 7];
+        __syncthreads();
+        if (valid) {
+          const double* lik = D.L + (rowI - fi) * 49 + r * 7;   // + 49 k: line r of L_ik
+          int k = max(c0, fi);
+          for (; k + 4 <= c1; k += 4) {   // four blocks' loads in flight
+            double l[4][7];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+              for (int p = 0; p < 7; ++p) l[u][p] = lik[(size_t)(k + u) * 49 + p];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const double* m = sM + (k + u - c0) * 49;
+#pragma unroll
+              for (int c = 0; c < 7; ++c) {
+                double s = 0;
+#pragma unroll
+                for (int p = 0; p < 7; ++p) s += l[u][p] * m[c * 7 + p];
+                acc[c] -= s;
+              }
+            }
+          }
+          for (; k < c1; ++k) {
+            double l[7];
+#pragma unroll
+            for (int p = 0; p < 7; ++p) l[p] = lik[(size_t)k * 49 + p];
+            const double* m = sM + (k - c0) * 49;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+              double s = 0;
+#pragma unroll
+              for (int p = 0; p < 7; ++p) s += l[p] * m[c * 7 + p];
+              acc[c] -= s;
+            }
+          }
+        }
+      }
+      if (valid) {
+        if (i == j) {
+#pragma unroll
+          for (int c = 0; c < 7; ++c) sS[r * 7 + c] = acc[c];
+        } else if (!one) {
+#pragma unroll
+          for (int c = 0; c < 7; ++c) mine[c] = acc[c];
+        }
+      }
+    }
+    if (!one) __threadfence_block();
+    __syncthreads();
+    // ---- the diagonal block: S_jj = L_jj D_j L_jj^T, and y_j = L_jj^-1 y_j ----
+    if (t == 0) {
+      double a[7][7], dd[7], yy[7];
+#pragma unroll
+      for (int r = 0; r < 7; ++r)
+#pragma unroll
+        for (int c = 0; c <= r; ++c) a[r][c] = sS[r * 7 + c];
+      bool ok = true;
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        double dc = a[c][c];
+#pragma unroll
+        for (int p = 0; p < c; ++p) dc -= (a[c][p] * dd[p]) * a[c][p];
+        dd[c] = dc;
+        ok = ok && dc > 0;
+#pragma unroll
+        for (int r = c + 1; r < 7; ++r) {
+          double v = a[r][c];
+#pragma unroll
+          for (int p = 0; p < c; ++p) v -= (a[r][p] * dd[p]) * a[c][p];
+          a[r][c] = v / dc;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 7; ++r) {
+        double v = sy[r];
+#pragma unroll
+        for (int p = 0; p < r; ++p) v -= a[r][p] * yy[p];
+        yy[r] = v;
+      }
+#pragma unroll
+      for (int r = 0; r < 7; ++r) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) sL[r * 7 + c] = c < r ? a[r][c] : (c == r ? 1.0 : 0.0);
+        sd[r] = dd[r];
+        sy[r] = yy[r];
+      }
+      if (!ok) sOk = 0;
+    }
+    __syncthreads();
+    if (!sOk) break;   // (the same for every lane)
+    if (t < 49) D.L[diag + t] = sL[t];
+    if (t >= 64 && t < 71) { D.d[(size_t)j * 7 + t - 64] = sd[t - 64]; D.y[(size_t)j * 7 + t - 64] = sy[t - 64]; }
+    // ---- the rows below: L_ij = S_ij L_jj^-T D_j^-1, and y_i -= L_ij y_j ----
+    if (one) {
+      if (t >= 7 && t < nItems) {
+        double l[7];
+        const double dot = eg_below_line(acc, sL, sd, sy, l);
+#pragma unroll
+        for (int c = 0; c < 7; ++c) mine[c] = l[c];
+        D.y[(size_t)myRow * 7 + (t % 7)] -= dot;
+      }
+    } else {
+      for (int item = 7 + t; item < nItems; item += EG_NT) {
+        const int w = item / 7, r = item - 7 * w;
+        const int i = D.colRows[cs + w - 1];
+        double* o = D.L + ((size_t)D.rowOff[i] + (j - D.rowFirst[i])) * 49 + r * 7;
+        double s[7], l[7];
+#pragma unroll
+        for (int c = 0; c < 7; ++c) s[c] = o[c];
+        const double dot = eg_below_line(s, sL, sd, sy, l);
+#pragma unroll
+        for (int c = 0; c < 7; ++c) o[c] = l[c];
+        D.y[(size_t)i * 7 + r] -= dot;
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  if (t == 0) D.lmi[EG_OK2] = sOk;
+}
+
+// x = L^-T D^-1 y: row i, once final, is taken out of the rows above it; then the trial estimates exp(x_v) * S_v.  One workgroup.
+__global__ __launch_bounds__(EG_NT) void k_eg_backsub(EgDev D) {
+  __shared__ double sLb[2][49], sx[7];
+  if (D.lmi[EG_DONE]) return;
+  const int t = threadIdx.x, n = D.n;
+  if (D.lmi[EG_OK2]) {
+    for (int i = t; i < 7 * n; i += EG_NT) D.x[i] = D.y[i] / D.d[i];
+    if (t >= 192 && t < 241) sLb[(n - 1) & 1][t - 192] = D.L[((size_t)D.rowOff[n] - 1) * 49 + t - 192];
+    __threadfence_block();
+    __syncthreads();
+    for (int i = n - 1; i >= 0; --i) {
+      const int fi = D.rowFirst[i];
+      const size_t rowI = (size_t)D.rowOff[i];
+      if (t == 0) {   // x_i = L_ii^-T z_i
+        const double* sL = sLb[i & 1];
+        double z[7], xx[7];
+#pragma unroll
+        for (int r = 0; r < 7; ++r) z[r] = D.x[(size_t)i * 7 + r];
+#pragma unroll
+        for (int r = 6; r >= 0; --r) {
+          double v = z[r];
+#pragma unroll
+          for (int p = r + 1; p < 7; ++p) v -= sL[p * 7 + r] * xx[p];
+          xx[r] = v;
+        }
+#pragma unroll
+        for (int r = 0; r < 7; ++r) { sx[r] = xx[r]; D.x[(size_t)i * 7 + r] = xx[r]; }
+      }
+      __syncthreads();
+      if (i > 0 && t >= 192 && t < 241) sLb[(i - 1) & 1][t - 192] = D.L[((size_t)D.rowOff[i] - 1) * 49 + t - 192];   // the next row's diagonal block
+      const int cnt = (i - fi) * 7;
+      for (int item = t; item < cnt; item += EG_NT) {
+        const int kk = item / 7, c = item - 7 * kk;
+        const double* lik = D.L + (rowI + kk) * 49;
+        double dot = 0;
+#pragma unroll
+        for (int r = 0; r < 7; ++r) dot += lik[r * 7 + c] * sx[r];
+        D.x[(size_t)(fi + kk) * 7 + c] -= dot;
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+  // ---- the trial estimates (a failed factorisation leaves x as it was: g2o still applies it) ----
+  for (int v = t; v < D.nKF; v += EG_NT) {
+    const int a = D.col[v];
+    Sim3d S = eg_load(D.S + (size_t)v * 8);
+    if (a >= 0) {
+      double u[7];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) u[k] = D.x[(size_t)a * 7 + k];
+      if (D.flags[v] & 2) u[6] = 0;
+      // (|u[6]| >= 512 would overflow the scale anyway: there the device library's exp)
+      S = sim3_mul(sim3_exp(u, fabs(u[6]) < 512.0 ? morbm64::exp_glibc(u[6]) : exp(u[6])), S);
+    }
+    eg_store(D.T + (size_t)v * 8, S);
+  }
+}
+
+// computeError of every edge at the trial estimates (trial != 0) or at S
+__global__ __launch_bounds__(EG_NT) void k_eg_errors(EgDev D, int trial) {
+  if (D.lmi[EG_DONE]) return;
+  const int e = blockIdx.x * EG_NT + threadIdx.x;
+  if (e >= D.nE) return;
+  const double* X = trial ? D.T : D.S;
+  double er[7];
+  eg_error(eg_load(D.eS + (size_t)e * 8), eg_load(X + (size_t)D.eI[e] * 8), eg_load(X + (size_t)D.eJ[e] * 8), er);
+  double chi = 0;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) chi += er[k] * er[k];
+  D.chiE[e] = chi;
+}
+
+// sum of n values in index order: the workgroup stages them in LDS, lane 0 adds.  term(i) is evaluated by every lane.
+template <class Term>
+__device__ double eg_ordered_sum(double* buf, int n, Term&& term) {
+  double acc = 0;
+  for (int base = 0; base < n; base += EG_SUM) {
+    const int m = min(EG_SUM, n - base);
+    for (int q = threadIdx.x; q < m; q += EG_NT) buf[q] = term(base + q);
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int q = 0; q < m; ++q) acc += buf[q];
+    __syncthreads();
+  }
+  return acc;   // (lane 0's)
+}
+
+// init != 0: behind the first computeActiveErrors; else g2o's decision after a trial (lm_control.h).  One workgroup.
+__global__ __launch_bounds__(EG_NT) void k_eg_decide(EgDev D, int init) {
+  __shared__ double buf[EG_SUM];
+  __shared__ int sKeep;
+  if (D.lmi[EG_DONE]) return;
+  const int t = threadIdx.x;
+  const double chi = eg_ordered_sum(buf, D.nE, [&](int e) { return D.chiE[e]; });
+  LmControl c = *D.lm;
+  if (init) {
+    if (t == 0) {
+      lm_begin(c, 1e-16, 0.0);   // setUserLambdaInit(1e-16)
+      lm_iteration(c, chi);
+      *D.lm = c;
+      D.chi2[0] = chi; D.chi2[1] = chi;
+      D.lmi[EG_REBUILD] = 1; D.lmi[EG_ITS] = 0; D.lmi[EG_TRIALS] = 0; D.lmi[EG_OK2] = 1;
+    }
+    return;
+  }
+  const double lambda = c.lambda;
+  const double gain = eg_ordered_sum(buf, 7 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b[i]); });   // computeScale()
+  if (t == 0) {
+    bool again = false;
+    const bool keep = lm_trial(c, chi, D.lmi[EG_OK2] != 0, gain, &again);
+    int its = D.lmi[EG_ITS], done = 0, rebuild = 0;
+    const int trials = D.lmi[EG_TRIALS] + 1;
+    if (!again) {
+      ++its;
+      done = (lm_iteration_done(c) || its >= D.maxIts) ? 1 : 0;
+      if (!done) { lm_iteration(c, c.currentChi); rebuild = 1; }
+    }
+    *D.lm = c;
+    D.chi2[1] = c.currentChi;
+    D.lmi[EG_ITS] = its; D.lmi[EG_TRIALS] = trials; D.lmi[EG_REBUILD] = rebuild; D.lmi[EG_DONE] = done;
+    sKeep = keep ? 1 : 0;
+    __hip_atomic_store(D.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(D.lmHost + 0, trials, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided trials: the host queues trial k + 2 when it sees k
+  }
+  __syncthreads();
+  if (sKeep)
+    for (int i = t; i < 8 * D.nKF; i += EG_NT) D.S[i] = D.T[i];
+}
+
+// the point correction (:1707-1731): correctedSwr.map(Srw.map(P)) in FP64, then float
+__global__ __launch_bounds__(EG_NT) void k_eg_finish(EgDev D) {
+  const int m = blockIdx.x * EG_NT + threadIdx.x;
+  if (m >= D.nMP) return;
+  const int v = D.mpRef[m];
+  if (v < 0) return;
+  const Sim3d Srw = eg_load(D.S0 + (size_t)v * 8), Swr = sim3_inverse(eg_load(D.S + (size_t)v * 8));
+  const double P[3] = {(double)D.mp[m * 3], (double)D.mp[m * 3 + 1], (double)D.mp[m * 3 + 2]};
+  double a[3], o[3];
+  sim3_map(Srw, P, a);
+  sim3_map(Swr, a, o);
+  for (int k = 0; k < 3; ++k) D.mp[m * 3 + k] = (float)o[k];
+}
+
+// acos(d[i]) and log(s[i]) as sim3_log computes them
+__global__ __launch_bounds__(EG_NT) void k_eg_libm(int n, const double* d, const double* s, double* acosOut, double* logOut) {
+  const int i = blockIdx.x * EG_NT + threadIdx.x;
+  if (i >= n) return;
+  acosOut[i] = acos(d[i]);
+  logOut[i] = log(s[i]);
+}
+
+}  // namespace
+
+extern "C" int morb_optimize_essential_graph(morb_optimizer* o, int nKF, double* kfSim3, const uint8_t* kfFlags, int nE, const int* eI,
+                                             const int* eJ, const double* eSji, int nMP, float* mpPos, const int* mpRef, int* stats4,
+                                             double* chi2) {
+  MORB_REQUIRE(o && kfSim3 && kfFlags && stats4 && chi2 && (nE == 0 || (eI && eJ && eSji)) && (nMP == 0 || (mpPos && mpRef)), MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nKF > 0 && nE >= 0 && nMP >= 0, MORB_ERR_INVALID, "bad sizes");   // (nE = 0: no free vertex has an edge, below)
+  auto sound = [](const double* s) {
+    for (int k = 0; k < 8; ++k) if (!std::isfinite(s[k])) return false;
+    return s[7] > 0;
+  };
+  for (int v = 0; v < nKF; ++v) MORB_REQUIRE(sound(kfSim3 + (size_t)v * 8), MORB_ERR_INVALID, "a non-finite estimate or a scale <= 0");
+  for (int e = 0; e < nE; ++e) {
+    MORB_REQUIRE(eI[e] >= 0 && eI[e] < nKF && eJ[e] >= 0 && eJ[e] < nKF, MORB_ERR_INVALID, "edge index out of range");
+    MORB_REQUIRE(eI[e] != eJ[e], MORB_ERR_INVALID, "an edge joins a vertex to itself");
+    MORB_REQUIRE(sound(eSji + (size_t)e * 8), MORB_ERR_INVALID, "a non-finite measurement or a scale <= 0");
+  }
+  for (int m = 0; m < nMP; ++m) MORB_REQUIRE(mpRef[m] >= -1 && mpRef[m] < nKF, MORB_ERR_INVALID, "point reference out of range");
+  // ---- the system: free vertices with an edge, in the caller's order; the envelope of its block rows ----
+  std::vector<int> col(nKF, -1);
+  {
+    std::vector<char> used(nKF, 0);
+    for (int e = 0; e < nE; ++e) used[eI[e]] = used[eJ[e]] = 1;
+    int n = 0;
+    for (int v = 0; v < nKF; ++v) if (!(kfFlags[v] & 1) && used[v]) col[v] = n++;
+  }
+  int n = 0;
+  for (int v = 0; v < nKF; ++v) n += col[v] >= 0;
+  if (!n) {   // no free vertex has an edge: nothing to optimise, nothing written
+    for (int k = 0; k < 4; ++k) stats4[k] = 0;
+    chi2[0] = chi2[1] = 0;
+    return MORB_OK;
+  }
+  std::vector<int> rowFirst(n), rowOff(n + 1, 0);
+  for (int r = 0; r < n; ++r) rowFirst[r] = r;
+  for (int e = 0; e < nE; ++e) {
+    const int a = col[eI[e]], b = col[eJ[e]];
+    if (a >= 0 && b >= 0) rowFirst[std::max(a, b)] = std::min(rowFirst[std::max(a, b)], std::min(a, b));
+  }
+  size_t total = 0;
+  for (int r = 0; r < n; ++r) total += (size_t)(r - rowFirst[r] + 1);
+  MORB_REQUIRE(total <= EG_MAX_BLOCKS, MORB_ERR_CAPACITY, "the envelope of the essential graph exceeds what the handle may grow to");
+  for (int r = 0; r < n; ++r) rowOff[r + 1] = rowOff[r] + (r - rowFirst[r] + 1);
+  const int nBlocks = rowOff[n];
+  std::vector<int> colStart(n + 1, 0), colRows((size_t)std::max(nBlocks - n, 1));
+  for (int i = 0; i < n; ++i) for (int j = rowFirst[i]; j < i; ++j) ++colStart[j + 1];
+  for (int j = 0; j < n; ++j) colStart[j + 1] += colStart[j];
+  {
+    std::vector<int> fill(colStart.begin(), colStart.end() - 1);
+    for (int i = 0; i < n; ++i) for (int j = rowFirst[i]; j < i; ++j) colRows[fill[j]++] = i;
+  }
+  // contributions to the envelope blocks, in edge order
+  std::vector<int> cKey, cItem;
+  cKey.reserve((size_t)3 * nE); cItem.reserve((size_t)3 * nE);
+  for (int e = 0; e < nE; ++e) {
+    const int a = col[eI[e]], b = col[eJ[e]];
+    if (a >= 0) { cKey.push_back(rowOff[a + 1] - 1); cItem.push_back(e * 4 + 0); }
+    if (b >= 0) { cKey.push_back(rowOff[b + 1] - 1); cItem.push_back(e * 4 + 1); }
+    if (a >= 0 && b >= 0) {
+      if (a > b) { cKey.push_back(rowOff[a] + (b - rowFirst[a])); cItem.push_back(e * 4 + 2); }
+      else { cKey.push_back(rowOff[b] + (a - rowFirst[b])); cItem.push_back(e * 4 + 3); }
+    }
+  }
+  std::vector<int> listStart, listPos;
+  csr_by_key(cKey.data(), (int)cKey.size(), nBlocks, listStart, listPos);
+  std::vector<int> listItems(listPos.size());
+  for (size_t q = 0; q < listPos.size(); ++q) listItems[q] = cItem[listPos[q]];
+
+  MORB_ENTER(st, o, nullptr);
+  EgDev D;
+  memset(&D, 0, sizeof D);
+  D.nKF = nKF; D.nE = nE; D.n = n; D.nBlocks = nBlocks; D.nMP = nMP; D.maxIts = 20;
+  ArenaCarver A;
+  auto carve = [&]() {
+    D.eI = (const int*)A.take(eI, sizeof(int) * nE); D.eJ = (const int*)A.take(eJ, sizeof(int) * nE);
+    D.eS = (const double*)A.take(eSji, sizeof(double) * 8 * nE);
+    D.flags = (const uint8_t*)A.take(kfFlags, nKF); D.col = (const int*)A.take(col.data(), sizeof(int) * nKF);
+    D.rowFirst = (const int*)A.take(rowFirst.data(), sizeof(int) * n); D.rowOff = (const int*)A.take(rowOff.data(), sizeof(int) * (n + 1));
+    D.colStart = (const int*)A.take(colStart.data(), sizeof(int) * (n + 1)); D.colRows = (const int*)A.take(colRows.data(), sizeof(int) * colRows.size());
+    D.listStart = (const int*)A.take(listStart.data(), sizeof(int) * listStart.size());
+    D.listItems = (const int*)A.take(listItems.data(), sizeof(int) * listItems.size());
+    D.S = (double*)A.take(kfSim3, sizeof(double) * 8 * nKF); D.S0 = (const double*)A.take(kfSim3, sizeof(double) * 8 * nKF);
+    if (nMP) { D.mp = (float*)A.take(mpPos, sizeof(float) * 3 * nMP); D.mpRef = (const int*)A.take(mpRef, sizeof(int) * nMP); }
+    D.T = (double*)A.take(nullptr, sizeof(double) * 8 * nKF);
+    D.J = (double*)A.take(nullptr, sizeof(double) * 98 * nE); D.err = (double*)A.take(nullptr, sizeof(double) * 7 * nE);
+    D.chiE = (double*)A.take(nullptr, sizeof(double) * nE);
+    D.H = (double*)A.take(nullptr, sizeof(double) * 49 * (size_t)nBlocks); D.L = (double*)A.take(nullptr, sizeof(double) * 49 * (size_t)nBlocks);
+    D.b = (double*)A.take(nullptr, sizeof(double) * 7 * n); D.y = (double*)A.take(nullptr, sizeof(double) * 7 * n);
+    D.x = (double*)A.take(nullptr, sizeof(double) * 7 * n); D.d = (double*)A.take(nullptr, sizeof(double) * 7 * n);
+    D.lm = (LmControl*)A.take(nullptr, sizeof(LmControl)); D.chi2 = (double*)A.take(nullptr, sizeof(double) * 2);
+    D.lmi = (int*)A.take(nullptr, sizeof(int) * 8);
+  };
+  carve();   // (dry: sizes)
+  char *arena = nullptr, *stage = nullptr;
+  { const int rc = grow(o->essentialGraph, A.uploadBytes() + A.deviceBytes(), &arena); if (rc != MORB_OK) return rc; }
+  { const int rc = grow(o->stage, A.uploadBytes(), &stage); if (rc != MORB_OK) return rc; }
+  A.bind(arena, stage);
+  carve();
+  if (!A.ok()) { set_error("the two carve passes of OptimizeEssentialGraph differ"); return MORB_ERR_HIP; }
+  int *hostw = nullptr, *hostwDev = nullptr;
+  MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
+  D.lmHost = hostwDev;
+  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  MORB_HIP_CHECK(hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st));   // the one upload
+  // the workspace is reused from call to call: what the first kernels expect to find zero is cleared behind the carve
+  MORB_HIP_CHECK(hipMemsetAsync(D.lmi, 0, sizeof(int) * 8, st));
+  MORB_HIP_CHECK(hipMemsetAsync(D.lm, 0, sizeof(LmControl), st));
+  MORB_HIP_CHECK(hipMemsetAsync(D.x, 0, sizeof(double) * 7 * n, st));   // the solver's x before the first solve
+  MORB_HIP_CHECK(hipMemsetAsync(D.J, 0, sizeof(double) * 98 * nE, st));   // (the Jacobian of a fixed vertex is never written, and never read)
+
+  const int edgeBlocks = div_up(nE, EG_NT);
+  const size_t asmItems = (size_t)nBlocks * 49 + (size_t)n * 7;
+  hipLaunchKernelGGL(k_eg_errors, dim3(edgeBlocks), dim3(EG_NT), 0, st, D, 0);   // computeActiveErrors
+  hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 1);
+  MORB_HIP_CHECK(hipGetLastError());
+  // a slot is one trial: at most 20 iterations of 10 trials
+  const int q = lm_slot_queue(200, hostw + 0, hostw + 1, [&](int) {
+    hipLaunchKernelGGL(k_eg_linearize, dim3(div_up(nE * 16, EG_NT)), dim3(EG_NT), 0, st, D);   // (both run only behind an accepted trial)
+    hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)((asmItems + EG_NT - 1) / EG_NT)), dim3(EG_NT), 0, st, D);
+    hipLaunchKernelGGL(k_eg_factor, dim3(1), dim3(EG_NT), 0, st, D);
+    hipLaunchKernelGGL(k_eg_backsub, dim3(1), dim3(EG_NT), 0, st, D);
+    hipLaunchKernelGGL(k_eg_errors, dim3(edgeBlocks), dim3(EG_NT), 0, st, D, 1);
+    hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 0);
+    if (hipGetLastError() != hipSuccess) { set_error("OptimizeEssentialGraph: a trial's launch failed"); return (int)MORB_ERR_HIP; }
+    return (int)MORB_OK;
+  }, [&]() {
+    const hipError_t e = hipStreamQuery(st);
+    if (e != hipSuccess && e != hipErrorNotReady) set_error("OptimizeEssentialGraph: %s while waiting for the LM decision", hipGetErrorString(e));
+    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
+  }, []() {});
+  if (q < 0) return MORB_ERR_HIP;
+  if (nMP) hipLaunchKernelGGL(k_eg_finish, dim3(div_up(nMP, EG_NT)), dim3(EG_NT), 0, st, D);
+  MORB_HIP_CHECK(hipGetLastError());
+  int hi[8];
+  MORB_HIP_CHECK(hipMemcpyAsync(hi, D.lmi, sizeof hi, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipMemcpyAsync(chi2, D.chi2, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipMemcpyAsync(kfSim3, D.S, sizeof(double) * 8 * nKF, hipMemcpyDeviceToHost, st));
+  if (nMP) MORB_HIP_CHECK(hipMemcpyAsync(mpPos, D.mp, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipStreamSynchronize(st));   // (also drains a queue that ran out of slots before the words are reset again)
+  stats4[0] = hi[EG_ITS]; stats4[1] = hi[EG_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
+  return MORB_OK;
+}
+
+extern "C" int morb_sim3_log_libm(morb_optimizer* o, int n, const double* d, const double* s, double* acosOut, double* logOut) {
+  MORB_REQUIRE(o && d && s && acosOut && logOut && n > 0, MORB_ERR_INVALID, "bad argument");
+  MORB_ENTER(st, o, nullptr);
+  double* w = nullptr;
+  { const int rc = grow(o->essentialGraph, sizeof(double) * 4 * (size_t)n, &w); if (rc != MORB_OK) return rc; }
+  MORB_HIP_CHECK(hipMemcpyAsync(w, d, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  MORB_HIP_CHECK(hipMemcpyAsync(w + n, s, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_eg_libm, dim3(div_up(n, EG_NT)), dim3(EG_NT), 0, st, n, (const double*)w, (const double*)(w + n), w + 2 * (size_t)n, w + 3 * (size_t)n);
+  MORB_HIP_CHECK(hipGetLastError());
+  MORB_HIP_CHECK(hipMemcpyAsync(acosOut, w + 2 * (size_t)n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipMemcpyAsync(logOut, w + 3 * (size_t)n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipStreamSynchronize(st));
+  return MORB_OK;
+}

@@ -374,6 +374,32 @@ class Optimizer:
                                                    ptr(erase), ptr(level), ptr(stats)))
         return a[0], a[2], erase, level, stats
 
+    def OptimizeEssentialGraph(self, kfSim3, kfFlags, eI, eJ, eSji, mpPos=None, mpRef=None):
+        """Optimizer::OptimizeEssentialGraph, the Sim3 pose graph of loop closing, on host numpy arrays (see morb_optimize_essential_graph).
+        kfSim3: float64 [nKF, 8] (qx qy qz qw tx ty tz s); kfFlags: bit 0 fixed, bit 1 _fix_scale; edges (eI, eJ) with measurements eSji
+        [nE, 8] in insertion order; mpPos float32 [nMP, 3] with mpRef = the vertex each point is corrected through (-1: left alone), or None.
+        Returns (kfSim3, mpPos, stats4, chi2): stats4 = outer iterations, trials, vertices in the system, envelope blocks."""
+        S = np.ascontiguousarray(kfSim3, np.float64).reshape(-1, 8).copy()
+        fl = np.ascontiguousarray(kfFlags, np.uint8)
+        ei, ej = np.ascontiguousarray(eI, np.int32), np.ascontiguousarray(eJ, np.int32)
+        M = np.ascontiguousarray(eSji, np.float64).reshape(-1, 8)
+        assert len(fl) == len(S) and len(ei) == len(ej) == len(M)
+        mp = np.zeros((0, 3), np.float32) if mpPos is None else np.ascontiguousarray(mpPos, np.float32).reshape(-1, 3).copy()
+        ref = np.zeros(0, np.int32) if mpRef is None else np.ascontiguousarray(mpRef, np.int32)
+        assert len(ref) == len(mp)
+        stats, chi2 = np.zeros(4, np.int32), np.zeros(2, np.float64)
+        check(self._L.morb_optimize_essential_graph(self._h, len(S), ptr(S), ptr(fl), len(ei), ptr(ei), ptr(ej), ptr(M), len(mp),
+                                                    ptr(mp) if len(mp) else None, ptr(ref) if len(mp) else None, ptr(stats), ptr(chi2)))
+        return S, mp, stats, chi2
+
+    def Sim3LogLibm(self, d, s):
+        """acos(d) and log(s) as the device computes them inside Sim3::log (see morb_sim3_log_libm)."""
+        d, s = np.ascontiguousarray(d, np.float64), np.ascontiguousarray(s, np.float64)
+        assert d.shape == s.shape and d.ndim == 1
+        a, l = np.zeros_like(d), np.zeros_like(d)
+        check(self._L.morb_sim3_log_libm(self._h, len(d), ptr(d), ptr(s), ptr(a), ptr(l)))
+        return a, l
+
     def MergeInertialBA(self, kfState, kfKind, mpPos, eKF, eMP, eObs, eInvSigma2, iKF1, iKF2, iPre, cam, Tbc, stop_flag=None, rig=None):
         """Optimizer::MergeInertialBA(pCurrKF, pMergeKF, pbStopFlag, pMap, corrPoses), the welding bundle adjustment of an inertial map
         merge, on host numpy arrays (see morb_merge_inertial_ba).  kfKind: 0 free (15 unknowns), 1 fixed with an IMU state, 2 fixed observer,

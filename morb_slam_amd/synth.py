@@ -1705,3 +1705,122 @@ def make_merge_inertial_ba_problem(n_cur=5, n_merge=5, n_cov=4, n_points=300, se
                Tbc12=np.concatenate([Tbc[:3, :3].ravel(), Tbc[:3, 3]]).astype(np.float32), cam=cam, true=true, truePts=X, gross=gross,
                rig28=tumvi_rig28() if kb8 else None)
     return out
+
+
+# ---- the essential graph of loop closing (Optimizer::OptimizeEssentialGraph) ---------------------------------------------------------
+def _sim3_mul(a, b):
+    """g2o::Sim3::operator* on (qx qy qz qw tx ty tz s)."""
+    return np.concatenate([_quat_mul(a[:4], b[:4]), a[7] * _quat_rot(a[:4], b[4:7]) + a[4:7], [a[7] * b[7]]])
+
+
+def _sim3_inv(a):
+    qc = np.array([-a[0], -a[1], -a[2], a[3]])
+    return np.concatenate([qc, _quat_rot(qc, (-1.0 / a[7]) * a[4:7]), [1.0 / a[7]]])
+
+
+def make_essential_graph_problem(n_kf=30, band=3, n_loop=1, fix_scale=False, seed=0, n_old_loops=0, loop_kf=1, loop_rot_deg=3.0,
+                                 loop_trans=0.3, loop_scale=1.03, fixed=(0,), fix_scale_on=None, duplicate_every=0, fixed_pair_edge=False,
+                                 isolated=(), n_points=0, drift_rot_deg=0.3, drift_scale=0.004, meas_noise=0.0, fixed_pair_offset=0.05):
+    """A loop closure as LoopClosing::CorrectLoop hands it to Optimizer::OptimizeEssentialGraph, flattened for morb_optimize_essential_graph.
+    Keyframes 0 .. n_kf-1 (ascending mnId) move along a drifting trajectory (per-step rotation and scale drift); keyframe i's parent is the
+    nearest earlier keyframe that is not `isolated`; covisibility (weight >= 100) joins keyframes at most `band` apart.  The current keyframe
+    is the last one, the loop keyframe `loop_kf`.  CorrectedSim3 / NonCorrectedSim3 are propagated as LoopClosing.cc:1105-1180 does: the
+    current keyframe's corrected Sim3 is Sim3(loop error) * Scw, every keyframe connected to it (within `band`) gets Sic * corrected Scw, and
+    its non-corrected Sim3 is its pose with s = 1.  Edges in the insertion order of Optimizer.cc:1514-1682 (vertex 0 = the later keyframe):
+    the LoopConnections of the connected keyframes to the n_loop keyframes around the loop keyframe (measured between the ESTIMATES), then
+    per keyframe its spanning-tree edge, its old loop edges (n_old_loops random long-range pairs), its covisibility edges and, every
+    `duplicate_every`-th keyframe, an inertial edge that doubles the spanning-tree one; all measured between the NON-corrected poses.
+    fixed: fixed vertices; fix_scale sets _fix_scale on all vertices (overload 1), fix_scale_on on those listed only (overload 2's shape).
+    fixed_pair_edge adds an edge between two fixed vertices, its measurement off by fixed_pair_offset (a constant of chi2); `isolated` keyframes carry no edge.  Points: n_points with a reference
+    keyframe each (every tenth -1).  Returns a dict: kfSim3, kfFlags, eI, eJ, eSji, mpPos, mpRef, plus cur, loop, connected, S_true."""
+    rng = np.random.default_rng(seed)
+    iso = set(int(i) for i in isolated)
+    # true poses: a camera on a circle looking along its tangent; Scw with s = 1
+    S_true = np.zeros((n_kf, 8))
+    for i in range(n_kf):
+        a = 2 * np.pi * i / max(n_kf, 8)
+        q = _quat_from_rotvec(np.array([0.05 * np.sin(3 * a), -a, 0.03 * np.cos(2 * a)]))
+        c = np.array([6 * np.cos(a), 0.2 * np.sin(5 * a), 6 * np.sin(a)])
+        S_true[i] = np.concatenate([q, -_quat_rot(q, c), [1.0]])
+    # drifted estimates (SE3: s = 1): the relative motions pick up a rotation and a scale error each
+    S_est = np.zeros_like(S_true)
+    S_est[0] = S_true[0]
+    for i in range(1, n_kf):
+        rel = _sim3_mul(S_true[i], _sim3_inv(S_true[i - 1]))
+        dq = _quat_from_rotvec(np.deg2rad(drift_rot_deg) * (np.array([0.2, 1.0, 0.1]) + 0.3 * rng.normal(size=3)))
+        rel = np.concatenate([_quat_mul(dq, rel[:4]), (1.0 - drift_scale * (1 + 0.3 * rng.normal())) * _quat_rot(dq, rel[4:7]), [1.0]])
+        S_est[i] = _sim3_mul(rel, S_est[i - 1])
+        S_est[i, :4] /= np.linalg.norm(S_est[i, :4])
+    cur = n_kf - 1
+    while cur in iso:
+        cur -= 1
+    connected = [i for i in range(max(0, cur - band), cur + 1) if i not in iso]
+    # the loop error: Sim3(rotation, translation, scale) in front of the current keyframe's Scw
+    lq = _quat_from_rotvec(np.deg2rad(loop_rot_deg) * np.array([0.3, 0.9, -0.2]) / np.linalg.norm([0.3, 0.9, -0.2]))
+    G = np.concatenate([lq, loop_trans * np.array([0.5, -0.2, 0.8]), [1.0 if fix_scale else loop_scale]])
+    S_cur_corr = _sim3_mul(G, S_est[cur])
+    vS = S_est.copy()   # vScw: CorrectedSim3's entry, or the pose
+    for i in connected:
+        Sic = _sim3_mul(S_est[i], _sim3_inv(S_est[cur]))
+        vS[i] = S_cur_corr if i == cur else _sim3_mul(Sic, S_cur_corr)
+    eI, eJ, eS = [], [], []
+
+    def add(i, j, Si, Sj):
+        M = _sim3_mul(Sj, _sim3_inv(Si))
+        if meas_noise:
+            M = _sim3_mul(np.concatenate([_quat_from_rotvec(meas_noise * rng.normal(size=3)), meas_noise * rng.normal(size=3), [1.0]]), M)
+        eI.append(i); eJ.append(j); eS.append(M)
+
+    inserted = set()
+    loop_side = [j for j in range(max(0, loop_kf - n_loop // 2), max(0, loop_kf - n_loop // 2) + n_loop) if j not in iso and j not in connected]
+    if n_loop:
+        for i in connected:
+            for j in loop_side:
+                if i == cur or j == loop_kf or (i + j) % 2 == 0:   # (the pair (cur, loop) always; the others by their weight)
+                    add(i, j, vS[i], vS[j])
+                    inserted.add((min(i, j), max(i, j)))
+    old = []
+    for _ in range(n_old_loops):
+        i = int(rng.integers(n_kf // 2, n_kf)); j = int(rng.integers(0, max(1, n_kf // 4)))
+        if i not in iso and j not in iso and i != j:
+            old.append((i, j))
+    parent = {}
+    for i in range(n_kf):
+        if i in iso:
+            continue
+        p = i - 1
+        while p >= 0 and p in iso:
+            p -= 1
+        parent[i] = p
+        if p >= 0:
+            add(i, p, S_est[i], S_est[p])
+        for (a, b) in old:
+            if a == i and b < i:
+                add(i, b, S_est[i], S_est[b])
+        for j in range(i - 1, max(-1, i - band - 1), -1):
+            if j in iso or j == p or (j, i) in inserted:
+                continue
+            add(i, j, S_est[i], S_est[j])
+        if duplicate_every and p >= 0 and i % duplicate_every == 0:
+            add(i, p, S_est[i], S_est[p])
+    flags = np.zeros(n_kf, np.uint8)
+    for f in fixed:
+        flags[f] |= 1
+    if fix_scale_on is not None:
+        for f in fix_scale_on:
+            flags[f] |= 2
+    elif fix_scale:
+        flags |= 2
+    if fixed_pair_edge:
+        fx = [f for f in fixed if f not in iso]
+        if len(fx) >= 2:
+            add(fx[1], fx[0], vS[fx[1]], _sim3_mul(np.concatenate([_quat_from_rotvec([0.01, 0.02, -0.01]), [fixed_pair_offset, 0.0, 0.02], [1.0]]), vS[fx[0]]))
+    mpPos = np.zeros((n_points, 3), np.float32); mpRef = np.full(n_points, -1, np.int32)
+    for m in range(n_points):
+        r = int(rng.integers(0, n_kf))
+        Swr = _sim3_inv(vS[r])
+        Xc = np.array([rng.uniform(-2, 2), rng.uniform(-1, 1), rng.uniform(2, 8)])
+        mpPos[m] = (Swr[7] * _quat_rot(Swr[:4], Xc) + Swr[4:7]).astype(np.float32)
+        mpRef[m] = -1 if m % 10 == 9 else r
+    return dict(kfSim3=vS, kfFlags=flags, eI=np.array(eI, np.int32), eJ=np.array(eJ, np.int32), eSji=np.array(eS, np.float64).reshape(-1, 8),
+                mpPos=mpPos, mpRef=mpRef, cur=cur, loop=loop_kf, connected=connected, S_true=S_true)
