@@ -161,6 +161,23 @@ struct EssentialGraphView {
   int stats[4] = {0, 0, 0, 0};         // out: as morb_optimize_essential_graph's stats4
   double chi2[2] = {0, 0};             // out: the active chi2 before and after
 };
+// The graph Optimizer::OptimizeEssentialGraph4DoF assembles (Optimizer.cc:5194-5426), flattened as morb_optimize_essential_graph_4dof takes
+// it.  Vertices in ascending mnId.  A vertex's camera pose and body state are given independently, as ImuCamPose's constructors fill them.
+struct PoseGraph4DoFView {
+  int nKF = 0, nE = 0, nMP = 0;
+  double* kfPose = nullptr;            // [nKF][12] in / out: Rcw[0] row-major, tcw[0]
+  const double* kfBody = nullptr;      // [nKF][12] Rwb row-major, twb at entry
+  const uint8_t* kfFixed = nullptr;    // [nKF] setFixed(true)
+  float Tcb12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // mImuCalib.mTcb: R row-major, t
+  const int* eI = nullptr;             // [nE] setVertex(0, .)
+  const int* eJ = nullptr;             // [nE] setVertex(1, .)
+  const double* eTij = nullptr;        // [nE][12] dRij row-major, dtij, in the reference's insertion order
+  float* mpPos = nullptr;              // [nMP][3] in / out: the point correction of :5451-5470 (nMP = 0: none)
+  const int* mpRef = nullptr;          // [nMP] vertex of the reference keyframe, -1 = leave the point alone
+  const double* kfScw = nullptr;       // [nKF][8] vScw at entry (qx qy qz qw tx ty tz s), read when nMP > 0
+  int stats[4] = {0, 0, 0, 0};         // out: as morb_optimize_essential_graph_4dof's stats4
+  double chi2[2] = {0, 0};             // out: the active chi2 before and after
+};
 // What Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) reads and writes
 // (Optimizer.cc:2065-2322), per KF1 feature i < N as morb_optimize_sim3_batch (include/morb_hip.h) takes it: entry bits (matched, pMP1
 // present, pMP1 bad, pMP2 bad), world positions of pMP1 / pMP2, i2, the two keypoints and their mvInvLevelSigma2; the keyframe poses
@@ -292,6 +309,17 @@ class Optimizer {
     std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
     morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
     check(morb_optimize_essential_graph(o.h, g.nKF, g.kfSim3, g.kfFlags, g.nE, g.eI, g.eJ, g.eSji, g.nMP, g.mpPos, g.mpRef, g.stats, g.chi2));
+  }
+
+  // static void OptimizeEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const
+  // KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections)  Optimizer.h:89-94.  It shares the loop-closing
+  // handle's workspace with OptimizeEssentialGraph; the handle's mutex keeps the two apart.
+  static void OptimizeEssentialGraph4DoF(PoseGraph4DoFView& g, int device = 0) {
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    check(morb_optimize_essential_graph_4dof(o.h, g.nKF, g.kfPose, g.kfBody, g.kfFixed, g.Tcb12, g.nE, g.eI, g.eJ, g.eTij, g.nMP, g.mpPos, g.mpRef, g.kfScw,
+                                             g.stats, g.chi2));
   }
 
   // static int PoseInertialOptimizationLastKeyFrame(Frame* pFrame, bool bRecInit)  Optimizer.h:87 / ...LastFrame  Optimizer.h:88: one frame per call
@@ -476,6 +504,11 @@ class Optimizer {
   template <class MapT, class KF, class CorrMap, class ConnMap>
   static void OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
                                      const ConnMap& LoopConnections, const bool& bFixScale);
+
+  // (include/Optimizer.h:89-94; call site LoopClosing.cc:1201-1203): the pose graph of an inertial map whose IMU is initialised
+  template <class MapT, class KF, class CorrMap, class ConnMap>
+  static void OptimizeEssentialGraph4DoF(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
+                                         const ConnMap& LoopConnections);
 
   // (include/Optimizer.h:46-53; call site Tracking.cc:2398) on the map of a monocular initialisation; any other map shape throws
   template <class MapT>

@@ -11,6 +11,7 @@
 // KannalaBrandt8 rigs (mpCamera2 != NULL) dispatch to the *_fisheye entry points.  See reference_glue.h for what has been compiled.
 #pragma once
 #include <cmath>
+#include <cstring>
 #include <list>
 #include <map>
 #include <set>
@@ -719,6 +720,215 @@ void Optimizer::OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, cons
     pMP->UpdateNormalAndDepth();
   }
   pMap->IncreaseChangeIndex();   // :1734
+}
+
+// Optimizer::OptimizeEssentialGraph4DoF (Optimizer.cc:5163-5472), flattened for morb_optimize_essential_graph_4dof.  Vertices: the keyframes
+// of GetAllKeyFrames() that are not bad, in ascending mnId; VertexPose4DoF(pKF) from the keyframe's float members, or
+// VertexPose4DoF(Rwc, twc, pKF) from CorrectedSim3's inverse (:5201-5214); fixed = pLoopKF (:5216).  mImuCalib.mTcb is taken from the first
+// keyframe with a vertex: one calibration per map.  Edges in the reference's insertion order and under its conditions (:5236-5426); each
+// measurement is the rotation and the translation of the Sim3 product.  Where the reference is undefined this skips: its normal-edge and
+// write-back loops do not test isBad(), and mPrevKF or a loop connection may name a keyframe without a vertex (optimizer.vertex() is NULL
+// there) — an edge with such an endpoint is dropped (its pair still enters sInsertedEdges), a keyframe without a vertex contributes no
+// edges of its own and keeps its pose, and a point whose reference keyframe has no vertex keeps its position.
+struct PoseGraph4DoFFlat {
+  std::vector<double> kfPose, kfBody, kfScw, eTij;
+  std::vector<uint8_t> kfFixed;
+  std::vector<int> eI, eJ, mpRef;
+  std::vector<float> mpPos;
+  float Tcb12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  std::map<unsigned long, int> row;   // mnId -> vertex
+};
+namespace morb_glue {
+template <class Q> inline void quat_to_matrix(const Q& q, double* R) {   // Eigen::QuaternionBase::toRotationMatrix
+  const double x = q.x(), y = q.y(), z = q.z(), w = q.w();
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+  R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+inline void matrix_to_quat(const double* m, double* q) {   // Eigen::Quaterniond(Matrix3d): x y z w
+  double t = m[0] + m[4] + m[8];
+  if (t > 0) {
+    t = std::sqrt(t + 1.0);
+    q[3] = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
+  } else {
+    int i = 0;
+    if (m[4] > m[0]) i = 1;
+    if (m[8] > m[i * 4]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = std::sqrt(m[i * 4] - m[j * 4] - m[k * 4] + 1.0);
+    q[i] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (m[k * 3 + j] - m[j * 3 + k]) * t;
+    q[j] = (m[j * 3 + i] + m[i * 3 + j]) * t;
+    q[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
+  }
+}
+template <class MapT, class KF, class CorrMap, class ConnMap>
+void flatten_pose_graph_4dof(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3, const ConnMap& LoopConnections,
+                             PoseGraph4DoFFlat& f) {
+  using Sim3T = typename CorrMap::mapped_type;
+  using Quat = typename std::decay<decltype(std::declval<Sim3T>().rotation())>::type;
+  using Vec3 = typename std::decay<decltype(std::declval<Sim3T>().translation())>::type;
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMPs = pMap->GetAllMapPoints();
+  const int minFeat = 100;
+  for (KF* pKF : vpKFs) if (!pKF->isBad()) f.row[pKF->mnId] = 0;
+  int n = 0;
+  for (auto& kv : f.row) kv.second = n++;
+  std::vector<Sim3T> vScw(n);
+  f.kfPose.assign((size_t)n * 12, 0.0); f.kfBody.assign((size_t)n * 12, 0.0); f.kfScw.assign((size_t)n * 8, 0.0); f.kfFixed.assign(n, 0);
+  bool haveCalib = false;
+  double Rcb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tcb[3] = {0, 0, 0};
+  for (KF* pKF : vpKFs) {   // :5194-5224
+    if (pKF->isBad()) continue;
+    if (!haveCalib) {
+      const auto R = pKF->mImuCalib.mTcb.rotationMatrix();
+      const auto t = pKF->mImuCalib.mTcb.translation();
+      for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) f.Tcb12[r * 3 + c] = R(r, c); f.Tcb12[9 + r] = t(r); }
+      for (int k = 0; k < 9; ++k) Rcb[k] = (double)f.Tcb12[k];
+      for (int k = 0; k < 3; ++k) tcb[k] = (double)f.Tcb12[9 + k];
+      haveCalib = true;
+    }
+    const int r = f.row[pKF->mnId];
+    double* P = &f.kfPose[(size_t)r * 12];
+    double* B = &f.kfBody[(size_t)r * 12];
+    const auto it = CorrectedSim3.find(pKF);
+    if (it != CorrectedSim3.end()) {   // VertexPose4DoF(Rwc, twc, pKF): G2oTypes.cc:120-146
+      vScw[r] = it->second;
+      const Sim3T Swc = it->second.inverse();
+      double Rwc[9], twc[3];
+      quat_to_matrix(Swc.rotation(), Rwc);
+      for (int k = 0; k < 3; ++k) twc[k] = Swc.translation()(k);
+      for (int a = 0; a < 3; ++a) {
+        B[9 + a] = Rwc[a * 3] * tcb[0] + Rwc[a * 3 + 1] * tcb[1] + Rwc[a * 3 + 2] * tcb[2] + twc[a];
+        for (int c = 0; c < 3; ++c) {
+          B[a * 3 + c] = Rwc[a * 3] * Rcb[c] + Rwc[a * 3 + 1] * Rcb[3 + c] + Rwc[a * 3 + 2] * Rcb[6 + c];
+          P[a * 3 + c] = Rwc[c * 3 + a];
+        }
+      }
+      for (int a = 0; a < 3; ++a) P[9 + a] = -(P[a * 3] * twc[0] + P[a * 3 + 1] * twc[1] + P[a * 3 + 2] * twc[2]);
+    } else {   // VertexPose4DoF(pKF): the float members, cast
+      const auto Tcw = pKF->GetPose();
+      const auto q = Tcw.unit_quaternion();
+      const auto t = Tcw.translation();
+      Vec3 td;
+      for (int k = 0; k < 3; ++k) td(k) = (double)t(k);
+      vScw[r] = Sim3T(Quat((double)q.w(), (double)q.x(), (double)q.y(), (double)q.z()), td, 1.0);
+      const auto Rcw = pKF->GetRotation();
+      const auto tcw = pKF->GetTranslation();
+      const auto Rwb = pKF->GetImuRotation();
+      const auto twb = pKF->GetImuPosition();
+      for (int a = 0; a < 3; ++a) {
+        for (int c = 0; c < 3; ++c) { P[a * 3 + c] = (double)Rcw(a, c); B[a * 3 + c] = (double)Rwb(a, c); }
+        P[9 + a] = (double)tcw(a); B[9 + a] = (double)twb(a);
+      }
+    }
+    sim3_to8(vScw[r], &f.kfScw[(size_t)r * 8]);
+    f.kfFixed[r] = pKF == pLoopKF ? 1 : 0;
+  }
+  auto rowOf = [&](unsigned long id) { const auto it = f.row.find(id); return it == f.row.end() ? -1 : it->second; };
+  auto add = [&](unsigned long idi, unsigned long idj, const Sim3T& Sij) {   // setVertex(0, i), setVertex(1, j)
+    const int ri = rowOf(idi), rj = rowOf(idj);
+    if (ri < 0 || rj < 0) return;
+    f.eI.push_back(ri); f.eJ.push_back(rj);
+    f.eTij.resize(f.eTij.size() + 12);
+    double* T = &f.eTij[f.eTij.size() - 12];
+    quat_to_matrix(Sij.rotation(), T);
+    for (int k = 0; k < 3; ++k) T[9 + k] = Sij.translation()(k);
+  };
+  auto nonCorrected = [&](KF* pKF, Sim3T& out) {   // NonCorrectedSim3's entry, else vScw (false: the keyframe has neither)
+    const auto it = NonCorrectedSim3.find(pKF);
+    if (it != NonCorrectedSim3.end()) { out = it->second; return true; }
+    const int r = rowOf(pKF->mnId);
+    if (r < 0) return false;
+    out = vScw[r];
+    return true;
+  };
+  std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+  for (auto mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {   // :5238-5274
+    KF* pKF = mit->first;
+    const unsigned long nIDi = pKF->mnId;
+    const int ri = rowOf(nIDi);
+    for (auto sit = mit->second.begin(); sit != mit->second.end(); ++sit) {
+      const unsigned long nIDj = (*sit)->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+      const int rj = rowOf(nIDj);
+      if (ri >= 0 && rj >= 0) add(nIDi, nIDj, vScw[ri] * vScw[rj].inverse());
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  for (KF* pKF : vpKFs) {   // :5277-5426 (pParentKF is NULL there: no spanning-tree edge)
+    if (rowOf(pKF->mnId) < 0) continue;
+    Sim3T Siw, Sjw;
+    nonCorrected(pKF, Siw);
+    KF* prevKF = static_cast<KF*>(pKF->mPrevKF);
+    if (prevKF && nonCorrected(prevKF, Sjw)) add(pKF->mnId, prevKF->mnId, Siw * Sjw.inverse());
+    const auto sLoopEdges = pKF->GetLoopEdges();
+    for (auto sit = sLoopEdges.begin(); sit != sLoopEdges.end(); ++sit) {
+      KF* pLKF = *sit;
+      if (pLKF->mnId < pKF->mnId && nonCorrected(pLKF, Sjw)) add(pKF->mnId, pLKF->mnId, Siw * Sjw.inverse());
+    }
+    const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); ++vit) {
+      KF* pKFn = *vit;
+      if (pKFn && pKFn != prevKF && pKFn != pKF->mNextKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+          if (nonCorrected(pKFn, Sjw)) add(pKF->mnId, pKFn->mnId, Siw * Sjw.inverse());
+        }
+      }
+    }
+  }
+  f.mpPos.assign(vpMPs.size() * 3, 0.f); f.mpRef.assign(vpMPs.size(), -1);
+  for (size_t i = 0; i < vpMPs.size(); ++i) {   // :5451-5461
+    auto* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    f.mpRef[i] = rowOf(pMP->GetReferenceKeyFrame()->mnId);
+    const auto X = pMP->GetWorldPos();
+    for (int k = 0; k < 3; ++k) f.mpPos[i * 3 + k] = X(k);
+  }
+}
+}  // namespace morb_glue
+
+template <class MapT, class KF, class CorrMap, class ConnMap>
+void Optimizer::OptimizeEssentialGraph4DoF(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
+                                           const ConnMap& LoopConnections) {
+  PoseGraph4DoFFlat f;
+  morb_glue::flatten_pose_graph_4dof(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, f);
+  PoseGraph4DoFView g;
+  g.nKF = (int)f.kfFixed.size(); g.nE = (int)f.eI.size(); g.nMP = (int)f.mpRef.size();
+  g.kfPose = f.kfPose.data(); g.kfBody = f.kfBody.data(); g.kfFixed = f.kfFixed.data(); g.eI = f.eI.data(); g.eJ = f.eJ.data(); g.eTij = f.eTij.data();
+  std::memcpy(g.Tcb12, f.Tcb12, sizeof g.Tcb12);
+  g.mpPos = g.nMP ? f.mpPos.data() : nullptr; g.mpRef = g.nMP ? f.mpRef.data() : nullptr; g.kfScw = g.nMP ? f.kfScw.data() : nullptr;
+  if (g.nKF > 0) OptimizeEssentialGraph4DoF(g);   // optimize(20) (:5428-5430)
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);   // :5432
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  for (KF* pKFi : vpKFs) {   // :5435-5448: g2o::Sim3(Ri, ti, 1.) -> Sophus::SE3d -> float
+    const auto it = f.row.find(pKFi->mnId);
+    if (it == f.row.end()) continue;   // (a bad keyframe has no vertex)
+    const double* P = &f.kfPose[(size_t)it->second * 12];
+    double q[4];
+    morb_glue::matrix_to_quat(P, q);
+    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const float p7[7] = {(float)(q[0] / nq), (float)(q[1] / nq), (float)(q[2] / nq), (float)(q[3] / nq), (float)P[9], (float)P[10], (float)P[11]};
+    pKFi->SetPose(morb_glue::make_se3<typename std::decay<decltype(pKFi->GetPose())>::type>(p7));
+  }
+  const auto vpMPs = pMap->GetAllMapPoints();
+  for (size_t i = 0; i < vpMPs.size(); ++i) {   // :5451-5470
+    auto* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    if (f.mpRef[i] >= 0) {
+      typename std::decay<decltype(pMP->GetWorldPos())>::type X;
+      for (int k = 0; k < 3; ++k) X(k) = f.mpPos[i * 3 + k];
+      pMP->SetWorldPos(X);
+    }
+    pMP->UpdateNormalAndDepth();
+  }
+  pMap->IncreaseChangeIndex();   // :5471
 }
 
 // The three Optimizer::InertialOptimization overloads (Optimizer.cc:2979-3428) around one flattening: GetAllKeyFrames() without the keyframes

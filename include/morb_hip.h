@@ -1114,6 +1114,33 @@ int morb_optimize_essential_graph(morb_optimizer*, int nKF, double* kfSim3, cons
  * library's, for the tests that measure them against the host libm (HOST pointers, n > 0). */
 int morb_sim3_log_libm(morb_optimizer*, int n, const double* d, const double* s, double* acosOut, double* logOut);
 
+/* void static Optimizer::OptimizeEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose&
+ * NonCorrectedSim3, const LoopClosing::KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections)
+ * Optimizer.h:89-94, Optimizer.cc:5163-5472: the pose graph LoopClosing::CorrectLoop optimises in an inertial map whose IMU is
+ * initialised (LoopClosing.cc:1200-1203), on the graph the reference assembles at :5194-5426, flattened (HOST pointers).  nKF vertices
+ * VertexPose4DoF (G2oTypes.h:155-189): kfPose[k] = Rcw[0] row-major and tcw[0], in and out; kfBody[k] = Rwb row-major and twb at entry.
+ * The two are given independently, as the reference's constructors fill them (from a keyframe's float members, or from
+ * CorrectedSim3.inverse()): the first computeError reads kfPose as given, and the camera pose follows the body state from the first
+ * accepted update on (UpdateW, G2oTypes.cc:218-248, with its counter of five updates).  The unknowns are (yaw, tx, ty, tz) of the body
+ * in the world.  kfFixed[k] != 0 = setFixed(true) (:5216).  Tcb12 = mImuCalib.mTcb, one calibration for the map.  nE Edge4DoF
+ * (G2oTypes.h:816-842) in insertion order: setVertex(0, eI), setVertex(1, eJ), eTij[e] = dRij row-major and dtij; information
+ * diag(1e3, 1e3, 1, 1, 1, 1), no robust kernel (:5231-5234).  Several edges may join one pair; an edge between two fixed vertices is a
+ * constant of chi2.  optimize(20) (:5430) with g2o's Levenberg-Marquardt over numeric Jacobians; no setUserLambdaInit: the first lambda is
+ * 1e-5 * the largest diagonal entry of the first system.  H + lambda I is solved exactly by a block LDL^T over the envelope of the 4 x 4
+ * block rows in the order of the vertices given (pass them by ascending mnId; DESIGN.md section 6, "4-DoF pose graph").  A vertex without
+ * an edge is not in g2o's active set: it is not in the system and keeps its bytes, as a fixed one does.  The point correction of
+ * :5451-5470 runs on the device behind the solve: mpRef[m] = the vertex of the reference keyframe, -1 = skip (a bad point); mpPos[m]
+ * becomes correctedSwr.map(Srw.map(P)) in FP64, then float, with Srw = kfScw[ref] = qx qy qz qw tx ty tz s, the g2o::Sim3 vScw at entry
+ * (it keeps the scale of a CorrectedSim3 entry), and correctedSwr the inverse of (Rcw, tcw, 1) of the result.  nMP = 0 is allowed
+ * (mpPos, mpRef, kfScw may be NULL).  stats4 = {outer LM iterations, LM trials, vertices in the system, envelope blocks}; chi2 = the active
+ * chi2 before and after.  MORB_ERR_INVALID: a NULL array, an index out of range, eI == eJ, a non-finite value, a scale <= 0 in kfScw;
+ * MORB_ERR_CAPACITY: the envelope exceeds what the handle may grow to (2^22 blocks); both before any launch, nothing written.  No free
+ * vertex has an edge (nE = 0 included; eI, eJ, eTij may then be NULL): MORB_OK, nothing written, stats4 and chi2 zero.  Left with the
+ * caller: the edge list itself (:5236-5426), SetPose (:5435-5448), UpdateNormalAndDepth and IncreaseChangeIndex (:5468-5471). */
+int morb_optimize_essential_graph_4dof(morb_optimizer*, int nKF, double* kfPose, const double* kfBody, const uint8_t* kfFixed,
+                                       const float* Tcb12, int nE, const int* eI, const int* eJ, const double* eTij, int nMP,
+                                       float* mpPos, const int* mpRef, const double* kfScw, int* stats4, double* chi2);
+
 #ifdef __cplusplus
 }
 #endif

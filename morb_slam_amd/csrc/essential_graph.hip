@@ -31,6 +31,7 @@
 
 #include "ba_host.h"
 #include "common.h"
+#include "envelope_plan.h"
 #include "handles.h"
 #include "internal_abi.h"
 #include "lm_control.h"
@@ -598,55 +599,17 @@ extern "C" int morb_optimize_essential_graph(morb_optimizer* o, int nKF, double*
     MORB_REQUIRE(sound(eSji + (size_t)e * 8), MORB_ERR_INVALID, "a non-finite measurement or a scale <= 0");
   }
   for (int m = 0; m < nMP; ++m) MORB_REQUIRE(mpRef[m] >= -1 && mpRef[m] < nKF, MORB_ERR_INVALID, "point reference out of range");
-  // ---- the system: free vertices with an edge, in the caller's order; the envelope of its block rows ----
-  std::vector<int> col(nKF, -1);
-  {
-    std::vector<char> used(nKF, 0);
-    for (int e = 0; e < nE; ++e) used[eI[e]] = used[eJ[e]] = 1;
-    int n = 0;
-    for (int v = 0; v < nKF; ++v) if (!(kfFlags[v] & 1) && used[v]) col[v] = n++;
-  }
-  int n = 0;
-  for (int v = 0; v < nKF; ++v) n += col[v] >= 0;
-  if (!n) {   // no free vertex has an edge: nothing to optimise, nothing written
+  EnvelopePlan P;
+  const EnvelopeFit fit = plan_envelope(nKF, kfFlags, nE, eI, eJ, EG_MAX_BLOCKS, P);
+  if (fit == EnvelopeFit::Empty) {   // no free vertex has an edge: nothing to optimise, nothing written
     for (int k = 0; k < 4; ++k) stats4[k] = 0;
     chi2[0] = chi2[1] = 0;
     return MORB_OK;
   }
-  std::vector<int> rowFirst(n), rowOff(n + 1, 0);
-  for (int r = 0; r < n; ++r) rowFirst[r] = r;
-  for (int e = 0; e < nE; ++e) {
-    const int a = col[eI[e]], b = col[eJ[e]];
-    if (a >= 0 && b >= 0) rowFirst[std::max(a, b)] = std::min(rowFirst[std::max(a, b)], std::min(a, b));
-  }
-  size_t total = 0;
-  for (int r = 0; r < n; ++r) total += (size_t)(r - rowFirst[r] + 1);
-  MORB_REQUIRE(total <= EG_MAX_BLOCKS, MORB_ERR_CAPACITY, "the envelope of the essential graph exceeds what the handle may grow to");
-  for (int r = 0; r < n; ++r) rowOff[r + 1] = rowOff[r] + (r - rowFirst[r] + 1);
-  const int nBlocks = rowOff[n];
-  std::vector<int> colStart(n + 1, 0), colRows((size_t)std::max(nBlocks - n, 1));
-  for (int i = 0; i < n; ++i) for (int j = rowFirst[i]; j < i; ++j) ++colStart[j + 1];
-  for (int j = 0; j < n; ++j) colStart[j + 1] += colStart[j];
-  {
-    std::vector<int> fill(colStart.begin(), colStart.end() - 1);
-    for (int i = 0; i < n; ++i) for (int j = rowFirst[i]; j < i; ++j) colRows[fill[j]++] = i;
-  }
-  // contributions to the envelope blocks, in edge order
-  std::vector<int> cKey, cItem;
-  cKey.reserve((size_t)3 * nE); cItem.reserve((size_t)3 * nE);
-  for (int e = 0; e < nE; ++e) {
-    const int a = col[eI[e]], b = col[eJ[e]];
-    if (a >= 0) { cKey.push_back(rowOff[a + 1] - 1); cItem.push_back(e * 4 + 0); }
-    if (b >= 0) { cKey.push_back(rowOff[b + 1] - 1); cItem.push_back(e * 4 + 1); }
-    if (a >= 0 && b >= 0) {
-      if (a > b) { cKey.push_back(rowOff[a] + (b - rowFirst[a])); cItem.push_back(e * 4 + 2); }
-      else { cKey.push_back(rowOff[b] + (a - rowFirst[b])); cItem.push_back(e * 4 + 3); }
-    }
-  }
-  std::vector<int> listStart, listPos;
-  csr_by_key(cKey.data(), (int)cKey.size(), nBlocks, listStart, listPos);
-  std::vector<int> listItems(listPos.size());
-  for (size_t q = 0; q < listPos.size(); ++q) listItems[q] = cItem[listPos[q]];
+  MORB_REQUIRE(fit == EnvelopeFit::Ok, MORB_ERR_CAPACITY, "the envelope of the essential graph exceeds what the handle may grow to");
+  const int n = P.n, nBlocks = P.nBlocks;
+  const std::vector<int>&col = P.col, &rowFirst = P.rowFirst, &rowOff = P.rowOff, &colStart = P.colStart, &colRows = P.colRows, &listStart = P.listStart,
+                        &listItems = P.listItems;
 
   MORB_ENTER(st, o, nullptr);
   EgDev D;

@@ -392,6 +392,32 @@ class Optimizer:
                                                     ptr(mp) if len(mp) else None, ptr(ref) if len(mp) else None, ptr(stats), ptr(chi2)))
         return S, mp, stats, chi2
 
+    def OptimizeEssentialGraph4DoF(self, kfPose, kfBody, kfFixed, Tcb12, eI, eJ, eTij, mpPos=None, mpRef=None, kfScw=None):
+        """Optimizer::OptimizeEssentialGraph4DoF, the pose graph of loop closing in an inertial map, on host numpy arrays (see
+        morb_optimize_essential_graph_4dof).  kfPose: float64 [nKF, 12] (Rcw row-major, tcw); kfBody: [nKF, 12] (Rwb row-major, twb) at
+        entry; kfFixed: uint8 [nKF]; Tcb12: float32 [12]; edges (eI, eJ) with measurements eTij [nE, 12] (dRij row-major, dtij) in insertion
+        order; mpPos float32 [nMP, 3] with mpRef = the vertex each point is corrected through (-1: left alone) and kfScw [nKF, 8] = vScw at
+        entry, or None.  Returns (kfPose, mpPos, stats4, chi2): stats4 = outer iterations, trials, vertices in the system, envelope blocks."""
+        P = np.ascontiguousarray(kfPose, np.float64).reshape(-1, 12).copy()
+        B = np.ascontiguousarray(kfBody, np.float64).reshape(-1, 12)
+        fx = np.ascontiguousarray(kfFixed, np.uint8)
+        tcb = np.ascontiguousarray(Tcb12, np.float32).reshape(12)
+        ei, ej = np.ascontiguousarray(eI, np.int32), np.ascontiguousarray(eJ, np.int32)
+        M = np.ascontiguousarray(eTij, np.float64).reshape(-1, 12)
+        assert len(fx) == len(P) == len(B) and len(ei) == len(ej) == len(M)
+        mp = np.zeros((0, 3), np.float32) if mpPos is None else np.ascontiguousarray(mpPos, np.float32).reshape(-1, 3).copy()
+        ref = np.zeros(0, np.int32) if mpRef is None else np.ascontiguousarray(mpRef, np.int32)
+        assert len(ref) == len(mp)
+        scw = None
+        if len(mp):
+            scw = np.ascontiguousarray(kfScw, np.float64).reshape(-1, 8)
+            assert len(scw) == len(P)
+        stats, chi2 = np.zeros(4, np.int32), np.zeros(2, np.float64)
+        check(self._L.morb_optimize_essential_graph_4dof(self._h, len(P), ptr(P), ptr(B), ptr(fx), ptr(tcb), len(ei), ptr(ei), ptr(ej), ptr(M), len(mp),
+                                                         ptr(mp) if len(mp) else None, ptr(ref) if len(mp) else None, ptr(scw) if len(mp) else None,
+                                                         ptr(stats), ptr(chi2)))
+        return P, mp, stats, chi2
+
     def Sim3LogLibm(self, d, s):
         """acos(d) and log(s) as the device computes them inside Sim3::log (see morb_sim3_log_libm)."""
         d, s = np.ascontiguousarray(d, np.float64), np.ascontiguousarray(s, np.float64)

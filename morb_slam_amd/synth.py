@@ -1824,3 +1824,156 @@ def make_essential_graph_problem(n_kf=30, band=3, n_loop=1, fix_scale=False, see
         mpRef[m] = -1 if m % 10 == 9 else r
     return dict(kfSim3=vS, kfFlags=flags, eI=np.array(eI, np.int32), eJ=np.array(eJ, np.int32), eSji=np.array(eS, np.float64).reshape(-1, 8),
                 mpPos=mpPos, mpRef=mpRef, cur=cur, loop=loop_kf, connected=connected, S_true=S_true)
+
+
+# ---- the 4-DoF pose graph of loop closing in an inertial map (Optimizer::OptimizeEssentialGraph4DoF) ---------------------------------------
+def _rs_mul(a, b):
+    """g2o::Sim3::operator* on (R, t, s)."""
+    return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]
+
+
+def _rs_inv(a):
+    return a[0].T, (-1.0 / a[2]) * (a[0].T @ a[1]), 1.0 / a[2]
+
+
+def _quat_from_R_any(R):
+    """Rotation matrix -> unit quaternion (x y z w) at any angle: the largest of the four candidates divides."""
+    d = np.array([R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1], R[0, 0] + R[1, 1] + R[2, 2]])
+    k = int(np.argmax(d))
+    r = np.sqrt(1.0 + d[k])
+    q = np.zeros(4)
+    if k == 3:
+        q[3] = 0.5 * r
+        q[:3] = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (2 * r)
+    else:
+        i, j, l = k, (k + 1) % 3, (k + 2) % 3
+        q[i] = 0.5 * r
+        q[j] = (R[j, i] + R[i, j]) / (2 * r)
+        q[l] = (R[l, i] + R[i, l]) / (2 * r)
+        q[3] = (R[l, j] - R[j, l]) / (2 * r)
+    return q / np.linalg.norm(q)
+
+
+def make_pose_graph_4dof_problem(n_kf=30, band=3, n_loop=1, seed=0, n_old_loops=0, loop_kf=1, loop_yaw_deg=3.0, loop_trans=0.3, loop_scale=1.0,
+                                 fixed=(0,), duplicate_every=0, fixed_pair_edge=False, isolated=(), n_points=0, drift_yaw_deg=0.3,
+                                 drift_rp_deg=0.02, drift_trans=0.004, meas_noise=0.0, fixed_pair_offset=0.05):
+    """A loop closure in an inertial map as LoopClosing::CorrectLoop hands it to Optimizer::OptimizeEssentialGraph4DoF, flattened for
+    morb_optimize_essential_graph_4dof.  The world is gravity-aligned (z up).  Keyframes 0 .. n_kf-1 (ascending mnId): a body on a circle
+    heading along its tangent, with a small true roll and pitch; the estimates drift per step in yaw (drift_yaw_deg), a little in roll and
+    pitch (drift_rp_deg: what the IMU leaves) and in the length of the step (drift_trans).  A keyframe's pose and body state are what its
+    float members hold, cast to double each on its own, so the two agree to float rounding only.  mPrevKF of keyframe i is the nearest
+    earlier keyframe that is not `isolated`; covisibility (weight >= 100) joins keyframes at most `band` apart.  The current keyframe is
+    the last one, the loop keyframe `loop_kf`.  The loop's correction is a yaw about the vertical and a translation of the world
+    (loop_yaw_deg, loop_trans), with loop_scale in the corrected Sim3: CorrectedSim3 is propagated to the keyframes within `band` of the
+    current one as LoopClosing.cc does, and their vertices are built from its inverse (ImuCamPose's third constructor, in double).
+    Edges in the insertion order of Optimizer.cc:5236-5426 (vertex 0 = the later keyframe): the LoopConnections of the connected keyframes to
+    the n_loop keyframes around the loop keyframe (measured between vScw), then per keyframe its mPrevKF link, its old loop edges
+    (n_old_loops random long-range pairs), its covisibility edges and, every `duplicate_every`-th keyframe, a second edge on the mPrevKF
+    pair; all measured between the non-corrected poses.  Each measurement is the rotation and the translation of the Sim3 product.
+    fixed: fixed vertices; fixed_pair_edge adds an edge between two fixed vertices, its measurement off by fixed_pair_offset (a constant
+    of chi2); `isolated` keyframes carry no edge.  Points: n_points with a reference keyframe each (every tenth -1).
+    Returns a dict: kfPose, kfBody, kfFixed, Tcb12, eI, eJ, eTij, mpPos, mpRef, kfScw, plus cur, loop, connected."""
+    rng = np.random.default_rng(seed)
+    iso = set(int(i) for i in isolated)
+
+    def rz(a):
+        return np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1.0]])
+
+    Rcb = (np.array([[0, -1.0, 0], [0, 0, -1.0], [1.0, 0, 0]]) @ _rot_from_rotvec(np.array([0.01, -0.02, 0.015]))).astype(np.float32)
+    tcb = np.array([0.05, -0.02, 0.01], np.float32)
+    Tcb12 = np.concatenate([Rcb.ravel(), tcb]).astype(np.float32)
+    Rcb_d, tcb_d = Rcb.astype(np.float64), tcb.astype(np.float64)
+    # true body poses, then the drifted estimates
+    Rt, pt = [], []
+    for i in range(n_kf):
+        a = 2 * np.pi * i / max(n_kf, 8)
+        Rt.append(rz(a + np.pi / 2) @ _rot_from_rotvec(np.array([0.03 * np.sin(3 * a), 0.02 * np.cos(2 * a), 0.0])))
+        pt.append(np.array([6 * np.cos(a), 6 * np.sin(a), 0.2 * np.sin(5 * a)]))
+    Re, pe = [Rt[0]], [pt[0]]
+    for i in range(1, n_kf):
+        dRt, dpt = Rt[i - 1].T @ Rt[i], Rt[i - 1].T @ (pt[i] - pt[i - 1])
+        dy = np.deg2rad(drift_yaw_deg) * (1 + 0.3 * rng.normal())
+        drp = np.deg2rad(drift_rp_deg) * rng.normal(size=2)
+        dRe = dRt @ rz(dy) @ _rot_from_rotvec(np.array([drp[0], drp[1], 0.0]))
+        dpe = (1.0 - drift_trans * (1 + 0.3 * rng.normal())) * dpt
+        Re.append(Re[i - 1] @ dRe); pe.append(pe[i - 1] + Re[i - 1] @ dpe)
+    # the keyframes' float members, each cast to double on its own
+    S_est, body = [], np.zeros((n_kf, 12))
+    for i in range(n_kf):
+        Rbw = Re[i].T
+        Rcw = (Rcb_d @ Rbw).astype(np.float32).astype(np.float64)
+        tcw = (Rcb_d @ (-Rbw @ pe[i]) + tcb_d).astype(np.float32).astype(np.float64)
+        S_est.append((Rcw, tcw, 1.0))
+        body[i, :9] = Re[i].astype(np.float32).astype(np.float64).ravel(); body[i, 9:] = pe[i].astype(np.float32).astype(np.float64)
+    cur = n_kf - 1
+    while cur in iso:
+        cur -= 1
+    connected = [i for i in range(max(0, cur - band), cur + 1) if i not in iso]
+    # the loop's correction W of the world (a yaw and a translation): Twc <- W Twc, so Scw <- Scw W^-1; the corrected Sim3 carries loop_scale
+    W = (rz(np.deg2rad(loop_yaw_deg)), loop_trans * np.array([0.8, -0.5, 0.1]), 1.0)
+    cc = _rs_mul(S_est[cur], _rs_inv(W))
+    S_cur_corr = (cc[0], loop_scale * cc[1], loop_scale)
+    vS = list(S_est)   # vScw: CorrectedSim3's entry, or the pose
+    pose = np.zeros((n_kf, 12))
+    for i in range(n_kf):
+        pose[i, :9] = S_est[i][0].ravel(); pose[i, 9:] = S_est[i][1]
+    for i in connected:
+        vS[i] = S_cur_corr if i == cur else _rs_mul(_rs_mul(S_est[i], _rs_inv(S_est[cur])), S_cur_corr)
+        Rwc, twc, _ = _rs_inv(vS[i])   # VertexPose4DoF(Rwc, twc, pKF)
+        body[i, :9] = (Rwc @ Rcb_d).ravel(); body[i, 9:] = Rwc @ tcb_d + twc
+        pose[i, :9] = Rwc.T.ravel(); pose[i, 9:] = -Rwc.T @ twc
+    eI, eJ, eT = [], [], []
+
+    def add(i, j, Si, Sj):
+        M = _rs_mul(Si, _rs_inv(Sj))
+        if meas_noise:
+            M = _rs_mul((_rot_from_rotvec(meas_noise * rng.normal(size=3)), meas_noise * rng.normal(size=3), 1.0), M)
+        eI.append(i); eJ.append(j); eT.append(np.concatenate([M[0].ravel(), M[1]]))
+
+    inserted = set()
+    loop_side = [j for j in range(max(0, loop_kf - n_loop // 2), max(0, loop_kf - n_loop // 2) + n_loop) if j not in iso and j not in connected]
+    if n_loop:
+        for i in connected:
+            for j in loop_side:
+                if i == cur or j == loop_kf or (i + j) % 2 == 0:   # (the pair (cur, loop) always; the others by their weight)
+                    add(i, j, vS[i], vS[j])
+                    inserted.add((min(i, j), max(i, j)))
+    old = []
+    for _ in range(n_old_loops):
+        i = int(rng.integers(n_kf // 2, n_kf)); j = int(rng.integers(0, max(1, n_kf // 4)))
+        if i not in iso and j not in iso and i != j:
+            old.append((i, j))
+    for i in range(n_kf):
+        if i in iso:
+            continue
+        p = i - 1
+        while p >= 0 and p in iso:
+            p -= 1
+        if p >= 0:
+            add(i, p, S_est[i], S_est[p])
+        for (a, b) in old:
+            if a == i and b < i:
+                add(i, b, S_est[i], S_est[b])
+        for j in range(i - 1, max(-1, i - band - 1), -1):
+            if j in iso or j == p or (j, i) in inserted:
+                continue
+            add(i, j, S_est[i], S_est[j])
+        if duplicate_every and p >= 0 and i % duplicate_every == 0:
+            add(i, p, S_est[i], S_est[p])
+    fx = np.zeros(n_kf, np.uint8)
+    for f in fixed:
+        fx[f] = 1
+    if fixed_pair_edge:
+        ff = [f for f in fixed if f not in iso]
+        if len(ff) >= 2:
+            add(ff[1], ff[0], vS[ff[1]], _rs_mul((_rot_from_rotvec(np.array([0.01, 0.02, -0.01])), np.array([fixed_pair_offset, 0.0, 0.02]), 1.0), vS[ff[0]]))
+    scw = np.array([np.concatenate([_quat_from_R_any(S[0]), S[1], [S[2]]]) for S in vS])
+    mpPos = np.zeros((n_points, 3), np.float32); mpRef = np.full(n_points, -1, np.int32)
+    for m in range(n_points):
+        r = int(rng.integers(0, n_kf))
+        Swr = _rs_inv(vS[r])
+        Xc = np.array([rng.uniform(-2, 2), rng.uniform(-1, 1), rng.uniform(2, 8)])
+        mpPos[m] = (Swr[2] * (Swr[0] @ Xc) + Swr[1]).astype(np.float32)
+        mpRef[m] = -1 if m % 10 == 9 else r
+    return dict(kfPose=pose, kfBody=body, kfFixed=fx, Tcb12=Tcb12, eI=np.array(eI, np.int32), eJ=np.array(eJ, np.int32),
+                eTij=np.array(eT, np.float64).reshape(-1, 12), mpPos=mpPos, mpRef=mpRef, kfScw=scw, cur=cur, loop=loop_kf, connected=connected)
