@@ -124,6 +124,23 @@ struct MergeBAView {
   std::vector<uint8_t> levelFlag;   // out [nE]: edges put on level 1 between the rounds (:3662-3690)
   int stats[6] = {0, 0, 0, 0, 0, 0};   // out: as morb_merge_bundle_adjustment's stats6
 };
+// The graph Optimizer::BundleAdjustment assembles over a whole map (Optimizer.cc:113-268), flattened as morb_bundle_adjustment takes it: keyframes by
+// ascending mnId, edges by point, within a point by observing keyframe, the left observation before the right camera's.
+struct GlobalBAView {
+  int nKF = 0, nMP = 0, nE = 0;
+  float* kfPose = nullptr;          // [nKF][7] in / out (free keyframes that carry an edge)
+  const uint8_t* kfFixed = nullptr; // [nKF] 1 = mnId == GetInitKFid() (:121), and what the caller fixes besides
+  float* mpPos = nullptr;           // [nMP][3] in / out (points that carry an edge)
+  const int* eKF = nullptr;         // [nE]
+  const int* eMP = nullptr;         // [nE]
+  const float* eObs = nullptr;      // [nE][3] (x, y, uRight or < 0); with rig28 the third slot is not read
+  const float* eInvSigma2 = nullptr;
+  float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  const float* rig28 = nullptr;     // KannalaBrandt8 rig (as LocalBAView::rig28): edges with eRight[e] != 0 are EdgeSE3ProjectXYZToBody
+  const uint8_t* eRight = nullptr;
+  int stats[4] = {0, 0, 0, 0};      // out: as morb_bundle_adjustment's stats4
+  double chi2[2] = {0, 0};          // out: the active robust chi2 before and after
+};
 // The graph Optimizer::MergeInertialBA assembles (Optimizer.cc:3985-4272), flattened as morb_merge_inertial_ba takes it.
 struct MergeInertialBAView {
   int nKF = 0, nMP = 0, nE = 0, nI = 0;
@@ -299,6 +316,28 @@ class Optimizer {
     } else
     check(morb_merge_bundle_adjustment(o.h, g.nKF, g.kfPose, g.kfFixed, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.fx, g.fy, g.cx,
                                        g.cy, g.mbf, stop, g.eraseFlag.data(), g.levelFlag.data(), g.stats));
+  }
+
+  // void static BundleAdjustment(const vector<KeyFrame*>& vpKF, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag, const unsigned long
+  // nLoopKF, const bool bRobust)  Optimizer.h:49-52 over a whole map: the global bundle adjustment LoopClosing::RunGlobalBundleAdjustment starts
+  // (LoopClosing.cc:2302), on the loop-closing handle.  pbStopFlag is the caller's own bool (mbStopGBA), read at entry and polled at every LM
+  // iteration and trial.
+  static void BundleAdjustment(GlobalBAView& g, int nIterations, bool bRobust, bool* pbStopFlag, int device = 0) {
+    static_assert(sizeof(bool) == 1, "pbStopFlag is read as one byte");
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    const uint8_t* stop = reinterpret_cast<const uint8_t*>(pbStopFlag);
+    if (g.rig28) {
+      float trl7[7];
+      rot_to_pose7(g.rig28 + 16, trl7);
+      std::vector<float> obs2((size_t)g.nE * 2);
+      for (int e = 0; e < g.nE; ++e) { obs2[2 * e] = g.eObs[3 * e]; obs2[2 * e + 1] = g.eObs[3 * e + 1]; }
+      check(morb_bundle_adjustment_fisheye(o.h, g.nKF, g.kfPose, g.kfFixed, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, obs2.data(), g.eRight, g.eInvSigma2, g.rig28,
+                                           g.rig28 + 8, trl7, nIterations, bRobust ? 1 : 0, stop, g.stats, g.chi2));
+    } else
+    check(morb_bundle_adjustment(o.h, g.nKF, g.kfPose, g.kfFixed, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.fx, g.fy, g.cx, g.cy,
+                                 g.mbf, nIterations, bRobust ? 1 : 0, stop, g.stats, g.chi2));
   }
 
   // static void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const
@@ -510,12 +549,19 @@ class Optimizer {
   static void OptimizeEssentialGraph4DoF(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
                                          const ConnMap& LoopConnections);
 
-  // (include/Optimizer.h:46-53; call site Tracking.cc:2398) on the map of a monocular initialisation; any other map shape throws
+  // (include/Optimizer.h:46-53; call site Tracking.cc:2398) on the map of a monocular initialisation; any other map shape throws, or, with
+  // MORB_WHOLE_MAP_BUNDLE_ADJUSTMENT defined, goes to WholeMapBundleAdjustment
   template <class MapT>
   static void GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true);
   template <class KF, class MP>
   static void BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations = 5, bool* pbStopFlag = NULL,
                                const unsigned long nLoopKF = 0, const bool bRobust = true);
+
+  // the same function over any map (morb_bundle_adjustment*): what BundleAdjustment<KF, MP> hands a map that is not the initial-map shape to when
+  // MORB_WHOLE_MAP_BUNDLE_ADJUSTMENT is defined before this header is included (call site LoopClosing.cc:2302)
+  template <class KF, class MP>
+  static void WholeMapBundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations = 5, bool* pbStopFlag = NULL,
+                                       const unsigned long nLoopKF = 0, const bool bRobust = true);
 
   // (include/Optimizer.h:103-112; call sites LocalMapping.cc:1205, :1391 and LoopClosing.cc:1902)
   template <class MapT, class Mat3d, class Vec3d, class MatXd>
@@ -537,6 +583,9 @@ class Optimizer {
   template <class FrameT> static void write_back_inertial(FrameT* pFrame, const PoseInertialView& v);
   template <class MapT, class Fill, class Back> static void inertial_optimization_on_map(MapT* pMap, int mode, Fill fill, Back back);
   template <class SE3> static SE3 se3_from_matrix(const double R[9], const double t[3]);
+  template <class KF, class MP>
+  static bool initial_map_bundle_adjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag,
+                                            const unsigned long nLoopKF, const bool bRobust, std::string* whyNot);
   // rotation (9, row-major) + translation (3) -> unit quaternion xyzw + translation (the *_fisheye pose entries take Trl that way)
   static void rot_to_pose7(const float* Rt12, float out[7]) {
     const float* R = Rt12;

@@ -1042,29 +1042,32 @@ void Optimizer::GlobalBundleAdjustemnt(MapT* pMap, int nIterations, bool* pbStop
 //                                  nLoopKF, const bool bRobust)  Optimizer.cc:56-362, for the one map shape that is built: the map Tracking::
 // CreateInitialMapMonocular has just made — two keyframes, the one with GetInitKFid() fixed (at the identity), every point observed by both
 // through mono edges.  Flattened into an InitialMapView and solved with the scaling switched off (depthScale 0, minTracked 0); written back as
-// :276-361 does for both nLoopKF cases (the `dist > 1` block of :297-340 only counts and is left out).  Any other map throws std::runtime_error:
-// GlobalBundleAdjustemnt over a whole map after a loop closure is not built.
+// :276-361 does for both nLoopKF cases (the `dist > 1` block of :297-340 only counts and is left out).  Any other map is refused with
+// std::runtime_error, unless the integrator defines MORB_WHOLE_MAP_BUNDLE_ADJUSTMENT before including this header: then it goes to
+// WholeMapBundleAdjustment below, and LoopClosing.cc:2302 compiles unchanged.  (The default keeps what tests/native/initial_map_member_check.cc pins.)
+// false: the map is not the initial-map shape, *whyNot says why and nothing has been touched
 template <class KF, class MP>
-void Optimizer::BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
-                                 const bool bRobust) {
+bool Optimizer::initial_map_bundle_adjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
+                                              const bool bRobust, std::string* whyNot) {
   const char* what = "Optimizer::BundleAdjustment: only the map of a monocular initialisation is built (two keyframes, the initial one fixed at the identity, "
                      "every point seen by both through monocular observations); ";
+  auto refuse = [&](const std::string& why) { *whyNot = std::string(what) + why; return false; };
   std::vector<KF*> kfs;
   for (KF* k : vpKFs) if (!k->isBad()) kfs.push_back(k);
-  if (kfs.size() != 2) throw std::runtime_error(std::string(what) + "this map has " + std::to_string(kfs.size()) + " keyframes");
+  if (kfs.size() != 2) return refuse("this map has " + std::to_string(kfs.size()) + " keyframes");
   auto* pMap = vpKFs[0]->GetMap();
   const unsigned long initId = pMap->GetInitKFid();
-  if ((kfs[0]->mnId == initId) == (kfs[1]->mnId == initId)) throw std::runtime_error(std::string(what) + "exactly one keyframe must be the initial one");
+  if ((kfs[0]->mnId == initId) == (kfs[1]->mnId == initId)) return refuse("exactly one keyframe must be the initial one");
   KF* k1 = kfs[0]->mnId == initId ? kfs[0] : kfs[1];
   KF* k2 = kfs[0]->mnId == initId ? kfs[1] : kfs[0];
-  if (k1->mpCamera2 || k2->mpCamera2) throw std::runtime_error(std::string(what) + "a keyframe has a second camera");
+  if (k1->mpCamera2 || k2->mpCamera2) return refuse("a keyframe has a second camera");
   {
     const auto T1 = k1->GetPose();
     const auto R1 = T1.rotationMatrix();
     const auto t1 = T1.translation();
     for (int r = 0; r < 3; ++r) {
-      if (t1(r) != 0.f) throw std::runtime_error(std::string(what) + "the fixed keyframe is not at the origin");
-      for (int c = 0; c < 3; ++c) if (R1(r, c) != (r == c ? 1.f : 0.f)) throw std::runtime_error(std::string(what) + "the fixed keyframe is rotated");
+      if (t1(r) != 0.f) return refuse("the fixed keyframe is not at the origin");
+      for (int c = 0; c < 3; ++c) if (R1(r, c) != (r == c ? 1.f : 0.f)) return refuse("the fixed keyframe is rotated");
     }
   }
   InitialMapView v;
@@ -1085,9 +1088,9 @@ void Optimizer::BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vecto
       const int left = std::get<0>(ob.second);
       if (ob.first == k1) i1 = left; else if (ob.first == k2) i2 = left; else if (!ob.first->isBad()) ++others;
     }
-    if (others || i1 < 0 || i2 < 0 || i1 >= n1 || i2 >= n2) throw std::runtime_error(std::string(what) + "a point is not observed by exactly the two keyframes");
-    if (!(k1->mvuRight[i1] < 0) || !(k2->mvuRight[i2] < 0)) throw std::runtime_error(std::string(what) + "a point has a stereo observation");
-    if (owner[i1]) throw std::runtime_error(std::string(what) + "two points share a keypoint");
+    if (others || i1 < 0 || i2 < 0 || i1 >= n1 || i2 >= n2) return refuse("a point is not observed by exactly the two keyframes");
+    if (!(k1->mvuRight[i1] < 0) || !(k2->mvuRight[i2] < 0)) return refuse("a point has a stereo observation");
+    if (owner[i1]) return refuse("two points share a keypoint");
     owner[i1] = pMP; m12[i1] = i2; tri[i1] = 1;
     const auto X = pMP->GetWorldPos();
     for (int k = 0; k < 3; ++k) p3d[3 * (size_t)i1 + k] = X(k);
@@ -1121,6 +1124,132 @@ void Optimizer::BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vecto
     if (!pMP) continue;
     typename std::decay<decltype(pMP->GetWorldPos())>::type X;
     for (int k = 0; k < 3; ++k) X(k) = v.mpPos[3 * (size_t)i + k];
+    if (own) { pMP->SetWorldPos(X); pMP->UpdateNormalAndDepth(); }
+    else { pMP->mPosGBA = X; pMP->mnBAGlobalForKF = nLoopKF; }
+  }
+  return true;
+}
+template <class KF, class MP>
+void Optimizer::BundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF,
+                                 const bool bRobust) {
+  std::string whyNot;
+  if (initial_map_bundle_adjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust, &whyNot)) return;
+#ifdef MORB_WHOLE_MAP_BUNDLE_ADJUSTMENT
+  WholeMapBundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust);
+#else
+  throw std::runtime_error(whyNot);
+#endif
+}
+
+// The graph Optimizer::BundleAdjustment assembles at Optimizer.cc:113-268, flattened on the host (no device call: tests/native/
+// global_ba_member_check.cc checks it alone).  Vertices: the keyframes of vpKFs that are not bad, by ascending mnId (the order the solver's
+// envelope wants; g2o orders by id itself), the one with GetInitKFid() fixed (:121); the points of vpMP that are not bad and carry an edge
+// (:262-267), in vpMP's order.  Edges in the reference's order — by point, within a point by GetObservations()'s iteration, the left
+// observation (monocular: mvuRight < 0, else stereo, :155-221) before the right camera's (:223-259) — skipping an observation by a bad
+// keyframe, by one with mnId > maxKFid or by one that is not in vpKFs (:148-150).
+template <class KF, class MP>
+struct WholeMapFlat {
+  std::vector<KF*> kfs;
+  std::vector<MP*> mps;
+  std::vector<float> kfPose, mpPos, eObs, eInv;
+  std::vector<uint8_t> kfFixed, eRight;
+  std::vector<int> eKF, eMP;
+  bool rig = false;   // a keyframe has a second camera: every left observation is an EdgeSE3ProjectXYZ on the KannalaBrandt8 camera
+};
+namespace morb_glue {
+template <class KF, class MP>
+void flatten_whole_map(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, WholeMapFlat<KF, MP>& f) {
+  for (KF* k : vpKFs) if (!k->isBad()) f.kfs.push_back(k);
+  std::stable_sort(f.kfs.begin(), f.kfs.end(), [](KF* a, KF* b) { return a->mnId < b->mnId; });
+  if (f.kfs.empty()) return;
+  const unsigned long initId = vpKFs[0]->GetMap()->GetInitKFid();
+  std::map<KF*, int> kfIndex;
+  unsigned long maxKFid = 0;
+  for (KF* k : f.kfs) {
+    const int at = (int)kfIndex.size();
+    kfIndex[k] = at;
+    float p[7];
+    pose7(k->GetPose(), p);
+    f.kfPose.insert(f.kfPose.end(), p, p + 7);
+    f.kfFixed.push_back(k->mnId == initId ? 1 : 0);
+    if (k->mnId > maxKFid) maxKFid = k->mnId;
+    if (k->mpCamera2) f.rig = true;
+  }
+  for (MP* pMP : vpMP) {
+    if (pMP->isBad()) continue;
+    const int j = (int)f.mps.size();
+    const size_t before = f.eKF.size();
+    for (const auto& ob : pMP->GetObservations()) {
+      KF* pKF = ob.first;
+      if (pKF->isBad() || pKF->mnId > maxKFid) continue;
+      const auto it = kfIndex.find(pKF);
+      if (it == kfIndex.end()) continue;   // (optimizer.vertex(pKF->mnId) == NULL)
+      const int leftIndex = std::get<0>(ob.second);
+      if (leftIndex != -1) {
+        const auto& kpUn = pKF->mvKeysUn[leftIndex];
+        const float ur = pKF->mvuRight[leftIndex];
+        if (f.rig && !(ur < 0)) throw std::runtime_error("Optimizer::BundleAdjustment: a stereo observation in a map of KannalaBrandt8 rigs");
+        f.eKF.push_back(it->second); f.eMP.push_back(j); f.eRight.push_back(0);
+        f.eObs.push_back(kpUn.pt.x); f.eObs.push_back(kpUn.pt.y); f.eObs.push_back(ur < 0 ? -1.f : ur);
+        f.eInv.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+      }
+      if (pKF->mpCamera2) {
+        int rightIndex = std::get<1>(ob.second);
+        if (rightIndex != -1 && rightIndex < static_cast<int>(pKF->mvKeysRight.size())) {   // (:226, as the reference tests it)
+          rightIndex -= pKF->NLeft;
+          const auto& kp = pKF->mvKeysRight[rightIndex];
+          f.eKF.push_back(it->second); f.eMP.push_back(j); f.eRight.push_back(1);
+          f.eObs.push_back(kp.pt.x); f.eObs.push_back(kp.pt.y); f.eObs.push_back(-1.f);
+          f.eInv.push_back(pKF->mvInvLevelSigma2[kp.octave]);
+        }
+      }
+    }
+    if (f.eKF.size() == before) continue;   // :262-264: the vertex is removed again
+    f.mps.push_back(pMP);
+    const auto X = pMP->GetWorldPos();
+    f.mpPos.push_back(X(0)); f.mpPos.push_back(X(1)); f.mpPos.push_back(X(2));
+  }
+}
+}  // namespace morb_glue
+
+// Optimizer::BundleAdjustment (Optimizer.cc:56-362) over any map: flattened as above, solved by the view form (morb_bundle_adjustment*), written
+// back as :276-361 does — SetPose / SetWorldPos / UpdateNormalAndDepth when nLoopKF is the origin keyframe's id, else mTcwGBA / mPosGBA /
+// mnBAGlobalForKF; every keyframe that is not bad is written (a fixed one, or one without an edge, with the pose it has), as the reference
+// does.  A raised *pbStopFlag stops the optimisation, not the write-back.  The `dist > 1` block of :297-340 only counts and is left out.
+template <class KF, class MP>
+void Optimizer::WholeMapBundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations, bool* pbStopFlag,
+                                         const unsigned long nLoopKF, const bool bRobust) {
+  using SE3 = typename std::decay<decltype(vpKFs[0]->GetPose())>::type;
+  WholeMapFlat<KF, MP> f;
+  morb_glue::flatten_whole_map(vpKFs, vpMP, f);
+  if (f.kfs.empty()) return;
+  auto* pMap = vpKFs[0]->GetMap();
+  if (!f.eKF.empty()) {
+    GlobalBAView g;
+    g.nKF = (int)f.kfs.size(); g.nMP = (int)f.mps.size(); g.nE = (int)f.eKF.size();
+    g.kfPose = f.kfPose.data(); g.kfFixed = f.kfFixed.data(); g.mpPos = f.mpPos.data(); g.eKF = f.eKF.data(); g.eMP = f.eMP.data();
+    g.eObs = f.eObs.data(); g.eInvSigma2 = f.eInv.data();
+    KF* k0 = f.kfs[0];
+    g.fx = k0->fx; g.fy = k0->fy; g.cx = k0->cx; g.cy = k0->cy; g.mbf = k0->mbf;
+    float rigp[28];
+    if (f.rig) {
+      KF* kr = nullptr;
+      for (KF* k : f.kfs) if (k->mpCamera2) { kr = k; break; }
+      morb_glue::rig28(kr, rigp); g.rig28 = rigp; g.eRight = f.eRight.data();
+    }
+    BundleAdjustment(g, nIterations, bRobust, pbStopFlag);
+  }
+  const bool own = nLoopKF == pMap->GetOriginKF()->mnId;
+  for (size_t i = 0; i < f.kfs.size(); ++i) {   // :278-342
+    KF* pKF = f.kfs[i];
+    const SE3 T = morb_glue::make_se3<SE3>(&f.kfPose[7 * i]);
+    if (own) pKF->SetPose(T);
+    else { pKF->mTcwGBA = T; pKF->mnBAGlobalForKF = nLoopKF; }
+  }
+  for (size_t j = 0; j < f.mps.size(); ++j) {   // :345-361
+    MP* pMP = f.mps[j];
+    typename std::decay<decltype(pMP->GetWorldPos())>::type X;
+    for (int k = 0; k < 3; ++k) X(k) = f.mpPos[3 * j + k];
     if (own) { pMP->SetWorldPos(X); pMP->UpdateNormalAndDepth(); }
     else { pMP->mPosGBA = X; pMP->mnBAGlobalForKF = nLoopKF; }
   }

@@ -1141,6 +1141,45 @@ int morb_optimize_essential_graph_4dof(morb_optimizer*, int nKF, double* kfPose,
                                        const float* Tcb12, int nE, const int* eI, const int* eJ, const double* eTij, int nMP,
                                        float* mpPos, const int* mpRef, const double* kfScw, int* stats4, double* chi2);
 
+/* void static Optimizer::BundleAdjustment(const vector<KeyFrame*>& vpKF, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag,
+ * const unsigned long nLoopKF, const bool bRobust)  Optimizer.h:49-52, Optimizer.cc:56-362: the whole-map bundle adjustment
+ * Optimizer::GlobalBundleAdjustemnt (:47-54) hands every keyframe and point of the map to, which LoopClosing::RunGlobalBundleAdjustment starts
+ * behind a corrected loop (LoopClosing.cc:2302: 10 iterations, bRobust = false), on the graph the reference assembles at :113-268, flattened
+ * (HOST pointers) like morb_local_bundle_adjustment.  nKF keyframes, kfPose[k] = quaternion xyzw and t (7 floats), in and out; kfFixed[k] !=
+ * 0 stands for setFixed(pKF->mnId == pMap->GetInitKFid()) (:121) — the caller may fix more.  nMP points, mpPos in and out.  nE edges in
+ * insertion order (:144-260: by point, within a point by observing keyframe, the left observation before the right one): eKF, eMP, eObs =
+ * (x, y, uRight), information eInvSigma2 * I; uRight < 0 gives EdgeSE3ProjectXYZ (:155-183), else EdgeStereoSE3ProjectXYZ (:184-221).
+ * Several edges may share one (eKF, eMP) pair; they add into one Hpl block in edge order.  nIterations in 1 .. 100 is optimize(nIterations)
+ * (:273); there is no setUserLambdaInit: the first lambda is 1e-5 * the largest diagonal entry of the first system over the pose and the
+ * point blocks (g2o's computeLambdaInit).  bRobust != 0: Huber kernels with delta (float)sqrt(5.99) on the monocular and (float)sqrt(7.815)
+ * on the stereo edges (:126-127, :171-175, :204-208 — 5.99, not 5.991); 0: those edges carry no kernel (the loop-closing case).  stopFlag =
+ * pbStopFlag itself (one byte; NULL = none), polled at every LM iteration and trial (:78); set at entry the call returns MORB_OK with stats4
+ * and chi2 zero and nothing else written.  H + lambda I of the reduced camera system is solved exactly by a block LDL^T over the envelope of
+ * the 6 x 6 block rows in the order of the keyframes given: pass them by ascending mnId, so that covisible keyframes are neighbours and the
+ * envelope is a band with a few long rows where a loop was closed ("Global bundle adjustment"); the Schur complement of
+ * the points is built block by block over that envelope, nothing dense in nMP x nKF is allocated.  Outputs: kfPose of the free keyframes
+ * that carry an edge and mpPos of the points that carry one (:276-361); fixed keyframes, keyframes without an edge and points without an
+ * edge (:262-264) keep their bytes.  stats4 = {outer LM iterations, LM trials, keyframes in the system, envelope blocks}; chi2 = the active
+ * robust chi2 before and after.  This function erases no observation: the counts of :297-340 feed nothing and are left out.
+ * MORB_ERR_INVALID: a NULL array, an empty graph, an index out of range, a non-finite pose, point, observation or information, nIterations
+ * outside 1 .. 100; MORB_ERR_CAPACITY: the envelope exceeds what the handle may grow to (the bytes of the Sim3 pose graph's 2^22 blocks:
+ * 2^22 * 49 / 36 blocks of 6 x 6), or the Schur complement has more pair contributions than an int indexes (a point seen by k free
+ * keyframes gives k (k + 1) / 2); all before any launch, nothing written.  No free keyframe has an edge: MORB_OK, nothing written, stats4 and
+ * chi2 zero.  Left with the caller: the graph itself (:113-268), and SetPose / SetWorldPos / UpdateNormalAndDepth or mTcwGBA / mPosGBA /
+ * mnBAGlobalForKF (:276-361). */
+int morb_bundle_adjustment(morb_optimizer*, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
+                           int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                           float fx, float fy, float cx, float cy, float bf, int nIterations, int bRobust,
+                           const uint8_t* stopFlag, int* stats4, double* chi2);
+/* The same on a KannalaBrandt8 stereo rig (pKF->mpCamera2 != NULL), with the arrays of morb_local_bundle_adjustment_fisheye: eObs2 =
+ * [nE][2]; eRight[e] == 0 is an EdgeSE3ProjectXYZ with the left camera (mvuRight < 0 on such rigs: no stereo edge), eRight[e] != 0 an
+ * EdgeSE3ProjectXYZToBody with the right camera behind mTrl (:223-259), usually behind the left edge of the same keyframe and point.  A
+ * ToBody edge always carries Huber's kernel with delta (float)sqrt(5.99), whatever bRobust says (:244-246): restated, not repaired. */
+int morb_bundle_adjustment_fisheye(morb_optimizer*, int nKF, float* kfPose, const uint8_t* kfFixed, int nMP, float* mpPos,
+                                   int nE, const int* eKF, const int* eMP, const float* eObs2, const uint8_t* eRight,
+                                   const float* eInvSigma2, const float* camL8, const float* camR8, const float* Trl7,
+                                   int nIterations, int bRobust, const uint8_t* stopFlag, int* stats4, double* chi2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // Device helpers PoseOptimization (optimizer.hip) and LocalBundleAdjustment (local_ba.hip) share: the SE3Quat algebra, the reference's
 // projection edge with its pose Jacobian, the fixed-order block sum and the fisheye rig (Huber's kernel: quat_huber.h).  What only one of the two
-// uses lives in that unit.  Everything is in an unnamed namespace: each unit gets its own copy, and the kernels keep their mangled names.
+// uses lives in that unit; the binary edges at the end (point Jacobian, pinhole or rig) serve the bundle adjusters of local_ba.hip and
+// global_ba.hip.  Everything is in an unnamed namespace: each unit gets its own copy, and the kernels keep their mangled names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -207,6 +208,79 @@ inline Rig make_rig(const float* camL8, const float* camR8, const float* Trl7) {
     for (int i = 0; i < 3; ++i) rig.Trl.t[i] = Trl7[4 + i];
   }
   return rig;
+}
+
+// point Jacobian (d x 3)
+__device__ __forceinline__ void jac_point(const Cam& cam, bool stereo, const double* xc, const double* R, double* Jl) {
+  const double x = xc[0], y = xc[1], z = xc[2];
+  const double fx = cam.fx, fy = cam.fy, bf = cam.bf;
+  if (!stereo) {  // -projectJac * R
+    const double a = fx / z, b = -fx * x / (z * z), c = fy / z, d = -fy * y / (z * z);
+    for (int k = 0; k < 3; ++k) { Jl[k] = -(a * R[k] + b * R[6 + k]); Jl[3 + k] = -(c * R[3 + k] + d * R[6 + k]); Jl[6 + k] = 0; }
+  } else {
+    const double z_2 = z * z;
+    for (int k = 0; k < 3; ++k) {
+      Jl[k] = -fx * R[k] / z + fx * x * R[6 + k] / z_2;
+      Jl[3 + k] = -fy * R[3 + k] / z + fy * y * R[6 + k] / z_2;
+      Jl[6 + k] = Jl[k] - bf * R[6 + k] / z_2;
+    }
+  }
+}
+
+// ---- binary edges of the bundle adjusters (local_ba.hip, global_ba.hip), pinhole or fisheye rig -------------------------
+// obs[2] >= 0: EdgeStereoSE3ProjectXYZ; -1: EdgeSE3ProjectXYZ with the pinhole camera; -2: EdgeSE3ProjectXYZ with the
+// left KB8 camera; -3: EdgeSE3ProjectXYZToBody (right KB8 camera behind mTrl).  (Optimizer.cc:1244-1351)
+__device__ __forceinline__ bool edge_is_kb8(const Rig* rig, const float* o) { return rig != nullptr && o[2] < -1.5f; }
+__device__ __forceinline__ double ba_edge_error(const Cam& cam, const Rig* rig, bool st, const double* xc, const float* o,
+                                                double info, double* err) {
+  if (!edge_is_kb8(rig, o)) return edge_error(cam, st, xc, o, info, err);
+  double uv[2];
+  if (o[2] > -2.5f) morbcam::kb8_project_d(rig->kbL, xc, uv);
+  else { double xr[3]; se3_map(rig->Trl, xc, xr); morbcam::kb8_project_d(rig->kbR, xr, uv); }   // (mTrl * T).map(Xw) = mTrl.map(T.map(Xw))
+  err[0] = (double)o[0] - uv[0]; err[1] = (double)o[1] - uv[1]; err[2] = 0;
+  return err[0] * (info * err[0]) + err[1] * (info * err[1]);
+}
+// Jp (d x 6) and / or Jl (d x 3); R = rotation of the keyframe pose.  OptimizableTypes.cpp:134-156 / :185-208
+// RIG = false: the problem has no fisheye rig.  The KannalaBrandt8 branch (its float libm, the right camera's extrinsics) otherwise costs
+// the pinhole build kernel 100 VGPRs (220 instead of 119) and puts the pose Jacobian into scratch memory — for a branch it never takes.
+template <bool RIG>
+__device__ __forceinline__ void ba_edge_jac(const Cam& cam, const Rig* rig, bool st, const double* xc, const float* o,
+                                            const double* R, double* Jp, double* Jl) {
+  // RIG = true: EVERY edge of the problem is a KannalaBrandt8 edge (morb_ba_problem_create_fisheye writes obs[2] = -2 / -3 for all of them),
+  // so the choice is made at compile time: with a run-time `edge_is_kb8` both branches wrote Jp and the array went to scratch memory (160 B)
+  if (!RIG) {
+    if (Jp) jac_pose(cam, st, false, xc, Jp);
+    if (Jl) jac_point(cam, st, xc, R, Jl);
+    return;
+  }
+  const double x = xc[0], y = xc[1], z = xc[2];
+  double pj[6], pjM[6];
+  if (o[2] > -2.5f) {
+    morbcam::kb8_project_jac(rig->kbL, xc, pj);
+    _Pragma("unroll") for (int k = 0; k < 6; ++k) pjM[k] = pj[k];
+  } else {
+    double xr[3], M[9];
+    se3_map(rig->Trl, xc, xr);
+    morbcam::kb8_project_jac(rig->kbR, xr, pj);
+    q_to_R(rig->Trl.q, M);
+    _Pragma("unroll") for (int r = 0; r < 2; ++r)
+      _Pragma("unroll") for (int c = 0; c < 3; ++c) pjM[r * 3 + c] = pj[r * 3] * M[c] + pj[r * 3 + 1] * M[3 + c] + pj[r * 3 + 2] * M[6 + c];
+  }
+  _Pragma("unroll") for (int r = 0; r < 2; ++r) {
+    const double a = pjM[r * 3], b = pjM[r * 3 + 1], c = pjM[r * 3 + 2];
+    if (Jp) {
+      Jp[r * 6 + 0] = -(b * -z + c * y); Jp[r * 6 + 1] = -(a * z + c * -x); Jp[r * 6 + 2] = -(a * -y + b * x);
+      Jp[r * 6 + 3] = -a; Jp[r * 6 + 4] = -b; Jp[r * 6 + 5] = -c;
+    }
+    if (Jl) _Pragma("unroll") for (int k = 0; k < 3; ++k) Jl[r * 3 + k] = -(a * R[k] + b * R[3 + k] + c * R[6 + k]);
+  }
+  if (Jp) _Pragma("unroll") for (int k = 12; k < 18; ++k) Jp[k] = 0;
+  if (Jl) _Pragma("unroll") for (int k = 6; k < 9; ++k) Jl[k] = 0;
+}
+// isDepthPositive (OptimizableTypes.h:117-123 / :152-158)
+__device__ __forceinline__ bool ba_depth_positive(const Rig* rig, const float* o, const double* xc) {
+  if (edge_is_kb8(rig, o) && !(o[2] > -2.5f)) { double xr[3]; se3_map(rig->Trl, xc, xr); return xr[2] > 0.0; }
+  return xc[2] > 0.0;
 }
 
 }  // namespace

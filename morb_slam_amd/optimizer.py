@@ -418,6 +418,34 @@ class Optimizer:
                                                          ptr(stats), ptr(chi2)))
         return P, mp, stats, chi2
 
+    def BundleAdjustment(self, kfPose, kfFixed, mpPos, eKF, eMP, eObs, eInvSigma2, cam, n_iterations=10, robust=False, stop_flag=None,
+                         rig=None):
+        """Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust), the whole-map bundle adjustment of loop
+        closing, on host numpy arrays (see morb_bundle_adjustment).  Pass the keyframes by ascending mnId.  rig = dict(eRight uint8 [nE],
+        camL, camR (8 floats each), Trl (7 floats)) selects the KannalaBrandt8 stereo rig (eObs is then [nE, 2]; cam is ignored).
+        stop_flag: a one-byte numpy array standing for `bool* pbStopFlag`.
+        Returns (kfPose, mpPos, stats4, chi2): stats4 = outer iterations, trials, keyframes in the system, envelope blocks."""
+        a = [np.ascontiguousarray(kfPose, np.float32).copy(), np.ascontiguousarray(kfFixed, np.uint8),
+             np.ascontiguousarray(mpPos, np.float32).copy(), np.ascontiguousarray(eKF, np.int32), np.ascontiguousarray(eMP, np.int32),
+             np.ascontiguousarray(eObs, np.float32), np.ascontiguousarray(eInvSigma2, np.float32)]
+        nE = len(a[3])
+        assert len(a[1]) == len(a[0]) and len(a[4]) == len(a[6]) == nE
+        stats, chi2 = np.zeros(4, np.int32), np.zeros(2, np.float64)
+        st = ptr(stop_flag) if stop_flag is not None else None
+        if rig is not None:
+            er = np.ascontiguousarray(rig["eRight"], np.uint8)
+            cl, cr, trl = (np.ascontiguousarray(rig[k], np.float32) for k in ("camL", "camR", "Trl"))
+            assert cl.size == 8 and cr.size == 8 and trl.size == 7 and len(er) == nE and a[5].shape == (nE, 2)
+            check(self._L.morb_bundle_adjustment_fisheye(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]),
+                                                         ptr(a[5]), ptr(er), ptr(a[6]), ptr(cl), ptr(cr), ptr(trl), int(n_iterations),
+                                                         int(bool(robust)), st, ptr(stats), ptr(chi2)))
+            return a[0], a[2], stats, chi2
+        assert a[5].shape == (nE, 3)
+        check(self._L.morb_bundle_adjustment(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]), ptr(a[5]),
+                                             ptr(a[6]), cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["bf"], int(n_iterations),
+                                             int(bool(robust)), st, ptr(stats), ptr(chi2)))
+        return a[0], a[2], stats, chi2
+
     def Sim3LogLibm(self, d, s):
         """acos(d) and log(s) as the device computes them inside Sim3::log (see morb_sim3_log_libm)."""
         d, s = np.ascontiguousarray(d, np.float64), np.ascontiguousarray(s, np.float64)

@@ -1977,3 +1977,111 @@ def make_pose_graph_4dof_problem(n_kf=30, band=3, n_loop=1, seed=0, n_old_loops=
         mpRef[m] = -1 if m % 10 == 9 else r
     return dict(kfPose=pose, kfBody=body, kfFixed=fx, Tcb12=Tcb12, eI=np.array(eI, np.int32), eJ=np.array(eJ, np.int32),
                 eTij=np.array(eT, np.float64).reshape(-1, 12), mpPos=mpPos, mpRef=mpRef, kfScw=scw, cur=cur, loop=loop_kf, connected=connected)
+
+
+# ---- loop closing's global bundle adjustment: Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) ------------
+def make_global_ba_problem(n_kf=40, reach=6, n_points=600, n_loop_points=0, seed=0, mono_frac=0.3, kb8=False, n_fixed=1, step=0.12,
+                           kf_deg=0.3, kf_trans=0.02, point_noise=0.03, noise_px=1.0, right_frac=0.6, obs_frac=0.8, loop_span=3,
+                           single_free_points=0, fixed_only_points=0, mono_single_points=0, idle_kf=None, idle_points=0, at_truth=False,
+                           near_plane_point=False, cam=EUROC_CAM):
+    """Input of the whole-map bundle adjustment: n_kf keyframes along a path, in ascending id (keyframes 0 .. n_fixed - 1 fixed: the map's
+    initial keyframe, and what the caller fixes besides), looking sideways at n_points points.  Every point is seen by keyframes within
+    `reach` of one another (a share obs_frac of that window, at least two), so the reduced system is a band of `reach` blocks;
+    n_loop_points far points are seen from both ends of the path (its first and last loop_span keyframes) and give the long rows.  Poses,
+    points and observations carry noise (kf_deg, kf_trans, point_noise, noise_px times the level's sigma).  mono_frac: the share of monocular
+    observations on the pinhole camera (1.0: none stereo).  kb8: the TUM-VI KannalaBrandt8 rig, eObs is [nE, 2] and `rig` = dict(eRight, camL,
+    camR, Trl): a left observation, and with probability right_frac the right camera's of the same keyframe behind it (a ToBody edge, the
+    same (keyframe, point) pair).  Edges are ordered by point, then by keyframe, left before right.
+    The named scenes: single_free_points points seen by ONE free keyframe only; fixed_only_points seen by fixed keyframes only;
+    mono_single_points with one monocular observation; idle_kf: a free keyframe that observes nothing; idle_points: points nobody observes;
+    at_truth: no noise anywhere (the first step is already too small to move chi2); near_plane_point: the last point lies 2e-38 in front of
+    the focal plane of its first free observer, whose pose is the identity, and carries an information of 3e38 there: chi2 stays finite, the
+    point's Hessian block does not survive its inversion, and every factorisation fails on a NaN pivot."""
+    rng = np.random.default_rng(0x6BA00 + seed)
+    Trl_m = np.linalg.inv(TUMVI_T_C1_C2)
+    if at_truth:
+        kf_deg = kf_trans = point_noise = noise_px = 0.0
+    poses = []
+    for i in range(n_kf):
+        c = np.array([i * step, rng.normal(0, 0.03), rng.normal(0, 0.03)])
+        q_wc = _quat_from_rotvec(rng.normal(0, 0.02, 3))
+        q_cw = q_wc * np.array([-1, -1, -1, 1])
+        poses.append(np.concatenate([q_cw, -_quat_rot(q_cw, c)]))
+    poses = np.array(poses)
+    free = [k for k in range(n_fixed, n_kf) if k != idle_kf]
+    zr = (2.0, 8.0) if kb8 else (3.0, 10.0)
+    X, seen_by = [], []
+
+    def place(kfs, far=False):
+        x0 = np.mean([k * step for k in kfs])
+        z = rng.uniform(30, 40) if far else rng.uniform(*zr)
+        X.append(np.array([x0 + rng.uniform(-1, 1) * (0.2 * z), rng.uniform(-0.25, 0.25) * z, z]))
+        seen_by.append(sorted(int(k) for k in kfs))
+
+    usable = [k for k in range(n_kf) if k != idle_kf]
+    for j in range(n_points):
+        k0 = int(rng.integers(0, max(n_kf - 1 - reach, 0) + 1))       # (reach >= n_kf - 1: every window is the whole path)
+        window = [k for k in range(k0, min(k0 + reach + 1, n_kf)) if k != idle_kf]
+        if len(window) < 2:
+            window = usable[-2:]
+        take = max(2, int(round(obs_frac * len(window))))
+        place(rng.choice(window, size=min(take, len(window)), replace=False))
+    for j in range(n_loop_points):
+        ends = [k for k in list(range(min(loop_span, n_kf))) + list(range(max(n_kf - loop_span, 0), n_kf)) if k != idle_kf]
+        place(sorted(set(ends)), far=True)
+    single = []
+    for j in range(single_free_points):
+        single.append(len(X)); place([free[int(rng.integers(0, len(free)))]])
+    for j in range(fixed_only_points):
+        place(list(range(n_fixed)))
+    mono_single = []
+    for j in range(mono_single_points):
+        mono_single.append(len(X)); place([free[int(rng.integers(0, len(free)))]])
+    for j in range(idle_points):
+        place([usable[0]]); seen_by[-1] = []
+    X = np.array(X)
+    eKF, eMP, eObs, eInv, eRight = [], [], [], [], []
+    for j, kfs in enumerate(seen_by):
+        for kf in kfs:
+            Xc = _quat_rot(poses[kf][:4], X[j]) + poses[kf][4:]
+            s = 1.2 ** int(rng.integers(0, 8))
+            if kb8:
+                for right in (0, 1):
+                    if right and (rng.random() > right_frac or j in mono_single):
+                        continue
+                    Xs = Trl_m[:3, :3] @ Xc + Trl_m[:3, 3] if right else Xc
+                    assert Xs[2] > 0.4
+                    o = kb8_project(TUMVI_CAM_R if right else TUMVI_CAM_L, Xs[None])[0] + rng.normal(0, noise_px, 2) * s
+                    eKF.append(kf); eMP.append(j); eObs.append(o); eInv.append(1.0 / s ** 2); eRight.append(right)
+            else:
+                assert Xc[2] > 0.5
+                u = cam["fx"] * Xc[0] / Xc[2] + cam["cx"]; v = cam["fy"] * Xc[1] / Xc[2] + cam["cy"]
+                o = np.array([u, v, u - cam["bf"] / Xc[2]]) + rng.normal(0, noise_px, 3) * s
+                if rng.random() < mono_frac or j in mono_single or Xc[2] > 25.0:   # (a far point has no usable disparity)
+                    o[2] = -1
+                elif j in single:
+                    o[2] = max(o[2], 0.0)
+                o[2] = -1 if o[2] < 0 else o[2]
+                eKF.append(kf); eMP.append(j); eObs.append(o); eInv.append(1.0 / s ** 2)
+    pose0 = poses.copy()
+    for i in range(n_fixed, n_kf):
+        nq = _quat_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(kf_deg))
+        pose0[i] = np.concatenate([_quat_mul(nq, poses[i][:4]), _quat_rot(nq, poses[i][4:]) + rng.normal(0, 1, 3) / np.sqrt(3) * kf_trans])
+    X0 = X + rng.normal(0, point_noise, X.shape)
+    eInv = np.array(eInv, np.float32)
+    if near_plane_point:
+        j = len(X) - 1 - idle_points
+        e = next(k for k in range(len(eKF)) if eMP[k] == j and eKF[k] >= n_fixed)
+        pose0[eKF[e]] = np.array([0, 0, 0, 1.0, 0, 0, 0])               # the identity exactly: the camera coordinates are the point's own
+        X0[j] = np.array([0.5, 0.25, 2e-38])
+        eInv[e] = 3e38
+    fixed = np.zeros(n_kf, np.uint8); fixed[:n_fixed] = 1
+    out = dict(kfPose=pose0.astype(np.float32), kfFixed=fixed, mpPos=X0.astype(np.float32), eKF=np.array(eKF, np.int32),
+               eMP=np.array(eMP, np.int32), eInvSigma2=eInv, true_poses=poses, true_points=X, cam=cam, rig=None,
+               single=np.array(single, np.int32), mono_single=np.array(mono_single, np.int32))
+    if kb8:
+        Trl7 = np.concatenate([_quat_from_R(Trl_m[:3, :3]), Trl_m[:3, 3]]).astype(np.float32)
+        out.update(eObs=np.array(eObs, np.float32).reshape(-1, 2), rig=dict(eRight=np.array(eRight, np.uint8), camL=TUMVI_CAM_L, camR=TUMVI_CAM_R, Trl=Trl7))
+    else:
+        out["eObs"] = np.array(eObs, np.float32).reshape(-1, 3)
+    return out
