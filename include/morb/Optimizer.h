@@ -163,6 +163,29 @@ struct MergeInertialBAView {
   int outerIterations = 0, lmTrials = 0;
   bool ran = false;                    // false: *pbStopFlag was set at entry (:4276), nothing written
 };
+// The graph Optimizer::FullInertialBA assembles over a whole map (Optimizer.cc:392-687), flattened as morb_full_inertial_ba takes it: keyframes by
+// ascending mnId, edges by point, within a point by observing keyframe, the left observation before the right camera's.
+struct FullInertialBAView {
+  int nKF = 0, nMP = 0, nE = 0, nI = 0;
+  float* kfState = nullptr;            // [nKF][21] in / out: Rwb row-major, twb, velocity, gyro bias, acc bias (kind 0: all; kind 3: Rwb, twb only)
+  const uint8_t* kfKind = nullptr;     // [nKF] 0 free, 15 unknowns (bImu and in a link; 9 with bInit); 1 fixed with an IMU state in a link, 2 fixed observer
+                                       //       (bFixLocal); 3 free in the pose only (!bImu, or no link)
+  float* mpPos = nullptr;              // [nMP][3] in / out (points that carry an edge)
+  const int* eKF = nullptr;            // [nE]
+  const int* eMP = nullptr;            // [nE]
+  const float* eObs = nullptr;         // [nE][3] (x, y, uRight or < 0); with rig28 the third slot is not read
+  const float* eInvSigma2 = nullptr;   // [nE]
+  const int* iKF1 = nullptr;           // [nI] mPrevKF of the link's keyframe
+  const int* iKF2 = nullptr;           // [nI] the keyframe owning iPre[i]
+  const morb_imu_preintegrated* iPre = nullptr;   // [nI] mpImuPreintegrated, after SetNewBias(mPrevKF->GetImuBias()) (:455)
+  float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  const float* rig28 = nullptr;        // KannalaBrandt8 rig (as LocalInertialBAView::rig28): edges with eRight[e] != 0 are EdgeMono(1)
+  const uint8_t* eRight = nullptr;
+  float Tbc12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  float bias6[6] = {0, 0, 0, 0, 0, 0}; // in / out with bInit: the shared gyro, then accelerometer bias (in: the last keyframe's, pIncKF)
+  int stats[4] = {0, 0, 0, 0};         // out: as morb_full_inertial_ba's stats4 (all zero: *pbStopFlag was set at entry, nothing written)
+  double chi2[2] = {0, 0};             // out: the active robust chi2 before and after
+};
 
 // The graph Optimizer::OptimizeEssentialGraph assembles (Optimizer.cc:1477-1682; the second overload's at :1760-2020), flattened as
 // morb_optimize_essential_graph takes it.  Vertices in ascending mnId: the matrix is then a block band plus the loop edges' long rows.
@@ -402,6 +425,25 @@ class Optimizer {
     g.outerIterations = stats[0]; g.lmTrials = stats[1]; g.ran = stats[2] != 0;
   }
 
+  // void static FullInertialBA(Map* pMap, int its, const bool bFixLocal, const unsigned long nLoopKF, bool* pbStopFlag, bool bInit, float priorG,
+  // float priorA, Eigen::VectorXd* vSingVal, bool* bHess)  Optimizer.h:55-58: the inertial whole-map bundle adjustment, on the handle of the role
+  // that calls it (LocalMapping::InitializeIMU: kMapping; LoopClosing::RunGlobalBundleAdjustment: kLoopClosing).  pbStopFlag is the caller's own
+  // bool (or NULL), read at entry and polled at every LM iteration and trial.
+  enum Role { kTracking = 0, kMapping = 1, kLoopClosing = 2 };   // (the roles: see optimizer() below)
+  static void FullInertialBA(FullInertialBAView& g, int its, bool bInit, float priorG, float priorA, bool* pbStopFlag, Role role, int device = 0) {
+    static_assert(sizeof(bool) == 1, "pbStopFlag is read as one byte");
+    Slot& o = slot(device, role);
+    std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    const uint8_t* stop = reinterpret_cast<const uint8_t*>(pbStopFlag);
+    if (g.rig28)
+      check(morb_full_inertial_ba_fisheye(o.h, g.nKF, g.kfState, g.kfKind, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eRight, g.eInvSigma2, g.nI, g.iKF1,
+                                          g.iKF2, g.iPre, g.rig28, g.Tbc12, its, bInit ? 1 : 0, priorG, priorA, g.bias6, stop, g.stats, g.chi2));
+    else
+      check(morb_full_inertial_ba(o.h, g.nKF, g.kfState, g.kfKind, g.nMP, g.mpPos, g.nE, g.eKF, g.eMP, g.eObs, g.eInvSigma2, g.nI, g.iKF1, g.iKF2, g.iPre,
+                                  g.fx, g.fy, g.cx, g.cy, g.mbf, g.Tbc12, its, bInit ? 1 : 0, priorG, priorA, g.bias6, stop, g.stats, g.chi2));
+  }
+
   // void static InertialOptimization(Map*, ...)  Optimizer.h:103-112 in its three overloads: mode 0 = (Rwg, scale, bg, ba, bMono, covInertial,
   // bFixedVel, bGauss, priorG, priorA), 1 = (bg, ba, priorG, priorA), 2 = (Rwg, scale).  One problem through morb_inertial_optimization_batch:
   // modes 0 and 2 (LocalMapping) on the mapping handle, mode 1 (LoopClosing's merge) on the loop-closing handle.
@@ -563,6 +605,12 @@ class Optimizer {
   static void WholeMapBundleAdjustment(const std::vector<KF*>& vpKFs, const std::vector<MP*>& vpMP, int nIterations = 5, bool* pbStopFlag = NULL,
                                        const unsigned long nLoopKF = 0, const bool bRobust = true);
 
+  // (include/Optimizer.h:55-58; call sites LoopClosing.cc:2305 and LocalMapping.cc:1244-1249).  VecX stands for Eigen::VectorXd: vSingVal and
+  // bHess are never touched by the reference either.
+  template <class MapT, class VecX = void>
+  static void FullInertialBA(MapT* pMap, int its, const bool bFixLocal = false, const unsigned long nLoopId = 0, bool* pbStopFlag = NULL, bool bInit = false,
+                             float priorG = 1e2, float priorA = 1e6, VecX* vSingVal = NULL, bool* bHess = NULL);
+
   // (include/Optimizer.h:103-112; call sites LocalMapping.cc:1205, :1391 and LoopClosing.cc:1902)
   template <class MapT, class Mat3d, class Vec3d, class MatXd>
   static void InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale, Vec3d& bg, Vec3d& ba, bool bMono, MatXd& covInertial, bool bFixedVel = false,
@@ -576,7 +624,6 @@ class Optimizer {
   // LocalMapping (LocalBundleAdjustment, hundreds of milliseconds of LM trials): each role has its own handle — own stream, own
   // workspace — per device, created once (std::call_once), so a tracked frame never queues behind local-mapping trials; a mutex per
   // handle serialises callers of the same role.
-  enum Role { kTracking = 0, kMapping = 1, kLoopClosing = 2 };
   static morb_optimizer* optimizer(int device = 0, Role role = kTracking) { return slot(device, role).h; }
 
  private:

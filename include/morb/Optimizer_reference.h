@@ -1577,6 +1577,171 @@ void Optimizer::MergeInertialBA(KF* pCurrKF, KF* pMergeKF, bool* pbStopFlag, Map
   pMap->IncreaseChangeIndex();                                                          // :4388
 }
 
+// void Optimizer::FullInertialBA(Map* pMap, int its, const bool bFixLocal, const unsigned long nLoopId, bool* pbStopFlag, bool bInit, float priorG,
+// float priorA, Eigen::VectorXd* vSingVal, bool* bHess)  Optimizer.cc:364-760, the inertial whole-map bundle adjustment (call sites
+// LoopClosing.cc:2305 and LocalMapping.cc:1244-1249).  The map flattened as morb_full_inertial_ba takes it: a vertex per keyframe with mnId <=
+// maxKFid, by ascending mnId; what bFixLocal fixes (:401-406) with the return below three free keyframes (:438-440); a link per keyframe with
+// mPrevKF, both bImu, neither bad nor beyond maxKFid, whose predecessor has a vertex, after SetNewBias(mPrevKF->GetImuBias()) (:443-533); kind 0 /
+// 1 for a bImu keyframe that enters a link, 3 / 2 otherwise (velocity and bias vertices without an edge are not in g2o's active set); the
+// observations of every point by the keyframes that are not bad, the left before the right one, a point seen by fixed keyframes alone without
+// edges and not written (:683-686, :744); with bInit the last keyframe's bias (pIncKF) as the shared one.  Written back as :696-759 does: SetPose /
+// SetVelocity / SetNewBias / SetWorldPos / UpdateNormalAndDepth when nLoopId == 0, else mTcwGBA / mVwbGBA / mBiasGBA / mPosGBA / mnBAGlobalForKF;
+// with bInit every bImu keyframe gets the shared bias; then IncreaseChangeIndex().  The handle: LocalMapping's calls pass no stop flag
+// (kMapping), LoopClosing's does (kLoopClosing) — nLoopId cannot tell them apart, LocalMapping passes a keyframe id there.  A map without a
+// usable observation is written back as it stands.  vSingVal and bHess are not touched, as in the reference.
+template <class MapT, class VecX>
+void Optimizer::FullInertialBA(MapT* pMap, int its, const bool bFixLocal, const unsigned long nLoopId, bool* pbStopFlag, bool bInit, float priorG,
+                               float priorA, VecX*, bool*) {
+  const unsigned long maxKFid = pMap->GetMaxKFid();
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMPs = pMap->GetAllMapPoints();
+  using KF = typename std::remove_pointer<typename std::decay<decltype(vpKFs[0])>::type>::type;
+  using MP = typename std::remove_pointer<typename std::decay<decltype(vpMPs[0])>::type>::type;
+  using SE3 = typename std::decay<decltype(vpKFs[0]->GetPose())>::type;
+  using Bias = typename std::decay<decltype(vpKFs[0]->GetImuBias())>::type;
+  // vertices (:392-436)
+  std::vector<KF*> kfs;
+  KF* pIncKF = nullptr;
+  for (KF* k : vpKFs) {
+    if (k->mnId > maxKFid) continue;
+    kfs.push_back(k);
+    pIncKF = k;
+  }
+  if (kfs.empty()) return;
+  std::stable_sort(kfs.begin(), kfs.end(), [](KF* a, KF* b) { return a->mnId < b->mnId; });
+  std::map<KF*, int> kfIndex;
+  std::vector<uint8_t> fixed(kfs.size(), 0);
+  int nNonFixed = 0;
+  for (size_t i = 0; i < kfs.size(); ++i) {
+    kfIndex[kfs[i]] = (int)i;
+    if (bFixLocal) {
+      fixed[i] = (kfs[i]->mnBALocalForKF >= (maxKFid - 1)) || (kfs[i]->mnBAFixedForKF >= (maxKFid - 1)) ? 1 : 0;
+      if (!fixed[i]) nNonFixed++;
+    }
+  }
+  if (bFixLocal && nNonFixed < 3) return;                                               // :438-440
+  // links (:443-533), in the order of GetAllKeyFrames()
+  std::vector<int> iKF1, iKF2;
+  std::vector<morb_imu_preintegrated> iPre;
+  std::vector<uint8_t> linked(kfs.size(), 0);
+  for (KF* pKFi : vpKFs) {
+    if (!pKFi->mPrevKF || pKFi->mnId > maxKFid) continue;
+    if (pKFi->isBad() || pKFi->mPrevKF->mnId > maxKFid) continue;
+    if (!(pKFi->bImu && pKFi->mPrevKF->bImu)) continue;
+    pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());                  // :455
+    const auto it1 = kfIndex.find(pKFi->mPrevKF);
+    if (it1 == kfIndex.end()) continue;                                                 // (:479-491: a vertex is missing)
+    const int r1 = it1->second, r2 = kfIndex[pKFi];
+    iKF1.push_back(r1); iKF2.push_back(r2);
+    iPre.emplace_back(); morb_glue::fill_pre(iPre.back(), pKFi->mpImuPreintegrated);
+    linked[r1] = linked[r2] = 1;
+  }
+  std::vector<float> kfState;
+  std::vector<uint8_t> kfKind;
+  bool rig = false;
+  for (size_t i = 0; i < kfs.size(); ++i) {
+    float s[21];
+    morb_glue::imu_state21(kfs[i], s); morb_glue::bias6(kfs[i]->GetImuBias(), s + 15);
+    kfState.insert(kfState.end(), s, s + 21);
+    const bool imu = kfs[i]->bImu && linked[i];
+    kfKind.push_back((uint8_t)(fixed[i] ? (imu ? 1 : 2) : (imu ? 0 : 3)));
+    if (kfs[i]->mpCamera2) rig = true;
+  }
+  // points and visual edges (:563-687)
+  std::vector<float> mpPos, eObs, eInv;
+  std::vector<int> eKF, eMP;
+  std::vector<uint8_t> eRight, included(vpMPs.size(), 0);
+  for (size_t j = 0; j < vpMPs.size(); ++j) {
+    MP* pMP = vpMPs[j];
+    const auto X = pMP->GetWorldPos();
+    mpPos.push_back(X(0)); mpPos.push_back(X(1)); mpPos.push_back(X(2));
+    const size_t before = eKF.size();
+    bool bAllFixed = true;
+    for (const auto& ob : pMP->GetObservations()) {
+      KF* pKFi = ob.first;
+      if (pKFi->mnId > maxKFid || pKFi->isBad()) continue;
+      const auto it = kfIndex.find(pKFi);
+      if (it == kfIndex.end()) continue;   // (optimizer.vertex(pKFi->mnId) == NULL: the reference dereferences it)
+      const int leftIndex = std::get<0>(ob.second);
+      if (leftIndex != -1) {
+        const auto& kpUn = pKFi->mvKeysUn[leftIndex];
+        const float ur = pKFi->mvuRight[leftIndex];
+        eKF.push_back(it->second); eMP.push_back((int)j); eRight.push_back(0);
+        eObs.push_back(kpUn.pt.x); eObs.push_back(kpUn.pt.y); eObs.push_back(ur < 0 ? -1.f : ur);
+        eInv.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
+        if (!fixed[it->second]) bAllFixed = false;
+      }
+      if (pKFi->mpCamera2) {
+        int rightIndex = std::get<1>(ob.second);
+        if (rightIndex != -1 && rightIndex < static_cast<int>(pKFi->mvKeysRight.size())) {   // (:651, as the reference tests it)
+          rightIndex -= pKFi->NLeft;
+          const auto& kp = pKFi->mvKeysRight[rightIndex];
+          eKF.push_back(it->second); eMP.push_back((int)j); eRight.push_back(1);
+          eObs.push_back(kp.pt.x); eObs.push_back(kp.pt.y); eObs.push_back(-1.f);
+          eInv.push_back(pKFi->mvInvLevelSigma2[kp.octave]);
+          if (!fixed[it->second]) bAllFixed = false;
+        }
+      }
+    }
+    if (bAllFixed) { eKF.resize(before); eMP.resize(before); eRight.resize(before); eObs.resize(3 * before); eInv.resize(before); }   // :683-686
+    else included[j] = 1;
+  }
+  if (pbStopFlag && *pbStopFlag) return;                                                // :689-690
+  FullInertialBAView g;
+  g.nKF = (int)kfs.size(); g.nMP = (int)vpMPs.size(); g.nE = (int)eKF.size(); g.nI = (int)iKF1.size();
+  morb_glue::bias6(pIncKF->GetImuBias(), g.bias6);                                      // :428-435
+  KF* k0 = kfs[0];
+  morb_glue::tbc12(k0->mImuCalib.mTbc, g.Tbc12);
+  if (g.nE > 0) {
+    g.kfState = kfState.data(); g.kfKind = kfKind.data(); g.mpPos = mpPos.data(); g.eKF = eKF.data(); g.eMP = eMP.data();
+    g.eObs = eObs.data(); g.eInvSigma2 = eInv.data();
+    g.iKF1 = iKF1.data(); g.iKF2 = iKF2.data(); g.iPre = iPre.data();
+    g.fx = k0->fx; g.fy = k0->fy; g.cx = k0->cx; g.cy = k0->cy; g.mbf = k0->mbf;
+    float rigp[28];
+    if (rig) {
+      KF* kr = nullptr;
+      for (KF* k : kfs) if (k->mpCamera2) { kr = k; break; }
+      morb_glue::rig28(kr, rigp); g.rig28 = rigp; g.eRight = eRight.data();
+    }
+    FullInertialBA(g, its, bInit, priorG, priorA, pbStopFlag, pbStopFlag ? kLoopClosing : kMapping);
+    if (g.stats[2] == 0 && pbStopFlag && *pbStopFlag) return;   // (the flag was raised between the check above and the entry's own)
+  }
+  // :696-740: Tcw = (Rcb Rwb^T, tcb - Rcb Rwb^T twb) (ImuCamPose, G2oTypes.cc:74-113), velocity, bias
+  for (size_t i = 0; i < kfs.size(); ++i) {
+    KF* pKFi = kfs[i];
+    const float* s = &kfState[21 * i];
+    const float* Tbc = g.Tbc12;
+    double Rcw[9], tcw[3];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) { double a = 0; for (int k = 0; k < 3; ++k) a += (double)Tbc[3 * k + r] * s[3 * c + k]; Rcw[3 * r + c] = a; }
+    for (int r = 0; r < 3; ++r) {
+      double a = 0;
+      for (int k = 0; k < 3; ++k) a -= (double)Tbc[3 * k + r] * Tbc[9 + k];
+      for (int c = 0; c < 3; ++c) a -= Rcw[3 * r + c] * s[9 + c];
+      tcw[r] = a;
+    }
+    const SE3 T = se3_from_matrix<SE3>(Rcw, tcw);
+    if (nLoopId == 0) pKFi->SetPose(T);
+    else { pKFi->mTcwGBA = T; pKFi->mnBAGlobalForKF = nLoopId; }
+    if (!pKFi->bImu) continue;
+    typename std::decay<decltype(pKFi->GetVelocity())>::type vel;
+    for (int k = 0; k < 3; ++k) vel(k) = s[12 + k];
+    const float* bb = bInit ? g.bias6 : s + 15;                                         // (:719-729: with bInit the shared vertices, for every keyframe)
+    const Bias b(bb[3], bb[4], bb[5], bb[0], bb[1], bb[2]);
+    if (nLoopId == 0) { pKFi->SetVelocity(vel); pKFi->SetNewBias(b); }
+    else { pKFi->mVwbGBA = vel; pKFi->mBiasGBA = b; }
+  }
+  for (size_t j = 0; j < vpMPs.size(); ++j) {                                           // :743-757
+    if (!included[j]) continue;
+    MP* pMP = vpMPs[j];
+    typename std::decay<decltype(pMP->GetWorldPos())>::type X;
+    for (int k = 0; k < 3; ++k) X(k) = mpPos[3 * j + k];
+    if (nLoopId == 0) { pMP->SetWorldPos(X); pMP->UpdateNormalAndDepth(); }
+    else { pMP->mPosGBA = X; pMP->mnBAGlobalForKF = nLoopId; }
+  }
+  pMap->IncreaseChangeIndex();                                                          // :759
+}
+
 template <class SE3>
 SE3 Optimizer::se3_from_matrix(const double R[9], const double t[3]) {
   typename std::decay<decltype(std::declval<SE3>().rotationMatrix())>::type Rm;

@@ -1180,6 +1180,56 @@ int morb_bundle_adjustment_fisheye(morb_optimizer*, int nKF, float* kfPose, cons
                                    const float* eInvSigma2, const float* camL8, const float* camR8, const float* Trl7,
                                    int nIterations, int bRobust, const uint8_t* stopFlag, int* stats4, double* chi2);
 
+/* void static Optimizer::FullInertialBA(Map* pMap, int its, const bool bFixLocal, const unsigned long nLoopKF, bool* pbStopFlag, bool bInit,
+ * float priorG, float priorA, Eigen::VectorXd* vSingVal, bool* bHess)  Optimizer.h:55-58, Optimizer.cc:364-760: the inertial whole-map
+ * bundle adjustment — LoopClosing::RunGlobalBundleAdjustment at LoopClosing.cc:2305 (7 iterations, once the map's IMU is initialised) and
+ * LocalMapping::InitializeIMU at LocalMapping.cc:1244-1249 (100 iterations, bInit with the priors or without) — on the graph the reference
+ * assembles at :392-687, flattened (HOST pointers) like morb_merge_inertial_ba: nKF keyframes in ascending mnId (the caller's business: the
+ * envelope is a band then) with states of 21 floats (Rwb row-major, twb, velocity, gyro bias, acc bias), in and out; kfKind[k]: 0 = free with
+ * 15 unknowns (a bImu keyframe that enters a link), 1 = fixed with an IMU state that enters a link (bFixLocal), 2 = fixed keyframe that only
+ * observes points, 3 = free in the pose only, 6 unknowns (!bImu keyframes and bImu keyframes without a link: their velocity and bias
+ * vertices carry no edge, so g2o leaves them out of the active set).  nMP points, nE observations ordered by point, then keyframe, the left
+ * observation before the right one, as morb_bundle_adjustment takes them (eObs = x, y, uRight; uRight < 0 = EdgeMono(0), else EdgeStereo;
+ * information eInvSigma2 * I; every one under Huber with delta (float)sqrt(5.991) / (float)sqrt(7.815), :556-557).  nI links: iKF1 = mPrevKF,
+ * iKF2 = the keyframe owning iPre[i] (after SetNewBias(mPrevKF->GetImuBias()), :455): an EdgeInertial under Huber with delta sqrt(16.92) and
+ * its information unscaled (:493-505), and with !bInit EdgeGyroRW / EdgeAccRW with the inverted C blocks and no kernel (:507-528).  bInit:
+ * ONE gyro and one accelerometer bias for the map (:427-436), bias6 = gyro then accelerometer, in and out (read and written only then, and
+ * non-NULL then; the caller takes it from the last keyframe, pIncKF): every EdgeInertial hangs on them, there are no random-walk edges, a
+ * kind-0 keyframe owns 9 unknowns, and EdgePriorGyro / EdgePriorAcc at zero with information priorG I / priorA I are added (:535-554).  The
+ * priors' error is 0 - bias and their Jacobian is taken as -I, as the error demands; G2oTypes.cc:768-776 states +I.  A link between two
+ * keyframes of kind 1 is a constant of the robust chi2 (with bInit it still moves the shared biases).  setUserLambdaInit(1e-5) (:384),
+ * optimize(its) once (:693), its in 1 .. 100.  pbStopFlag is the caller's flag itself (one byte, NULL = none): set at entry (:689) the call
+ * returns MORB_OK with stats4 and chi2 zero and nothing else written; it is polled at every LM iteration and trial (:388).
+ * H + lambda I of the reduced system — 15, 9 or 6 rows per keyframe, 6 last rows for the shared biases that cover every linked keyframe — is
+ * solved exactly by a block LDL^T over the envelope of its 3 x 3 block rows ("FullInertialBA"); only the six pose
+ * columns of a keyframe meet a point, the Schur complement is built block by block, nothing dense in nMP x nKF or nKF x nKF is allocated.
+ * Outputs: kfState21 in place — all 21 floats of kind 0 (with bInit its bias floats hold the shared value, :719-738), the pose (Rwb, twb) of
+ * kind 3 whose velocity and bias floats keep their bytes, as do kinds 1 and 2 entirely and a kind-3 keyframe without an edge; mpPos of the
+ * points that carry an edge; bias6; stats4 = {outer LM iterations, LM trials, scalar unknowns of the reduced system, envelope blocks of
+ * 3 x 3}; chi2 = the active robust chi2 before and after.  MORB_ERR_INVALID: a NULL array, an empty graph, an index out of range, a link
+ * with an endpoint of kind 2 or 3 or with iKF1 == iKF2, a keyframe of kind 0 that enters no link (pass it as kind 3), a NaN or Inf input, its
+ * outside 1 .. 100; MORB_ERR_CAPACITY: the envelope exceeds what the handle may grow to (the bytes morb_bundle_adjustment allows: 2^22 * 49 /
+ * 9 blocks), the Schur complement has more contributions than an int indexes, or there are 2^23 links or more; all before any launch, nothing
+ * written.  No keyframe in the
+ * system: MORB_OK, nothing written, stats4 and chi2 zero.  Left with the caller: the graph itself — bFixLocal and its `< 3` return
+ * (:401-440), bad keyframes, maxKFid, points seen by fixed keyframes only (:683-686: pass them without edges) — SetNewBias on the
+ * preintegrations, and SetPose / SetVelocity / SetNewBias / SetWorldPos / UpdateNormalAndDepth or mTcwGBA / mVwbGBA / mBiasGBA / mPosGBA /
+ * mnBAGlobalForKF (:696-759).  vSingVal and bHess are never touched by the reference. */
+int morb_full_inertial_ba(morb_optimizer*, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
+                          int nE, const int* eKF, const int* eMP, const float* eObs, const float* eInvSigma2,
+                          int nI, const int* iKF1, const int* iKF2, const morb_imu_preintegrated* iPre,
+                          float fx, float fy, float cx, float cy, float bf, const float* Tbc12,
+                          int its, int bInit, float priorG, float priorA, float* bias6,
+                          const uint8_t* pbStopFlag, int* stats4, double* chi2);
+/* The same on a KannalaBrandt8 rig (rig28 as morb_local_inertial_ba_fisheye takes it): every edge is an EdgeMono, eRight[e] != 0 on the
+ * right camera (EdgeMono(1), :648-679), usually behind the left edge of the same keyframe and point; eObs = (x, y, unused). */
+int morb_full_inertial_ba_fisheye(morb_optimizer*, int nKF, float* kfState21, const uint8_t* kfKind, int nMP, float* mpPos,
+                                  int nE, const int* eKF, const int* eMP, const float* eObs, const uint8_t* eRight,
+                                  const float* eInvSigma2, int nI, const int* iKF1, const int* iKF2,
+                                  const morb_imu_preintegrated* iPre, const float* rig28, const float* Tbc12,
+                                  int its, int bInit, float priorG, float priorA, float* bias6,
+                                  const uint8_t* pbStopFlag, int* stats4, double* chi2);
+
 #ifdef __cplusplus
 }
 #endif

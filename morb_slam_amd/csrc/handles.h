@@ -66,6 +66,7 @@ struct morb_optimizer {
   morb::DeviceGrow initialMap;   // CreateInitialMapMonocular's per-point records of problems that do not fit the LDS (k_initial_map); its own buffer, as mlpnpCorr is
   morb::DeviceGrow essentialGraph;  // OptimizeEssentialGraph's graph lists, per-edge Jacobians and the block envelope of H and of its LDL^T factor (essential_graph.hip), carved anew at every call by ArenaCarver; its own buffer: a map-sized block that `work`'s local windows never need
   morb::DeviceGrow globalBA;        // BundleAdjustment's flattened map, per-edge Jacobians, Schur contribution lists and the 6 x 6 block envelope of the reduced system and of its LDL^T factor (global_ba.hip), carved anew at every call by ArenaCarver; its own buffer, as essentialGraph is
+  morb::DeviceGrow fullInertialBA;  // FullInertialBA's flattened map, per-edge and per-link records, Schur contribution lists and the 3 x 3 block envelope of the reduced system and of its LDL^T factor (full_inertial_ba.hip), carved anew at every call by ArenaCarver; its own buffer, as globalBA is
   morb::PinnedGrow stage;      // pinned host buffer: the one-shot entry points gather their inputs here for a single upload (ba_host.h: the mirror of `work`'s upload region)
   morb::PinnedArray<int> lmWords;   // 16 pinned, device-mapped ints: LM state mirror of the one-shot entry points (optimizer.hip: morb_optimizer_lm_words)
   int exactOrder = 1;             // PoseOptimization: 1 (default) = edge-order sums, the LM path of g2o decision for decision; 0 = tree sums

@@ -481,6 +481,37 @@ class Optimizer:
                                              cam["bf"], ptr(a[10]), st, ptr(erase), ptr(stats)))
         return a[0], a[2], erase, stats
 
+    def FullInertialBA(self, kfState, kfKind, mpPos, eKF, eMP, eObs, eInvSigma2, iKF1, iKF2, iPre, cam, Tbc, its=7, init=False, prior_g=1e2,
+                       prior_a=1e6, bias6=None, stop_flag=None, rig=None, eRight=None):
+        """Optimizer::FullInertialBA(pMap, its, bFixLocal, nLoopId, pbStopFlag, bInit, priorG, priorA), the inertial whole-map bundle
+        adjustment, on host numpy arrays (see morb_full_inertial_ba).  Pass the keyframes by ascending mnId.  kfKind: 0 free (15 unknowns; 9
+        with init), 1 fixed with an IMU state, 2 fixed observer, 3 free in the pose only.  iPre: float32 [nI, PREINT_FLOATS].  init: one
+        shared gyro and accelerometer bias, bias6 (gyro, then accelerometer), with the priors prior_g / prior_a.  rig = 28 floats and eRight
+        (uint8 [nE]) select the KannalaBrandt8 rig (cam is ignored).  stop_flag: a one-byte numpy array standing for `bool* pbStopFlag`.
+        Returns (kfState, mpPos, bias6, stats4, chi2): stats4 = outer iterations, trials, scalar unknowns, envelope blocks."""
+        a = [np.ascontiguousarray(kfState, np.float32).copy(), np.ascontiguousarray(kfKind, np.uint8),
+             np.ascontiguousarray(mpPos, np.float32).copy(), np.ascontiguousarray(eKF, np.int32), np.ascontiguousarray(eMP, np.int32),
+             np.ascontiguousarray(eObs, np.float32), np.ascontiguousarray(eInvSigma2, np.float32), np.ascontiguousarray(iKF1, np.int32),
+             np.ascontiguousarray(iKF2, np.int32), np.ascontiguousarray(iPre, np.float32).reshape(-1, PREINT_FLOATS),
+             np.ascontiguousarray(Tbc, np.float32)]
+        nE, nI = len(a[3]), len(a[7])
+        assert a[9].shape == (nI, PREINT_FLOATS) and a[0].shape[1] == 21 and a[5].shape == (nE, 3)
+        b6 = np.ascontiguousarray(bias6, np.float32).copy() if bias6 is not None else np.zeros(6, np.float32)
+        assert b6.size == 6 and (bias6 is not None or not init)
+        stats, chi2 = np.zeros(4, np.int32), np.zeros(2, np.float64)
+        st = ptr(stop_flag) if stop_flag is not None else None
+        links = (nI, ptr(a[7]) if nI else None, ptr(a[8]) if nI else None, ptr(a[9]) if nI else None)
+        tail = (ptr(a[10]), int(its), int(bool(init)), float(prior_g), float(prior_a), ptr(b6), st, ptr(stats), ptr(chi2))
+        if rig is not None:
+            r28, er = np.ascontiguousarray(rig, np.float32), np.ascontiguousarray(eRight, np.uint8)
+            assert r28.size == 28 and len(er) == nE
+            check(self._L.morb_full_inertial_ba_fisheye(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]),
+                                                        ptr(a[5]), ptr(er), ptr(a[6]), *links, ptr(r28), *tail))
+            return a[0], a[2], b6, stats, chi2
+        check(self._L.morb_full_inertial_ba(self._h, len(a[0]), ptr(a[0]), ptr(a[1]), len(a[2]), ptr(a[2]), nE, ptr(a[3]), ptr(a[4]), ptr(a[5]),
+                                            ptr(a[6]), *links, cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["bf"], *tail))
+        return a[0], a[2], b6, stats, chi2
+
 
 def local_bundle_adjustment_oneshot(opt, kfPose, kfFixed, mpPos, eKF, eMP, eObs, eInvSigma2, cam, inertial=False, stop_flag=None):
     """The one-shot ABI entry (`morb_local_bundle_adjustment`), as the reference binding calls it: `stop_flag` is a one-byte

@@ -2085,3 +2085,140 @@ def make_global_ba_problem(n_kf=40, reach=6, n_points=600, n_loop_points=0, seed
     else:
         out["eObs"] = np.array(eObs, np.float32).reshape(-1, 3)
     return out
+
+
+# ---- the inertial whole-map bundle adjustment (Optimizer::FullInertialBA) -----------------------------------------------------------------
+def make_full_inertial_ba_problem(n_kf=40, reach=6, n_points=600, n_loop_points=0, seed=0, mono_frac=0.3, kb8=False, init=False, no_imu=(),
+                                  n_fixed=0, observers=0, observer_frac=0.5, n_imu=20, step=0.12, kf_deg=0.3, kf_trans=0.02, vel_noise=0.03, bias_noise=1.0,
+                                  point_noise=0.03, noise_px=1.0, right_frac=0.6, obs_frac=0.8, loop_span=3, idle_points=0, at_truth=False,
+                                  near_plane_point=None, prior_g=1e2, prior_a=1e6, cam=EUROC_CAM):
+    """Input of the inertial whole-map bundle adjustment (morb_full_inertial_ba): make_global_ba_problem's map — n_kf keyframes in ascending
+    id along a path, every point seen by keyframes within `reach` of one another (a share obs_frac of that window), n_loop_points far points
+    seen from both ends — with ONE temporal chain through all keyframes whose links carry n_imu IMU samples of a smooth motion, as
+    make_inertial_ba_problem synthesises them.  Nothing is fixed unless asked: kfKind is 0 for every keyframe that enters a link.  no_imu:
+    keyframes with !bImu, kind 3, which cut the chain on both sides (a keyframe left without any link is kind 3 too); n_fixed: the first
+    n_fixed keyframes are fixed — kind 1 where they enter a link (n_fixed = 2 gives a link between two fixed keyframes), else kind 2;
+    observers: extra fixed keyframes of kind 2 behind the chain, one of which sees a share observer_frac of the points.  init: bInit — `bias6` (gyro, accelerometer) is the shared bias the caller
+    takes from the last keyframe, prior_g / prior_a the priors.  kb8: the TUM-VI rig, every observation monocular, eRight marks the right
+    camera's (behind the left one of the same keyframe and point, with probability right_frac); eObs is [nE, 3] either way.  Edges are ordered
+    by point, then keyframe, left before right.  idle_points: points nobody observes; at_truth: no noise anywhere; near_plane_point = k: the
+    body-camera transform is the identity, keyframe k's pose too, and the last point lies 2e-38 in front of its focal plane with an
+    information of 3e38 there (global BA's scene: the point's Hessian block does not survive its inversion)."""
+    rng = np.random.default_rng(0xF1BA00 + seed)
+    if at_truth:
+        kf_deg = kf_trans = vel_noise = bias_noise = point_noise = noise_px = 0.0
+    g = np.array([0, 0, -9.81])
+    dt = 1.0 / IMU_FREQ
+    bg = rng.normal(0, 0.01, 3); ba = rng.normal(0, 0.05, 3)
+    Tbc = np.eye(4) if near_plane_point is not None else EUROC_TBC
+    Rcb = Tbc[:3, :3].T; tcb = -Rcb @ Tbc[:3, 3]
+    Trl = np.linalg.inv(TUMVI_T_C1_C2)
+    # the body starts so that the camera's x axis is the direction of travel: the cameras look sideways at the points
+    R = _rot_from_rotvec(rng.normal(0, 0.05, 3)); p = rng.normal(0, 0.1, 3)
+    T = n_imu * dt
+    v = R @ Tbc[:3, 0] * (step / T) + rng.normal(0, 0.02, 3)
+    states = [(R, p, v)]
+    acc, gyro, dts, start = [], [], [], [0]
+    for k in range(n_kf - 1):
+        w_b = rng.normal(0, 0.05, 3); a_w = rng.normal(0, 0.3, 3)
+        for i in range(n_imu):
+            Rm = R @ _rot_from_rotvec(w_b * (i + 0.5) * dt)
+            acc.append(Rm.T @ (a_w - g) + ba + rng.normal(0, 0.02, 3))
+            gyro.append(w_b + bg + rng.normal(0, 0.002, 3))
+            dts.append(dt)
+        R, p, v = R @ _rot_from_rotvec(w_b * T), p + v * T + 0.5 * a_w * T * T, v + a_w * T
+        states.append((R, p, v))
+        start.append(len(dts))
+    for _ in range(observers):
+        Rk, pk, _v = states[int(rng.integers(0, n_kf))]
+        states.append((Rk @ _rot_from_rotvec(rng.normal(0, 0.03, 3)), pk + rng.normal(0, 0.1, 3), np.zeros(3)))
+    nKF = len(states)
+    # the chain: link k joins keyframes k and k + 1 unless one of them has no IMU
+    cut = set(int(k) for k in no_imu)
+    links = [k for k in range(n_kf - 1) if k not in cut and k + 1 not in cut]
+    linked = set(links) | set(k + 1 for k in links)
+    kind = np.array([(1 if k in linked else 2) if (k < n_fixed or k >= n_kf) else (0 if k in linked else 3) for k in range(nKF)], np.uint8)
+    cams = [(Rcb @ Rk.T, Rcb @ (-Rk.T @ pk) + tcb) for Rk, pk, _ in states]
+    zr = (2.0, 8.0) if kb8 else (3.0, 10.0)
+    X, seen_by = [], []
+
+    def place(kfs, far=False):
+        Rm, tm = cams[sorted(kfs)[len(kfs) // 2]]
+        z = rng.uniform(30, 40) if far else rng.uniform(*zr)
+        xc = np.array([rng.uniform(-1, 1) * (0.2 * z), rng.uniform(-0.25, 0.25) * z, z])
+        X.append(Rm.T @ (xc - tm))
+        seen_by.append(sorted(int(k) for k in kfs))
+
+    for j in range(n_points):
+        k0 = int(rng.integers(0, max(n_kf - 1 - reach, 0) + 1))
+        window = list(range(k0, min(k0 + reach + 1, n_kf)))
+        take = max(2, int(round(obs_frac * len(window))))
+        kfs = list(rng.choice(window, size=min(take, len(window)), replace=False))
+        if observers and rng.random() < observer_frac:
+            kfs.append(int(rng.integers(n_kf, nKF)))
+        place(kfs)
+    for j in range(n_loop_points):
+        place(sorted(set(list(range(min(loop_span, n_kf))) + list(range(max(n_kf - loop_span, 0), n_kf)))), far=True)
+    for j in range(idle_points):
+        place([0]); seen_by[-1] = []
+    X = np.array(X)
+    w_img = 512 if kb8 else 752
+    h_img = 512 if kb8 else 480
+    eKF, eMP, eObs, eInv, eRight = [], [], [], [], []
+    for j, kfs in enumerate(seen_by):
+        for kf in kfs:
+            Rcw, tcw = cams[kf]
+            xc = Rcw @ X[j] + tcw
+            s = 1.2 ** int(rng.integers(0, 8))
+            if xc[2] < 0.5:
+                continue
+            if kb8:
+                for right in (0, 1):
+                    if right and rng.random() > right_frac:
+                        continue
+                    xs = Trl[:3, :3] @ xc + Trl[:3, 3] if right else xc
+                    if xs[2] < 0.4:
+                        continue
+                    uv = kb8_project(TUMVI_CAM_R if right else TUMVI_CAM_L, xs[None])[0]
+                    if not (5 < uv[0] < w_img - 5 and 5 < uv[1] < h_img - 5):
+                        continue
+                    o = uv + rng.normal(0, noise_px, 2) * s * 0.5
+                    eKF.append(kf); eMP.append(j); eObs.append([o[0], o[1], -1.0]); eInv.append(4.0 / s ** 2); eRight.append(right)
+            else:
+                u = cam["fx"] * xc[0] / xc[2] + cam["cx"]; vv = cam["fy"] * xc[1] / xc[2] + cam["cy"]
+                if not (0 <= u < w_img and 0 <= vv < h_img):
+                    continue
+                o = np.array([u, vv, u - cam["bf"] / xc[2]]) + rng.normal(0, noise_px, 3) * s
+                if rng.random() < mono_frac or xc[2] > 25.0 or o[2] < 0:
+                    o[2] = -1
+                eKF.append(kf); eMP.append(j); eObs.append(o); eInv.append(1.0 / s ** 2); eRight.append(0)
+    true = np.stack([np.concatenate([Rk.ravel(), pk, vk, bg, ba]) for Rk, pk, vk in states])
+    init_s = true.copy()
+    for k in range(nKF):
+        if kind[k] in (1, 2):
+            continue
+        Rk, pk, vk = states[k]
+        Rk = Rk @ _rot_from_rotvec(rng.normal(0, 1, 3) / np.sqrt(3) * np.deg2rad(kf_deg))
+        init_s[k, :9] = Rk.ravel(); init_s[k, 9:12] = pk + rng.normal(0, 1, 3) / np.sqrt(3) * kf_trans
+        if kind[k] == 0:
+            init_s[k, 12:15] = vk + rng.normal(0, vel_noise, 3)
+            init_s[k, 15:18] += rng.normal(0, 0.001, 3) * bias_noise; init_s[k, 18:21] += rng.normal(0, 0.005, 3) * bias_noise
+    bias6 = np.concatenate([bg + rng.normal(0, 0.001, 3) * bias_noise, ba + rng.normal(0, 0.005, 3) * bias_noise])
+    X0 = X + rng.normal(0, point_noise, X.shape)
+    eInv = np.array(eInv, np.float32)
+    eKF = np.array(eKF, np.int32); eMP = np.array(eMP, np.int32)
+    if near_plane_point is not None:
+        k = int(near_plane_point)
+        j = len(X) - 1 - idle_points
+        e = np.flatnonzero((eMP == j) & (eKF == k))
+        assert len(e), "the last point is not seen by the near-plane keyframe"
+        init_s[k, :9] = np.eye(3).ravel(); init_s[k, 9:12] = 0.0          # the identity exactly: the camera coordinates are the point's own
+        X0[j] = np.array([0.5, 0.25, 2e-38])
+        eInv[e[0]] = 3e38
+    return dict(kfState=init_s.astype(np.float32), kfKind=kind, mpPos=X0.astype(np.float32), eKF=eKF, eMP=eMP,
+                eObs=np.array(eObs, np.float32).reshape(-1, 3), eInvSigma2=eInv, eRight=np.array(eRight, np.uint8),
+                iKF1=np.array(links, np.int32), iKF2=np.array(links, np.int32) + 1,
+                imuStart=np.array(start, np.int32), acc=np.array(acc, np.float32), gyro=np.array(gyro, np.float32), dt=np.array(dts, np.float32),
+                bias=np.concatenate([ba, bg]).astype(np.float32), Tbc12=np.concatenate([Tbc[:3, :3].ravel(), Tbc[:3, 3]]).astype(np.float32),
+                cam=cam, rig28=tumvi_rig28() if kb8 else None, init=bool(init), bias6=bias6.astype(np.float32), priorG=float(prior_g),
+                priorA=float(prior_a), true=true, truePts=X)
