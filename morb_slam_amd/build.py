@@ -68,6 +68,7 @@ def build_test_native(probe=False):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
     if probe:
         build_dense_probe()
+        build_math_probe()
     return out
 
 
@@ -82,3 +83,34 @@ def build_dense_probe():
     if _stale(PROBE_OUT, deps):
         subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + HIPCC_FLAGS + ["-o", PROBE_OUT, src])
     return PROBE_OUT
+
+
+MATH_PROBE_OUT = os.path.join(ROOT, "tests", "native", "libmath_probe.so")
+
+
+def build_math_probe():
+    """tests/native/libmath_probe.so: the scalar, 3 x 3 and wave-level device functions (libm restatements, camera models, SE3 / SO3 / Sim3
+    algebra, small dense helpers, row Jacobi, DPP reductions, RANSAC scaffolding) behind thin test-only entry points.  One translation unit
+    per header family (optimizer_device.h and sim3_math.h both define R_to_q in an unnamed namespace), each compiled with the library's
+    own HIPCC_FLAGS so that the headers build exactly as they do in libmorb_hip.so (which gains no export from it), then one link."""
+    from concurrent.futures import ThreadPoolExecutor
+    nat = os.path.join(ROOT, "tests", "native")
+    srcs = sorted(glob.glob(os.path.join(nat, "math_probe_*.hip")))
+    deps = srcs + [os.path.join(nat, "math_probe_common.h")] + glob.glob(os.path.join(CSRC, "*.h")) + \
+        glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(ROOT, "include", "morb", "*.h"))
+    if not _stale(MATH_PROBE_OUT, deps):
+        return MATH_PROBE_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objdir = os.path.join(nat, "_obj_math_probe")
+    os.makedirs(objdir, exist_ok=True)
+    flags = [f for f in HIPCC_FLAGS if f != "-shared"]
+
+    def compile_one(src):
+        obj = os.path.join(objdir, os.path.basename(src) + ".o")
+        subprocess.check_call([hipcc] + flags + ["-c", "-o", obj, src])
+        return obj
+
+    with ThreadPoolExecutor(max_workers=len(srcs)) as ex:
+        objs = list(ex.map(compile_one, srcs))
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", MATH_PROBE_OUT] + objs)
+    return MATH_PROBE_OUT

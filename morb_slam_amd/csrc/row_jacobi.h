@@ -32,7 +32,27 @@ __device__ __forceinline__ double g_colsum(const double* A, double* red, int m, 
 __device__ __forceinline__ void g_jacobi(double* A, double* V, double* red, int m, int l) {
   for (int e = l; e < m * m; e += ROW_LANES) V[e] = (e / m == e % m) ? 1.0 : 0.0;
   MORB_ROW_SYNC();
-  const double fro = g_colsum(A, red, m, l, false);
+  double fro = g_colsum(A, red, m, l, false);
+  // The stopping rule compares sums of squares, and those leave FP64's range for entries below 1e-154 or above 1e+154: fro is then 0 or
+  // inf and the loop would stop before its first rotation.  Such a matrix (never one the solvers build from image coordinates; the
+  // test is one comparison of a row-uniform value) is scaled by an exact power of two first, and scaled back at the end.
+  int back = 0;
+  if (!(fro >= 0x1p-600 && fro <= 0x1p600)) {
+    double c = 0;
+    if (l < m)
+      for (int i = 0; i < m; ++i) c = fmax(c, fabs(A[i * m + l]));
+    red[l] = c;
+    MORB_ROW_SYNC();
+    double mx = 0;
+    for (int j = 0; j < m; ++j) mx = fmax(mx, red[j]);
+    MORB_ROW_SYNC();
+    if (mx > 0 && mx < __builtin_huge_val()) {
+      (void)frexp(mx, &back);
+      for (int e = l; e < m * m; e += ROW_LANES) A[e] = ldexp(A[e], -back);
+      MORB_ROW_SYNC();
+      fro = g_colsum(A, red, m, l, false);
+    }
+  }
   for (int sweep = 0; sweep < 30; ++sweep) {
     const double off = g_colsum(A, red, m, l, true);
     if (!(off > 1e-30 * fro)) break;
@@ -69,6 +89,10 @@ __device__ __forceinline__ void g_jacobi(double* A, double* V, double* red, int 
         }
         MORB_ROW_SYNC();
       }
+  }
+  if (back != 0) {
+    for (int e = l; e < m * m; e += ROW_LANES) A[e] = ldexp(A[e], back);
+    MORB_ROW_SYNC();
   }
 }
 
