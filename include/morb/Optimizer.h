@@ -201,6 +201,23 @@ struct EssentialGraphView {
   int stats[4] = {0, 0, 0, 0};         // out: as morb_optimize_essential_graph's stats4
   double chi2[2] = {0, 0};             // out: the active chi2 before and after
 };
+// What the second overload of Optimizer::OptimizeEssentialGraph reads and writes (Optimizer.cc:1737-2063), flattened as
+// morb_optimize_essential_graph_merge takes it.  Vertices in ascending mnId; the entry applies the good / bad rule to the candidates itself.
+struct MergeEssentialGraphView {
+  int nKF = 0, nC = 0, nMP = 0;
+  const uint8_t* kfLists = nullptr;    // [nKF] bit 0 vpFixedKFs, bit 1 vpFixedCorrectedKFs, bit 2 vpNonFixedKFs: 1, 2, 4 or 6
+  float* kfTcw = nullptr;              // [nKF][7] in / out: GetPose(), unit quaternion xyzw and translation
+  float* kfTwc = nullptr;              // [nKF][7] in / out: GetPoseInverse()
+  float* kfTcwBefMerge = nullptr;      // [nKF][7] in / out: mTcwBefMerge (read for bit 1, written for bit 2)
+  float* kfTwcBefMerge = nullptr;      // [nKF][7] in / out: mTwcBefMerge
+  const int* cI = nullptr;             // [nC] setVertex(0, .) of a candidate edge, in the insertion order of :1888-1999
+  const int* cJ = nullptr;             // [nC] setVertex(1, .)
+  uint8_t* cKept = nullptr;            // [nC] out: 1 where both ends are good or both are bad (:1907-1913)
+  float* mpPos = nullptr;              // [nMP][3] in / out: the point correction of :2034-2062 (nMP = 0: none)
+  const int* mpRef = nullptr;          // [nMP] vertex of the reference keyframe, -1 = leave the point alone
+  int stats[4] = {0, 0, 0, 0};         // out: as morb_optimize_essential_graph's stats4
+  double chi2[2] = {0, 0};             // out: the active chi2 before and after
+};
 // The graph Optimizer::OptimizeEssentialGraph4DoF assembles (Optimizer.cc:5194-5426), flattened as morb_optimize_essential_graph_4dof takes
 // it.  Vertices in ascending mnId.  A vertex's camera pose and body state are given independently, as ImuCamPose's constructors fill them.
 struct PoseGraph4DoFView {
@@ -364,13 +381,24 @@ class Optimizer {
   }
 
   // static void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const
-  // KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool& bFixScale)  Optimizer.h:76-81, and the
-  // graph of the second overload (Optimizer.h:82-86), which differs in its per-vertex flags only.  The entry takes host arrays and stages them itself.
+  // KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool& bFixScale)  Optimizer.h:76-81.  The
+  // entry takes host arrays and stages them itself.
   static void OptimizeEssentialGraph(EssentialGraphView& g, int device = 0) {
     Slot& o = slot(device, kLoopClosing);
     std::lock_guard<std::mutex> lock(o.mu);   // the entry point works in the handle's grow-only workspace
     morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
     check(morb_optimize_essential_graph(o.h, g.nKF, g.kfSim3, g.kfFlags, g.nE, g.eI, g.eJ, g.eSji, g.nMP, g.mpPos, g.mpRef, g.stats, g.chi2));
+  }
+
+  // static void OptimizeEssentialGraph(KeyFrame* pCurKF, vector<KeyFrame*>& vpFixedKFs, vector<KeyFrame*>& vpFixedCorrectedKFs,
+  // vector<KeyFrame*>& vpNonFixedKFs, vector<MapPoint*>& vpNonCorrectedMPs)  Optimizer.h:82-86: map merging's pose graph, on the loop-closing
+  // handle (LoopClosing's thread runs loops and merges one after the other).
+  static void OptimizeEssentialGraph(MergeEssentialGraphView& g, int device = 0) {
+    Slot& o = slot(device, kLoopClosing);
+    std::lock_guard<std::mutex> lock(o.mu);
+    morb_adapter::hip_check(hipSetDevice(device), "hipSetDevice");
+    check(morb_optimize_essential_graph_merge(o.h, g.nKF, g.kfLists, g.kfTcw, g.kfTwc, g.kfTcwBefMerge, g.kfTwcBefMerge, g.nC, g.cI, g.cJ, g.cKept, g.nMP, g.mpPos,
+                                              g.mpRef, g.stats, g.chi2));
   }
 
   // static void OptimizeEssentialGraph4DoF(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const
@@ -585,6 +613,11 @@ class Optimizer {
   template <class MapT, class KF, class CorrMap, class ConnMap>
   static void OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, const CorrMap& NonCorrectedSim3, const CorrMap& CorrectedSim3,
                                      const ConnMap& LoopConnections, const bool& bFixScale);
+
+  // (include/Optimizer.h:82-86; call site LoopClosing.cc:1747-1749): overload 2 of OptimizeEssentialGraph, the pose graph of a map merge
+  template <class KF, class MP>
+  static void OptimizeEssentialGraph(KF* pCurKF, std::vector<KF*>& vpFixedKFs, std::vector<KF*>& vpFixedCorrectedKFs, std::vector<KF*>& vpNonFixedKFs,
+                                     std::vector<MP*>& vpNonCorrectedMPs);
 
   // (include/Optimizer.h:89-94; call site LoopClosing.cc:1201-1203): the pose graph of an inertial map whose IMU is initialised
   template <class MapT, class KF, class CorrMap, class ConnMap>

@@ -722,6 +722,126 @@ void Optimizer::OptimizeEssentialGraph(MapT* pMap, KF* pLoopKF, KF* pCurKF, cons
   pMap->IncreaseChangeIndex();   // :1734
 }
 
+// Optimizer::OptimizeEssentialGraph, overload 2 (Optimizer.cc:1737-2063), flattened for morb_optimize_essential_graph_merge.  Vertices: the
+// keyframes of the three lists that are not bad, in ascending mnId, each with the lists it is in.  Candidate edges in the reference's insertion
+// order (:1888-1999) — vpKFs is the three lists one behind the other, so a keyframe of two lists gives its candidates twice — with its
+// hasChild, sLoopEdges.count and mnId < tests; a candidate whose end has no vertex (a bad keyframe is neither good nor bad, :1907-1913) is
+// left out, the good / bad rule itself is the entry's.  Points in vpNonCorrectedMPs order: mpRef = the vertex of the reference keyframe behind
+// the while (pRefKF->isBad()) EraseObservation loop of :2038-2048, -1 for a bad point and for a reference outside the lists.  Where the
+// reference is undefined this skips: a point without a reference keyframe (:2038 dereferences it), an mnId beyond GetMaxKFid() (the
+// reference's vectors have nMaxKFid + 1 entries).  A keyframe listed twice in vpNonFixedKFs gets the tail once.
+struct MergeGraphFlat {
+  std::vector<uint8_t> kfLists, cKept;
+  std::vector<float> kfTcw, kfTwc, kfTcwBefMerge, kfTwcBefMerge, mpPos;
+  std::vector<int> cI, cJ, mpRef;
+  std::map<unsigned long, int> row;   // mnId -> vertex
+};
+namespace morb_glue {
+template <class KF, class MP>
+void flatten_merge_graph(KF* pCurKF, std::vector<KF*>& vpFixedKFs, std::vector<KF*>& vpFixedCorrectedKFs, std::vector<KF*>& vpNonFixedKFs,
+                         std::vector<MP*>& vpNonCorrectedMPs, MergeGraphFlat& f) {
+  auto* pMap = pCurKF->GetMap();
+  const unsigned long nMaxKFid = pMap->GetMaxKFid();
+  const int minFeat = 100;
+  std::map<unsigned long, std::pair<KF*, int>> byId;   // mnId -> keyframe, lists
+  std::vector<KF*>* const lists[3] = {&vpFixedKFs, &vpFixedCorrectedKFs, &vpNonFixedKFs};
+  for (int l = 0; l < 3; ++l)
+    for (KF* pKFi : *lists[l]) {
+      if (pKFi->isBad() || pKFi->mnId > nMaxKFid) continue;
+      auto& e = byId[pKFi->mnId];
+      e.first = pKFi; e.second |= 1 << l;
+    }
+  const int n = (int)byId.size();
+  f.kfLists.resize(n); f.kfTcw.resize((size_t)n * 7); f.kfTwc.resize((size_t)n * 7); f.kfTcwBefMerge.resize((size_t)n * 7); f.kfTwcBefMerge.resize((size_t)n * 7);
+  int r = 0;
+  for (auto& kv : byId) {
+    KF* pKFi = kv.second.first;
+    f.row[kv.first] = r;
+    f.kfLists[r] = (uint8_t)kv.second.second;
+    pose7(pKFi->GetPose(), &f.kfTcw[(size_t)r * 7]); pose7(pKFi->GetPoseInverse(), &f.kfTwc[(size_t)r * 7]);
+    pose7(pKFi->mTcwBefMerge, &f.kfTcwBefMerge[(size_t)r * 7]); pose7(pKFi->mTwcBefMerge, &f.kfTwcBefMerge[(size_t)r * 7]);
+    ++r;
+  }
+  auto rowOf = [&](KF* k) { const auto it = f.row.find(k->mnId); return (it == f.row.end() || byId[k->mnId].first != k) ? -1 : it->second; };
+  std::vector<KF*> vpKFs;   // :1876-1883
+  vpKFs.insert(vpKFs.end(), vpFixedKFs.begin(), vpFixedKFs.end());
+  vpKFs.insert(vpKFs.end(), vpFixedCorrectedKFs.begin(), vpFixedCorrectedKFs.end());
+  vpKFs.insert(vpKFs.end(), vpNonFixedKFs.begin(), vpNonFixedKFs.end());
+  std::set<KF*> spKFs(vpKFs.begin(), vpKFs.end());
+  auto add = [&](int ri, KF* pKFj) {
+    const int rj = rowOf(pKFj);
+    if (rj < 0) return;
+    f.cI.push_back(ri); f.cJ.push_back(rj);
+  };
+  for (KF* pKFi : vpKFs) {   // :1888-1999
+    const int ri = pKFi->isBad() ? -1 : rowOf(pKFi);
+    if (ri < 0) continue;
+    KF* pParentKFi = pKFi->GetParent();
+    if (pParentKFi && spKFs.find(pParentKFi) != spKFs.end()) add(ri, pParentKFi);
+    const auto sLoopEdges = pKFi->GetLoopEdges();
+    for (auto sit = sLoopEdges.begin(); sit != sLoopEdges.end(); ++sit) {
+      KF* pLKF = *sit;
+      if (spKFs.find(pLKF) != spKFs.end() && pLKF->mnId < pKFi->mnId) add(ri, pLKF);
+    }
+    const auto vpConnectedKFs = pKFi->GetCovisiblesByWeight(minFeat);
+    for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); ++vit) {
+      KF* pKFn = *vit;
+      if (pKFn && pKFn != pParentKFi && !pKFi->hasChild(pKFn) && !sLoopEdges.count(pKFn) && spKFs.find(pKFn) != spKFs.end()) {
+        if (!pKFn->isBad() && pKFn->mnId < pKFi->mnId) add(ri, pKFn);
+      }
+    }
+  }
+  f.cKept.assign(f.cI.size(), 0);
+  f.mpPos.assign(vpNonCorrectedMPs.size() * 3, 0.f); f.mpRef.assign(vpNonCorrectedMPs.size(), -1);
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);   // (EraseObservation below is :2046's, which the reference runs under this lock)
+  for (size_t i = 0; i < vpNonCorrectedMPs.size(); ++i) {   // :2034-2048
+    MP* pMPi = vpNonCorrectedMPs[i];
+    if (pMPi->isBad()) continue;
+    KF* pRefKF = pMPi->GetReferenceKeyFrame();
+    while (pRefKF && pRefKF->isBad()) {
+      pMPi->EraseObservation(pRefKF);
+      pRefKF = pMPi->GetReferenceKeyFrame();
+    }
+    if (!pRefKF || pRefKF->mnId > nMaxKFid) continue;
+    f.mpRef[i] = rowOf(pRefKF);
+    const auto X = pMPi->GetWorldPos();
+    for (int k = 0; k < 3; ++k) f.mpPos[i * 3 + k] = X(k);
+  }
+}
+}  // namespace morb_glue
+
+template <class KF, class MP>
+void Optimizer::OptimizeEssentialGraph(KF* pCurKF, std::vector<KF*>& vpFixedKFs, std::vector<KF*>& vpFixedCorrectedKFs, std::vector<KF*>& vpNonFixedKFs,
+                                       std::vector<MP*>& vpNonCorrectedMPs) {
+  MergeGraphFlat f;
+  morb_glue::flatten_merge_graph(pCurKF, vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs, vpNonCorrectedMPs, f);
+  MergeEssentialGraphView g;
+  g.nKF = (int)f.kfLists.size(); g.nC = (int)f.cI.size(); g.nMP = (int)f.mpRef.size();
+  g.kfLists = f.kfLists.data(); g.kfTcw = f.kfTcw.data(); g.kfTwc = f.kfTwc.data(); g.kfTcwBefMerge = f.kfTcwBefMerge.data(); g.kfTwcBefMerge = f.kfTwcBefMerge.data();
+  g.cI = g.nC ? f.cI.data() : nullptr; g.cJ = g.nC ? f.cJ.data() : nullptr; g.cKept = g.nC ? f.cKept.data() : nullptr;
+  g.mpPos = g.nMP ? f.mpPos.data() : nullptr; g.mpRef = g.nMP ? f.mpRef.data() : nullptr;
+  if (g.nKF > 0) OptimizeEssentialGraph(g);   // optimize(20) (:2009-2010) and the tail's arithmetic
+  auto* pMap = pCurKF->GetMap();
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);   // :2012
+  std::set<unsigned long> done;
+  for (KF* pKFi : vpNonFixedKFs) {   // :2015-2030
+    if (pKFi->isBad()) continue;
+    const auto it = f.row.find(pKFi->mnId);
+    if (it == f.row.end() || !done.insert(pKFi->mnId).second) continue;
+    pKFi->mTcwBefMerge = pKFi->GetPose();
+    pKFi->mTwcBefMerge = pKFi->GetPoseInverse();
+    pKFi->SetPose(morb_glue::make_se3<typename std::decay<decltype(pKFi->GetPose())>::type>(&f.kfTcw[(size_t)it->second * 7]));
+  }
+  for (size_t i = 0; i < vpNonCorrectedMPs.size(); ++i) {   // :2034-2062
+    MP* pMPi = vpNonCorrectedMPs[i];
+    if (pMPi->isBad() || f.mpRef[i] < 0 || !(f.kfLists[f.mpRef[i]] & 6)) continue;   // (:2059: a reference of vpFixedKFs, the point stays)
+    typename std::decay<decltype(pMPi->GetWorldPos())>::type X;
+    for (int k = 0; k < 3; ++k) X(k) = f.mpPos[i * 3 + k];
+    pMPi->SetWorldPos(X);
+    pMPi->UpdateNormalAndDepth();
+  }
+}
+
 // Optimizer::OptimizeEssentialGraph4DoF (Optimizer.cc:5163-5472), flattened for morb_optimize_essential_graph_4dof.  Vertices: the keyframes
 // of GetAllKeyFrames() that are not bad, in ascending mnId; VertexPose4DoF(pKF) from the keyframe's float members, or
 // VertexPose4DoF(Rwc, twc, pKF) from CorrectedSim3's inverse (:5201-5214); fixed = pLoopKF (:5216).  mImuCalib.mTcb is taken from the first

@@ -1110,6 +1110,39 @@ int morb_merge_inertial_ba_fisheye(morb_optimizer*, int nKF, float* kfState21, c
 int morb_optimize_essential_graph(morb_optimizer*, int nKF, double* kfSim3, const uint8_t* kfFlags, int nE, const int* eI,
                                   const int* eJ, const double* eSji, int nMP, float* mpPos, const int* mpRef, int* stats4,
                                   double* chi2);
+/* void static Optimizer::OptimizeEssentialGraph(KeyFrame* pCurKF, vector<KeyFrame*>& vpFixedKFs, vector<KeyFrame*>& vpFixedCorrectedKFs,
+ * vector<KeyFrame*>& vpNonFixedKFs, vector<MapPoint*>& vpNonCorrectedMPs)  Optimizer.h:83-87, Optimizer.cc:1737-2063: the Sim3 pose graph
+ * LoopClosing::MergeLocal optimises behind the welding bundle adjustment on every non-monocular sensor (LoopClosing.cc:1747-1749), flattened
+ * (HOST pointers).  nKF vertices, the keyframes of the three lists that are not bad, in ascending mnId (the order of elimination).
+ * kfLists[k]: bit 0 = vpFixedKFs (fixed, _fix_scale, vpGoodPose; :1783-1808), bit 1 = vpFixedCorrectedKFs (fixed, good and bad, vScw from
+ * mTcwBefMerge; :1813-1843), bit 2 = vpNonFixedKFs (free with a free scale, vpBadPose, vScw = the pose; :1845-1874).  Legal values: 1, 2, 4,
+ * and 6 for a keyframe of both the window and the non-fixed list, which keeps the vertex of the window (sIdKF, :1850) and still gets the
+ * tail.  kfTcw / kfTwc / kfTcwBefMerge / kfTwcBefMerge = GetPose(), GetPoseInverse(), mTcwBefMerge, mTwcBefMerge of every vertex, 7 floats
+ * each (unit quaternion xyzw and translation, as morb_merge_bundle_adjustment takes a pose), in and out.  nC candidate edges in the
+ * reference's insertion order (:1888-1999), chosen by topology alone: setVertex(0, cI), setVertex(1, cJ); a keyframe of two lists is
+ * visited twice there and gives its candidates twice.  The entry applies the rule of :1907-1913 itself — an edge exists where both ends
+ * are good or both are bad — and reports it in cKept[c] (1 = the edge exists).  Its measurement is Sjw * Swi with the reference's quirks:
+ * Swi = vScw[i]^-1 only where i is bad, so for a keyframe of vpFixedKFs it is the default g2o::Sim3(), the identity; Sjw =
+ * (vCorrectedSwc[j])^-1 where both are good, else vScw[j]; correctedSwi is never used.  An edge between two fixed vertices moves nothing and
+ * is a constant of chi2, which g2o's stop rule sees.  On the device: the float poses go to FP64 through Sophus' normalising cast, the
+ * measurements are formed, then setUserLambdaInit(1e-16) (:1767), optimize(20) (:2010) by the solver of morb_optimize_essential_graph
+ * unchanged, then the tail of :2015-2062: every vertex with bit 2 gets kfTcwBefMerge / kfTwcBefMerge = the bytes of kfTcw / kfTwc at entry,
+ * kfTcw = SE3d(q, t / s).cast<float>() and kfTwc = its inverse as SE3f::inverse computes it in float (SetPose); every other vertex keeps
+ * the bytes of all four.  A vertex without an edge is not in the system; with bit 2 its pose still makes the float -> double -> float
+ * round trip.  mpRef[m] = the vertex of the point's reference keyframe, -1 = skip (a bad point, a reference outside the lists); a point
+ * whose reference has bit 1 or bit 2 becomes (Twr * TwrBefMerge^-1) * P in float — the SE3f product first, then the point — with Twr and
+ * TwrBefMerge as they stand behind the tail (for a vertex of bit 1 alone: kfTwc and kfTwcBefMerge as given, LoopClosing.cc:1544-1546);
+ * a point whose reference is in vpFixedKFs keeps its bytes (:2059-2061).  Quaternions are normalised as Eigen's four-wide sum does it,
+ * (x^2 + z^2) + (y^2 + w^2).  nMP = 0 is allowed (mpPos, mpRef may be NULL), and nC = 0 (cI, cJ, cKept may be NULL).  stats4 and chi2 as
+ * morb_optimize_essential_graph gives them.  No free vertex has an edge: the solve is skipped, stats4 and chi2 are zero, the tail still
+ * runs.  MORB_ERR_INVALID: a NULL array, an index out of range, cI == cJ, a non-finite pose or a zero quaternion (the poses before the merge
+ * are read, and checked, for vertices with bit 1 only), a value of kfLists other than 1, 2, 4, 6 (the reference would add one vertex id
+ * twice); MORB_ERR_CAPACITY: the envelope exceeds what the handle may grow to (2^22 blocks); both before any launch, nothing written.  One
+ * upload and one download, on the handle's stream.  Left with the caller: the candidate list (:1888-1999), the map's mutex, SetPose,
+ * SetWorldPos, UpdateNormalAndDepth and the EraseObservation loop of :2038-2048. */
+int morb_optimize_essential_graph_merge(morb_optimizer*, int nKF, const uint8_t* kfLists, float* kfTcw, float* kfTwc,
+                                        float* kfTcwBefMerge, float* kfTwcBefMerge, int nC, const int* cI, const int* cJ,
+                                        uint8_t* cKept, int nMP, float* mpPos, const int* mpRef, int* stats4, double* chi2);
 /* acos(d[i]) and log(s[i]) as g2o::Sim3::log (types/sim3.h:151, :181) gets them inside morb_optimize_essential_graph: the device
  * library's, for the tests that measure them against the host libm (HOST pointers, n > 0). */
 int morb_sim3_log_libm(morb_optimizer*, int n, const double* d, const double* s, double* acosOut, double* logOut);

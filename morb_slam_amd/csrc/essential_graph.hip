@@ -19,6 +19,10 @@
 //   * k_eg_errors / k_eg_decide: the trial's chi2 per edge, summed in edge order by one lane; g2o's Levenberg-Marquardt decisions
 //     (lm_control.h) with setUserLambdaInit(1e-16) and optimize(20) on the device, the host queueing trials through ba_host.h's lm_slot_queue.
 //   * k_eg_finish: the point correction of :1707-1731 behind the solve.
+//   * k_egm_prepare / k_egm_finish: the second overload (map merging, :1737-2063) around the same solve.  Before it, the float poses of the
+//     three lists become g2o::Sim3 estimates in FP64 and every kept edge gets its measurement by the reference's good / bad rules; after
+//     it, the SE3 recovery, the float inverse, the BefMerge copies and the float SE3 point correction of :2015-2062.  The two entries
+//     share the carve of the solver's arrays and the launch sequence (eg_carve_plan, eg_carve_solver, eg_solve).
 // A vertex without an edge is not in g2o's active set: it is not in the system and keeps its bytes.  A free component with no path to a
 // fixed vertex is gauge-free; it is neither detected nor repaired here (lambda keeps the factorisation defined, as it does in g2o).
 // acos and log inside Sim3::log are the device library's (tests/test_essential_graph_gpu.py measures them against the host libm).
@@ -581,6 +585,247 @@ __global__ __launch_bounds__(EG_NT) void k_eg_libm(int n, const double* d, const
   logOut[i] = log(s[i]);
 }
 
+// ---- map merging: the second overload (Optimizer.cc:1737-2063) around the same solve ----
+// A vertex's list mask.  vpGoodPose = FIXED or CORRECTED, vpBadPose = CORRECTED or NONFIXED (:1806-1807, :1841-1842, :1872-1873); a vertex
+// of CORRECTED | NONFIXED is the fixed-corrected one (sIdKF, :1850) that the tail of :2015-2030 still visits.
+enum { MG_FIXED = 1, MG_CORRECTED = 2, MG_NONFIXED = 4 };
+
+struct MgDev {
+  int nKF, nE, nMP;
+  const uint8_t* lists;      // [nKF] MG_*
+  const float* in;           // [4][nKF][7] Tcw, Twc, TcwBefMerge, TwcBefMerge at entry: quaternion xyzw, translation
+  float* out;                // [4][nKF][7] the same at exit, and [nMP][3] the points at exit behind them
+  const int *eI, *eJ;        // [nE] the kept edges
+  double* eS;                // [nE][8] their measurements
+  double* S;                 // [nKF][8] the estimates
+  const float* mp;           // [nMP][3] the points at entry
+  const int* mpRef;          // [nMP]
+};
+
+struct Se3f { float q[4]; float t[3]; };   // Sophus::SE3f: unit quaternion x y z w, translation
+
+// SO3(quaternion): coeffs() /= norm(), the squares summed as Eigen's four-wide reduction sums them, (x^2 + z^2) + (y^2 + w^2)
+__device__ __forceinline__ void mg_normalize(double* q) {
+  const double n = sqrt((q[0] * q[0] + q[2] * q[2]) + (q[1] * q[1] + q[3] * q[3]));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] /= n;
+}
+__device__ __forceinline__ void mg_normalize(float* q) {
+  const float n = sqrtf((q[0] * q[0] + q[2] * q[2]) + (q[1] * q[1] + q[3] * q[3]));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] /= n;
+}
+// SO3f::operator*(point): uv = q.vec x p, uv += uv, p + w uv + q.vec x uv
+__device__ __forceinline__ void mg_rotate(const float* q, const float* p, float* o) {
+  float a = q[1] * p[2] - q[2] * p[1], b = q[2] * p[0] - q[0] * p[2], c = q[0] * p[1] - q[1] * p[0];
+  a += a; b += b; c += c;
+  o[0] = (p[0] + q[3] * a) + (q[1] * c - q[2] * b);
+  o[1] = (p[1] + q[3] * b) + (q[2] * a - q[0] * c);
+  o[2] = (p[2] + q[3] * c) + (q[0] * b - q[1] * a);
+}
+__device__ __forceinline__ Se3f mg_load(const float* p) {
+  Se3f T;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) T.q[k] = p[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) T.t[k] = p[4 + k];
+  return T;
+}
+__device__ __forceinline__ void mg_store(float* p, const Se3f& T) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) p[k] = T.q[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[4 + k] = T.t[k];
+}
+// SE3f::inverse: invR = SO3f(q.conjugate()), which normalises; SE3f(invR, invR * (t * -1))
+__device__ __forceinline__ Se3f mg_inverse(const Se3f& T) {
+  Se3f r;
+  r.q[0] = -T.q[0]; r.q[1] = -T.q[1]; r.q[2] = -T.q[2]; r.q[3] = T.q[3];
+  mg_normalize(r.q);
+  const float v[3] = {T.t[0] * -1.f, T.t[1] * -1.f, T.t[2] * -1.f};
+  mg_rotate(r.q, v, r.t);
+  return r;
+}
+// SE3f::operator*: SO3f(a.q * b.q), which normalises; a.t + a.so3 * b.t
+__device__ __forceinline__ Se3f mg_mul(const Se3f& A, const Se3f& B) {
+  Se3f r;
+  const float *a = A.q, *b = B.q;
+  r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+  r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+  r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+  r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+  mg_normalize(r.q);
+  float rt[3];
+  mg_rotate(A.q, B.t, rt);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) r.t[k] = A.t[k] + rt[k];
+  return r;
+}
+// Sophus::SE3d T = pose.cast<double>() (SO3d(q.cast<double>()) normalises); g2o::Sim3(T.unit_quaternion(), T.translation(), 1.0)
+__device__ __forceinline__ Sim3d mg_sim3_of(const float* p) {
+  Sim3d S;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) S.q[k] = (double)p[k];
+  mg_normalize(S.q);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) S.t[k] = (double)p[4 + k];
+  S.s = 1.0;
+  return S;
+}
+// :2022-2029: Sophus::SE3d Tiw(CorrectedSiw.rotation(), CorrectedSiw.translation() / s), Tiw.cast<float>()
+__device__ __forceinline__ Se3f mg_se3_of(const Sim3d& S) {
+  double q[4] = {S.q[0], S.q[1], S.q[2], S.q[3]};
+  mg_normalize(q);
+  Se3f T;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) T.q[k] = (float)q[k];
+  mg_normalize(T.q);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) T.t[k] = (float)(S.t[k] / S.s);
+  return T;
+}
+
+// Before the solve.  Lane v < nKF: the estimate Siw of vertex v (:1790-1794, :1820-1824, :1855-1859).  Lane nKF + e: the measurement of kept
+// edge e, Sji = Sjw * Swi (:1892-1916): Swi = vScw[i]^-1 where i is bad and the default g2o::Sim3() otherwise; Sjw = vCorrectedSwc[j]^-1
+// where both are good, else vScw[j].  vScw is the Sim3 of mTcwBefMerge on a fixed-corrected vertex and of the pose on a non-fixed one.
+__global__ __launch_bounds__(EG_NT) void k_egm_prepare(MgDev D) {
+  const int gid = blockIdx.x * EG_NT + threadIdx.x;
+  if (gid < D.nKF) {
+    eg_store(D.S + (size_t)gid * 8, mg_sim3_of(D.in + (size_t)gid * 7));
+    return;
+  }
+  const int e = gid - D.nKF;
+  if (e >= D.nE) return;
+  const int i = D.eI[e], j = D.eJ[e];
+  const int li = D.lists[i], lj = D.lists[j];
+  const float* bef = D.in + (size_t)2 * D.nKF * 7;   // TcwBefMerge
+  Sim3d Swi;
+  Swi.q[0] = Swi.q[1] = Swi.q[2] = 0; Swi.q[3] = 1; Swi.t[0] = Swi.t[1] = Swi.t[2] = 0; Swi.s = 1;
+  if (li & (MG_CORRECTED | MG_NONFIXED)) Swi = sim3_inverse(mg_sim3_of(((li & MG_CORRECTED) ? bef : D.in) + (size_t)i * 7));
+  Sim3d Sjw;
+  if ((li & (MG_FIXED | MG_CORRECTED)) && (lj & (MG_FIXED | MG_CORRECTED))) Sjw = sim3_inverse(sim3_inverse(mg_sim3_of(D.in + (size_t)j * 7)));
+  else Sjw = mg_sim3_of(((lj & MG_CORRECTED) ? bef : D.in) + (size_t)j * 7);
+  eg_store(D.eS + (size_t)e * 8, sim3_mul(Sjw, Swi));
+}
+
+// After the solve (:2015-2062).  Lane v < nKF: a vertex of vpNonFixedKFs gets mTcwBefMerge / mTwcBefMerge = the pose and its inverse at
+// entry, SetPose(SE3d(q, t / s).cast<float>()) and mTwc = mTcw.inverse() in float; every other vertex keeps its four poses.  Lane nKF + m:
+// a point whose reference keyframe is bad-flagged becomes (Twr * TwrBefMerge^-1) * P in float, with the values the vertex lanes write
+// (recomputed here: no lane reads another's output).
+__global__ __launch_bounds__(EG_NT) void k_egm_finish(MgDev D) {
+  const int gid = blockIdx.x * EG_NT + threadIdx.x;
+  const size_t plane = (size_t)D.nKF * 7;
+  if (gid < D.nKF) {
+    const size_t at = (size_t)gid * 7;
+    if (D.lists[gid] & MG_NONFIXED) {
+      const Se3f Tcw = mg_se3_of(eg_load(D.S + (size_t)gid * 8));
+      mg_store(D.out + at, Tcw);
+      mg_store(D.out + plane + at, mg_inverse(Tcw));
+#pragma unroll
+      for (int k = 0; k < 7; ++k) { D.out[2 * plane + at + k] = D.in[at + k]; D.out[3 * plane + at + k] = D.in[plane + at + k]; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 7; ++k)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) D.out[a * plane + at + k] = D.in[a * plane + at + k];
+    }
+    return;
+  }
+  const int m = gid - D.nKF;
+  if (m >= D.nMP) return;
+  const int v = D.mpRef[m];
+  const float P[3] = {D.mp[m * 3], D.mp[m * 3 + 1], D.mp[m * 3 + 2]};
+  float* o = D.out + 4 * plane + (size_t)m * 3;
+  const int l = v < 0 ? 0 : D.lists[v];
+  if (!(l & (MG_CORRECTED | MG_NONFIXED))) {   // no reference, or (:2059) "a reference KF from another map": the point stays
+    o[0] = P[0]; o[1] = P[1]; o[2] = P[2];
+    return;
+  }
+  const size_t at = (size_t)v * 7;
+  Se3f Twr, TwrBef;
+  if (l & MG_NONFIXED) {
+    Twr = mg_inverse(mg_se3_of(eg_load(D.S + (size_t)v * 8)));
+    TwrBef = mg_load(D.in + plane + at);
+  } else {
+    Twr = mg_load(D.in + plane + at);
+    TwrBef = mg_load(D.in + 3 * plane + at);
+  }
+  const Se3f T = mg_mul(Twr, mg_inverse(TwrBef));
+  float r[3];
+  mg_rotate(T.q, P, r);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[k] = r[k] + T.t[k];
+}
+
+// ---- the host side both entries share ----
+// the graph lists of a plan, in the upload region
+void eg_carve_plan(ArenaCarver& A, EgDev& D, const EnvelopePlan& P, const uint8_t* flags, const int* eI, const int* eJ) {
+  D.eI = (const int*)A.take(eI, sizeof(int) * D.nE); D.eJ = (const int*)A.take(eJ, sizeof(int) * D.nE);
+  D.flags = (const uint8_t*)A.take(flags, D.nKF); D.col = (const int*)A.take(P.col.data(), sizeof(int) * D.nKF);
+  D.rowFirst = (const int*)A.take(P.rowFirst.data(), sizeof(int) * D.n); D.rowOff = (const int*)A.take(P.rowOff.data(), sizeof(int) * (D.n + 1));
+  D.colStart = (const int*)A.take(P.colStart.data(), sizeof(int) * (D.n + 1)); D.colRows = (const int*)A.take(P.colRows.data(), sizeof(int) * P.colRows.size());
+  D.listStart = (const int*)A.take(P.listStart.data(), sizeof(int) * P.listStart.size());
+  D.listItems = (const int*)A.take(P.listItems.data(), sizeof(int) * P.listItems.size());
+}
+// the solver's own arrays, device only
+void eg_carve_solver(ArenaCarver& A, EgDev& D) {
+  const int nKF = D.nKF, nE = D.nE, n = D.n;
+  D.T = (double*)A.take(nullptr, sizeof(double) * 8 * nKF);
+  D.J = (double*)A.take(nullptr, sizeof(double) * 98 * nE); D.err = (double*)A.take(nullptr, sizeof(double) * 7 * nE);
+  D.chiE = (double*)A.take(nullptr, sizeof(double) * nE);
+  D.H = (double*)A.take(nullptr, sizeof(double) * 49 * (size_t)D.nBlocks); D.L = (double*)A.take(nullptr, sizeof(double) * 49 * (size_t)D.nBlocks);
+  D.b = (double*)A.take(nullptr, sizeof(double) * 7 * n); D.y = (double*)A.take(nullptr, sizeof(double) * 7 * n);
+  D.x = (double*)A.take(nullptr, sizeof(double) * 7 * n); D.d = (double*)A.take(nullptr, sizeof(double) * 7 * n);
+  D.lm = (LmControl*)A.take(nullptr, sizeof(LmControl)); D.chi2 = (double*)A.take(nullptr, sizeof(double) * 2);
+  D.lmi = (int*)A.take(nullptr, sizeof(int) * 8);
+}
+// the handle's block and its pinned mirror for a carve function, bound and carved
+template <class Carve>
+int eg_bind(morb_optimizer* o, ArenaCarver& A, Carve&& carve, char** arena, char** stage) {
+  carve();   // (dry: sizes)
+  { const int rc = grow(o->essentialGraph, A.uploadBytes() + A.deviceBytes(), arena); if (rc != MORB_OK) return rc; }
+  { const int rc = grow(o->stage, A.uploadBytes(), stage); if (rc != MORB_OK) return rc; }
+  A.bind(*arena, *stage);
+  carve();
+  if (!A.ok()) { set_error("the two carve passes of OptimizeEssentialGraph differ"); return MORB_ERR_HIP; }
+  return MORB_OK;
+}
+// setUserLambdaInit(1e-16), optimize(20) on the uploaded graph: the clears, computeActiveErrors and the queue of trials
+int eg_solve(morb_optimizer* o, hipStream_t st, EgDev& D) {
+  const int nE = D.nE, n = D.n, nBlocks = D.nBlocks;
+  int *hostw = nullptr, *hostwDev = nullptr;
+  MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
+  D.lmHost = hostwDev;
+  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  // the workspace is reused from call to call: what the first kernels expect to find zero is cleared behind the carve
+  MORB_HIP_CHECK(hipMemsetAsync(D.lmi, 0, sizeof(int) * 8, st));
+  MORB_HIP_CHECK(hipMemsetAsync(D.lm, 0, sizeof(LmControl), st));
+  MORB_HIP_CHECK(hipMemsetAsync(D.x, 0, sizeof(double) * 7 * n, st));   // the solver's x before the first solve
+  MORB_HIP_CHECK(hipMemsetAsync(D.J, 0, sizeof(double) * 98 * nE, st));   // (the Jacobian of a fixed vertex is never written, and never read)
+
+  const int edgeBlocks = div_up(nE, EG_NT);
+  const size_t asmItems = (size_t)nBlocks * 49 + (size_t)n * 7;
+  hipLaunchKernelGGL(k_eg_errors, dim3(edgeBlocks), dim3(EG_NT), 0, st, D, 0);   // computeActiveErrors
+  hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 1);
+  MORB_HIP_CHECK(hipGetLastError());
+  // a slot is one trial: at most 20 iterations of 10 trials
+  const int q = lm_slot_queue(200, hostw + 0, hostw + 1, [&](int) {
+    hipLaunchKernelGGL(k_eg_linearize, dim3(div_up(nE * 16, EG_NT)), dim3(EG_NT), 0, st, D);   // (both run only behind an accepted trial)
+    hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)((asmItems + EG_NT - 1) / EG_NT)), dim3(EG_NT), 0, st, D);
+    hipLaunchKernelGGL(k_eg_factor, dim3(1), dim3(EG_NT), 0, st, D);
+    hipLaunchKernelGGL(k_eg_backsub, dim3(1), dim3(EG_NT), 0, st, D);
+    hipLaunchKernelGGL(k_eg_errors, dim3(edgeBlocks), dim3(EG_NT), 0, st, D, 1);
+    hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 0);
+    if (hipGetLastError() != hipSuccess) { set_error("OptimizeEssentialGraph: a trial's launch failed"); return (int)MORB_ERR_HIP; }
+    return (int)MORB_OK;
+  }, [&]() {
+    const hipError_t e = hipStreamQuery(st);
+    if (e != hipSuccess && e != hipErrorNotReady) set_error("OptimizeEssentialGraph: %s while waiting for the LM decision", hipGetErrorString(e));
+    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
+  }, []() {});
+  return q < 0 ? MORB_ERR_HIP : MORB_OK;
+}
+
 }  // namespace
 
 extern "C" int morb_optimize_essential_graph(morb_optimizer* o, int nKF, double* kfSim3, const uint8_t* kfFlags, int nE, const int* eI,
@@ -608,72 +853,25 @@ extern "C" int morb_optimize_essential_graph(morb_optimizer* o, int nKF, double*
   }
   MORB_REQUIRE(fit == EnvelopeFit::Ok, MORB_ERR_CAPACITY, "the envelope of the essential graph exceeds what the handle may grow to");
   const int n = P.n, nBlocks = P.nBlocks;
-  const std::vector<int>&col = P.col, &rowFirst = P.rowFirst, &rowOff = P.rowOff, &colStart = P.colStart, &colRows = P.colRows, &listStart = P.listStart,
-                        &listItems = P.listItems;
 
   MORB_ENTER(st, o, nullptr);
   EgDev D;
   memset(&D, 0, sizeof D);
   D.nKF = nKF; D.nE = nE; D.n = n; D.nBlocks = nBlocks; D.nMP = nMP; D.maxIts = 20;
   ArenaCarver A;
-  auto carve = [&]() {
-    D.eI = (const int*)A.take(eI, sizeof(int) * nE); D.eJ = (const int*)A.take(eJ, sizeof(int) * nE);
-    D.eS = (const double*)A.take(eSji, sizeof(double) * 8 * nE);
-    D.flags = (const uint8_t*)A.take(kfFlags, nKF); D.col = (const int*)A.take(col.data(), sizeof(int) * nKF);
-    D.rowFirst = (const int*)A.take(rowFirst.data(), sizeof(int) * n); D.rowOff = (const int*)A.take(rowOff.data(), sizeof(int) * (n + 1));
-    D.colStart = (const int*)A.take(colStart.data(), sizeof(int) * (n + 1)); D.colRows = (const int*)A.take(colRows.data(), sizeof(int) * colRows.size());
-    D.listStart = (const int*)A.take(listStart.data(), sizeof(int) * listStart.size());
-    D.listItems = (const int*)A.take(listItems.data(), sizeof(int) * listItems.size());
-    D.S = (double*)A.take(kfSim3, sizeof(double) * 8 * nKF); D.S0 = (const double*)A.take(kfSim3, sizeof(double) * 8 * nKF);
-    if (nMP) { D.mp = (float*)A.take(mpPos, sizeof(float) * 3 * nMP); D.mpRef = (const int*)A.take(mpRef, sizeof(int) * nMP); }
-    D.T = (double*)A.take(nullptr, sizeof(double) * 8 * nKF);
-    D.J = (double*)A.take(nullptr, sizeof(double) * 98 * nE); D.err = (double*)A.take(nullptr, sizeof(double) * 7 * nE);
-    D.chiE = (double*)A.take(nullptr, sizeof(double) * nE);
-    D.H = (double*)A.take(nullptr, sizeof(double) * 49 * (size_t)nBlocks); D.L = (double*)A.take(nullptr, sizeof(double) * 49 * (size_t)nBlocks);
-    D.b = (double*)A.take(nullptr, sizeof(double) * 7 * n); D.y = (double*)A.take(nullptr, sizeof(double) * 7 * n);
-    D.x = (double*)A.take(nullptr, sizeof(double) * 7 * n); D.d = (double*)A.take(nullptr, sizeof(double) * 7 * n);
-    D.lm = (LmControl*)A.take(nullptr, sizeof(LmControl)); D.chi2 = (double*)A.take(nullptr, sizeof(double) * 2);
-    D.lmi = (int*)A.take(nullptr, sizeof(int) * 8);
-  };
-  carve();   // (dry: sizes)
   char *arena = nullptr, *stage = nullptr;
-  { const int rc = grow(o->essentialGraph, A.uploadBytes() + A.deviceBytes(), &arena); if (rc != MORB_OK) return rc; }
-  { const int rc = grow(o->stage, A.uploadBytes(), &stage); if (rc != MORB_OK) return rc; }
-  A.bind(arena, stage);
-  carve();
-  if (!A.ok()) { set_error("the two carve passes of OptimizeEssentialGraph differ"); return MORB_ERR_HIP; }
-  int *hostw = nullptr, *hostwDev = nullptr;
-  MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
-  D.lmHost = hostwDev;
-  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  {
+    const int rc = eg_bind(o, A, [&]() {
+      eg_carve_plan(A, D, P, kfFlags, eI, eJ);
+      D.eS = (const double*)A.take(eSji, sizeof(double) * 8 * nE);
+      D.S = (double*)A.take(kfSim3, sizeof(double) * 8 * nKF); D.S0 = (const double*)A.take(kfSim3, sizeof(double) * 8 * nKF);
+      if (nMP) { D.mp = (float*)A.take(mpPos, sizeof(float) * 3 * nMP); D.mpRef = (const int*)A.take(mpRef, sizeof(int) * nMP); }
+      eg_carve_solver(A, D);
+    }, &arena, &stage);
+    if (rc != MORB_OK) return rc;
+  }
   MORB_HIP_CHECK(hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st));   // the one upload
-  // the workspace is reused from call to call: what the first kernels expect to find zero is cleared behind the carve
-  MORB_HIP_CHECK(hipMemsetAsync(D.lmi, 0, sizeof(int) * 8, st));
-  MORB_HIP_CHECK(hipMemsetAsync(D.lm, 0, sizeof(LmControl), st));
-  MORB_HIP_CHECK(hipMemsetAsync(D.x, 0, sizeof(double) * 7 * n, st));   // the solver's x before the first solve
-  MORB_HIP_CHECK(hipMemsetAsync(D.J, 0, sizeof(double) * 98 * nE, st));   // (the Jacobian of a fixed vertex is never written, and never read)
-
-  const int edgeBlocks = div_up(nE, EG_NT);
-  const size_t asmItems = (size_t)nBlocks * 49 + (size_t)n * 7;
-  hipLaunchKernelGGL(k_eg_errors, dim3(edgeBlocks), dim3(EG_NT), 0, st, D, 0);   // computeActiveErrors
-  hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 1);
-  MORB_HIP_CHECK(hipGetLastError());
-  // a slot is one trial: at most 20 iterations of 10 trials
-  const int q = lm_slot_queue(200, hostw + 0, hostw + 1, [&](int) {
-    hipLaunchKernelGGL(k_eg_linearize, dim3(div_up(nE * 16, EG_NT)), dim3(EG_NT), 0, st, D);   // (both run only behind an accepted trial)
-    hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)((asmItems + EG_NT - 1) / EG_NT)), dim3(EG_NT), 0, st, D);
-    hipLaunchKernelGGL(k_eg_factor, dim3(1), dim3(EG_NT), 0, st, D);
-    hipLaunchKernelGGL(k_eg_backsub, dim3(1), dim3(EG_NT), 0, st, D);
-    hipLaunchKernelGGL(k_eg_errors, dim3(edgeBlocks), dim3(EG_NT), 0, st, D, 1);
-    hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 0);
-    if (hipGetLastError() != hipSuccess) { set_error("OptimizeEssentialGraph: a trial's launch failed"); return (int)MORB_ERR_HIP; }
-    return (int)MORB_OK;
-  }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("OptimizeEssentialGraph: %s while waiting for the LM decision", hipGetErrorString(e));
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, []() {});
-  if (q < 0) return MORB_ERR_HIP;
+  { const int rc = eg_solve(o, st, D); if (rc != MORB_OK) return rc; }
   if (nMP) hipLaunchKernelGGL(k_eg_finish, dim3(div_up(nMP, EG_NT)), dim3(EG_NT), 0, st, D);
   MORB_HIP_CHECK(hipGetLastError());
   int hi[8];
@@ -683,6 +881,95 @@ extern "C" int morb_optimize_essential_graph(morb_optimizer* o, int nKF, double*
   if (nMP) MORB_HIP_CHECK(hipMemcpyAsync(mpPos, D.mp, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st));
   MORB_HIP_CHECK(hipStreamSynchronize(st));   // (also drains a queue that ran out of slots before the words are reset again)
   stats4[0] = hi[EG_ITS]; stats4[1] = hi[EG_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
+  return MORB_OK;
+}
+
+extern "C" int morb_optimize_essential_graph_merge(morb_optimizer* o, int nKF, const uint8_t* kfLists, float* kfTcw, float* kfTwc, float* kfTcwBefMerge,
+                                                   float* kfTwcBefMerge, int nC, const int* cI, const int* cJ, uint8_t* cKept, int nMP, float* mpPos,
+                                                   const int* mpRef, int* stats4, double* chi2) {
+  MORB_REQUIRE(o && kfLists && kfTcw && kfTwc && kfTcwBefMerge && kfTwcBefMerge && stats4 && chi2 && (nC == 0 || (cI && cJ && cKept)) &&
+               (nMP == 0 || (mpPos && mpRef)), MORB_ERR_INVALID, "NULL argument");
+  MORB_REQUIRE(nKF > 0 && nC >= 0 && nMP >= 0, MORB_ERR_INVALID, "bad sizes");
+  auto sound = [](const float* p) {   // finite, and a quaternion that SO3's constructor can normalise
+    for (int k = 0; k < 7; ++k) if (!std::isfinite(p[k])) return false;
+    return p[0] != 0 || p[1] != 0 || p[2] != 0 || p[3] != 0;
+  };
+  for (int v = 0; v < nKF; ++v) {
+    const int l = kfLists[v];
+    MORB_REQUIRE(l == MG_FIXED || l == MG_CORRECTED || l == MG_NONFIXED || l == (MG_CORRECTED | MG_NONFIXED), MORB_ERR_INVALID,
+                 "a vertex is in no list, or in vpFixedKFs and another one");
+    MORB_REQUIRE(sound(kfTcw + (size_t)v * 7) && sound(kfTwc + (size_t)v * 7), MORB_ERR_INVALID, "a non-finite pose or a zero quaternion");
+    if (l & MG_CORRECTED)
+      MORB_REQUIRE(sound(kfTcwBefMerge + (size_t)v * 7) && sound(kfTwcBefMerge + (size_t)v * 7), MORB_ERR_INVALID,
+                   "a non-finite pose before the merge or a zero quaternion");
+  }
+  for (int c = 0; c < nC; ++c) {
+    MORB_REQUIRE(cI[c] >= 0 && cI[c] < nKF && cJ[c] >= 0 && cJ[c] < nKF, MORB_ERR_INVALID, "edge index out of range");
+    MORB_REQUIRE(cI[c] != cJ[c], MORB_ERR_INVALID, "an edge joins a vertex to itself");
+  }
+  for (int m = 0; m < nMP; ++m) MORB_REQUIRE(mpRef[m] >= -1 && mpRef[m] < nKF, MORB_ERR_INVALID, "point reference out of range");
+  // the good / bad rule (:1907-1913): an edge exists where both ends are good or both are bad; fixed = every list but vpNonFixedKFs alone
+  std::vector<uint8_t> flags(nKF), kept(nC);
+  std::vector<int> eI, eJ;
+  for (int v = 0; v < nKF; ++v) flags[v] = kfLists[v] == MG_NONFIXED ? 0 : (kfLists[v] == MG_FIXED ? 3 : 1);
+  for (int c = 0; c < nC; ++c) {
+    const int li = kfLists[cI[c]], lj = kfLists[cJ[c]];
+    const bool good = (li & (MG_FIXED | MG_CORRECTED)) && (lj & (MG_FIXED | MG_CORRECTED));
+    const bool bad = (li & (MG_CORRECTED | MG_NONFIXED)) && (lj & (MG_CORRECTED | MG_NONFIXED));
+    kept[c] = good || bad;
+    if (kept[c]) { eI.push_back(cI[c]); eJ.push_back(cJ[c]); }
+  }
+  const int nE = (int)eI.size();
+  EnvelopePlan P;
+  const EnvelopeFit fit = plan_envelope(nKF, flags.data(), nE, eI.data(), eJ.data(), EG_MAX_BLOCKS, P);
+  MORB_REQUIRE(fit != EnvelopeFit::TooLarge, MORB_ERR_CAPACITY, "the envelope of the essential graph exceeds what the handle may grow to");
+  const bool solve = fit == EnvelopeFit::Ok;   // (else no free vertex has an edge: the tail of :2015-2062 still runs)
+
+  MORB_ENTER(st, o, nullptr);
+  EgDev D;
+  MgDev M;
+  memset(&D, 0, sizeof D); memset(&M, 0, sizeof M);
+  D.nKF = M.nKF = nKF; D.nE = M.nE = solve ? nE : 0; D.n = P.n; D.nBlocks = solve ? P.nBlocks : 0; D.nMP = M.nMP = nMP; D.maxIts = 20;
+  const size_t plane = (size_t)7 * nKF;
+  std::vector<float> in(4 * plane);   // the four poses of every vertex, plane by plane
+  float* const host[4] = {kfTcw, kfTwc, kfTcwBefMerge, kfTwcBefMerge};
+  for (int a = 0; a < 4; ++a) memcpy(in.data() + a * plane, host[a], sizeof(float) * plane);
+  ArenaCarver A;
+  char *arena = nullptr, *stage = nullptr;
+  {
+    const int rc = eg_bind(o, A, [&]() {
+      M.lists = (const uint8_t*)A.take(kfLists, nKF);
+      M.in = (const float*)A.take(in.data(), sizeof(float) * 4 * plane);
+      if (nMP) { M.mp = (const float*)A.take(mpPos, sizeof(float) * 3 * nMP); M.mpRef = (const int*)A.take(mpRef, sizeof(int) * nMP); }
+      if (solve) eg_carve_plan(A, D, P, flags.data(), eI.data(), eJ.data());
+      M.out = (float*)A.take(nullptr, sizeof(float) * (4 * plane + (size_t)3 * nMP));
+      D.S = M.S = (double*)A.take(nullptr, sizeof(double) * 8 * nKF);
+      if (solve) { M.eS = (double*)A.take(nullptr, sizeof(double) * 8 * nE); D.eS = M.eS; eg_carve_solver(A, D); }
+    }, &arena, &stage);
+    if (rc != MORB_OK) return rc;
+  }
+  M.eI = D.eI; M.eJ = D.eJ;
+  MORB_HIP_CHECK(hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st));   // the one upload
+  hipLaunchKernelGGL(k_egm_prepare, dim3(div_up(nKF + M.nE, EG_NT)), dim3(EG_NT), 0, st, M);
+  MORB_HIP_CHECK(hipGetLastError());
+  int hi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double hchi[2] = {0, 0};
+  if (solve) {
+    const int rc = eg_solve(o, st, D);
+    if (rc != MORB_OK) return rc;
+    MORB_HIP_CHECK(hipMemcpyAsync(hi, D.lmi, sizeof hi, hipMemcpyDeviceToHost, st));
+    MORB_HIP_CHECK(hipMemcpyAsync(hchi, D.chi2, sizeof hchi, hipMemcpyDeviceToHost, st));
+  }
+  hipLaunchKernelGGL(k_egm_finish, dim3(div_up(nKF + nMP, EG_NT)), dim3(EG_NT), 0, st, M);
+  MORB_HIP_CHECK(hipGetLastError());
+  std::vector<float> out(4 * plane + (size_t)3 * nMP);   // the one download: the four planes and the points behind them
+  MORB_HIP_CHECK(hipMemcpyAsync(out.data(), M.out, sizeof(float) * out.size(), hipMemcpyDeviceToHost, st));
+  MORB_HIP_CHECK(hipStreamSynchronize(st));   // (also drains a queue that ran out of slots before the words are reset again)
+  for (int a = 0; a < 4; ++a) memcpy(host[a], out.data() + a * plane, sizeof(float) * plane);
+  if (nMP) memcpy(mpPos, out.data() + 4 * plane, sizeof(float) * 3 * nMP);
+  if (nC) memcpy(cKept, kept.data(), nC);
+  stats4[0] = hi[EG_ITS]; stats4[1] = hi[EG_TRIALS]; stats4[2] = solve ? P.n : 0; stats4[3] = solve ? P.nBlocks : 0;
+  chi2[0] = hchi[0]; chi2[1] = hchi[1];
   return MORB_OK;
 }
 

@@ -392,6 +392,26 @@ class Optimizer:
                                                     ptr(mp) if len(mp) else None, ptr(ref) if len(mp) else None, ptr(stats), ptr(chi2)))
         return S, mp, stats, chi2
 
+    def OptimizeEssentialGraphMerge(self, kfLists, kfTcw, kfTwc, kfTcwBefMerge, kfTwcBefMerge, cI, cJ, mpPos=None, mpRef=None):
+        """The second overload of Optimizer::OptimizeEssentialGraph, the Sim3 pose graph of map merging, on host numpy arrays (see
+        morb_optimize_essential_graph_merge).  kfLists: uint8 [nKF], bit 0 vpFixedKFs, bit 1 vpFixedCorrectedKFs, bit 2 vpNonFixedKFs; the
+        four poses float32 [nKF, 7] (unit quaternion xyzw, translation); candidate edges (cI, cJ) in insertion order; mpPos float32
+        [nMP, 3] with mpRef = the vertex of each point's reference keyframe (-1: left alone), or None.  Returns a dict: kfTcw, kfTwc,
+        kfTcwBefMerge, kfTwcBefMerge, mpPos, cKept (1 where the good / bad rule keeps the candidate), stats4, chi2."""
+        lists = np.ascontiguousarray(kfLists, np.uint8)
+        poses = [np.ascontiguousarray(a, np.float32).reshape(-1, 7).copy() for a in (kfTcw, kfTwc, kfTcwBefMerge, kfTwcBefMerge)]
+        ci, cj = np.ascontiguousarray(cI, np.int32), np.ascontiguousarray(cJ, np.int32)
+        assert all(len(a) == len(lists) for a in poses) and len(ci) == len(cj)
+        mp = np.zeros((0, 3), np.float32) if mpPos is None else np.ascontiguousarray(mpPos, np.float32).reshape(-1, 3).copy()
+        ref = np.zeros(0, np.int32) if mpRef is None else np.ascontiguousarray(mpRef, np.int32)
+        assert len(ref) == len(mp)
+        kept, stats, chi2 = np.zeros(len(ci), np.uint8), np.zeros(4, np.int32), np.zeros(2, np.float64)
+        some = len(ci) > 0
+        check(self._L.morb_optimize_essential_graph_merge(self._h, len(lists), ptr(lists), *[ptr(a) for a in poses], len(ci), ptr(ci) if some else None,
+                                                          ptr(cj) if some else None, ptr(kept) if some else None, len(mp), ptr(mp) if len(mp) else None,
+                                                          ptr(ref) if len(mp) else None, ptr(stats), ptr(chi2)))
+        return dict(kfTcw=poses[0], kfTwc=poses[1], kfTcwBefMerge=poses[2], kfTwcBefMerge=poses[3], mpPos=mp, cKept=kept, stats4=stats, chi2=chi2)
+
     def OptimizeEssentialGraph4DoF(self, kfPose, kfBody, kfFixed, Tcb12, eI, eJ, eTij, mpPos=None, mpRef=None, kfScw=None):
         """Optimizer::OptimizeEssentialGraph4DoF, the pose graph of loop closing in an inertial map, on host numpy arrays (see
         morb_optimize_essential_graph_4dof).  kfPose: float64 [nKF, 12] (Rcw row-major, tcw); kfBody: [nKF, 12] (Rwb row-major, twb) at

@@ -1826,6 +1826,157 @@ def make_essential_graph_problem(n_kf=30, band=3, n_loop=1, fix_scale=False, see
                 mpPos=mpPos, mpRef=mpRef, cur=cur, loop=loop_kf, connected=connected, S_true=S_true)
 
 
+# ---- the pose graph of map merging (Optimizer::OptimizeEssentialGraph, overload 2) ---------------------------------------------------------
+def _pose7(S):
+    """A Sim3 (qx qy qz qw tx ty tz s) as the float pose SE3(q, t / s)."""
+    q = S[:4] / np.linalg.norm(S[:4])
+    return np.concatenate([q, S[4:7] / S[7]]).astype(np.float32)
+
+
+def _pose7_inv(p):
+    p = p.astype(np.float64)
+    qc = np.array([-p[0], -p[1], -p[2], p[3]])
+    return np.concatenate([qc, -_quat_rot(qc, p[4:7])]).astype(np.float32)
+
+
+def make_merge_graph_problem(n_fixed=6, n_window=5, n_nonfixed=20, overlap=True, band=3, n_old_loops=1, seed=0, n_points=0, fixed_links=True,
+                             window_links=True, weld=True, reroot=True, corr_rot_deg=8.0, corr_trans=6.0, corr_scale=1.05, bad=(), isolated=(),
+                             long_loop=False, drift_rot_deg=0.3, drift_scale=0.004, origin=(0.0, 0.0, 0.0)):
+    """Two maps joined at a window, as LoopClosing::MergeLocal hands them to the second overload of Optimizer::OptimizeEssentialGraph
+    (LoopClosing.cc:1747-1749), flattened for morb_optimize_essential_graph_merge.  Keyframes in ascending mnId: n_fixed keyframes of the
+    merged map (vpFixedKFs, list bit 1), then the old map's n_nonfixed keyframes along a drifting chain (vpNonFixedKFs, bit 4).  The window
+    (vpFixedCorrectedKFs, bit 2) is the last n_window keyframes of the chain with overlap (bits 2 | 4: vpLocalCurrentWindowKFs is a subset of
+    vpCurrentMapKFs), or n_window further keyframes behind the chain without.  A window keyframe's mTcwBefMerge is its pose in the old map
+    and its pose is that times the inverse of the merge's Sim3 correction (corr_*), as SE3 with t / s; every other keyframe's BefMerge
+    members are Sophus' defaults.  `origin` moves the merged map's keyframes away from the world origin: an edge between two of them measures
+    the parent's pose itself (the reference's identity Swi), so its error, a constant of chi2, grows with that distance.  Topology: a fixed keyframe's parent is the one before it and its covisibles (weight >= 100) are those
+    at most `band` before (fixed_links); the same along the chain and the window (window_links: edges between two window keyframes), plus
+    n_old_loops old loop edges inside the chain and, with long_loop, one from the last chain keyframe to the first; with reroot the window's
+    spanning tree hangs from the merged map as MergeLocal leaves it — the newest window keyframe's parent is the last fixed keyframe, every
+    other window keyframe's parent is the next one — and with weld each window keyframe is covisible with two fixed keyframes.  `bad`
+    keyframes (indices before removal) are bad: no vertex, no edge, so a child of one has no spanning-tree edge; `isolated` non-fixed
+    keyframes have a fixed keyframe as their only candidate, which the good / bad rule drops.  Candidates in the insertion order of
+    Optimizer.cc:1888-1999: vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs, so an overlapped keyframe is visited twice; per keyframe the
+    parent, the loop edges with a smaller id, the covisibles with a smaller id that are neither parent, child nor loop edge.  Points: n_points
+    with references over every list, every eighth -1.  Returns a dict: kfLists, kfTcw, kfTwc, kfTcwBefMerge, kfTwcBefMerge, cI, cJ, mpPos,
+    mpRef, plus window (vertices) and ids (vertex -> index before removal)."""
+    rng = np.random.default_rng(seed)
+    n_chain = n_nonfixed if overlap else n_nonfixed + n_window
+    n_all = n_fixed + n_chain
+    chain0 = n_fixed
+    window = list(range(n_all - n_window, n_all))
+    lists = np.zeros(n_all, np.uint8)
+    lists[:n_fixed] = 1
+    lists[chain0:chain0 + n_nonfixed] = 4
+    for w in window:
+        lists[w] |= 2
+    # the old map: a camera on a circle looking along its tangent, with drift along the chain
+    S_true = np.zeros((n_chain, 8))
+    for i in range(n_chain):
+        a = 2 * np.pi * i / max(n_chain, 8)
+        q = _quat_from_rotvec(np.array([0.05 * np.sin(3 * a), -a, 0.03 * np.cos(2 * a)]))
+        c = np.array([6 * np.cos(a), 0.2 * np.sin(5 * a), 6 * np.sin(a)])
+        S_true[i] = np.concatenate([q, -_quat_rot(q, c), [1.0]])
+    S_old = np.zeros_like(S_true)
+    S_old[0] = S_true[0]
+    for i in range(1, n_chain):
+        rel = _sim3_mul(S_true[i], _sim3_inv(S_true[i - 1]))
+        dq = _quat_from_rotvec(np.deg2rad(drift_rot_deg) * (np.array([0.2, 1.0, 0.1]) + 0.3 * rng.normal(size=3)))
+        rel = np.concatenate([_quat_mul(dq, rel[:4]), (1.0 - drift_scale * (1 + 0.3 * rng.normal())) * _quat_rot(dq, rel[4:7]), [1.0]])
+        S_old[i] = _sim3_mul(rel, S_old[i - 1])
+        S_old[i, :4] /= np.linalg.norm(S_old[i, :4])
+    # the merge's correction: Scw_corrected = Scw_old * G^-1
+    gq = _quat_from_rotvec(np.deg2rad(corr_rot_deg) * np.array([0.3, 0.9, -0.2]) / np.linalg.norm([0.3, 0.9, -0.2]))
+    G = np.concatenate([gq, corr_trans * np.array([0.5, -0.2, 0.8]), [corr_scale]])
+    Ginv = _sim3_inv(G)
+    ident = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
+    Tcw, Twc = np.zeros((n_all, 7), np.float32), np.zeros((n_all, 7), np.float32)
+    TcwBef, TwcBef = np.tile(ident, (n_all, 1)), np.tile(ident, (n_all, 1))
+    for v in range(n_all):
+        if v < n_fixed:   # the merged map: keyframes near where the correction puts the window
+            a = 2 * np.pi * (n_chain - 1 - 0.7 * (n_fixed - v)) / max(n_chain, 8)
+            q = _quat_from_rotvec(np.array([0.02, -a, 0.01]))
+            c = np.array([6.3 * np.cos(a), 0.1, 6.3 * np.sin(a)]) + np.asarray(origin, np.float64)
+            Tcw[v] = _pose7(_sim3_mul(np.concatenate([q, -_quat_rot(q, c), [1.0]]), Ginv))
+        elif lists[v] & 2:
+            TcwBef[v] = _pose7(S_old[v - chain0])
+            TwcBef[v] = _pose7_inv(TcwBef[v])
+            Tcw[v] = _pose7(_sim3_mul(S_old[v - chain0], Ginv))
+        else:
+            Tcw[v] = _pose7(S_old[v - chain0])
+        Twc[v] = _pose7_inv(Tcw[v])
+    # topology on the indices before removal
+    dead, lone = set(int(b) for b in bad), set(int(i) for i in isolated)
+    parent, covis, loops = {}, {v: [] for v in range(n_all)}, {v: set() for v in range(n_all)}
+    for v in range(n_all):
+        if v in lone:
+            parent[v] = None
+            covis[v] = [0]
+            continue
+        first = v == 0 or v == chain0
+        in_window = v in window
+        if not first and (fixed_links if v < n_fixed else True):
+            p = v - 1
+            while p in lone:
+                p -= 1
+            parent[v] = p if (p >= 0 and (p < n_fixed) == (v < n_fixed)) else None
+        else:
+            parent[v] = None
+        if in_window and reroot and n_fixed:
+            parent[v] = n_fixed - 1 if v == n_all - 1 else v + 1
+        lo = 0 if v < n_fixed else chain0
+        for j in range(v - 1, max(lo - 1, v - band - 1), -1):
+            if j in lone or (v < n_fixed and not fixed_links):
+                continue
+            if in_window and j in window and not window_links:
+                continue
+            covis[v].append(j)
+        if in_window and weld and n_fixed:
+            covis[v] += [j for j in (n_fixed - 1, n_fixed - 2) if j >= 0]
+    if not window_links:
+        for w in window:
+            if parent[w] in window:
+                parent[w] = None
+    olds = []
+    for _ in range(n_old_loops):
+        i = int(rng.integers(chain0 + n_nonfixed // 2, chain0 + n_nonfixed)); j = int(rng.integers(chain0, chain0 + max(1, n_nonfixed // 4)))
+        if i not in lone and j not in lone and i != j and not (lists[i] & 2 and lists[j] & 2):
+            olds.append((i, j))
+    if long_loop:
+        olds.append((chain0 + n_nonfixed - 1 - (n_window if overlap else 0), chain0))
+    for i, j in olds:
+        loops[i].add(j); loops[j].add(i)
+    children = {v: set(c for c in range(n_all) if parent.get(c) == v) for v in range(n_all)}
+    alive = [v for v in range(n_all) if v not in dead]
+    row = {v: k for k, v in enumerate(alive)}
+    cI, cJ = [], []
+    order = [v for v in range(n_fixed)] + window + [v for v in range(chain0, chain0 + n_nonfixed)]
+    for v in order:
+        if v in dead:
+            continue   # (a bad keyframe is neither good nor bad: every candidate of its own is dropped, :1907-1913)
+        p = parent[v]
+        if p is not None and p not in dead:
+            cI.append(row[v]); cJ.append(row[p])
+        for j in sorted(loops[v]):
+            if j < v and j not in dead:
+                cI.append(row[v]); cJ.append(row[j])
+        for j in covis[v]:
+            if j != p and j not in children[v] and j not in loops[v] and j not in dead and j < v:
+                cI.append(row[v]); cJ.append(row[j])
+    keep = np.array(alive, np.int64)
+    lists, Tcw, Twc, TcwBef, TwcBef = lists[keep], Tcw[keep], Twc[keep], TcwBef[keep], TwcBef[keep]
+    nKF = len(keep)
+    mpPos = np.zeros((n_points, 3), np.float32); mpRef = np.full(n_points, -1, np.int32)
+    for m in range(n_points):
+        r = m % nKF if m < 2 * nKF else int(rng.integers(0, nKF))   # (every vertex, so every list, is somebody's reference)
+        T = (TwcBef[r] if lists[r] & 2 else Twc[r]).astype(np.float64)
+        Xc = np.array([rng.uniform(-2, 2), rng.uniform(-1, 1), rng.uniform(2, 8)])
+        mpPos[m] = (_quat_rot(T[:4], Xc) + T[4:7]).astype(np.float32)
+        mpRef[m] = -1 if m % 8 == 7 else r
+    return dict(kfLists=lists, kfTcw=Tcw, kfTwc=Twc, kfTcwBefMerge=TcwBef, kfTwcBefMerge=TwcBef, cI=np.array(cI, np.int32), cJ=np.array(cJ, np.int32),
+                mpPos=mpPos, mpRef=mpRef, window=[row[w] for w in window if w in row], ids=keep)
+
+
 # ---- the 4-DoF pose graph of loop closing in an inertial map (Optimizer::OptimizeEssentialGraph4DoF) ---------------------------------------
 def _rs_mul(a, b):
     """g2o::Sim3::operator* on (R, t, s)."""
