@@ -397,6 +397,59 @@ int morb_track_discard_outliers_batch(morb_matcher*, int nframes, const int* d_f
                                       uint8_t* d_outlier, int mpCap, const uint8_t* d_mpHasObs, uint8_t* d_blocked,
                                       uint8_t* d_mpSeen, int* d_nmatches, int* d_nmatchesMap, void* stream);
 
+/* void Tracking::UpdateLocalMap() (src/Tracking.cc:3184-3191) = UpdateLocalKeyFrames (:3220-3358) + UpdateLocalPoints (:3193-3218),
+ * the step TrackLocalMap runs between the first PoseOptimization and SearchLocalPoints, for nq query frames at once on map tables
+ * that stay on the device.  A batch of n equals n independent calls.  Every index is an int32 row, -1 = NULL; a row outside its
+ * table is read as NULL, a count beyond its capacity as the capacity.  Integers only: two calls give identical bytes.
+ * Map tables, shared by the queries.  Keyframes, nkf rows:
+ *   d_kfMp [nkf][kfCap] mvpMapPoints as map-point rows, d_kfCount [nkf] = N; d_kfFlags [nkf]: bit 0 = isBad();
+ *   d_kfOrder [nkf]   the keyframe's position in the iteration order of std::map<KeyFrame*, int> (:3222, :3271): a permutation of
+ *                     0 .. nkf-1, taken as given; NULL = row order.  The reference orders by pointer value; here that order is data.
+ *   d_covis [nkf][ncovis]  GetBestCovisibilityKeyFrames(10) in its order, padded with -1 (as morb_detect_n_best_candidates_batch's);
+ *   d_childStart [nkf + 1] / d_child   CSR of GetChilds() in the set's iteration order (d_childStart NULL = no children);
+ *   d_parent [nkf] GetParent(), d_prevKf [nkf] mPrevKF (either may be NULL = none).
+ * Map points, nmp rows: d_mpObsStart [nmp + 1] / d_mpObsKf = CSR of the keys of GetObservations(), one entry per observing keyframe
+ * (uniqueness is taken as given); d_mpFlags [nmp]: bit 0 = isBad().
+ * Per query: d_frameMp [nq][cap] IN/OUT = mvpMapPoints of the voting frame as map-point rows (the caller passes the current or the
+ * last frame's, the choice of :3223-3224); an entry whose point is bad is written to -1 (:3237 / :3257).  d_count [nq] = N;
+ * d_lastKf [nq] = mCurrentFrame.mpLastKeyFrame (NULL = none); inertial != 0 <=> mSensor is one of the three IMU_* types (:3338).
+ * What is reproduced, quirks included: every non-bad frame point votes for every keyframe of its observations, whatever the
+ * keyframe's state; the voted, non-bad keyframes are listed in d_kfOrder order and pKFmax is the first of them with the strictly
+ * greatest count (:3271-3285); the second loop (:3289-3335) runs over those entries only, stops when the list, additions included,
+ * is larger than 80 at the top of an iteration, adds per entry the first non-bad unstamped covisible, the first non-bad unstamped
+ * child and the unstamped parent, the parent without an isBad() test, and LEAVES THE LOOP after adding a parent (:3332); the
+ * inertial tail (:3338-3352) runs below 80 entries, from d_lastKf along d_prevKf for at most 20 additions, ends at a stamped
+ * keyframe and has no size test inside; the points (:3193-3218) are those of the listed keyframes in REVERSE list order, features
+ * ascending, NULL, bad and already taken ones skipped.  The stamps a query starts from are clear.
+ * Outputs: d_localKf [nq][kfOut], d_nLocalKf [nq] = mvpLocalKeyFrames; d_refKf [nq] = pKFmax, -1 = mpReferenceKF stays;
+ * d_localMp [nq][mpCap], d_nLocalMp [nq] = mvpLocalMapPoints; d_frameLocal [nq][cap] (may be NULL) = the position of each feature's
+ * point in d_localMp, -1 where it has none, where the point is not in the list (or at or beyond mpCap), and at or beyond d_count:
+ * the per-frame table index the tracking entries above call "mvpMapPoints"; d_votes [nq][nkf] (may be NULL) = keyframeCounter, 0
+ * where absent; d_overflow [nq]: bit 0 = the keyframe list is longer than kfOut, bit 1 = the point list is longer than mpCap; the
+ * counts then hold the true lengths, the first kfOut / mpCap entries are correct and nothing is written beyond them.  Entries
+ * beyond a count are not written.  Workspace on the handle: nq * (nkf + nmp) ints.
+ * MORB_ERR_INVALID for a negative size or cap, kfCap, kfOut or mpCap < 1; MORB_ERR_CAPACITY for more than 65535 queries, or
+ * nkf * kfCap or nq * (nkf + nmp) beyond 2^31 - 1.  nq == 0 is MORB_OK with nothing written; nkf == 0 or nmp == 0 is MORB_OK with
+ * empty lists written. */
+int morb_update_local_map_batch(morb_matcher*, int nq, int nkf, int kfCap, const int* d_kfMp, const int* d_kfCount,
+                                const uint8_t* d_kfFlags, const int* d_kfOrder, const int* d_covis, int ncovis, const int* d_childStart,
+                                const int* d_child, const int* d_parent, const int* d_prevKf, int nmp, const int* d_mpObsStart,
+                                const int* d_mpObsKf, const uint8_t* d_mpFlags, int cap, int* d_frameMp, const int* d_count,
+                                const int* d_lastKf, int inertial, int kfOut, int* d_localKf, int* d_nLocalKf, int* d_refKf, int mpCap,
+                                int* d_localMp, int* d_nLocalMp, int* d_frameLocal, int* d_votes, int* d_overflow, void* stream);
+
+/* The per-frame map-point tables Tracking::SearchLocalPoints (src/Tracking.cc:3117-3183) hands to isInFrustum and
+ * SearchByProjection(F, mvpLocalMapPoints), filled from map-wide arrays through morb_update_local_map_batch's d_localMp [nq][mpCap]
+ * / d_nLocalMp [nq].  Inputs [nmp]: world position (3 floats), normal (3), mfMaxDistance, mfMinDistance, the representative descriptor
+ * (32 bytes), isBad(), Observations() > 0.  Outputs [nq][mpCap] in the layout morb_is_in_frustum_batch and
+ * morb_search_by_projection_mps_batch take (d_nMP = d_nLocalMp; a count beyond mpCap is read as mpCap).  Rows at or beyond a query's
+ * count are not written.  MORB_ERR_INVALID for a negative size or mpCap < 1; nq == 0 or nmp == 0 is MORB_OK with nothing written. */
+int morb_gather_local_map_points_batch(morb_matcher*, int nq, int nmp, const float* d_mpPw, const float* d_mpNormal,
+                                       const float* d_mpMaxDist, const float* d_mpMinDist, const uint8_t* d_mpDescriptor,
+                                       const uint8_t* d_mpIsBad, const uint8_t* d_mpObserved, int mpCap, const int* d_localMp,
+                                       const int* d_nLocalMp, float* d_Pw, float* d_normal, float* d_maxDist, float* d_minDist,
+                                       uint8_t* d_mpDesc, uint8_t* d_isBad, uint8_t* d_mpHasObs, void* stream);
+
 /* int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)
  * ORBmatcher.h:55-56, ORBmatcher.cc:1521-1733.  Frame pair f = (image d_curImg[f], image d_lastImg[f]); d_Tcw
  * [f][7] = CurrentFrame pose (quaternion xyzw + translation); per last-frame feature [nframes][cap]:

@@ -30,6 +30,7 @@ struct morb_matcher {
   morb::DeviceGrow queryCount;   // queries per frame / pair
   morb::DeviceGrow kfdbPair;     // k_kfdb_intersect's per-(query, keyframe) first-word ranks, scores and common-word counts (keyframe_database.hip)
   morb::DeviceGrow kfdbList;     // k_kfdb_select's sort lists of queries on a pool of more keyframes than fit the LDS
+  morb::DeviceGrow localMap;     // UpdateLocalMap's per-query keyframe words (votes, then stamps) and map point sequence keys: nq * (nkf + nmp) ints (local_map.hip)
   morb::DeviceGrow scratch;      // per call: the unused projXR plane of isInFrustum (KB8), SearchForInitialization's gathered query descriptors, SearchByBoW's matched2
   // small constant tables (PredictScale thresholds, camera parameters): device copy + the host bytes it was made from, so that a
   // call with the same table neither uploads nor waits (matcher.hip: morb_matcher_const)

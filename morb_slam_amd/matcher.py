@@ -157,6 +157,69 @@ class ORBmatcher:
                                                                   ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), self._st(stream)))
         return out
 
+    # ---- the local map (local_map.hip) ---------------------------------------------------------------------
+    @staticmethod
+    def local_map_tables(scene, device):
+        """The map tables of update_local_map / gather_local_map_points as device tensors, from a dict of host arrays with synth.
+        make_local_map_scene's keys (kfOrder, childStart / child, parent, prevKf may be None)."""
+        import torch
+        up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dt)).to(device)
+        t = {k: up(scene.get(k), np.int32) for k in ("kfMp", "kfCount", "kfOrder", "covis", "childStart", "child", "parent", "prevKf",
+                                                     "mpObsStart", "mpObsKf")}
+        t.update({k: up(scene.get(k), np.uint8) for k in ("kfFlags", "mpFlags", "mpDesc", "mpIsBad", "mpObserved")})
+        t.update({k: up(scene.get(k), np.float32) for k in ("mpPw", "mpNormal", "mpMaxD", "mpMinD")})
+        return t
+
+    def update_local_map(self, tables, frame_mp, count, last_kf=None, inertial=False, kf_out=128, mp_cap=4096, want_frame_local=True,
+                         want_votes=False, out=None, stream=None):
+        """Tracking::UpdateLocalMap (morb_update_local_map_batch) for nq frames.  tables: dict of device tensors (local_map_tables):
+        kfMp i32 [nkf, kfCap], kfCount i32 [nkf], kfFlags u8 [nkf], kfOrder i32 [nkf] or None, covis i32 [nkf, ncovis], childStart i32
+        [nkf + 1] / child, parent, prevKf i32 [nkf], mpObsStart i32 [nmp + 1] / mpObsKf, mpFlags u8 [nmp].  frame_mp i32 [nq, cap] IN/OUT
+        (bad points become -1), count i32 [nq], last_kf i32 [nq] or None.  Returns a dict: localKf i32 [nq, kf_out], nLocalKf, refKf,
+        localMp i32 [nq, mp_cap], nLocalMp, frameLocal i32 [nq, cap] or None, votes i32 [nq, nkf] or None, overflow i32 [nq]; entries
+        beyond a count keep what they held (-1 in tensors allocated here).  out = such a dict to write into."""
+        import torch
+        T = tables
+        nq, cap = frame_mp.shape
+        nkf, kfCap = T["kfMp"].shape
+        nmp = int(T["mpFlags"].shape[0])
+        ncovis = int(T["covis"].shape[1]) if T.get("covis") is not None else 0
+        assert frame_mp.dtype == torch.int32 and frame_mp.is_contiguous() and T["kfFlags"].dtype == torch.uint8 and T["mpFlags"].dtype == torch.uint8
+        if out is None:
+            dev, i32 = frame_mp.device, torch.int32
+            full = lambda shape: torch.full(shape, -1, dtype=i32, device=dev)
+            out = dict(localKf=full((nq, kf_out)), nLocalKf=full((nq,)), refKf=full((nq,)), localMp=full((nq, mp_cap)), nLocalMp=full((nq,)),
+                       frameLocal=full((nq, cap)) if want_frame_local else None, votes=full((nq, nkf)) if want_votes else None,
+                       overflow=full((nq,)))
+        kf_out, mp_cap = out["localKf"].shape[1], out["localMp"].shape[1]
+        check(self._L.morb_update_local_map_batch(
+            self._h, nq, nkf, kfCap, ptr(T["kfMp"]), ptr(T["kfCount"]), ptr(T["kfFlags"]), ptr(T.get("kfOrder")), ptr(T.get("covis")), ncovis,
+            ptr(T.get("childStart")), ptr(T.get("child")), ptr(T.get("parent")), ptr(T.get("prevKf")), nmp, ptr(T["mpObsStart"]),
+            ptr(T["mpObsKf"]), ptr(T["mpFlags"]), cap, ptr(frame_mp), ptr(count), ptr(last_kf), 1 if inertial else 0, kf_out,
+            ptr(out["localKf"]), ptr(out["nLocalKf"]), ptr(out["refKf"]), mp_cap, ptr(out["localMp"]), ptr(out["nLocalMp"]),
+            ptr(out.get("frameLocal")), ptr(out.get("votes")), ptr(out["overflow"]), self._st(stream)))
+        return out
+
+    def gather_local_map_points(self, tables, local_mp, n_local_mp, out=None, stream=None):
+        """morb_gather_local_map_points_batch: the per-frame tables isInFrustum and SearchByProjectionMapPoints read ([nq, mpCap] rows of
+        Pw, normal, maxDist, minDist, mpDesc, isBad, mpHasObs) from the map-wide arrays mpPw, mpNormal f32 [nmp, 3], mpMaxD, mpMinD f32
+        [nmp], mpDesc u8 [nmp, 32], mpIsBad, mpObserved u8 [nmp] of `tables`, through update_local_map's localMp / nLocalMp.  Rows at or
+        beyond a frame's count keep what they held (zeros in tensors allocated here).  Returns the dict; out = one to write into."""
+        import torch
+        T = tables
+        nq, mpCap = local_mp.shape
+        nmp = int(T["mpIsBad"].shape[0])
+        if out is None:
+            dev, f32, u8 = local_mp.device, torch.float32, torch.uint8
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            out = dict(Pw=z((nq, mpCap, 3), f32), normal=z((nq, mpCap, 3), f32), maxDist=z((nq, mpCap), f32), minDist=z((nq, mpCap), f32),
+                       mpDesc=z((nq, mpCap, 32), u8), isBad=z((nq, mpCap), u8), mpHasObs=z((nq, mpCap), u8))
+        check(self._L.morb_gather_local_map_points_batch(
+            self._h, nq, nmp, ptr(T["mpPw"]), ptr(T["mpNormal"]), ptr(T["mpMaxD"]), ptr(T["mpMinD"]), ptr(T["mpDesc"]), ptr(T["mpIsBad"]),
+            ptr(T["mpObserved"]), mpCap, ptr(local_mp), ptr(n_local_mp), ptr(out["Pw"]), ptr(out["normal"]), ptr(out["maxDist"]),
+            ptr(out["minDist"]), ptr(out["mpDesc"]), ptr(out["isBad"]), ptr(out["mpHasObs"]), self._st(stream)))
+        return out
+
     def bow_transform_tree(self, desc, count, voc_desc, voc_first, voc_nchild, L, levelsup=4, stream=None):
         """DBoW2 transform on a trained (possibly incomplete) tree: children of n = [first[n], first[n] + nchild[n])."""
         import torch

@@ -2373,3 +2373,126 @@ def make_full_inertial_ba_problem(n_kf=40, reach=6, n_points=600, n_loop_points=
                 bias=np.concatenate([ba, bg]).astype(np.float32), Tbc12=np.concatenate([Tbc[:3, :3].ravel(), Tbc[:3, 3]]).astype(np.float32),
                 cam=cam, rig28=tumvi_rig28() if kb8 else None, init=bool(init), bias6=bias6.astype(np.float32), priorG=float(prior_g),
                 priorA=float(prior_a), true=true, truePts=X)
+
+
+# ---- the map graph of Tracking::UpdateLocalMap (morb_update_local_map_batch) ------------------------------------------------------
+def local_map_scene_from_rows(rows, nmp, kf_cap, frames, cap=None, order=None, bad_kf=(), bad_mp=(), covis=None, ncovis=10, parent=None,
+                              prev=None, last_kf=None, extra_obs=(), seed=0):
+    """The device tables of morb_update_local_map_batch from explicit keyframe rows.  rows: one sequence of map-point rows per keyframe
+    (-1 = NULL, repeats allowed); the observations are derived from them (a point is observed by exactly the keyframes that hold it),
+    plus extra_obs = (point, keyframe) pairs that deliberately break that.  frames: one sequence of map-point rows per query.  order:
+    d_kfOrder or None (row order).  covis: per-keyframe neighbour lists, None = by shared points (descending, ties by row).  parent:
+    array or None = the earlier keyframe sharing most points (keyframe 0 is the root).  prev: mPrevKF, None = row - 1.  last_kf: per
+    query, None = -1.  Children are listed in `order` order, as a std::set<KeyFrame*> iterates.  Returns a dict of host arrays:
+    kfMp i32 [nkf, kf_cap], kfCount, kfFlags u8, kfOrder (or None), covis i32 [nkf, ncovis], childStart / child, parent, prevKf,
+    mpObsStart / mpObsKf, mpFlags u8, frameMp i32 [nq, cap], count, lastKf, the per-point arrays the gather reads (mpPw, mpNormal f32
+    [nmp, 3], mpMaxD, mpMinD f32, mpDesc u8 [nmp, 32], mpIsBad, mpObserved u8) and the sizes nkf, nmp, kf_cap, cap, ncovis."""
+    rng = np.random.default_rng(0x10ca1 + seed)
+    nkf, nq = len(rows), len(frames)
+    kfMp, kfCount = np.full((nkf, kf_cap), -1, np.int32), np.zeros(nkf, np.int32)
+    for k, r in enumerate(rows):
+        r = np.asarray(r, np.int32)
+        assert len(r) <= kf_cap
+        kfMp[k, :len(r)], kfCount[k] = r, len(r)
+    held = (kfMp >= 0) & (np.arange(kf_cap)[None, :] < kfCount[:, None])
+    codes = kfMp[held].astype(np.int64) * max(nkf, 1) + np.nonzero(held)[0]
+    codes = np.unique(np.concatenate([codes, np.array([int(m) * max(nkf, 1) + int(k) for m, k in extra_obs], np.int64)]))   # (point, keyframe), sorted
+    pm = np.stack([codes // max(nkf, 1), codes % max(nkf, 1)], 1)
+    mpObsStart = np.zeros(nmp + 1, np.int32)
+    np.add.at(mpObsStart, pm[:, 0] + 1, 1)
+    mpObsStart = np.cumsum(mpObsStart).astype(np.int32)
+    mpObsKf = pm[:, 1].astype(np.int32)
+    kfFlags, mpFlags = np.zeros(nkf, np.uint8), np.zeros(nmp, np.uint8)
+    kfFlags[list(bad_kf)] = 1
+    mpFlags[list(bad_mp)] = 1
+    order = None if order is None else np.asarray(order, np.int32)
+    pos = np.arange(nkf) if order is None else order
+    shared = None
+    if covis is None or parent is None:
+        step = max(nmp // 4096, 1)               # a sample of the points is enough to rank neighbours
+        M = np.zeros((nkf, nmp // step + 1), np.float32)
+        for k in range(nkf):
+            r = kfMp[k, :kfCount[k]]
+            r = r[(r >= 0) & (r % step == 0)]
+            M[k, r // step] = 1
+        shared = M @ M.T
+        np.fill_diagonal(shared, 0)
+    cv = np.full((nkf, max(ncovis, 1)), -1, np.int32)[:, :ncovis]
+    for k in range(nkf):
+        if covis is not None:
+            nb = list(covis[k]) if k < len(covis) else []
+        else:
+            cand = np.flatnonzero(shared[k] > 0)
+            nb = cand[np.lexsort((cand, -shared[k, cand]))][:ncovis]
+        cv[k, :len(nb)] = nb[:ncovis]
+    if parent is None:
+        parent = np.full(nkf, -1, np.int32)
+        for k in range(1, nkf):
+            parent[k] = int(np.argmax(shared[k, :k])) if shared[k, :k].max() > 0 else k - 1
+    parent = np.asarray(parent, np.int32)
+    kids = [[] for _ in range(nkf)]
+    for k in sorted(range(nkf), key=lambda k: pos[k]):
+        if parent[k] >= 0:
+            kids[parent[k]].append(k)
+    childStart = np.concatenate([[0], np.cumsum([len(c) for c in kids])]).astype(np.int32)
+    child = np.array([c for cs in kids for c in cs], np.int32)
+    prevKf = np.arange(-1, nkf - 1, dtype=np.int32) if prev is None else np.asarray(prev, np.int32)
+    cap = cap or max([len(f) for f in frames] + [1])
+    frameMp, count = np.full((nq, cap), -1, np.int32), np.zeros(nq, np.int32)
+    for q, f in enumerate(frames):
+        frameMp[q, :len(f)], count[q] = np.asarray(f, np.int32), len(f)
+    lastKf = np.full(nq, -1, np.int32) if last_kf is None else np.asarray(last_kf, np.int32)
+    Pw = rng.normal(0, 3, (nmp, 3)).astype(np.float32)
+    nrm = rng.normal(0, 1, (nmp, 3))
+    maxD = rng.uniform(2, 20, nmp).astype(np.float32)
+    return dict(kfMp=kfMp, kfCount=kfCount, kfFlags=kfFlags, kfOrder=order, covis=np.ascontiguousarray(cv), childStart=childStart, child=child,
+                parent=parent, prevKf=prevKf, mpObsStart=mpObsStart, mpObsKf=mpObsKf, mpFlags=mpFlags, frameMp=frameMp, count=count,
+                lastKf=lastKf, mpPw=Pw, mpNormal=(nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32), mpMaxD=maxD,
+                mpMinD=(maxD / np.float32(3.58)).astype(np.float32), mpDesc=rng.integers(0, 256, (nmp, 32), dtype=np.uint8),
+                mpIsBad=(mpFlags & 1).astype(np.uint8), mpObserved=(np.diff(mpObsStart) > 0).astype(np.uint8),
+                nkf=nkf, nmp=nmp, kf_cap=kf_cap, cap=cap, ncovis=ncovis)
+
+
+def make_local_map_scene(seed=0, nkf=60, nmp=2000, kf_cap=128, nq=4, cap=None, track=6, ncovis=10, shuffle_order=True, bad_kf_frac=0.05,
+                         bad_mp_frac=0.03, null_frac=0.1, dup_frac=0.02, stray_frac=0.05):
+    """A consistent synthetic map for Tracking::UpdateLocalMap: nkf keyframes along a trajectory, nmp points, point j seen by (most
+    of) the keyframes of an interval of about `track` keyframes around its place, so that a frame at keyframe c is voted for by about
+    2 track keyframes.  A keyframe's row holds its points in a shuffled feature order with null_frac NULL entries and dup_frac of
+    them repeated once more (at most kf_cap entries: surplus observations are dropped on both sides).  The covisibility rows rank
+    the keyframes by shared points, the spanning tree hangs every keyframe under the earlier one it shares most with, mPrevKF is the
+    keyframe before, d_kfOrder a random permutation (shuffle_order), bad_kf_frac / bad_mp_frac of the rows are bad.  The nq query
+    frames stand at keyframes spread over the trajectory: each holds most points of its keyframe and of the next one, stray_frac
+    points from anywhere in the map (usually outside the local map) and NULLs; lastKf is its keyframe.  Returns
+    local_map_scene_from_rows's dict."""
+    rng = np.random.default_rng(0x5ce9e + seed)
+    start = rng.integers(-track, nkf, nmp)
+    length = rng.integers(2, 2 * track + 1, nmp)
+    mp = np.repeat(np.arange(nmp), length)
+    kf = np.concatenate([np.arange(s, s + n) for s, n in zip(start, length)]) if nmp else np.zeros(0, np.int64)
+    keep = (kf >= 0) & (kf < nkf) & (rng.random(len(kf)) < 0.9)
+    mp, kf = mp[keep], kf[keep]
+    by_kf = np.argsort(kf, kind="stable")
+    bounds = np.searchsorted(kf[by_kf], np.arange(nkf + 1))
+    rows = []
+    for k in range(nkf):
+        r = rng.permutation(mp[by_kf[bounds[k]:bounds[k + 1]]])
+        room = int(kf_cap / (1 + null_frac + dup_frac)) - 1
+        r = r[:max(room, 0)]
+        extra = [np.full(int(round(len(r) * null_frac)), -1, np.int64), r[:int(np.ceil(len(r) * dup_frac))]]
+        r = np.concatenate([r] + extra)
+        tail = rng.permutation(len(r))            # NULLs and repeats anywhere in the row
+        rows.append(r[tail][:kf_cap])
+    bad_kf = rng.choice(nkf, int(round(nkf * bad_kf_frac)), replace=False) if nkf else []
+    bad_mp = rng.choice(nmp, int(round(nmp * bad_mp_frac)), replace=False) if nmp else []
+    cap = cap or kf_cap
+    frames, last = [], []
+    for q in range(nq):
+        c = int((q + 0.5) * nkf / max(nq, 1)) if nkf else -1
+        pts = np.unique(np.concatenate([r[r >= 0] for r in rows[c:c + 2]])) if nkf else np.zeros(0, np.int64)
+        pts = rng.permutation(pts)[:int(cap * 0.8)]
+        f = np.concatenate([pts, rng.integers(0, max(nmp, 1), int(cap * stray_frac)) if nmp else [], np.full(int(cap * 0.1), -1)]).astype(np.int64)
+        frames.append(rng.permutation(f)[:cap])
+        last.append(c)
+    order = rng.permutation(nkf) if shuffle_order else None
+    return local_map_scene_from_rows(rows, nmp, kf_cap, frames, cap=cap, order=order, bad_kf=bad_kf, bad_mp=bad_mp, ncovis=ncovis,
+                                     last_kf=last, seed=seed)

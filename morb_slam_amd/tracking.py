@@ -453,3 +453,96 @@ def build_chains(images, B, npairs=20, nfeatures=1200, device=0, seq_len=64, shi
     host["scene"], host["kscene"] = scene, kscene
     chain._keep = (ext, m)      # the pool's owners
     return chain, ks, host
+
+
+class TrackLocalMapChain:
+    """Tracking::TrackLocalMap (Tracking.cc:2745-2806) with the local map COMPUTED on the device, for B frames whose features and poses
+    and a map whose tables stay in HBM:
+
+        UpdateLocalMap()                                                                               Tracking.cc:3184-3358
+        SearchLocalPoints(): the frame's own points are marked seen                                    Tracking.cc:3117-3133
+            Frame::isInFrustum(pMP, 0.5) over mvpLocalMapPoints                                        Frame.cc:611-678
+            ORBmatcher(0.8).SearchByProjection(CurrentFrame, mvpLocalMapPoints, th)                    ORBmatcher.cc:42-209
+        Optimizer::PoseOptimization(&CurrentFrame), inlier count                                       Tracking.cc:2779-2806
+
+    TrackingChain takes the per-frame map-point tables as given; here morb_update_local_map_batch forms them from the keyframes' rows and
+    the points' observations, morb_gather_local_map_points_batch fills them, and update_local_map's frameLocal is the frame's
+    mvpMapPoints as rows of its table.  One stream, no host round trip.  There is no CPU path."""
+
+    def __init__(self, params, cam, kps, desc, count, uRight, tables, curImg, frameMp, pose0, lastKf=None, inertial=False, kf_out=128,
+                 mp_cap=2048, th_local=1.0, device=0, exact_order=True):
+        """params: capi.FrameParams; cam: dict fx fy cx cy bf; kps / desc / count: the feature pool [nimg][cap] (device); uRight [B][cap]
+        of the frames or None; tables: ORBmatcher.local_map_tables (device); curImg i32 [B] pool rows; frameMp i32 [B][cap] = the frames'
+        mvpMapPoints as MAP rows behind TrackWithMotionModel; pose0 f32 [B][7] = the poses behind it; lastKf i32 [B] or None (all device)."""
+        import torch
+        self.torch = torch
+        dev = torch.device("cuda", device)
+        self.P, self.cam, self.tables = params, cam, tables
+        self.kps, self.desc, self.count, self.uRight = kps, desc, count, uRight
+        self.curImg, self.frameMp0, self.pose0, self.lastKf, self.inertial = curImg, frameMp, pose0, lastKf, bool(inertial)
+        self.B = B = int(curImg.shape[0])
+        self.cap = cap = kps.shape[1]
+        assert tuple(frameMp.shape) == (B, cap)
+        self.mpCap, self.th_local = int(mp_cap), float(th_local)
+        self.frameCount = count.index_select(0, curImg.long()).contiguous()       # N of each frame
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        self.m = ORBmatcher(0.8, True, device=device)            # SearchLocalPoints: ORBmatcher(0.8)
+        self.opt = Optimizer(device=device)
+        self.opt.set_exact_order(bool(exact_order))
+        self.stream = torch.cuda.ExternalStream(int(lib().morb_matcher_stream(self.m._h)), device=dev)   # the handle's own: no stream is added
+        self.frameGlobal, self.pose = e((B, cap), i32), e((B, 7), f32)
+        self.lm = dict(localKf=z((B, kf_out), i32), nLocalKf=z((B,), i32), refKf=z((B,), i32), localMp=z((B, mp_cap), i32),
+                       nLocalMp=z((B,), i32), frameLocal=z((B, cap), i32), votes=None, overflow=z((B,), i32))
+        self.nMP = z((B,), i32)
+        self.mp = self.m.gather_local_map_points(tables, self.lm["localMp"], self.nMP)    # allocates the per-frame tables (nothing to copy yet)
+        self.Rcw, self.tcw, self.Ow = e((B, 9), f32), e((B, 3), f32), e((B, 3), f32)
+        self.trk = dict(inView=z((B, mp_cap), u8), projX=e((B, mp_cap), f32), projY=e((B, mp_cap), f32), projXR=e((B, mp_cap), f32),
+                        depth=e((B, mp_cap), f32), level=e((B, mp_cap), i32), viewCos=e((B, mp_cap), f32))
+        self.frameMP, self.noOutlier = e((B, cap), i32), z((B, cap), u8)
+        self.blocked, self.mpSeen = e((B, cap), u8), e((B, mp_cap), u8)
+        self.nm1, self.nmMap1, self.nmLocal = e((B,), i32), e((B,), i32), z((B,), i32)
+        self.hasMP, self.obs, self.invS2, self.Xw = e((B, cap), u8), e((B, cap, 3), f32), e((B, cap), f32), e((B, cap, 3), f32)
+        self.po = (e((B,), i32), z((B, cap), u8), e((B, 2), i32))
+        self.nInl, self.nInlMap = e((B,), i32), e((B,), i32)
+        self._L = lib()
+
+    def close(self):
+        self.stream.synchronize()
+        self.m.close(); self.opt.close()
+
+    def step(self, stream=None):
+        """Enqueue UpdateLocalMap + SearchLocalPoints + PoseOptimization for the B frames; asynchronous on `stream` (default: the chain's)."""
+        torch, L, P = self.torch, self._L, self.P
+        s = self.stream if stream is None else stream
+        st = s.cuda_stream
+        B, cap, mpCap, mh = self.B, self.cap, self.mpCap, self.m._h
+        with torch.cuda.stream(s):
+            self.frameGlobal.copy_(self.frameMp0)
+            self.pose.copy_(self.pose0)
+        self.m.update_local_map(self.tables, self.frameGlobal, self.frameCount, self.lastKf, self.inertial, out=self.lm, stream=st)
+        with torch.cuda.stream(s):
+            torch.clamp(self.lm["nLocalMp"], max=mpCap, out=self.nMP)      # a list longer than the tables (overflow bit 1) is cut to them
+            self.frameMP.copy_(self.lm["frameLocal"])
+        self.m.gather_local_map_points(self.tables, self.lm["localMp"], self.nMP, out=self.mp, stream=st)
+        G = self.mp
+        # SearchLocalPoints' first loop: no outlier to discard here, the call marks the frame's own points seen and the features blocked
+        check(L.morb_track_discard_outliers_batch(mh, B, ptr(self.curImg), cap, ptr(self.count), ptr(self.frameMP), ptr(self.noOutlier), mpCap,
+                                                  ptr(G["mpHasObs"]), ptr(self.blocked), ptr(self.mpSeen), ptr(self.nm1), ptr(self.nmMap1),
+                                                  C.c_void_p(st)))
+        check(L.morb_frame_set_pose_batch(mh, B, ptr(self.pose), ptr(self.Rcw), ptr(self.tcw), ptr(self.Ow), C.c_void_p(st)))
+        self.m.isInFrustum(P, self.Rcw, self.tcw, self.Ow, self.nMP, G["Pw"], G["normal"], G["maxDist"], G["minDist"], 0.5, out=self.trk, stream=st)
+        # the local map holds no bad point (UpdateLocalPoints skips them): mpSeen takes the isBad slot of the search, as in TrackingChain
+        self.m.SearchByProjectionMapPoints(P, self.curImg, self.kps, self.desc, self.count, self.uRight, self.blocked, self.nMP, self.trk,
+                                           self.mpSeen, G["mpDesc"], G["mpHasObs"], self.th_local, False, 0.0, matchF=self.frameMP,
+                                           nm=self.nmLocal, stream=st)
+        check(L.morb_pose_edges_batch(mh, C.byref(P), B, ptr(self.curImg), cap, ptr(self.count), ptr(self.kps), ptr(self.uRight), None, None, 0,
+                                      mpCap, ptr(G["Pw"]), ptr(self.frameMP), ptr(self.hasMP), ptr(self.obs), ptr(self.invS2), ptr(self.Xw),
+                                      C.c_void_p(st)))
+        self.opt.PoseOptimization(self.hasMP, self.obs, self.invS2, self.Xw, self.pose, self.cam, out=self.po, stream=st)
+        check(L.morb_track_discard_outliers_batch(mh, B, ptr(self.curImg), cap, ptr(self.count), ptr(self.frameMP), ptr(self.po[1]), mpCap,
+                                                  ptr(G["mpHasObs"]), None, None, ptr(self.nInl), ptr(self.nInlMap), C.c_void_p(st)))
+
+    def sync(self):
+        self.stream.synchronize()
