@@ -10,14 +10,14 @@
 //     contributes no block and no gradient; a scale column of a _fix_scale vertex is exactly zero and stays in the system (diagonal =
 //     lambda, right-hand side 0).
 //   * k_eg_factor: the block-sparse LDL^T.  7 unknowns per vertex over the whole map and no points to eliminate: in the caller's vertex order
-//     the matrix is a block band (spanning tree, covisibility) plus a few long rows (loop edges).  Storage is the block ENVELOPE: row i
-//     holds the blocks from its first non-zero column to i, and fill never leaves it.  One workgroup takes the block columns in sequence
-//     (left-looking); within a column the rows whose envelope covers it are parallel, one lane per (row, line of the block), the column's
-//     own row staged in LDS in panels of EG_PANEL blocks, scaled by D.  The forward substitution rides on the column loop.  No pivoting
-//     across blocks: H + lambda I is positive definite or the trial fails (ok2 = false), as the reference's Cholesky does.
-//   * k_eg_backsub: the backward substitution, scattering row by row, and the trial estimates exp(x) * S behind it.
+//     the matrix is a block band (spanning tree, covisibility) plus a few long rows (loop edges), which the block envelope of
+//     envelope_plan.h holds with its fill.  The factorisation is envelope_ldlt.h's, which describes storage and schedule: 36 covering rows
+//     take one pass, EG_PANEL blocks of the column's own row are staged at a time, four blocks' loads are kept in flight.  H + lambda I is
+//     positive definite or the trial fails (ok2 = false), as the reference's Cholesky does.
+//   * k_eg_backsub: the backward substitution (envelope_ldlt.h), and the trial estimates exp(x) * S behind it.
 //   * k_eg_errors / k_eg_decide: the trial's chi2 per edge, summed in edge order by one lane; g2o's Levenberg-Marquardt decisions
-//     (lm_control.h) with setUserLambdaInit(1e-16) and optimize(20) on the device, the host queueing trials through ba_host.h's lm_slot_queue.
+//     (lm_control.h: lm_decide_trial) with setUserLambdaInit(1e-16) and optimize(20) on the device, the host queueing trials through
+//     ba_host.h's lm_slot_queue.
 //   * k_eg_finish: the point correction of :1707-1731 behind the solve.
 //   * k_egm_prepare / k_egm_finish: the second overload (map merging, :1737-2063) around the same solve.  Before it, the float poses of the
 //     three lists become g2o::Sim3 estimates in FP64 and every kept edge gets its measurement by the reference's good / bad rules; after
@@ -35,6 +35,7 @@
 
 #include "ba_host.h"
 #include "common.h"
+#include "envelope_ldlt.h"
 #include "envelope_plan.h"
 #include "handles.h"
 #include "internal_abi.h"
@@ -46,10 +47,9 @@ namespace {
 using namespace morb;
 
 constexpr int EG_NT = 256;
-constexpr int EG_PANEL = 32;                    // blocks of the column's own row staged in LDS at a time
+constexpr int EG_PANEL = 32;                    // blocks of the column's own row envelope_factor stages in LDS at a time
 constexpr size_t EG_MAX_BLOCKS = (size_t)1 << 22;   // envelope blocks a handle may grow to (matrix and factor: 2 x 1.5 GiB)
 constexpr int EG_SUM = 2048;                    // values staged in LDS per pass of an ordered sum
-enum { EG_DONE = 0, EG_REBUILD, EG_ITS, EG_TRIALS, EG_OK2 };
 
 struct EgDev {
   int nKF, nE, n, nBlocks, nMP, maxIts;
@@ -72,7 +72,7 @@ struct EgDev {
   double *b, *y, *x, *d;     // [7 n] right-hand side, work vector, solution, D of the factorisation
   LmControl* lm;
   double* chi2;              // [2] active chi2 before and after
-  int* lmi;                  // [8] EG_*
+  int* lmi;                  // [8] LMW_* (lm_control.h)
   int* lmHost;               // mapped host words: [0] decided trials, [1] done
   float* mp;                 // [nMP][3]
   const int* mpRef;          // [nMP]
@@ -188,7 +188,7 @@ __device__ __forceinline__ Sim3d eg_perturbed(const Sim3d& S, int d, bool plus, 
 
 // linearizeOplus of every edge at S: lanes 0 .. 6 of an edge's 16 take the columns of vertex 0, 7 .. 13 those of vertex 1, 14 the error
 __global__ __launch_bounds__(EG_NT) void k_eg_linearize(EgDev D) {
-  if (D.lmi[EG_DONE] || !D.lmi[EG_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const int gid = blockIdx.x * EG_NT + threadIdx.x;
   const int e = gid >> 4, k = gid & 15;
   if (e >= D.nE || k >= 15) return;
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(EG_NT) void k_eg_linearize(EgDev D) {
 
 // H in the envelope and b, every entry summed over its contributions in edge order
 __global__ __launch_bounds__(EG_NT) void k_eg_assemble(EgDev D) {
-  if (D.lmi[EG_DONE] || !D.lmi[EG_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const size_t gid = (size_t)blockIdx.x * EG_NT + threadIdx.x;
   const size_t nH = (size_t)D.nBlocks * 49;
   if (gid < nH) {
@@ -253,192 +253,23 @@ __global__ __launch_bounds__(EG_NT) void k_eg_assemble(EgDev D) {
   D.b[g] = acc;
 }
 
-// L_ij = S_ij L_jj^-T D_j^-1 for one line of a block below the diagonal (sL, sd: the diagonal block's factors in LDS); returns L_ij y_j
-__device__ __forceinline__ double eg_below_line(const double* s, const double* sL, const double* sd, const double* sy, double* l) {
-#pragma unroll
-  for (int c = 0; c < 7; ++c) {
-    double v = s[c];
-#pragma unroll
-    for (int p = 0; p < c; ++p) v -= (l[p] * sd[p]) * sL[c * 7 + p];
-    l[c] = v / sd[c];
-  }
-  double dot = 0;
-#pragma unroll
-  for (int c = 0; c < 7; ++c) dot += l[c] * sy[c];
-  return dot;
-}
-
-// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way.  One workgroup takes the block columns in sequence.
+// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way (envelope_ldlt.h).  One workgroup.  A pivot has to be positive, as
+// the reference's Cholesky asks.
 __global__ __launch_bounds__(EG_NT) void k_eg_factor(EgDev D) {
-  __shared__ double sM[EG_PANEL * 49];
-  __shared__ double sS[49], sL[49], sd[7], sy[7];
-  __shared__ int sOk;
-  if (D.lmi[EG_DONE]) return;
-  const int t = threadIdx.x, n = D.n;
-  const double lambda = D.lm->lambda;
-  if (t == 0) sOk = 1;
-  for (int i = t; i < 7 * n; i += EG_NT) D.y[i] = D.b[i];
-  __threadfence_block();
-  __syncthreads();
-  for (int j = 0; j < n; ++j) {
-    const int fj = D.rowFirst[j];
-    const int cs = D.colStart[j];
-    const int nItems = (D.colStart[j + 1] - cs + 1) * 7;   // a lane per (row, line of its block); lines 0 .. 6 are the diagonal block's
-    const bool one = nItems <= EG_NT;                      // (the usual case: the lines stay in registers from the sums to the division)
-    const size_t rowJ = (size_t)D.rowOff[j];
-    const size_t diag = (rowJ + (j - fj)) * 49;
-    if (t >= 64 && t < 71) sy[t - 64] = D.y[(size_t)j * 7 + t - 64];   // (final since the last column's barrier)
-    double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-    double* mine = nullptr;   // the line's place in the factor
-    int myRow = 0;
-    // ---- S_ij = H_ij - sum_k L_ik D_k L_jk^T, over the k both rows hold ----
-    for (int base = 0; base < nItems; base += EG_NT) {
-      const int item = base + t;
-      const bool valid = item < nItems;
-      int i = j, r = 0, fi = fj;
-      size_t rowI = rowJ;
-      if (valid) {
-        const int w = item / 7;
-        r = item - 7 * w;
-        if (w) { i = D.colRows[cs + w - 1]; fi = D.rowFirst[i]; rowI = (size_t)D.rowOff[i]; }
-        const double* h = D.H + (rowI + (j - fi)) * 49 + r * 7;
-#pragma unroll
-        for (int c = 0; c < 7; ++c) acc[c] = h[c] + ((i == j && c == r) ? lambda : 0.0);
-        mine = D.L + (rowI + (j - fi)) * 49 + r * 7;
-        myRow = i;
-      }
-      for (int c0 = fj; c0 < j; c0 += EG_PANEL) {
-        const int c1 = min(c0 + EG_PANEL, j);
-        __syncthreads();
-        for (int q = t; q < (c1 - c0) * 49; q += EG_NT)   // M_jk = L_jk D_k
-          sM[q] = D.L[(rowJ + (c0 - fj)) * 49 + q] * D.d[(size_t)(c0 + q / 49) * 7 + q % 7];
-        __syncthreads();
-        if (valid) {
-          const double* lik = D.L + (rowI - fi) * 49 + r * 7;   // + 49 k: line r of L_ik
-          int k = max(c0, fi);
-          for (; k + 4 <= c1; k += 4) {   // four blocks' loads in flight
-            double l[4][7];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-              for (int p = 0; p < 7; ++p) l[u][p] = lik[(size_t)(k + u) * 49 + p];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const double* m = sM + (k + u - c0) * 49;
-#pragma unroll
-              for (int c = 0; c < 7; ++c) {
-                double s = 0;
-#pragma unroll
-                for (int p = 0; p < 7; ++p) s += l[u][p] * m[c * 7 + p];
-                acc[c] -= s;
-              }
-            }
-          }
-          for (; k < c1; ++k) {
-            double l[7];
-#pragma unroll
-            for (int p = 0; p < 7; ++p) l[p] = lik[(size_t)k * 49 + p];
-            const double* m = sM + (k - c0) * 49;
-#pragma unroll
-            for (int c = 0; c < 7; ++c) {
-              double s = 0;
-#pragma unroll
-              for (int p = 0; p < 7; ++p) s += l[p] * m[c * 7 + p];
-              acc[c] -= s;
-            }
-          }
-        }
-      }
-      if (valid) {
-        if (i == j) {
-#pragma unroll
-          for (int c = 0; c < 7; ++c) sS[r * 7 + c] = acc[c];
-        } else if (!one) {
-#pragma unroll
-          for (int c = 0; c < 7; ++c) mine[c] = acc[c];
-        }
-      }
-    }
-    if (!one) __threadfence_block();
-    __syncthreads();
-    // ---- the diagonal block: S_jj = L_jj D_j L_jj^T, and y_j = L_jj^-1 y_j ----
-    if (t == 0) {
-      double a[7][7], dd[7], yy[7];
-#pragma unroll
-      for (int r = 0; r < 7; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c) a[r][c] = sS[r * 7 + c];
-      bool ok = true;
-#pragma unroll
-      for (int c = 0; c < 7; ++c) {
-        double dc = a[c][c];
-#pragma unroll
-        for (int p = 0; p < c; ++p) dc -= (a[c][p] * dd[p]) * a[c][p];
-        dd[c] = dc;
-        ok = ok && dc > 0;
-#pragma unroll
-        for (int r = c + 1; r < 7; ++r) {
-          double v = a[r][c];
-#pragma unroll
-          for (int p = 0; p < c; ++p) v -= (a[r][p] * dd[p]) * a[c][p];
-          a[r][c] = v / dc;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 7; ++r) {
-        double v = sy[r];
-#pragma unroll
-        for (int p = 0; p < r; ++p) v -= a[r][p] * yy[p];
-        yy[r] = v;
-      }
-#pragma unroll
-      for (int r = 0; r < 7; ++r) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) sL[r * 7 + c] = c < r ? a[r][c] : (c == r ? 1.0 : 0.0);
-        sd[r] = dd[r];
-        sy[r] = yy[r];
-      }
-      if (!ok) sOk = 0;
-    }
-    __syncthreads();
-    if (!sOk) break;   // (the same for every lane)
-    if (t < 49) D.L[diag + t] = sL[t];
-    if (t >= 64 && t < 71) { D.d[(size_t)j * 7 + t - 64] = sd[t - 64]; D.y[(size_t)j * 7 + t - 64] = sy[t - 64]; }
-    // ---- the rows below: L_ij = S_ij L_jj^-T D_j^-1, and y_i -= L_ij y_j ----
-    if (one) {
-      if (t >= 7 && t < nItems) {
-        double l[7];
-        const double dot = eg_below_line(acc, sL, sd, sy, l);
-#pragma unroll
-        for (int c = 0; c < 7; ++c) mine[c] = l[c];
-        D.y[(size_t)myRow * 7 + (t % 7)] -= dot;
-      }
-    } else {
-      for (int item = 7 + t; item < nItems; item += EG_NT) {
-        const int w = item / 7, r = item - 7 * w;
-        const int i = D.colRows[cs + w - 1];
-        double* o = D.L + ((size_t)D.rowOff[i] + (j - D.rowFirst[i])) * 49 + r * 7;
-        double s[7], l[7];
-#pragma unroll
-        for (int c = 0; c < 7; ++c) s[c] = o[c];
-        const double dot = eg_below_line(s, sL, sd, sy, l);
-#pragma unroll
-        for (int c = 0; c < 7; ++c) o[c] = l[c];
-        D.y[(size_t)i * 7 + r] -= dot;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  if (t == 0) D.lmi[EG_OK2] = sOk;
+  if (D.lmi[LMW_DONE]) return;
+  const bool ok = envelope_factor<7, EG_NT, EG_PANEL, 4, true>(envelope_sys(D), D.lm->lambda);
+  if (threadIdx.x == 0) D.lmi[LMW_OK2] = ok ? 1 : 0;
 }
 
 // x = L^-T D^-1 y: row i, once final, is taken out of the rows above it; then the trial estimates exp(x_v) * S_v.  One workgroup.
+// The 7 x 7 substitution keeps a schedule of its own instead of envelope_ldlt.h's envelope_backsub: the next row's diagonal block (392
+// bytes) is fetched into LDS by 49 idle lanes while the others scatter the current row, so lane 0's serial solve never waits for global
+// memory.  Measured (profiles/r23): 4.74 ms per call at 500 keyframes and 24.0 ms at 2000 against 5.53 and 27.4 on the shared body.
 __global__ __launch_bounds__(EG_NT) void k_eg_backsub(EgDev D) {
   __shared__ double sLb[2][49], sx[7];
-  if (D.lmi[EG_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x, n = D.n;
-  if (D.lmi[EG_OK2]) {
+  if (D.lmi[LMW_OK2]) {
     for (int i = t; i < 7 * n; i += EG_NT) D.x[i] = D.y[i] / D.d[i];
     if (t >= 192 && t < 241) sLb[(n - 1) & 1][t - 192] = D.L[((size_t)D.rowOff[n] - 1) * 49 + t - 192];
     __threadfence_block();
@@ -494,7 +325,7 @@ __global__ __launch_bounds__(EG_NT) void k_eg_backsub(EgDev D) {
 
 // computeError of every edge at the trial estimates (trial != 0) or at S
 __global__ __launch_bounds__(EG_NT) void k_eg_errors(EgDev D, int trial) {
-  if (D.lmi[EG_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int e = blockIdx.x * EG_NT + threadIdx.x;
   if (e >= D.nE) return;
   const double* X = trial ? D.T : D.S;
@@ -506,28 +337,13 @@ __global__ __launch_bounds__(EG_NT) void k_eg_errors(EgDev D, int trial) {
   D.chiE[e] = chi;
 }
 
-// sum of n values in index order: the workgroup stages them in LDS, lane 0 adds.  term(i) is evaluated by every lane.
-template <class Term>
-__device__ double eg_ordered_sum(double* buf, int n, Term&& term) {
-  double acc = 0;
-  for (int base = 0; base < n; base += EG_SUM) {
-    const int m = min(EG_SUM, n - base);
-    for (int q = threadIdx.x; q < m; q += EG_NT) buf[q] = term(base + q);
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int q = 0; q < m; ++q) acc += buf[q];
-    __syncthreads();
-  }
-  return acc;   // (lane 0's)
-}
-
 // init != 0: behind the first computeActiveErrors; else g2o's decision after a trial (lm_control.h).  One workgroup.
 __global__ __launch_bounds__(EG_NT) void k_eg_decide(EgDev D, int init) {
   __shared__ double buf[EG_SUM];
   __shared__ int sKeep;
-  if (D.lmi[EG_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x;
-  const double chi = eg_ordered_sum(buf, D.nE, [&](int e) { return D.chiE[e]; });
+  const double chi = lm_sum_in_index_order<EG_NT, EG_SUM>(buf, D.nE, [&](int e) { return D.chiE[e]; });
   LmControl c = *D.lm;
   if (init) {
     if (t == 0) {
@@ -535,29 +351,13 @@ __global__ __launch_bounds__(EG_NT) void k_eg_decide(EgDev D, int init) {
       lm_iteration(c, chi);
       *D.lm = c;
       D.chi2[0] = chi; D.chi2[1] = chi;
-      D.lmi[EG_REBUILD] = 1; D.lmi[EG_ITS] = 0; D.lmi[EG_TRIALS] = 0; D.lmi[EG_OK2] = 1;
+      D.lmi[LMW_REBUILD] = 1; D.lmi[LMW_ITS] = 0; D.lmi[LMW_TRIALS] = 0; D.lmi[LMW_OK2] = 1;
     }
     return;
   }
   const double lambda = c.lambda;
-  const double gain = eg_ordered_sum(buf, 7 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b[i]); });   // computeScale()
-  if (t == 0) {
-    bool again = false;
-    const bool keep = lm_trial(c, chi, D.lmi[EG_OK2] != 0, gain, &again);
-    int its = D.lmi[EG_ITS], done = 0, rebuild = 0;
-    const int trials = D.lmi[EG_TRIALS] + 1;
-    if (!again) {
-      ++its;
-      done = (lm_iteration_done(c) || its >= D.maxIts) ? 1 : 0;
-      if (!done) { lm_iteration(c, c.currentChi); rebuild = 1; }
-    }
-    *D.lm = c;
-    D.chi2[1] = c.currentChi;
-    D.lmi[EG_ITS] = its; D.lmi[EG_TRIALS] = trials; D.lmi[EG_REBUILD] = rebuild; D.lmi[EG_DONE] = done;
-    sKeep = keep ? 1 : 0;
-    __hip_atomic_store(D.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(D.lmHost + 0, trials, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided trials: the host queues trial k + 2 when it sees k
-  }
+  const double gain = lm_sum_in_index_order<EG_NT, EG_SUM>(buf, 7 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b[i]); });   // computeScale()
+  if (t == 0) sKeep = lm_decide_trial(c, chi, D.lmi[LMW_OK2] != 0, gain, false, D.maxIts, D.lm, D.chi2, D.lmi, D.lmHost) ? 1 : 0;
   __syncthreads();
   if (sKeep)
     for (int i = t; i < 8 * D.nKF; i += EG_NT) D.S[i] = D.T[i];
@@ -796,7 +596,7 @@ int eg_solve(morb_optimizer* o, hipStream_t st, EgDev& D) {
   int *hostw = nullptr, *hostwDev = nullptr;
   MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
   D.lmHost = hostwDev;
-  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  reset_lm_words(hostw, 2, nullptr);
   // the workspace is reused from call to call: what the first kernels expect to find zero is cleared behind the carve
   MORB_HIP_CHECK(hipMemsetAsync(D.lmi, 0, sizeof(int) * 8, st));
   MORB_HIP_CHECK(hipMemsetAsync(D.lm, 0, sizeof(LmControl), st));
@@ -818,11 +618,7 @@ int eg_solve(morb_optimizer* o, hipStream_t st, EgDev& D) {
     hipLaunchKernelGGL(k_eg_decide, dim3(1), dim3(EG_NT), 0, st, D, 0);
     if (hipGetLastError() != hipSuccess) { set_error("OptimizeEssentialGraph: a trial's launch failed"); return (int)MORB_ERR_HIP; }
     return (int)MORB_OK;
-  }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("OptimizeEssentialGraph: %s while waiting for the LM decision", hipGetErrorString(e));
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, []() {});
+  }, [&]() { return stream_look(st, "OptimizeEssentialGraph"); }, []() {});
   return q < 0 ? MORB_ERR_HIP : MORB_OK;
 }
 
@@ -880,7 +676,7 @@ extern "C" int morb_optimize_essential_graph(morb_optimizer* o, int nKF, double*
   MORB_HIP_CHECK(hipMemcpyAsync(kfSim3, D.S, sizeof(double) * 8 * nKF, hipMemcpyDeviceToHost, st));
   if (nMP) MORB_HIP_CHECK(hipMemcpyAsync(mpPos, D.mp, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st));
   MORB_HIP_CHECK(hipStreamSynchronize(st));   // (also drains a queue that ran out of slots before the words are reset again)
-  stats4[0] = hi[EG_ITS]; stats4[1] = hi[EG_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
+  stats4[0] = hi[LMW_ITS]; stats4[1] = hi[LMW_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
   return MORB_OK;
 }
 
@@ -968,7 +764,7 @@ extern "C" int morb_optimize_essential_graph_merge(morb_optimizer* o, int nKF, c
   for (int a = 0; a < 4; ++a) memcpy(host[a], out.data() + a * plane, sizeof(float) * plane);
   if (nMP) memcpy(mpPos, out.data() + 4 * plane, sizeof(float) * 3 * nMP);
   if (nC) memcpy(cKept, kept.data(), nC);
-  stats4[0] = hi[EG_ITS]; stats4[1] = hi[EG_TRIALS]; stats4[2] = solve ? P.n : 0; stats4[3] = solve ? P.nBlocks : 0;
+  stats4[0] = hi[LMW_ITS]; stats4[1] = hi[LMW_TRIALS]; stats4[2] = solve ? P.n : 0; stats4[3] = solve ? P.nBlocks : 0;
   chi2[0] = hchi[0]; chi2[1] = hchi[1];
   return MORB_OK;
 }

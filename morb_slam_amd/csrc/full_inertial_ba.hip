@@ -15,10 +15,10 @@
 //   * k_fiba_dinv, k_fiba_schur, k_fiba_finish: global_ba.hip's sparse Schur complement — only the 6 pose columns of a keyframe meet a
 //     point — cut into chunks of FIBA_CHUNK per 3 x 3 envelope block; finish adds, per envelope entry, the keyframe's visual block, its
 //     links' records in link order and the priors, and takes the chunks' sums off in order.  No floating-point atomics anywhere.
-//   * k_fiba_factor: H + lambda I = L D L^T over the envelope, k_gba_factor's layout with 6 -> 3: FIBA_ROWS covering rows a pass (a lane
-//     per row and line), the column's own row staged in LDS FIBA_STAGE blocks at a time, every lane factorises the diagonal block in
-//     registers.  A zero or NaN pivot: zero step, rejected trial.
-//   * k_fiba_backsub: back-substitution and oplus (ImuCamPose::Update, additive velocity and biases; the shared biases once).
+//   * k_fiba_factor: H + lambda I = L D L^T over the envelope by envelope_ldlt.h, which describes the schedule: FIBA_ROWS covering rows a
+//     pass, FIBA_STAGE blocks staged at a time.  A zero or NaN pivot: zero step, rejected trial.
+//   * k_fiba_backsub: back-substitution (envelope_ldlt.h) and oplus (ImuCamPose::Update, additive velocity and biases; the shared biases
+//     once).
 //   * k_fiba_points, k_fiba_errors, k_fiba_decide: as global_ba.hip's; lambda starts at the user value 1e-5 (:384).
 #include <hip/hip_runtime.h>
 
@@ -31,6 +31,7 @@
 
 #include "ba_host.h"
 #include "common.h"
+#include "envelope_ldlt.h"
 #include "envelope_plan.h"
 #include "handles.h"
 #include "internal_abi.h"
@@ -42,9 +43,8 @@ namespace {
 using namespace morb;
 
 constexpr int FIBA_NT = 256;                  // lanes of a workgroup
-constexpr int FIBA_ROWS = FIBA_NT / 3;        // covering rows of 3 lines one pass of the factorisation takes (the diagonal block's among them): 85
-constexpr int FIBA_PASS = FIBA_ROWS * 3;      // lanes at work in a pass
-constexpr int FIBA_STAGE = 128;               // blocks of the column's own row staged in LDS at a time (9 KiB)
+constexpr int FIBA_ROWS = FIBA_NT / 3;        // covering rows of 3 lines one pass of envelope_factor takes (the diagonal block's among them): 85
+constexpr int FIBA_STAGE = 128;               // blocks of the column's own row envelope_factor stages in LDS at a time (9 KiB)
 constexpr int FIBA_CHUNK = 64;                // Schur contributions one lane adds before the chunks are added
 // envelope blocks a handle may grow to: the bytes global_ba.hip allows its 6 x 6 envelope, in 3 x 3 blocks
 constexpr size_t FIBA_MAX_BLOCKS = ((size_t)1 << 22) * 49 / 9;
@@ -52,7 +52,6 @@ constexpr int FIBA_EDGE = 31;                 // doubles of a visual edge's reco
 enum { FE_JP = 0, FE_JL = 18, FE_RW = 27, FE_WO = 30 };
 constexpr int FIBA_LCOLS = 30;                // columns of a link's record: pose 1 (6), v1, bg1, ba1, pose 2 (6), v2, bg2, ba2
 constexpr int FIBA_LREC = FIBA_LCOLS * FIBA_LCOLS + FIBA_LCOLS;   // w J^T Omega J (+ the random-walk edges), then -w J^T Omega e
-enum { FIBA_DONE = 0, FIBA_REBUILD, FIBA_ITS, FIBA_TRIALS, FIBA_OK2 };
 
 struct FibaDev {
   int nKF, nMP, nE, nI, nSys, n, P, nBlocks, nPairs, nChunks, maxIts, bInit, nChi, rbB;
@@ -94,7 +93,7 @@ struct FibaDev {
   double* chiE;                         // [nChi] visual edges, links, the two priors
   LmControl* lm;
   double* chi2;                         // [2]
-  int* lmi;                             // [8] FIBA_*
+  int* lmi;                             // [8] LMW_* (lm_control.h)
   int* lmHost;                          // mapped host words: [0] decided trials, [1] done, [2] the caller's stop flag as the host forwards it
   double priorG, priorA;
   CamGeom g;
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_setup(FibaDev D) {
 // computeError and the robust chi2 of every edge at the trial estimate (trial != 0) or at the current one: visual edges, links (EdgeInertial
 // under Huber, EdgeGyroRW, EdgeAccRW), the two priors
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_errors(FibaDev D, int trial) {
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = blockIdx.x * FIBA_NT + threadIdx.x;
   if (t >= D.nChi) return;
   const double *S = trial ? D.ST : D.S, *pt = trial ? D.ptT : D.pt, *sb = trial ? D.sbT : D.sb;
@@ -235,7 +234,7 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_errors(FibaDev D, int trial) {
 // linearizeOplus and the robust weight of every visual edge at the current estimate
 template <bool RIG>
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_linearize(FibaDev D) {
-  if (D.lmi[FIBA_DONE] || !D.lmi[FIBA_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const int e = blockIdx.x * FIBA_NT + threadIdx.x;
   if (e >= D.nE) return;
   VIState V;
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_linearize(FibaDev D) {
 __global__ __launch_bounds__(64) void k_fiba_links(FibaDev D) {
   __shared__ double J[216], OJ[216], Oe[9], ge[3], ae[3];
   __shared__ double sw;
-  if (D.lmi[FIBA_DONE] || !D.lmi[FIBA_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const int i = blockIdx.x, tid = threadIdx.x;
   for (int k = tid; k < 216; k += 64) J[k] = 0;
   __syncthreads();
@@ -365,7 +364,7 @@ __device__ __forceinline__ double fiba_sum_jtr(const double* E, const int* list,
 
 // Hpp, bp (42 lanes per keyframe of the system), Hll, bl (12 per point), Hpl (18 per pair)
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_assemble(FibaDev D) {
-  if (D.lmi[FIBA_DONE] || !D.lmi[FIBA_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   size_t gid = (size_t)blockIdx.x * FIBA_NT + threadIdx.x;
   if (gid < (size_t)D.nSys * 42) {
     const int a = (int)(gid / 42), k = (int)(gid % 42);
@@ -391,7 +390,7 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_assemble(FibaDev D) {
 
 // Dinv per point; Hpl Dinv and Hpl Dinv bl per pair (a pair's lane inverts its point's block itself)
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_dinv(FibaDev D) {
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int gid = blockIdx.x * FIBA_NT + threadIdx.x;
   if (gid >= D.nMP + D.nPairs) return;
   const double lambda = D.lm->lambda;
@@ -422,7 +421,7 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_dinv(FibaDev D) {
 
 // a chunk of an envelope block's contributions: sum of (Hpl_i1 Dinv) Hpl_i2^T restricted to the block, a lane per (chunk, entry), in point order
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_schur(FibaDev D) {
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const size_t gid = (size_t)blockIdx.x * FIBA_NT + threadIdx.x;
   if (gid >= (size_t)D.nChunks * 9) return;
   const int c = (int)(gid / 9), ent = (int)(gid % 9), r = ent / 3, cc = ent % 3;
@@ -439,7 +438,7 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_schur(FibaDev D) {
 // the reduced system: an envelope entry = the keyframe's visual block + its links' records in link order + the prior - the chunks' sums in
 // order; a row of b likewise, minus sum Hpl Dinv bl over the keyframe's pairs in point order
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_finish(FibaDev D) {
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const size_t gid = (size_t)blockIdx.x * FIBA_NT + threadIdx.x;
   const size_t nH = (size_t)D.nBlocks * 9;
   if (gid < nH) {
@@ -480,215 +479,20 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_finish(FibaDev D) {
   D.b[k] = base - acc;
 }
 
-// one line of S_ij -= L_ik (D_k L_jk^T): l = line r of L_ik, m = M_jk = L_jk D_k (row-major, in LDS)
-__device__ __forceinline__ void fiba_line_minus(double* acc, const double* l, const double* m) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double s = 0;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) s += l[p] * m[c * 3 + p];
-    acc[c] -= s;
-  }
-}
-// L_ij = S_ij L_jj^-T D_j^-1 for one line of a block below the diagonal (a: L_jj's strictly lower part); returns L_ij y_j
-__device__ __forceinline__ double fiba_below_line(const double* s, const double (*a)[3], const double* dd, const double* yy, double* l) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double v = s[c];
-#pragma unroll
-    for (int p = 0; p < c; ++p) v -= (l[p] * dd[p]) * a[c][p];
-    l[c] = v / dd[c];
-  }
-  double dot = 0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) dot += l[c] * yy[c];
-  return dot;
-}
-
-// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way.  One workgroup takes the block columns in sequence.
+// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way (envelope_ldlt.h).  One workgroup.  A zero or NaN pivot fails.
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_factor(FibaDev D) {
-  __shared__ double sM[FIBA_STAGE * 9];
-  __shared__ double sS[9];
-  if (D.lmi[FIBA_DONE]) return;
-  const int t = threadIdx.x, n = D.n;
-  const double lambda = D.lm->lambda;
-  bool ok = true;
-  for (int i = t; i < 3 * n; i += FIBA_NT) D.y[i] = D.b[i];
-  __threadfence_block();
-  __syncthreads();
-  for (int j = 0; j < n; ++j) {
-    const int fj = D.rowFirst[j];
-    const int cs = D.colStart[j];
-    const int nItems = (D.colStart[j + 1] - cs + 1) * 3;   // a lane per (row, line of its block); lines 0 .. 2 are the diagonal block's
-    const bool one = nItems <= FIBA_PASS;                  // (the usual case: the lines stay in registers from the sums to the division)
-    const size_t rowJ = (size_t)D.rowOff[j];
-    const size_t diag = (rowJ + (j - fj)) * 9;
-    double yj[3];                                          // (final since the last column's barrier)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) yj[r] = D.y[(size_t)j * 3 + r];
-    double acc[3] = {0, 0, 0};
-    double* mine = nullptr;   // the line's place in the factor
-    int myRow = 0;
-    // ---- S_ij = H_ij - sum_k L_ik D_k L_jk^T, over the k both rows hold ----
-    for (int base = 0; base < nItems; base += FIBA_PASS) {
-      const int item = base + t;
-      const bool valid = t < FIBA_PASS && item < nItems;
-      int i = j, r = 0, fi = fj;
-      size_t rowI = rowJ;
-      if (valid) {
-        const int w = item / 3;
-        r = item - w * 3;
-        if (w) { i = D.colRows[cs + w - 1]; fi = D.rowFirst[i]; rowI = (size_t)D.rowOff[i]; }
-        const double* h = D.H + (rowI + (j - fi)) * 9 + r * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = h[c] + ((i == j && c == r) ? lambda : 0.0);
-        mine = D.L + (rowI + (j - fi)) * 9 + r * 3;
-        myRow = i;
-      }
-      for (int c0 = fj; c0 < j; c0 += FIBA_STAGE) {
-        const int c1 = min(c0 + FIBA_STAGE, j);
-        if (base || c0 != fj) __syncthreads();   // (the column's first stage follows the last column's barrier)
-        for (int q = t; q < (c1 - c0) * 9; q += FIBA_NT)   // M_jk = L_jk D_k
-          sM[q] = D.L[(rowJ + (c0 - fj)) * 9 + q] * D.d[(size_t)(c0 + q / 9) * 3 + q % 3];
-        __syncthreads();
-        if (valid) {
-          const double* lik = D.L + (rowI - fi) * 9 + r * 3;   // + 9 k: line r of L_ik
-          for (int k = max(c0, fi); k < c1; ++k) {
-            double l[3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) l[p] = lik[(size_t)k * 9 + p];
-            fiba_line_minus(acc, l, sM + (k - c0) * 9);
-          }
-        }
-      }
-      if (valid) {
-        if (i == j) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) sS[r * 3 + c] = acc[c];
-        } else if (!one) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) mine[c] = acc[c];
-        }
-      }
-    }
-    if (!one) __threadfence_block();
-    __syncthreads();
-    // ---- the diagonal block, by every lane for itself: S_jj = L_jj D_j L_jj^T, and y_j = L_jj^-1 y_j ----
-    double a[3][3], dd[3], yy[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) a[r][c] = c <= r ? sS[r * 3 + c] : 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      double dc = a[c][c];
-#pragma unroll
-      for (int p = 0; p < c; ++p) dc -= (a[c][p] * dd[p]) * a[c][p];
-      dd[c] = dc;
-      ok = ok && dc != 0 && dc == dc;   // a zero or NaN pivot: the factorisation has failed
-#pragma unroll
-      for (int r = c + 1; r < 3; ++r) {
-        double v = a[r][c];
-#pragma unroll
-        for (int p = 0; p < c; ++p) v -= (a[r][p] * dd[p]) * a[c][p];
-        a[r][c] = v / dc;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double v = yj[r];
-#pragma unroll
-      for (int p = 0; p < r; ++p) v -= a[r][p] * yy[p];
-      yy[r] = v;
-    }
-    if (!ok) break;   // (the same for every lane)
-    if (t < 9) {
-      double v = 0.0;   // (written out: no array is indexed by a run-time value)
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          if (t == r * 3 + c) v = c < r ? a[r][c] : (c == r ? 1.0 : 0.0);
-      D.L[diag + t] = v;
-    }
-    if (t >= 64 && t < 67) {
-      double dv = 0.0, yv = 0.0;
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        if (t - 64 == r) { dv = dd[r]; yv = yy[r]; }
-      D.d[(size_t)j * 3 + t - 64] = dv;
-      D.y[(size_t)j * 3 + t - 64] = yv;
-    }
-    // ---- the rows below: L_ij = S_ij L_jj^-T D_j^-1, and y_i -= L_ij y_j ----
-    if (one) {
-      if (t >= 3 && t < nItems) {
-        double l[3];
-        const double dot = fiba_below_line(acc, a, dd, yy, l);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) mine[c] = l[c];
-        D.y[(size_t)myRow * 3 + (t % 3)] -= dot;
-      }
-    } else {
-      for (int item = 3 + t; item < nItems; item += FIBA_NT) {
-        const int w = item / 3, r = item - w * 3;
-        const int i = D.colRows[cs + w - 1];
-        double* o = D.L + ((size_t)D.rowOff[i] + (j - D.rowFirst[i])) * 9 + r * 3;
-        double s[3], l[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] = o[c];
-        const double dot = fiba_below_line(s, a, dd, yy, l);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = l[c];
-        D.y[(size_t)i * 3 + r] -= dot;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  if (t == 0) D.lmi[FIBA_OK2] = ok ? 1 : 0;
+  if (D.lmi[LMW_DONE]) return;
+  const bool ok = envelope_factor<3, FIBA_NT, FIBA_STAGE, 1, false>(envelope_sys(D), D.lm->lambda);
+  if (threadIdx.x == 0) D.lmi[LMW_OK2] = ok ? 1 : 0;
 }
 
-// x = L^-T D^-1 y: row i, once final, is taken out of the rows above it; then the trial states: ImuCamPose::Update for the pose, additive
-// velocity and biases, the shared biases once.  One workgroup.  A failed factorisation leaves the step zero.
+// x = L^-T D^-1 y (envelope_ldlt.h), then the trial states: ImuCamPose::Update for the pose, additive velocity and biases, the shared
+// biases once.  One workgroup.  A failed factorisation leaves the step zero.
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_backsub(FibaDev D) {
-  __shared__ double sx[3];
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x, n = D.n;
-  if (D.lmi[FIBA_OK2]) {
-    for (int i = t; i < 3 * n; i += FIBA_NT) D.x[i] = D.y[i] / D.d[i];
-    __threadfence_block();
-    __syncthreads();
-    for (int i = n - 1; i >= 0; --i) {
-      const int fi = D.rowFirst[i];
-      const size_t rowI = (size_t)D.rowOff[i];
-      if (t == 0) {   // x_i = L_ii^-T z_i
-        const double* Ld = D.L + ((size_t)D.rowOff[i + 1] - 1) * 9;
-        double z[3], xx[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) z[r] = D.x[(size_t)i * 3 + r];
-#pragma unroll
-        for (int r = 2; r >= 0; --r) {
-          double v = z[r];
-#pragma unroll
-          for (int p = r + 1; p < 3; ++p) v -= Ld[p * 3 + r] * xx[p];
-          xx[r] = v;
-        }
-#pragma unroll
-        for (int r = 0; r < 3; ++r) { sx[r] = xx[r]; D.x[(size_t)i * 3 + r] = xx[r]; }
-      }
-      __syncthreads();
-      const int cnt = (i - fi) * 3;
-      for (int item = t; item < cnt; item += FIBA_NT) {
-        const int kk = item / 3, c = item - kk * 3;
-        const double* lik = D.L + (rowI + kk) * 9;
-        double dot = 0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) dot += lik[r * 3 + c] * sx[r];
-        D.x[(size_t)(fi + kk) * 3 + c] -= dot;
-      }
-      __threadfence_block();
-      __syncthreads();
-    }
+  if (D.lmi[LMW_OK2]) {
+    envelope_backsub<3, FIBA_NT>(envelope_sys(D));
   } else {
     for (int i = t; i < 3 * n; i += FIBA_NT) D.x[i] = 0.0;
     __threadfence_block();
@@ -714,11 +518,11 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_backsub(FibaDev D) {
 
 // xl = Dinv (bl - Hpl^T xp) over the point's pairs in order, and the trial points
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_points(FibaDev D) {
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int m = blockIdx.x * FIBA_NT + threadIdx.x;
   if (m >= D.nMP) return;
   double xl[3] = {0, 0, 0};
-  if (D.lmi[FIBA_OK2] && D.mpStart[m + 1] > D.mpStart[m]) {
+  if (D.lmi[LMW_OK2] && D.mpStart[m + 1] > D.mpStart[m]) {
     double cl[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) cl[j] = D.bl[(size_t)m * 3 + j];
@@ -738,28 +542,13 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_points(FibaDev D) {
   for (int j = 0; j < 3; ++j) { D.xl[(size_t)m * 3 + j] = xl[j]; D.ptT[(size_t)m * 3 + j] = D.pt[(size_t)m * 3 + j] + xl[j]; }
 }
 
-// sum of n values in a fixed order: lane t adds its slice of ceil(n / FIBA_NT) consecutive values, lane 0 adds the lanes' sums
-template <class Term>
-__device__ double fiba_ordered_sum(double* buf, int n, Term&& term) {
-  const int per = (n + FIBA_NT - 1) / FIBA_NT, t = threadIdx.x;
-  double s = 0;
-  for (int i = t * per; i < min((t + 1) * per, n); ++i) s += term(i);
-  __syncthreads();
-  buf[t] = s;
-  __syncthreads();
-  double acc = 0;
-  if (t == 0)
-    for (int q = 0; q < FIBA_NT; ++q) acc += buf[q];
-  return acc;   // (lane 0's)
-}
-
 // init != 0: behind the first computeActiveErrors; else g2o's decision after a trial (lm_control.h).  One workgroup.
 __global__ __launch_bounds__(FIBA_NT) void k_fiba_decide(FibaDev D, int init) {
   __shared__ double buf[FIBA_NT];
   __shared__ int sKeep;
-  if (D.lmi[FIBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x;
-  const double chi = fiba_ordered_sum(buf, D.nChi, [&](int e) { return D.chiE[e]; });
+  const double chi = lm_sum_of_lane_slices<FIBA_NT>(buf, D.nChi, [&](int e) { return D.chiE[e]; });
   LmControl c = *D.lm;
   if (init) {
     if (t == 0) {
@@ -768,33 +557,15 @@ __global__ __launch_bounds__(FIBA_NT) void k_fiba_decide(FibaDev D, int init) {
       lm_iteration(c, chi);
       *D.lm = c;
       D.chi2[0] = chi; D.chi2[1] = chi;
-      D.lmi[FIBA_REBUILD] = 1; D.lmi[FIBA_ITS] = 0; D.lmi[FIBA_TRIALS] = 0; D.lmi[FIBA_OK2] = 1; D.lmi[FIBA_DONE] = stop;
+      D.lmi[LMW_REBUILD] = 1; D.lmi[LMW_ITS] = 0; D.lmi[LMW_TRIALS] = 0; D.lmi[LMW_OK2] = 1; D.lmi[LMW_DONE] = stop;
       if (stop) __hip_atomic_store(D.lmHost + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     return;
   }
   const double lambda = c.lambda;
-  const double gainP = fiba_ordered_sum(buf, D.P, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b0[i]); });   // computeScale()
-  const double gainL = fiba_ordered_sum(buf, 3 * D.nMP, [&](int i) { return D.xl[i] * (lambda * D.xl[i] + D.bl[i]); });
-  if (t == 0) {
-    bool again = false;
-    const bool keep = lm_trial(c, chi, D.lmi[FIBA_OK2] != 0, gainP + gainL, &again);
-    const bool stop = fiba_stop(D);
-    if (stop) again = false;
-    int its = D.lmi[FIBA_ITS], done = 0, rebuild = 0;
-    const int trials = D.lmi[FIBA_TRIALS] + 1;
-    if (!again) {
-      ++its;
-      done = (lm_iteration_done(c) || its >= D.maxIts || stop) ? 1 : 0;
-      if (!done) { lm_iteration(c, c.currentChi); rebuild = 1; }
-    }
-    *D.lm = c;
-    D.chi2[1] = c.currentChi;
-    D.lmi[FIBA_ITS] = its; D.lmi[FIBA_TRIALS] = trials; D.lmi[FIBA_REBUILD] = rebuild; D.lmi[FIBA_DONE] = done;
-    sKeep = keep ? 1 : 0;
-    __hip_atomic_store(D.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(D.lmHost + 0, trials, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided trials: the host queues trial k + 2 when it sees k
-  }
+  const double gainP = lm_sum_of_lane_slices<FIBA_NT>(buf, D.P, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b0[i]); });   // computeScale()
+  const double gainL = lm_sum_of_lane_slices<FIBA_NT>(buf, 3 * D.nMP, [&](int i) { return D.xl[i] * (lambda * D.xl[i] + D.bl[i]); });
+  if (t == 0) sKeep = lm_decide_trial(c, chi, D.lmi[LMW_OK2] != 0, gainP + gainL, fiba_stop(D), D.maxIts, D.lm, D.chi2, D.lmi, D.lmHost) ? 1 : 0;
   __syncthreads();
   if (sKeep) {
     for (int i = t; i < 33 * D.nKF; i += FIBA_NT) D.S[i] = D.ST[i];
@@ -1088,7 +859,7 @@ int fiba_run(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind
   D.lmHost = hostwDev;
   const volatile uint8_t* userStop = pbStopFlag;
   auto forwardStop = [&]() { if (userStop && *userStop) __atomic_store_n(hostw + 2, 1, __ATOMIC_RELEASE); };   // optimizer.setForceStopFlag(pbStopFlag) (:388)
-  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 2, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  reset_lm_words(hostw, 2, hostw + 2);
   forwardStop();
   MORB_HIP_CHECK(hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st));   // the one upload
   // the workspace is reused from call to call: what the first kernels expect to find zero is cleared
@@ -1121,11 +892,7 @@ int fiba_run(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind
     hipLaunchKernelGGL(k_fiba_decide, dim3(1), dim3(FIBA_NT), 0, st, D, 0);
     if (hipGetLastError() != hipSuccess) { set_error("FullInertialBA: a trial's launch failed"); return (int)MORB_ERR_HIP; }
     return (int)MORB_OK;
-  }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("FullInertialBA: %s while waiting for the LM decision", hipGetErrorString(e));
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, forwardStop);
+  }, [&]() { return stream_look(st, "FullInertialBA"); }, forwardStop);
   if (q < 0) return MORB_ERR_HIP;
   int hi[8];
   double c2[2], sb[6];
@@ -1147,7 +914,7 @@ int fiba_run(morb_optimizer* o, int nKF, float* kfState21, const uint8_t* kfKind
   }
   if (bInit) for (int k = 0; k < 6; ++k) bias6[k] = (float)sb[k];
   for (int m = 0; m < nMP; ++m) if (mpStart[m + 1] > mpStart[m]) for (int k = 0; k < 3; ++k) mpPos[3 * m + k] = (float)pt[(size_t)3 * m + k];
-  stats4[0] = hi[FIBA_ITS]; stats4[1] = hi[FIBA_TRIALS]; stats4[2] = P; stats4[3] = nBlocks;
+  stats4[0] = hi[LMW_ITS]; stats4[1] = hi[LMW_TRIALS]; stats4[2] = P; stats4[3] = nBlocks;
   chi2[0] = c2[0]; chi2[1] = c2[1];
   return MORB_OK;
 }

@@ -12,13 +12,14 @@
 //     the points both keyframes see of (Hpl_i1 Dinv) Hpl_i2^T, in point order (block_solver.hpp:354-480); its contribution list is cut into
 //     chunks of GBA_CHUNK, a lane per (chunk, entry) over the whole grid, and the chunks' sums are added in order.  Nothing dense in
 //     nMP x nKF exists.
-//   * k_gba_factor: H + lambda I = L D L^T over the envelope of the 6 x 6 block rows (envelope_plan.h), left-looking by block column in one
-//     workgroup, as pose_graph_4dof.hip's 4 x 4 kernel: GBA_ROWS covering rows take one pass (a lane per row and line), the column's own row,
-//     scaled by D, is staged in LDS GBA_STAGE blocks at a time, every lane factorises the diagonal block itself.  A zero or NaN pivot is a
-//     failed factorisation: a rejected trial.
-//   * k_gba_backsub / k_gba_points: the backward substitution and SE3Quat::exp(dx) * T; xl = Dinv (bl - Hpl^T xp) and += per point.
-//   * k_gba_errors / k_gba_decide: robust chi2 per edge, summed in a fixed order; g2o's Levenberg-Marquardt decisions (lm_control.h),
-//     optimize(nIterations), the stop flag polled at every decision, the host queueing trials through ba_host.h's lm_slot_queue.
+//   * k_gba_factor: H + lambda I = L D L^T over the envelope of the 6 x 6 block rows (envelope_plan.h) by envelope_ldlt.h, which describes
+//     the schedule: GBA_ROWS covering rows take one pass, GBA_STAGE blocks are staged at a time.  A zero or NaN pivot is a failed
+//     factorisation: a rejected trial.
+//   * k_gba_backsub / k_gba_points: the backward substitution (envelope_ldlt.h) and SE3Quat::exp(dx) * T; xl = Dinv (bl - Hpl^T xp) and +=
+//     per point.
+//   * k_gba_errors / k_gba_decide: robust chi2 per edge, summed by lane slices; g2o's Levenberg-Marquardt decisions (lm_control.h:
+//     lm_decide_trial), optimize(nIterations), the stop flag polled at every decision, the host queueing trials through ba_host.h's
+//     lm_slot_queue.
 // A keyframe without an edge, a fixed keyframe and a point without an edge are not in the system and keep their bytes.
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,7 @@
 
 #include "ba_host.h"
 #include "common.h"
+#include "envelope_ldlt.h"
 #include "envelope_plan.h"
 #include "handles.h"
 #include "internal_abi.h"
@@ -42,15 +44,13 @@ namespace {
 using namespace morb;
 
 constexpr int GBA_NT = 256;                 // lanes of a workgroup
-constexpr int GBA_ROWS = GBA_NT / 6;        // covering rows of 6 lines one pass of the factorisation takes (the diagonal block's among them): 42
-constexpr int GBA_PASS = GBA_ROWS * 6;      // lanes at work in a pass
-constexpr int GBA_STAGE = 64;               // blocks of the column's own row staged in LDS at a time (18 KiB)
+constexpr int GBA_ROWS = GBA_NT / 6;        // covering rows of 6 lines one pass of envelope_factor takes (the diagonal block's among them): 42
+constexpr int GBA_STAGE = 64;               // blocks of the column's own row envelope_factor stages in LDS at a time (18 KiB)
 constexpr int GBA_CHUNK = 64;               // Schur contributions one lane adds before the chunks are added
 // envelope blocks a handle may grow to: the bytes the Sim3 pose graph allows its 7 x 7 envelope (2^22 blocks of H and of L), in 6 x 6 blocks
 constexpr size_t GBA_MAX_BLOCKS = ((size_t)1 << 22) * 49 / 36;
 constexpr int GBA_EDGE = 31;                // doubles of an edge's record: Jp 3 x 6, Jl 3 x 3, -(w info) e, w info
 enum { GE_JP = 0, GE_JL = 18, GE_RW = 27, GE_WO = 30 };
-enum { GBA_DONE = 0, GBA_REBUILD, GBA_ITS, GBA_TRIALS, GBA_OK2, GBA_LAMBDA0 };
 
 struct GbaDev {
   int nKF, nMP, nE, n, nBlocks, nPairs, nChunks, maxIts, robust;
@@ -81,7 +81,7 @@ struct GbaDev {
   double* chiE;                         // [nE]
   LmControl* lm;
   double* chi2;                         // [2]
-  int* lmi;                             // [8] GBA_*
+  int* lmi;                             // [8] LMW_* (lm_control.h)
   int* lmHost;                          // mapped host words: [0] decided trials, [1] done, [2] the caller's stop flag as the host forwards it
   Cam cam;
   const Rig* rig;
@@ -114,7 +114,7 @@ __device__ __forceinline__ bool gba_stop(const GbaDev& D) { return __hip_atomic_
 // linearizeOplus and the robust weight of every edge at the current estimate
 template <bool RIG>
 __global__ __launch_bounds__(GBA_NT) void k_gba_linearize(GbaDev D) {
-  if (D.lmi[GBA_DONE] || !D.lmi[GBA_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const int e = blockIdx.x * GBA_NT + threadIdx.x;
   if (e >= D.nE) return;
   const SE3 T = gba_load(D.pose + 7 * (size_t)D.eKF[e]);
@@ -165,7 +165,7 @@ __device__ __forceinline__ double gba_sum_jtr(const double* E, const int* list, 
 
 // Hpp, bp (42 lanes per block row), Hll, bl (12 per point), Hpl (18 per pair)
 __global__ __launch_bounds__(GBA_NT) void k_gba_assemble(GbaDev D) {
-  if (D.lmi[GBA_DONE] || !D.lmi[GBA_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   size_t gid = (size_t)blockIdx.x * GBA_NT + threadIdx.x;
   if (gid < (size_t)D.n * 42) {
     const int a = (int)(gid / 42), k = (int)(gid % 42), kf = D.rowKF[a];
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_assemble(GbaDev D) {
 // computeLambdaInit behind the first assembly.  One workgroup; a maximum has no order.
 __global__ __launch_bounds__(GBA_NT) void k_gba_maxdiag(GbaDev D) {
   __shared__ double sMax[GBA_NT];
-  if (D.lmi[GBA_DONE] || !D.lmi[GBA_LAMBDA0]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_LAMBDA0]) return;
   const int t = threadIdx.x;
   double m = 0;
   for (int i = t; i < 6 * D.n; i += GBA_NT) m = fmax(m, fabs(D.Hpp[(size_t)(i / 6) * 36 + (i % 6) * 7]));
@@ -207,13 +207,13 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_maxdiag(GbaDev D) {
     LmControl c = *D.lm;
     lm_begin(c, 0.0, sMax[0]);
     *D.lm = c;
-    D.lmi[GBA_LAMBDA0] = 0;
+    D.lmi[LMW_LAMBDA0] = 0;
   }
 }
 
 // Dinv per point; Hpl Dinv and Hpl Dinv bl per pair (a pair's lane inverts its point's block itself)
 __global__ __launch_bounds__(GBA_NT) void k_gba_dinv(GbaDev D) {
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int gid = blockIdx.x * GBA_NT + threadIdx.x;
   if (gid >= D.nMP + D.nPairs) return;
   const double lambda = D.lm->lambda;
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_dinv(GbaDev D) {
 
 // a chunk of an envelope block's contributions: sum of (Hpl_i1 Dinv) Hpl_i2^T, a lane per (chunk, entry), in point order
 __global__ __launch_bounds__(GBA_NT) void k_gba_schur(GbaDev D) {
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const size_t gid = (size_t)blockIdx.x * GBA_NT + threadIdx.x;
   if (gid >= (size_t)D.nChunks * 36) return;
   const int c = (int)(gid / 36), ent = (int)(gid % 36), r = ent / 6, cc = ent % 6;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_schur(GbaDev D) {
 
 // the reduced system: H = Hpp - the chunks' sums in order, b = bp - sum Hpl Dinv bl over the block row's pairs in point order
 __global__ __launch_bounds__(GBA_NT) void k_gba_schur_finish(GbaDev D) {
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const size_t gid = (size_t)blockIdx.x * GBA_NT + threadIdx.x;
   const size_t nH = (size_t)D.nBlocks * 36;
   if (gid < nH) {
@@ -279,215 +279,20 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_schur_finish(GbaDev D) {
   D.b[k] = D.bp[k] - acc;
 }
 
-// one line of S_ij -= L_ik (D_k L_jk^T): l = line r of L_ik, m = M_jk = L_jk D_k (row-major, in LDS)
-__device__ __forceinline__ void gba_line_minus(double* acc, const double* l, const double* m) {
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double s = 0;
-#pragma unroll
-    for (int p = 0; p < 6; ++p) s += l[p] * m[c * 6 + p];
-    acc[c] -= s;
-  }
-}
-// L_ij = S_ij L_jj^-T D_j^-1 for one line of a block below the diagonal (a: L_jj's strictly lower part); returns L_ij y_j
-__device__ __forceinline__ double gba_below_line(const double* s, const double (*a)[6], const double* dd, const double* yy, double* l) {
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double v = s[c];
-#pragma unroll
-    for (int p = 0; p < c; ++p) v -= (l[p] * dd[p]) * a[c][p];
-    l[c] = v / dd[c];
-  }
-  double dot = 0;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) dot += l[c] * yy[c];
-  return dot;
-}
-
-// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way.  One workgroup takes the block columns in sequence.
+// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way (envelope_ldlt.h).  One workgroup.  A zero or NaN pivot fails.
 __global__ __launch_bounds__(GBA_NT) void k_gba_factor(GbaDev D) {
-  __shared__ double sM[GBA_STAGE * 36];
-  __shared__ double sS[36];
-  if (D.lmi[GBA_DONE]) return;
-  const int t = threadIdx.x, n = D.n;
-  const double lambda = D.lm->lambda;
-  bool ok = true;
-  for (int i = t; i < 6 * n; i += GBA_NT) D.y[i] = D.b[i];
-  __threadfence_block();
-  __syncthreads();
-  for (int j = 0; j < n; ++j) {
-    const int fj = D.rowFirst[j];
-    const int cs = D.colStart[j];
-    const int nItems = (D.colStart[j + 1] - cs + 1) * 6;   // a lane per (row, line of its block); lines 0 .. 5 are the diagonal block's
-    const bool one = nItems <= GBA_PASS;                   // (the usual case: the lines stay in registers from the sums to the division)
-    const size_t rowJ = (size_t)D.rowOff[j];
-    const size_t diag = (rowJ + (j - fj)) * 36;
-    double yj[6];                                          // (final since the last column's barrier)
-#pragma unroll
-    for (int r = 0; r < 6; ++r) yj[r] = D.y[(size_t)j * 6 + r];
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    double* mine = nullptr;   // the line's place in the factor
-    int myRow = 0;
-    // ---- S_ij = H_ij - sum_k L_ik D_k L_jk^T, over the k both rows hold ----
-    for (int base = 0; base < nItems; base += GBA_PASS) {
-      const int item = base + t;
-      const bool valid = t < GBA_PASS && item < nItems;
-      int i = j, r = 0, fi = fj;
-      size_t rowI = rowJ;
-      if (valid) {
-        const int w = item / 6;
-        r = item - w * 6;
-        if (w) { i = D.colRows[cs + w - 1]; fi = D.rowFirst[i]; rowI = (size_t)D.rowOff[i]; }
-        const double* h = D.H + (rowI + (j - fi)) * 36 + r * 6;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) acc[c] = h[c] + ((i == j && c == r) ? lambda : 0.0);
-        mine = D.L + (rowI + (j - fi)) * 36 + r * 6;
-        myRow = i;
-      }
-      for (int c0 = fj; c0 < j; c0 += GBA_STAGE) {
-        const int c1 = min(c0 + GBA_STAGE, j);
-        if (base || c0 != fj) __syncthreads();   // (the column's first stage follows the last column's barrier)
-        for (int q = t; q < (c1 - c0) * 36; q += GBA_NT)   // M_jk = L_jk D_k
-          sM[q] = D.L[(rowJ + (c0 - fj)) * 36 + q] * D.d[(size_t)(c0 + q / 36) * 6 + q % 6];
-        __syncthreads();
-        if (valid) {
-          const double* lik = D.L + (rowI - fi) * 36 + r * 6;   // + 36 k: line r of L_ik
-          for (int k = max(c0, fi); k < c1; ++k) {
-            double l[6];
-#pragma unroll
-            for (int p = 0; p < 6; ++p) l[p] = lik[(size_t)k * 36 + p];
-            gba_line_minus(acc, l, sM + (k - c0) * 36);
-          }
-        }
-      }
-      if (valid) {
-        if (i == j) {
-#pragma unroll
-          for (int c = 0; c < 6; ++c) sS[r * 6 + c] = acc[c];
-        } else if (!one) {
-#pragma unroll
-          for (int c = 0; c < 6; ++c) mine[c] = acc[c];
-        }
-      }
-    }
-    if (!one) __threadfence_block();
-    __syncthreads();
-    // ---- the diagonal block, by every lane for itself: S_jj = L_jj D_j L_jj^T, and y_j = L_jj^-1 y_j ----
-    double a[6][6], dd[6], yy[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) a[r][c] = c <= r ? sS[r * 6 + c] : 0.0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      double dc = a[c][c];
-#pragma unroll
-      for (int p = 0; p < c; ++p) dc -= (a[c][p] * dd[p]) * a[c][p];
-      dd[c] = dc;
-      ok = ok && dc != 0 && dc == dc;   // a zero or NaN pivot: the factorisation has failed
-#pragma unroll
-      for (int r = c + 1; r < 6; ++r) {
-        double v = a[r][c];
-#pragma unroll
-        for (int p = 0; p < c; ++p) v -= (a[r][p] * dd[p]) * a[c][p];
-        a[r][c] = v / dc;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      double v = yj[r];
-#pragma unroll
-      for (int p = 0; p < r; ++p) v -= a[r][p] * yy[p];
-      yy[r] = v;
-    }
-    if (!ok) break;   // (the same for every lane)
-    if (t < 36) {
-      double v = 0.0;   // (written out: no array is indexed by a run-time value)
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-          if (t == r * 6 + c) v = c < r ? a[r][c] : (c == r ? 1.0 : 0.0);
-      D.L[diag + t] = v;
-    }
-    if (t >= 64 && t < 70) {
-      double dv = 0.0, yv = 0.0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-        if (t - 64 == r) { dv = dd[r]; yv = yy[r]; }
-      D.d[(size_t)j * 6 + t - 64] = dv;
-      D.y[(size_t)j * 6 + t - 64] = yv;
-    }
-    // ---- the rows below: L_ij = S_ij L_jj^-T D_j^-1, and y_i -= L_ij y_j ----
-    if (one) {
-      if (t >= 6 && t < nItems) {
-        double l[6];
-        const double dot = gba_below_line(acc, a, dd, yy, l);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) mine[c] = l[c];
-        D.y[(size_t)myRow * 6 + (t % 6)] -= dot;
-      }
-    } else {
-      for (int item = 6 + t; item < nItems; item += GBA_NT) {
-        const int w = item / 6, r = item - w * 6;
-        const int i = D.colRows[cs + w - 1];
-        double* o = D.L + ((size_t)D.rowOff[i] + (j - D.rowFirst[i])) * 36 + r * 6;
-        double s[6], l[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) s[c] = o[c];
-        const double dot = gba_below_line(s, a, dd, yy, l);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) o[c] = l[c];
-        D.y[(size_t)i * 6 + r] -= dot;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  if (t == 0) D.lmi[GBA_OK2] = ok ? 1 : 0;
+  if (D.lmi[LMW_DONE]) return;
+  const bool ok = envelope_factor<6, GBA_NT, GBA_STAGE, 1, false>(envelope_sys(D), D.lm->lambda);
+  if (threadIdx.x == 0) D.lmi[LMW_OK2] = ok ? 1 : 0;
 }
 
-// x = L^-T D^-1 y: row i, once final, is taken out of the rows above it; then the trial poses SE3Quat::exp(x_v) * T_v.  One workgroup.
-// A failed factorisation leaves the step zero.
+// x = L^-T D^-1 y (envelope_ldlt.h), then the trial poses SE3Quat::exp(x_v) * T_v.  One workgroup.  A failed factorisation leaves the
+// step zero.
 __global__ __launch_bounds__(GBA_NT) void k_gba_backsub(GbaDev D) {
-  __shared__ double sx[6];
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x, n = D.n;
-  if (D.lmi[GBA_OK2]) {
-    for (int i = t; i < 6 * n; i += GBA_NT) D.x[i] = D.y[i] / D.d[i];
-    __threadfence_block();
-    __syncthreads();
-    for (int i = n - 1; i >= 0; --i) {
-      const int fi = D.rowFirst[i];
-      const size_t rowI = (size_t)D.rowOff[i];
-      if (t == 0) {   // x_i = L_ii^-T z_i
-        const double* Ld = D.L + ((size_t)D.rowOff[i + 1] - 1) * 36;
-        double z[6], xx[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) z[r] = D.x[(size_t)i * 6 + r];
-#pragma unroll
-        for (int r = 5; r >= 0; --r) {
-          double v = z[r];
-#pragma unroll
-          for (int p = r + 1; p < 6; ++p) v -= Ld[p * 6 + r] * xx[p];
-          xx[r] = v;
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) { sx[r] = xx[r]; D.x[(size_t)i * 6 + r] = xx[r]; }
-      }
-      __syncthreads();
-      const int cnt = (i - fi) * 6;
-      for (int item = t; item < cnt; item += GBA_NT) {
-        const int kk = item / 6, c = item - kk * 6;
-        const double* lik = D.L + (rowI + kk) * 36;
-        double dot = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) dot += lik[r * 6 + c] * sx[r];
-        D.x[(size_t)(fi + kk) * 6 + c] -= dot;
-      }
-      __threadfence_block();
-      __syncthreads();
-    }
+  if (D.lmi[LMW_OK2]) {
+    envelope_backsub<6, GBA_NT>(envelope_sys(D));
   } else {
     for (int i = t; i < 6 * n; i += GBA_NT) D.x[i] = 0.0;
     __threadfence_block();
@@ -511,11 +316,11 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_backsub(GbaDev D) {
 
 // xl = Dinv (bl - Hpl^T xp) over the point's pairs in order, and the trial points
 __global__ __launch_bounds__(GBA_NT) void k_gba_points(GbaDev D) {
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int m = blockIdx.x * GBA_NT + threadIdx.x;
   if (m >= D.nMP) return;
   double xl[3] = {0, 0, 0};
-  if (D.lmi[GBA_OK2] && D.mpStart[m + 1] > D.mpStart[m]) {
+  if (D.lmi[LMW_OK2] && D.mpStart[m + 1] > D.mpStart[m]) {
     double cl[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) cl[j] = D.bl[(size_t)m * 3 + j];
@@ -537,7 +342,7 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_points(GbaDev D) {
 
 // computeError and the robust chi2 of every edge at the trial estimate (trial != 0) or at the current one
 __global__ __launch_bounds__(GBA_NT) void k_gba_errors(GbaDev D, int trial) {
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int e = blockIdx.x * GBA_NT + threadIdx.x;
   if (e >= D.nE) return;
   const double *pose = trial ? D.poseT : D.pose, *pt = trial ? D.ptT : D.pt;
@@ -549,28 +354,13 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_errors(GbaDev D, int trial) {
   D.chiE[e] = delta > 0 ? huber(delta, c, &w) : c;
 }
 
-// sum of n values in a fixed order: lane t adds its slice of ceil(n / GBA_NT) consecutive values, lane 0 adds the lanes' sums
-template <class Term>
-__device__ double gba_ordered_sum(double* buf, int n, Term&& term) {
-  const int per = (n + GBA_NT - 1) / GBA_NT, t = threadIdx.x;
-  double s = 0;
-  for (int i = t * per; i < min((t + 1) * per, n); ++i) s += term(i);
-  __syncthreads();
-  buf[t] = s;
-  __syncthreads();
-  double acc = 0;
-  if (t == 0)
-    for (int q = 0; q < GBA_NT; ++q) acc += buf[q];
-  return acc;   // (lane 0's)
-}
-
 // init != 0: behind the first computeActiveErrors; else g2o's decision after a trial (lm_control.h).  One workgroup.
 __global__ __launch_bounds__(GBA_NT) void k_gba_decide(GbaDev D, int init) {
   __shared__ double buf[GBA_NT];
   __shared__ int sKeep;
-  if (D.lmi[GBA_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x;
-  const double chi = gba_ordered_sum(buf, D.nE, [&](int e) { return D.chiE[e]; });
+  const double chi = lm_sum_of_lane_slices<GBA_NT>(buf, D.nE, [&](int e) { return D.chiE[e]; });
   LmControl c = *D.lm;
   if (init) {
     if (t == 0) {
@@ -578,33 +368,15 @@ __global__ __launch_bounds__(GBA_NT) void k_gba_decide(GbaDev D, int init) {
       lm_iteration(c, chi);   // (lambda comes behind the first assembly: k_gba_maxdiag)
       *D.lm = c;
       D.chi2[0] = chi; D.chi2[1] = chi;
-      D.lmi[GBA_REBUILD] = 1; D.lmi[GBA_ITS] = 0; D.lmi[GBA_TRIALS] = 0; D.lmi[GBA_OK2] = 1; D.lmi[GBA_LAMBDA0] = 1; D.lmi[GBA_DONE] = stop;
+      D.lmi[LMW_REBUILD] = 1; D.lmi[LMW_ITS] = 0; D.lmi[LMW_TRIALS] = 0; D.lmi[LMW_OK2] = 1; D.lmi[LMW_LAMBDA0] = 1; D.lmi[LMW_DONE] = stop;
       if (stop) __hip_atomic_store(D.lmHost + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     return;
   }
   const double lambda = c.lambda;
-  const double gainP = gba_ordered_sum(buf, 6 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.bp[i]); });   // computeScale()
-  const double gainL = gba_ordered_sum(buf, 3 * D.nMP, [&](int i) { return D.xl[i] * (lambda * D.xl[i] + D.bl[i]); });
-  if (t == 0) {
-    bool again = false;
-    const bool keep = lm_trial(c, chi, D.lmi[GBA_OK2] != 0, gainP + gainL, &again);
-    const bool stop = gba_stop(D);
-    if (stop) again = false;
-    int its = D.lmi[GBA_ITS], done = 0, rebuild = 0;
-    const int trials = D.lmi[GBA_TRIALS] + 1;
-    if (!again) {
-      ++its;
-      done = (lm_iteration_done(c) || its >= D.maxIts || stop) ? 1 : 0;
-      if (!done) { lm_iteration(c, c.currentChi); rebuild = 1; }
-    }
-    *D.lm = c;
-    D.chi2[1] = c.currentChi;
-    D.lmi[GBA_ITS] = its; D.lmi[GBA_TRIALS] = trials; D.lmi[GBA_REBUILD] = rebuild; D.lmi[GBA_DONE] = done;
-    sKeep = keep ? 1 : 0;
-    __hip_atomic_store(D.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(D.lmHost + 0, trials, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided trials: the host queues trial k + 2 when it sees k
-  }
+  const double gainP = lm_sum_of_lane_slices<GBA_NT>(buf, 6 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.bp[i]); });   // computeScale()
+  const double gainL = lm_sum_of_lane_slices<GBA_NT>(buf, 3 * D.nMP, [&](int i) { return D.xl[i] * (lambda * D.xl[i] + D.bl[i]); });
+  if (t == 0) sKeep = lm_decide_trial(c, chi, D.lmi[LMW_OK2] != 0, gainP + gainL, gba_stop(D), D.maxIts, D.lm, D.chi2, D.lmi, D.lmHost) ? 1 : 0;
   __syncthreads();
   if (sKeep) {
     for (int i = t; i < 7 * D.nKF; i += GBA_NT) D.pose[i] = D.poseT[i];
@@ -756,7 +528,7 @@ int gba_run(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, i
   D.lmHost = hostwDev;
   const volatile uint8_t* userStop = stopFlag;
   auto forwardStop = [&]() { if (userStop && *userStop) __atomic_store_n(hostw + 2, 1, __ATOMIC_RELEASE); };   // optimizer.setForceStopFlag(pbStopFlag) (:78)
-  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 2, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  reset_lm_words(hostw, 2, hostw + 2);
   forwardStop();
   MORB_HIP_CHECK(hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st));   // the one upload
   // the workspace is reused from call to call: what the first kernels expect to find zero is cleared
@@ -788,11 +560,7 @@ int gba_run(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, i
     hipLaunchKernelGGL(k_gba_decide, dim3(1), dim3(GBA_NT), 0, st, D, 0);
     if (hipGetLastError() != hipSuccess) { set_error("BundleAdjustment: a trial's launch failed"); return (int)MORB_ERR_HIP; }
     return (int)MORB_OK;
-  }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("BundleAdjustment: %s while waiting for the LM decision", hipGetErrorString(e));
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, forwardStop);
+  }, [&]() { return stream_look(st, "BundleAdjustment"); }, forwardStop);
   if (q < 0) return MORB_ERR_HIP;
   int hi[8];
   double c2[2];
@@ -804,7 +572,7 @@ int gba_run(morb_optimizer* o, int nKF, float* kfPose, const uint8_t* kfFixed, i
   // (:276-361) the keyframes of the system and the points that carry an edge; everything else keeps its bytes
   for (int v = 0; v < nKF; ++v) if (P.col[v] >= 0) for (int k = 0; k < 7; ++k) kfPose[7 * v + k] = (float)pose[(size_t)7 * v + k];
   for (int m = 0; m < nMP; ++m) if (mpStart[m + 1] > mpStart[m]) for (int k = 0; k < 3; ++k) mpPos[3 * m + k] = (float)pt[(size_t)3 * m + k];
-  stats4[0] = hi[GBA_ITS]; stats4[1] = hi[GBA_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
+  stats4[0] = hi[LMW_ITS]; stats4[1] = hi[LMW_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
   chi2[0] = c2[0]; chi2[1] = c2[1];
   return MORB_OK;
 }

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "ba_host.h"
 #include "common.h"
 #include "hip_owned.h"
 
@@ -99,6 +100,22 @@ inline int grow_beyond_lds(DeviceGrow& b, int nprob, int cap, int ldsN, int word
 // the stream a call runs on: the caller's, or the handle's own when the caller passes none
 template <class Handle>
 inline hipStream_t stream_or_own(const Handle* h, void* stream) { return stream ? (hipStream_t)stream : (hipStream_t)h->stream; }
+
+// The host's two steps around ba_host.h's lm_slot_queue, which is compiled without HIP and therefore cannot hold them.
+// Before a solve's first launch: the mapped LM words are cleared — `stop`, the word the caller's stop flag is forwarded to (null: the
+// optimiser has none), and the mirror hostw[0 .. words): [0] decided trials, [1] done (last, with release), then what the unit keeps there.
+inline void reset_lm_words(int* hostw, int words, int* stop) {
+  if (stop) __atomic_store_n(stop, 0, __ATOMIC_RELAXED);
+  for (int k = 0; k < words; ++k)
+    if (k != 1) __atomic_store_n(hostw + k, 0, __ATOMIC_RELAXED);
+  __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+}
+// The queue's look(): is everything queued on st done?  A failed stream leaves its error, under the optimiser's name `who`.
+inline StreamLook stream_look(hipStream_t st, const char* who) {
+  const hipError_t e = hipStreamQuery(st);
+  if (e != hipSuccess && e != hipErrorNotReady) set_error("%s: %s while waiting for the LM decision", who, hipGetErrorString(e));
+  return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
+}
 
 }  // namespace morb
 

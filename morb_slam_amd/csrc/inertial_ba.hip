@@ -784,8 +784,7 @@ static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLa
   D.optIt = plan.iterations; D.eraseChi2Only = plan.eraseChi2Only ? 1 : 0;
   D.stopWord = stopFlag ? hostwDev + 2 : nullptr;
   auto forwardStop = [&]() { if (stopFlag && *stopFlag) __atomic_store_n(hostw + 2, 1, __ATOMIC_RELEASE); };
-  __atomic_store_n(hostw + 2, 0, __ATOMIC_RELAXED);
-  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  reset_lm_words(hostw, 2, hostw + 2);
   forwardStop();
   hipLaunchKernelGGL(k_iba_lm_init, dim3(1), dim3(1), 0, st, D, chi, plan.lambda0);
   const int beginGrid = div_up((int)std::max<size_t>(std::max<size_t>(std::max<size_t>(nS, nPts), (size_t)nMP * 8 /* k_iba_points: eight lanes per point */), std::max<size_t>((size_t)P * P, (size_t)18 * nE)), 256);
@@ -808,11 +807,7 @@ static int iba_lm_loop(morb_optimizer* o, hipStream_t st, IbaDev& D, const IbaLa
     hipLaunchKernelGGL(k_iba_errors, dim3(div_up(nE + nI, 256)), dim3(256), 0, st, D, 1);
     if (hipGetLastError() != hipSuccess) { set_error("%s trial failed", plan.who); return (int)MORB_ERR_HIP; }
     return (int)MORB_OK;
-  }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("%s: device error while waiting for the LM decision", plan.who);
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, forwardStop);   // (LocalInertialBA's caller has no flag to forward)
+  }, [&]() { return stream_look(st, plan.who); }, forwardStop);   // (LocalInertialBA's caller has no flag to forward)
   if (q < 0) return MORB_ERR_HIP;
   // (a queue that ran out of slots without `done` is drained by the read-back below, before the words are reset again)
   hipLaunchKernelGGL(k_iba_end, dim3(div_up((int)std::max<size_t>(nS, nPts), 256)), dim3(256), 0, st, D);

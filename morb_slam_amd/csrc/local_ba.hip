@@ -1288,14 +1288,10 @@ static void ba_launch_solve_phases(const morb_ba_problem* p, hipStream_t st) {
 template <class LaunchSlot, class LaunchFinish>
 static int ba_queue_solve(morb_ba_problem* p, hipStream_t st, int maxSlots, const char* who, LaunchSlot&& launchSlot, LaunchFinish&& launchFinish) {
   auto forwardStop = [&]() { if (p->userStop && *p->userStop) __atomic_store_n(p->h_stop + 1, 1, __ATOMIC_RELEASE); };
-  __atomic_store_n(p->h_stop + 1, 0, __ATOMIC_RELAXED);
-  for (int k = 4; k < 8; ++k) __atomic_store_n(p->h_stop + k, 0, __ATOMIC_RELAXED);
+  reset_lm_words(p->h_stop + 4, 4, p->h_stop + 1);   // the mirror is h_stop[4 .. 7]: [4] decided, [5] done, [6] iterations, [7] trials; [1] the forwarded stop flag
   forwardStop();
-  const int q = lm_slot_queue(maxSlots, p->h_stop + 4, p->h_stop + 5, [&](int slot) { launchSlot(slot); MORB_HIP_CHECK(hipGetLastError()); return MORB_OK; }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("%s: %s while waiting for the LM decision", who, hipGetErrorString(e));
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, forwardStop);
+  const int q = lm_slot_queue(maxSlots, p->h_stop + 4, p->h_stop + 5, [&](int slot) { launchSlot(slot); MORB_HIP_CHECK(hipGetLastError()); return MORB_OK; },
+                              [&]() { return stream_look(st, who); }, forwardStop);
   if (q < 0) return MORB_ERR_HIP;
   launchFinish();
   MORB_HIP_CHECK(hipGetLastError());

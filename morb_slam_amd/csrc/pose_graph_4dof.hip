@@ -14,13 +14,11 @@
 //     summed in edge insertion order over the lists of envelope_plan.h: no floating-point atomics.
 //   * k_pg4_maxdiag: computeLambdaInit (optimization_algorithm_levenberg.cpp:171-185).  There is no setUserLambdaInit in this optimiser:
 //     the first lambda is 1e-5 * max |H_jj| of the first assembled system, taken behind the first assembly and before the first factorisation.
-//   * k_pg4_factor: the block LDL^T over the envelope of the 4 x 4 block rows, left-looking by column in one workgroup, as
-//     essential_graph.hip's.  A block is 128 bytes: the column's own row, scaled by D, is staged in LDS PG4_STAGE blocks at a time (a
-//     whole row of any graph below that many vertices), 64 covering rows take one pass of the workgroup (a lane per row and line), and every
-//     lane factorises the 4 x 4 diagonal block itself instead of waiting for one lane's: three barriers per column.
-//   * k_pg4_backsub: the backward substitution, and the trial states UpdateW(x) behind it.
-//   * k_pg4_errors / k_pg4_decide: chi2 = e^T Omega e per edge, summed in edge order; g2o's Levenberg-Marquardt decisions (lm_control.h),
-//     optimize(20), no stop flag, the host queueing trials through ba_host.h's lm_slot_queue.
+//   * k_pg4_factor / k_pg4_backsub: the block LDL^T over the envelope of the 4 x 4 block rows and both substitutions (envelope_ldlt.h,
+//     which describes the schedule).  A block is 128 bytes: PG4_STAGE of them are staged at a time, 64 covering rows take one pass, four
+//     blocks' loads are kept in flight.  A pivot has to be positive.  The trial states UpdateW(x) follow the backward substitution.
+//   * k_pg4_errors / k_pg4_decide: chi2 = e^T Omega e per edge, summed in edge order; g2o's Levenberg-Marquardt decisions (lm_control.h:
+//     lm_decide_trial), optimize(20), no stop flag, the host queueing trials through ba_host.h's lm_slot_queue.
 //   * k_pg4_finish: the point correction of :5451-5470.
 // A vertex without an edge is not in g2o's active set: it is not in the system and keeps its bytes.
 #include <hip/hip_runtime.h>
@@ -32,6 +30,7 @@
 
 #include "ba_host.h"
 #include "common.h"
+#include "envelope_ldlt.h"
 #include "envelope_plan.h"
 #include "handles.h"
 #include "inertial_device.h"
@@ -43,12 +42,11 @@ namespace {
 using namespace morb;
 
 constexpr int PG4_NT = 256;                          // lanes of a workgroup: 64 covering rows of 4 lines in one pass of the factorisation
-constexpr int PG4_STAGE = 128;                       // blocks of the column's own row staged in LDS at a time (16 KiB)
+constexpr int PG4_STAGE = 128;                       // blocks of the column's own row envelope_factor stages in LDS at a time (16 KiB)
 constexpr size_t PG4_MAX_BLOCKS = (size_t)1 << 22;   // envelope blocks a handle may grow to
 constexpr int PG4_SUM = 2048;                        // values staged in LDS per pass of an ordered sum
 constexpr int PG4_STATE = 28;                        // doubles of a vertex state: Rcw 0..8, tcw 9..11, DR 12..20, twb 21..23, its 24
 constexpr double PG4_DELTA = 1e-9;                   // the step of g2o's numeric Jacobians
-enum { PG4_DONE = 0, PG4_REBUILD, PG4_ITS, PG4_TRIALS, PG4_OK2, PG4_LAMBDA0 };
 
 struct Pg4Dev {
   int nKF, nE, n, nBlocks, nMP, maxIts;
@@ -68,7 +66,7 @@ struct Pg4Dev {
   double *b, *y, *x, *d;     // [4 n] right-hand side, work vector, solution, D of the factorisation
   LmControl* lm;
   double* chi2;              // [2] active chi2 before and after
-  int* lmi;                  // [8] PG4_*
+  int* lmi;                  // [8] LMW_* (lm_control.h)
   int* lmHost;               // mapped host words: [0] decided trials, [1] done
   float* mp;                 // [nMP][3]
   const int* mpRef;          // [nMP]
@@ -123,7 +121,7 @@ __device__ __forceinline__ void pg4_load(const double* p, double* s) {
 
 // linearizeOplus of every edge at S: lanes 0 .. 3 of an edge's 16 take the columns of vertex 0, 4 .. 7 those of vertex 1, 8 the error
 __global__ __launch_bounds__(PG4_NT) void k_pg4_linearize(Pg4Dev D) {
-  if (D.lmi[PG4_DONE] || !D.lmi[PG4_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const int gid = blockIdx.x * PG4_NT + threadIdx.x;
   const int e = gid >> 4, k = gid & 15;
   if (e >= D.nE || k >= 9) return;
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(PG4_NT) void k_pg4_linearize(Pg4Dev D) {
 
 // H in the envelope and b, every entry summed over its contributions in edge order
 __global__ __launch_bounds__(PG4_NT) void k_pg4_assemble(Pg4Dev D) {
-  if (D.lmi[PG4_DONE] || !D.lmi[PG4_REBUILD]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_REBUILD]) return;
   const size_t gid = (size_t)blockIdx.x * PG4_NT + threadIdx.x;
   const size_t nH = (size_t)D.nBlocks * 16;
   if (gid < nH) {
@@ -198,7 +196,7 @@ __global__ __launch_bounds__(PG4_NT) void k_pg4_assemble(Pg4Dev D) {
 // computeLambdaInit behind the first assembly: 1e-5 * max |H_jj| over the vertices of the system.  One workgroup; a maximum has no order.
 __global__ __launch_bounds__(PG4_NT) void k_pg4_maxdiag(Pg4Dev D) {
   __shared__ double sMax[PG4_NT];
-  if (D.lmi[PG4_DONE] || !D.lmi[PG4_LAMBDA0]) return;
+  if (D.lmi[LMW_DONE] || !D.lmi[LMW_LAMBDA0]) return;
   const int t = threadIdx.x;
   double m = 0;
   for (int i = t; i < 4 * D.n; i += PG4_NT) {
@@ -215,229 +213,23 @@ __global__ __launch_bounds__(PG4_NT) void k_pg4_maxdiag(Pg4Dev D) {
     LmControl c = *D.lm;
     lm_begin(c, 0.0, sMax[0]);
     *D.lm = c;
-    D.lmi[PG4_LAMBDA0] = 0;
+    D.lmi[LMW_LAMBDA0] = 0;
   }
 }
 
-// one line of S_ij -= L_ik (D_k L_jk^T): l = line r of L_ik, m = M_jk = L_jk D_k (row-major, in LDS)
-__device__ __forceinline__ void pg4_line_minus(double* acc, const double* l, const double* m) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    double s = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) s += l[p] * m[c * 4 + p];
-    acc[c] -= s;
-  }
-}
-// L_ij = S_ij L_jj^-T D_j^-1 for one line of a block below the diagonal (a: L_jj's strictly lower part); returns L_ij y_j
-__device__ __forceinline__ double pg4_below_line(const double* s, const double (*a)[4], const double* dd, const double* yy, double* l) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    double v = s[c];
-#pragma unroll
-    for (int p = 0; p < c; ++p) v -= (l[p] * dd[p]) * a[c][p];
-    l[c] = v / dd[c];
-  }
-  double dot = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) dot += l[c] * yy[c];
-  return dot;
-}
-
-// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way.  One workgroup takes the block columns in sequence.
+// H + lambda I = L D L^T over the envelope, and y = L^-1 b on the way (envelope_ldlt.h).  One workgroup.  A pivot has to be positive: the
+// reference's Cholesky fails otherwise.
 __global__ __launch_bounds__(PG4_NT) void k_pg4_factor(Pg4Dev D) {
-  __shared__ double sM[PG4_STAGE * 16];
-  __shared__ double sS[16];
-  if (D.lmi[PG4_DONE]) return;
-  const int t = threadIdx.x, n = D.n;
-  const double lambda = D.lm->lambda;
-  bool ok = true;
-  for (int i = t; i < 4 * n; i += PG4_NT) D.y[i] = D.b[i];
-  __threadfence_block();
-  __syncthreads();
-  for (int j = 0; j < n; ++j) {
-    const int fj = D.rowFirst[j];
-    const int cs = D.colStart[j];
-    const int nItems = (D.colStart[j + 1] - cs + 1) * 4;   // a lane per (row, line of its block); lines 0 .. 3 are the diagonal block's
-    const bool one = nItems <= PG4_NT;                     // (the usual case: the lines stay in registers from the sums to the division)
-    const size_t rowJ = (size_t)D.rowOff[j];
-    const size_t diag = (rowJ + (j - fj)) * 16;
-    double yj[4];                                          // (final since the last column's barrier)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) yj[r] = D.y[(size_t)j * 4 + r];
-    double acc[4] = {0, 0, 0, 0};
-    double* mine = nullptr;   // the line's place in the factor
-    int myRow = 0;
-    // ---- S_ij = H_ij - sum_k L_ik D_k L_jk^T, over the k both rows hold ----
-    for (int base = 0; base < nItems; base += PG4_NT) {
-      const int item = base + t;
-      const bool valid = item < nItems;
-      int i = j, r = 0, fi = fj;
-      size_t rowI = rowJ;
-      if (valid) {
-        const int w = item >> 2;
-        r = item & 3;
-        if (w) { i = D.colRows[cs + w - 1]; fi = D.rowFirst[i]; rowI = (size_t)D.rowOff[i]; }
-        const double* h = D.H + (rowI + (j - fi)) * 16 + r * 4;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = h[c] + ((i == j && c == r) ? lambda : 0.0);
-        mine = D.L + (rowI + (j - fi)) * 16 + r * 4;
-        myRow = i;
-      }
-      for (int c0 = fj; c0 < j; c0 += PG4_STAGE) {
-        const int c1 = min(c0 + PG4_STAGE, j);
-        if (base || c0 != fj) __syncthreads();   // (the column's first stage follows the last column's barrier)
-        for (int q = t; q < (c1 - c0) * 16; q += PG4_NT)   // M_jk = L_jk D_k
-          sM[q] = D.L[(rowJ + (c0 - fj)) * 16 + q] * D.d[(size_t)(c0 + (q >> 4)) * 4 + (q & 3)];
-        __syncthreads();
-        if (valid) {
-          const double* lik = D.L + (rowI - fi) * 16 + r * 4;   // + 16 k: line r of L_ik
-          int k = max(c0, fi);
-          for (; k + 4 <= c1; k += 4) {   // four blocks' loads in flight
-            double l[4][4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-              for (int p = 0; p < 4; ++p) l[u][p] = lik[(size_t)(k + u) * 16 + p];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) pg4_line_minus(acc, l[u], sM + (k + u - c0) * 16);
-          }
-          for (; k < c1; ++k) {
-            double l[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) l[p] = lik[(size_t)k * 16 + p];
-            pg4_line_minus(acc, l, sM + (k - c0) * 16);
-          }
-        }
-      }
-      if (valid) {
-        if (i == j) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) sS[r * 4 + c] = acc[c];
-        } else if (!one) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) mine[c] = acc[c];
-        }
-      }
-    }
-    if (!one) __threadfence_block();
-    __syncthreads();
-    // ---- the diagonal block, by every lane for itself: S_jj = L_jj D_j L_jj^T, and y_j = L_jj^-1 y_j ----
-    double a[4][4], dd[4], yy[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) a[r][c] = c <= r ? sS[r * 4 + c] : 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      double dc = a[c][c];
-#pragma unroll
-      for (int p = 0; p < c; ++p) dc -= (a[c][p] * dd[p]) * a[c][p];
-      dd[c] = dc;
-      ok = ok && dc > 0;
-#pragma unroll
-      for (int r = c + 1; r < 4; ++r) {
-        double v = a[r][c];
-#pragma unroll
-        for (int p = 0; p < c; ++p) v -= (a[r][p] * dd[p]) * a[c][p];
-        a[r][c] = v / dc;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double v = yj[r];
-#pragma unroll
-      for (int p = 0; p < r; ++p) v -= a[r][p] * yy[p];
-      yy[r] = v;
-    }
-    if (!ok) break;   // (the same for every lane)
-    if (t < 16) {
-      double v = 0.0;   // (written out: no array is indexed by a run-time value)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (t == r * 4 + c) v = c < r ? a[r][c] : (c == r ? 1.0 : 0.0);
-      D.L[diag + t] = v;
-    }
-    if (t >= 64 && t < 68) {
-      double dv = 0.0, yv = 0.0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (t - 64 == r) { dv = dd[r]; yv = yy[r]; }
-      D.d[(size_t)j * 4 + t - 64] = dv;
-      D.y[(size_t)j * 4 + t - 64] = yv;
-    }
-    // ---- the rows below: L_ij = S_ij L_jj^-T D_j^-1, and y_i -= L_ij y_j ----
-    if (one) {
-      if (t >= 4 && t < nItems) {
-        double l[4];
-        const double dot = pg4_below_line(acc, a, dd, yy, l);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) mine[c] = l[c];
-        D.y[(size_t)myRow * 4 + (t & 3)] -= dot;
-      }
-    } else {
-      for (int item = 4 + t; item < nItems; item += PG4_NT) {
-        const int w = item >> 2, r = item & 3;
-        const int i = D.colRows[cs + w - 1];
-        double* o = D.L + ((size_t)D.rowOff[i] + (j - D.rowFirst[i])) * 16 + r * 4;
-        double s[4], l[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s[c] = o[c];
-        const double dot = pg4_below_line(s, a, dd, yy, l);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o[c] = l[c];
-        D.y[(size_t)i * 4 + r] -= dot;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  if (t == 0) D.lmi[PG4_OK2] = ok ? 1 : 0;
+  if (D.lmi[LMW_DONE]) return;
+  const bool ok = envelope_factor<4, PG4_NT, PG4_STAGE, 4, true>(envelope_sys(D), D.lm->lambda);
+  if (threadIdx.x == 0) D.lmi[LMW_OK2] = ok ? 1 : 0;
 }
 
-// x = L^-T D^-1 y: row i, once final, is taken out of the rows above it; then the trial states UpdateW(x_v).  One workgroup.
+// x = L^-T D^-1 y (envelope_ldlt.h), then the trial states UpdateW(x_v).  One workgroup.
 __global__ __launch_bounds__(PG4_NT) void k_pg4_backsub(Pg4Dev D) {
-  __shared__ double sx[4];
-  if (D.lmi[PG4_DONE]) return;
-  const int t = threadIdx.x, n = D.n;
-  if (D.lmi[PG4_OK2]) {
-    for (int i = t; i < 4 * n; i += PG4_NT) D.x[i] = D.y[i] / D.d[i];
-    __threadfence_block();
-    __syncthreads();
-    for (int i = n - 1; i >= 0; --i) {
-      const int fi = D.rowFirst[i];
-      const size_t rowI = (size_t)D.rowOff[i];
-      if (t == 0) {   // x_i = L_ii^-T z_i
-        const double* Ld = D.L + ((size_t)D.rowOff[i + 1] - 1) * 16;
-        double z[4], xx[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z[r] = D.x[(size_t)i * 4 + r];
-#pragma unroll
-        for (int r = 3; r >= 0; --r) {
-          double v = z[r];
-#pragma unroll
-          for (int p = r + 1; p < 4; ++p) v -= Ld[p * 4 + r] * xx[p];
-          xx[r] = v;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { sx[r] = xx[r]; D.x[(size_t)i * 4 + r] = xx[r]; }
-      }
-      __syncthreads();
-      const int cnt = (i - fi) * 4;
-      for (int item = t; item < cnt; item += PG4_NT) {
-        const int kk = item >> 2, c = item & 3;
-        const double* lik = D.L + (rowI + kk) * 16;
-        double dot = 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dot += lik[r * 4 + c] * sx[r];
-        D.x[(size_t)(fi + kk) * 4 + c] -= dot;
-      }
-      __threadfence_block();
-      __syncthreads();
-    }
-  }
+  if (D.lmi[LMW_DONE]) return;
+  const int t = threadIdx.x;
+  if (D.lmi[LMW_OK2]) envelope_backsub<4, PG4_NT>(envelope_sys(D));
   // ---- the trial states (a failed factorisation leaves x as it was: g2o still applies it) ----
   for (int v = t; v < D.nKF; v += PG4_NT) {
     const int a = D.col[v];
@@ -456,7 +248,7 @@ __global__ __launch_bounds__(PG4_NT) void k_pg4_backsub(Pg4Dev D) {
 
 // computeError of every edge at the trial states (trial != 0) or at S
 __global__ __launch_bounds__(PG4_NT) void k_pg4_errors(Pg4Dev D, int trial) {
-  if (D.lmi[PG4_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int e = blockIdx.x * PG4_NT + threadIdx.x;
   if (e >= D.nE) return;
   const double* X = trial ? D.T : D.S;
@@ -468,57 +260,26 @@ __global__ __launch_bounds__(PG4_NT) void k_pg4_errors(Pg4Dev D, int trial) {
   D.chiE[e] = chi;
 }
 
-// sum of n values in index order: the workgroup stages them in LDS, lane 0 adds.  term(i) is evaluated by every lane.
-template <class Term>
-__device__ double pg4_ordered_sum(double* buf, int n, Term&& term) {
-  double acc = 0;
-  for (int base = 0; base < n; base += PG4_SUM) {
-    const int m = min(PG4_SUM, n - base);
-    for (int q = threadIdx.x; q < m; q += PG4_NT) buf[q] = term(base + q);
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int q = 0; q < m; ++q) acc += buf[q];
-    __syncthreads();
-  }
-  return acc;   // (lane 0's)
-}
-
 // init != 0: behind the first computeActiveErrors; else g2o's decision after a trial (lm_control.h).  One workgroup.
 __global__ __launch_bounds__(PG4_NT) void k_pg4_decide(Pg4Dev D, int init) {
   __shared__ double buf[PG4_SUM];
   __shared__ int sKeep;
-  if (D.lmi[PG4_DONE]) return;
+  if (D.lmi[LMW_DONE]) return;
   const int t = threadIdx.x;
-  const double chi = pg4_ordered_sum(buf, D.nE, [&](int e) { return D.chiE[e]; });
+  const double chi = lm_sum_in_index_order<PG4_NT, PG4_SUM>(buf, D.nE, [&](int e) { return D.chiE[e]; });
   LmControl c = *D.lm;
   if (init) {
     if (t == 0) {
       lm_iteration(c, chi);   // (lambda comes behind the first assembly: k_pg4_maxdiag)
       *D.lm = c;
       D.chi2[0] = chi; D.chi2[1] = chi;
-      D.lmi[PG4_REBUILD] = 1; D.lmi[PG4_ITS] = 0; D.lmi[PG4_TRIALS] = 0; D.lmi[PG4_OK2] = 1; D.lmi[PG4_LAMBDA0] = 1;
+      D.lmi[LMW_REBUILD] = 1; D.lmi[LMW_ITS] = 0; D.lmi[LMW_TRIALS] = 0; D.lmi[LMW_OK2] = 1; D.lmi[LMW_LAMBDA0] = 1;
     }
     return;
   }
   const double lambda = c.lambda;
-  const double gain = pg4_ordered_sum(buf, 4 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b[i]); });   // computeScale()
-  if (t == 0) {
-    bool again = false;
-    const bool keep = lm_trial(c, chi, D.lmi[PG4_OK2] != 0, gain, &again);
-    int its = D.lmi[PG4_ITS], done = 0, rebuild = 0;
-    const int trials = D.lmi[PG4_TRIALS] + 1;
-    if (!again) {
-      ++its;
-      done = (lm_iteration_done(c) || its >= D.maxIts) ? 1 : 0;
-      if (!done) { lm_iteration(c, c.currentChi); rebuild = 1; }
-    }
-    *D.lm = c;
-    D.chi2[1] = c.currentChi;
-    D.lmi[PG4_ITS] = its; D.lmi[PG4_TRIALS] = trials; D.lmi[PG4_REBUILD] = rebuild; D.lmi[PG4_DONE] = done;
-    sKeep = keep ? 1 : 0;
-    __hip_atomic_store(D.lmHost + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(D.lmHost + 0, trials, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // decided trials: the host queues trial k + 2 when it sees k
-  }
+  const double gain = lm_sum_in_index_order<PG4_NT, PG4_SUM>(buf, 4 * D.n, [&](int i) { return D.x[i] * (lambda * D.x[i] + D.b[i]); });   // computeScale()
+  if (t == 0) sKeep = lm_decide_trial(c, chi, D.lmi[LMW_OK2] != 0, gain, false, D.maxIts, D.lm, D.chi2, D.lmi, D.lmHost) ? 1 : 0;
   __syncthreads();
   if (sKeep)
     for (int i = t; i < PG4_STATE * D.nKF; i += PG4_NT) D.S[i] = D.T[i];
@@ -637,7 +398,7 @@ extern "C" int morb_optimize_essential_graph_4dof(morb_optimizer* o, int nKF, do
   int *hostw = nullptr, *hostwDev = nullptr;
   MORB_REQUIRE(morb_optimizer_lm_words(o, &hostw, &hostwDev) == MORB_OK, MORB_ERR_HIP, "cannot map the LM state words");
   D.lmHost = hostwDev;
-  __atomic_store_n(hostw + 0, 0, __ATOMIC_RELAXED); __atomic_store_n(hostw + 1, 0, __ATOMIC_RELEASE);
+  reset_lm_words(hostw, 2, nullptr);
   MORB_HIP_CHECK(hipMemcpyAsync(arena, stage, A.uploadBytes(), hipMemcpyHostToDevice, st));   // the one upload
   // the workspace is reused from call to call (and shared with OptimizeEssentialGraph): what the first kernels expect to find zero is cleared
   MORB_HIP_CHECK(hipMemsetAsync(D.lmi, 0, sizeof(int) * 8, st));
@@ -661,11 +422,7 @@ extern "C" int morb_optimize_essential_graph_4dof(morb_optimizer* o, int nKF, do
     hipLaunchKernelGGL(k_pg4_decide, dim3(1), dim3(PG4_NT), 0, st, D, 0);
     if (hipGetLastError() != hipSuccess) { set_error("OptimizeEssentialGraph4DoF: a trial's launch failed"); return (int)MORB_ERR_HIP; }
     return (int)MORB_OK;
-  }, [&]() {
-    const hipError_t e = hipStreamQuery(st);
-    if (e != hipSuccess && e != hipErrorNotReady) set_error("OptimizeEssentialGraph4DoF: %s while waiting for the LM decision", hipGetErrorString(e));
-    return e == hipSuccess ? StreamLook::Idle : e == hipErrorNotReady ? StreamLook::Busy : StreamLook::Failed;
-  }, []() {});
+  }, [&]() { return stream_look(st, "OptimizeEssentialGraph4DoF"); }, []() {});
   if (q < 0) return MORB_ERR_HIP;
   if (nMP) hipLaunchKernelGGL(k_pg4_finish, dim3(div_up(nMP, PG4_NT)), dim3(PG4_NT), 0, st, D);
   MORB_HIP_CHECK(hipGetLastError());
@@ -677,6 +434,6 @@ extern "C" int morb_optimize_essential_graph_4dof(morb_optimizer* o, int nKF, do
   if (nMP) MORB_HIP_CHECK(hipMemcpyAsync(mpPos, D.mp, sizeof(float) * 3 * nMP, hipMemcpyDeviceToHost, st));
   MORB_HIP_CHECK(hipStreamSynchronize(st));   // (also drains a queue that ran out of slots before the words are reset again)
   for (int v = 0; v < nKF; ++v) memcpy(kfPose + (size_t)v * 12, out.data() + (size_t)v * PG4_STATE, sizeof(double) * 12);
-  stats4[0] = hi[PG4_ITS]; stats4[1] = hi[PG4_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
+  stats4[0] = hi[LMW_ITS]; stats4[1] = hi[LMW_TRIALS]; stats4[2] = n; stats4[3] = nBlocks;
   return MORB_OK;
 }

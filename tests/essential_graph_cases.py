@@ -11,8 +11,8 @@ import numpy as np
 import essential_graph_oracle as eo
 from morb_slam_amd.synth import make_essential_graph_problem
 
-PANEL = 32    # csrc/essential_graph.hip: EG_PANEL, blocks of a column's own row staged in LDS at a time
-LINES = 256   # ... EG_NT: block lines (7 per covering row) one pass of the workgroup takes
+PANEL = 32    # csrc/essential_graph.hip: EG_PANEL, blocks of a column's own row csrc/envelope_ldlt.h's envelope_factor stages in LDS at a time
+LINES = 256   # ... EG_NT: lanes of the workgroup; a pass takes the block lines (7 per covering row) of 36 rows, 252
 
 # name -> (classes, keyword arguments of the generator; "start" = "optimum": the oracle's result is the starting point)
 CASES = {

@@ -17,8 +17,8 @@ CAMS = ("mix", "mono", "kb8")          # pinhole monocular + stereo, pinhole mon
 _CAM_KW = {"mix": dict(mono_frac=0.3), "mono": dict(mono_frac=1.0), "kb8": dict(kb8=True)}
 N_IMU = 100
 # the tier constants of csrc/full_inertial_ba.hip
-ROWS_PER_PASS = 85                     # FIBA_ROWS: covering rows (the diagonal block's among them) one pass of the factorisation takes
-LDS_PANEL = 128                        # FIBA_STAGE: 3 x 3 blocks of a column's own row staged in LDS at a time
+ROWS_PER_PASS = 85                     # FIBA_ROWS: covering rows (the diagonal block's among them) one pass of csrc/envelope_ldlt.h's envelope_factor takes
+LDS_PANEL = 128                        # FIBA_STAGE: 3 x 3 blocks of a column's own row envelope_factor stages in LDS at a time
 CHUNK = 64                             # FIBA_CHUNK: Schur contributions to one envelope block added by one lane
 
 # seeds replaced on the CPU by the first of seed + 1000 k on which the oracle's two builds agree (tests/test_full_inertial_ba_cpu.py)

@@ -11,8 +11,8 @@ from morb_slam_amd.synth import make_global_ba_problem
 CAMS = ("mix", "mono", "kb8")          # pinhole monocular + stereo, pinhole monocular only, KannalaBrandt8 rig with right-camera edges
 _CAM_KW = {"mix": dict(mono_frac=0.3), "mono": dict(mono_frac=1.0), "kb8": dict(kb8=True)}
 # the tier constants of csrc/global_ba.hip
-ROWS_PER_PASS = 42                     # GBA_ROWS: covering rows (the diagonal block's among them) one pass of the factorisation takes
-LDS_PANEL = 64                         # GBA_STAGE: blocks of a column's own row staged in LDS at a time
+ROWS_PER_PASS = 42                     # GBA_ROWS: covering rows (the diagonal block's among them) one pass of csrc/envelope_ldlt.h's envelope_factor takes
+LDS_PANEL = 64                         # GBA_STAGE: blocks of a column's own row envelope_factor stages in LDS at a time
 CHUNK = 64                             # GBA_CHUNK: Schur contributions to one envelope block added by one lane
 
 # KannalaBrandt8::project takes theta and psi from atan2f, so chi2 is a staircase of ~1e-5 px steps in the estimate: a change of the rounding

@@ -11,7 +11,7 @@ import numpy as np
 import pose_graph_4dof_oracle as po
 from morb_slam_amd.synth import make_pose_graph_4dof_problem
 
-STAGE = 128   # csrc/pose_graph_4dof.hip: PG4_STAGE, blocks of a column's own row staged in LDS at a time
+STAGE = 128   # csrc/pose_graph_4dof.hip: PG4_STAGE, blocks of a column's own row csrc/envelope_ldlt.h's envelope_factor stages in LDS at a time
 LINES = 256   # ... PG4_NT: block lines (4 per covering row) one pass of the workgroup takes
 
 # name -> (classes, keyword arguments of the generator; "start" = "optimum": the oracle's result is the starting point)

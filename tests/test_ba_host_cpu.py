@@ -56,12 +56,14 @@ def test_the_adjusters_size_and_carve_through_the_shared_header():
         assert '#include "ba_host.h"' in src, name
         assert "& ~(size_t)255" not in src and "blkIndex[(size_t)bi *" not in src, name
         assert "ArenaCarver" in src and "csr_by_key(" in src and "chunks_of(" in src and "schur_block_lists(" in src, name
-        # the wait for the LM decisions is the header's: no unit backs off or polls the stream in a loop of its own (its one
-        # hipStreamQuery is the look() it hands to the queue)
+        # the wait for the LM decisions is the header's: no unit backs off or polls the stream in a loop of its own (the look() it
+        # hands to the queue is handles.h's stream_look, which holds the one hipStreamQuery)
         assert "lm_slot_queue(" in src, name
         for gone in ("__builtin_ia32_pause", "sched_yield", "nanosleep", "spins"):
             assert gone not in src, (name, gone)
-        assert src.count("hipStreamQuery") == 1 and re.search(r"\}, \[&\]\(\) \{\s*const hipError_t e = hipStreamQuery\(st\);", src), name
+        assert "hipStreamQuery" not in src and src.count("stream_look(") == 1 and re.search(r"\[&\]\(\) \{ return stream_look\(st, [\w.]+\); \}", src), name
+    handles = open(os.path.join(CSRC, "handles.h")).read()
+    assert handles.count("hipStreamQuery") == 1 and re.search(r"StreamLook stream_look\(hipStream_t st, const char\* who\) \{\s*const hipError_t e = hipStreamQuery\(st\);", handles)
     for name in ("inertial.hip", "inertial_ba.hip"):   # (LocalInertialBA lived in inertial.hip before it had a unit of its own)
         inertial = open(os.path.join(CSRC, name)).read()
         assert "& ~(size_t)255" not in inertial and "blkIndex[(size_t)bi *" not in inertial, name

@@ -75,7 +75,7 @@ def test_mode1_parity(opt, n):
     p["global16"] = p["global16"].copy()
     p["global16"][:10] = np.arange(10) * 0.37 + 0.11
     res, _ = run_gpu(opt, [p], [pre], 1)
-    o = cases.oracle(("m1", n), p, pre, 1)
+    o = cases.oracle(("m1", n, "ten values given"), p, pre, 1)   # (a key of its own: ("m1", n) is the unmodified scene of the CPU tests)
     assert_parity(res[0], o, 1, n)
     assert res[0]["global16"][:10].tobytes() == p["global16"][:10].tobytes()
     assert o["global16"][:10].tobytes() == p["global16"][:10].tobytes()
